@@ -8,10 +8,10 @@ resolve + tile gather to rank 0 + un-tile/quantise), with the scene already resi
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-Arithmetic: the F64 kernels by default — the reference is f64 end to end (src/math/vec3.rs:12); the F32
+Arithmetic: the F64 kernels by default — the reference is f64 end to end (src/math/vec3.rs:12); with --full the F32
 (throughput) kernels are timed beside them and reported under "f32_kernels".
 
-N = 1 (default): BASELINE.json's metric config, final_scene 800x800 spp=1000, in the top-level fields; the other two
+N = 1 (default): BASELINE.json's metric config, final_scene 800x800 spp=1000, in the top-level fields; with --full the other two
 single-GPU configs of BASELINE.json — cornell_box 800x800 spp=1000 (configs[1]) and spheres_1m 1024x1024 spp=256
 (configs[4]) — are timed in the same run with a few steps each and reported as the sub-records "cornell_box" and
 "spheres_1m" (own steps, ms_per_step, kernel_ms, roofline; --no-sub skips them).
@@ -21,11 +21,17 @@ is BASELINE configs[3]'s frame, final_scene 1600x1600, at spp = 1250 x N: per-GP
 3200 Msamples per GPU and step) and the N = 8 point IS configs[3] (1600x1600 spp=10000 tile-sharded across 8).
 value = samples of all ranks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line of at most 6 KB on stdout: the contract's top-level fields, a FLAT `roofline`, `cpu_baseline`, the
-headline workload through the other two builds as flat scalars (`strict_value` / `strict_ms_per_step`: RTTNW_F64_STRICT, the build whose
-pixels ARE the reference's; `f32_value` / `f32_ms_per_step`) and, under `sub`, one flat record per sub-workload and build.  Everything
-else (notes, instruction classes, per-sample counts, the other readings of the byte accounting) goes to `gpurun_out/bench_detail.json`
-(RTTNW_BENCH_DETAIL=<path> to move it) and, as one line, to stderr.
+Rank 0 prints ONE JSON line of at most 6 KB on stdout.  A plain run sets up, warms up, times the --steps steps and prints the
+contract's top-level fields (metric, value, unit, ms_per_step, higher_is_better, dtype, ...) and the run's `config`: nothing else runs.
+`metric` keeps its wording for whoever matches on it; its "achieved HBM GB/s vs peak" part (the roofline) is on the line only with --full.
+`--dump-outputs DIR` then writes what the last timed step computed (the frame rank 0 assembled) as DIR/<name>.npy; the inputs are
+seeded, so two builds given the same arguments can be compared output for output.
+
+--full adds everything else the benchmark measures, each with runs of its own: a FLAT `roofline`, `cpu_baseline`, the headline
+workload through the other two builds as flat scalars (`strict_value` / `strict_ms_per_step`: RTTNW_F64_STRICT, the build whose
+pixels ARE the reference's; `f32_value` / `f32_ms_per_step`), under `sub` one flat record per sub-workload and build, and for N > 1
+`per_gpu_reference`.  Everything else (notes, instruction classes, per-sample counts, the other readings of the byte accounting) goes,
+as one line, to stderr and to the file RTTNW_BENCH_DETAIL=<path> names.
 
 `roofline` says what bounds the dominant (trace) kernel:
   * scenes whose node records live in LDS (final_scene, cornell_box): "bound": "valu" — achieved = full-wave VALU
@@ -117,6 +123,7 @@ def committed_pmc(scene_name, precision_name):
 FLAT_ROOFLINE_KEYS = ("bound", "achieved", "peak", "unit", "frac", "hbm_alg_frac", "hbm_alg_gbps", "alg_bytes_per_sample", "traffic",
                       "traffic_over_algorithmic", "lane_utilisation", "issue_utilisation", "valu_insts_per_sample", "kernel", "kernel_ms", "pmc")
 LINE_LIMIT = 6000   # bytes of the ONE stdout line (the driver keeps an 8 KB tail of stdout; round 5's 25.9 KB line could not be parsed)
+DUMP_LIMIT = 64 << 20   # bytes of all --dump-outputs files together
 
 
 def flat_roofline(detail):
@@ -135,6 +142,27 @@ def flat_sub(rec, cpu=None):
     return out
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as `path/<name>.npy`, float64 kept, anything else as float32.  The arrays are pixels first
+    (H x W x C or pixels x C, the same pixels in each).  When together they would exceed DUMP_LIMIT, the same fixed, seeded sample of
+    pixels is written from each (pixels x C), with the sample's flat pixel indices as `pixel_index.npy`."""
+    import numpy as np
+    out = {k: a if a.dtype == np.float64 else a.astype(np.float32) for k, a in arrays.items()}
+    if sum(a.nbytes for a in out.values()) > DUMP_LIMIT:
+        rows = {k: a.reshape(-1, a.shape[-1]) for k, a in out.items()}
+        n_pix = {len(r) for r in rows.values()}
+        assert len(n_pix) == 1, "dump_outputs: the arrays cover different pixels"
+        n_pix = n_pix.pop()
+        per_pixel = 8 + sum(r.itemsize * r.shape[1] for r in rows.values())
+        keep = (DUMP_LIMIT - 4096) // per_pixel   # (room for the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(n_pix, min(n_pix, keep), replace=False))
+        out = {k: r[idx] for k, r in rows.items()}
+        out["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -146,11 +174,16 @@ def main():
                     help="f64 (default, the reported arithmetic), f32 (throughput mode), f64strict (RTTNW_F64_STRICT: nothing contracted)")
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (per GPU)")
     ap.add_argument("--size", type=int, default=0, help="override width = height")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target duration of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--counter-spp", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of their own: roofline (an untimed counting pass), "
+                         "the other builds, the sub-workloads, the CPU baseline, the single-GPU reference of an N > 1 run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target duration of the CPU baseline sample (0 = skip; --full)")
+    ap.add_argument("--counter-spp", type=int, default=8, help="spp of the untimed counting pass of the roofline (--full)")
     ap.add_argument("--counter-level", type=int, default=1, help="collect_counters of the untimed counting pass (2, 3: more RTTNW_DEBUG_SCHED statistics)")
-    ap.add_argument("--no-other", action="store_true", help="skip the timing of the other precision's kernels")
-    ap.add_argument("--no-sub", action="store_true", help="skip the cornell_box / spheres_1m sub-records of the default run")
+    ap.add_argument("--no-other", action="store_true", help="skip the timing of the other precision's kernels (--full)")
+    ap.add_argument("--no-sub", action="store_true", help="skip the cornell_box / spheres_1m sub-records of the default run (--full)")
     ap.add_argument("--sub-steps", type=int, default=3, help="timed steps of each sub-record (after one warm-up step)")
     ap.add_argument("--spp-chunk", type=int, default=0, help="samples per work item (0 = the library's tapered schedule)")
     ap.add_argument("--bvh", default="auto", choices=["auto", "sah", "lbvh", "dsah"],
@@ -160,6 +193,8 @@ def main():
                     help="trace ONE rank's share (rank R of a W-way partition) of the N = W workload on this GPU, no gather: "
                          "what each GPU of a W-GPU run does (not a bench line for the driver)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -247,9 +282,10 @@ def main():
             per = dict(rays=st.rays / n, nodes=st.nodes_visited / n, prims=st.prims_tested / n, texels=st.texel_fetches / n)
             return per, st.reserved
 
-        def timed(self, prec, steps, warmup):
+        def timed(self, prec, steps, warmup, dump_dir=None):
             """`steps` timed steps after `warmup` untimed ones: (ms_per_step over the barrier-bracketed region, mean device
-            time of the trace kernel(s) per step from the library's HIP events on the launch stream)."""
+            time of the trace kernel(s) per step from the library's HIP events on the launch stream).  `dump_dir`: write what the
+            last step computed there (rank 0's frame; with --share the rank's packed tiles)."""
             cam_t, p = S.params_for(self.setup, self.W, self.H, self.spp, precision=prec, tile_rank=rank, tile_world=world, seed=1,
                                     spp_chunk=args.spp_chunk)
             r = render.DeviceRenderer(self.sc, cam_t, p)
@@ -270,7 +306,8 @@ def main():
             if use_dist:
                 dist.barrier()
             elapsed = time.perf_counter() - t0
-            ms_per_step = elapsed * 1e3 / max(1, steps)
+            self.steps_timed = len(kms)   # the steps the loop above ran: what the line reports as `steps`
+            ms_per_step = elapsed * 1e3 / max(1, self.steps_timed)
             kernel_ms = float(np.mean(kms)) if kms else 0.0
             self.rank_kernel_ms = None
             if use_dist:
@@ -286,6 +323,12 @@ def main():
                 torch.cuda.synchronize()
                 np.savez(args.dump_image, linear=r.linear.cpu().numpy(), rgba8=r.rgba8.cpu().numpy())
                 args.dump_image = None   # (the reported precision's frame only)
+            if dump_dir and share is not None:
+                torch.cuda.synchronize()
+                dump_outputs(dump_dir, {"packed": r.packed.cpu().numpy()})
+            elif dump_dir and rank == 0:
+                torch.cuda.synchronize()
+                dump_outputs(dump_dir, {"linear": r.linear.cpu().numpy(), "rgba8": r.rgba8.cpu().numpy()})
             del r
             return ms_per_step, kernel_ms
 
@@ -402,13 +445,13 @@ def main():
     wl = Workload(workload, args.spp, args.size)
     precision = {"f32": abi.F32, "f64": abi.F64, "f64strict": abi.F64_STRICT}[args.precision]
 
-    # ---- N > 1: what ONE GPU does with the same frame at the per-GPU sample count — rank 0 alone traces the whole 1600x1600 frame at
+    # ---- N > 1, --full: what ONE GPU does with the same frame at the per-GPU sample count — rank 0 alone traces the whole 1600x1600 frame at
     # spp = 1250 (one step after one warm-up; the other ranks wait at the barrier), so that the line carries its own single-GPU reference on
     # the same frame (the N = 1 bench line is the 800x800 headline frame: ~1.7 % apart per GPU) and the efficiency read off it is not inflated
     per_gpu_reference = None
     if use_dist and world > 1:
         assert dist.get_world_size() == world == args.gpus, "bench: %d ranks joined, WORLD_SIZE %d, --gpus %d" % (dist.get_world_size(), world, args.gpus)
-        if rank == 0:
+        if rank == 0 and args.full:
             cam1, p1 = S.params_for(wl.setup, wl.W, wl.H, wl.spp1, precision=precision, tile_rank=0, tile_world=1, seed=1, spp_chunk=args.spp_chunk)
             r1 = render.DeviceRenderer(wl.sc, cam1, p1)
             r1.step()
@@ -426,16 +469,16 @@ def main():
         dist.barrier()
 
     # ---- timed region (the reported precision)
-    ms_per_step, kernel_ms = wl.timed(precision, args.steps, args.warmup)
-    rank_kernel_ms = wl.rank_kernel_ms
+    ms_per_step, kernel_ms = wl.timed(precision, args.steps, args.warmup, args.dump_outputs)
+    rank_kernel_ms, steps_timed = wl.rank_kernel_ms, wl.steps_timed
     value = wl.samples_total / (ms_per_step * 1e-3) / 1e6
-    roof = wl.roofline(precision, kernel_ms)
+    roof = wl.roofline(precision, kernel_ms) if args.full else None
 
     # ---- the same workload through the other precision's kernels, its own multi-step timing; and through the IEEE-strict build of the f64
     # kernels (RTTNW_F64_STRICT: nothing contracted, every object tested in the reference's frame — the build whose pixels ARE the CPU
     # reference's, tests/test_gpu_parity.py::test_f64_strict_takes_the_oracles_decisions)
     other = strict = None
-    if not args.no_other:
+    if args.full and not args.no_other:
         oprec = abi.F64 if precision == abi.F32 else abi.F32
         other = wl.record(oprec, max(1, min(args.steps, 5)), 1)
         if precision != abi.F64_STRICT and world == 1 and share is None:
@@ -473,7 +516,7 @@ def main():
     # IEEE-strict f64 build first: on that scene (rounding grows ~100x per bounce) it is the build whose pixels equal the CPU
     # reference's (tests/test_gpu_parity.py::test_config5_spheres_1m_at_its_size_vs_oracle); the contracted build rides along.
     subs, subs_detail = {}, {}
-    if world == 1 and share is None and args.workload is None and not args.no_sub and not args.spp and not args.size:
+    if args.full and world == 1 and share is None and args.workload is None and not args.no_sub and not args.spp and not args.size:
         for name in ("cornell_box", "spheres_1m"):
             w2 = Workload(name)
             recs = {pn: w2.record(pr, args.sub_steps, 1) for pn, pr in (("f64strict", abi.F64_STRICT), ("f64", abi.F64), ("f32", abi.F32))}
@@ -485,7 +528,7 @@ def main():
 
     # ---- CPU baseline (rank 0, N = 1 only): the oracle on the host cores, bounded sample
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_sample(wl, args.cpu_seconds, workload)
 
     if rank == 0 or share is not None:
@@ -496,13 +539,13 @@ def main():
         cfg.update(wl.config())
         out = {
             "metric": "Msamples/sec on final_scene 800x800 spp=1000; achieved HBM GB/s vs peak",
-            "value": round(value, 3), "unit": "Msamples/s", "n_gpus": 1 if share is not None else world, "steps": args.steps, "warmup": args.warmup,
+            "value": round(value, 3), "unit": "Msamples/s", "n_gpus": 1 if share is not None else world, "steps": steps_timed, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32" if precision == abi.F32 else "f64", "precision": args.precision, "data": "synthetic",
             "config": cfg,
-            "roofline": flat_roofline(roof),
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            out.update(roofline=flat_roofline(roof), cpu_baseline=cpu)
         detail = dict(out, roofline=roof)
         # the headline workload through the other builds, flat: the IEEE-strict build first — its pixels ARE the CPU reference's (tier bar 1)
         if strict is not None:
@@ -534,14 +577,16 @@ def main():
             log("bench: the stdout line is %d bytes (limit %d): dropping '%s' from it (see the detail file)" % (len(line), LINE_LIMIT, optional))
             out.pop(optional, None)
             line = json.dumps(out, separators=(",", ":"))
-        dpath = os.environ.get("RTTNW_BENCH_DETAIL") or os.path.join(ROOT, "gpurun_out", "bench_detail.json")
-        try:
-            os.makedirs(os.path.dirname(dpath), exist_ok=True)
-            with open(dpath, "w") as f:
-                json.dump(detail, f, indent=1)
-        except OSError as e:
-            log("bench: detail file not written (%s)" % e)
-        log("bench detail: " + json.dumps(detail))
+        if args.full:
+            dpath = os.environ.get("RTTNW_BENCH_DETAIL")
+            if dpath:
+                try:
+                    os.makedirs(os.path.dirname(os.path.abspath(dpath)), exist_ok=True)
+                    with open(dpath, "w") as f:
+                        json.dump(detail, f, indent=1)
+                except OSError as e:
+                    log("bench: detail file not written (%s)" % e)
+            log("bench detail: " + json.dumps(detail))
         print(line, flush=True)
     if use_dist:
         dist.destroy_process_group()

@@ -19,5 +19,5 @@ for spec in "final_scene f64" "final_scene f64strict" "final_scene f32" "cornell
 done
 bash profiles/collect_phases.sh $OUT
 cp $OUT/pmc_*.txt profiles/r06/
-RTTNW_BENCH_DETAIL=$OUT/bench_detail_r06.json python3 bench.py --steps 20 --warmup 5 > $OUT/bench_r06.json 2> $OUT/bench_r06.err
+RTTNW_BENCH_DETAIL=$OUT/bench_detail_r06.json python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_r06.json 2> $OUT/bench_r06.err
 ls $OUT

@@ -488,8 +488,6 @@ def test_per_bounce_records_equal_oracle(gpu, oracle, scenes_lib, earth, name, n
     build: 1e-9 at every depth where nothing amplifies a last place (cornell_box, smoke_cornell_box); on final_scene and random_scene — small
     spheres: a fused multiply-add or the world-space form of a sphere test is another ray a few bounces on — 1e-9 for the first three
     bounces, then x 8 per bounce (capped at 1e-4); decisions exact at every depth either way."""
-    if precision == abi.F64_STRICT and bvh == abi.BVH_DEVICE_LBVH:
-        pytest.skip("one device builder is enough for the strict probes")
     sg, setup = util.build(gpu, scenes_lib, name, earth, bvh=bvh)
     so, _ = util.build(oracle, scenes_lib, name, earth)
     cam, p = util.params_for(setup, 96, 96, 8, seed=21, precision=precision)
@@ -877,7 +875,7 @@ def test_bench_line_through_torch_distributed_with_one_rank(gpu):
     env = dict(os.environ, RTTNW_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0",
-           "--spp", "16", "--no-other"]
+           "--spp", "16", "--no-other", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -888,7 +886,7 @@ def test_bench_line_through_torch_distributed_with_one_rank(gpu):
 
 
 def test_bench_default_line_fits_the_drivers_window(gpu, tmp_path):
-    """The default bench run — headline + strict + f32 + both sub-workloads + CPU legs, as the driver starts it (fewer steps, shorter CPU
+    """The --full bench run — headline + strict + f32 + both sub-workloads + CPU legs (fewer steps, shorter CPU
     samples) — prints ONE line that a reader holding only the last 8 KB of stdout can parse (round 5's 25.9 KB line could not be: BENCH_r05.json
     `parsed: null`): under 6000 bytes, flat `roofline` with `frac`, `cpu_baseline.value`, the strict build's figures at the top level, one flat
     record per sub-workload and build; the long form lands in the detail file."""
@@ -899,7 +897,8 @@ def test_bench_default_line_fits_the_drivers_window(gpu, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     detail = str(tmp_path / "bench_detail.json")
     env = dict(os.environ, RTTNW_BENCH_DETAIL=detail)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--sub-steps", "1", "--cpu-seconds", "1.5"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--sub-steps", "1", "--cpu-seconds", "1.5",
+           "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     line = r.stdout[-8000:].splitlines()[-1]
@@ -923,25 +922,63 @@ def test_bench_default_line_fits_the_drivers_window(gpu, tmp_path):
     assert "note" in full["roofline"] and full["sub"]["spheres_1m"]["f64strict"]["roofline"]["per_sample"]["nodes"] > 0
 
 
-@pytest.mark.parametrize("world", [2, 8])
-def test_bench_n_ranks_rehearsed_on_one_gpu(gpu, scenes_lib, earth, tmp_path, world):
-    """`bench.py --gpus N` (N = 2, and N = 8: configs[3]'s partition) exactly as the driver launches it — `python -m torch.distributed.run --nproc-per-node N ...` — on a
-    box with ONE GPU: RTTNW_BENCH_ONE_DEVICE=1 puts both ranks on device 0 and takes gloo for the barriers, the max-over-ranks and
-    the gather (RCCL refuses two ranks on one device); the tile partition, each rank's launches, the packed buffers, the un-tile
-    and the JSON line are the N-GPU code path.  Checked: ONE JSON line with n_gpus 2 and the weak-scaling workload (configs[3]'s
-    frame, final_scene 1600x1600, spp = per-GPU spp x 2), value consistent with ms_per_step, and the frame rank 0 assembled is
-    BIT-identical to the single-rank render of the same frame (fresh children, launched before anything touches the GPU in them).
-    No 8-GPU node has been available: this is a rehearsal of the mechanics, not a scaling measurement."""
+def test_bench_plain_line_and_dumped_outputs(gpu, scenes_lib, earth, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the contract's fields without the legs --full adds; --dump-outputs
+    writes the frame of the last timed step (linear as float64, rgba8 as float32), the single-rank render of the same seeded frame."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "4", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert len(r.stdout.strip().splitlines()) == 1, r.stdout[-2000:]
+    d = json.loads(r.stdout)
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["metric"].startswith("Msamples/sec on final_scene 800x800 spp=1000") and d["unit"] == "Msamples/s"
+    assert d["value"] == pytest.approx(800 * 800 * 4 / (d["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    assert not {"roofline", "cpu_baseline", "sub", "strict_value", "f32_value"} & set(d), sorted(d)
+    sc, setup = util.build(gpu, scenes_lib, "final_scene", earth)
+    cam, p = util.params_for(setup, 800, 800, 4, precision=abi.F64, seed=1)
+    lin, rgba, _ = gpu_render(gpu, sc, cam, p)
+    assert sorted(os.listdir(out)) == ["linear.npy", "rgba8.npy"]
+    got_lin, got_rgba = np.load(out / "linear.npy"), np.load(out / "rgba8.npy")
+    assert got_lin.dtype == np.float64 and np.array_equal(got_lin, lin)
+    assert got_rgba.dtype == np.float32 and np.array_equal(got_rgba, rgba.astype(np.float32))
+
+
+ONE_DEVICE_MAX_RANKS = 3   # a one-device rehearsal has N ranks + the launcher + pytest with the device open: kept to N <= 3
+
+
+@pytest.mark.parametrize("world", [2, 3, 8])
+def test_bench_n_ranks_rehearsed_on_one_gpu(gpu, scenes_lib, earth, tmp_path, world):
+    """`bench.py --gpus N --full` exactly as the driver launches it — `python -m torch.distributed.run --nproc-per-node N ...`.
+    N = 2 and N = 3 (the ranks get unequal shares of the 200 x 200 tiles) are rehearsed on ONE GPU: RTTNW_BENCH_ONE_DEVICE=1 puts
+    every rank on device 0 and takes gloo for the barriers, the max-over-ranks and the gather (RCCL refuses two ranks on one device).
+    N = 8 is configs[3]'s partition as the driver measures it — one rank per GPU, RCCL — and needs 8 GPUs: with fewer it skips (on
+    one device it would hold N + 2 processes on the GPU at once).  Either way the tile partition, each rank's launches, the packed
+    buffers, the gather, the un-tile and the JSON line are the N-GPU code path.  Checked: ONE JSON line with n_gpus N and the
+    weak-scaling workload (configs[3]'s frame, final_scene 1600x1600, spp = per-GPU spp x N), value consistent with ms_per_step, and
+    the frame rank 0 assembled is BIT-identical to the single-rank render of the same frame (fresh children, launched before anything
+    touches the GPU in them).  This checks the mechanics, not a scaling measurement."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    one_device = world <= ONE_DEVICE_MAX_RANKS
+    if not one_device and torch.cuda.device_count() < world:
+        pytest.skip("needs %d GPUs, found %d" % (world, torch.cuda.device_count()))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     dump = str(tmp_path / "frame.npz")
-    env = dict(os.environ, RTTNW_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1")
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
+    if one_device:
+        env["RTTNW_BENCH_ONE_DEVICE"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(29531 + world), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "0", "--cpu-seconds", "0",
-           "--spp", "3", "--no-other", "--dump-image", dump]
+           "--spp", "3", "--no-other", "--dump-image", dump, "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -951,7 +988,7 @@ def test_bench_n_ranks_rehearsed_on_one_gpu(gpu, scenes_lib, earth, tmp_path, wo
     assert d["config"]["workload"].startswith("final_scene 1600x1600 spp=%d " % (3 * world)), d["config"]["workload"]
     assert abs(d["value"] - 1600 * 1600 * 3 * world / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * d["value"]
     # the line names the ranks that really joined, every rank's kernel time, and its own single-GPU reference on the SAME frame (round 5)
-    assert d["distributed"]["world_size"] == world == d["distributed"]["ranks_expected"] and d["distributed"]["backend"] == "gloo"
+    assert d["distributed"]["world_size"] == world == d["distributed"]["ranks_expected"] and d["distributed"]["backend"] == ("gloo" if one_device else "nccl")
     rk = d["distributed"]["rank_kernel_ms"]
     assert 0 < rk["min"] <= rk["mean"] <= rk["max"] == pytest.approx(d["roofline"]["kernel_ms"], rel=1e-6)
     ref = d["per_gpu_reference"]
