@@ -27,6 +27,7 @@
 // the root is node 0 before and after the re-numbering.
 #include "bvh_build.hpp"
 #include "bvh_quant.hpp"
+#include "device_mem.hpp"
 
 #include <chrono>
 #include <cstdio>
@@ -44,7 +45,7 @@ namespace {
 #define LBVH_TRY(expr)                                                                           \
     do {                                                                                         \
         hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) { err = std::string("lbvh_build: ") + hipGetErrorString(e_); rc = -4; goto done; } \
+        if (e_ != hipSuccess) { err = std::string("lbvh_build: ") + hipGetErrorString(e_); return -4; } \
     } while (0)
 
 __device__ __forceinline__ uint64_t spread21(uint32_t v) { // bit i of v -> bit 3i
@@ -603,26 +604,10 @@ __global__ void rebase4_kernel(Bvh4Node* __restrict__ nodes, uint32_t n, int32_t
 
 } // namespace
 
-namespace {
-struct DeviceFree { // frees on the device the buffer lives on
-    int device;
-    void operator()(void* p) const {
-        if (!p) return;
-        int prev = -1;
-        (void)hipGetDevice(&prev);
-        if (prev != device) (void)hipSetDevice(device);
-        (void)hipFree(p);
-        if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    }
-};
-} // namespace
-
 int lbvh_build_device_tree(const BuildPrim* prims, size_t n, const float* centroid_bounds, bool sah, DeviceTree& tree, double* kernel_ms, std::string& err) {
     if (n < 2 || n >= (size_t(1) << 26)) { err = "lbvh_build: needs 2 .. 2^26-1 leaves"; return -1; }
-    int rc = 0;
     const auto wall0 = std::chrono::steady_clock::now();
     auto wall_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count(); };
-    double t_alloc = 0, t_up = 0, t_kernels = 0;
     // centroid bounds on the host (the leaves come from the host anyway)
     float cmin[3] = {INFINITY, INFINITY, INFINITY}, cmax[3] = {-INFINITY, -INFINITY, -INFINITY};
     if (centroid_bounds) {
@@ -641,261 +626,238 @@ int lbvh_build_device_tree(const BuildPrim* prims, size_t n, const float* centro
         scale[a] = (ext > 0.f && std::isfinite(ext)) ? 2097151.f / ext : 0.f;
     }
 
-    int device = -1;
-    BuildPrim* d_prims = nullptr;
-    uint64_t *d_keys = nullptr, *d_keys2 = nullptr;
-    uint32_t *d_order = nullptr, *d_order2 = nullptr;
-    int2* d_children = nullptr;
-    int *d_node_parent = nullptr, *d_done = nullptr, *d_levels = nullptr;
-    NodeBox* d_box = nullptr;
-    BvhNode *d_out = nullptr, *d_out2 = nullptr;
-    int* d_pos = nullptr;
-    void *d_temp = nullptr, *d_temp2 = nullptr, *d_temp3 = nullptr;
-    size_t temp_bytes = 0, temp2_bytes = 0, temp3_bytes = 0;
-    // binned SAH
-    BuildPrim *d_pa = nullptr, *d_pb = nullptr;
-    int *d_sa = nullptr, *d_sb = nullptr, *d_slot = nullptr, *d_list[4] = {nullptr, nullptr, nullptr, nullptr}; // lists: large a/b, small a/b
-    SahSeg* d_segs = nullptr;
-    SahSplit* d_split = nullptr;
-    SahBin* d_bins = nullptr;
-    SahLists* d_next = nullptr;
-    uint32_t *d_flag = nullptr, *d_scan = nullptr;
-    int sah_levels = 0;
-    const size_t max_large = n / size_t(SAH_SMALL + 1) + 2;
-    // collapse
-    int* d_heads = nullptr;
-    uint32_t *d_is_head = nullptr, *d_rank = nullptr, *d_need = nullptr, *d_fcount = nullptr, *d_foff = nullptr;
-    Bvh4Node* d_out4 = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     const uint32_t nb = uint32_t((n + 255) / 256);
     const int n_inner = int(n - 1);
-    int h_levels = 0;
-    std::vector<int> level_off; // frontier k = heads[level_off[k] .. level_off[k + 1])
-    uint32_t n_heads = 0, h_need = 0;
-    {
-        LBVH_TRY(hipGetDevice(&device));
-        // both hierarchies: the leaves, the pre-ordered binary records, the collapse's arrays
-        LBVH_TRY(hipMalloc((void**)&d_prims, n * sizeof(BuildPrim)));
-        LBVH_TRY(hipMalloc((void**)&d_levels, (n - 1) * 4));
-        LBVH_TRY(hipMalloc((void**)&d_out2, (n - 1) * sizeof(BvhNode)));
-        LBVH_TRY(hipMalloc((void**)&d_heads, (n - 1) * 4));
-        LBVH_TRY(hipMalloc((void**)&d_is_head, (n - 1) * 4));
-        LBVH_TRY(hipMalloc((void**)&d_rank, (n - 1) * 4));
-        LBVH_TRY(hipMalloc((void**)&d_fcount, (n - 1) * 4));
-        LBVH_TRY(hipMalloc((void**)&d_foff, (n - 1) * 4));
-        LBVH_TRY(rocprim::exclusive_scan(nullptr, temp2_bytes, d_is_head, d_rank, 0u, size_t(n_inner), rocprim::plus<uint32_t>(), hipStream_t(0)));
-        LBVH_TRY(hipMalloc(&d_temp2, std::max<size_t>(temp2_bytes, 16)));
-        if (!sah) {
-            LBVH_TRY(hipMalloc((void**)&d_keys, n * 8));
-            LBVH_TRY(hipMalloc((void**)&d_keys2, n * 8));
-            LBVH_TRY(hipMalloc((void**)&d_order, n * 4));
-            LBVH_TRY(hipMalloc((void**)&d_order2, n * 4));
-            LBVH_TRY(hipMalloc((void**)&d_children, (n - 1) * sizeof(int2)));
-            LBVH_TRY(hipMalloc((void**)&d_node_parent, (n - 1) * 4));
-            LBVH_TRY(hipMalloc((void**)&d_done, (n - 1) * 4));
-            LBVH_TRY(hipMalloc((void**)&d_box, (n - 1) * sizeof(NodeBox)));
-            LBVH_TRY(hipMalloc((void**)&d_out, (n - 1) * sizeof(BvhNode)));
-            LBVH_TRY(hipMalloc((void**)&d_pos, (n - 1) * 4));
-            LBVH_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, d_keys, d_keys2, d_order, d_order2, n, 0, 63, hipStream_t(0)));
-            LBVH_TRY(hipMalloc(&d_temp, std::max<size_t>(temp_bytes, 16)));
-        } else {
-            LBVH_TRY(hipMalloc((void**)&d_pa, n * sizeof(BuildPrim)));
-            LBVH_TRY(hipMalloc((void**)&d_pb, n * sizeof(BuildPrim)));
-            LBVH_TRY(hipMalloc((void**)&d_sa, n * 4));
-            LBVH_TRY(hipMalloc((void**)&d_sb, n * 4));
-            LBVH_TRY(hipMalloc((void**)&d_slot, n * 4));
-            LBVH_TRY(hipMalloc((void**)&d_list[0], max_large * 4));
-            LBVH_TRY(hipMalloc((void**)&d_list[1], max_large * 4));
-            LBVH_TRY(hipMalloc((void**)&d_list[2], (n / 2 + 2) * 4));
-            LBVH_TRY(hipMalloc((void**)&d_list[3], (n / 2 + 2) * 4));
-            LBVH_TRY(hipMalloc((void**)&d_segs, n * sizeof(SahSeg)));
-            LBVH_TRY(hipMalloc((void**)&d_split, n * sizeof(SahSplit)));
-            LBVH_TRY(hipMalloc((void**)&d_bins, max_large * 3 * SAH_BINS * sizeof(SahBin)));
-            LBVH_TRY(hipMalloc((void**)&d_next, sizeof(SahLists)));
-            LBVH_TRY(hipMalloc((void**)&d_flag, n * 4));
-            LBVH_TRY(hipMalloc((void**)&d_scan, n * 4));
-            LBVH_TRY(rocprim::exclusive_scan(nullptr, temp3_bytes, d_flag, d_scan, 0u, n, rocprim::plus<uint32_t>(), hipStream_t(0)));
-            LBVH_TRY(hipMalloc(&d_temp3, std::max<size_t>(temp3_bytes, 16)));
-        }
-        LBVH_TRY(hipEventCreate(&e0));
-        LBVH_TRY(hipEventCreate(&e1));
-        t_alloc = wall_ms();
-        LBVH_TRY(hipMemcpy(d_prims, prims, n * sizeof(BuildPrim), hipMemcpyHostToDevice));
-        t_up = wall_ms();
+    int device = -1;
+    LBVH_TRY(hipGetDevice(&device));
+    // both hierarchies: the leaves, the pre-ordered binary records, the collapse's arrays
+    DevBuf<BuildPrim> d_prims;
+    DevBuf<int> d_levels, d_heads;
+    DevBuf<BvhNode> d_out2;
+    DevBuf<uint32_t> d_is_head, d_rank, d_fcount, d_foff;
+    LBVH_TRY(d_prims.alloc(n));
+    LBVH_TRY(d_levels.alloc(n - 1));
+    LBVH_TRY(d_out2.alloc(n - 1));
+    LBVH_TRY(d_heads.alloc(n - 1));
+    LBVH_TRY(d_is_head.alloc(n - 1));
+    LBVH_TRY(d_rank.alloc(n - 1));
+    LBVH_TRY(d_fcount.alloc(n - 1));
+    LBVH_TRY(d_foff.alloc(n - 1));
+    size_t temp2_bytes = 0;
+    LBVH_TRY(rocprim::exclusive_scan(nullptr, temp2_bytes, d_is_head.p, d_rank.p, 0u, size_t(n_inner), rocprim::plus<uint32_t>(), hipStream_t(0)));
+    DevBuf<uint8_t> d_temp2;
+    LBVH_TRY(d_temp2.alloc(std::max<size_t>(temp2_bytes, 16)));
+    // linear BVH
+    DevBuf<uint64_t> d_keys, d_keys2;
+    DevBuf<uint32_t> d_order, d_order2;
+    DevBuf<int2> d_children;
+    DevBuf<int> d_node_parent, d_done, d_pos;
+    DevBuf<NodeBox> d_box;
+    DevBuf<BvhNode> d_out;
+    DevBuf<uint8_t> d_temp, d_temp3;
+    size_t temp_bytes = 0, temp3_bytes = 0;
+    // binned SAH
+    DevBuf<BuildPrim> d_pa, d_pb;
+    DevBuf<int> d_sa, d_sb, d_slot, d_list[4]; // lists: large a/b, small a/b
+    DevBuf<SahSeg> d_segs;
+    DevBuf<SahSplit> d_split;
+    DevBuf<SahBin> d_bins;
+    DevBuf<SahLists> d_next;
+    DevBuf<uint32_t> d_flag, d_scan;
+    const size_t max_large = n / size_t(SAH_SMALL + 1) + 2;
+    if (!sah) {
+        LBVH_TRY(d_keys.alloc(n));
+        LBVH_TRY(d_keys2.alloc(n));
+        LBVH_TRY(d_order.alloc(n));
+        LBVH_TRY(d_order2.alloc(n));
+        LBVH_TRY(d_children.alloc(n - 1));
+        LBVH_TRY(d_node_parent.alloc(n - 1));
+        LBVH_TRY(d_done.alloc(n - 1));
+        LBVH_TRY(d_box.alloc(n - 1));
+        LBVH_TRY(d_out.alloc(n - 1));
+        LBVH_TRY(d_pos.alloc(n - 1));
+        LBVH_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, d_keys.p, d_keys2.p, d_order.p, d_order2.p, n, 0, 63, hipStream_t(0)));
+        LBVH_TRY(d_temp.alloc(std::max<size_t>(temp_bytes, 16)));
+    } else {
+        LBVH_TRY(d_pa.alloc(n));
+        LBVH_TRY(d_pb.alloc(n));
+        LBVH_TRY(d_sa.alloc(n));
+        LBVH_TRY(d_sb.alloc(n));
+        LBVH_TRY(d_slot.alloc(n));
+        LBVH_TRY(d_list[0].alloc(max_large));
+        LBVH_TRY(d_list[1].alloc(max_large));
+        LBVH_TRY(d_list[2].alloc(n / 2 + 2));
+        LBVH_TRY(d_list[3].alloc(n / 2 + 2));
+        LBVH_TRY(d_segs.alloc(n));
+        LBVH_TRY(d_split.alloc(n));
+        LBVH_TRY(d_bins.alloc(max_large * 3 * SAH_BINS));
+        LBVH_TRY(d_next.alloc(1));
+        LBVH_TRY(d_flag.alloc(n));
+        LBVH_TRY(d_scan.alloc(n));
+        LBVH_TRY(rocprim::exclusive_scan(nullptr, temp3_bytes, d_flag.p, d_scan.p, 0u, n, rocprim::plus<uint32_t>(), hipStream_t(0)));
+        LBVH_TRY(d_temp3.alloc(std::max<size_t>(temp3_bytes, 16)));
+    }
+    Event e0, e1;
+    LBVH_TRY(create_event(e0));
+    LBVH_TRY(create_event(e1));
+    const double t_alloc = wall_ms();
+    LBVH_TRY(hipMemcpy(d_prims.p, prims, n * sizeof(BuildPrim), hipMemcpyHostToDevice));
+    const double t_up = wall_ms();
 
-        LBVH_TRY(hipEventRecord(e0, 0));
-        if (sah) {
-            // level 0: the root segment over all leaves, with the centroid bounds the host has already
-            SahSeg root;
-            root.begin = 0; root.count = int(n);
-            for (int a = 0; a < 3; ++a) { root.clo[a] = cmin[a]; root.chi[a] = cmax[a]; }
-            const int zero = 0;
-            LBVH_TRY(hipMemcpyAsync(d_segs, &root, sizeof(root), hipMemcpyHostToDevice, 0));
-            LBVH_TRY(hipMemcpyAsync(d_slot, &zero, 4, hipMemcpyHostToDevice, 0));
-            int n_large = n > size_t(SAH_SMALL) ? 1 : 0, n_small = 1 - n_large;
-            LBVH_TRY(hipMemcpyAsync(d_list[n_large ? 0 : 2], &zero, 4, hipMemcpyHostToDevice, 0));
-            LBVH_TRY(hipMemsetAsync(d_sa, n_large ? 0 : 0xFF, n * 4, 0)); // every position in segment 0 (large) or none (small)
-            LBVH_TRY(hipMemcpyAsync(d_pa, d_prims, n * sizeof(BuildPrim), hipMemcpyDeviceToDevice, 0));
-            LBVH_TRY(hipMemsetAsync(d_levels, 0, 4, 0)); // the height reached inside the small subtrees
-            int cur = 0; // which of the ping-pong arrays / lists is the level's input
-            while (n_large > 0 || n_small > 0) {
-                if (++sah_levels > 4096) { err = "lbvh_build: the SAH build did not converge"; rc = -4; goto done; }
-                BuildPrim *pin = cur ? d_pb : d_pa, *pout = cur ? d_pa : d_pb;
-                int *sin = cur ? d_sb : d_sa, *sout = cur ? d_sa : d_sb;
-                int *large_in = d_list[cur], *large_out = d_list[cur ^ 1], *small_in = d_list[2 + cur], *small_out = d_list[2 + (cur ^ 1)];
-                LBVH_TRY(hipMemsetAsync(d_next, 0, sizeof(SahLists), 0));
-                if (n_large > 0) {
-                    const int n_bins = n_large * 3 * SAH_BINS;
-                    hipLaunchKernelGGL(sah_bins_init_kernel, dim3((n_bins + 255) / 256), dim3(256), 0, 0, d_bins, n_bins);
-                    hipLaunchKernelGGL(sah_bin_kernel, dim3(nb), dim3(256), 0, 0, pin, sin, int(n), d_segs, d_slot, d_bins);
-                    hipLaunchKernelGGL(sah_eval_kernel, dim3((n_large + 63) / 64), dim3(64), 0, 0, large_in, n_large, d_bins, d_segs, d_split, d_out2, d_slot,
-                                       large_out, small_out, d_next);
-                    hipLaunchKernelGGL(sah_flag_kernel, dim3(nb), dim3(256), 0, 0, pin, sin, int(n), d_segs, d_split, d_flag);
-                    LBVH_TRY(rocprim::exclusive_scan(d_temp3, temp3_bytes, d_flag, d_scan, 0u, n, rocprim::plus<uint32_t>(), hipStream_t(0)));
-                    hipLaunchKernelGGL(sah_partition_kernel, dim3(nb), dim3(256), 0, 0, pin, sin, int(n), d_segs, d_split, d_flag, d_scan, pout, sout, d_out2);
-                }
-                if (n_small > 0) // (the segments of 64 leaves or fewer that the large splits of the last level made: each a whole subtree)
-                    hipLaunchKernelGGL(sah_small_kernel, dim3((n_small + SAH_WAVES_PER_BLOCK - 1) / SAH_WAVES_PER_BLOCK), dim3(64 * SAH_WAVES_PER_BLOCK), 0, 0,
-                                       small_in, n_small, pin, d_segs, d_out2, sah_levels, d_levels);
-                SahLists h_next;
-                LBVH_TRY(hipMemcpy(&h_next, d_next, sizeof(h_next), hipMemcpyDeviceToHost));
-                if (size_t(h_next.n_large) > max_large || size_t(h_next.n_small) > n / 2 + 2) { err = "lbvh_build: SAH segment lists overflowed"; rc = -4; goto done; }
-                n_large = h_next.n_large; n_small = h_next.n_small;
-                cur ^= 1;
+    LBVH_TRY(hipEventRecord(e0.get(), 0));
+    int sah_levels = 0;
+    if (sah) {
+        // level 0: the root segment over all leaves, with the centroid bounds the host has already
+        SahSeg root;
+        root.begin = 0; root.count = int(n);
+        for (int a = 0; a < 3; ++a) { root.clo[a] = cmin[a]; root.chi[a] = cmax[a]; }
+        const int zero = 0;
+        LBVH_TRY(hipMemcpyAsync(d_segs.p, &root, sizeof(root), hipMemcpyHostToDevice, 0));
+        LBVH_TRY(hipMemcpyAsync(d_slot.p, &zero, 4, hipMemcpyHostToDevice, 0));
+        int n_large = n > size_t(SAH_SMALL) ? 1 : 0, n_small = 1 - n_large;
+        LBVH_TRY(hipMemcpyAsync(d_list[n_large ? 0 : 2].p, &zero, 4, hipMemcpyHostToDevice, 0));
+        LBVH_TRY(hipMemsetAsync(d_sa.p, n_large ? 0 : 0xFF, n * 4, 0)); // every position in segment 0 (large) or none (small)
+        LBVH_TRY(hipMemcpyAsync(d_pa.p, d_prims.p, n * sizeof(BuildPrim), hipMemcpyDeviceToDevice, 0));
+        LBVH_TRY(hipMemsetAsync(d_levels.p, 0, 4, 0)); // the height reached inside the small subtrees
+        int cur = 0; // which of the ping-pong arrays / lists is the level's input
+        while (n_large > 0 || n_small > 0) {
+            if (++sah_levels > 4096) { err = "lbvh_build: the SAH build did not converge"; return -4; }
+            BuildPrim *pin = cur ? d_pb.p : d_pa.p, *pout = cur ? d_pa.p : d_pb.p;
+            int *sin = cur ? d_sb.p : d_sa.p, *sout = cur ? d_sa.p : d_sb.p;
+            int *large_in = d_list[cur].p, *large_out = d_list[cur ^ 1].p, *small_in = d_list[2 + cur].p, *small_out = d_list[2 + (cur ^ 1)].p;
+            LBVH_TRY(hipMemsetAsync(d_next.p, 0, sizeof(SahLists), 0));
+            if (n_large > 0) {
+                const int n_bins = n_large * 3 * SAH_BINS;
+                hipLaunchKernelGGL(sah_bins_init_kernel, dim3((n_bins + 255) / 256), dim3(256), 0, 0, d_bins.p, n_bins);
+                hipLaunchKernelGGL(sah_bin_kernel, dim3(nb), dim3(256), 0, 0, pin, sin, int(n), d_segs.p, d_slot.p, d_bins.p);
+                hipLaunchKernelGGL(sah_eval_kernel, dim3((n_large + 63) / 64), dim3(64), 0, 0, large_in, n_large, d_bins.p, d_segs.p, d_split.p, d_out2.p, d_slot.p,
+                                   large_out, small_out, d_next.p);
+                hipLaunchKernelGGL(sah_flag_kernel, dim3(nb), dim3(256), 0, 0, pin, sin, int(n), d_segs.p, d_split.p, d_flag.p);
+                LBVH_TRY(rocprim::exclusive_scan(d_temp3.p, temp3_bytes, d_flag.p, d_scan.p, 0u, n, rocprim::plus<uint32_t>(), hipStream_t(0)));
+                hipLaunchKernelGGL(sah_partition_kernel, dim3(nb), dim3(256), 0, 0, pin, sin, int(n), d_segs.p, d_split.p, d_flag.p, d_scan.p, pout, sout, d_out2.p);
             }
-        } else {
-        LBVH_TRY(hipMemsetAsync(d_done, 0, (n - 1) * 4, 0));
-        hipLaunchKernelGGL(morton_kernel, dim3(nb), dim3(256), 0, 0, d_prims, uint32_t(n), cmin[0], cmin[1], cmin[2], scale[0], scale[1],
-                           scale[2], d_keys, d_order);
-        LBVH_TRY(rocprim::radix_sort_pairs(d_temp, temp_bytes, d_keys, d_keys2, d_order, d_order2, n, 0, 63, hipStream_t(0)));
-        hipLaunchKernelGGL(hierarchy_kernel, dim3(nb), dim3(256), 0, 0, d_keys2, int(n), d_children, d_node_parent);
+            if (n_small > 0) // (the segments of 64 leaves or fewer that the large splits of the last level made: each a whole subtree)
+                hipLaunchKernelGGL(sah_small_kernel, dim3((n_small + SAH_WAVES_PER_BLOCK - 1) / SAH_WAVES_PER_BLOCK), dim3(64 * SAH_WAVES_PER_BLOCK), 0, 0,
+                                   small_in, n_small, pin, d_segs.p, d_out2.p, sah_levels, d_levels.p);
+            SahLists h_next;
+            LBVH_TRY(hipMemcpy(&h_next, d_next.p, sizeof(h_next), hipMemcpyDeviceToHost));
+            if (size_t(h_next.n_large) > max_large || size_t(h_next.n_small) > n / 2 + 2) { err = "lbvh_build: SAH segment lists overflowed"; return -4; }
+            n_large = h_next.n_large; n_small = h_next.n_small;
+            cur ^= 1;
+        }
+    } else {
+        LBVH_TRY(hipMemsetAsync(d_done.p, 0, (n - 1) * 4, 0));
+        hipLaunchKernelGGL(morton_kernel, dim3(nb), dim3(256), 0, 0, d_prims.p, uint32_t(n), cmin[0], cmin[1], cmin[2], scale[0], scale[1],
+                           scale[2], d_keys.p, d_order.p);
+        LBVH_TRY(rocprim::radix_sort_pairs(d_temp.p, temp_bytes, d_keys.p, d_keys2.p, d_order.p, d_order2.p, n, 0, 63, hipStream_t(0)));
+        hipLaunchKernelGGL(hierarchy_kernel, dim3(nb), dim3(256), 0, 0, d_keys2.p, int(n), d_children.p, d_node_parent.p);
         // bottom-up fit: sweeps until the root is finished (the tree's height, which is not known beforehand: look at
         // the root's flag after every batch of sweeps)
         for (int sweep = 1, root_done = 0; !root_done;) {
             for (int k = 0; k < 16; ++k, ++sweep)
-                hipLaunchKernelGGL(fit_sweep_kernel, dim3(nb), dim3(256), 0, 0, d_prims, d_order2, n_inner, d_children, d_done, sweep,
-                                   d_box, d_levels, d_out, 0);
-            LBVH_TRY(hipMemcpy(&root_done, d_done, 4, hipMemcpyDeviceToHost));
-            if (sweep > 4096) { err = "lbvh_build: fit did not converge"; rc = -4; goto done; }
+                hipLaunchKernelGGL(fit_sweep_kernel, dim3(nb), dim3(256), 0, 0, d_prims.p, d_order2.p, n_inner, d_children.p, d_done.p, sweep,
+                                   d_box.p, d_levels.p, d_out.p, 0);
+            LBVH_TRY(hipMemcpy(&root_done, d_done.p, 4, hipMemcpyDeviceToHost));
+            if (sweep > 4096) { err = "lbvh_build: fit did not converge"; return -4; }
         }
-        hipLaunchKernelGGL(preorder_kernel, dim3(nb), dim3(256), 0, 0, d_children, d_node_parent, n_inner, d_pos);
-        hipLaunchKernelGGL(relayout_kernel, dim3(nb), dim3(256), 0, 0, d_out, d_pos, n_inner, 0, d_out2);
-        }
-
-        // ---- collapse: heads level by level (root first), numbering, records, stack bound
-        LBVH_TRY(hipMemsetAsync(d_is_head, 0, size_t(n_inner) * 4, 0));
-        {
-            static const uint32_t one = 1u; // (static: the source of an asynchronous copy must outlive the call)
-            static const int zero = 0;
-            LBVH_TRY(hipMemcpyAsync(d_is_head, &one, 4, hipMemcpyHostToDevice, 0)); // the root (binary node 0) heads record 0
-            LBVH_TRY(hipMemcpyAsync(d_heads, &zero, 4, hipMemcpyHostToDevice, 0));
-        }
-        level_off.push_back(0);
-        level_off.push_back(1);
-        for (;;) {
-            const int lo = level_off[level_off.size() - 2], hi = level_off.back(), n_front = hi - lo;
-            hipLaunchKernelGGL(collapse_count_kernel, dim3((n_front + 255) / 256), dim3(256), 0, 0, d_out2, d_heads + lo, n_front, d_fcount);
-            LBVH_TRY(rocprim::exclusive_scan(d_temp2, temp2_bytes, d_fcount, d_foff, 0u, size_t(n_front), rocprim::plus<uint32_t>(), hipStream_t(0)));
-            hipLaunchKernelGGL(collapse_mark_kernel, dim3((n_front + 255) / 256), dim3(256), 0, 0, d_out2, d_heads + lo, n_front, d_heads + hi, d_foff,
-                               d_is_head);
-            uint32_t last[2] = {0, 0};
-            LBVH_TRY(hipMemcpy(&last[0], d_fcount + (n_front - 1), 4, hipMemcpyDeviceToHost));
-            LBVH_TRY(hipMemcpy(&last[1], d_foff + (n_front - 1), 4, hipMemcpyDeviceToHost));
-            const int added = int(last[0] + last[1]);
-            if (added == 0) break;
-            if (hi + added > n_inner || level_off.size() > 4096) { err = "lbvh_build: collapse did not converge"; rc = -4; goto done; }
-            level_off.push_back(hi + added);
-        }
-        n_heads = uint32_t(level_off.back());
-        // Numbering of the records.  Level order (default since round 6): a record's number is its head's position in the frontier arrays, so the
-        // inner children of a record lie side by side — two 64-byte quantised records to a 128-byte line, and a walk that visits a record visits
-        // 1.6 of its children on average (tests/hostsim/cache_model.hpp: 50.1 -> 45.1 node-record miss lines per sample on spheres_1m against
-        // the binary tree's pre-order; treelets of 4 .. 64 records: 47 - 48).  RTTNW_NODE_ORDER=pre: the binary pre-order of rounds 1-5.
-        const char* order_env = getenv("RTTNW_NODE_ORDER");
-        if (order_env && std::string(order_env) == "pre")
-            LBVH_TRY(rocprim::exclusive_scan(d_temp2, temp2_bytes, d_is_head, d_rank, 0u, size_t(n_inner), rocprim::plus<uint32_t>(), hipStream_t(0)));
-        else
-            hipLaunchKernelGGL(rank_by_position_kernel, dim3((n_heads + 255) / 256), dim3(256), 0, 0, d_heads, int(n_heads), d_rank);
-        LBVH_TRY(hipMalloc((void**)&d_out4, size_t(n_heads) * sizeof(Bvh4Node)));
-        LBVH_TRY(hipMalloc((void**)&d_need, size_t(n_heads) * 4));
-        hipLaunchKernelGGL(collapse_write_kernel, dim3((n_heads + 255) / 256), dim3(256), 0, 0, d_out2, d_heads, int(n_heads), d_rank, d_out4);
-        for (size_t k = level_off.size() - 1; k-- > 0;) {
-            const int lo = level_off[k], n_level = level_off[k + 1] - lo;
-            hipLaunchKernelGGL(collapse_need_kernel, dim3((n_level + 255) / 256), dim3(256), 0, 0, d_out4, d_heads + lo, n_level, d_rank, d_need);
-        }
-        LBVH_TRY(hipEventRecord(e1, 0));
-        LBVH_TRY(hipGetLastError());
-        LBVH_TRY(hipEventSynchronize(e1));
-        float ms = 0;
-        LBVH_TRY(hipEventElapsedTime(&ms, e0, e1));
-        if (kernel_ms) *kernel_ms += ms;
-        t_kernels = wall_ms();
-        LBVH_TRY(hipMemcpy(&h_levels, d_levels, 4, hipMemcpyDeviceToHost));
-        if (sah) h_levels = std::max(h_levels, sah_levels); // the rounds of large segments are a level each; the small subtrees report theirs
-        LBVH_TRY(hipMemcpy(&h_need, d_need, 4, hipMemcpyDeviceToHost)); // record 0 = the root
-        tree = DeviceTree();
-        tree.nodes4 = std::shared_ptr<void>(d_out4, DeviceFree{device});
-        tree.nodes2 = std::shared_ptr<void>(d_out2, DeviceFree{device});
-        d_out4 = nullptr; d_out2 = nullptr; // owned by the tree now
-        tree.count4 = n_heads;
-        tree.count2 = uint32_t(n_inner);
-        tree.need = h_need;
-        tree.levels = uint32_t(h_levels);
-        tree.device = device;
-        if (getenv("RTTNW_DEBUG_LOWER"))
-            fprintf(stderr, "[lbvh] %s, %zu leaves -> %u 4-wide records in %zu levels: centroid bounds + allocations %.1f ms, upload %.1f ms, kernels %.1f ms (device %.2f); nothing downloaded\n",
-                    sah ? ("binned SAH, " + std::to_string(sah_levels) + " rounds").c_str() : "Karras hierarchy", n, n_heads, level_off.size() - 1, t_alloc, t_up - t_alloc, t_kernels - t_up, ms);
+        hipLaunchKernelGGL(preorder_kernel, dim3(nb), dim3(256), 0, 0, d_children.p, d_node_parent.p, n_inner, d_pos.p);
+        hipLaunchKernelGGL(relayout_kernel, dim3(nb), dim3(256), 0, 0, d_out.p, d_pos.p, n_inner, 0, d_out2.p);
     }
-done:
-    for (void* p : {(void*)d_prims, (void*)d_keys, (void*)d_keys2, (void*)d_order, (void*)d_order2, (void*)d_children, (void*)d_node_parent,
-                    (void*)d_done, (void*)d_levels, (void*)d_box, (void*)d_out, (void*)d_out2, (void*)d_pos, d_temp, d_temp2, (void*)d_heads,
-                    (void*)d_is_head, (void*)d_rank, (void*)d_fcount, (void*)d_foff, (void*)d_need, (void*)d_out4, d_temp3, (void*)d_pa, (void*)d_pb, (void*)d_sa, (void*)d_sb,
-                    (void*)d_slot, (void*)d_list[0], (void*)d_list[1], (void*)d_list[2], (void*)d_list[3], (void*)d_segs, (void*)d_split, (void*)d_bins,
-                    (void*)d_next, (void*)d_flag, (void*)d_scan})
-        if (p) (void)hipFree(p);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+
+    // ---- collapse: heads level by level (root first), numbering, records, stack bound
+    LBVH_TRY(hipMemsetAsync(d_is_head.p, 0, size_t(n_inner) * 4, 0));
+    {
+        static const uint32_t one = 1u; // (static: the source of an asynchronous copy must outlive the call)
+        static const int zero = 0;
+        LBVH_TRY(hipMemcpyAsync(d_is_head.p, &one, 4, hipMemcpyHostToDevice, 0)); // the root (binary node 0) heads record 0
+        LBVH_TRY(hipMemcpyAsync(d_heads.p, &zero, 4, hipMemcpyHostToDevice, 0));
+    }
+    std::vector<int> level_off{0, 1}; // frontier k = heads[level_off[k] .. level_off[k + 1])
+    for (;;) {
+        const int lo = level_off[level_off.size() - 2], hi = level_off.back(), n_front = hi - lo;
+        hipLaunchKernelGGL(collapse_count_kernel, dim3((n_front + 255) / 256), dim3(256), 0, 0, d_out2.p, d_heads.p + lo, n_front, d_fcount.p);
+        LBVH_TRY(rocprim::exclusive_scan(d_temp2.p, temp2_bytes, d_fcount.p, d_foff.p, 0u, size_t(n_front), rocprim::plus<uint32_t>(), hipStream_t(0)));
+        hipLaunchKernelGGL(collapse_mark_kernel, dim3((n_front + 255) / 256), dim3(256), 0, 0, d_out2.p, d_heads.p + lo, n_front, d_heads.p + hi, d_foff.p,
+                           d_is_head.p);
+        uint32_t last[2] = {0, 0};
+        LBVH_TRY(hipMemcpy(&last[0], d_fcount.p + (n_front - 1), 4, hipMemcpyDeviceToHost));
+        LBVH_TRY(hipMemcpy(&last[1], d_foff.p + (n_front - 1), 4, hipMemcpyDeviceToHost));
+        const int added = int(last[0] + last[1]);
+        if (added == 0) break;
+        if (hi + added > n_inner || level_off.size() > 4096) { err = "lbvh_build: collapse did not converge"; return -4; }
+        level_off.push_back(hi + added);
+    }
+    const uint32_t n_heads = uint32_t(level_off.back());
+    // Numbering of the records.  Level order (default since round 6): a record's number is its head's position in the frontier arrays, so the
+    // inner children of a record lie side by side — two 64-byte quantised records to a 128-byte line, and a walk that visits a record visits
+    // 1.6 of its children on average (tests/hostsim/cache_model.hpp: 50.1 -> 45.1 node-record miss lines per sample on spheres_1m against
+    // the binary tree's pre-order; treelets of 4 .. 64 records: 47 - 48).  RTTNW_NODE_ORDER=pre: the binary pre-order of rounds 1-5.
+    const char* order_env = getenv("RTTNW_NODE_ORDER");
+    if (order_env && std::string(order_env) == "pre")
+        LBVH_TRY(rocprim::exclusive_scan(d_temp2.p, temp2_bytes, d_is_head.p, d_rank.p, 0u, size_t(n_inner), rocprim::plus<uint32_t>(), hipStream_t(0)));
+    else
+        hipLaunchKernelGGL(rank_by_position_kernel, dim3((n_heads + 255) / 256), dim3(256), 0, 0, d_heads.p, int(n_heads), d_rank.p);
+    DevBuf<Bvh4Node> d_out4;
+    DevBuf<uint32_t> d_need;
+    LBVH_TRY(d_out4.alloc(n_heads));
+    LBVH_TRY(d_need.alloc(n_heads));
+    hipLaunchKernelGGL(collapse_write_kernel, dim3((n_heads + 255) / 256), dim3(256), 0, 0, d_out2.p, d_heads.p, int(n_heads), d_rank.p, d_out4.p);
+    for (size_t k = level_off.size() - 1; k-- > 0;) {
+        const int lo = level_off[k], n_level = level_off[k + 1] - lo;
+        hipLaunchKernelGGL(collapse_need_kernel, dim3((n_level + 255) / 256), dim3(256), 0, 0, d_out4.p, d_heads.p + lo, n_level, d_rank.p, d_need.p);
+    }
+    LBVH_TRY(hipEventRecord(e1.get(), 0));
+    LBVH_TRY(hipGetLastError());
+    LBVH_TRY(hipEventSynchronize(e1.get()));
+    float ms = 0;
+    LBVH_TRY(hipEventElapsedTime(&ms, e0.get(), e1.get()));
+    if (kernel_ms) *kernel_ms += ms;
+    const double t_kernels = wall_ms();
+    int h_levels = 0;
+    uint32_t h_need = 0;
+    LBVH_TRY(hipMemcpy(&h_levels, d_levels.p, 4, hipMemcpyDeviceToHost));
+    if (sah) h_levels = std::max(h_levels, sah_levels); // the rounds of large segments are a level each; the small subtrees report theirs
+    LBVH_TRY(hipMemcpy(&h_need, d_need.p, 4, hipMemcpyDeviceToHost)); // record 0 = the root
+    tree = DeviceTree();
+    tree.nodes4 = std::move(d_out4.mem);
+    tree.nodes2 = std::move(d_out2.mem);
+    tree.count4 = n_heads;
+    tree.count2 = uint32_t(n_inner);
+    tree.need = h_need;
+    tree.levels = uint32_t(h_levels);
+    tree.device = device;
+    if (getenv("RTTNW_DEBUG_LOWER"))
+        fprintf(stderr, "[lbvh] %s, %zu leaves -> %u 4-wide records in %zu levels: centroid bounds + allocations %.1f ms, upload %.1f ms, kernels %.1f ms (device %.2f); nothing downloaded\n",
+                sah ? ("binned SAH, " + std::to_string(sah_levels) + " rounds").c_str() : "Karras hierarchy", n, n_heads, level_off.size() - 1, t_alloc, t_up - t_alloc, t_kernels - t_up, ms);
+    return 0;
 }
 
 int device_tree_rebase(DeviceTree& tree, uint32_t base4, uint32_t base2, std::string& err) {
-    int rc = 0;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    {
-        LBVH_TRY(hipSetDevice(tree.device));
-        const int32_t delta = int32_t(base4) - int32_t(tree.base4);
-        if (delta != 0 && tree.count4) {
-            hipLaunchKernelGGL(rebase4_kernel, dim3((tree.count4 * 4u + 255u) / 256u), dim3(256), 0, 0, (Bvh4Node*)tree.nodes4.get(), tree.count4, delta);
-            LBVH_TRY(hipGetLastError());
-            LBVH_TRY(hipDeviceSynchronize());
-        }
-        tree.base4 = base4;
-        tree.base2 = base2;
+    DeviceGuard restore;
+    LBVH_TRY(hipSetDevice(tree.device));
+    const int32_t delta = int32_t(base4) - int32_t(tree.base4);
+    if (delta != 0 && tree.count4) {
+        hipLaunchKernelGGL(rebase4_kernel, dim3((tree.count4 * 4u + 255u) / 256u), dim3(256), 0, 0, (Bvh4Node*)tree.nodes4.get(), tree.count4, delta);
+        LBVH_TRY(hipGetLastError());
+        LBVH_TRY(hipDeviceSynchronize());
     }
-done:
-    if (prev >= 0) (void)hipSetDevice(prev);
-    return rc;
+    tree.base4 = base4;
+    tree.base2 = base2;
+    return 0;
 }
 
 int device_tree_download(const DeviceTree& tree, Bvh4Node* out4, BvhNode* out2, std::string& err) {
-    int rc = 0;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    {
-        LBVH_TRY(hipSetDevice(tree.device));
-        if (out4 && tree.count4) LBVH_TRY(hipMemcpy(out4, tree.nodes4.get(), size_t(tree.count4) * sizeof(Bvh4Node), hipMemcpyDeviceToHost));
-        if (out2 && tree.count2) {
-            LBVH_TRY(hipMemcpy(out2, tree.nodes2.get(), size_t(tree.count2) * sizeof(BvhNode), hipMemcpyDeviceToHost));
-            for (uint32_t i = 0; i < tree.count2; ++i) { // the binary records keep local indices on the device
-                if (out2[i].child0 >= 0) out2[i].child0 += int32_t(tree.base2);
-                if (out2[i].child1 >= 0) out2[i].child1 += int32_t(tree.base2);
-            }
+    DeviceGuard restore;
+    LBVH_TRY(hipSetDevice(tree.device));
+    if (out4 && tree.count4) LBVH_TRY(hipMemcpy(out4, tree.nodes4.get(), size_t(tree.count4) * sizeof(Bvh4Node), hipMemcpyDeviceToHost));
+    if (out2 && tree.count2) {
+        LBVH_TRY(hipMemcpy(out2, tree.nodes2.get(), size_t(tree.count2) * sizeof(BvhNode), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < tree.count2; ++i) { // the binary records keep local indices on the device
+            if (out2[i].child0 >= 0) out2[i].child0 += int32_t(tree.base2);
+            if (out2[i].child1 >= 0) out2[i].child1 += int32_t(tree.base2);
         }
     }
-done:
-    if (prev >= 0) (void)hipSetDevice(prev);
-    return rc;
+    return 0;
 }
 
 

@@ -19,35 +19,10 @@ static int render_tiles_any(::rttnw_scene* s, DeviceState* d, const rttnw_camera
     return render_tiles_t<double>(s, d, cam, p, d_packed, stream, stats, sync_for_stats, prepare_only);
 }
 
-int grow(void** p, size_t* have, size_t want) {
-    if (*have >= want && *p) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *have = 0;
-    HIP_TRY(hipMalloc(p, std::max<size_t>(want, 16)));
-    *have = want;
-    return 0;
-}
-
 void device_release(DeviceState* d) {
     if (!d) return;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
+    DeviceGuard restore;
     if (d->device >= 0) (void)hipSetDevice(d->device);
-    struct Restore { int dev; ~Restore() { if (dev >= 0) (void)hipSetDevice(dev); } } restore{prev};
-    d->s32.release(); d->s64.release(); d->s64_ref.release();
-    if (d->partial) (void)hipFree(d->partial);
-    if (d->pool_r) (void)hipFree(d->pool_r);
-    if (d->pool_u) (void)hipFree(d->pool_u);
-    if (d->spill) (void)hipFree(d->spill);
-    if (d->job_counter) (void)hipFree(d->job_counter);
-    if (d->packed) (void)hipFree(d->packed);
-    if (d->linear) (void)hipFree(d->linear);
-    if (d->rgba) (void)hipFree(d->rgba);
-    if (d->multi_packed) (void)hipFree(d->multi_packed);
-    if (d->gathered) (void)hipFree(d->gathered);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
     delete d;
 }
 
@@ -87,9 +62,9 @@ int device_state_create(DeviceState*& out, std::string& err) {
     if (e != hipSuccess) { err = std::string("hipGetDeviceProperties: ") + hipGetErrorString(e); device_release(d); return RTTNW_ERR_HIP; }
     d->num_cus = prop.multiProcessorCount;
     d->chunk_budget = std::min<uint64_t>(24ull << 30, std::max<uint64_t>(4ull << 30, uint64_t(prop.totalGlobalMem) / 12));
-    e = hipMalloc((void**)&d->job_counter, sizeof(unsigned long long) + sizeof(DeviceCounters));
-    if (e == hipSuccess) e = hipEventCreate(&d->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&d->ev1);
+    e = d->job_counter.alloc(1 + sizeof(DeviceCounters) / sizeof(unsigned long long));
+    if (e == hipSuccess) e = create_event(d->ev0);
+    if (e == hipSuccess) e = create_event(d->ev1);
     if (e != hipSuccess) { err = std::string("device state: ") + hipGetErrorString(e); device_release(d); return RTTNW_ERR_HIP; }
     out = d;
     return 0;
@@ -179,16 +154,16 @@ int validate(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params*
             s->build_kernel_ms = 0;
             if (int rc = lower_scene(s->graph, wider, err, on_device ? &device_builder : nullptr, t0, t1)) { set_last_error(err); return rc; }
             s->lower_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
-            int prev = -1;
-            (void)hipGetDevice(&prev);
             std::vector<DeviceState*> all = s->more_devices;
             all.push_back(s->device);
-            for (DeviceState* d : all) { // nothing of an earlier render may still read the arrays that are about to go
-                (void)hipSetDevice(d->device);
-                (void)hipDeviceSynchronize();
-                d->s32.release(); d->s64.release(); d->s64_ref.release();
+            {
+                DeviceGuard restore;
+                for (DeviceState* d : all) { // nothing of an earlier render may still read the arrays that are about to go
+                    (void)hipSetDevice(d->device);
+                    (void)hipDeviceSynchronize();
+                    d->s32 = {}; d->s64 = {}; d->s64_ref = {};
+                }
             }
-            if (prev >= 0) (void)hipSetDevice(prev);
             s->flat = std::move(wider);
             s->flat_ref.reset(); // (made again, for the wider interval, by the next RTTNW_F64_STRICT render)
         }
@@ -265,25 +240,26 @@ int rttnw_render(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_param
     rt::fill_layout(p->width, p->height, 1, L);
     const size_t rsz = p->precision == RTTNW_F32 ? sizeof(float) : sizeof(double);
     const size_t npx = size_t(p->width) * p->height;
-    if (int g = rt::grow(&d->packed, &d->packed_bytes, size_t(L.pixels_per_rank) * 4 * rsz)) return g;
-    if (int g = rt::grow(&d->linear, &d->linear_bytes, npx * 3 * rsz)) return g;
-    if (int g = rt::grow((void**)&d->rgba, &d->rgba_bytes, npx * 4)) return g;
-    int rc = rttnw_render_tiles_device(s, cam, p, d->packed, nullptr, stats);
+    hipError_t e = d->packed.grow(size_t(L.pixels_per_rank) * 4 * rsz);
+    if (e == hipSuccess) e = d->linear.grow(npx * 3 * rsz);
+    if (e == hipSuccess) e = d->rgba.grow(npx * 4);
+    if (e != hipSuccess) { rt::set_last_error(std::string("render: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
+    int rc = rttnw_render_tiles_device(s, cam, p, d->packed.p, nullptr, stats);
     if (rc) return rc;
-    rc = rttnw_untile_device(p->width, p->height, 1, p->precision, d->packed, d->linear, d->rgba, nullptr);
+    rc = rttnw_untile_device(p->width, p->height, 1, p->precision, d->packed.p, d->linear.p, d->rgba.p, nullptr);
     if (rc) return rc;
-    hipError_t e = hipDeviceSynchronize();
+    e = hipDeviceSynchronize();
     if (e != hipSuccess) { rt::set_last_error(std::string("render: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
     if (out_rgba8) {
-        e = hipMemcpy(out_rgba8, d->rgba, npx * 4, hipMemcpyDeviceToHost);
+        e = hipMemcpy(out_rgba8, d->rgba.p, npx * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) { rt::set_last_error(std::string("render: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
     }
     if (out_linear_rgb) {
         if (p->precision != RTTNW_F32) {
-            e = hipMemcpy(out_linear_rgb, d->linear, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+            e = hipMemcpy(out_linear_rgb, d->linear.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
         } else {
             std::vector<float> tmp(npx * 3);
-            e = hipMemcpy(tmp.data(), d->linear, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
+            e = hipMemcpy(tmp.data(), d->linear.p, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
             for (size_t i = 0; i < npx * 3; ++i) out_linear_rgb[i] = double(tmp[i]);
         }
         if (e != hipSuccess) { rt::set_last_error(std::string("render: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
@@ -373,9 +349,7 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
     const int n_dev = rttnw_device_count();
     for (uint32_t r = 0; r < ngpu; ++r)
         if (device_ids[r] < 0 || device_ids[r] >= n_dev) { set_last_error("render_multi: no such device"); return RTTNW_ERR_INVALID; }
-    int prev_dev = -1;
-    (void)hipGetDevice(&prev_dev);
-    struct Restore { int dev; ~Restore() { if (dev >= 0) (void)hipSetDevice(dev); } } restore{prev_dev};
+    DeviceGuard restore;
 
     std::string err;
     std::vector<DeviceState*> st(ngpu);
@@ -396,39 +370,38 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
     for (size_t k = 0; k < distinct.size(); ++k) {
         DeviceState* d = state_on(s, distinct[k], err);
         HIP_TRY(hipSetDevice(d->device));
-        if (!d->stream) HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-        if (int g = grow(&d->multi_packed, &d->multi_packed_bytes, chunk * per_dev[k])) return g;
+        if (!d->stream) HIP_TRY(create_stream(d->stream, hipStreamNonBlocking));
+        HIP_TRY(d->multi_packed.grow(chunk * per_dev[k]));
     }
     DeviceState* root = st[0];
     HIP_TRY(hipSetDevice(root->device));
-    if (int g = grow(&root->gathered, &root->gathered_bytes, chunk * ngpu)) return g;
-    if (int g = grow(&root->linear, &root->linear_bytes, npx * 3 * rsz)) return g;
-    if (int g = grow((void**)&root->rgba, &root->rgba_bytes, npx * 4)) return g;
+    HIP_TRY(root->gathered.grow(chunk * ngpu));
+    HIP_TRY(root->linear.grow(npx * 3 * rsz));
+    HIP_TRY(root->rgba.grow(npx * 4));
 
-    // ---- first use: scene uploads and workspace growth for EVERY rank, before anything is launched (a hipMalloc or a
-    // hipFree between two ranks' launches would synchronise its whole device)
+    // ---- first use: scene uploads and workspace growth for EVERY rank, before anything is launched (an allocation or a
+    // free between two ranks' launches would synchronise its whole device)
     for (uint32_t r = 0; r < ngpu; ++r) {
         rttnw_params pr = p;
         pr.tile_rank = r;
-        void* dst = (char*)st[r]->multi_packed + chunk * slot[r];
-        int rc = render_tiles_any(s, st[r], cam, &pr, dst, st[r]->stream, nullptr, false, true);
+        void* dst = st[r]->multi_packed.p + chunk * slot[r];
+        int rc = render_tiles_any(s, st[r], cam, &pr, dst, st[r]->stream.get(), nullptr, false, true);
         if (rc) return rc;
     }
     // ---- every rank traces its tiles, on its device's stream; ranks that share a device run one after the other
-    std::vector<hipEvent_t> ev(size_t(ngpu) * 2, nullptr);
-    struct EvFree { std::vector<hipEvent_t>& v; ~EvFree() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); } } ev_free{ev};
+    std::vector<Event> ev(size_t(ngpu) * 2);
     for (uint32_t r = 0; r < ngpu; ++r) {
         DeviceState* d = st[r];
         HIP_TRY(hipSetDevice(d->device));
         rttnw_params pr = p;
         pr.tile_rank = r;
-        void* dst = (char*)d->multi_packed + chunk * slot[r];
-        HIP_TRY(hipEventCreate(&ev[2 * r]));
-        HIP_TRY(hipEventCreate(&ev[2 * r + 1]));
-        HIP_TRY(hipEventRecord(ev[2 * r], d->stream));
-        int rc = render_tiles_any(s, d, cam, &pr, dst, d->stream, stats ? &stats[r] : nullptr, false);
+        void* dst = d->multi_packed.p + chunk * slot[r];
+        HIP_TRY(create_event(ev[2 * r]));
+        HIP_TRY(create_event(ev[2 * r + 1]));
+        HIP_TRY(hipEventRecord(ev[2 * r].get(), d->stream.get()));
+        int rc = render_tiles_any(s, d, cam, &pr, dst, d->stream.get(), stats ? &stats[r] : nullptr, false);
         if (rc) return rc;
-        HIP_TRY(hipEventRecord(ev[2 * r + 1], d->stream));
+        HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), d->stream.get()));
     }
 
     // ---- gather to the root: a device-to-device copy for ranks on the root's device; for the others one of TWO transports over xGMI
@@ -490,9 +463,9 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
                 size_t k = 0;
                 while (distinct[k] != device_ids[r]) ++k;
                 if (k == 0 && !force_rccl) continue; // on the root's device: copied below
-                const void* src = (const char*)st[r]->multi_packed + chunk * slot[r];
-                nr = g_rccl.Send(src, chunk, ncclChar, 0, mc->comms[k], st[r]->stream);
-                if (nr == ncclSuccess) nr = g_rccl.Recv((char*)root->gathered + chunk * r, chunk, ncclChar, int(k), mc->comms[0], root->stream);
+                const void* src = st[r]->multi_packed.p + chunk * slot[r];
+                nr = g_rccl.Send(src, chunk, ncclChar, 0, mc->comms[k], st[r]->stream.get());
+                if (nr == ncclSuccess) nr = g_rccl.Recv(root->gathered.p + chunk * r, chunk, ncclChar, int(k), mc->comms[0], root->stream.get());
                 ++n_sent;
             }
             ncclResult_t ne = g_rccl.GroupEnd();
@@ -512,21 +485,20 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
                 (void)hipGetLastError();
             }
         }
-        std::vector<hipEvent_t> sent(ngpu, nullptr);
-        struct SentFree { std::vector<hipEvent_t>& v; ~SentFree() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); } } sent_free{sent};
+        std::vector<Event> sent(ngpu);
         uint32_t n_sent = 0;
         for (uint32_t r = 0; r < ngpu; ++r) {
             if (device_ids[r] == root->device && !force_rccl) continue; // on the root's device: copied below
             HIP_TRY(hipSetDevice(st[r]->device));
-            const void* src = (const char*)st[r]->multi_packed + chunk * slot[r];
-            HIP_TRY(hipMemcpyPeerAsync((char*)root->gathered + chunk * r, root->device, src, st[r]->device, chunk, st[r]->stream));
-            HIP_TRY(hipEventCreateWithFlags(&sent[r], hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(sent[r], st[r]->stream));
+            const void* src = st[r]->multi_packed.p + chunk * slot[r];
+            HIP_TRY(hipMemcpyPeerAsync(root->gathered.p + chunk * r, root->device, src, st[r]->device, chunk, st[r]->stream.get()));
+            HIP_TRY(create_event(sent[r], hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(sent[r].get(), st[r]->stream.get()));
             ++n_sent;
         }
         HIP_TRY(hipSetDevice(root->device));
         for (uint32_t r = 0; r < ngpu; ++r)
-            if (sent[r]) HIP_TRY(hipStreamWaitEvent(root->stream, sent[r], 0)); // the un-tile below reads what the ranks' streams have written
+            if (sent[r]) HIP_TRY(hipStreamWaitEvent(root->stream.get(), sent[r].get(), 0)); // the un-tile below reads what the ranks' streams have written
         if (debug_multi) fprintf(stderr, "[render_multi] %u rank buffer(s) of %zu bytes through hipMemcpyPeerAsync\n", n_sent, chunk);
         // (the events are destroyed when this block ends: a recorded event may be destroyed while work waits on it — the wait was enqueued)
     }
@@ -534,31 +506,31 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
     if (!force_rccl)
         for (uint32_t r = 0; r < ngpu; ++r)
             if (device_ids[r] == root->device)
-                HIP_TRY(hipMemcpyAsync((char*)root->gathered + chunk * r, (const char*)root->multi_packed + chunk * slot[r], chunk, hipMemcpyDeviceToDevice, root->stream));
-    int rc = rttnw_untile_device(p.width, p.height, ngpu, p.precision, root->gathered, root->linear, root->rgba, root->stream);
+                HIP_TRY(hipMemcpyAsync(root->gathered.p + chunk * r, root->multi_packed.p + chunk * slot[r], chunk, hipMemcpyDeviceToDevice, root->stream.get()));
+    int rc = rttnw_untile_device(p.width, p.height, ngpu, p.precision, root->gathered.p, root->linear.p, root->rgba.p, root->stream.get());
     if (rc) return rc;
     for (size_t k = 0; k < distinct.size(); ++k) {
         DeviceState* d = state_on(s, distinct[k], err);
         HIP_TRY(hipSetDevice(d->device));
-        HIP_TRY(hipStreamSynchronize(d->stream));
+        HIP_TRY(hipStreamSynchronize(d->stream.get()));
     }
     HIP_TRY(hipSetDevice(root->device));
     if (stats)
         for (uint32_t r = 0; r < ngpu; ++r) {
             float ms = 0;
             HIP_TRY(hipSetDevice(st[r]->device));
-            HIP_TRY(hipEventElapsedTime(&ms, ev[2 * r], ev[2 * r + 1]));
+            HIP_TRY(hipEventElapsedTime(&ms, ev[2 * r].get(), ev[2 * r + 1].get()));
             stats[r].kernel_ms = ms; // trace + resolve of this rank
         }
     if (stats && use_peer && (distinct.size() > 1 || force_rccl)) stats[0].reserved |= 0x100u | (fell_back ? 0x200u : 0u);
     HIP_TRY(hipSetDevice(root->device));
-    if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, root->rgba, npx * 4, hipMemcpyDeviceToHost));
+    if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, root->rgba.p, npx * 4, hipMemcpyDeviceToHost));
     if (out_linear_rgb) {
         if (p.precision != RTTNW_F32) {
-            HIP_TRY(hipMemcpy(out_linear_rgb, root->linear, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(out_linear_rgb, root->linear.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
         } else {
             std::vector<float> tmp(npx * 3);
-            HIP_TRY(hipMemcpy(tmp.data(), root->linear, npx * 3 * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(tmp.data(), root->linear.p, npx * 3 * sizeof(float), hipMemcpyDeviceToHost));
             for (size_t i = 0; i < npx * 3; ++i) out_linear_rgb[i] = double(tmp[i]);
         }
     }

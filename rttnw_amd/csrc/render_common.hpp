@@ -8,6 +8,7 @@
 #include "../../include/rttnw_hip.h"
 #include "rt_core.hpp"
 #include "scene_handle.hpp"
+#include "device_mem.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -33,32 +34,9 @@ namespace rt {
         }                                                                                  \
     } while (0)
 
-template <typename T> struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    template <typename A> int upload(const std::vector<T, A>& v) {
-        release();
-        n = v.size();
-        const size_t bytes = (std::max<size_t>(n, 1) * sizeof(T) + 31) / 32 * 32; // (the LDS staging of small record arrays copies whole 32-byte units)
-        HIP_TRY(hipMalloc((void**)&p, bytes));
-        if (n) HIP_TRY(hipMemcpy(p, v.data(), n * sizeof(T), hipMemcpyHostToDevice));
-        return 0;
-    }
-    void release() {
-        if (p && !adopted) (void)hipFree(p);
-        adopted.reset();
-        p = nullptr;
-        n = 0;
-    }
-    std::shared_ptr<void> adopted; // set: p is a buffer someone else made on this device (a device-built tree); kept alive, not freed here
-    void adopt(const std::shared_ptr<void>& buf, size_t count) {
-        release();
-        adopted = buf;
-        p = (T*)buf.get();
-        n = count;
-    }
-};
-
+// A scene's arrays on one device.  A scene is uploaded whole or not at all (upload), and the decoupled kernels' records are added whole or not at
+// all (ensure_quant4): every step builds into local owners, which the members take over only once all of them have succeeded.  An empty
+// DeviceScene{} is a scene not yet uploaded; assigning one drops the arrays.
 template <typename R> struct DeviceScene {
     bool ready = false;
     DevBuf<Bvh4Node> nodes;
@@ -94,18 +72,15 @@ template <typename R> struct DeviceScene {
     // nodes are ONE device-built tree on this very device (spheres_1m: 57 MB) simply adopts the builder's buffer; otherwise the
     // pieces are put together — device-to-device for trees built here, through the host copy (materialize_host_nodes) for
     // trees built on another device.
-    int upload_nodes(const FlatScene& f) {
+    static int upload_nodes(const FlatScene& f, DevBuf<Bvh4Node>& nodes) {
         int dev = -1;
         HIP_TRY(hipGetDevice(&dev));
-        if (f.device_trees.empty()) return nodes.upload(f.nodes4);
+        if (f.device_trees.empty()) { HIP_TRY(nodes.upload(f.nodes4)); return 0; }
         if (f.n_host4 == 0 && f.device_trees.size() == 1 && f.device_trees[0].device == dev) {
             nodes.adopt(f.device_trees[0].nodes4, f.device_trees[0].count4);
             return 0;
         }
-        nodes.release();
-        const size_t total = f.total_nodes4();
-        HIP_TRY(hipMalloc((void**)&nodes.p, std::max<size_t>(total, 1) * sizeof(Bvh4Node)));
-        nodes.n = total;
+        HIP_TRY(nodes.alloc(f.total_nodes4()));
         if (f.n_host4) HIP_TRY(hipMemcpy(nodes.p, f.nodes4.data(), size_t(f.n_host4) * sizeof(Bvh4Node), hipMemcpyHostToDevice));
         for (const DeviceTree& t : f.device_trees) {
             if (t.device == dev) {
@@ -122,19 +97,20 @@ template <typename R> struct DeviceScene {
     // The decoupled kernels' node records, made on this device from the f32 ones the first time such a kernel is chosen.
     int ensure_quant4(const FlatScene& f) {
         if (nodes4q.p) return 0;
-        {
-            const char* e = getenv("RTTNW_INTERLEAVE"); // (0: the separate arrays of rounds 1-5, for A/B runs and tests)
-            if (f.sphere_mat_is_index && f.insts.empty() && f.moving.empty() && f.media.empty() && !(e && e[0] == '0')) return build_interleaved(f);
-        }
+        const char* e = getenv("RTTNW_INTERLEAVE"); // (0: the separate arrays of rounds 1-5, for A/B runs and tests)
+        if (f.sphere_mat_is_index && f.insts.empty() && f.moving.empty() && f.media.empty() && !(e && e[0] == '0')) return build_interleaved(f);
+        return build_quant4(f);
+    }
+    int build_quant4(const FlatScene& f) {
         const uint32_t n = f.total_nodes4();
-        HIP_TRY(hipMalloc((void**)&nodes4q.p, std::max<size_t>(n, 1) * sizeof(Bvh4QNode)));
-        nodes4q.n = n;
+        DevBuf<Bvh4QNode> q;
+        HIP_TRY(q.alloc(n));
         std::string err;
-        if (int rc = quant4_build_device(nodes.p, n, nodes4q.p, err)) { set_last_error(err); nodes4q.release(); return rc; }
+        if (int rc = quant4_build_device(nodes.p, n, q.p, err)) { set_last_error(err); return rc; }
+        nodes4q = q;
         view.nodes4q = nodes4q.p;
         return 0;
     }
-
 
     // A big cloud (FlatScene::sphere_mat_is_index: >= 65 536 spheres, slot i holds i, no instance, medium or moving sphere): the quantised node
     // records and the spheres of their leaves in ONE buffer.  Per-record sphere counts come from the device (the tree may live only there), the
@@ -144,13 +120,11 @@ template <typename R> struct DeviceScene {
     int build_interleaved(const FlatScene& f) {
         const uint32_t n4 = f.total_nodes4();
         std::string err;
-        uint8_t* d_cnt = nullptr;
-        uint32_t* d_off = nullptr;
-        struct Free { uint8_t*& a; uint32_t*& b; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } free_tmp{d_cnt, d_off};
-        HIP_TRY(hipMalloc((void**)&d_cnt, std::max<uint32_t>(n4, 1)));
-        if (int rc = interleave_count_device(nodes.p, n4, d_cnt, err)) { set_last_error(err); return rc; }
+        DevBuf<uint8_t> d_cnt;
+        HIP_TRY(d_cnt.alloc(n4));
+        if (int rc = interleave_count_device(nodes.p, n4, d_cnt.p, err)) { set_last_error(err); return rc; }
         std::vector<uint8_t> cnt(n4);
-        if (n4) HIP_TRY(hipMemcpy(cnt.data(), d_cnt, n4, hipMemcpyDeviceToHost));
+        if (n4) HIP_TRY(hipMemcpy(cnt.data(), d_cnt.p, n4, hipMemcpyDeviceToHost));
         constexpr uint32_t su = uint32_t(sizeof(SphereRec<R>) / 16);
         std::vector<uint32_t> off(n4);
         uint64_t at = 0;
@@ -162,21 +136,25 @@ template <typename R> struct DeviceScene {
         }
         at = (at + 7) / 8 * 8;
         const uint64_t n_sparse = at / su;               // sphere indices of the buffer run up to here
-        if (at >= (1ull << 32) || n_sparse >= (1ull << 26)) return ensure_quant4_plain(f); // (beyond the leaf bits' 26-bit record index: the separate arrays)
-        HIP_TRY(hipMalloc((void**)&d_off, std::max<size_t>(n4, 1) * 4));
-        if (n4) HIP_TRY(hipMemcpy(d_off, off.data(), size_t(n4) * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void**)&nodes4q.p, size_t(at) * 16));
-        nodes4q.n = size_t(at) / 4;
-        HIP_TRY(hipMemset(nodes4q.p, 0, size_t(at) * 16));
-        HIP_TRY(hipMalloc((void**)&seq_q.p, size_t(n_sparse) * 4)); seq_q.n = size_t(n_sparse);
-        HIP_TRY(hipMemset(seq_q.p, 0, size_t(n_sparse) * 4));
+        if (at >= (1ull << 32) || n_sparse >= (1ull << 26)) return build_quant4(f); // (beyond the leaf bits' 26-bit record index: the separate arrays)
+        DevBuf<uint32_t> d_off;
+        HIP_TRY(d_off.alloc(n4));
+        if (n4) HIP_TRY(hipMemcpy(d_off.p, off.data(), size_t(n4) * 4, hipMemcpyHostToDevice));
+        DevBuf<Bvh4QNode> buf;
+        HIP_TRY(buf.alloc(size_t(at) / 4));
+        HIP_TRY(hipMemset(buf.p, 0, size_t(at) * 16));
+        DevBuf<int32_t> seq;
+        HIP_TRY(seq.alloc(size_t(n_sparse)));
+        HIP_TRY(hipMemset(seq.p, 0, size_t(n_sparse) * 4));
         const size_t nm = f.mats.size();
-        HIP_TRY(hipMalloc((void**)&mats_q.p, (size_t(n_sparse) + nm) * sizeof(MaterialRec<R>))); mats_q.n = size_t(n_sparse) + nm;
-        HIP_TRY(hipMemset(mats_q.p, 0, size_t(n_sparse) * sizeof(MaterialRec<R>)));
-        if (nm) HIP_TRY(hipMemcpy(mats_q.p + n_sparse, mats.p, nm * sizeof(MaterialRec<R>), hipMemcpyDeviceToDevice)); // the scene's materials, behind the spheres'
+        DevBuf<MaterialRec<R>> mq;
+        HIP_TRY(mq.alloc(size_t(n_sparse) + nm));
+        HIP_TRY(hipMemset(mq.p, 0, size_t(n_sparse) * sizeof(MaterialRec<R>)));
+        if (nm) HIP_TRY(hipMemcpy(mq.p + n_sparse, mats.p, nm * sizeof(MaterialRec<R>), hipMemcpyDeviceToDevice)); // the scene's materials, behind the spheres'
+        static_assert(sizeof(SphereRec<R>) % 16 == 0 && sizeof(MaterialRec<R>) % 16 == 0, "interleave_scatter_kernel copies 16-byte units");
         InterleaveArgs a{};
-        a.nodes4 = nodes.p; a.n4 = n4; a.noff = d_off; a.spheres = spheres.p; a.sphere_bytes = uint32_t(sizeof(SphereRec<R>)); a.sphere_seq = sphere_seq.p;
-        a.mats = mats.p; a.mat_bytes = uint32_t(sizeof(MaterialRec<R>)); a.buffer = nodes4q.p; a.seq_out = seq_q.p; a.mats_out = mats_q.p;
+        a.nodes4 = nodes.p; a.n4 = n4; a.noff = d_off.p; a.spheres = spheres.p; a.sphere_bytes = uint32_t(sizeof(SphereRec<R>)); a.sphere_seq = sphere_seq.p;
+        a.mats = mats.p; a.mat_bytes = uint32_t(sizeof(MaterialRec<R>)); a.buffer = buf.p; a.seq_out = seq.p; a.mats_out = mq.p;
         if (int rc = interleave_build_device(a, err)) { set_last_error(err); return rc; }
         // the other kinds' records keep their places; their material references move behind the sparse block
         std::vector<RectRec<R>> rq;
@@ -188,8 +166,12 @@ template <typename R> struct DeviceScene {
             o.mat = b.mat + int32_t(n_sparse); o.seq = b.seq;
             bq.push_back(o);
         }
-        if (int rc = rects_q.upload(rq)) return rc;
-        if (int rc = boxes_q.upload(bq)) return rc;
+        DevBuf<RectRec<R>> rects_buf;
+        DevBuf<BoxRec<R>> boxes_buf;
+        HIP_TRY(rects_buf.upload(rq));
+        HIP_TRY(boxes_buf.upload(bq));
+        // every step has succeeded: the scene takes the new arrays
+        nodes4q = buf; seq_q = seq; mats_q = mq; rects_q = rects_buf; boxes_q = boxes_buf;
         view_q = view;
         view_q.nodes4q = nodes4q.p;
         view_q.spheres = reinterpret_cast<const SphereRec<R>*>(nodes4q.p);
@@ -201,15 +183,6 @@ template <typename R> struct DeviceScene {
         view_q.top_root = int32_t(off[size_t(f.top_root)] >> 2);
         view.nodes4q = nodes4q.p; // (never walked through `view`: the records' child slots are the interleaved buffer's)
         interleaved = true;
-        return 0;
-    }
-    int ensure_quant4_plain(const FlatScene& f) {
-        const uint32_t n = f.total_nodes4();
-        HIP_TRY(hipMalloc((void**)&nodes4q.p, std::max<size_t>(n, 1) * sizeof(Bvh4QNode)));
-        nodes4q.n = n;
-        std::string err;
-        if (int rc = quant4_build_device(nodes.p, n, nodes4q.p, err)) { set_last_error(err); nodes4q.release(); return rc; }
-        view.nodes4q = nodes4q.p;
         return 0;
     }
 
@@ -251,30 +224,26 @@ template <typename R> struct DeviceScene {
         std::vector<R> pv;
         for (double v : f.perlin_vec) pv.push_back(R(v));
 
-        int rc;
-        if ((rc = upload_nodes(f)) || (rc = spheres.upload(sp)) || (!f.sphere_mat_is_index && (rc = sphere_mat.upload(f.sphere_mat))) ||
-            (rc = sphere_seq.upload(f.sphere_seq)) || (rc = moving.upload(mv)) || (rc = rects.upload(rc_)) ||
-            (rc = boxes.upload(bx)) || (rc = insts.upload(in)) || (rc = media.upload(md)) || (rc = medium_refs.upload(f.medium_refs)) || (rc = mats.upload(mt)) ||
-            (rc = texs.upload(tx)) || (rc = images.upload(f.images)) || (rc = texels.upload(f.texels)) ||
-            (rc = perlin_vec.upload(pv)) || (rc = perlin_perm.upload(f.perlin_perm)))
-            return rc;
-        view.nodes = nodes.p; view.nodes4q = nullptr; view.spheres = spheres.p; view.sphere_mat = f.sphere_mat_is_index ? nullptr : sphere_mat.p; view.sphere_seq = sphere_seq.p;
-        view.moving = moving.p; view.rects = rects.p; view.boxes = boxes.p; view.insts = insts.p; view.media = media.p; view.medium_refs = medium_refs.p;
-        view.mats = mats.p; view.texs = texs.p; view.images = images.p; view.texels = texels.p;
-        view.perlin_vec = perlin_vec.p; view.perlin_perm = perlin_perm.p;
-        view.top_root = f.top_root;
-        view.n_media = int32_t(f.media.size());
-        bytes = size_t(f.total_nodes4()) * sizeof(Bvh4Node) + sp.size() * sizeof(SphereRec<R>) + mv.size() * sizeof(MovingSphereRec<R>) +
-                rc_.size() * sizeof(RectRec<R>) + bx.size() * sizeof(BoxRec<R>) + in.size() * sizeof(InstanceRec<R>);
-        ready = true;
+        DeviceScene s; // taken over whole once every upload has succeeded
+        if (int rc = upload_nodes(f, s.nodes)) return rc;
+        HIP_TRY(s.spheres.upload(sp));
+        if (!f.sphere_mat_is_index) HIP_TRY(s.sphere_mat.upload(f.sphere_mat));
+        HIP_TRY(s.sphere_seq.upload(f.sphere_seq)); HIP_TRY(s.moving.upload(mv)); HIP_TRY(s.rects.upload(rc_)); HIP_TRY(s.boxes.upload(bx));
+        HIP_TRY(s.insts.upload(in)); HIP_TRY(s.media.upload(md)); HIP_TRY(s.medium_refs.upload(f.medium_refs)); HIP_TRY(s.mats.upload(mt));
+        HIP_TRY(s.texs.upload(tx)); HIP_TRY(s.images.upload(f.images)); HIP_TRY(s.texels.upload(f.texels));
+        HIP_TRY(s.perlin_vec.upload(pv)); HIP_TRY(s.perlin_perm.upload(f.perlin_perm));
+        SceneView<R>& v = s.view;
+        v.nodes = s.nodes.p; v.spheres = s.spheres.p; v.sphere_mat = f.sphere_mat_is_index ? nullptr : s.sphere_mat.p; v.sphere_seq = s.sphere_seq.p;
+        v.moving = s.moving.p; v.rects = s.rects.p; v.boxes = s.boxes.p; v.insts = s.insts.p; v.media = s.media.p; v.medium_refs = s.medium_refs.p;
+        v.mats = s.mats.p; v.texs = s.texs.p; v.images = s.images.p; v.texels = s.texels.p;
+        v.perlin_vec = s.perlin_vec.p; v.perlin_perm = s.perlin_perm.p;
+        v.top_root = f.top_root;
+        v.n_media = int32_t(f.media.size());
+        s.bytes = size_t(f.total_nodes4()) * sizeof(Bvh4Node) + sp.size() * sizeof(SphereRec<R>) + mv.size() * sizeof(MovingSphereRec<R>) +
+                  rc_.size() * sizeof(RectRec<R>) + bx.size() * sizeof(BoxRec<R>) + in.size() * sizeof(InstanceRec<R>);
+        s.ready = true;
+        *this = s;
         return 0;
-    }
-    void release() {
-        seq_q.release(); mats_q.release(); rects_q.release(); boxes_q.release(); interleaved = false;
-        nodes.release(); nodes4q.release(); spheres.release(); sphere_mat.release(); sphere_seq.release(); moving.release(); rects.release();
-        boxes.release(); insts.release(); media.release(); medium_refs.release(); mats.release(); texs.release(); images.release();
-        texels.release(); perlin_vec.release(); perlin_perm.release();
-        ready = false;
     }
 };
 
@@ -285,24 +254,18 @@ struct DeviceState {
     DeviceScene<float> s32;
     DeviceScene<double> s64;
     DeviceScene<double> s64_ref; // rttnw_scene::flat_ref on this device (RTTNW_F64_STRICT renders of scenes with world-space copies)
-    // workspace, grown on demand and kept
-    void* partial = nullptr;
-    size_t partial_bytes = 0;
-    void* pool_r = nullptr; size_t pool_r_bytes = 0; // path-slot state (reals / words), SoA over all slots
-    void* pool_u = nullptr; size_t pool_u_bytes = 0;
-    void* spill = nullptr; size_t spill_bytes = 0;   // traversal-stack entries beyond LDS_STACK_ENTRIES, per thread of the launch
-    unsigned long long* job_counter = nullptr; // [0] job counter, then DeviceCounters
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipStream_t stream = nullptr;              // rttnw_render_multi: this device's launch stream
-    void* multi_packed = nullptr; size_t multi_packed_bytes = 0; // packed tiles of the logical ranks living on this device
-    void* gathered = nullptr; size_t gathered_bytes = 0;         // root device: every rank's packed tiles
+    // workspace, grown on demand and kept (DevBuf::grow: n = bytes)
+    DevBuf<uint8_t> partial;
+    DevBuf<uint8_t> pool_r, pool_u; // path-slot state (reals / words), SoA over all slots
+    DevBuf<uint8_t> spill;          // traversal-stack entries beyond LDS_STACK_ENTRIES, per thread of the launch
+    DevBuf<unsigned long long> job_counter; // [0] job counter, then DeviceCounters
+    Event ev0, ev1;
+    Stream stream;                  // rttnw_render_multi: this device's launch stream
+    DevBuf<uint8_t> multi_packed;   // packed tiles of the logical ranks living on this device
+    DevBuf<uint8_t> gathered;       // root device: every rank's packed tiles
     // scratch for the blocking host-output render()
-    void* packed = nullptr; size_t packed_bytes = 0;
-    void* linear = nullptr; size_t linear_bytes = 0;
-    uint8_t* rgba = nullptr; size_t rgba_bytes = 0;
+    DevBuf<uint8_t> packed, linear, rgba;
 };
-
-int grow(void** p, size_t* have, size_t want); // a workspace buffer kept at its high-water mark (render_api.cpp)
 void debug_print_sched(const DeviceCounters& hc, bool plain, uint32_t profile, uint64_t samples); // RTTNW_DEBUG_SCHED=1 only (debug_sched.cpp)
 int device_state_create(DeviceState*& out, std::string& err);
 // The lowering an RTTNW_F64_STRICT render walks: s->flat, or — when that holds world-space copies of transformed groups' spheres — the same

@@ -9,8 +9,8 @@
 namespace rt {
 inline namespace RT_ARITH_NS {
 
-// prepare_only: upload the scene on first use and grow every workspace buffer this render will need (blocking hipMalloc /
-// hipMemcpy / hipFree calls), launch nothing — rttnw_render_multi does that for ALL its ranks before the first launch, so
+// prepare_only: upload the scene on first use and grow every workspace buffer this render will need (blocking
+// allocations, copies and frees), launch nothing — rttnw_render_multi does that for ALL its ranks before the first launch, so
 // that no allocation (a device-wide synchronisation) sits between two ranks' kernels.
 template <typename R>
 int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
@@ -54,22 +54,20 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
     for (uint64_t budget = d->chunk_budget;; budget /= 2) {
         per_launch = launch_chunks(uint64_t(rc.my_tiles) * 64, 3 * sizeof(R), total_chunks, budget);
         const size_t want = std::max<size_t>(size_t(rc.my_tiles) * 64 * std::min(per_launch, total_chunks), 1) * 3 * sizeof(R);
-        if (d->partial_bytes >= want && d->partial) break;
-        void* bigger = nullptr;
-        const hipError_t e = hipMalloc(&bigger, std::max<size_t>(want, 16));
+        if (d->partial.n >= want && d->partial.p) break;
+        DevBuf<uint8_t> bigger;
+        const hipError_t e = bigger.grow(want);
         if (e == hipSuccess) {
-            if (d->partial) (void)hipFree(d->partial);
             d->partial = bigger;
-            d->partial_bytes = want;
             if (!getenv("RTTNW_CHUNK_SUM_BUDGET")) d->chunk_budget = budget;
             break;
         }
         (void)hipGetLastError(); // clear the sticky out-of-memory
         const size_t one_group = size_t(rc.my_tiles) * 64 * std::min<uint32_t>(16u, total_chunks) * 3 * sizeof(R);
         // (not under RTTNW_CHUNK_SUM_BUDGET: launch_chunks() would size the launches by the environment's budget again, not by the buffer in hand)
-        if (d->partial && d->partial_bytes >= one_group && !getenv("RTTNW_CHUNK_SUM_BUDGET")) { // no larger buffer to be had: split the render by the one in hand
-            per_launch = launch_chunks(uint64_t(rc.my_tiles) * 64, 3 * sizeof(R), total_chunks, d->partial_bytes);
-            if (!getenv("RTTNW_CHUNK_SUM_BUDGET")) d->chunk_budget = std::max<uint64_t>(d->partial_bytes, 1ull << 30);
+        if (d->partial.p && d->partial.n >= one_group && !getenv("RTTNW_CHUNK_SUM_BUDGET")) { // no larger buffer to be had: split the render by the one in hand
+            per_launch = launch_chunks(uint64_t(rc.my_tiles) * 64, 3 * sizeof(R), total_chunks, d->partial.n);
+            if (!getenv("RTTNW_CHUNK_SUM_BUDGET")) d->chunk_budget = std::max<uint64_t>(d->partial.n, 1ull << 30);
             break;
         }
         if (budget <= (1ull << 30) || getenv("RTTNW_CHUNK_SUM_BUDGET")) { set_last_error(std::string("render: no memory for the chunk sums: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
@@ -98,8 +96,8 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
     bool plain = flat.total_nodes4() < (sizeof(R) == 4 ? 5000u : 9000u);
     if (kv && (std::strcmp(kv, "plain") == 0 || std::strcmp(kv, "plainglobal") == 0)) plain = true;
     if (kv && std::strcmp(kv, "wave") == 0) plain = false;
-    if (!prepare_only) HIP_TRY(hipMemsetAsync(d->job_counter, 0, sizeof(unsigned long long) + sizeof(DeviceCounters), stream));
-    DeviceCounters* dc = reinterpret_cast<DeviceCounters*>(d->job_counter + 1);
+    if (!prepare_only) HIP_TRY(hipMemsetAsync(d->job_counter.p, 0, sizeof(unsigned long long) + sizeof(DeviceCounters), stream));
+    DeviceCounters* dc = reinterpret_cast<DeviceCounters*>(d->job_counter.p + 1);
     auto persistent_grid = [&](const void* kernel, size_t lds_bytes, size_t waves_needed, size_t& grid, int block = TRACE_BLOCK) -> int {
         if (lds_bytes > 160 * 1024) { set_last_error("render: queues + traversal stacks do not fit in LDS"); return RTTNW_ERR_UNSUPPORTED; }
         HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
@@ -116,7 +114,8 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
     // stack entries beyond the LDS-resident ones, for every thread of a launch
     auto grow_spill = [&](size_t threads, uint32_t lds_entries = LDS_STACK_ENTRIES) -> int {
         const size_t extra = rc.stack_depth > lds_entries ? rc.stack_depth - lds_entries : 0;
-        return grow(&d->spill, &d->spill_bytes, std::max<size_t>(threads * extra, 1) * sizeof(int32_t));
+        HIP_TRY(d->spill.grow(std::max<size_t>(threads * extra, 1) * sizeof(int32_t)));
+        return 0;
     };
     bool three_steps = false; // the lane-owns-path kernel's instantiation with three node steps per trip (tiny top trees)
     bool no_inst = false;     // the decoupled kernel's instantiation for scenes without instance records
@@ -189,11 +188,11 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
             if (int g = grow_spill(grid * size_t(block))) return g;
             if (n_jobs > 0 && !prepare_only) {
                 R bg0 = R(p->background[0]), bg1 = R(p->background[1]), bg2 = R(p->background[2]), tmin = R(p->t_min);
-                R* part = (R*)d->partial;
-                unsigned long long* jc = d->job_counter;
+                R* part = (R*)d->partial.p;
+                unsigned long long* jc = d->job_counter.p;
                 SceneView<R> view = ds.view;
                 CameraRec<R> camv = camr;
-                int32_t* sp = (int32_t*)d->spill;
+                int32_t* sp = (int32_t*)d->spill.p;
                 void* args[] = {&view, &camv, &rc, &bg0, &bg1, &bg2, &tmin, &part, &jc, &dc, &sp};
                 HIP_TRY(hipLaunchKernel(kernel, dim3(uint32_t(grid)), dim3(block), args, lds_bytes, stream));
             }
@@ -218,30 +217,30 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
             size_t grid = 1;
             if (int g = persistent_grid((const void*)kernel, lds_bytes, (n_jobs + SLOTS_PER_WAVE - 1) / SLOTS_PER_WAVE, grid, wblock)) return g;
             const size_t n_slots = grid * size_t(wblock / 64) * SLOTS_PER_WAVE;
-            if (int g = grow(&d->pool_r, &d->pool_r_bytes, n_slots * PR_COUNT * sizeof(R))) return g;
-            if (int g = grow(&d->pool_u, &d->pool_u_bytes, n_slots * PU_COUNT * sizeof(uint32_t))) return g;
+            HIP_TRY(d->pool_r.grow(n_slots * PR_COUNT * sizeof(R)));
+            HIP_TRY(d->pool_u.grow(n_slots * PU_COUNT * sizeof(uint32_t)));
             if (int g = grow_spill(grid * size_t(wblock), wave_stack_entries<R>())) return g;
             if (n_jobs > 0 && !prepare_only) {
                 hipLaunchKernelGGL(kernel, dim3(uint32_t(grid)), dim3(uint32_t(wblock)), lds_bytes, stream, ds.decoupled_view(), camr, rc, R(p->background[0]),
-                                   R(p->background[1]), R(p->background[2]), R(p->t_min), (R*)d->partial, d->job_counter, dc, (R*)d->pool_r,
-                                   (uint32_t*)d->pool_u, uint32_t(n_slots), (int32_t*)d->spill);
+                                   R(p->background[1]), R(p->background[2]), R(p->t_min), (R*)d->partial.p, d->job_counter.p, dc, (R*)d->pool_r.p,
+                                   (uint32_t*)d->pool_u.p, uint32_t(n_slots), (int32_t*)d->spill.p);
                 HIP_TRY(hipGetLastError());
             }
         }
         return 0;
     };
-    if (stats && !prepare_only) HIP_TRY(hipEventRecord(d->ev0, stream));
+    if (stats && !prepare_only) HIP_TRY(hipEventRecord(d->ev0.get(), stream));
     for (uint32_t c0 = 0; c0 < total_chunks; c0 += per_launch) {
         rc.chunk_base = c0;
         rc.n_chunks = std::min(per_launch, total_chunks - c0);
         const bool first = c0 == 0, last = c0 + per_launch >= total_chunks;
         if (!plan_jobs(rc)) { set_last_error("render: more than 2^32 jobs in a launch"); return RTTNW_ERR_UNSUPPORTED; }
-        if (int g = grow(&d->partial, &d->partial_bytes, std::max<size_t>(size_t(rc.jobs_per_chunk) * rc.n_chunks, 1) * 3 * sizeof(R))) return g;
-        if (!first && !prepare_only) HIP_TRY(hipMemsetAsync(d->job_counter, 0, sizeof(unsigned long long), stream)); // the job counter only: statistics add up
+        HIP_TRY(d->partial.grow(std::max<size_t>(size_t(rc.jobs_per_chunk) * rc.n_chunks, 1) * 3 * sizeof(R)));
+        if (!first && !prepare_only) HIP_TRY(hipMemsetAsync(d->job_counter.p, 0, sizeof(unsigned long long), stream)); // the job counter only: statistics add up
         if (int g = trace_pass()) return g;
         if (prepare_only) continue;
-        if (stats && last) HIP_TRY(hipEventRecord(d->ev1, stream));
-        hipLaunchKernelGGL(resolve_kernel<R>, dim3((L.pixels_per_rank + 255) / 256), dim3(256), 0, stream, (const R*)d->partial,
+        if (stats && last) HIP_TRY(hipEventRecord(d->ev1.get(), stream));
+        hipLaunchKernelGGL(resolve_kernel<R>, dim3((L.pixels_per_rank + 255) / 256), dim3(256), 0, stream, (const R*)d->partial.p,
                            (R*)d_packed, rc, L.pixels_per_rank, uint32_t(first), uint32_t(last), p->spp);
         HIP_TRY(hipGetLastError());
     }
@@ -252,7 +251,7 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
         if (sync_for_stats) {
             HIP_TRY(hipStreamSynchronize(stream));
             float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+            HIP_TRY(hipEventElapsedTime(&ms, d->ev0.get(), d->ev1.get()));
             stats->kernel_ms = ms;
         }
         // samples traced by this rank: pixels of its tiles that lie inside the image
@@ -305,14 +304,11 @@ int probe_path_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_par
     CameraRec<double> cam64;
     make_camera(cam->lookfrom, cam->lookat, cam->view_up, cam->vertical_fov, cam->aspect_ratio, cam->aperture,
                 cam->focus_distance, cam->open_time, cam->close_time, cam64);
-    DevBuf<double> d_out; // released on every exit path
-    DevBuf<int32_t> d_n;
-    if (int r = d_out.upload(std::vector<double>(size_t(max_out) * PROBE_STRIDE + 4, 0.0))) return r;
-    if (int r = d_n.upload(std::vector<int32_t>(1, 0))) { d_out.release(); return r; }
-    struct Release { DevBuf<double>& a; DevBuf<int32_t>& b; ~Release() { a.release(); b.release(); } } release{d_out, d_n};
-    DevBuf<int32_t> d_spill;
-    if (int r = d_spill.upload(std::vector<int32_t>(std::max<size_t>(rc.stack_depth, 1), 0))) { d_out.release(); d_n.release(); return r; }
-    struct Release2 { DevBuf<int32_t>& a; ~Release2() { a.release(); } } release2{d_spill};
+    DevBuf<double> d_out;
+    DevBuf<int32_t> d_n, d_spill;
+    HIP_TRY(d_out.upload(std::vector<double>(size_t(max_out) * PROBE_STRIDE + 4, 0.0)));
+    HIP_TRY(d_n.upload(std::vector<int32_t>(1, 0)));
+    HIP_TRY(d_spill.upload(std::vector<int32_t>(std::max<size_t>(rc.stack_depth, 1), 0)));
     const size_t lds = size_t(LDS_STACK_ENTRIES + 1) * 64 * sizeof(int32_t);
     hipLaunchKernelGGL(probe_path_kernel<R>, dim3(1), dim3(64), lds, 0, ds.view, narrow_camera<R>(cam64), rc, R(p->t_min), px, row,
                        sample, d_out.p, max_out, d_n.p, d_spill.p);

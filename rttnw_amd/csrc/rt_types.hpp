@@ -165,10 +165,7 @@ constexpr uint32_t MAT_HOME_SPHERE_MASK = (1u << MAT_HOME_INST_SHIFT) - 1u, MAT_
 enum : int32_t { MAT_LAMBERTIAN = 0, MAT_METAL = 1, MAT_DIELECTRIC = 2, MAT_DIFFUSE_LIGHT = 3, MAT_ISOTROPIC = 4 };
 // Padded to a power of two (64 B in f64, 32 B in f32): a record never straddles two 128-byte lines.  On spheres_1m (10^6 materials, one L2-miss line
 // per hit at best) 30 % of the 40-byte f64 records did (tests/hostsim/cache_model.hpp: 7.3 -> 5.8 material miss lines per sample).
-#ifndef RT_MAT_PAD
-#define RT_MAT_PAD 1
-#endif
-template <typename R> struct alignas(RT_MAT_PAD ? sizeof(R) * 8 : 8) MaterialRec {
+template <typename R> struct alignas(sizeof(R) * 8) MaterialRec {
     int32_t type;
     int32_t tex;  // texture index, or -1 when the colour below is the whole texture (solid)
     R albedo[3];  // metal albedo / inlined solid colour
