@@ -131,3 +131,50 @@ def probe_path(scene, cam, params, px, row, sample, max_out=64):
     n = b.probe_path(scene.handle, C.byref(cam), C.byref(params), px, row, sample, out.ctypes.data_as(_dp), max_out)
     abi.check(n, b, "rto_probe_path")
     return out[:n]
+
+
+# ---- direct calls of one operation at a given input (the re-anchored per-bounce checker, tests/util.py)
+DBL_MAX = float(np.finfo(np.float64).max)
+SLOT_JITTER_U, SLOT_JITTER_V, SLOT_MEDIUM, SLOT_DIELECTRIC, SLOT_SCATTER = 0, 1, 0, 16, 32
+
+
+def probe_camera_ray(cam, s, t, seed, pixel, sample):
+    """rto_probe_camera_ray: Camera::ray(s, t) with the keyed draws of (seed, pixel, sample) -> [7] origin, direction, time."""
+    out = np.zeros(7)
+    abi.check(binding().probe_camera_ray(C.byref(cam), float(s), float(t), seed, pixel, sample, out.ctypes.data_as(_dp)),
+              binding(), "rto_probe_camera_ray")
+    return out
+
+
+def probe_hit(scene, ray, t_min, seed, pixel, sample, bounce, quirks, t_max=DBL_MAX, world=-1):
+    """rto_probe_hit: world.hit() (or any hittable's) for the ray [7] with the keyed draws of bounce `bounce` -> None on a
+    miss, else [11] t, p(3), normal(3), u, v, front_face, material id."""
+    ray = np.ascontiguousarray(ray, dtype=np.float64)
+    out = np.zeros(11)
+    rc = binding().probe_hit(scene.handle, world, ray.ctypes.data_as(_dp), float(t_min), float(t_max), seed, pixel, sample,
+                             bounce, quirks, out.ctypes.data_as(_dp))
+    abi.check(rc, binding(), "rto_probe_hit")
+    return out if rc == 1 else None
+
+
+def probe_scatter(scene, mat, ray, rec, seed, pixel, sample, bounce):
+    """rto_probe_scatter: Material::scatter + emitted of material `mat` for the ray [7] and the record [10] (t, p, normal, u, v,
+    front_face) -> [13] scattered (0/1), attenuation(3), scattered origin(3), direction(3), emitted(3)."""
+    ray = np.ascontiguousarray(ray, dtype=np.float64)
+    rec = np.ascontiguousarray(rec, dtype=np.float64)
+    out = np.zeros(13)
+    abi.check(binding().probe_scatter(scene.handle, mat, ray.ctypes.data_as(_dp), rec.ctypes.data_as(_dp), seed, pixel, sample,
+                                      bounce, out.ctypes.data_as(_dp)), binding(), "rto_probe_scatter")
+    return out
+
+
+def probe_uniform(seed, pixel, sample, block, slot):
+    return binding().probe_uniform(seed, pixel, sample, block, slot)
+
+
+def probe_word(seed, pixel, sample, block, slot):
+    return binding().probe_word(seed, pixel, sample, block, slot)
+
+
+def probe_schlick(cosine, ri):
+    return binding().probe_schlick(float(cosine), float(ri))

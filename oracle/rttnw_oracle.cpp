@@ -1203,7 +1203,9 @@ int rto_probe_hit(rttnw_scene* s, rttnw_id id, const double* ray, double t_min, 
 // scattered origin(3), direction(3), emitted(3)
 int rto_probe_scatter(rttnw_scene* s, rttnw_id mat, const double* ray, const double* rec_in, uint64_t seed,
                       uint64_t pixel, uint64_t sample, uint32_t bounce, double* out) {
-    auto m = get_mat(s, mat);
+    std::shared_ptr<Material> m = get_mat(s, mat);
+    if (!m)   // a medium's phase function: probe_hit reports the medium's own object id for it (rto_constant_medium)
+        if (auto md = std::dynamic_pointer_cast<ConstantMedium>(get_hit(s, mat))) m = md->phase_function;
     if (!m || !ray || !rec_in || !out) return fail(RTTNW_ERR_INVALID, "probe_scatter: bad arguments");
     Ray r{V3(ray[0], ray[1], ray[2]), V3(ray[3], ray[4], ray[5]), ray[6]};
     HitRecord rec;

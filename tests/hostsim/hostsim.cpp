@@ -233,6 +233,11 @@ static int probe_path_t(rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
         ps.bounce += 1;
         if (ps.bounce >= rc.max_depth) break;
     }
+    // the same sample again through path_step(), as the device probe does: radiance (background black) and bounce count after `out`
+    path_begin(ps, camr, rc, px, row, sample);
+    while (path_step(ps, hs.view, rc, V3<R>(), R(p->t_min), stack, cnt)) {}
+    double* tail = out + size_t(max_out) * 20;
+    tail[0] = ps.radiance.x; tail[1] = ps.radiance.y; tail[2] = ps.radiance.z; tail[3] = double(ps.bounce);
     return int(n);
 }
 
