@@ -86,6 +86,16 @@ pub struct rttnw_stats {
     pub reserved: u32,
 }
 
+/// The stopping rule of `rttnw_render_adaptive` (include/rttnw_hip.h states the contract).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rttnw_adaptive {
+    pub pass_spp: u32,
+    pub reserved0: u32,
+    pub rel_error: f64,
+    pub abs_error: f64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct rttnw_tile_layout {
@@ -170,6 +180,7 @@ extern "C" {
     pub fn rttnw_tile_layout_get(width: u32, height: u32, world: u32, out: *mut rttnw_tile_layout) -> c_int;
     pub fn rttnw_render(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_render_multi(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, ngpu: u32, device_ids: *const i32, out_linear_rgb: *mut f64, out_rgba8: *mut u8, stats: *mut rttnw_stats) -> c_int;
+    pub fn rttnw_render_adaptive(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_spp: *mut u32, out_stderr_rgb: *mut f64, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_render_tiles_device(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, d_packed: *mut c_void, hip_stream: *mut c_void, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_untile_device(width: u32, height: u32, world: u32, precision: u32, d_gathered: *const c_void, d_linear_rgb: *mut c_void, d_rgba8: *mut u8, hip_stream: *mut c_void) -> c_int;
     // ---- introspection

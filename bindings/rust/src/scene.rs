@@ -147,6 +147,17 @@ impl Scene {
         ok(unsafe { ffi::rttnw_render(self.raw, cam, p, ptr::null_mut(), rgba.as_mut_ptr(), &mut stats) })?;
         Ok((rgba, stats))
     }
+    /// Adaptive sampling on one GPU: passes of `a.pass_spp` samples until every pixel meets `a`'s noise bound or has `p.spp` samples.
+    /// Returns (RGBA8, samples per pixel, standard error of each pixel's mean per channel, stats), row-major, top row first.
+    pub fn render_adaptive(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, a: &ffi::rttnw_adaptive) -> Result<(Vec<u8>, Vec<u32>, Vec<f64>, ffi::rttnw_stats)> {
+        let n = p.width as usize * p.height as usize;
+        let mut rgba = vec![0u8; n * 4];
+        let mut spp = vec![0u32; n];
+        let mut stderr = vec![0f64; n * 3];
+        let mut stats = ffi::rttnw_stats::default();
+        ok(unsafe { ffi::rttnw_render_adaptive(self.raw, cam, p, a, ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), &mut stats) })?;
+        Ok((rgba, spp, stderr, stats))
+    }
     /// The same image from the GPUs `devices` of this node (tile partition + RCCL gather inside the library).
     pub fn render_multi(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, devices: &[i32]) -> Result<(Vec<u8>, Vec<ffi::rttnw_stats>)> {
         let mut rgba = vec![0u8; p.width as usize * p.height as usize * 4];

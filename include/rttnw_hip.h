@@ -39,7 +39,8 @@ extern "C" {
 
 #define RTTNW_ABI_VERSION 3 /* 2: 4-wide node records (n_nodes, debug_scene_nodes4), rttnw_render_multi
                              * 3: RTTNW_F64_STRICT, rttnw_shutdown, RTTNW_BVH_AUTO (the default builder), rttnw_stats.reserved is a bit mask
-                             *    (below), validate() rejects t_min < 0 */
+                             *    (below), validate() rejects t_min < 0
+                             * (rttnw_render_adaptive came later, without a version bump: a caller detects it by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -245,6 +246,41 @@ int rttnw_tile_layout_get(uint32_t width, uint32_t height, uint32_t world, rttnw
  * (main.rs:219-225).  Requires tile_world == 1. */
 int rttnw_render(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p,
                  double* out_linear_rgb, uint8_t* out_rgba8, rttnw_stats* stats);
+
+/* Adaptive sampling: `render()` for one GPU that stops sampling a pixel once its mean is known well enough.
+ *
+ * Samples.  Pixel q gets samples [sample_begin, sample_begin + n_q) with n_q a multiple of B = a->pass_spp and n_q <= p->spp (the cap).
+ *   Pass k traces samples [sample_begin + kB, sample_begin + (k+1)B) of every pixel still active, with the chunk schedule of a render
+ *   with spp = B and the caller's spp_chunk: exactly the jobs rttnw_render(spp = B, sample_begin = sample_begin + kB) runs for that pixel.
+ *   The pixel's running sum is the chain of the passes' chunk-sum chains, in pass order, in the kernels' arithmetic type; its value is
+ *   that sum / n_q.  So a pixel that stops after pass 0 is BIT-IDENTICAL to rttnw_render(spp = B), linear value and RGBA8 alike.
+ * Noise estimate.  Over the chunk means m_c (n_c samples each) of all chunks of all passes so far, M2 = sum_c n_c (m_c - mu)^2 is folded
+ *   with the weighted incremental (West) update in chunk order, in double for every precision, no product fused into an add (every build folds to the same bits); the standard error of
+ *   the pixel's mean is sqrt(M2 / ((K - 1) N)), K chunks, N = n_q samples — +inf with K < 2.  Unbiased, the samples being i.i.d. per
+ *   pixel; with spp_chunk = 1 it is the textbook sample standard error.
+ * Stopping.  After each pass a pixel stays active unless n_q == p->spp or, for each of r, g, b,
+ *       stderr <= abs_error + rel_error * value            (linear radiance, value = the pixel's reported mean)
+ *   The decision depends on the pixel's own samples only — not on its neighbours, its tile, the launch split (RTTNW_CHUNK_SUM_BUDGET) or
+ *   the order jobs are handed out in.  Refinement passes trace the 2x2 pixel blocks that hold an active pixel (a converged pixel of
+ *   such a block traces nothing).
+ * Padding.  A job group spans 16 chunks of a 2x2 block: with the default schedule (spp_chunk = 0) a pass of B = 32 has 11 chunks,
+ *   padded to 16; B = 64 with spp_chunk = 4 is exactly 16 (the Python driver takes spp_chunk = max(1, B / 16) when
+ *   given 0).
+ * Outputs (each optional; row-major, top row first like rttnw_render): out_linear_rgb w*h*3, out_rgba8 w*h*4, out_spp w*h sample counts
+ *   n_q, out_stderr_rgb w*h*3 standard errors of the pixel's mean.  `stats`: samples = sum_q n_q, kernel_ms = device time of all passes
+ *   (the per-pass list building and one small copy to the host included), reserved = the kernel form, as for rttnw_render.  Blocking.
+ * Refusals, before the device is touched: RTTNW_ERR_INVALID for pass_spp == 0, p->spp not a positive multiple of pass_spp, a negative
+ *   or NaN tolerance, reserved0 != 0 or tile_world != 1; RTTNW_ERR_UNSUPPORTED for collect_counters != 0. */
+struct rttnw_adaptive {
+    uint32_t pass_spp;  /* B: samples per pixel per pass; p->spp (the cap) must be a positive multiple of B */
+    uint32_t reserved0; /* must be 0 */
+    double rel_error;   /* a pixel stops after the first pass at which, for each of r, g, b, */
+    double abs_error;   /*   stderr <= abs_error + rel_error * mean   (linear radiance) */
+};
+typedef struct rttnw_adaptive rttnw_adaptive;
+int rttnw_render_adaptive(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
+                          double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb,
+                          rttnw_stats* stats);
 
 /* `render()` on the GPUs of ONE NODE, in one call from one host thread ("library owns its HIP
  * streams / RCCL comms"): the framebuffer's 8x8 tiles are interleaved over `ngpu` ranks, rank r traces its tiles on

@@ -2,7 +2,9 @@
 
 One positional argument, the scene number 1..9 with the reference's per-scene defaults (size, spp, camera:
 main.rs:66-183); writes `image.png` into the current directory (main.rs:231) and prints the wall time.
-Optional extras (not in the reference): --spp, --width, --precision f32|f64, --out, --seed, --passes.
+Optional extras (not in the reference): --spp, --width, --precision f32|f64, --out, --seed, --passes, and adaptive sampling:
+--noise R [--abs-noise A] [--pass-spp B] [--spp-map FILE] stops sampling a pixel once the standard error of its mean is at most
+A + R * mean in every channel, --spp being the cap.
 """
 import argparse
 import sys
@@ -33,6 +35,10 @@ def main(argv=None):
     ap.add_argument("--out", default="image.png")
     ap.add_argument("--passes", type=int, default=1, help="render in this many passes over disjoint sample ranges, "
                     "rewriting the image after each (progressive)")
+    ap.add_argument("--noise", type=float, default=None, help="adaptive sampling: relative noise bound (standard error / mean); --spp is the cap")
+    ap.add_argument("--abs-noise", type=float, default=0.0, help="adaptive sampling: absolute noise bound added to the relative one")
+    ap.add_argument("--pass-spp", type=int, default=64, help="adaptive sampling: samples per pixel per pass (the cap must be a multiple)")
+    ap.add_argument("--spp-map", default=None, help="adaptive sampling: also write a grey-scale PNG of samples / cap")
     try:
         args = ap.parse_args(argv)
     except SystemExit:
@@ -59,6 +65,23 @@ def main(argv=None):
     cam.aspect_ratio = setup.width / setup.height
     p = make_params(w, h, args.spp or setup.spp, background=tuple(setup.background), seed=args.seed,
                     precision={"f32": abi.F32, "f64": abi.F64, "f64strict": abi.F64_STRICT}[args.precision])
+    if args.noise is not None:
+        if args.pass_spp < 1:
+            print("--pass-spp must be at least 1", file=sys.stderr)
+            return 1
+        if p.spp % args.pass_spp:   # the cap is a whole number of passes: the scene's default spp (200 for scene 7) rounds up
+            cap = (p.spp + args.pass_spp - 1) // args.pass_spp * args.pass_spp
+            print("cap %d spp rounded up to %d, a multiple of --pass-spp %d" % (p.spp, cap, args.pass_spp))
+            p.spp = cap
+        _, rgba, spp_map, _, st = render.render_adaptive(sc, cam, p, args.pass_spp, args.noise, args.abs_noise)
+        Image.fromarray(np.ascontiguousarray(rgba), "RGBA").save(args.out)
+        if args.spp_map:
+            grey = np.minimum(spp_map.astype(np.float64) / p.spp * 255.0 + 0.5, 255.0).astype(np.uint8)
+            Image.fromarray(grey, "L").save(args.spp_map)
+        full = w * h * p.spp
+        print("%.3fs (adaptive: %d samples traced of %d = %dx%dx%d, %.1f %%; kernels %.1f ms)"
+              % (time.time() - t0, st.samples, full, w, h, p.spp, 100.0 * st.samples / full, st.kernel_ms))
+        return 0
     if args.passes > 1:
         def show(k, linear):
             Image.fromarray(render.quantise_rgba8(linear), "RGBA").save(args.out)

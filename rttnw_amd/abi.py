@@ -49,6 +49,11 @@ class Stats(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class Adaptive(C.Structure):
+    """`rttnw_adaptive` — the stopping rule of `rttnw_render_adaptive`."""
+    _fields_ = [("pass_spp", C.c_uint32), ("reserved0", C.c_uint32), ("rel_error", C.c_double), ("abs_error", C.c_double)]
+
+
 class TileLayout(C.Structure):
     _fields_ = [("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32), ("n_tiles", C.c_uint32),
                 ("tiles_per_rank", C.c_uint32), ("pixels_per_rank", C.c_uint32)]
@@ -98,6 +103,8 @@ PRODUCT_FUNCS = [
                          C.POINTER(Stats)]),
     ("render_multi", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_uint32, C.POINTER(C.c_int32), C.c_void_p,
                                C.c_void_p, C.c_void_p]),
+    ("render_adaptive", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("render_tiles_device", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_void_p,
                                       C.c_void_p, C.POINTER(Stats)]),
     ("untile_device", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

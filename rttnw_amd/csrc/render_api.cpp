@@ -267,6 +267,40 @@ int rttnw_render(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_param
     return RTTNW_OK;
 }
 
+int rttnw_render_adaptive(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, double* out_linear_rgb,
+                          uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, rttnw_stats* stats) {
+    // the adaptive arguments first: their refusals need no device (nor a committed scene)
+    if (!p || !a) { rt::set_last_error("render_adaptive: NULL argument"); return RTTNW_ERR_INVALID; }
+    if (a->pass_spp == 0) { rt::set_last_error("render_adaptive: pass_spp is 0"); return RTTNW_ERR_INVALID; }
+    if (p->spp == 0 || p->spp % a->pass_spp != 0) { rt::set_last_error("render_adaptive: spp (the cap) must be a positive multiple of pass_spp"); return RTTNW_ERR_INVALID; }
+    if (!(a->rel_error >= 0.0) || !(a->abs_error >= 0.0)) { rt::set_last_error("render_adaptive: rel_error and abs_error must be >= 0 (and not NaN)"); return RTTNW_ERR_INVALID; }
+    if (a->reserved0 != 0) { rt::set_last_error("render_adaptive: reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (p->tile_world != 1) { rt::set_last_error("render_adaptive: host-output form needs tile_world == 1"); return RTTNW_ERR_INVALID; }
+    if (p->collect_counters != 0) { rt::set_last_error("render_adaptive: collect_counters is not supported"); return RTTNW_ERR_UNSUPPORTED; }
+    if (int rc = rt::validate(s, cam, p)) return rc;
+    rt::DeviceState* d = s->device;
+    int rc = p->precision == RTTNW_F32          ? rt::render_adaptive_t<float>(s, cam, p, a, stats)
+             : p->precision == RTTNW_F64_STRICT ? rt::ieee_strict::render_adaptive_t<double>(s, cam, p, a, stats)
+                                                : rt::render_adaptive_t<double>(s, cam, p, a, stats);
+    if (rc) return rc;
+    const size_t npx = size_t(p->width) * p->height;
+    hipError_t e = hipSuccess;
+    if (out_rgba8) e = hipMemcpy(out_rgba8, d->rgba.p, npx * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_spp) e = hipMemcpy(out_spp, d->ad_spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_stderr_rgb) e = hipMemcpy(out_stderr_rgb, d->ad_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_linear_rgb) {
+        if (p->precision != RTTNW_F32) {
+            e = hipMemcpy(out_linear_rgb, d->linear.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        } else {
+            std::vector<float> tmp(npx * 3);
+            e = hipMemcpy(tmp.data(), d->linear.p, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
+            for (size_t i = 0; i < npx * 3; ++i) out_linear_rgb[i] = double(tmp[i]);
+        }
+    }
+    if (e != hipSuccess) { rt::set_last_error(std::string("render_adaptive: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
+    return RTTNW_OK;
+}
+
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 #pragma once
 #include "../../include/rttnw_hip.h"
 #include "rt_core.hpp"
+#include "adaptive.hpp"
 #include "scene_handle.hpp"
 #include "device_mem.hpp"
 
@@ -265,6 +266,19 @@ struct DeviceState {
     DevBuf<uint8_t> gathered;       // root device: every rank's packed tiles
     // scratch for the blocking host-output render()
     DevBuf<uint8_t> packed, linear, rgba;
+    // rttnw_render_adaptive: per packed pixel the noise state (adaptive.hpp) and the active bit, the block list and its scan, the maps
+    DevBuf<uint8_t> ad_state, ad_active, ad_quads, ad_scan, ad_spp, ad_stderr;
+};
+// What render_tiles_t needs to run one pass of rttnw_render_adaptive (render_tiles.hpp render_adaptive_t): the adaptive resolve step in place
+// of resolve_kernel and, for a refinement pass, the active-list instantiation of the scene's kernel over `quads`.
+struct AdaptivePass {
+    const uint32_t* quads = nullptr; // nullptr: pass 0, every pixel of the rank in the render's own job numbering
+    uint32_t n_quads = 0;
+    bool first = true;               // pass 0: the running sums and the noise state start here
+    AdaptivePixel* state = nullptr;
+    uint8_t* active = nullptr;
+    uint32_t cap = 0;
+    double rel_error = 0, abs_error = 0;
 };
 void debug_print_sched(const DeviceCounters& hc, bool plain, uint32_t profile, uint64_t samples); // RTTNW_DEBUG_SCHED=1 only (debug_sched.cpp)
 int device_state_create(DeviceState*& out, std::string& err);
@@ -294,14 +308,19 @@ int validate(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params*
 inline namespace RT_ARITH_NS {
 template <typename R>
 int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
-                   rttnw_stats* stats, bool sync_for_stats = true, bool prepare_only = false);
+                   rttnw_stats* stats, bool sync_for_stats = true, bool prepare_only = false, const AdaptivePass* adaptive = nullptr);
 template <typename R>
 int probe_path_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t px, uint32_t row, uint32_t sample,
                  double* out, uint32_t max_out);
 template <typename R>
 int untile_launch(uint32_t width, uint32_t height, uint32_t world, const void* d_gathered, void* d_linear_rgb, uint8_t* d_rgba8, hipStream_t stream);
-extern template int render_tiles_t<float>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool);
-extern template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool);
+// rttnw_render_adaptive's device half: every pass, then the image (d->linear, d->rgba) and the maps (d->ad_spp, d->ad_stderr) on the device
+template <typename R>
+int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, rttnw_stats* stats);
+extern template int render_adaptive_t<float>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
+extern template int render_adaptive_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
+extern template int render_tiles_t<float>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const AdaptivePass*);
+extern template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const AdaptivePass*);
 extern template int probe_path_t<float>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
 extern template int probe_path_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
 extern template int untile_launch<float>(uint32_t, uint32_t, uint32_t, const void*, void*, uint8_t*, hipStream_t);
@@ -313,12 +332,15 @@ extern template int untile_launch<double>(uint32_t, uint32_t, uint32_t, const vo
 namespace ieee_strict {
 template <typename R>
 int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
-                   rttnw_stats* stats, bool sync_for_stats, bool prepare_only);
+                   rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const AdaptivePass* adaptive = nullptr);
 template <typename R>
 int probe_path_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t px, uint32_t row, uint32_t sample,
                  double* out, uint32_t max_out);
-extern template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool);
+extern template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const AdaptivePass*);
 extern template int probe_path_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
+template <typename R>
+int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, rttnw_stats* stats);
+extern template int render_adaptive_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
 } // namespace ieee_strict
 #endif
 

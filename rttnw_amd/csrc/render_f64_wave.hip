@@ -10,5 +10,10 @@ inline namespace RT_ARITH_NS {
                                                                   double*, unsigned long long*, DeviceCounters*, double*, uint32_t*, uint32_t, int32_t*);
 RT_WAVE_INST(false, SHAPES_FAST) RT_WAVE_INST(false, SHAPES_GENERAL) RT_WAVE_INST(false, SHAPES_NONE) RT_WAVE_INST(false, SHAPES_NONE_NT) RT_WAVE_INST(true, SHAPES_FAST) RT_WAVE_INST(true, SHAPES_GENERAL)
 #undef RT_WAVE_INST
+#define RT_WAVE_INST_LIST(GENERAL)                                                                                                                    \
+    template __global__ void trace_kernel<double, false, GENERAL, true>(SceneView<double>, CameraRec<double>, RenderConsts, double, double, double, \
+                                                                        double, double*, unsigned long long*, DeviceCounters*, double*, uint32_t*, uint32_t, int32_t*);
+RT_WAVE_INST_LIST(SHAPES_FAST) RT_WAVE_INST_LIST(SHAPES_GENERAL) RT_WAVE_INST_LIST(SHAPES_NONE) RT_WAVE_INST_LIST(SHAPES_NONE_NT)
+#undef RT_WAVE_INST_LIST
 } // namespace RT_ARITH_NS
 } // namespace rt

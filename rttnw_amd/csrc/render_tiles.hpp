@@ -9,12 +9,46 @@
 namespace rt {
 inline namespace RT_ARITH_NS {
 
+// The lane-owns-path kernel for a scene: its instantiation by what the scene holds (render_tiles_t says why each exists).  LIST: the
+// active-list form of rttnw_render_adaptive's refinement passes — non-counting forms only.
+template <typename R, bool LIST>
+const void* plain_kernel_of(bool count, bool gen, bool want_lds, bool lds_no_inst, bool instance_leaves, bool no_time, bool tiny_tree) {
+    constexpr int LDS_BLOCK = sizeof(R) == 4 ? 1024 : RT_F64_BLOCK;
+    constexpr int N = RT_NODE_STEPS, T = RT_TINY_TREE_STEPS;
+    if constexpr (!LIST) {
+        if (count && !tiny_tree && !lds_no_inst)
+            return want_lds ? (gen ? (const void*)trace_kernel_plain<R, true, LDS_BLOCK, true, true> : (const void*)trace_kernel_plain<R, true, LDS_BLOCK, true, false>)
+                            : (gen ? (const void*)trace_kernel_plain<R, true, TRACE_BLOCK, false, true> : (const void*)trace_kernel_plain<R, true, TRACE_BLOCK, false, false>);
+    } else if (count) {
+        return nullptr;
+    }
+    return lds_no_inst && !instance_leaves && no_time ? (tiny_tree ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_NONE_NT, T, LIST> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_NONE_NT, N, LIST>) :
+           lds_no_inst && !instance_leaves ? (tiny_tree ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_NONE, T, LIST> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_NONE, N, LIST>) :
+           lds_no_inst && no_time ? (tiny_tree ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_SINGLE_NT, T, LIST> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_SINGLE_NT, N, LIST>) :
+           lds_no_inst ? (tiny_tree ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_SINGLE, T, LIST> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_SINGLE, N, LIST>) :
+           tiny_tree ? (gen ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_GENERAL, T, LIST> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_FAST, T, LIST>) :
+           want_lds ? (gen ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, true, N, LIST> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, false, N, LIST>)
+                    : (gen ? (const void*)trace_kernel_plain<R, false, TRACE_BLOCK, false, true, N, LIST> : (const void*)trace_kernel_plain<R, false, TRACE_BLOCK, false, false, N, LIST>);
+}
+// ... and the decoupled kernel's
+template <typename R, bool LIST>
+auto wave_kernel_of(bool count, bool gen, bool no_inst, bool no_time) {
+    using K = decltype(&trace_kernel<R, false, SHAPES_FAST>);
+    if constexpr (!LIST) {
+        if (count) return gen ? (K)trace_kernel<R, true, SHAPES_GENERAL> : (K)trace_kernel<R, true, SHAPES_FAST>;
+    } else if (count) {
+        return (K) nullptr;
+    }
+    return gen ? (K)trace_kernel<R, false, SHAPES_GENERAL, LIST>
+               : (no_inst ? (no_time ? (K)trace_kernel<R, false, SHAPES_NONE_NT, LIST> : (K)trace_kernel<R, false, SHAPES_NONE, LIST>) : (K)trace_kernel<R, false, SHAPES_FAST, LIST>);
+}
+
 // prepare_only: upload the scene on first use and grow every workspace buffer this render will need (blocking
 // allocations, copies and frees), launch nothing — rttnw_render_multi does that for ALL its ranks before the first launch, so
 // that no allocation (a device-wide synchronisation) sits between two ranks' kernels.
 template <typename R>
 int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
-                   rttnw_stats* stats, bool sync_for_stats, bool prepare_only) {
+                   rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const AdaptivePass* ad) {
     HIP_TRY(hipSetDevice(d->device));
     const FlatScene* flat_p = &s->flat;
     DeviceScene<R>* ds_p = &scene_of<R>(d);
@@ -46,14 +80,17 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
     // chain, so the image does not depend on the split).
     plan_chunks(rc, p->spp, p->spp_chunk);
     const uint32_t total_chunks = rc.n_chunks;
+    // (an adaptive refinement pass keeps the sums of its listed blocks only: 4 per block and chunk)
+    const bool listed = ad && ad->quads;
+    const uint64_t sum_pixels = listed ? uint64_t(ad->n_quads) * 4 : uint64_t(rc.my_tiles) * 64;
     // (if the device cannot give the workspace — other tenants of its memory — the budget is halved, down to 1 GiB: more launches, same image)
     // The budget that worked is REMEMBERED (d->chunk_budget): a later render does not retry the allocation that failed, and the
     // buffer in hand is released only once a larger one has been obtained — or, if none can be, simply used: the launch split
     // then follows ITS size.
     uint32_t per_launch = 0;
     for (uint64_t budget = d->chunk_budget;; budget /= 2) {
-        per_launch = launch_chunks(uint64_t(rc.my_tiles) * 64, 3 * sizeof(R), total_chunks, budget);
-        const size_t want = std::max<size_t>(size_t(rc.my_tiles) * 64 * std::min(per_launch, total_chunks), 1) * 3 * sizeof(R);
+        per_launch = launch_chunks(sum_pixels, 3 * sizeof(R), total_chunks, budget);
+        const size_t want = std::max<size_t>(size_t(sum_pixels) * std::min(per_launch, total_chunks), 1) * 3 * sizeof(R);
         if (d->partial.n >= want && d->partial.p) break;
         DevBuf<uint8_t> bigger;
         const hipError_t e = bigger.grow(want);
@@ -63,10 +100,10 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
             break;
         }
         (void)hipGetLastError(); // clear the sticky out-of-memory
-        const size_t one_group = size_t(rc.my_tiles) * 64 * std::min<uint32_t>(16u, total_chunks) * 3 * sizeof(R);
+        const size_t one_group = size_t(sum_pixels) * std::min<uint32_t>(16u, total_chunks) * 3 * sizeof(R);
         // (not under RTTNW_CHUNK_SUM_BUDGET: launch_chunks() would size the launches by the environment's budget again, not by the buffer in hand)
         if (d->partial.p && d->partial.n >= one_group && !getenv("RTTNW_CHUNK_SUM_BUDGET")) { // no larger buffer to be had: split the render by the one in hand
-            per_launch = launch_chunks(uint64_t(rc.my_tiles) * 64, 3 * sizeof(R), total_chunks, d->partial.n);
+            per_launch = launch_chunks(sum_pixels, 3 * sizeof(R), total_chunks, d->partial.n);
             if (!getenv("RTTNW_CHUNK_SUM_BUDGET")) d->chunk_budget = std::max<uint64_t>(d->partial.n, 1ull << 30);
             break;
         }
@@ -167,16 +204,8 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
             const bool tiny_tree = three_steps && !count; // (the counting variant's tallied loop is written for two: same steps per lane, same counters)
             // (... and, of those two, the LEAN flavour where the scene holds no moving sphere, no medium and only solid colours: rt_core.hpp SHAPES_*_NT)
             no_time = flat.lean();
-            const void* kernel =
-                lds_no_inst && !flat.has_instance_leaves && no_time ? (tiny_tree ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_NONE_NT, RT_TINY_TREE_STEPS> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_NONE_NT>) :
-                lds_no_inst && !flat.has_instance_leaves ? (tiny_tree ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_NONE, RT_TINY_TREE_STEPS> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_NONE>) :
-                lds_no_inst && no_time ? (tiny_tree ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_SINGLE_NT, RT_TINY_TREE_STEPS> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_SINGLE_NT>) :
-                lds_no_inst ? (tiny_tree ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_SINGLE, RT_TINY_TREE_STEPS> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_SINGLE>) :
-                tiny_tree ? (gen ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_GENERAL, RT_TINY_TREE_STEPS> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, SHAPES_FAST, RT_TINY_TREE_STEPS>) :
-                want_lds ? (count ? (gen ? (const void*)trace_kernel_plain<R, true, LDS_BLOCK, true, true> : (const void*)trace_kernel_plain<R, true, LDS_BLOCK, true, false>)
-                                  : (gen ? (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, true> : (const void*)trace_kernel_plain<R, false, LDS_BLOCK, true, false>))
-                         : (count ? (gen ? (const void*)trace_kernel_plain<R, true, TRACE_BLOCK, false, true> : (const void*)trace_kernel_plain<R, true, TRACE_BLOCK, false, false>)
-                                  : (gen ? (const void*)trace_kernel_plain<R, false, TRACE_BLOCK, false, true> : (const void*)trace_kernel_plain<R, false, TRACE_BLOCK, false, false>));
+            const void* kernel = listed ? plain_kernel_of<R, true>(count, gen, want_lds, lds_no_inst, flat.has_instance_leaves, no_time, tiny_tree)
+                                        : plain_kernel_of<R, false>(count, gen, want_lds, lds_no_inst, flat.has_instance_leaves, no_time, tiny_tree);
             const size_t lds_bytes = lds_form_bytes(want_lds ? n4 : 0u, rc.stack_depth, uint32_t(block)) + perlin_bytes;
             if (lds_bytes > 160 * 1024) { set_last_error("render: traversal stacks do not fit in LDS"); return RTTNW_ERR_UNSUPPORTED; }
             HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
@@ -193,7 +222,8 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
                 SceneView<R> view = ds.view;
                 CameraRec<R> camv = camr;
                 int32_t* sp = (int32_t*)d->spill.p;
-                void* args[] = {&view, &camv, &rc, &bg0, &bg1, &bg2, &tmin, &part, &jc, &dc, &sp};
+                DeviceCounters* dcl = listed ? (DeviceCounters*)ad->quads : dc; // (the active-list form takes its list in this argument)
+                void* args[] = {&view, &camv, &rc, &bg0, &bg1, &bg2, &tmin, &part, &jc, &dcl, &sp};
                 HIP_TRY(hipLaunchKernel(kernel, dim3(uint32_t(grid)), dim3(block), args, lds_bytes, stream));
             }
         } else {
@@ -204,9 +234,7 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
             // (a scene without any instance record takes the instantiation whose walk never changes frames, rt_core.hpp SHAPES_NONE)
             no_inst = !gen && !count && !flat.has_instance_leaves;
             no_time = flat.lean();
-            auto kernel = count ? (gen ? trace_kernel<R, true, SHAPES_GENERAL> : trace_kernel<R, true, SHAPES_FAST>)
-                                : (gen ? trace_kernel<R, false, SHAPES_GENERAL>
-                                       : (no_inst ? (no_time ? trace_kernel<R, false, SHAPES_NONE_NT> : trace_kernel<R, false, SHAPES_NONE>) : trace_kernel<R, false, SHAPES_FAST>));
+            auto kernel = listed ? wave_kernel_of<R, true>(count, gen, no_inst, no_time) : wave_kernel_of<R, false>(count, gen, no_inst, no_time);
             // (the LEAN flavour: ONE block per CU of as many waves as its LDS holds — 13 in f64, where three 4-wave blocks make 12; RTTNW_WAVE_BLOCK=<threads>: experiments)
             const bool lean_kernel = !count && !gen && no_inst && no_time;
             const uint32_t wave_bytes = wave_lds_bytes<R>(rc.stack_depth, lean_kernel);
@@ -222,7 +250,8 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
             if (int g = grow_spill(grid * size_t(wblock), wave_stack_entries<R>())) return g;
             if (n_jobs > 0 && !prepare_only) {
                 hipLaunchKernelGGL(kernel, dim3(uint32_t(grid)), dim3(uint32_t(wblock)), lds_bytes, stream, ds.decoupled_view(), camr, rc, R(p->background[0]),
-                                   R(p->background[1]), R(p->background[2]), R(p->t_min), (R*)d->partial.p, d->job_counter.p, dc, (R*)d->pool_r.p,
+                                   R(p->background[1]), R(p->background[2]), R(p->t_min), (R*)d->partial.p, d->job_counter.p,
+                                   listed ? (DeviceCounters*)ad->quads : dc, (R*)d->pool_r.p,
                                    (uint32_t*)d->pool_u.p, uint32_t(n_slots), (int32_t*)d->spill.p);
                 HIP_TRY(hipGetLastError());
             }
@@ -234,14 +263,19 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
         rc.chunk_base = c0;
         rc.n_chunks = std::min(per_launch, total_chunks - c0);
         const bool first = c0 == 0, last = c0 + per_launch >= total_chunks;
-        if (!plan_jobs(rc)) { set_last_error("render: more than 2^32 jobs in a launch"); return RTTNW_ERR_UNSUPPORTED; }
+        if (!(listed ? plan_jobs_list(rc, ad->n_quads) : plan_jobs(rc))) { set_last_error("render: more than 2^32 jobs in a launch"); return RTTNW_ERR_UNSUPPORTED; }
         HIP_TRY(d->partial.grow(std::max<size_t>(size_t(rc.jobs_per_chunk) * rc.n_chunks, 1) * 3 * sizeof(R)));
         if (!first && !prepare_only) HIP_TRY(hipMemsetAsync(d->job_counter.p, 0, sizeof(unsigned long long), stream)); // the job counter only: statistics add up
         if (int g = trace_pass()) return g;
         if (prepare_only) continue;
         if (stats && last) HIP_TRY(hipEventRecord(d->ev1.get(), stream));
-        hipLaunchKernelGGL(resolve_kernel<R>, dim3((L.pixels_per_rank + 255) / 256), dim3(256), 0, stream, (const R*)d->partial.p,
-                           (R*)d_packed, rc, L.pixels_per_rank, uint32_t(first), uint32_t(last), p->spp);
+        if (ad)
+            hipLaunchKernelGGL(adaptive_resolve_kernel<R>, dim3((rc.jobs_per_chunk + 255) / 256), dim3(256), 0, stream, (const R*)d->partial.p, (R*)d_packed,
+                               ad->state, ad->active, ad->quads, rc, rc.jobs_per_chunk, uint32_t(first && ad->first), uint32_t(last), ad->cap, ad->rel_error,
+                               ad->abs_error);
+        else
+            hipLaunchKernelGGL(resolve_kernel<R>, dim3((L.pixels_per_rank + 255) / 256), dim3(256), 0, stream, (const R*)d->partial.p,
+                               (R*)d_packed, rc, L.pixels_per_rank, uint32_t(first), uint32_t(last), p->spp);
         HIP_TRY(hipGetLastError());
     }
     if (prepare_only) return RTTNW_OK;
@@ -332,12 +366,86 @@ int untile_launch(uint32_t width, uint32_t height, uint32_t world, const void* d
     return RTTNW_OK;
 }
 
+// rttnw_render_adaptive (include/rttnw_hip.h has the contract, DESIGN.md "Adaptive sampling" the why).  Pass k traces samples
+// [sample_begin + kB, sample_begin + (k+1)B) of every active pixel with render_tiles_t's own kernel choice, chunk schedule and launch split:
+// pass 0 over every pixel, in the plain render's job numbering; pass k > 0 over the list of 2x2 blocks that hold an active pixel, built on the
+// device after each pass (one 8-byte copy to the host per pass: the list's length sizes the next pass).  Arguments were checked by the caller.
+template <typename R>
+int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, rttnw_stats* stats) {
+    DeviceState* d = s->device;
+    HIP_TRY(hipSetDevice(d->device));
+    rttnw_tile_layout L;
+    fill_layout(p->width, p->height, 1, L);
+    const size_t npx = size_t(p->width) * p->height;
+    const uint32_t n_blocks = L.n_tiles * 16u, n_waves = (n_blocks + 63u) / 64u;
+    HIP_TRY(d->packed.grow(size_t(L.pixels_per_rank) * 4 * sizeof(R)));
+    HIP_TRY(d->linear.grow(npx * 3 * sizeof(R)));
+    HIP_TRY(d->rgba.grow(npx * 4));
+    HIP_TRY(d->ad_state.grow(size_t(L.pixels_per_rank) * sizeof(AdaptivePixel)));
+    HIP_TRY(d->ad_active.grow(L.pixels_per_rank));
+    HIP_TRY(d->ad_quads.grow(size_t(n_blocks) * sizeof(uint32_t)));
+    HIP_TRY(d->ad_scan.grow((size_t(n_waves) * 3 + 2) * sizeof(uint32_t)));
+    HIP_TRY(d->ad_spp.grow(npx * sizeof(uint32_t)));
+    HIP_TRY(d->ad_stderr.grow(npx * 3 * sizeof(double)));
+    uint32_t* wave_counts = (uint32_t*)d->ad_scan.p;
+    uint32_t* wave_base = wave_counts + 2 * size_t(n_waves);
+    uint32_t* totals = wave_base + n_waves;
+    const uint32_t* quads = (const uint32_t*)d->ad_quads.p;
+
+    AdaptivePass ad;
+    ad.state = (AdaptivePixel*)d->ad_state.p;
+    ad.active = d->ad_active.p;
+    ad.cap = p->spp;
+    ad.rel_error = a->rel_error;
+    ad.abs_error = a->abs_error;
+    rttnw_params pass = *p;
+    pass.spp = a->pass_spp;
+    const hipStream_t stream = nullptr;
+    const uint32_t n_passes = p->spp / a->pass_spp;
+    uint64_t samples = uint64_t(npx) * a->pass_spp;
+    for (uint32_t k = 0; k < n_passes; ++k) {
+        pass.sample_begin = p->sample_begin + k * a->pass_spp;
+        if (k > 0) {
+            const uint32_t grid = (n_blocks + 255u) / 256u;
+            hipLaunchKernelGGL(quad_count_kernel<R>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)ad.active, n_blocks, wave_counts);
+            hipLaunchKernelGGL(quad_scan_kernel<R>, dim3(1), dim3(QUAD_SCAN_BLOCK), 0, stream, (const uint32_t*)wave_counts, wave_base, n_waves, totals);
+            hipLaunchKernelGGL(quad_list_kernel<R>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)ad.active, n_blocks, (const uint32_t*)wave_base,
+                               (uint32_t*)quads);
+            HIP_TRY(hipGetLastError());
+            uint32_t count[2] = {0, 0}; // listed blocks, active pixels
+            HIP_TRY(hipMemcpy(count, totals, sizeof(count), hipMemcpyDeviceToHost));
+            if (count[0] == 0) break; // every pixel is done
+            ad.quads = quads;
+            ad.n_quads = count[0];
+            ad.first = false;
+            samples += uint64_t(count[1]) * a->pass_spp;
+        }
+        // (pass 0 fills `stats` as a plain render does — kernel form, scene sizes — and starts its clock)
+        if (int rc = render_tiles_t<R>(s, d, cam, &pass, d->packed.p, stream, k == 0 ? stats : nullptr, false, false, &ad)) return rc;
+    }
+    dim3 block(32, 8), grid((p->width + 31) / 32, (p->height + 7) / 8);
+    hipLaunchKernelGGL(adaptive_output_kernel<R>, grid, block, 0, stream, (R*)d->packed.p, (const AdaptivePixel*)ad.state, (uint32_t*)d->ad_spp.p,
+                       (double*)d->ad_stderr.p, p->width, p->height, L.tiles_x);
+    HIP_TRY(hipGetLastError());
+    if (stats) HIP_TRY(hipEventRecord(d->ev1.get(), stream));
+    if (int rc = untile_launch<R>(p->width, p->height, 1, d->packed.p, d->linear.p, d->rgba.p, stream)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (stats) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, d->ev0.get(), d->ev1.get()));
+        stats->kernel_ms = ms;
+        stats->samples = samples;
+    }
+    return RTTNW_OK;
+}
+
 // what a precision's translation unit instantiates
 #define RT_INSTANTIATE_PRECISION(R)                                                                                                             \
     template int render_tiles_t<R>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, \
-                                   bool, bool);                                                                                                 \
+                                   bool, bool, const AdaptivePass*);                                                                            \
     template int probe_path_t<R>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t); \
-    template int untile_launch<R>(uint32_t, uint32_t, uint32_t, const void*, void*, uint8_t*, hipStream_t);
+    template int untile_launch<R>(uint32_t, uint32_t, uint32_t, const void*, void*, uint8_t*, hipStream_t);                                       \
+    template int render_adaptive_t<R>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
 
 } // namespace RT_ARITH_NS
 } // namespace rt

@@ -1861,5 +1861,51 @@ inline bool plan_jobs(RenderConsts& rc) {
     return true;
 }
 
+// ---- the ACTIVE-LIST numbering of rttnw_render_adaptive's refinement passes.  The pass traces only the pixel blocks (2x2 quads) of a
+// list; an entry is the block's index in the rank (tile * 16 + block in tile, as job_decode numbers them) | the mask of its pixels that
+// are still active << QUAD_MASK_SHIFT.  64 consecutive jobs are still one block x 16 chunks; a pixel of a listed block that is no longer
+// active gets empty jobs (s == s_end), like a tile pixel outside the image.  Chunk c of the launch writes its sums at
+// c * jobs_per_chunk + slot, jobs_per_chunk = 4 * (listed blocks), slot = 4 * (list position) + pixel in block.
+static_assert(JOB_BLOCK_LG == 1, "the active list packs a 2x2 block's four pixel bits");
+constexpr uint32_t QUAD_MASK_SHIFT = 28u;
+constexpr uint32_t QUAD_INDEX_MASK = (1u << QUAD_MASK_SHIFT) - 1u;
+// pixel pp (0..3) of block b of the rank -> its index in the packed tiles (tile * 64 + y * 8 + x)
+RT_HD uint32_t block_pixel(uint32_t b, uint32_t pp) {
+    const uint32_t tile = b >> 4, q = b & 15u;
+    const uint32_t x = (q & 3u) * 2u + (pp & 1u), y = (q >> 2) * 2u + (pp >> 1);
+    return tile * 64u + y * 8u + x;
+}
+RT_HD JobInfo job_decode_list(const RenderConsts& rc, uint32_t job, const uint32_t* quads) {
+    const uint32_t group = fdiv(job, rc.div_jobs_per_group);
+    const uint32_t rem = job - group * rc.div_jobs_per_group.d;
+    const uint32_t slot = rem >> 6, l = rem & 63u; // list position, lane of the wave's 64
+    const uint32_t e = quads[slot];
+    const uint32_t b = e & QUAD_INDEX_MASK, pp = l & 3u;
+    const uint32_t tile = b >> 4, q = b & 15u;
+    const uint32_t chunk = group * JOB_GROUP_CHUNKS + (l >> 2);
+    uint32_t tx, ty;
+    tile_unpermute(rc.tile_rank + tile * rc.tile_world, rc.div_tiles_x, tx, ty);
+    const uint32_t x = (q & 3u) * 2u + (pp & 1u), y = (q >> 2) * 2u + (pp >> 1);
+    JobInfo j;
+    j.px = tx * 8u + x;
+    j.row = ty * 8u + y;
+    j.real = chunk < rc.n_chunks;
+    j.s = j.s_end = 0;
+    if (j.real) chunk_samples(rc, rc.chunk_base + chunk, j.s, j.s_end);
+    if (j.px >= rc.width || j.row >= rc.height || ((e >> QUAD_MASK_SHIFT) >> pp & 1u) == 0u) j.s = j.s_end; // nothing to trace for this pixel
+    j.sum_index = chunk * rc.jobs_per_chunk + slot * 4u + pp;
+    return j;
+}
+// Host: the job numbering of a pass over `n_quads` listed blocks.
+inline bool plan_jobs_list(RenderConsts& rc, uint32_t n_quads) {
+    rc.jobs_per_chunk = n_quads * 4u;
+    const uint64_t groups = (uint64_t(rc.n_chunks) + JOB_GROUP_CHUNKS - 1) / JOB_GROUP_CHUNKS;
+    const uint64_t per_group = uint64_t(rc.jobs_per_chunk) * JOB_GROUP_CHUNKS, total = groups * per_group;
+    if (per_group >= (1ull << 32) || total >= (1ull << 32)) return false;
+    rc.div_jobs_per_group = make_fastdiv(uint32_t(std::max<uint64_t>(1, per_group)));
+    rc.n_jobs = uint32_t(total);
+    return true;
+}
+
 } // namespace RT_ARITH_NS
 } // namespace rt

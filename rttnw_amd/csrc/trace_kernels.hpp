@@ -18,6 +18,7 @@
 // No CPU fallback: every entry point needs a HIP device.
 #pragma once
 #include "render_common.hpp"
+#include "adaptive.hpp"
 #ifndef RT_ASYNC_SHADE
 #define RT_ASYNC_SHADE 1 // the lane-owns-path kernel leaves its walk loop for a shade phase once at most RT_ASYNC_SLACK walks are unfinished; those are
                          // SUSPENDED — their lanes skip the phase and walk on in the next one (0: every round waits for its longest walk, rounds 1-4)
@@ -255,8 +256,12 @@ template <typename T> __device__ __forceinline__ T kernarg_reload(uint32_t offse
 // alignment, which is what this struct does with its members (the GPU parity tests would not survive a mismatch).
 template <typename R> struct TraceArgsHead { SceneView<R> sc; CameraRec<R> cam; RenderConsts rc; };
 static_assert(alignof(SceneView<float>) <= 8 && alignof(CameraRec<double>) <= 8 && alignof(RenderConsts) <= 8, "kernarg_reload assumes naturally aligned arguments");
+// ACTIVE-LIST instantiations (LIST = true, rttnw_render_adaptive's refinement passes; rt_core.hpp job_decode_list): jobs are numbered over a list
+// of 2x2 pixel blocks.  The list rides in the `counters` argument, which the non-counting forms — the only ones with a list form — never
+// read: the kernel arguments, and every other instantiation, stay as they are.  Where the decoupled kernel finds it:
+template <typename R> struct TraceArgsList { SceneView<R> sc; CameraRec<R> cam; RenderConsts rc; R bg_r, bg_g, bg_b, t_min; R* partial; unsigned long long* job_counter; const uint32_t* quads; };
 
-template <typename R, bool COUNT, int GENERAL> // GENERAL: SHAPES_FAST (0) / SHAPES_GENERAL (1) / SHAPES_NONE (2: the scene has no instance record, rt_core.hpp)
+template <typename R, bool COUNT, int GENERAL, bool LIST = false> // GENERAL: SHAPES_FAST (0) / SHAPES_GENERAL (1) / SHAPES_NONE (2: the scene has no instance record, rt_core.hpp)
 // (at least 3 waves/SIMD: 170 VGPRs — the f32 code needs 164; the f64 code, allowed 256, ran at 2 waves/SIMD and waited on
 // the fabric: spheres_1m f64 167 -> 264 Msamples/s with 140 registers spilled; 4 waves/SIMD: 205)
 // (the LEAN flavour — 127-129 registers in f64, ~110 in f32 — may be launched as ONE block per CU of as many waves as the CU's LDS holds, wave_block_waves():
@@ -372,7 +377,9 @@ __global__ __launch_bounds__(GENERAL == SHAPES_NONE_NT ? 1024 : TRACE_BLOCK, GEN
                         slot_done = true; // no jobs left: this slot retires
                     } else {
                         const RenderConsts rj = kernarg_reload<RenderConsts>(offsetof(TraceArgsHead<R>, rc)); // cold: keep it out of the SGPRs
-                        const JobInfo ji = job_decode(rj, uint32_t(job));
+                        // (a constant condition: the arm not taken is not even emitted, so the list-less forms compile as they did)
+                        const JobInfo ji = LIST ? job_decode_list(rj, uint32_t(job), kernarg_reload<const uint32_t*>(offsetof(TraceArgsList<R>, quads)))
+                                                : job_decode(rj, uint32_t(job));
                         pxrow = ji.px | (ji.row << 16);
                         smp = ji.s; smp_end = ji.s_end;
                         job = ji.real ? (unsigned long long)ji.sum_index : ~0ull; // from here on: where the job's sum goes (none for padding)
@@ -482,6 +489,11 @@ __global__ __launch_bounds__(GENERAL == SHAPES_NONE_NT ? 1024 : TRACE_BLOCK, GEN
                                                                          double*, unsigned long long*, DeviceCounters*, double*, uint32_t*, uint32_t, int32_t*);
 RT_WAVE_DECL(false, SHAPES_FAST) RT_WAVE_DECL(false, SHAPES_GENERAL) RT_WAVE_DECL(false, SHAPES_NONE) RT_WAVE_DECL(false, SHAPES_NONE_NT) RT_WAVE_DECL(true, SHAPES_FAST) RT_WAVE_DECL(true, SHAPES_GENERAL)
 #undef RT_WAVE_DECL
+#define RT_WAVE_DECL_LIST(GENERAL)                                                                                                                        \
+    extern template __global__ void trace_kernel<double, false, GENERAL, true>(SceneView<double>, CameraRec<double>, RenderConsts, double, double, double, \
+                                                                               double, double*, unsigned long long*, DeviceCounters*, double*, uint32_t*, uint32_t, int32_t*);
+RT_WAVE_DECL_LIST(SHAPES_FAST) RT_WAVE_DECL_LIST(SHAPES_GENERAL) RT_WAVE_DECL_LIST(SHAPES_NONE) RT_WAVE_DECL_LIST(SHAPES_NONE_NT)
+#undef RT_WAVE_DECL_LIST
 #endif
 
 // The plain form of the same loop: a lane OWNS a path (and its job): path state stays in registers, no queues.  Rounds 1-4 alternated
@@ -491,7 +503,7 @@ RT_WAVE_DECL(false, SHAPES_FAST) RT_WAVE_DECL(false, SHAPES_GENERAL) RT_WAVE_DEC
 // their cursor and walk on beside them.  Kept beside the decoupled kernel because which of the two is faster depends on the scene
 // (render_tiles.hpp: the crossover is at ~13 000 four-wide records; KERNELS.md).
 // NSTEPS: node steps per trip round the walk loop (rt_core.hpp closest_solid): RT_NODE_STEPS, or 3 for tiny top trees (render_tiles.hpp).
-template <typename R, bool COUNT, int BLOCK, bool LDSN, int GENERAL, int NSTEPS = RT_NODE_STEPS> // GENERAL: SHAPES_FAST / SHAPES_GENERAL / SHAPES_NONE, as above
+template <typename R, bool COUNT, int BLOCK, bool LDSN, int GENERAL, int NSTEPS = RT_NODE_STEPS, bool LIST = false> // GENERAL: SHAPES_FAST / SHAPES_GENERAL / SHAPES_NONE, as above
 // (the 256-thread form — nodes in global memory — asks for at least 3 waves/SIMD like the decoupled kernel: its f64 code,
 // allowed 256 VGPRs, ran at 2: a 20 000-sphere scene 29.9 -> 13.7 ms per 67 Msamples)
 __global__ __launch_bounds__(BLOCK, BLOCK == 256 ? 3 : 1) void trace_kernel_plain(SceneView<R> sc_arg, CameraRec<R> cam, RenderConsts rc, R bg_r, R bg_g,
@@ -589,7 +601,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 256 ? 3 : 1) void trace_kernel_plai
                 if (mine >= n_jobs) {
                     done = true;
                 } else {
-                    const JobInfo ji = job_decode(rc, uint32_t(mine));
+                    const JobInfo ji = LIST ? job_decode_list(rc, uint32_t(mine), reinterpret_cast<const uint32_t*>(counters)) : job_decode(rc, uint32_t(mine));
                     pxrow = ji.px | (ji.row << 16); s = ji.s; s_end = ji.s_end;
                     job = ji.sum_index; // from here on: where the job's sum goes
                     acc = V3<R>();
@@ -720,6 +732,117 @@ __global__ void untile_kernel(const R* __restrict__ gathered, R* __restrict__ li
     if (rgba8) {
         rgba8[o * 4] = quantise(r); rgba8[o * 4 + 1] = quantise(g); rgba8[o * 4 + 2] = quantise(b); rgba8[o * 4 + 3] = 255;
     }
+}
+
+// ---- rttnw_render_adaptive (include/rttnw_hip.h; DESIGN.md "Adaptive sampling").
+// The adaptive resolve step: resolve_kernel's chain for the pixels a pass traced, plus the pixel's noise estimate and its active bit.
+// One thread per SLOT of the launch's chunk sums: pass 0 numbers them like a plain render (slot = packed pixel), a refinement pass by
+// the active list (rt_core.hpp job_decode_list: slot = 4 * list position + pixel in block; `quads` != nullptr).  Per pixel, in chunk order:
+// the running sum in `packed` (the R chain: exactly resolve_kernel's additions, continued over launches AND passes), and the double state
+// of adaptive.hpp folded with the chunk's mean.  The pass's last launch decides whether the pixel takes part in the next pass.
+template <typename R>
+__global__ void adaptive_resolve_kernel(const R* __restrict__ partial, R* __restrict__ packed, AdaptivePixel* __restrict__ state,
+                                        uint8_t* __restrict__ active, const uint32_t* __restrict__ quads, RenderConsts rc, uint32_t n_slots,
+                                        uint32_t first_of_render, uint32_t last_of_pass, uint32_t cap, double rel_error, double abs_error) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n_slots) return;
+    uint32_t p = slot;
+    if (quads) {
+        const uint32_t e = quads[slot >> 2];
+        if (((e >> QUAD_MASK_SHIFT) >> (slot & 3u) & 1u) == 0u) return; // a converged pixel of a listed block: it traced nothing
+        p = block_pixel(e & QUAD_INDEX_MASK, slot & 3u);
+    }
+    uint32_t tx, ty;
+    tile_unpermute(rc.tile_rank + (p >> 6) * rc.tile_world, rc.div_tiles_x, tx, ty);
+    const bool inside = tx * 8u + (p & 7u) < rc.width && ty * 8u + ((p >> 3) & 7u) < rc.height;
+    R* dst = packed + (unsigned long long)p * 4ull;
+    R r = 0, g = 0, b = 0;
+    AdaptivePixel a = {{0, 0, 0}, {0, 0, 0}, 0u, 0u};
+    if (!first_of_render) { r = dst[0]; g = dst[1]; b = dst[2]; a = state[p]; }
+    if (inside) {
+        for (uint32_t c = 0; c < rc.n_chunks; ++c) {
+            const R* src = partial + ((unsigned long long)c * n_slots + slot) * 3ull;
+            const R sr = src[0], sg = src[1], sb = src[2];
+            r = r + sr; g = g + sg; b = b + sb;
+            uint32_t s0, s1;
+            chunk_samples(rc, rc.chunk_base + c, s0, s1);
+            const double n_c = double(s1 - s0);
+            const double m[3] = {double(sr) / n_c, double(sg) / n_c, double(sb) / n_c};
+            adaptive_fold(a, m, s1 - s0);
+        }
+    }
+    dst[0] = r; dst[1] = g; dst[2] = b; dst[3] = R(0);
+    state[p] = a;
+    if (last_of_pass) {
+        const R n = R(a.n);
+        const double value[3] = {double(r / n), double(g / n), double(b / n)};
+        active[p] = inside && adaptive_active(a, value, rel_error, abs_error, cap) ? 1u : 0u;
+    }
+}
+
+// Compaction of the active pixels into the list of 2x2 blocks the next pass traces — deterministic, no atomics: (1) every wave counts its
+// blocks with an active pixel (ballot + popcount) and their active pixels, (2) one workgroup scans the waves' counts, (3) every wave writes
+// its entries at its base, in block order.  Block b of the rank is thread b; its entry is b | pixel mask << QUAD_MASK_SHIFT.
+__device__ __forceinline__ uint32_t block_active_mask(const uint8_t* active, uint32_t b, uint32_t n_blocks) {
+    uint32_t mask = 0;
+    if (b < n_blocks)
+        for (uint32_t pp = 0; pp < 4u; ++pp) mask |= active[block_pixel(b, pp)] ? 1u << pp : 0u;
+    return mask;
+}
+template <typename R>
+__global__ void quad_count_kernel(const uint8_t* __restrict__ active, uint32_t n_blocks, uint32_t* __restrict__ wave_counts) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x, wave = b >> 6;
+    const uint32_t mask = block_active_mask(active, b, n_blocks);
+    const unsigned long long listed = __ballot(mask != 0u);
+    uint32_t px = uint32_t(__popc(mask));
+    for (int off = 32; off > 0; off >>= 1) px += __shfl_xor(px, off);
+    if ((threadIdx.x & 63u) == 0u && wave * 64u < n_blocks) { wave_counts[2u * wave] = uint32_t(__popcll(listed)); wave_counts[2u * wave + 1u] = px; }
+}
+constexpr uint32_t QUAD_SCAN_BLOCK = 1024;
+template <typename R>
+__global__ void __launch_bounds__(QUAD_SCAN_BLOCK) quad_scan_kernel(const uint32_t* __restrict__ wave_counts, uint32_t* __restrict__ wave_base,
+                                                                    uint32_t n_waves, uint32_t* __restrict__ totals) {
+    __shared__ uint32_t sq[QUAD_SCAN_BLOCK], sp[QUAD_SCAN_BLOCK];
+    const uint32_t t = threadIdx.x, per = (n_waves + QUAD_SCAN_BLOCK - 1u) / QUAD_SCAN_BLOCK;
+    const uint32_t w0 = t * per < n_waves ? t * per : n_waves, w1 = w0 + per < n_waves ? w0 + per : n_waves;
+    uint32_t q = 0, px = 0;
+    for (uint32_t w = w0; w < w1; ++w) { q += wave_counts[2u * w]; px += wave_counts[2u * w + 1u]; }
+    sq[t] = q; sp[t] = px;
+    __syncthreads();
+    for (uint32_t off = 1; off < QUAD_SCAN_BLOCK; off <<= 1) { // inclusive scan over the threads' segments
+        const uint32_t aq = t >= off ? sq[t - off] : 0u, ap = t >= off ? sp[t - off] : 0u;
+        __syncthreads();
+        sq[t] += aq; sp[t] += ap;
+        __syncthreads();
+    }
+    uint32_t base = sq[t] - q;
+    for (uint32_t w = w0; w < w1; ++w) { wave_base[w] = base; base += wave_counts[2u * w]; }
+    if (t == QUAD_SCAN_BLOCK - 1u) { totals[0] = sq[t]; totals[1] = sp[t]; }
+}
+template <typename R>
+__global__ void quad_list_kernel(const uint8_t* __restrict__ active, uint32_t n_blocks, const uint32_t* __restrict__ wave_base,
+                                 uint32_t* __restrict__ quads) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x, wave = b >> 6;
+    const uint32_t mask = block_active_mask(active, b, n_blocks);
+    const unsigned long long listed = __ballot(mask != 0u);
+    if (mask) quads[wave_base[wave] + uint32_t(__popcll(listed & ((1ull << (threadIdx.x & 63u)) - 1ull)))] = b | (mask << QUAD_MASK_SHIFT);
+}
+
+// After the last pass: the packed running sums become the pixel means (sum / n_q, resolve_kernel's division) for untile_kernel, and the
+// samples and standard errors go to row-major, top-first maps.
+template <typename R>
+__global__ void adaptive_output_kernel(R* __restrict__ packed, const AdaptivePixel* __restrict__ state, uint32_t* __restrict__ spp_map,
+                                       double* __restrict__ stderr_map, uint32_t width, uint32_t height, uint32_t tiles_x) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const unsigned long long src = tile_permuted(x >> 3, y >> 3, tiles_x) * 64ull + ((y & 7u) << 3) + (x & 7u);
+    const AdaptivePixel a = state[src];
+    R* dst = packed + src * 4ull;
+    const R n = R(a.n);
+    dst[0] = dst[0] / n; dst[1] = dst[1] / n; dst[2] = dst[2] / n; dst[3] = R(1);
+    const unsigned long long o = (unsigned long long)y * width + x;
+    spp_map[o] = a.n;
+    for (int ch = 0; ch < 3; ++ch) stderr_map[o * 3ull + ch] = adaptive_stderr(a, ch);
 }
 
 // Debug probe: one lane walks one sample's path and dumps every hit record (t, p, normal, material, u, v,

@@ -39,6 +39,29 @@ def render_multi(scene, cam, params, device_ids, want_stats=True):
     return lin, rgba, list(st)
 
 
+def render_adaptive(scene, cam, params, pass_spp=64, rel_error=0.02, abs_error=0.0):
+    """`rttnw_render_adaptive`: passes of `pass_spp` samples per pixel, a pixel stopping once its standard error is at most
+    abs_error + rel_error * mean in every channel, or at `params.spp` samples (the cap, a multiple of pass_spp).  A `params.spp_chunk`
+    of 0 is taken as max(1, pass_spp // 16) here, so that a pass of 16 k samples is exactly one job group of 16 chunks (64 -> 4).
+    Returns (linear HxWx3 f64, rgba8 HxWx4 u8, spp_map HxW u32, stderr HxWx3 f64, Stats)."""
+    import copy
+    b = library.product()
+    p = copy.copy(params)
+    if p.spp_chunk == 0:
+        p.spp_chunk = max(1, pass_spp // 16)
+    h, w = p.height, p.width
+    lin = np.zeros((h, w, 3), dtype=np.float64)
+    rgba = np.zeros((h, w, 4), dtype=np.uint8)
+    spp = np.zeros((h, w), dtype=np.uint32)
+    se = np.zeros((h, w, 3), dtype=np.float64)
+    st = Stats()
+    a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
+    rc = b.render_adaptive(scene.handle, C.byref(cam), C.byref(p), C.byref(a), lin.ctypes.data, rgba.ctypes.data, spp.ctypes.data,
+                           se.ctypes.data, C.byref(st))
+    check(rc, b, "rttnw_render_adaptive")
+    return lin, rgba, spp, se, st
+
+
 def render_host_passes(scene, cam, params, passes, on_pass=None):
     """The same image as `render_host`, in `passes` passes over disjoint sample ranges (`rttnw_params.sample_begin`):
     after every pass the running mean is a complete, displayable estimate — progressive display and a natural
