@@ -96,6 +96,17 @@ pub struct rttnw_adaptive {
     pub abs_error: f64,
 }
 
+/// The parameters of `rttnw_denoise` (include/rttnw_hip.h states the contract); a sigma of 0 is the library default.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rttnw_denoise_params {
+    pub iterations: u32,
+    pub reserved0: u32,
+    pub sigma_luminance: f64,
+    pub sigma_normal: f64,
+    pub sigma_depth: f64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct rttnw_tile_layout {
@@ -181,6 +192,8 @@ extern "C" {
     pub fn rttnw_render(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_render_multi(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, ngpu: u32, device_ids: *const i32, out_linear_rgb: *mut f64, out_rgba8: *mut u8, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_render_adaptive(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_spp: *mut u32, out_stderr_rgb: *mut f64, stats: *mut rttnw_stats) -> c_int;
+    pub fn rttnw_render_features(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, out_albedo: *mut f64, out_normal: *mut f64, out_depth: *mut f64, out_alpha: *mut f64, stats: *mut rttnw_stats) -> c_int;
+    pub fn rttnw_denoise(width: u32, height: u32, linear_rgb: *const f64, variance_rgb: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, d: *const rttnw_denoise_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_render_tiles_device(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, d_packed: *mut c_void, hip_stream: *mut c_void, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_untile_device(width: u32, height: u32, world: u32, precision: u32, d_gathered: *const c_void, d_linear_rgb: *mut c_void, d_rgba8: *mut u8, hip_stream: *mut c_void) -> c_int;
     // ---- introspection

@@ -158,6 +158,13 @@ impl Scene {
         ok(unsafe { ffi::rttnw_render_adaptive(self.raw, cam, p, a, ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), &mut stats) })?;
         Ok((rgba, spp, stderr, stats))
     }
+    /// First-hit feature buffers of the frame `render` renders (`rttnw_render_features`), row-major, top row first.
+    pub fn render_features(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params) -> Result<Features> {
+        let n = p.width as usize * p.height as usize;
+        let mut f = Features { width: p.width, height: p.height, albedo: vec![0f64; n * 3], normal: vec![0f64; n * 3], depth: vec![0f64; n], alpha: vec![0f64; n] };
+        ok(unsafe { ffi::rttnw_render_features(self.raw, cam, p, f.albedo.as_mut_ptr(), f.normal.as_mut_ptr(), f.depth.as_mut_ptr(), f.alpha.as_mut_ptr(), ptr::null_mut()) })?;
+        Ok(f)
+    }
     /// The same image from the GPUs `devices` of this node (tile partition + RCCL gather inside the library).
     pub fn render_multi(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, devices: &[i32]) -> Result<(Vec<u8>, Vec<ffi::rttnw_stats>)> {
         let mut rgba = vec![0u8; p.width as usize * p.height as usize * 4];
@@ -171,6 +178,32 @@ impl Scene {
         Ok(bi)
     }
 }
+/// What `Scene::render_features` returns: albedo and normal w*h*3, depth and alpha w*h.
+pub struct Features {
+    pub width: u32,
+    pub height: u32,
+    pub albedo: Vec<f64>,
+    pub normal: Vec<f64>,
+    pub depth: Vec<f64>,
+    pub alpha: Vec<f64>,
+}
+
+/// `rttnw_denoise`: the feature-guided a-trous filter over a linear image (w*h*3); `variance` is the variance of the pixel means (the
+/// square of `render_adaptive`'s standard errors).  Returns (linear w*h*3, RGBA8 w*h*4).
+pub fn denoise(linear: &[f64], variance: Option<&[f64]>, f: &Features, d: &ffi::rttnw_denoise_params) -> Result<(Vec<f64>, Vec<u8>)> {
+    let n = f.width as usize * f.height as usize;
+    if linear.len() != n * 3 || variance.map_or(false, |v| v.len() != n * 3) || f.albedo.len() != n * 3 || f.normal.len() != n * 3 || f.depth.len() != n || f.alpha.len() != n {
+        return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "denoise: array sizes do not match the image".into() });
+    }
+    let mut out = vec![0f64; n * 3];
+    let mut rgba = vec![0u8; n * 4];
+    ok(unsafe {
+        ffi::rttnw_denoise(f.width, f.height, linear.as_ptr(), variance.map_or(ptr::null(), |v| v.as_ptr()), f.albedo.as_ptr(), f.normal.as_ptr(), f.depth.as_ptr(),
+                           f.alpha.as_ptr(), d, out.as_mut_ptr(), rgba.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())
+    })?;
+    Ok((out, rgba))
+}
+
 impl Drop for Scene {
     fn drop(&mut self) {
         if !self.raw.is_null() { unsafe { ffi::rttnw_scene_destroy(self.raw) } }

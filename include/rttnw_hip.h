@@ -282,6 +282,68 @@ int rttnw_render_adaptive(rttnw_scene* s, const rttnw_camera_desc* cam, const rt
                           double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb,
                           rttnw_stats* stats);
 
+/* First-hit feature buffers ("AOVs") of the frame rttnw_render renders: albedo, normal, depth, coverage — the inputs of a denoiser
+ * (rttnw_denoise below, or an external one), an alpha channel, a way to look at a scene.  The reference has no counterpart: its color()
+ * (main.rs:26-45) keeps nothing of a path but its radiance.  (Came without a version bump, like rttnw_render_adaptive: detect it by its symbol.)
+ *
+ * Samples.  For every pixel, samples [sample_begin, sample_begin + spp) start with THE CAMERA RAYS OF rttnw_render (the same keys: pixel,
+ *   sample, seed — main.rs:212-215) and do bounce 0 only: world.hit() (main.rs:33) with the keyed draws of bounce 0, so a ConstantMedium in
+ *   front (hittable.rs:745-797) decides exactly as it does in the render, and Material::scatter / emitted (main.rs:34-41) at that hit.
+ * Per sample.  On a hit: alpha = 1, normal = rec.normal as the hit record holds it (hittable.rs:30-44: against the ray), depth =
+ *   rec.t * |ray.direction| (the product formed after the square root, not fused into it or into the sum), albedo = the attenuation if
+ *   the material scattered, else what it emitted.  On a miss: alpha = 0, normal = 0, depth = 0, albedo = p->background.
+ * Per pixel.  Each channel is ONE chain of additions in sample order in the kernel's arithmetic type, then one division by spp: the
+ *   result does not depend on the launch shape.  alpha is fractional and normals are shorter than 1 where a pixel's samples disagree
+ *   (silhouettes).  Features over disjoint sample ranges combine like renders do (weights = their spp).
+ * p->precision selects the arithmetic build as for rttnw_render (RTTNW_F64_STRICT: the reference's operations, every value within 1e-12 of
+ *   the CPU restatement); max_depth and spp_chunk are not used (max_depth must still be valid).  The first call whose camera shutter
+ *   reaches outside the trees' interval rebuilds them, and the strict build walks its own lowering, exactly as for rttnw_render.
+ * Outputs (each optional; row-major, top row first like rttnw_render; doubles): out_albedo w*h*3, out_normal w*h*3, out_depth w*h,
+ *   out_alpha w*h.  `stats`: samples, rays (= samples), kernel_ms, the scene's sizes.  Blocking.
+ * Refusals, before the device is touched, in this order: RTTNW_ERR_INVALID for a NULL p, spp == 0, reserved0 != 0 or tile_world != 1;
+ *   RTTNW_ERR_UNSUPPORTED for collect_counters != 0; then whatever rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes). */
+int rttnw_render_features(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p,
+                          double* out_albedo, double* out_normal, double* out_depth, double* out_alpha, rttnw_stats* stats);
+
+/* A denoiser for the images above: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by the feature buffers of
+ * rttnw_render_features and, optionally, by the variance of the pixel means (the colour stop of SVGF, Schied et al. 2017) — the square of
+ * rttnw_render_adaptive's out_stderr_rgb.  Host arrays in, host arrays out (row-major, top row first), blocking, on the current device;
+ * no scene handle.  No CPU fallback: RTTNW_ERR_HIP without a device.  Everything is double.
+ *
+ * Demodulation.  A pixel with alpha != 0 is filtered as c = colour / albedo in every channel whose albedo > 1e-3 (c = colour in the others)
+ *   and multiplied back at the end; its variance is divided and multiplied by albedo^2 likewise.
+ * Passes.  `iterations` passes (0 .. 8), pass i with the 5x5 B3-spline taps h = (1, 4, 6, 4, 1) / 16 at stride 2^i, taps outside the image
+ *   dropped, accumulated row-major over the 5x5.  0 iterations copy the input to the output, without demodulation: the identity, bit for bit.
+ *   tap weight  w = h_x h_y * w_n * w_z * w_l; taps whose alpha is 0 are dropped, and a centre whose alpha is 0 passes through unchanged
+ *     w_n = max(0, n . n')^E              E = the smallest power of two >= sigma_normal (at most 1024), by repeated squaring
+ *     w_z = r^2,  r = 1 / (1 + (dz / (sigma_depth * (|z| + |z'|) / 2 + 1e-12))^2)
+ *     w_l = 1 / (1 + (dlum / (sigma_luminance * sqrt(max(V, 0)) + 1e-12))^2)    lum = 0.2126 r + 0.7152 g + 0.0722 b of c;  w_l = 1 when
+ *           variance_rgb == NULL or the centre's variance is not finite (in any channel).  V = the variance of the centre's luminance
+ *           (0.2126^2 var_r + ...) averaged over its 3x3 neighbourhood with taps (1, 2, 1) x (1, 2, 1), dropping taps outside the image,
+ *           with alpha == 0 or with a variance that is not finite
+ *     alpha, normal and albedo are sample means: alpha is fractional and normals are shorter than 1 on silhouettes; the weights take
+ *     them as they are.
+ *   colour = sum w c / sum w;  variance = sum w^2 var / (sum w)^2 over the taps whose variance is finite (a centre whose own variance is
+ *   not finite keeps it), both carried to the next pass.  A centre all of whose taps weigh 0 passes through.
+ * No transcendental function anywhere: + - * /, sqrt and comparisons only, no product fused into a sum, so the device code, a host build
+ *   of the same header (rttnw_amd/csrc/denoise.hpp) and a restatement in numpy give the same bits.
+ * Parameters.  A sigma of 0 means the library default: sigma_luminance 4 (SVGF's), sigma_normal 64 (|n . n'| = 0.99, 8 degrees, weighs
+ *   0.53), sigma_depth 0.1 (a tap 10 % nearer or farther weighs 0.25, 30 %: 0.01).  DESIGN.md section 10b says how they were chosen.
+ * Outputs: out_linear_rgb w*h*3 (optional), out_rgba8 w*h*4 after main.rs:219-225 (optional), out_variance_rgb w*h*3 (optional; written
+ *   only when variance_rgb was given), kernel_ms (optional): device time of the passes.
+ * Refusals, before the device is touched: RTTNW_ERR_INVALID for a NULL linear_rgb, albedo, normal, depth, alpha or d, width * height == 0,
+ *   iterations > 8, reserved0 != 0, a negative or NaN sigma. */
+struct rttnw_denoise_params {
+    uint32_t iterations; /* 0 .. 8; 5 reaches 2 * 16 = 32 pixels to either side */
+    uint32_t reserved0;  /* must be 0 */
+    double sigma_luminance, sigma_normal, sigma_depth; /* 0 = the library default */
+};
+typedef struct rttnw_denoise_params rttnw_denoise_params; /* (not `rttnw_denoise`: in C a typedef and a function share one name space) */
+int rttnw_denoise(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb,
+                  const double* albedo, const double* normal, const double* depth, const double* alpha,
+                  const rttnw_denoise_params* d, double* out_linear_rgb, uint8_t* out_rgba8, double* out_variance_rgb,
+                  double* kernel_ms);
+
 /* `render()` on the GPUs of ONE NODE, in one call from one host thread ("library owns its HIP
  * streams / RCCL comms"): the framebuffer's 8x8 tiles are interleaved over `ngpu` ranks, rank r traces its tiles on
  * device `device_ids[r]` (the scene is replicated there on first use), the packed tiles are gathered on rank 0's device —

@@ -4,7 +4,9 @@ One positional argument, the scene number 1..9 with the reference's per-scene de
 main.rs:66-183); writes `image.png` into the current directory (main.rs:231) and prints the wall time.
 Optional extras (not in the reference): --spp, --width, --precision f32|f64, --out, --seed, --passes, and adaptive sampling:
 --noise R [--abs-noise A] [--pass-spp B] [--spp-map FILE] stops sampling a pixel once the standard error of its mean is at most
-A + R * mean in every channel, --spp being the cap.
+A + R * mean in every channel, --spp being the cap.  --denoise [--denoise-iterations N] filters the image with rttnw_denoise, guided by
+first-hit feature buffers of min(spp, 16) samples (and, with --noise, by the adaptive render's standard errors); --features PREFIX writes
+PREFIX_albedo.png, PREFIX_normal.png (n * 0.5 + 0.5), PREFIX_depth.png (normalised to the farthest hit) and PREFIX_alpha.png.
 """
 import argparse
 import sys
@@ -39,6 +41,10 @@ def main(argv=None):
     ap.add_argument("--abs-noise", type=float, default=0.0, help="adaptive sampling: absolute noise bound added to the relative one")
     ap.add_argument("--pass-spp", type=int, default=64, help="adaptive sampling: samples per pixel per pass (the cap must be a multiple)")
     ap.add_argument("--spp-map", default=None, help="adaptive sampling: also write a grey-scale PNG of samples / cap")
+    ap.add_argument("--denoise", action="store_true", help="filter the image with the feature-guided denoiser (rttnw_denoise)")
+    ap.add_argument("--denoise-iterations", type=int, default=5, help="a-trous passes of the denoiser (0..8)")
+    ap.add_argument("--features", default=None, metavar="PREFIX", help="write the first-hit feature buffers as PREFIX_albedo.png, "
+                    "PREFIX_normal.png, PREFIX_depth.png, PREFIX_alpha.png")
     try:
         args = ap.parse_args(argv)
     except SystemExit:
@@ -65,6 +71,33 @@ def main(argv=None):
     cam.aspect_ratio = setup.width / setup.height
     p = make_params(w, h, args.spp or setup.spp, background=tuple(setup.background), seed=args.seed,
                     precision={"f32": abi.F32, "f64": abi.F64, "f64strict": abi.F64_STRICT}[args.precision])
+    features = None
+    if args.denoise or args.features:
+        if args.denoise and args.passes > 1:
+            print("--denoise does not combine with --passes", file=sys.stderr)
+            return 1
+        import copy
+        fp = copy.copy(p)
+        fp.spp = min(p.spp, 16)
+        features = render.render_features(sc, cam, fp)
+        if args.features:
+            def grey(a):
+                return Image.fromarray(np.minimum(np.maximum(a, 0.0) * 255.0 + 0.5, 255.0).astype(np.uint8), "L")
+            Image.fromarray(render.quantise_rgba8(features["albedo"]), "RGBA").save(args.features + "_albedo.png")
+            rgb = np.minimum(np.maximum(features["normal"] * 0.5 + 0.5, 0.0) * 255.0 + 0.5, 255.0).astype(np.uint8)
+            Image.fromarray(np.ascontiguousarray(rgb), "RGB").save(args.features + "_normal.png")
+            grey(features["depth"] / max(features["depth"].max(), 1e-300)).save(args.features + "_depth.png")
+            grey(features["alpha"]).save(args.features + "_alpha.png")
+            print("features (%d spp, %.1f ms) written to %s_{albedo,normal,depth,alpha}.png" % (fp.spp, features["stats"].kernel_ms, args.features))
+
+    def finish(linear, rgba, stderr):
+        """The image as it is written: denoised when asked for."""
+        if not args.denoise:
+            return np.ascontiguousarray(rgba)
+        _, out, _, ms = render.denoise(linear, features, stderr, iterations=args.denoise_iterations, want_ms=True)
+        print("denoised: %d iterations, %.2f ms" % (args.denoise_iterations, ms))
+        return out
+
     if args.noise is not None:
         if args.pass_spp < 1:
             print("--pass-spp must be at least 1", file=sys.stderr)
@@ -73,8 +106,8 @@ def main(argv=None):
             cap = (p.spp + args.pass_spp - 1) // args.pass_spp * args.pass_spp
             print("cap %d spp rounded up to %d, a multiple of --pass-spp %d" % (p.spp, cap, args.pass_spp))
             p.spp = cap
-        _, rgba, spp_map, _, st = render.render_adaptive(sc, cam, p, args.pass_spp, args.noise, args.abs_noise)
-        Image.fromarray(np.ascontiguousarray(rgba), "RGBA").save(args.out)
+        lin, rgba, spp_map, se, st = render.render_adaptive(sc, cam, p, args.pass_spp, args.noise, args.abs_noise)
+        Image.fromarray(finish(lin, rgba, se), "RGBA").save(args.out)
         if args.spp_map:
             grey = np.minimum(spp_map.astype(np.float64) / p.spp * 255.0 + 0.5, 255.0).astype(np.uint8)
             Image.fromarray(grey, "L").save(args.spp_map)
@@ -89,8 +122,8 @@ def main(argv=None):
         _, rgba, _ = render.render_host_passes(sc, cam, p, args.passes, on_pass=show)
         print("%.3fs" % (time.time() - t0))
         return 0
-    _, rgba, st = render.render_host(sc, cam, p)
-    Image.fromarray(np.ascontiguousarray(rgba), "RGBA").save(args.out)
+    lin, rgba, st = render.render_host(sc, cam, p)
+    Image.fromarray(finish(lin, rgba, None), "RGBA").save(args.out)
     print("%.3fs (trace kernel %.1f ms, %.1f Msamples/s)" % (time.time() - t0, st.kernel_ms,
                                                           st.samples / max(st.kernel_ms, 1e-9) / 1e3))
     return 0

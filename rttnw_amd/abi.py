@@ -54,6 +54,12 @@ class Adaptive(C.Structure):
     _fields_ = [("pass_spp", C.c_uint32), ("reserved0", C.c_uint32), ("rel_error", C.c_double), ("abs_error", C.c_double)]
 
 
+class Denoise(C.Structure):
+    """`rttnw_denoise_params` — the parameters of `rttnw_denoise` (a sigma of 0: the library default)."""
+    _fields_ = [("iterations", C.c_uint32), ("reserved0", C.c_uint32), ("sigma_luminance", C.c_double),
+                ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
+
+
 class TileLayout(C.Structure):
     _fields_ = [("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32), ("n_tiles", C.c_uint32),
                 ("tiles_per_rank", C.c_uint32), ("pixels_per_rank", C.c_uint32)]
@@ -105,6 +111,10 @@ PRODUCT_FUNCS = [
                                C.c_void_p, C.c_void_p]),
     ("render_adaptive", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    ("render_features", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.POINTER(Stats)]),
+    ("denoise", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.POINTER(Denoise), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("render_tiles_device", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_void_p,
                                       C.c_void_p, C.POINTER(Stats)]),
     ("untile_device", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

@@ -1,0 +1,37 @@
+// feature_api.cpp — the extern "C" half of rttnw_render_features and rttnw_denoise (include/rttnw_hip.h): argument checks, then the
+// feature pass of the requested arithmetic build (feature_kernels.hpp) or the denoiser's device half (denoise.hip).  Host code only.
+#include "feature_api.hpp"
+
+extern "C" {
+
+int rttnw_render_features(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* out_albedo, double* out_normal,
+                          double* out_depth, double* out_alpha, rttnw_stats* stats) {
+    // the call's own arguments first, as rttnw_render_adaptive: their refusals need no device (nor a committed scene)
+    if (!p) { rt::set_last_error("render_features: NULL argument"); return RTTNW_ERR_INVALID; }
+    if (p->spp == 0) { rt::set_last_error("render_features: spp is 0"); return RTTNW_ERR_INVALID; }
+    if (p->reserved0 != 0) { rt::set_last_error("render_features: reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (p->tile_world != 1) { rt::set_last_error("render_features: host-output form needs tile_world == 1"); return RTTNW_ERR_INVALID; }
+    if (p->collect_counters != 0) { rt::set_last_error("render_features: collect_counters is not supported"); return RTTNW_ERR_UNSUPPORTED; }
+    if (int rc = rt::validate(s, cam, p)) return rc;
+    return p->precision == RTTNW_F32          ? rt::render_features_t<float>(s, cam, p, out_albedo, out_normal, out_depth, out_alpha, stats)
+           : p->precision == RTTNW_F64_STRICT ? rt::ieee_strict::render_features_t<double>(s, cam, p, out_albedo, out_normal, out_depth, out_alpha, stats)
+                                              : rt::render_features_t<double>(s, cam, p, out_albedo, out_normal, out_depth, out_alpha, stats);
+}
+
+int rttnw_denoise(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const double* albedo, const double* normal,
+                  const double* depth, const double* alpha, const rttnw_denoise_params* d, double* out_linear_rgb, uint8_t* out_rgba8,
+                  double* out_variance_rgb, double* kernel_ms) {
+    if (!linear_rgb || !albedo || !normal || !depth || !alpha || !d) { rt::set_last_error("denoise: NULL argument"); return RTTNW_ERR_INVALID; }
+    if (uint64_t(width) * height == 0 || uint64_t(width) * height > (1ull << 28)) { rt::set_last_error("denoise: empty image (or more than 2^28 pixels)"); return RTTNW_ERR_INVALID; }
+    if (d->iterations > rt::DENOISE_MAX_ITERATIONS) { rt::set_last_error("denoise: more than 8 iterations"); return RTTNW_ERR_INVALID; }
+    if (d->reserved0 != 0) { rt::set_last_error("denoise: reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (!(d->sigma_luminance >= 0.0) || !(d->sigma_normal >= 0.0) || !(d->sigma_depth >= 0.0)) {
+        rt::set_last_error("denoise: the sigmas must be >= 0 (and not NaN)");
+        return RTTNW_ERR_INVALID;
+    }
+    const rt::DenoiseParams prm = rt::denoise_params(d->sigma_luminance, d->sigma_normal, d->sigma_depth, variance_rgb != nullptr);
+    return rt::denoise_device(width, height, linear_rgb, variance_rgb, albedo, normal, depth, alpha, d->iterations, prm, out_linear_rgb, out_rgba8,
+                              out_variance_rgb, kernel_ms);
+}
+
+} // extern "C"

@@ -1,0 +1,158 @@
+// feature_kernels.hpp — rttnw_render_features (include/rttnw_hip.h has the contract): the first hit of every camera ray as feature
+// buffers — albedo, normal, depth, coverage — for a denoiser or a compositor.  A template over the arithmetic type like the trace kernels,
+// instantiated once per arithmetic build in translation units of its own (features_f32.hip, features_f64.hip, features_f64_strict.hip,
+// each under the flags of the render unit of that build).
+//
+// The plain form: one lane owns one PIXEL and loops over its samples — bounce 0 of the render's own path (path_begin, world_hit with the
+// keyed draws of bounce 0, shade), nothing else.  Lanes are laid out in the render's 8x8 tile order, so a wave is one tile and its
+// primary rays are coherent; the traversal stack is the trace kernels' (LdsStack: 16 entries in LDS, the rest in a global strip).
+// 256-thread blocks: 17 KB of LDS each, so LDS never limits occupancy; the kernel is a few milliseconds next to a render of hundreds.
+#pragma once
+#include "trace_kernels.hpp"
+#include "feature_api.hpp"
+
+namespace rt {
+inline namespace RT_ARITH_NS {
+
+constexpr int FEATURE_BLOCK = 256;
+constexpr uint32_t FEATURE_CHANNELS = 8; // albedo r g b, normal x y z, depth, alpha
+
+// a product kept as a value of its own: the contracted builds would otherwise fuse it into the sum it is added to (rt_core.hpp keep_rounded)
+template <typename R> __device__ __forceinline__ R feature_rounded(R v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+// Packed pixel p = tile * 64 + y * 8 + x (tile in the permuted order of a single rank) -> FEATURE_CHANNELS sample means.
+template <typename R>
+__global__ __launch_bounds__(FEATURE_BLOCK) void feature_kernel(SceneView<R> sc, CameraRec<R> cam, RenderConsts rc, R bg_r, R bg_g, R bg_b, R t_min,
+                                                                R* __restrict__ packed, uint32_t n_pixels, int32_t* __restrict__ spill) {
+    extern __shared__ int32_t lds_stack[];
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pixels) return;
+    LdsStack<FEATURE_BLOCK> stack{(LdsIntPtr)(lds_stack + threadIdx.x), (GlobalIntPtr)(spill + p), gridDim.x * blockDim.x};
+    uint32_t tx, ty;
+    tile_unpermute(p >> 6, rc.div_tiles_x, tx, ty);
+    const uint32_t px = tx * 8u + (p & 7u), row = ty * 8u + ((p >> 3) & 7u);
+    R sum[FEATURE_CHANNELS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (px < rc.width && row < rc.height) {
+        NoCounters cnt;
+        for (uint32_t s = 0; s < rc.spp; ++s) { // ONE chain per channel, in sample order
+            PathState<R> ps;
+            path_begin(ps, cam, rc, px, row, s);
+            HitRecord<R> rec;
+            if (world_hit(sc, ps.ray, t_min, ps.key, 0u, rc.quirks, rec, stack, cnt)) {
+                const R depth = feature_rounded(rec.t * magnitude(ps.ray.d));
+                V3<R> att, emitted;
+                const bool scattered = shade(sc, rec, ps.key, 0u, ps.ray, att, emitted, cnt);
+                const V3<R> albedo = scattered ? att : emitted;
+                sum[0] = sum[0] + albedo.x; sum[1] = sum[1] + albedo.y; sum[2] = sum[2] + albedo.z;
+                sum[3] = sum[3] + rec.normal.x; sum[4] = sum[4] + rec.normal.y; sum[5] = sum[5] + rec.normal.z;
+                sum[6] = sum[6] + depth;
+                sum[7] = sum[7] + R(1);
+            } else {
+                sum[0] = sum[0] + bg_r; sum[1] = sum[1] + bg_g; sum[2] = sum[2] + bg_b;
+            }
+        }
+        const R n = R(rc.spp);
+        for (uint32_t c = 0; c < FEATURE_CHANNELS; ++c) sum[c] = sum[c] / n;
+    }
+    R* dst = packed + size_t(p) * FEATURE_CHANNELS;
+    for (uint32_t c = 0; c < FEATURE_CHANNELS; ++c) dst[c] = sum[c];
+}
+
+// Packed feature records -> the four row-major, top-first maps, as doubles (untile_kernel's addressing for one rank).
+template <typename R>
+__global__ void feature_untile_kernel(const R* __restrict__ packed, double* __restrict__ albedo, double* __restrict__ normal, double* __restrict__ depth,
+                                      double* __restrict__ alpha, uint32_t width, uint32_t height, uint32_t tiles_x) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const R* src = packed + (tile_permuted(x >> 3, y >> 3, tiles_x) * 64ull + ((y & 7u) << 3) + (x & 7u)) * FEATURE_CHANNELS;
+    const unsigned long long o = (unsigned long long)y * width + x;
+    for (uint32_t c = 0; c < 3u; ++c) {
+        albedo[o * 3 + c] = double(src[c]);
+        normal[o * 3 + c] = double(src[3u + c]);
+    }
+    depth[o] = double(src[6]);
+    alpha[o] = double(src[7]);
+}
+
+template <typename R>
+int render_features_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* out_albedo, double* out_normal, double* out_depth,
+                      double* out_alpha, rttnw_stats* stats) {
+    DeviceState* d = s->device;
+    // The render's own scene preparation (render_tiles_t, prepare_only): the strict build's second lowering, the upload on first use.
+    // One sample per pixel: the workspace that call sizes for its launch stays at its smallest.
+    rttnw_params prep = *p;
+    prep.spp = 1;
+    prep.sample_begin = 0;
+    if (int rc = render_tiles_t<R>(s, d, cam, &prep, nullptr, nullptr, nullptr, false, true, nullptr)) return rc;
+    const FlatScene* flat_p = &s->flat;
+    DeviceScene<R>* ds_p = &scene_of<R>(d);
+#if defined(RT_STRICT_F64)
+    if (int rc = reference_frame_scene(s, flat_p)) return rc;
+    if (flat_p != &s->flat) ds_p = &d->s64_ref;
+#endif
+    const FlatScene& flat = *flat_p;
+    const DeviceScene<R>& ds = *ds_p;
+
+    rttnw_tile_layout L;
+    fill_layout(p->width, p->height, 1, L);
+    RenderConsts rc{};
+    rc.width = p->width; rc.height = p->height; rc.spp = p->spp; rc.max_depth = p->max_depth;
+    rc.tiles_x = L.tiles_x; rc.tiles_y = L.tiles_y; rc.n_tiles = L.n_tiles;
+    rc.tile_rank = 0; rc.tile_world = 1; rc.my_tiles = L.n_tiles;
+    rc.quirks = p->quirks; rc.seed = p->seed; rc.stack_depth = flat.stack_depth;
+    rc.sample_begin = p->sample_begin;
+    rc.scene_flags = flat.moving.empty() ? SCENE_NO_TIME : 0u;
+    rc.inv_width = 1.0 / double(p->width); rc.inv_height = 1.0 / double(p->height);
+    rc.div_tiles_x = make_fastdiv(std::max<uint32_t>(1u, rc.tiles_x));
+    CameraRec<double> cam64;
+    make_camera(cam->lookfrom, cam->lookat, cam->view_up, cam->vertical_fov, cam->aspect_ratio, cam->aperture, cam->focus_distance, cam->open_time,
+                cam->close_time, cam64);
+
+    const size_t npx = size_t(p->width) * p->height;
+    const uint32_t n_pixels = L.pixels_per_rank;
+    const uint32_t grid = (n_pixels + FEATURE_BLOCK - 1) / FEATURE_BLOCK;
+    const size_t threads = size_t(grid) * FEATURE_BLOCK;
+    const size_t extra = rc.stack_depth > LDS_STACK_ENTRIES ? rc.stack_depth - LDS_STACK_ENTRIES : 0;
+    DevBuf<R> packed;
+    DevBuf<int32_t> spill;
+    DevBuf<double> maps; // albedo, normal, depth, alpha: 8 doubles per pixel
+    HIP_TRY(packed.alloc(size_t(n_pixels) * FEATURE_CHANNELS));
+    HIP_TRY(spill.alloc(threads * extra + threads)); // (+ threads: `spill + p` is a valid address for every lane even without extra entries)
+    HIP_TRY(maps.alloc(npx * 8));
+    double *m_albedo = maps.p, *m_normal = maps.p + npx * 3, *m_depth = maps.p + npx * 6, *m_alpha = maps.p + npx * 7;
+
+    const hipStream_t stream = nullptr;
+    const size_t lds = size_t(LDS_STACK_ENTRIES + 1) * FEATURE_BLOCK * sizeof(int32_t);
+    HIP_TRY(hipEventRecord(d->ev0.get(), stream));
+    hipLaunchKernelGGL(feature_kernel<R>, dim3(grid), dim3(FEATURE_BLOCK), lds, stream, ds.view, narrow_camera<R>(cam64), rc, R(p->background[0]),
+                       R(p->background[1]), R(p->background[2]), R(p->t_min), packed.p, n_pixels, spill.p);
+    HIP_TRY(hipGetLastError());
+    dim3 ublock(32, 8), ugrid((p->width + 31) / 32, (p->height + 7) / 8);
+    hipLaunchKernelGGL(feature_untile_kernel<R>, ugrid, ublock, 0, stream, (const R*)packed.p, m_albedo, m_normal, m_depth, m_alpha, p->width, p->height,
+                       L.tiles_x);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(d->ev1.get(), stream));
+    HIP_TRY(hipDeviceSynchronize());
+    if (out_albedo) HIP_TRY(hipMemcpy(out_albedo, m_albedo, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_normal) HIP_TRY(hipMemcpy(out_normal, m_normal, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_depth) HIP_TRY(hipMemcpy(out_depth, m_depth, npx * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_alpha) HIP_TRY(hipMemcpy(out_alpha, m_alpha, npx * sizeof(double), hipMemcpyDeviceToHost));
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, d->ev0.get(), d->ev1.get()));
+        stats->kernel_ms = ms;
+        stats->samples = uint64_t(npx) * p->spp;
+        stats->rays = stats->samples;
+        stats->n_nodes = flat.total_nodes4();
+        stats->n_prims = flat.n_prims_in_bvh;
+        stats->scene_bytes = uint32_t(std::min<size_t>(ds.bytes, 0xFFFFFFFFu));
+    }
+    return RTTNW_OK;
+}
+
+} // namespace RT_ARITH_NS
+} // namespace rt

@@ -62,6 +62,44 @@ def render_adaptive(scene, cam, params, pass_spp=64, rel_error=0.02, abs_error=0
     return lin, rgba, spp, se, st
 
 
+def render_features(scene, cam, params):
+    """`rttnw_render_features`: the first hit of the render's own camera rays, averaged over `params.spp` samples per pixel.
+    Returns {"albedo": HxWx3, "normal": HxWx3, "depth": HxW, "alpha": HxW (all f64), "stats": Stats}."""
+    b = library.product()
+    h, w = params.height, params.width
+    out = {"albedo": np.zeros((h, w, 3)), "normal": np.zeros((h, w, 3)), "depth": np.zeros((h, w)), "alpha": np.zeros((h, w))}
+    st = Stats()
+    rc = b.render_features(scene.handle, C.byref(cam), C.byref(params), out["albedo"].ctypes.data, out["normal"].ctypes.data,
+                           out["depth"].ctypes.data, out["alpha"].ctypes.data, C.byref(st))
+    check(rc, b, "rttnw_render_features")
+    out["stats"] = st
+    return out
+
+
+def denoise(linear, features, stderr=None, iterations=5, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0, want_ms=False):
+    """`rttnw_denoise`: the edge-avoiding a-trous filter over `linear` (HxWx3), guided by `features` (what `render_features` returns)
+    and, when `stderr` (HxWx3, `render_adaptive`'s standard errors of the pixel means) is given, by their variance.  A sigma of 0 is
+    the library default.  Returns (linear HxWx3 f64, rgba8 HxWx4 u8, variance HxWx3 f64 or None) — and the device time in ms after
+    them with `want_ms`."""
+    b = library.product()
+    lin = np.ascontiguousarray(linear, dtype=np.float64)
+    h, w = lin.shape[:2]
+    var = None if stderr is None else np.ascontiguousarray(np.square(np.asarray(stderr, dtype=np.float64)))
+    f = {k: np.ascontiguousarray(features[k], dtype=np.float64) for k in ("albedo", "normal", "depth", "alpha")}
+    assert f["albedo"].shape == (h, w, 3) and f["normal"].shape == (h, w, 3) and f["depth"].shape == (h, w) and f["alpha"].shape == (h, w)
+    assert var is None or var.shape == (h, w, 3)
+    out = np.zeros((h, w, 3))
+    rgba = np.zeros((h, w, 4), dtype=np.uint8)
+    out_var = None if var is None else np.zeros((h, w, 3))
+    d = abi.Denoise(iterations=iterations, reserved0=0, sigma_luminance=sigma_luminance, sigma_normal=sigma_normal, sigma_depth=sigma_depth)
+    ms = C.c_double(0.0)
+    rc = b.denoise(w, h, lin.ctypes.data, None if var is None else var.ctypes.data, f["albedo"].ctypes.data, f["normal"].ctypes.data,
+                   f["depth"].ctypes.data, f["alpha"].ctypes.data, C.byref(d), out.ctypes.data, rgba.ctypes.data,
+                   None if out_var is None else out_var.ctypes.data, C.byref(ms))
+    check(rc, b, "rttnw_denoise")
+    return (out, rgba, out_var, ms.value) if want_ms else (out, rgba, out_var)
+
+
 def render_host_passes(scene, cam, params, passes, on_pass=None):
     """The same image as `render_host`, in `passes` passes over disjoint sample ranges (`rttnw_params.sample_begin`):
     after every pass the running mean is a complete, displayable estimate — progressive display and a natural
