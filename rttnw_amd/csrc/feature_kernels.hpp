@@ -81,35 +81,12 @@ template <typename R>
 int render_features_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* out_albedo, double* out_normal, double* out_depth,
                       double* out_alpha, rttnw_stats* stats) {
     DeviceState* d = s->device;
-    // The render's own scene preparation (render_tiles_t, prepare_only): the strict build's second lowering, the upload on first use.
-    // One sample per pixel: the workspace that call sizes for its launch stays at its smallest.
-    rttnw_params prep = *p;
-    prep.spp = 1;
-    prep.sample_begin = 0;
-    if (int rc = render_tiles_t<R>(s, d, cam, &prep, nullptr, nullptr, nullptr, false, true, nullptr)) return rc;
-    const FlatScene* flat_p = &s->flat;
-    DeviceScene<R>* ds_p = &scene_of<R>(d);
-#if defined(RT_STRICT_F64)
-    if (int rc = reference_frame_scene(s, flat_p)) return rc;
-    if (flat_p != &s->flat) ds_p = &d->s64_ref;
-#endif
-    const FlatScene& flat = *flat_p;
-    const DeviceScene<R>& ds = *ds_p;
-
+    const FlatScene* flat = nullptr;
+    DeviceScene<R>* ds = nullptr;
+    if (int rc = bind_scene<R>(s, d, flat, ds)) return rc;
     rttnw_tile_layout L;
     fill_layout(p->width, p->height, 1, L);
-    RenderConsts rc{};
-    rc.width = p->width; rc.height = p->height; rc.spp = p->spp; rc.max_depth = p->max_depth;
-    rc.tiles_x = L.tiles_x; rc.tiles_y = L.tiles_y; rc.n_tiles = L.n_tiles;
-    rc.tile_rank = 0; rc.tile_world = 1; rc.my_tiles = L.n_tiles;
-    rc.quirks = p->quirks; rc.seed = p->seed; rc.stack_depth = flat.stack_depth;
-    rc.sample_begin = p->sample_begin;
-    rc.scene_flags = flat.moving.empty() ? SCENE_NO_TIME : 0u;
-    rc.inv_width = 1.0 / double(p->width); rc.inv_height = 1.0 / double(p->height);
-    rc.div_tiles_x = make_fastdiv(std::max<uint32_t>(1u, rc.tiles_x));
-    CameraRec<double> cam64;
-    make_camera(cam->lookfrom, cam->lookat, cam->view_up, cam->vertical_fov, cam->aspect_ratio, cam->aperture, cam->focus_distance, cam->open_time,
-                cam->close_time, cam64);
+    const RenderConsts rc = base_consts(p, *flat, L); // (the caller has checked: one rank, no counters)
 
     const size_t npx = size_t(p->width) * p->height;
     const uint32_t n_pixels = L.pixels_per_rank;
@@ -127,7 +104,7 @@ int render_features_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
     const hipStream_t stream = nullptr;
     const size_t lds = size_t(LDS_STACK_ENTRIES + 1) * FEATURE_BLOCK * sizeof(int32_t);
     HIP_TRY(hipEventRecord(d->ev0.get(), stream));
-    hipLaunchKernelGGL(feature_kernel<R>, dim3(grid), dim3(FEATURE_BLOCK), lds, stream, ds.view, narrow_camera<R>(cam64), rc, R(p->background[0]),
+    hipLaunchKernelGGL(feature_kernel<R>, dim3(grid), dim3(FEATURE_BLOCK), lds, stream, ds->view, camera_of<R>(cam), rc, R(p->background[0]),
                        R(p->background[1]), R(p->background[2]), R(p->t_min), packed.p, n_pixels, spill.p);
     HIP_TRY(hipGetLastError());
     dim3 ublock(32, 8), ugrid((p->width + 31) / 32, (p->height + 7) / 8);
@@ -147,9 +124,9 @@ int render_features_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
         stats->kernel_ms = ms;
         stats->samples = uint64_t(npx) * p->spp;
         stats->rays = stats->samples;
-        stats->n_nodes = flat.total_nodes4();
-        stats->n_prims = flat.n_prims_in_bvh;
-        stats->scene_bytes = uint32_t(std::min<size_t>(ds.bytes, 0xFFFFFFFFu));
+        stats->n_nodes = flat->total_nodes4();
+        stats->n_prims = flat->n_prims_in_bvh;
+        stats->scene_bytes = uint32_t(std::min<size_t>(ds->bytes, 0xFFFFFFFFu));
     }
     return RTTNW_OK;
 }

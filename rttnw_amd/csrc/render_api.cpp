@@ -19,6 +19,15 @@ static int render_tiles_any(::rttnw_scene* s, DeviceState* d, const rttnw_camera
     return render_tiles_t<double>(s, d, cam, p, d_packed, stream, stats, sync_for_stats, prepare_only);
 }
 
+// The linear image of a blocking render (d->linear, in the render's precision) to the caller's doubles: an f32 image is widened through a temporary.
+static hipError_t copy_linear_out(const DeviceState* d, uint32_t precision, size_t npx, double* out) {
+    if (precision != RTTNW_F32) return hipMemcpy(out, d->linear.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    std::vector<float> tmp(npx * 3);
+    const hipError_t e = hipMemcpy(tmp.data(), d->linear.p, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    for (size_t i = 0; i < npx * 3; ++i) out[i] = double(tmp[i]);
+    return e;
+}
+
 void device_release(DeviceState* d) {
     if (!d) return;
     DeviceGuard restore;
@@ -77,7 +86,7 @@ int device_commit(::rttnw_scene* s, std::string& err) {
         return RTTNW_ERR_HIP;
     }
     if (s->device) { device_release(s->device); s->device = nullptr; } // a commit that failed half-way and is retried
-    // The scene arrays are uploaded per precision on first use (render), see render_tiles_t.
+    // The scene arrays are uploaded per precision on first use (render), see bind_scene.
     return device_state_create(s->device, err);
 }
 
@@ -249,21 +258,9 @@ int rttnw_render(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_param
     rc = rttnw_untile_device(p->width, p->height, 1, p->precision, d->packed.p, d->linear.p, d->rgba.p, nullptr);
     if (rc) return rc;
     e = hipDeviceSynchronize();
+    if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, d->rgba.p, npx * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_linear_rgb) e = rt::copy_linear_out(d, p->precision, npx, out_linear_rgb);
     if (e != hipSuccess) { rt::set_last_error(std::string("render: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
-    if (out_rgba8) {
-        e = hipMemcpy(out_rgba8, d->rgba.p, npx * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { rt::set_last_error(std::string("render: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
-    }
-    if (out_linear_rgb) {
-        if (p->precision != RTTNW_F32) {
-            e = hipMemcpy(out_linear_rgb, d->linear.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-        } else {
-            std::vector<float> tmp(npx * 3);
-            e = hipMemcpy(tmp.data(), d->linear.p, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
-            for (size_t i = 0; i < npx * 3; ++i) out_linear_rgb[i] = double(tmp[i]);
-        }
-        if (e != hipSuccess) { rt::set_last_error(std::string("render: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
-    }
     return RTTNW_OK;
 }
 
@@ -288,15 +285,7 @@ int rttnw_render_adaptive(rttnw_scene* s, const rttnw_camera_desc* cam, const rt
     if (out_rgba8) e = hipMemcpy(out_rgba8, d->rgba.p, npx * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && out_spp) e = hipMemcpy(out_spp, d->ad_spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess && out_stderr_rgb) e = hipMemcpy(out_stderr_rgb, d->ad_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_linear_rgb) {
-        if (p->precision != RTTNW_F32) {
-            e = hipMemcpy(out_linear_rgb, d->linear.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-        } else {
-            std::vector<float> tmp(npx * 3);
-            e = hipMemcpy(tmp.data(), d->linear.p, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
-            for (size_t i = 0; i < npx * 3; ++i) out_linear_rgb[i] = double(tmp[i]);
-        }
-    }
+    if (e == hipSuccess && out_linear_rgb) e = rt::copy_linear_out(d, p->precision, npx, out_linear_rgb);
     if (e != hipSuccess) { rt::set_last_error(std::string("render_adaptive: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
     return RTTNW_OK;
 }
@@ -559,15 +548,7 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
     if (stats && use_peer && (distinct.size() > 1 || force_rccl)) stats[0].reserved |= 0x100u | (fell_back ? 0x200u : 0u);
     HIP_TRY(hipSetDevice(root->device));
     if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, root->rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_linear_rgb) {
-        if (p.precision != RTTNW_F32) {
-            HIP_TRY(hipMemcpy(out_linear_rgb, root->linear.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-        } else {
-            std::vector<float> tmp(npx * 3);
-            HIP_TRY(hipMemcpy(tmp.data(), root->linear.p, npx * 3 * sizeof(float), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < npx * 3; ++i) out_linear_rgb[i] = double(tmp[i]);
-        }
-    }
+    if (out_linear_rgb) HIP_TRY(copy_linear_out(root, p.precision, npx, out_linear_rgb));
     return RTTNW_OK;
 }
 

@@ -286,11 +286,45 @@ int device_state_create(DeviceState*& out, std::string& err);
 // graph lowered without them (made once, under the scene's mutex).  render_api.cpp.
 int reference_frame_scene(::rttnw_scene* s, const FlatScene*& flat);
 
-template <typename R> DeviceScene<R>& scene_of(DeviceState* d);
-template <> inline DeviceScene<float>& scene_of<float>(DeviceState* d) { return d->s32; }
-template <> inline DeviceScene<double>& scene_of<double>(DeviceState* d) { return d->s64; }
+void fill_layout(uint32_t w, uint32_t h, uint32_t world, rttnw_tile_layout& L);
+int validate(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p);
 
-template <typename R> CameraRec<R> narrow_camera(const CameraRec<double>& c) {
+// The launch code of one precision (render_tiles.hpp), instantiated in render_f32.hip / render_f64.hip — and, for double, a second
+// time in render_f64_strict.hip in the namespace rt::ieee_strict (rt_core.hpp: the two builds of the f64 arithmetic).
+inline namespace RT_ARITH_NS {
+// What every entry point that launches over a scene starts with: the device made current, the lowering this build walks and its arrays on the
+// device, uploaded on first use.
+template <typename R> int bind_scene(::rttnw_scene* s, DeviceState* d, const FlatScene*& flat, DeviceScene<R>*& ds) {
+    HIP_TRY(hipSetDevice(d->device));
+    flat = &s->flat;
+    if constexpr (sizeof(R) == 4) ds = &d->s32; else ds = &d->s64;
+#if defined(RT_STRICT_F64)
+    // the IEEE-strict build walks the lowering that tests every object in the reference's frame (render_api.cpp reference_frame_scene)
+    if (int rc = reference_frame_scene(s, flat)) return rc;
+    if (flat != &s->flat) ds = &d->s64_ref;
+#endif
+    return ds->ready ? 0 : ds->upload(*flat);
+}
+// The constants of a render of `p` over tile layout L (fill_layout); the chunk schedule, the jobs and the LDS staging follow where they are planned.
+// (probe_path_t sets sample_begin and scene_flags back to 0: a field added here that path_begin reads needs a look there)
+inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, const rttnw_tile_layout& L) {
+    RenderConsts rc{};
+    rc.width = p->width; rc.height = p->height; rc.spp = p->spp; rc.max_depth = p->max_depth;
+    rc.tiles_x = L.tiles_x; rc.tiles_y = L.tiles_y; rc.n_tiles = L.n_tiles;
+    rc.tile_rank = p->tile_rank; rc.tile_world = p->tile_world;
+    rc.my_tiles = L.n_tiles > p->tile_rank ? (L.n_tiles - p->tile_rank + p->tile_world - 1) / p->tile_world : 0;
+    rc.quirks = p->quirks; rc.seed = p->seed; rc.stack_depth = flat.stack_depth;
+    rc.profile = p->collect_counters;
+    rc.sample_begin = p->sample_begin;
+    rc.scene_flags = flat.moving.empty() ? SCENE_NO_TIME : 0u;
+    rc.inv_width = 1.0 / double(p->width); rc.inv_height = 1.0 / double(p->height);
+    rc.div_tiles_x = make_fastdiv(std::max<uint32_t>(1u, rc.tiles_x));
+    return rc;
+}
+template <typename R> CameraRec<R> camera_of(const rttnw_camera_desc* cam) {
+    CameraRec<double> c;
+    make_camera(cam->lookfrom, cam->lookat, cam->view_up, cam->vertical_fov, cam->aspect_ratio, cam->aperture, cam->focus_distance, cam->open_time,
+                cam->close_time, c);
     CameraRec<R> o;
     for (int k = 0; k < 3; ++k) {
         o.origin[k] = R(c.origin[k]); o.lower_left_corner[k] = R(c.lower_left_corner[k]);
@@ -300,12 +334,6 @@ template <typename R> CameraRec<R> narrow_camera(const CameraRec<double>& c) {
     return o;
 }
 
-void fill_layout(uint32_t w, uint32_t h, uint32_t world, rttnw_tile_layout& L);
-int validate(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p);
-
-// The launch code of one precision (render_tiles.hpp), instantiated in render_f32.hip / render_f64.hip — and, for double, a second
-// time in render_f64_strict.hip in the namespace rt::ieee_strict (rt_core.hpp: the two builds of the f64 arithmetic).
-inline namespace RT_ARITH_NS {
 template <typename R>
 int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
                    rttnw_stats* stats, bool sync_for_stats = true, bool prepare_only = false, const AdaptivePass* adaptive = nullptr);

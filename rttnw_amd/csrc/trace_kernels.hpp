@@ -19,6 +19,7 @@
 #pragma once
 #include "render_common.hpp"
 #include "adaptive.hpp"
+#include "launch_plan.hpp" // block sizes, LDS sizes and SLOTS_PER_WAVE: what the host plans a launch by
 #ifndef RT_ASYNC_SHADE
 #define RT_ASYNC_SHADE 1 // the lane-owns-path kernel leaves its walk loop for a shade phase once at most RT_ASYNC_SLACK walks are unfinished; those are
                          // SUSPENDED — their lanes skip the phase and walk on in the next one (0: every round waits for its longest walk, rounds 1-4)
@@ -34,12 +35,6 @@
 #endif
 #include "trace_tally.hpp"
 
-#ifndef RT_WAVE_QUANT
-#define RT_WAVE_QUANT 2 // which decoupled kernels walk the quantised records (rt_types.hpp Bvh4QNode): 1 the f64 ones, 2 all, 0 none.  (Mid-round-4: f64 +4 / +7 %,
-                        // f32 -2 % against the f32 records — and +4 % for half-precision node-local records, 80 of 128 bytes a visit, which the f32 kernel walked
-                        // for a while.  At the round's end — no slot tests, no instance code, 13-real path slots — the f32 kernel moves 6.2 TB/s and little else,
-                        // and half the node bytes are worth +10 %: spheres_1m f32 433 -> 476 Msamples/s on these records; the half-precision ones are gone.)
-#endif
 #ifndef RT_WAVE_RETIRE
 #define RT_WAVE_RETIRE 8 // finished rays that end a burst while rays are queued (the hand-over of their lanes).  Round 4's end, spheres_1m f64 / f32 Msamples/s:
                          // 4 / 6 / 8 / 12 / 16 / 24 / 32 -> 342 / 340 / 342 / 339 / 336 / 323 / 308 and 490 / 484 / 489 / 489 / 483 / 464 / 449
@@ -47,9 +42,6 @@
 #ifndef RT_WAVE_STEPS
 #define RT_WAVE_STEPS 5 // node steps per trip of the decoupled kernel's bursts (2 / 3 / 4 / 6: 302 / 321 / 325 / 330 Msamples/s in round 1; round 4's end, spheres_1m
                         // f64 / strict / f32 with 4 / 5 / 6: 334 / 340 / 332, 331 / 332 / 331, 481 / 481 / 476; 8: f32 442)
-#endif
-#ifndef RT_F64_BLOCK
-#define RT_F64_BLOCK 1024 // threads per block of the LDS-resident f64 kernel (4 waves/SIMD at 128 VGPRs; see the Makefile's f64 flags and profiles/r03/README.md)
 #endif
 
 namespace rt {
@@ -179,51 +171,11 @@ template <typename T, typename V> __device__ __forceinline__ void pool_st(T* p, 
     *p = T(v);
 #endif
 }
-constexpr int TRACE_BLOCK = 256;
-#ifndef RT_SLOTS
-#define RT_SLOTS 128
-#endif
-constexpr uint32_t SLOTS_PER_WAVE = RT_SLOTS; // paths owned by one wave64: 64 being traversed + up to 64 queued
-constexpr uint32_t QCAP = RT_SLOTS;           // capacity of a wave's ray queue and hit queue (entries)
-static_assert(QCAP == SLOTS_PER_WAVE, "a slot has at most one ray or hit in flight: the queues never hold more entries than the wave has slots");
-
 // Path state of a slot, in global memory (L2-resident), struct-of-arrays over all slots of the launch.
 // (no radiance: a path's value is the term of its last bounce, rt_core.hpp path_shade — round 4; 13 reals a slot instead of 16)
 enum : uint32_t { PR_TX = 0, PR_TY, PR_TZ, PR_AX, PR_AY, PR_AZ, PR_COUNT }; // (the slot's RAY stays in LDS from its emit to its shade: the wave's ray arena, below)
 enum : uint32_t { PU_KEY_LO = 0, PU_KEY_HI, PU_BOUNCE, PU_PXROW, PU_S, PU_SEND, PU_JOB_LO, PU_JOB_HI, PU_COUNT };
-// bytes of LDS one wave needs: ray queue (7 reals + slot), hit queue (t + prim + inst + meta), traversal stacks
-// LDS stack entries of the decoupled kernel: 16 for f32; 13 for f64, whose queues are twice as wide: THREE 256-thread blocks must fit a CU's 160 KB,
-// or the kernel runs at 2 waves per SIMD however few registers it is held to.  gfx950 hands LDS out in granules of 1280 BYTES (128 to a CU): a block
-// of 42 granules (53 760 B) fits three times, one of 54 016 B does not — measured in round 5 (profiles/r05/README.md: 445 against 344 Msamples/s
-// on spheres_1m; hipOccupancyMaxActiveBlocksPerMultiprocessor says 3 for both).  Rounds 1-4 asked for 54 272 B with 12 entries — the runtime's
-// answer was 3, SQ_WAVE_CYCLES said 2 of 3 waves were ever resident — so the f64 decoupled kernels ran a third short of their waves: the ray slot
-// queue as bytes (slots are < 128) and 13 entries make it 53 760 B exactly (the spill strip in global memory takes the rare deeper entries).
-#ifndef RT_F64_WAVE_STACK
-#define RT_F64_WAVE_STACK 13
-#endif
-#ifndef RT_WAVE_LDS_PAD
-#define RT_WAVE_LDS_PAD 0 // experiments: unused bytes per wave (where the LDS stops holding three blocks per CU)
-#endif
-template <typename R> __host__ __device__ constexpr uint32_t wave_stack_entries() { return sizeof(R) == 8 ? uint32_t(RT_F64_WAVE_STACK) : LDS_STACK_ENTRIES; }
-template <typename R> __host__ __device__ constexpr uint32_t wave_lds_bytes(uint32_t stack_depth, bool no_time = false) {
-    // ray queue (7 reals) + hit t | hit prim, inst, meta (words) | ray slot (bytes) | stack: + the spare slot
-    return (no_time ? 7u : 8u) * QCAP * uint32_t(sizeof(R)) + 3u * QCAP * 4u + QCAP + (wave_stack_entries<R>() + 1u) * 64u * 4u + RT_WAVE_LDS_PAD;
-}
-constexpr uint32_t LDS_GRANULE_BYTES = 1280u, LDS_BYTES_PER_CU = 160u * 1024u; // gfx950: 128 granules per CU
-__host__ __device__ constexpr uint32_t lds_blocks_per_cu(uint32_t block_bytes) {
-    return block_bytes == 0u ? 1024u : LDS_BYTES_PER_CU / ((block_bytes + LDS_GRANULE_BYTES - 1u) / LDS_GRANULE_BYTES * LDS_GRANULE_BYTES);
-}
-// waves of ONE block that fills a CU (the LEAN flavour of the decoupled kernel): as many as the CU's LDS granules hold, at most 16 (4 per SIMD)
-__host__ __device__ constexpr uint32_t wave_block_waves(uint32_t wave_bytes) {
-    uint32_t n = 16u;
-    while (n > 4u && (n * wave_bytes + LDS_GRANULE_BYTES - 1u) / LDS_GRANULE_BYTES > LDS_BYTES_PER_CU / LDS_GRANULE_BYTES) --n;
-    return n;
-}
-static_assert(RT_WAVE_LDS_PAD != 0 || lds_blocks_per_cu(wave_lds_bytes<double>(0) * 4u) >= 3u, "the f64 decoupled kernel's block must fit a CU's LDS three times");
-static_assert(lds_blocks_per_cu(wave_lds_bytes<float>(0) * 4u) >= 3u, "the f32 decoupled kernel's block must fit a CU's LDS three times");
-template <typename R> __host__ __device__ constexpr bool wave_walks_quantised() { return RT_WAVE_QUANT == 2 || (RT_WAVE_QUANT == 1 && sizeof(R) == 8); }
 constexpr uint32_t HIT_FRESH = 0x100u; // hit-queue meta: slot (8 bits) | FRESH | box face << 9
-static_assert(SLOTS_PER_WAVE <= 256u, "slot numbers travel as bytes");
 
 // The per-pixel sample loop of main.rs:202-229 as ONE persistent kernel in which PATHS ARE DECOUPLED FROM LANES.
 //

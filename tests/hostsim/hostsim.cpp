@@ -6,6 +6,7 @@
 #include "../../rttnw_amd/csrc/rt_core.hpp"
 #include "../../rttnw_amd/csrc/bvh_quant.hpp"
 #include "../../rttnw_amd/csrc/scene_handle.hpp"
+#include "../../rttnw_amd/csrc/launch_plan.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -749,6 +750,21 @@ int hostsim_scene_dims(rttnw_scene* s, uint32_t* out /* nodes, spheres, moving, 
 int hostsim_scene_flags(rttnw_scene* s) {
     if (!s || !s->committed) return RTTNW_ERR_INVALID;
     return (s->flat.lean() ? 1 : 0) | (s->flat.sphere_mat_is_index ? 2 : 0);
+}
+// The launch plan of a render of the committed scene (launch_plan.hpp plan_launch) as a struct of plain integers (tests/util.py LaunchPlanOut mirrors
+// it, field by field).  forced: 0 auto, 1 plain, 2 plainglobal, 3 wave.
+struct HostsimLaunchPlan {
+    uint32_t decoupled, lds, count, list, quantised, shapes, steps, block, lds_nodes, lds_recs[6], staged_bytes, lds_bytes, form_bits, n_nodes;
+};
+int hostsim_launch_plan(rttnw_scene* s, uint32_t real_bytes, int count, int listed, int forced, int wave_block, HostsimLaunchPlan* out) {
+    if (!s || !s->committed || (real_bytes != 4 && real_bytes != 8) || forced < 0 || forced > 3) return RTTNW_ERR_INVALID;
+    const LaunchPlan pl = plan_launch(s->flat, real_bytes, count != 0, listed != 0, KernelForm(forced), wave_block);
+    *out = HostsimLaunchPlan{};
+    out->decoupled = pl.decoupled; out->lds = pl.lds; out->count = pl.count; out->list = pl.list; out->quantised = pl.quantised;
+    out->shapes = uint32_t(pl.shapes); out->steps = uint32_t(pl.steps); out->block = uint32_t(pl.block); out->lds_nodes = pl.lds_nodes;
+    std::copy(pl.lds_recs, pl.lds_recs + 6, out->lds_recs);
+    out->staged_bytes = pl.staged_bytes; out->lds_bytes = pl.lds_bytes; out->form_bits = pl.form_bits; out->n_nodes = s->flat.total_nodes4();
+    return RTTNW_OK;
 }
 int hostsim_probe_path(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t px, uint32_t row,
                        uint32_t sample, double* out, uint32_t max_out) {

@@ -26,6 +26,8 @@ cases = [("spheres_1m", 200000)] if sys.argv[2] == "commit" else [("final_scene"
 for name, n in cases:
     sc, setup = util.build(b, sl, name, earth, n)
     if sys.argv[2] == "commit": continue
+    for real_bytes, form, count, listed in [(r, f, c, l) for r in (4, 8) for f in range(4) for c in (0, 1) for l in (0, 1)]:   # the launch plan of every form (launch_plan.hpp)
+        util.hostsim_launch_plan(lib, sc, real_bytes, count, listed, form, 832)
     for prec in (abi.F64, abi.F32):
         cam, p = util.params_for(setup, 24, 24, 3, precision=prec, seed=3, collect_counters=1)
         os.environ.pop("HOSTSIM_QUANT", None)

@@ -18,6 +18,28 @@ def hostsim_render(hostsim, sc, cam, p, n_threads=0):
     return lin, st
 
 
+class LaunchPlanOut(C.Structure):
+    """tests/hostsim/hostsim.cpp HostsimLaunchPlan: launch_plan.hpp's LaunchPlan as plain integers, and the scene's 4-wide node count."""
+    _fields_ = [(n, C.c_uint32) for n in ("decoupled", "lds", "count", "list", "quantised", "shapes", "steps", "block", "lds_nodes")] + \
+               [("lds_recs", C.c_uint32 * 6)] + [(n, C.c_uint32) for n in ("staged_bytes", "lds_bytes", "form_bits", "n_nodes")]
+
+    def key(self, **replace):
+        """The fields as a comparable tuple, some of them replaced."""
+        d = {n: (tuple(getattr(self, n)) if n == "lds_recs" else getattr(self, n)) for n, _ in self._fields_}
+        assert set(replace) <= set(d)
+        d.update(replace)
+        return tuple(sorted(d.items()))
+
+
+def hostsim_launch_plan(lib, sc, real_bytes, count=0, listed=0, forced=0, wave_block=0):
+    """The launch plan of a render of `sc` through the host build `lib` (a ctypes library).  forced: 0 auto, 1 plain, 2 plainglobal, 3 wave."""
+    lib.hostsim_launch_plan.restype = C.c_int
+    lib.hostsim_launch_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(LaunchPlanOut)]
+    out = LaunchPlanOut()
+    assert lib.hostsim_launch_plan(sc.handle, real_bytes, count, listed, forced, wave_block, C.byref(out)) == 0
+    return out
+
+
 def block_means(rgb, n):
     h, w, _ = rgb.shape
     bh, bw = h // n, w // n
