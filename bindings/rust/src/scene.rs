@@ -165,6 +165,19 @@ impl Scene {
         ok(unsafe { ffi::rttnw_render_features(self.raw, cam, p, f.albedo.as_mut_ptr(), f.normal.as_mut_ptr(), f.depth.as_mut_ptr(), f.alpha.as_mut_ptr(), ptr::null_mut()) })?;
         Ok(f)
     }
+    /// Pixels `[x0, x1) x [y0, y1)` of the frame `render` renders (`rttnw_render_region`): all of them, or those whose byte of `mask`
+    /// (window-sized, row-major, top row first) is nonzero — each bit-identical to the full render's; an unselected pixel is 0, 0, 0, 0.
+    /// Returns (RGBA8 of the window, row-major, top row first; stats).
+    pub fn render_region(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, x0: u32, y0: u32, x1: u32, y1: u32, mask: Option<&[u8]>) -> Result<(Vec<u8>, ffi::rttnw_stats)> {
+        let n = (x1.saturating_sub(x0) as usize) * (y1.saturating_sub(y0) as usize);
+        if mask.map_or(false, |m| m.len() != n) {
+            return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "render_region: the mask does not have the window's size".into() });
+        }
+        let mut rgba = vec![0u8; n * 4];
+        let mut stats = ffi::rttnw_stats::default();
+        ok(unsafe { ffi::rttnw_render_region(self.raw, cam, p, x0, y0, x1, y1, mask.map_or(ptr::null(), |m| m.as_ptr()), ptr::null_mut(), rgba.as_mut_ptr(), &mut stats) })?;
+        Ok((rgba, stats))
+    }
     /// The same image from the GPUs `devices` of this node (tile partition + RCCL gather inside the library).
     pub fn render_multi(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, devices: &[i32]) -> Result<(Vec<u8>, Vec<ffi::rttnw_stats>)> {
         let mut rgba = vec![0u8; p.width as usize * p.height as usize * 4];

@@ -40,7 +40,8 @@ extern "C" {
 #define RTTNW_ABI_VERSION 3 /* 2: 4-wide node records (n_nodes, debug_scene_nodes4), rttnw_render_multi
                              * 3: RTTNW_F64_STRICT, rttnw_shutdown, RTTNW_BVH_AUTO (the default builder), rttnw_stats.reserved is a bit mask
                              *    (below), validate() rejects t_min < 0
-                             * (rttnw_render_adaptive came later, without a version bump: a caller detects it by its symbol) */
+                             * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise and rttnw_render_region came later, without a
+                             *  version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -304,6 +305,33 @@ int rttnw_render_adaptive(rttnw_scene* s, const rttnw_camera_desc* cam, const rt
  *   RTTNW_ERR_UNSUPPORTED for collect_counters != 0; then whatever rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes). */
 int rttnw_render_features(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p,
                           double* out_albedo, double* out_normal, double* out_depth, double* out_alpha, rttnw_stats* stats);
+
+/* A window, or a pixel mask, of the frame rttnw_render renders — a preview of the area being worked on, a re-render of a few pixels, one
+ * frame split into windows across hosts — at the cost of the selected pixels, not of the frame.  The reference has no counterpart: its
+ * render() (main.rs:202-229) always walks the whole image.  (Came without a version bump, like rttnw_render_adaptive: detect it by its symbol.)
+ *
+ * Frame and window.  The frame is the p->width x p->height frame of rttnw_render, with the same camera and the same keys (pixel, sample,
+ *   seed).  The window is its pixels [x0, x1) x [y0, y1), row 0 = top.  `mask` (optional): (x1-x0)*(y1-y0) bytes, row-major, top row first,
+ *   nonzero = selected; NULL selects every pixel of the window.
+ * Selected pixels.  Samples [sample_begin, sample_begin + spp) under the chunk schedule of spp and spp_chunk, ONE chain of chunk sums in chunk
+ *   order, divided by spp: exactly the jobs rttnw_render runs for that pixel.  Its linear value and its RGBA8 are BIT-IDENTICAL to
+ *   rttnw_render(s, cam, p) at that pixel — for every `precision`, every kernel form and every launch split (RTTNW_CHUNK_SUM_BUDGET).
+ *   The trace runs over the list of 2x2 pixel blocks that hold a selected pixel (an unselected pixel of such a block traces nothing).
+ * Unselected pixels of the window.  Linear 0, 0, 0 and RGBA8 0, 0, 0, 0: a rendered pixel has alpha 255, so alpha tells the two apart.
+ * Outputs (each optional, sized by the WINDOW; row-major, top row first): out_linear_rgb (x1-x0)*(y1-y0)*3 doubles, out_rgba8
+ *   (x1-x0)*(y1-y0)*4 bytes.  Blocking.  `stats`: samples = selected pixels x spp, kernel_ms = device time of everything the call runs (the
+ *   list building and one small copy to the host included), reserved = the kernel form, as for rttnw_render; the scene's sizes as usual.
+ * All-zero mask.  RTTNW_OK with the outputs cleared and stats->samples == 0; no trace kernel is launched.
+ * Memory.  Beyond one selection byte per frame pixel (and the block list: a word per 2x2 block), everything the call allocates is sized by the
+ *   listed blocks or by the window: chunk sums 4 per listed block and chunk, running sums 4 per listed block.
+ * Refusals, before the device is touched, in this order: RTTNW_ERR_INVALID for a NULL p; RTTNW_ERR_INVALID for x0 >= x1, y0 >= y1,
+ *   x1 > width or y1 > height; RTTNW_ERR_INVALID for reserved0 != 0 or tile_world != 1; RTTNW_ERR_UNSUPPORTED for collect_counters != 0 (the
+ *   active-list kernels do not tally); then whatever rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes).
+ * The first call whose camera shutter reaches outside the trees' interval rebuilds them, and the strict build walks its own lowering,
+ *   exactly as for rttnw_render; one render in flight per scene, as before. */
+int rttnw_render_region(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p,
+                        uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const uint8_t* mask,
+                        double* out_linear_rgb, uint8_t* out_rgba8, rttnw_stats* stats);
 
 /* A denoiser for the images above: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by the feature buffers of
  * rttnw_render_features and, optionally, by the variance of the pixel means (the colour stop of SVGF, Schied et al. 2017) — the square of

@@ -7,6 +7,8 @@ Optional extras (not in the reference): --spp, --width, --precision f32|f64, --o
 A + R * mean in every channel, --spp being the cap.  --denoise [--denoise-iterations N] filters the image with rttnw_denoise, guided by
 first-hit feature buffers of min(spp, 16) samples (and, with --noise, by the adaptive render's standard errors); --features PREFIX writes
 PREFIX_albedo.png, PREFIX_normal.png (n * 0.5 + 0.5), PREFIX_depth.png (normalised to the farthest hit) and PREFIX_alpha.png.
+--window X0,Y0,X1,Y1 renders pixels [X0, X1) x [Y0, Y1) of the frame only (rttnw_render_region) and writes that window as the image; it does
+not combine with --noise, --denoise, --features or --passes.
 """
 import argparse
 import sys
@@ -27,6 +29,15 @@ Possible scenes:
 \t- 9: final_scene"""
 
 
+def parse_window(text):
+    """'X0,Y0,X1,Y1' -> four non-negative integers with X0 < X1 and Y0 < Y1, or None."""
+    parts = text.split(",")
+    if len(parts) != 4 or not all(s.strip().isdigit() for s in parts):
+        return None
+    x0, y0, x1, y1 = (int(s) for s in parts)
+    return (x0, y0, x1, y1) if x0 < x1 and y0 < y1 else None
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(add_help=True, usage=USAGE)
     ap.add_argument("scene", type=int)
@@ -45,11 +56,24 @@ def main(argv=None):
     ap.add_argument("--denoise-iterations", type=int, default=5, help="a-trous passes of the denoiser (0..8)")
     ap.add_argument("--features", default=None, metavar="PREFIX", help="write the first-hit feature buffers as PREFIX_albedo.png, "
                     "PREFIX_normal.png, PREFIX_depth.png, PREFIX_alpha.png")
+    ap.add_argument("--window", default=None, metavar="X0,Y0,X1,Y1", help="render pixels [X0, X1) x [Y0, Y1) of the frame only (row 0 = top) "
+                    "and write that window as the image")
     try:
         args = ap.parse_args(argv)
     except SystemExit:
         print("There was an error", file=sys.stderr)   # DummyError, main.rs:260-268
         raise
+    window = None
+    if args.window is not None:
+        window = parse_window(args.window)
+        if window is None:
+            print("--window wants X0,Y0,X1,Y1: four non-negative integers with X0 < X1 and Y0 < Y1, got %r" % args.window, file=sys.stderr)
+            return 1
+        clash = [name for name, on in (("--noise", args.noise is not None), ("--denoise", args.denoise), ("--features", args.features is not None),
+                                       ("--passes", args.passes > 1)) if on]
+        if clash:
+            print("--window does not combine with %s: it renders pixels of the plain frame only" % ", ".join(clash), file=sys.stderr)
+            return 1
     from PIL import Image
     from . import abi, library, render
     from .abi import CameraDesc
@@ -71,6 +95,16 @@ def main(argv=None):
     cam.aspect_ratio = setup.width / setup.height
     p = make_params(w, h, args.spp or setup.spp, background=tuple(setup.background), seed=args.seed,
                     precision={"f32": abi.F32, "f64": abi.F64, "f64strict": abi.F64_STRICT}[args.precision])
+    if window is not None:
+        x0, y0, x1, y1 = window
+        if x1 > w or y1 > h:
+            print("--window %s reaches outside the %dx%d frame" % (args.window, w, h), file=sys.stderr)
+            return 1
+        _, rgba, st = render.render_region(sc, cam, p, x0, y0, x1, y1)
+        Image.fromarray(np.ascontiguousarray(rgba), "RGBA").save(args.out)
+        print("%.3fs (window %dx%d at (%d, %d) of %dx%d: %d samples, kernels %.1f ms)"
+              % (time.time() - t0, x1 - x0, y1 - y0, x0, y0, w, h, st.samples, st.kernel_ms))
+        return 0
     features = None
     if args.denoise or args.features:
         if args.denoise and args.passes > 1:

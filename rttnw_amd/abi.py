@@ -113,6 +113,8 @@ PRODUCT_FUNCS = [
                                   C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("render_features", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.POINTER(Stats)]),
+    ("render_region", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("denoise", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.POINTER(Denoise), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("render_tiles_device", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_void_p,

@@ -19,11 +19,12 @@ static int render_tiles_any(::rttnw_scene* s, DeviceState* d, const rttnw_camera
     return render_tiles_t<double>(s, d, cam, p, d_packed, stream, stats, sync_for_stats, prepare_only);
 }
 
-// The linear image of a blocking render (d->linear, in the render's precision) to the caller's doubles: an f32 image is widened through a temporary.
-static hipError_t copy_linear_out(const DeviceState* d, uint32_t precision, size_t npx, double* out) {
-    if (precision != RTTNW_F32) return hipMemcpy(out, d->linear.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+// The linear image of a blocking render (`linear`: d->linear or d->rg_linear, in the render's precision) to the caller's doubles: an f32 image is
+// widened through a temporary.
+static hipError_t copy_linear_out(const DevBuf<uint8_t>& linear, uint32_t precision, size_t npx, double* out) {
+    if (precision != RTTNW_F32) return hipMemcpy(out, linear.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
     std::vector<float> tmp(npx * 3);
-    const hipError_t e = hipMemcpy(tmp.data(), d->linear.p, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    const hipError_t e = hipMemcpy(tmp.data(), linear.p, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
     for (size_t i = 0; i < npx * 3; ++i) out[i] = double(tmp[i]);
     return e;
 }
@@ -259,7 +260,7 @@ int rttnw_render(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_param
     if (rc) return rc;
     e = hipDeviceSynchronize();
     if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, d->rgba.p, npx * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_linear_rgb) e = rt::copy_linear_out(d, p->precision, npx, out_linear_rgb);
+    if (e == hipSuccess && out_linear_rgb) e = rt::copy_linear_out(d->linear, p->precision, npx, out_linear_rgb);
     if (e != hipSuccess) { rt::set_last_error(std::string("render: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
     return RTTNW_OK;
 }
@@ -285,8 +286,33 @@ int rttnw_render_adaptive(rttnw_scene* s, const rttnw_camera_desc* cam, const rt
     if (out_rgba8) e = hipMemcpy(out_rgba8, d->rgba.p, npx * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && out_spp) e = hipMemcpy(out_spp, d->ad_spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess && out_stderr_rgb) e = hipMemcpy(out_stderr_rgb, d->ad_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_linear_rgb) e = rt::copy_linear_out(d, p->precision, npx, out_linear_rgb);
+    if (e == hipSuccess && out_linear_rgb) e = rt::copy_linear_out(d->linear, p->precision, npx, out_linear_rgb);
     if (e != hipSuccess) { rt::set_last_error(std::string("render_adaptive: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
+    return RTTNW_OK;
+}
+
+int rttnw_render_region(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                        const uint8_t* mask, double* out_linear_rgb, uint8_t* out_rgba8, rttnw_stats* stats) {
+    // the region's own arguments first, in the header's order: their refusals need no device (nor a committed scene)
+    if (!p) { rt::set_last_error("render_region: NULL argument"); return RTTNW_ERR_INVALID; }
+    if (x0 >= x1 || y0 >= y1 || x1 > p->width || y1 > p->height) {
+        rt::set_last_error("render_region: the window [x0, x1) x [y0, y1) must be non-empty and lie inside the width x height frame");
+        return RTTNW_ERR_INVALID;
+    }
+    if (p->reserved0 != 0) { rt::set_last_error("render_region: reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (p->tile_world != 1) { rt::set_last_error("render_region: host-output form needs tile_world == 1"); return RTTNW_ERR_INVALID; }
+    if (p->collect_counters != 0) { rt::set_last_error("render_region: collect_counters is not supported (the active-list kernels do not tally)"); return RTTNW_ERR_UNSUPPORTED; }
+    if (int rc = rt::validate(s, cam, p)) return rc;
+    rt::DeviceState* d = s->device;
+    int rc = p->precision == RTTNW_F32          ? rt::render_region_t<float>(s, cam, p, x0, y0, x1, y1, mask, stats)
+             : p->precision == RTTNW_F64_STRICT ? rt::ieee_strict::render_region_t<double>(s, cam, p, x0, y0, x1, y1, mask, stats)
+                                                : rt::render_region_t<double>(s, cam, p, x0, y0, x1, y1, mask, stats);
+    if (rc) return rc;
+    const size_t wpx = size_t(x1 - x0) * (y1 - y0);
+    hipError_t e = hipSuccess;
+    if (out_rgba8) e = hipMemcpy(out_rgba8, d->rg_rgba.p, wpx * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_linear_rgb) e = rt::copy_linear_out(d->rg_linear, p->precision, wpx, out_linear_rgb);
+    if (e != hipSuccess) { rt::set_last_error(std::string("render_region: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
     return RTTNW_OK;
 }
 
@@ -548,7 +574,7 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
     if (stats && use_peer && (distinct.size() > 1 || force_rccl)) stats[0].reserved |= 0x100u | (fell_back ? 0x200u : 0u);
     HIP_TRY(hipSetDevice(root->device));
     if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, root->rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_linear_rgb) HIP_TRY(copy_linear_out(root, p.precision, npx, out_linear_rgb));
+    if (out_linear_rgb) HIP_TRY(copy_linear_out(root->linear, p.precision, npx, out_linear_rgb));
     return RTTNW_OK;
 }
 

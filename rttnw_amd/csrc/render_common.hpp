@@ -268,13 +268,19 @@ struct DeviceState {
     DevBuf<uint8_t> packed, linear, rgba;
     // rttnw_render_adaptive: per packed pixel the noise state (adaptive.hpp) and the active bit, the block list and its scan, the maps
     DevBuf<uint8_t> ad_state, ad_active, ad_quads, ad_scan, ad_spp, ad_stderr;
+    // rttnw_render_region: the caller's mask (window-sized), the selection byte per packed pixel, the running sums per list slot and the
+    // window-sized outputs.  (The block list and its scan are ad_quads / ad_scan: scratch that every user builds anew before it reads it.)
+    DevBuf<uint8_t> rg_mask, rg_select, rg_sums, rg_linear, rg_rgba;
 };
-// What render_tiles_t needs to run one pass of rttnw_render_adaptive (render_tiles.hpp render_adaptive_t): the adaptive resolve step in place
-// of resolve_kernel and, for a refinement pass, the active-list instantiation of the scene's kernel over `quads`.
-struct AdaptivePass {
-    const uint32_t* quads = nullptr; // nullptr: pass 0, every pixel of the rank in the render's own job numbering
+// What render_tiles_t needs to run a pass that is not a plain render's (render_tiles.hpp): a resolve step of the pass's own in place of
+// resolve_kernel and, with `quads`, the active-list instantiation of the scene's kernel over that list of 2x2 blocks.
+//   state != nullptr  a pass of rttnw_render_adaptive (render_adaptive_t): adaptive_resolve_kernel, which keeps the noise state
+//   state == nullptr  rttnw_render_region (render_region_t): region_resolve_kernel; d_packed holds the running sums BY LIST SLOT
+struct ListPass {
+    const uint32_t* quads = nullptr; // nullptr: pass 0 of an adaptive render, every pixel of the rank in the render's own job numbering
     uint32_t n_quads = 0;
     bool first = true;               // pass 0: the running sums and the noise state start here
+    bool clock_started = false;      // the caller recorded d->ev0 itself, before it built the list
     AdaptivePixel* state = nullptr;
     uint8_t* active = nullptr;
     uint32_t cap = 0;
@@ -336,7 +342,7 @@ template <typename R> CameraRec<R> camera_of(const rttnw_camera_desc* cam) {
 
 template <typename R>
 int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
-                   rttnw_stats* stats, bool sync_for_stats = true, bool prepare_only = false, const AdaptivePass* adaptive = nullptr);
+                   rttnw_stats* stats, bool sync_for_stats = true, bool prepare_only = false, const ListPass* adaptive = nullptr);
 template <typename R>
 int probe_path_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t px, uint32_t row, uint32_t sample,
                  double* out, uint32_t max_out);
@@ -347,8 +353,14 @@ template <typename R>
 int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, rttnw_stats* stats);
 extern template int render_adaptive_t<float>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
 extern template int render_adaptive_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
-extern template int render_tiles_t<float>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const AdaptivePass*);
-extern template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const AdaptivePass*);
+// rttnw_render_region's device half: selection, list, trace, resolve; the window's image on the device (d->rg_linear, d->rg_rgba)
+template <typename R>
+int render_region_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                    const uint8_t* mask, rttnw_stats* stats);
+extern template int render_region_t<float>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*, rttnw_stats*);
+extern template int render_region_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*, rttnw_stats*);
+extern template int render_tiles_t<float>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const ListPass*);
+extern template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const ListPass*);
 extern template int probe_path_t<float>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
 extern template int probe_path_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
 extern template int untile_launch<float>(uint32_t, uint32_t, uint32_t, const void*, void*, uint8_t*, hipStream_t);
@@ -360,15 +372,19 @@ extern template int untile_launch<double>(uint32_t, uint32_t, uint32_t, const vo
 namespace ieee_strict {
 template <typename R>
 int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
-                   rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const AdaptivePass* adaptive = nullptr);
+                   rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const ListPass* adaptive = nullptr);
 template <typename R>
 int probe_path_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t px, uint32_t row, uint32_t sample,
                  double* out, uint32_t max_out);
-extern template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const AdaptivePass*);
+extern template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const ListPass*);
 extern template int probe_path_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
 template <typename R>
 int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, rttnw_stats* stats);
 extern template int render_adaptive_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
+template <typename R>
+int render_region_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                    const uint8_t* mask, rttnw_stats* stats);
+extern template int render_region_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*, rttnw_stats*);
 } // namespace ieee_strict
 #endif
 

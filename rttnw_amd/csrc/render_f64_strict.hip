@@ -13,9 +13,11 @@
 namespace rt {
 inline namespace RT_ARITH_NS {
 template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool,
-                                    const AdaptivePass*);
+                                    const ListPass*);
 template int untile_launch<double>(uint32_t, uint32_t, uint32_t, const void*, void*, uint8_t*, hipStream_t); // (render_adaptive_t's)
 template int render_adaptive_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
+template int render_region_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*,
+                                     rttnw_stats*);
 template int probe_path_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
 } // namespace RT_ARITH_NS
 } // namespace rt

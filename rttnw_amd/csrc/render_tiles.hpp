@@ -2,6 +2,7 @@
 // the per-bounce probe and the un-tile launch, as templates over the arithmetic type.
 #pragma once
 #include "trace_kernels.hpp"
+#include "region_kernels.hpp"
 
 namespace rt {
 inline namespace RT_ARITH_NS {
@@ -116,10 +117,14 @@ int launch_pass(DeviceState* d, DeviceScene<R>& ds, const FlatScene& flat, const
     return 0;
 }
 
-// ... and the step behind it: the pass's chunk sums continue every pixel's chain in d_packed (an adaptive pass: and its noise state)
+// ... and the step behind it: the pass's chunk sums continue every pixel's chain in d_packed (an adaptive pass: and its noise state; a
+// region render: in the running sums by list slot)
 template <typename R>
-int resolve_pass(DeviceState* d, const RenderConsts& rc, const rttnw_tile_layout& L, const AdaptivePass* ad, void* d_packed, bool first, bool last, hipStream_t stream) {
-    if (ad)
+int resolve_pass(DeviceState* d, const RenderConsts& rc, const rttnw_tile_layout& L, const ListPass* ad, void* d_packed, bool first, bool last, hipStream_t stream) {
+    if (ad && !ad->state)
+        hipLaunchKernelGGL(region_resolve_kernel<R>, dim3((rc.jobs_per_chunk + 255) / 256), dim3(256), 0, stream, (const R*)d->partial.p, (R*)d_packed,
+                           ad->quads, rc.n_chunks, rc.jobs_per_chunk, uint32_t(first), uint32_t(last), rc.spp);
+    else if (ad)
         hipLaunchKernelGGL(adaptive_resolve_kernel<R>, dim3((rc.jobs_per_chunk + 255) / 256), dim3(256), 0, stream, (const R*)d->partial.p, (R*)d_packed,
                            ad->state, ad->active, ad->quads, rc, rc.jobs_per_chunk, uint32_t(first && ad->first), uint32_t(last), ad->cap, ad->rel_error,
                            ad->abs_error);
@@ -170,7 +175,7 @@ int fill_stats(DeviceState* d, const DeviceScene<R>& ds, const FlatScene& flat, 
 // that no allocation (a device-wide synchronisation) sits between two ranks' kernels.
 template <typename R>
 int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
-                   rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const AdaptivePass* ad) {
+                   rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const ListPass* ad) {
     const FlatScene* flat = nullptr;
     DeviceScene<R>* ds = nullptr;
     if (int rc = bind_scene<R>(s, d, flat, ds)) return rc;
@@ -180,7 +185,7 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
     // The render's chunk schedule (a function of spp alone)
     plan_chunks(rc, p->spp, p->spp_chunk);
     const uint32_t total_chunks = rc.n_chunks;
-    // (an adaptive refinement pass keeps the sums of its listed blocks only: 4 per block and chunk)
+    // (an adaptive refinement pass and a region render keep the sums of their listed blocks only: 4 per block and chunk)
     const bool listed = ad && ad->quads, count = p->collect_counters != 0;
     if (listed && count) { set_last_error("render: an active-list pass cannot collect counters"); return RTTNW_ERR_UNSUPPORTED; }
     uint32_t per_launch = 0;
@@ -192,7 +197,7 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
     rc.lds_nodes = pl.lds_nodes;
     for (int k = 0; k < 6; ++k) rc.lds_recs[k] = pl.lds_recs[k];
     if (!prepare_only) HIP_TRY(hipMemsetAsync(d->job_counter.p, 0, sizeof(unsigned long long) + sizeof(DeviceCounters), stream));
-    if (stats && !prepare_only) HIP_TRY(hipEventRecord(d->ev0.get(), stream));
+    if (stats && !prepare_only && !(ad && ad->clock_started)) HIP_TRY(hipEventRecord(d->ev0.get(), stream));
     for (uint32_t c0 = 0; c0 < total_chunks; c0 += per_launch) {
         rc.chunk_base = c0;
         rc.n_chunks = std::min(per_launch, total_chunks - c0);
@@ -274,7 +279,7 @@ int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
     uint32_t* totals = wave_base + n_waves;
     const uint32_t* quads = (const uint32_t*)d->ad_quads.p;
 
-    AdaptivePass ad;
+    ListPass ad;
     ad.state = (AdaptivePixel*)d->ad_state.p;
     ad.active = d->ad_active.p;
     ad.cap = p->spp;
@@ -321,13 +326,84 @@ int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
     return RTTNW_OK;
 }
 
+// rttnw_render_region (include/rttnw_hip.h has the contract, DESIGN.md §10c the why).  The selected pixels of the window become the list of 2x2
+// blocks that hold one (region_kernels.hpp region_select_kernel, then the compaction kernels of the adaptive passes; one 8-byte copy gives the host
+// the list's length), and render_tiles_t traces that list with its own kernel choice, chunk schedule and launch split — the jobs rttnw_render runs
+// for those pixels.  The running sums are kept by list slot (d->rg_sums): beyond the selection byte nothing here scales with the frame.
+// Arguments were checked by the caller.
+template <typename R>
+int render_region_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                    const uint8_t* mask, rttnw_stats* stats) {
+    DeviceState* d = s->device;
+    const FlatScene* flat = nullptr;
+    DeviceScene<R>* ds = nullptr;
+    if (int rc = bind_scene<R>(s, d, flat, ds)) return rc;
+    rttnw_tile_layout L;
+    fill_layout(p->width, p->height, 1, L);
+    const RenderConsts rc = base_consts(p, *flat, L);
+    const size_t wpx = size_t(x1 - x0) * (y1 - y0);
+    const uint32_t n_blocks = L.n_tiles * 16u, n_waves = (n_blocks + 63u) / 64u;
+    HIP_TRY(d->rg_select.grow(L.pixels_per_rank));
+    HIP_TRY(d->ad_quads.grow(size_t(n_blocks) * sizeof(uint32_t)));
+    HIP_TRY(d->ad_scan.grow((size_t(n_waves) * 3 + 2) * sizeof(uint32_t)));
+    HIP_TRY(d->rg_linear.grow(wpx * 3 * sizeof(R)));
+    HIP_TRY(d->rg_rgba.grow(wpx * 4));
+    if (mask) HIP_TRY(d->rg_mask.grow(wpx));
+    uint32_t* wave_counts = (uint32_t*)d->ad_scan.p;
+    uint32_t* wave_base = wave_counts + 2 * size_t(n_waves);
+    uint32_t* totals = wave_base + n_waves;
+    uint32_t* quads = (uint32_t*)d->ad_quads.p;
+    const hipStream_t stream = nullptr;
+    if (stats) HIP_TRY(hipEventRecord(d->ev0.get(), stream));
+    if (mask) HIP_TRY(hipMemcpy(d->rg_mask.p, mask, wpx, hipMemcpyHostToDevice)); // uploaded once, window-sized
+    HIP_TRY(hipMemsetAsync(d->rg_linear.p, 0, wpx * 3 * sizeof(R), stream)); // what an unselected pixel of the window keeps
+    HIP_TRY(hipMemsetAsync(d->rg_rgba.p, 0, wpx * 4, stream));
+    const uint32_t grid = (n_blocks + 255u) / 256u;
+    hipLaunchKernelGGL(region_select_kernel<R>, dim3((L.pixels_per_rank + 255u) / 256u), dim3(256), 0, stream, mask ? (const uint8_t*)d->rg_mask.p : nullptr,
+                       d->rg_select.p, rc, L.pixels_per_rank, x0, y0, x1, y1);
+    hipLaunchKernelGGL(quad_count_kernel<R>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)d->rg_select.p, n_blocks, wave_counts);
+    hipLaunchKernelGGL(quad_scan_kernel<R>, dim3(1), dim3(QUAD_SCAN_BLOCK), 0, stream, (const uint32_t*)wave_counts, wave_base, n_waves, totals);
+    hipLaunchKernelGGL(quad_list_kernel<R>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)d->rg_select.p, n_blocks, (const uint32_t*)wave_base, quads);
+    HIP_TRY(hipGetLastError());
+    uint32_t count[2] = {0, 0}; // listed blocks, selected pixels
+    HIP_TRY(hipMemcpy(count, totals, sizeof(count), hipMemcpyDeviceToHost));
+    if (count[0] != 0) {
+        HIP_TRY(d->rg_sums.grow(size_t(count[0]) * 4 * 4 * sizeof(R)));
+        ListPass list;
+        list.quads = quads;
+        list.n_quads = count[0];
+        list.clock_started = true;
+        // (fills `stats` as a plain render does: kernel form, scene sizes)
+        if (int g = render_tiles_t<R>(s, d, cam, p, d->rg_sums.p, stream, stats, false, false, &list)) return g;
+        hipLaunchKernelGGL(region_output_kernel<R>, dim3((count[0] * 4u + 255u) / 256u), dim3(256), 0, stream, (const R*)d->rg_sums.p, (const uint32_t*)quads,
+                           rc, count[0] * 4u, x0, y0, x1, y1, (R*)d->rg_linear.p, d->rg_rgba.p);
+        HIP_TRY(hipGetLastError());
+    } else if (stats) {
+        // nothing selected: no trace launch; the stats say what a render of this scene would have run
+        const char* wave_block = getenv("RTTNW_WAVE_BLOCK");
+        const LaunchPlan pl = plan_launch(*flat, sizeof(R), false, true, kernel_form_named(getenv("RTTNW_KERNEL")), wave_block ? atoi(wave_block) : 0);
+        if (int g = fill_stats<R>(d, *ds, *flat, pl, rc, false, stream, stats)) return g;
+    }
+    if (stats) HIP_TRY(hipEventRecord(d->ev1.get(), stream));
+    HIP_TRY(hipDeviceSynchronize());
+    if (stats) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, d->ev0.get(), d->ev1.get()));
+        stats->kernel_ms = ms;
+        stats->samples = uint64_t(count[1]) * p->spp;
+    }
+    return RTTNW_OK;
+}
+
 // what a precision's translation unit instantiates
 #define RT_INSTANTIATE_PRECISION(R)                                                                                                             \
     template int render_tiles_t<R>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, \
-                                   bool, bool, const AdaptivePass*);                                                                            \
+                                   bool, bool, const ListPass*);                                                                            \
     template int probe_path_t<R>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t); \
     template int untile_launch<R>(uint32_t, uint32_t, uint32_t, const void*, void*, uint8_t*, hipStream_t);                                       \
-    template int render_adaptive_t<R>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
+    template int render_adaptive_t<R>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);           \
+    template int render_region_t<R>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*, \
+                                    rttnw_stats*);
 
 } // namespace RT_ARITH_NS
 } // namespace rt

@@ -76,6 +76,26 @@ def render_features(scene, cam, params):
     return out
 
 
+def render_region(scene, cam, params, x0, y0, x1, y1, mask=None):
+    """`rttnw_render_region`: pixels [x0, x1) x [y0, y1) of the frame `render_host` renders — all of them, or those whose byte of
+    `mask` ((y1-y0) x (x1-x0), nonzero = selected) is set — each bit-identical to the full render's; an unselected pixel comes back as
+    0, 0, 0 with alpha 0.  Returns (linear hxwx3 f64, rgba8 hxwx4 u8, Stats), h = y1 - y0, w = x1 - x0."""
+    b = library.product()
+    h, w = max(int(y1) - int(y0), 0), max(int(x1) - int(x0), 0)
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.shape != (h, w):
+            raise ValueError("render_region: the mask must be (y1 - y0) x (x1 - x0) = %d x %d, got %s" % (h, w, m.shape))
+    lin = np.zeros((h, w, 3), dtype=np.float64)
+    rgba = np.zeros((h, w, 4), dtype=np.uint8)
+    st = Stats()
+    rc = b.render_region(scene.handle, C.byref(cam), C.byref(params), x0, y0, x1, y1, None if m is None else m.ctypes.data,
+                         lin.ctypes.data, rgba.ctypes.data, C.byref(st))
+    check(rc, b, "rttnw_render_region")
+    return lin, rgba, st
+
+
 def denoise(linear, features, stderr=None, iterations=5, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0, want_ms=False):
     """`rttnw_denoise`: the edge-avoiding a-trous filter over `linear` (HxWx3), guided by `features` (what `render_features` returns)
     and, when `stderr` (HxWx3, `render_adaptive`'s standard errors of the pixel means) is given, by their variance.  A sigma of 0 is
