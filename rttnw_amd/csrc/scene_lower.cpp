@@ -738,9 +738,17 @@ struct Lowering {
                 to_world(in, p);
                 wb.grow_pt(p);
             }
-            // guard the sin/cos rounding of the corner transform
+            // guard the sin/cos rounding of the corner transform: relative to the largest coordinate the transform handled (the object's
+            // corners, the chain's offsets, the result), not to 1 — a world of size 1e-3 gets a box as tight, in f32 steps, as one of size 1
+            // (the transform's double rounding is ~1e-16 of that magnitude: the guard keeps seven orders of margin.  A degenerate object at the
+            // origin under no offset handles only zeros: its guard is 0 and set_box's outward rounding alone remains — nothing was rounded)
+            double handled = 0.0;
+            for (int k = 0; k < 3; ++k) handled = std::max(handled, std::max(std::fabs(ob.lo[k]), std::fabs(ob.hi[k])));
+            for (int i = 0; i < in.n_ops; ++i)
+                if (in.ops[i].type == OP_TRANSLATE)
+                    for (int k = 0; k < 3; ++k) handled = std::max(handled, std::fabs(in.ops[i].v[k]));
             for (int k = 0; k < 3; ++k) {
-                double pad = 1e-9 * std::max(1.0, std::max(std::fabs(wb.lo[k]), std::fabs(wb.hi[k])));
+                double pad = 1e-9 * std::max(handled, std::max(std::fabs(wb.lo[k]), std::fabs(wb.hi[k])));
                 wb.lo[k] -= pad; wb.hi[k] += pad;
             }
             fs.insts.push_back(in);
