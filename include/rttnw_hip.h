@@ -440,7 +440,7 @@ int rttnw_debug_scene_nodes4(const rttnw_scene* s, void* out_nodes, uint32_t max
  *   [0] t  [1..3] p  [4..6] normal  [7] material index  [8] u  [9] v  [10] front_face
  *   [11..13] ray origin  [14..16] ray direction  [17] ray time  [18] emitted.r  [19] attenuation.r (-1: absorbed)
  * `out` must hold max_out*20 + 4 doubles: out[max_out*20 .. +3] = the sample's radiance r,g,b (background taken
- * as black) and its final bounce count, computed by the same path_step() loop the trace kernel runs.
+ * as black) and its final bounce count, computed by path_step(): the same walk and shade steps the trace kernels run.
  * Returns the number of bounces written (<= max_out) or a negative error.  Blocking; test use only. */
 int rttnw_debug_probe_path(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p,
                            uint32_t px, uint32_t row, uint32_t sample, double* out, uint32_t max_out);

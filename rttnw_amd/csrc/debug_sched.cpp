@@ -1,5 +1,5 @@
 // debug_sched.cpp — DEBUG ONLY: prints the statistics the counting kernel variants tally (RTTNW_DEBUG_SCHED=1 with
-// rttnw_params.collect_counters 1-3): wave clock per phase, lockstep iterations and the lanes they served, walk-length
+// rttnw_params.collect_counters 1-3): wave clock per phase, trips of the walk loop and the lanes they served, walk-length
 // histograms.  Nothing here runs in a render without that environment variable; kept out of the launch path's source
 // (render_tiles.hpp).  The meaning of DeviceCounters::dbg[] per kernel is documented where it is tallied (trace_tally.hpp,
 // trace_kernels.hpp).  profiles/r0N/phases_*.txt are this output (since round 5 of the

@@ -10,12 +10,9 @@
 #ifndef RT_TINY_TREE_STEPS
 #define RT_TINY_TREE_STEPS 3 // node steps per walk trip of the lane-owns-path kernel for top trees of <= 16 nodes (RT_NODE_STEPS otherwise)
 #endif
-#ifndef RT_WAVE_QUANT
-#define RT_WAVE_QUANT 2 // which decoupled kernels walk the quantised records (rt_types.hpp Bvh4QNode): 1 the f64 ones, 2 all, 0 none.  (Mid-round-4: f64 +4 / +7 %,
-                        // f32 -2 % against the f32 records — and +4 % for half-precision node-local records, 80 of 128 bytes a visit, which the f32 kernel walked
-                        // for a while.  At the round's end — no slot tests, no instance code, 13-real path slots — the f32 kernel moves 6.2 TB/s and little else,
-                        // and half the node bytes are worth +10 %: spheres_1m f32 433 -> 476 Msamples/s on these records; the half-precision ones are gone.)
-#endif
+// Every decoupled kernel walks the QUANTISED records (rt_types.hpp Bvh4QNode; LaunchPlan::quantised).  (Mid-round-4: f64 +4 / +7 %, f32 -2 % against the
+// f32 records.  At the round's end — no slot tests, no instance code, 13-real path slots — the f32 kernel moves 6.2 TB/s and little else, and half the
+// node bytes are worth +10 %: spheres_1m f32 433 -> 476 Msamples/s on these records.)
 #ifndef RT_F64_BLOCK
 #define RT_F64_BLOCK 1024 // threads per block of the LDS-resident f64 kernel (4 waves/SIMD at 128 VGPRs; see the Makefile's f64 flags and profiles/r03/README.md)
 #endif
@@ -31,9 +28,6 @@
 #ifndef RT_F64_WAVE_STACK
 #define RT_F64_WAVE_STACK 13
 #endif
-#ifndef RT_WAVE_LDS_PAD
-#define RT_WAVE_LDS_PAD 0 // experiments: unused bytes per wave (where the LDS stops holding three blocks per CU)
-#endif
 
 namespace rt {
 inline namespace RT_ARITH_NS {
@@ -48,7 +42,7 @@ static_assert(SLOTS_PER_WAVE <= 256u, "slot numbers travel as bytes");
 template <typename R> constexpr uint32_t wave_stack_entries() { return sizeof(R) == 8 ? uint32_t(RT_F64_WAVE_STACK) : LDS_STACK_ENTRIES; }
 template <typename R> constexpr uint32_t wave_lds_bytes(uint32_t stack_depth, bool no_time = false) {
     // ray queue (7 reals) + hit t | hit prim, inst, meta (words) | ray slot (bytes) | stack: + the spare slot
-    return (no_time ? 7u : 8u) * QCAP * uint32_t(sizeof(R)) + 3u * QCAP * 4u + QCAP + (wave_stack_entries<R>() + 1u) * 64u * 4u + RT_WAVE_LDS_PAD;
+    return (no_time ? 7u : 8u) * QCAP * uint32_t(sizeof(R)) + 3u * QCAP * 4u + QCAP + (wave_stack_entries<R>() + 1u) * 64u * 4u;
 }
 constexpr uint32_t LDS_GRANULE_BYTES = 1280u, LDS_BYTES_PER_CU = 160u * 1024u; // gfx950: 128 granules per CU
 constexpr uint32_t lds_blocks_per_cu(uint32_t block_bytes) {
@@ -60,9 +54,8 @@ constexpr uint32_t wave_block_waves(uint32_t wave_bytes) {
     while (n > 4u && (n * wave_bytes + LDS_GRANULE_BYTES - 1u) / LDS_GRANULE_BYTES > LDS_BYTES_PER_CU / LDS_GRANULE_BYTES) --n;
     return n;
 }
-static_assert(RT_WAVE_LDS_PAD != 0 || lds_blocks_per_cu(wave_lds_bytes<double>(0) * 4u) >= 3u, "the f64 decoupled kernel's block must fit a CU's LDS three times");
+static_assert(lds_blocks_per_cu(wave_lds_bytes<double>(0) * 4u) >= 3u, "the f64 decoupled kernel's block must fit a CU's LDS three times");
 static_assert(lds_blocks_per_cu(wave_lds_bytes<float>(0) * 4u) >= 3u, "the f32 decoupled kernel's block must fit a CU's LDS three times");
-template <typename R> constexpr bool wave_walks_quantised() { return RT_WAVE_QUANT == 2 || (RT_WAVE_QUANT == 1 && sizeof(R) == 8); }
 
 // RTTNW_KERNEL (experiments and tests): the caller reads the environment, plan_launch does not
 enum class KernelForm : int { AUTO = 0, PLAIN = 1, PLAINGLOBAL = 2, WAVE = 3 };
@@ -159,7 +152,7 @@ inline LaunchPlan plan_launch(const FlatScene& flat, size_t real_bytes, bool cou
         pl.form_bits = (in_lds ? FORM_LDS_NODES : 0u) | (three_steps ? FORM_THREE_STEPS : 0u) | (eligible ? FORM_NO_FRAMES : 0u) |
                        (eligible && flat.has_instance_leaves ? FORM_SINGLE : 0u) | (eligible && lean ? FORM_LEAN : 0u);
     } else {
-        pl.quantised = f32 ? wave_walks_quantised<float>() : wave_walks_quantised<double>();
+        pl.quantised = true;
         // (a scene without any instance record takes the instantiation whose walk never changes frames, rt_core.hpp SHAPES_NONE)
         const bool no_inst = !gen && !flat.has_instance_leaves;
         pl.shapes = gen ? SHAPES_GENERAL : !no_inst || count ? SHAPES_FAST : lean ? SHAPES_NONE_NT : SHAPES_NONE;

@@ -27,28 +27,13 @@
 // one library without their template instantiations colliding.
 #if defined(RT_STRICT_F64)
 #define RT_ARITH_NS ieee_strict
-#ifndef RT_SHARED_RECIPROCALS // (overridden in experiments only: what the IEEE quotients cost)
-#define RT_SHARED_RECIPROCALS 0
-#endif
+#define RT_SHARED_RECIPROCALS 0 // (what the IEEE quotients cost: profiles/r05/README.md)
 #else
 #define RT_ARITH_NS contracted
 #define RT_SHARED_RECIPROCALS 1
 #endif
 
 namespace rt {
-#ifndef RT_NODE_EMPTY_CHECK
-#define RT_NODE_EMPTY_CHECK 0 // 1: the node steps over f32 and quantised records test child != CHILD_EMPTY beside the (inverted) box of an unused slot.  Without:
-                              // final_scene f64 1394 -> 1434 Msamples/s, f32 1857 -> 1889, cornell_box f64 1728 -> 1751 (four compares and the scalar ANDs between the
-                              // hit tests and the selects); the kernels that read f32 records from memory +-0.3 %
-#endif
-#ifndef RT_PIN_CHILD_PIECE
-#define RT_PIN_CHILD_PIECE 1 // the step over quantised records (read from memory) keeps the read of the children's piece beside the other pieces' reads
-#endif
-#ifndef RT_F64_SLAB_FOLDED
-#define RT_F64_SLAB_FOLDED 2 // the f64 kernels' box test: 0 every box's entry / exit widened by 3.6e-7 |t| + slack (15 operations per box), 1 the widening in per-walk
-                             // constants for both ends (11, five registers more: spills), 2 the slack in the constants and one multiplication per entry (12, two
-                             // registers more), 3 one fma per end (13).  Measured (final_scene / cornell_box f64, Msamples/s): 1364 / 1692, 1370 / 1589, 1393 / 1727, 1.5-2 % behind 2
-#endif
 inline namespace RT_ARITH_NS {
 
 // ---------------------------------------------------------------- math wrappers
@@ -386,22 +371,25 @@ template <typename Stack, typename R> constexpr int slab_form() { return sizeof(
 // kernels need not be: origin and 1/d are rounded to f32 once per walk (1/d as v_rcp_f32 of the rounded d: 1 ulp — three
 // f64 divisions per walk start, instance entry and instance exit were 5 % of the f64 kernel's instructions), a plane
 // distance is ONE fused multiply-add, t32 = fl(b inv32 - oi32) with oi32 = fl(o32 inv32) kept per walk (round 3: 6 instead
-// of 12 operations per box, a sixth of a node step), and every plane distance is widened by a bound on what the roundings
+// of 12 operations per box, a sixth of a node step), and the test is widened by a bound on what the roundings
 // can have done to it.  With o32 = o(1+e0), |e0| <= 2^-24, inv32 = inv(1+e1), |e1| <= 2^-24 + 2^-23, oi32 = o32 inv32 (1+e2),
 // |e2| <= 2^-24, and the fma's single rounding e3:
 //   t32 = [ (b - o) inv (1+e1) - o inv (1+e1)((1+e0)(1+e2) - 1) ] (1+e3)
 //   |t32 - t| <= 2.4e-7 |t| + 1.2e-7 |o inv|          (t = (b - o) inv exactly, b a float)
-// so near planes move down and far planes up by 3.6e-7 |t32| + slack, slack = 2.4e-7 |oi32| (twice the bound, as before;
-// the two-operation form fl(fl(b - o32) inv32) it replaces had 6e-8 |o inv| there and used 1.2e-7), the range's ends are
-// rounded outward, and NaN / inf (axis-parallel rays) never cull.  A box the exact test would pass always passes: images
-// and hits are those of f64 slab tests, a node step costs about a third (f64 runs at half rate and selects move register
-// pairs).
+// The ABSOLUTE part lives in the per-walk constants: near planes subtract oi32 + 3.0e-7 |oi32|, far planes oi32 - 3.0e-7 |oi32| (2.5 times the
+// bound: the roundings of the sum and of the shifted distance are inside it), so for the t >= 0 that matter a near distance is
+// <= t (1 + 2.4e-7) and a far distance >= t (1 - 2.4e-7).  The RELATIVE part is one multiplication of the box's entry by 1 - 9.6e-7, which
+// covers the exit's share too: a box the exact test passes has entry <= exit, hence entry32 (1 - 9.6e-7) <= entry (1 - 7.2e-7 + 2^-24) <=
+// exit (1 - 2.4e-7) <= exit32.  A negative near distance cannot set the entry (t_min >= 0 or another axis does), a negative far distance is
+// a box behind the origin; the range's ends are rounded outward, and NaN / inf (axis-parallel rays) never cull.  A box the exact test
+// would pass always passes: images and hits are those of f64 slab tests, a node step costs about a third (f64 runs at half rate
+// and selects move register pairs).  12 operations per box and nine per-walk floats — round 4, final_scene / cornell_box f64 Msamples/s:
+// 1393 / 1727, against 1364 / 1692 for 15 operations (every box's entry and exit widened by 3.6e-7 |t| + the largest axis slack), 1370 / 1589 for
+// 11 (both ends' relative widening in the constants too: 12 floats, five registers more, spills) and 1.5-2 % less for 13 (one fma per end).
 template <> struct SlabRay<double> {
-    float oinv[3], inv[3]; // o * (1 / d) and 1 / d: a plane distance is ONE fma, plane * inv - oinv (below)
-    float slack; // the largest of the three axes' slacks: one widening of the box's entry / exit serves all planes (below)
-#if RT_F64_SLAB_FOLDED
-    float inv_n[3], oinv_n[3], inv_f[3], oinv_f[3]; // the same with the widening folded into the constants (slab_hit4 below)
-#endif
+    float oinv[3], inv[3]; // o * (1 / d) and 1 / d
+    float slack; // DEAD, like inv_n and inv_f: nothing reads them; pinned with their stores in slab_ray by register allocation (profiles/LEDGER.md "Settled switches retired")
+    float inv_n[3], oinv_n[3], inv_f[3], oinv_f[3]; // oinv_n / oinv_f: o * (1 / d) moved by the axis's slack — what a near / far plane's fma subtracts
 };
 template <int FORM, typename R> RT_HD SlabRay<R> slab_ray(V3<R> o, V3<R> d) {
     SlabRay<R> sr;
@@ -413,31 +401,22 @@ template <int FORM, typename R> RT_HD SlabRay<R> slab_ray(V3<R> o, V3<R> d) {
             const float o32 = float(oo[a]);
             float inv = rt_rcp(float(dd[a]));
             // an axis the ray is exactly parallel to (or whose direction component underflows in f32): 1/d = inf would make
-            // the ONE slack below infinite and the whole walk lose its culling.  NaN instead: every plane distance of this
-            // axis is then NaN, which the maxNum / minNum of slab4_planes drop — the axis never culls (conservative: the
-            // exact test could at most cull more) and stays out of the slack.
+            // o inv and the axis's slack infinite or NaN by accident of signs.  NaN on purpose instead: every plane distance of this
+            // axis is then NaN, which the maxNum / minNum of slab_hit4 drop — the axis never culls (conservative: the
+            // exact test could at most cull more).
             if (!(rt_fabs(inv) < __builtin_huge_valf())) inv = __builtin_nanf("");
             sr.inv[a] = inv;
             sr.oinv[a] = o32 * inv;
             sr.slack = rt_max(sr.slack, rt_fabs(sr.oinv[a]) * 2.4e-7f); // maxNum: a NaN axis drops out
-#if RT_F64_SLAB_FOLDED
-            // The widening folded into the per-walk constants, as in the f32 kernels' SLAB_FMA_FOLDED form: near planes take
-            // inv (1 - 4.8e-7) and oi (1 - 4.8e-7) + 3.0e-7 |oi|, far planes the opposite.  With r1, r2, r3 the roundings of inv_n, of
-            // oinv_n's fma and of the plane's fma (each <= 2^-24):
-            //   t_n32 = (1 - 4.8e-7)(1 + e1)(1 + r3) [ t (1 + r1) + o inv (r1 - e0 - e2 - r2) ] - slack (1 + r2)(1 + r3)
-            // — for t >= 0 the first factor times (1 + r1) is <= 1 (4.8e-7 >= |e1| + |r1| + |r3| = 3.0e-7) and the second term is at most
-            // 2.4e-7 |o inv| < slack: t_n32 <= t.  A negative near distance cannot set the entry (t_min >= 0 or another axis does), a
-            // negative far distance is a box behind the origin; a NaN axis drops out of max3 / min3.
+            // the axis's slack in two copies of o inv (above); a NaN axis stays NaN and drops out of max3 / min3.  (The stores to slack, inv_n and inv_f and
+            // the fma pair that is overwritten at once are dead: see SlabRay<double>.)
             const float slack_a = rt_fabs(sr.oinv[a]) * 3.0e-7f;
             sr.inv_n[a] = inv * (1.f - 4.8e-7f);
             sr.inv_f[a] = inv * (1.f + 4.8e-7f);
             sr.oinv_n[a] = __builtin_fmaf(sr.oinv[a], 1.f - 4.8e-7f, slack_a);
             sr.oinv_f[a] = __builtin_fmaf(sr.oinv[a], 1.f + 4.8e-7f, -slack_a);
-#if RT_F64_SLAB_FOLDED == 2
             sr.oinv_n[a] = sr.oinv[a] + slack_a;
             sr.oinv_f[a] = sr.oinv[a] - slack_a;
-#endif
-#endif
         }
     } else {
         sr.inv = V3<R>(rt_rcp(d.x), rt_rcp(d.y), rt_rcp(d.z));
@@ -482,16 +461,6 @@ template <typename R> RT_HD uint32_t near_piece(int a, const SlabRay<R>& sr) {
 // near-plane distance, tf[c] = the smallest far-plane distance.  (As 24 PACKED f32 operations — v_pk_add_f32 / v_pk_mul_f32
 // with the ray's component splat by op_sel, which the by-axis layout makes natural — it measured SLOWER: final_scene f32
 // 1389 against 1452, spheres_1m 340 against 397: on wave64 a packed operation issues no faster than its two halves.)
-RT_HD void slab4_planes_fma(const Planes4& nd, const float oinv[3], const float inv[3], float tn[4], float tf[4]) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float nx = __builtin_fmaf(nd.nr[0][c], inv[0], -oinv[0]), fx = __builtin_fmaf(nd.fr[0][c], inv[0], -oinv[0]);
-        const float ny = __builtin_fmaf(nd.nr[1][c], inv[1], -oinv[1]), fy = __builtin_fmaf(nd.fr[1][c], inv[1], -oinv[1]);
-        const float nz = __builtin_fmaf(nd.nr[2][c], inv[2], -oinv[2]), fz = __builtin_fmaf(nd.fr[2][c], inv[2], -oinv[2]);
-        tn[c] = rt_max(nz, rt_max(ny, nx));
-        tf[c] = rt_min(fz, rt_min(fy, fx));
-    }
-}
 RT_HD void slab4_planes(const Planes4& nd, const float o[3], const float inv[3], float tn[4], float tf[4]) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -503,55 +472,14 @@ RT_HD void slab4_planes(const Planes4& nd, const float o[3], const float inv[3],
     }
 }
 // Hit test of the four children against [lo_t, hi_t]; e[c] = the entry distance (>= lo_t: the ordering key).
-// f64 kernels: the conservative form.  With k the plane that sets tn, the true entry is >= t_k >= n_k - (3.6e-7 |n_k| +
-// slack_k), so tn - 3.6e-7 |tn| - slack (slack = the largest axis slack) is a lower bound of the true entry, and likewise
-// an upper bound of the true exit: ONE widening per box instead of one per plane (round 1), a box the exact f64 test
-// would pass still always passes.  NaN / inf (axis-parallel rays) never cull.
+// f64 kernels: the conservative form derived at SlabRay<double> — the slack in the constants, the relative widening on the entry alone.
 template <int FORM> RT_HD void slab_hit4(const Planes4& nd, V3<double>, const SlabRay<double>& sr, float lo_t, float hi_t, float e[4], bool h[4]) {
-#if RT_F64_SLAB_FOLDED == 3
-    {
-        float tn[4], tf[4];
-        slab4_planes_fma(nd, sr.oinv, sr.inv, tn, tf);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { // 13 operations per box: one fma per end widens it (valid for the non-negative distances that matter)
-            const float n = __builtin_fmaf(tn[c], 1.f - 3.6e-7f, -sr.slack);
-            const float f = __builtin_fmaf(tf[c], 1.f + 3.6e-7f, sr.slack);
-            const float lo = rt_max(n, lo_t), hi = rt_min(f, hi_t);
-            e[c] = lo;
-            h[c] = !(hi < lo);
-        }
-        return;
-    }
-#elif RT_F64_SLAB_FOLDED == 2
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { // 12 operations per box: the slack in the constants, the relative widening on the entry alone
+    for (int c = 0; c < 4; ++c) {
         const float nx = __builtin_fmaf(nd.nr[0][c], sr.inv[0], -sr.oinv_n[0]), fx = __builtin_fmaf(nd.fr[0][c], sr.inv[0], -sr.oinv_f[0]);
         const float ny = __builtin_fmaf(nd.nr[1][c], sr.inv[1], -sr.oinv_n[1]), fy = __builtin_fmaf(nd.fr[1][c], sr.inv[1], -sr.oinv_f[1]);
         const float nz = __builtin_fmaf(nd.nr[2][c], sr.inv[2], -sr.oinv_n[2]), fz = __builtin_fmaf(nd.fr[2][c], sr.inv[2], -sr.oinv_f[2]);
-        const float lo = rt_max(rt_max(nz, rt_max(ny, nx)) * (1.f - 9.6e-7f), lo_t), hi = rt_min(rt_min(fz, rt_min(fy, fx)), hi_t);
-        e[c] = lo;
-        h[c] = !(hi < lo);
-    }
-    return;
-#elif RT_F64_SLAB_FOLDED
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { // 11 operations per box instead of 15: the widening is in the constants (slab_ray)
-        const float nx = __builtin_fmaf(nd.nr[0][c], sr.inv_n[0], -sr.oinv_n[0]), fx = __builtin_fmaf(nd.fr[0][c], sr.inv_f[0], -sr.oinv_f[0]);
-        const float ny = __builtin_fmaf(nd.nr[1][c], sr.inv_n[1], -sr.oinv_n[1]), fy = __builtin_fmaf(nd.fr[1][c], sr.inv_f[1], -sr.oinv_f[1]);
-        const float nz = __builtin_fmaf(nd.nr[2][c], sr.inv_n[2], -sr.oinv_n[2]), fz = __builtin_fmaf(nd.fr[2][c], sr.inv_f[2], -sr.oinv_f[2]);
-        const float lo = rt_max(rt_max(nz, rt_max(ny, nx)), lo_t), hi = rt_min(rt_min(fz, rt_min(fy, fx)), hi_t); // maxNum / minNum: a NaN drops out
-        e[c] = lo;
-        h[c] = !(hi < lo);
-    }
-    return;
-#endif
-    float tn[4], tf[4];
-    slab4_planes_fma(nd, sr.oinv, sr.inv, tn, tf);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float n = __builtin_fmaf(-rt_fabs(tn[c]), 3.6e-7f, tn[c]) - sr.slack;
-        const float f = __builtin_fmaf(rt_fabs(tf[c]), 3.6e-7f, tf[c]) + sr.slack;
-        const float lo = rt_max(n, lo_t), hi = rt_min(f, hi_t); // maxNum / minNum: a NaN drops out
+        const float lo = rt_max(rt_max(nz, rt_max(ny, nx)) * (1.f - 9.6e-7f), lo_t), hi = rt_min(rt_min(fz, rt_min(fy, fx)), hi_t); // maxNum / minNum: a NaN drops out
         e[c] = lo;
         h[c] = !(hi < lo);
     }
@@ -705,9 +633,6 @@ RT_HD bool box_t(const BoxRec<R>& bx, const Ray<R>& ray, R t_min, R t_max, R& t_
 // o_a + t d_a in f64 (2^-52 of the same sum), 60 times the f32 error of the plane distances themselves.  Everything else — a ray within g of an
 // edge, an entry within g of t_min, any NaN / infinity (axis-parallel rays: S is not finite, no comparison holds) — takes box_t.  `face` as box_t.
 // tests/test_core_parity_cpu.py::test_fast_cube_test_is_the_six_rectangle_test holds the two to the same (hit, t, face) bit for bit.
-#ifndef RT_BOX_FAST
-#define RT_BOX_FAST 1
-#endif
 #ifndef RT_BOX_FAST_MARGIN
 #define RT_BOX_FAST_MARGIN 2e-5f
 #endif
@@ -717,10 +642,6 @@ RT_HD float rt_med3(float a, float b, float c) {
 #else
     return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c));
 #endif
-}
-template <typename R> RT_HD float slab_inv32(const SlabRay<R>& sr, int a) {
-    if constexpr (sizeof(R) == 8) return sr.inv[a];
-    else return a == 0 ? sr.inv.x : (a == 1 ? sr.inv.y : sr.inv.z);
 }
 // returns 0: certainly no face hits; 1: the only face that can is (axis, use_mx), and its extents test is true; 2: not certain (box_t decides)
 // FORM: the same verdicts written two ways — 0: comparison by comparison, 1: one comparison of a min3 / max3 per verdict (fewer instructions).
@@ -741,7 +662,7 @@ RT_HD int box_classify(const BoxRec<R>& bx, const Ray<R>& ray, const SlabRay<R>&
                            // direction's sign alone — would swap and the verdicts with them: such a record is box_t's (round-5 advisor)
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float inv = slab_inv32(sr, a);
+        const float inv = slab_inv_of(sr, a);
         float oi;
         if constexpr (sizeof(R) == 8) oi = sr.oinv[a]; else oi = float(o[a]) * inv;
         const float mn32 = float(bx.mn[a]), mx32 = float(bx.mx[a]);
@@ -948,9 +869,7 @@ RT_HD bool prim_t(const SceneView<R>& sc, uint32_t kind, uint32_t idx, const Ray
         SphereRec<R> s = sc.spheres[idx];
         return sphere_t(V3<R>(s.cx, s.cy, s.cz), s.r, ray, t_min, t_max, t);
     } else if (kind == PRIM_BOX) {
-#if RT_BOX_FAST
         if constexpr (HAVE_SR) return box_t_fast(sc.boxes[idx], ray, sr, t_min, t_max, t, aux);
-#endif
         const BoxRec<R> bx = sc.boxes[idx];
         return box_t(bx, ray, t_min, t_max, t, aux);
     } else if (kind == PRIM_RECT) {
@@ -1017,7 +936,7 @@ template <typename R, typename Stack> RT_HD void trav_set_ray(Trav<R>& tr, const
 }
 // A ray NOTHING can cull: on every axis its plane distances are NaN (a NaN / infinite origin or direction, a zero direction, |o / d| beyond the
 // floats) — maxNum / minNum drop them all, so even the inverted box of an UNUSED node slot "passes" (the node steps do not test the slot itself,
-// RT_NODE_EMPTY_CHECK).  Such a walk would push three entries per node, past the bound the lowering sized the stacks by (FlatScene::stack_depth
+// trav_node_step4).  Such a walk would push three entries per node, past the bound the lowering sized the stacks by (FlatScene::stack_depth
 // counts real children).  One axis with a finite, non-zero 1 / d and a finite o / d is enough for every unused slot to miss (entry +inf, exit -inf).
 // A ray without one is not walked at all: no hit, closest = NaN — which path_shade turns into a NaN path value, the NaN pixel the reference
 // renders from such a ray (main.rs:219-225 then writes 0).  Checked once per world.hit(), not per node.
@@ -1034,7 +953,7 @@ template <typename R> RT_HD bool slab_ray_can_be_culled(const SlabRay<R>& sr, V3
     return any;
 }
 // trav_begin() in two halves — the walk's cursor, and what the ray contributes to its slab tests — for the kernel that SUSPENDS walks across its
-// shade phases (trace_kernels.hpp trace_kernel_plain, RT_ASYNC_SHADE): only the cursor lives through a shade phase, the slab constants are made
+// shade phases (trace_kernels.hpp trace_kernel_plain): only the cursor lives through a shade phase, the slab constants are made
 // again from the path's ray when the walk goes on.
 template <typename R> RT_HD void trav_init(Trav<R>& tr, const SceneView<R>& sc) {
     tr.closest = Lim<R>::max(); // world.hit(ray, t_min, f64::MAX) — main.rs:33
@@ -1134,12 +1053,10 @@ RT_HD void trav_node_step4(Trav<R>& tr, const SceneView<R>& sc, const Ray<R>& wr
         ch[c] = nd.child[c];
         // (entry distances are positive: their bit patterns order like the values.  An unused slot needs no test of its own: its box is
         // inverted, lo = +inf / hi = -inf (rt_types.hpp Bvh4Node), so its entry is +inf and its exit -inf whatever the direction's signs;
-        // were every one of its plane distances NaN — |o / d| overflowing — it would be descended into and popped at once, trav_leaf_step)
-#if RT_NODE_EMPTY_CHECK
-        k[c] = (h[c] && ch[c] != CHILD_EMPTY) ? float_bits(e[c]) : MISS;
-#else
+        // were every one of its plane distances NaN — |o / d| overflowing — it would be descended into and popped at once, trav_leaf_step.
+        // A test of child != CHILD_EMPTY beside the box's — four compares and the scalar ANDs between the hit tests and the selects — cost
+        // final_scene f64 1434 -> 1394 Msamples/s, f32 1889 -> 1857, cornell_box f64 1751 -> 1728; the kernels that read f32 records from memory +-0.3 %)
         k[c] = h[c] ? float_bits(e[c]) : MISS;
-#endif
     }
     trav_descend_sorted4<Cnt::NO_INST>(tr, wray, stack, k, ch);
 }
@@ -1158,7 +1075,7 @@ template <typename R, typename Stack, typename Cnt>
 RT_HD void trav_node_step4q(Trav<R>& tr, const SceneView<R>& sc, const Ray<R>& wray, R t_min, Stack& stack, Cnt& cnt) {
     uint32_t w[16]; // pieces 0-3 of the record
     stack.fetch4q(sc, tr.node, w);
-#if RT_PIN_CHILD_PIECE && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
     // the children's piece is READ with the others: nothing below needs it before the hit tests are done, and left alone the compiler sinks its
     // read below them — a second dependent round trip to memory per visit (spheres_1m f64 280 -> 248 Msamples/s)
     asm volatile("" : "+v"(w[12]), "+v"(w[13]), "+v"(w[14]), "+v"(w[15]));
@@ -1200,12 +1117,9 @@ RT_HD void trav_node_step4q(Trav<R>& tr, const SceneView<R>& sc, const Ray<R>& w
         const float tn = rt_max(nz, rt_max(ny, nx)), tf = rt_min(fz, rt_min(fy, fx));
         const float n = __builtin_fmaf(tn, 1.f - 4e-7f, -K), f = __builtin_fmaf(tf, 1.f + 4e-7f, K);
         const float lo = rt_max(n, lo_t), hi = rt_min(f, hi_t); // maxNum / minNum: a NaN drops out
-        // (an unused slot: q_lo = 255, q_hi = 0 — its entry lies 255 max |S| beyond its exit, the widening moves them by 3e-4 max |S| + 8e-7 |t|)
-#if RT_NODE_EMPTY_CHECK || !RT_PIN_CHILD_PIECE
-        k[c] = (!(hi < lo) && ch[c] != CHILD_EMPTY) ? float_bits(lo) : MISS_KEY;
-#else
+        // (an unused slot: q_lo = 255, q_hi = 0 — its entry lies 255 max |S| beyond its exit, the widening moves them by 3e-4 max |S| + 8e-7 |t|,
+        // so it needs no test of its own, as in trav_node_step4: with the children's read pinned above, +-0)
         k[c] = !(hi < lo) ? float_bits(lo) : MISS_KEY;
-#endif
     }
     trav_descend_sorted4<Cnt::NO_INST>(tr, wray, stack, k, ch);
 }
@@ -1216,9 +1130,8 @@ RT_HD void trav_node_step(Trav<R>& tr, const SceneView<R>& sc, const Ray<R>& wra
     else trav_node_step4(tr, sc, wray, t_min, stack, cnt);
 }
 
-// One step at a leaf (tr.node < 0, not TRAV_DONE): enter an instance, or test ONE primitive record.  WHOLE_LEAF tests
-// all (<= 4) records of the leaf in one step instead — the same tests in the same order; measured 10-14 % SLOWER in
-// the lockstep kernel (lanes with a one-record leaf wait instead of going on with node steps), so nothing uses it.
+// One step at a leaf (tr.node < 0, not TRAV_DONE): enter an instance, or test ONE primitive record.  (All (<= 4) records of the
+// leaf in one step measured 10-14 % slower: lanes with a one-record leaf wait instead of going on with node steps.)
 // (`ray`: the ray in the frame of the record — tr.ray, the world ray itself where the walk never changes frames, or a single wrapped record's
 // object-space ray; `inst`: the instance that frame belongs to, or -1)
 // Leaves of kind PRIM_SPHERE_WC (the lowering RTTNW_F64_STRICT renders; the host build of the core knows them too): the world-space copy of a sphere
@@ -1263,7 +1176,7 @@ template <bool G = false, bool NO_TIME = false, bool FRAME_RAY = false, typename
     hit = prim_t<NO_TIME, FRAME_RAY>(sc, kind, idx, ray, t_min, tr.closest, t, aux, tr.sr);
     if (hit) trav_accept(tr, sc, kind, idx, t, aux, inst);
 }
-template <bool WHOLE_LEAF = false, typename R, typename Stack, typename Cnt>
+template <typename R, typename Stack, typename Cnt>
 RT_HD void trav_leaf_step(Trav<R>& tr, const SceneView<R>& sc, const Ray<R>& wray, R t_min, Stack& stack, Cnt& cnt) {
     constexpr bool NI = Cnt::NO_INST;
     // (the fast cube test where the walk's plane distances are to hand and cubes are what a leaf step meets: not in the decoupled kernel — big trees of
@@ -1295,20 +1208,12 @@ RT_HD void trav_leaf_step(Trav<R>& tr, const SceneView<R>& sc, const Ray<R>& wra
         }
         return;
     }
-    if constexpr (WHOLE_LEAF) {
-        for (uint32_t k = 0; k < count; ++k) {
-            cnt.prim();
-            trav_test_record<Cnt::GENERAL, Cnt::NO_TIME, FAST_CUBES>(tr, sc, kind, first + k, t_min, NI ? wray : tr.ray, NI ? -1 : tr.cur_inst);
-        }
-        trav_pop<NI>(tr, wray, stack);
-    } else {
-        cnt.prim();
-        trav_test_record<Cnt::GENERAL, Cnt::NO_TIME, FAST_CUBES>(tr, sc, kind, first + tr.leaf_k, t_min, NI ? wray : tr.ray, NI ? -1 : tr.cur_inst);
-        if (++tr.leaf_k >= count) trav_pop<NI>(tr, wray, stack);
-    }
+    cnt.prim();
+    trav_test_record<Cnt::GENERAL, Cnt::NO_TIME, FAST_CUBES>(tr, sc, kind, first + tr.leaf_k, t_min, NI ? wray : tr.ray, NI ? -1 : tr.cur_inst);
+    if (++tr.leaf_k >= count) trav_pop<NI>(tr, wray, stack);
 }
 
-template <int NODE_STEPS = RT_NODE_STEPS, typename R, typename Stack, typename Cnt>
+template <typename R, typename Stack, typename Cnt>
 RT_HD bool closest_solid(const SceneView<R>& sc, const Ray<R>& wray, R t_min, R& closest, HitRef& best, Stack& stack, Cnt& cnt) {
     Trav<R> tr;
     trav_begin(tr, sc, wray, stack);
@@ -1322,9 +1227,8 @@ RT_HD bool closest_solid(const SceneView<R>& sc, const Ray<R>& wray, R t_min, R&
         // 1605 / 1632 / 1562, f64 - / 1058 / 1037; cornell_box f32 1893 / 2040 / 2066, f64 - / 1359 / 1370)
         // (round 4, per tree size: the lane-owns-path kernel takes THREE for a top tree of <= 16 nodes — cornell_box, whose walks are mostly
         // entered instances: f64 1749 -> 1804, f32 2305 -> 2347; final_scene with three: 1429 -> 1401 — render_tiles.hpp picks the instantiation)
-        constexpr int node_steps = NODE_STEPS;
 #pragma unroll
-        for (int k = 0; k < node_steps; ++k)
+        for (int k = 0; k < RT_NODE_STEPS; ++k)
             if (tr.node >= 0) trav_node_step(tr, sc, wray, t_min, stack, cnt);
         if (tr.node < 0 && tr.node != TRAV_DONE) trav_leaf_step(tr, sc, wray, t_min, stack, cnt);
     }
@@ -1767,13 +1671,13 @@ RT_HD bool path_shade(PathState<R>& ps, const SceneView<R>& sc, const RenderCons
     return ps.bounce < rc.max_depth;
 }
 
-template <int NODE_STEPS = RT_NODE_STEPS, typename R, typename Stack, typename Cnt>
+template <typename R, typename Stack, typename Cnt>
 RT_HD bool path_step(PathState<R>& ps, const SceneView<R>& sc, const RenderConsts& rc, V3<R> background, R t_min,
                      Stack& stack, Cnt& cnt) {
     cnt.ray();
     R closest;
     HitRef best;
-    const bool found = closest_solid<NODE_STEPS>(sc, ps.ray, t_min, closest, best, stack, cnt);
+    const bool found = closest_solid(sc, ps.ray, t_min, closest, best, stack, cnt);
     return path_shade(ps, sc, rc, background, t_min, found, closest, best, cnt);
 }
 
@@ -1820,10 +1724,9 @@ RT_HD void tile_unpermute(uint32_t permuted, FastDiv div_tiles_x, uint32_t& tx, 
 // Jobs are numbered group-major: group g = chunks [16 g, 16 g + 16) of every pixel of the rank, then inside a group
 // the 2x2 blocks in tile order.  Chunks past the last one are padding (empty jobs).  `sum_index` is where the job's
 // sequential sum goes: chunk-major over (tile, pixel-in-tile), the layout resolve_kernel reads.
-#ifndef RT_JOB_BLOCK_LG
-#define RT_JOB_BLOCK_LG 1 // (re-measured under round 5's shade phases, final_scene f64 / cornell_box f64: 0 = 1 pixel x 64 chunks, 2 = 4x4 x 4: profiles/r05/README.md)
-#endif
-constexpr uint32_t JOB_BLOCK_LG = RT_JOB_BLOCK_LG;                    // 2x2 pixels
+// (re-measured under round 5's shade phases, final_scene f64 / cornell_box f64, against 1 pixel x 64 chunks and 4x4 x 4: profiles/r05/README.md;
+// the active list of rttnw_render_adaptive packs a 2x2 block's four pixel bits, job_decode_list)
+constexpr uint32_t JOB_BLOCK_LG = 1;                                   // 2x2 pixels
 constexpr uint32_t JOB_GROUP_CHUNKS = 64u >> (2u * JOB_BLOCK_LG);      // 16 chunks
 struct JobInfo {
     uint32_t px, row, s, s_end;

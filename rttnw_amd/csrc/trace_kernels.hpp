@@ -20,18 +20,9 @@
 #include "render_common.hpp"
 #include "adaptive.hpp"
 #include "launch_plan.hpp" // block sizes, LDS sizes and SLOTS_PER_WAVE: what the host plans a launch by
-#ifndef RT_ASYNC_SHADE
-#define RT_ASYNC_SHADE 1 // the lane-owns-path kernel leaves its walk loop for a shade phase once at most RT_ASYNC_SLACK walks are unfinished; those are
-                         // SUSPENDED — their lanes skip the phase and walk on in the next one (0: every round waits for its longest walk, rounds 1-4)
-#endif
-#ifndef RT_ASYNC_WHOLE_LEAF
-#define RT_ASYNC_WHOLE_LEAF 0 // 1: a leaf step tests all (<= 4) records of the leaf instead of one
-#endif
 #ifndef RT_ASYNC_SLACK
-#define RT_ASYNC_SLACK 8
-#endif
-#ifndef RT_WAVE_WHOLE_LEAF
-#define RT_WAVE_WHOLE_LEAF 0 // decoupled kernels: a leaf step tests all (<= 4) records of the leaf instead of one
+#define RT_ASYNC_SLACK 8 // the lane-owns-path kernel leaves its walk loop for a shade phase once at most this many walks are unfinished; those are
+                         // SUSPENDED — their lanes skip the phase and walk on in the next one
 #endif
 #include "trace_tally.hpp"
 
@@ -154,23 +145,8 @@ __device__ __forceinline__ unsigned long long wave_take_jobs(unsigned long long 
     return job;
 }
 
-#ifndef RT_POOL_NT
-#define RT_POOL_NT 0
-#endif
-template <typename T> __device__ __forceinline__ T pool_ld(const T* p) {
-#if RT_POOL_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-template <typename T, typename V> __device__ __forceinline__ void pool_st(T* p, V v) {
-#if RT_POOL_NT
-    __builtin_nontemporal_store(T(v), p);
-#else
-    *p = T(v);
-#endif
-}
+template <typename T> __device__ __forceinline__ T pool_ld(const T* p) { return *p; }
+template <typename T, typename V> __device__ __forceinline__ void pool_st(T* p, V v) { *p = T(v); } // (stores a real or an index into the pool's type)
 // Path state of a slot, in global memory (L2-resident), struct-of-arrays over all slots of the launch.
 // (no radiance: a path's value is the term of its last bounce, rt_core.hpp path_shade — round 4; 13 reals a slot instead of 16)
 enum : uint32_t { PR_TX = 0, PR_TY, PR_TZ, PR_AX, PR_AY, PR_AZ, PR_COUNT }; // (the slot's RAY stays in LDS from its emit to its shade: the wave's ray arena, below)
@@ -236,7 +212,7 @@ __global__ __launch_bounds__(GENERAL == SHAPES_NONE_NT ? 1024 : TRACE_BLOCK, GEN
     int32_t* const hq_inst = hq_prim + QCAP;
     uint32_t* const hq_meta = reinterpret_cast<uint32_t*>(hq_inst + QCAP);
     uint8_t* const rq_slot = reinterpret_cast<uint8_t*>(hq_meta + QCAP); // (slots are 0 .. 127: a byte each)
-    typename std::conditional<wave_walks_quantised<R>(), LdsStackQuant4<64, wave_stack_entries<R>()>, LdsStack<64, wave_stack_entries<R>()>>::type stack;
+    LdsStackQuant4<64, wave_stack_entries<R>()> stack; // every decoupled kernel walks the quantised records (launch_plan.hpp plan_launch: quantised)
     stack.base = (LdsIntPtr)(reinterpret_cast<int32_t*>(rq_slot + QCAP) + lane);
     stack.spill = (GlobalIntPtr)(spill + (blockIdx.x * blockDim.x + threadIdx.x));
     stack.spill_stride = gridDim.x * blockDim.x;
@@ -399,7 +375,7 @@ __global__ __launch_bounds__(GENERAL == SHAPES_NONE_NT ? 1024 : TRACE_BLOCK, GEN
 #pragma unroll
                     for (int k = 0; k < RT_WAVE_STEPS; ++k)
                         if (tr.node >= 0) trav_node_step(tr, sc, wray, t_min, stack, cnt);
-                    if (tr.node < 0 && tr.node != TRAV_DONE) trav_leaf_step<RT_WAVE_WHOLE_LEAF != 0>(tr, sc, wray, t_min, stack, cnt);
+                    if (tr.node < 0 && tr.node != TRAV_DONE) trav_leaf_step(tr, sc, wray, t_min, stack, cnt);
                 }
                 if (uint32_t(__popcll(__ballot(has_ray && tr.node == TRAV_DONE))) >= retire_batch) break;
             }
@@ -450,7 +426,7 @@ RT_WAVE_DECL_LIST(SHAPES_FAST) RT_WAVE_DECL_LIST(SHAPES_GENERAL) RT_WAVE_DECL_LI
 
 // The plain form of the same loop: a lane OWNS a path (and its job): path state stays in registers, no queues.  Rounds 1-4 alternated
 // "regenerate or advance by one bounce" (rt_core.hpp path_step = whole BVH walk + shade) with the wave-aggregated job fetch, and every lane
-// waited for the longest BVH walk of the wave at every bounce.  Since round 5 (RT_ASYNC_SHADE) the walk loop is left for a SHADE PHASE once
+// waited for the longest BVH walk of the wave at every bounce.  Since round 5 the walk loop is left for a SHADE PHASE once
 // at most RT_ASYNC_SLACK walks are unfinished: the finished lanes shade, regenerate and start their next walk, the unfinished ones keep
 // their cursor and walk on beside them.  Kept beside the decoupled kernel because which of the two is faster depends on the scene
 // (render_tiles.hpp: the crossover is at ~13 000 four-wide records; KERNELS.md).
@@ -528,13 +504,13 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 256 ? 3 : 1) void trace_kernel_plai
     uint32_t s = 0, s_end = 0;
     V3<R> acc;
     PathState<R> ps;
-    bool walking = false; // RT_ASYNC_SHADE: the lane has a walk in progress (begun, or suspended by a shade phase)
+    bool walking = false; // the lane has a walk in progress (begun, or suspended by a shade phase)
     Trav<R> tr;
     uint32_t tally_trips = 0; // (counting variant: trips of the lane's walk so far)
 
     // counting variant only: where a wave's time and lanes go (RTTNW_DEBUG_SCHED prints it) — wave clock per phase
-    // [0..3], lockstep iterations of the BVH walk [4] (with a node lane [7], with a leaf lane [8]) against the lane
-    // steps they served [5] node / [6] leaf, bounce rounds [9] and the lanes alive in them [10], regenerations [11,12]
+    // [0..3], trips of the walk loop [4] (with a node lane [7], with a leaf lane [8]) against the lane
+    // steps they served [5] node / [6] leaf, phases [9] and the lanes they shaded [10], regenerations [11,12] (trace_tally.hpp)
     unsigned long long prof[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (;;) {
         long long tk0 = 0;
@@ -564,7 +540,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 256 ? 3 : 1) void trace_kernel_plai
         if (__ballot(!done) == 0ull) break;
 
         // ---- one path per lane: regenerate or advance by one bounce
-        if constexpr (!COUNT && RT_ASYNC_SHADE != 0) {
+        if constexpr (!COUNT) {
             // ASYNCHRONOUS SHADE PHASES (round 5).  Rounds 1-4 ran `path_step` here: every lane's whole walk, then the shade — a round lasted as long as
             // its LONGEST walk (final_scene: 9.5 trips where the mean walk has 4.2; a node step served 20 of 64 lanes).  Now the walk loop is left once
             // at most RT_ASYNC_SLACK walks are unfinished: the finished lanes shade, regenerate and start their next walk, the unfinished ones keep
@@ -592,7 +568,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 256 ? 3 : 1) void trace_kernel_plai
                 }
                 // (serving the lanes at a leaf by CLASS of record kind — the cube's ~200 instructions run for 2 lanes of 64 on final_scene — only once enough
                 // lanes wait at a class was modelled at -8.8 % instructions and measured at -1.4 % / -4.5 % (f64 / f32): profiles/r05/README.md)
-                if (unfinished && tr.node < 0 && tr.node != TRAV_DONE) trav_leaf_step<RT_ASYNC_WHOLE_LEAF != 0>(tr, sc, ps.ray, t_min, stack, cnt);
+                if (unfinished && tr.node < 0 && tr.node != TRAV_DONE) trav_leaf_step(tr, sc, ps.ray, t_min, stack, cnt);
                 const unsigned long long um = __ballot(walking && tr.node != TRAV_DONE);
                 if (um == 0ull) break;
                 if (uint32_t(__popcll(um)) <= uint32_t(RT_ASYNC_SLACK) && __ballot(walking && tr.node == TRAV_DONE) != 0ull) break;
@@ -605,26 +581,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 256 ? 3 : 1) void trace_kernel_plai
                     ++s;
                 }
             }
-        } else if constexpr (!COUNT) {
-            if (!done) {
-                if (!alive && s < s_end) {
-                    path_begin(ps, kernarg_reload<CameraRec<R>>(offsetof(TraceArgsHead<R>, cam)), rc, pxrow & 0xFFFFu, pxrow >> 16, s);
-                    alive = true;
-                }
-                if (alive) {
-                    alive = path_step<NSTEPS>(ps, sc, rc, background, t_min, stack, cnt);
-                    if (!alive) { // main.rs:216: acc + color(...)
-                        acc = acc + ps.radiance;
-                        ++s;
-                    }
-                }
-            }
-        } else { // the same steps, with the wave clock read between the phases and the lockstep loop tallied (trace_tally.hpp)
-#if RT_ASYNC_SHADE
+        } else { // the same phase, with the wave clock read between its parts and the trips of the walk loop tallied (trace_tally.hpp)
             plain_phase_tallied<NSTEPS>(done, alive, walking, tr, tally_trips, pxrow & 0xFFFFu, pxrow >> 16, s, s_end, acc, ps, cam, rc, sc, background, t_min, stack, cnt, prof, counters, lane, tk0);
-#else
-            plain_round_tallied(done, alive, pxrow & 0xFFFFu, pxrow >> 16, s, s_end, acc, ps, cam, rc, sc, background, t_min, stack, cnt, prof, counters, lane, tk0);
-#endif
         }
     }
 
@@ -829,7 +787,7 @@ __global__ void probe_path_kernel(SceneView<R> sc, CameraRec<R> cam, RenderConst
         if (ps.bounce >= rc.max_depth) break;
     }
     *n_out = int32_t(n);
-    // the same sample again through path_step(), exactly as the trace kernel runs it: radiance after `out`
+    // the same sample again through path_step(), the same walk and shade steps the trace kernels run: radiance after `out`
     path_begin(ps, cam, rc, px, row, sample);
     while (path_step(ps, sc, rc, V3<R>(), t_min, stack, cnt)) {}
     double* tail = out + size_t(max_out) * PROBE_STRIDE;

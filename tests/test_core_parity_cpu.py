@@ -466,7 +466,7 @@ def test_quantised_records_on_hostile_geometry(hostsim, monkeypatch):
 def test_rays_nothing_can_cull_stay_inside_the_stack_bound(hostsim, scenes_lib, earth, precision):
     """A camera with lookfrom == lookat (w = unit(0): every ray NaN — the reference renders NaN pixels, main.rs:219-225 writes 0) and one whose
     view_up is parallel to the view: no plane distance of such a ray is a number, so even the inverted box of an unused node slot 'passes' (the
-    node steps leave the slot's own test to its box, rt_core.hpp RT_NODE_EMPTY_CHECK).  The walk must not start (rt_core.hpp
+    node steps leave the slot's own test to its box, rt_core.hpp trav_node_step4).  The walk must not start (rt_core.hpp
     slab_ray_can_be_culled): its stack stays inside the bound the lowering sized the device's LDS stacks by, and the pixels are NaN (or black)."""
     for name in ("cornell_box", "final_scene"):
         sc, setup = util.build(hostsim, scenes_lib, name, earth)

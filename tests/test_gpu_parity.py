@@ -497,7 +497,7 @@ def test_per_bounce_records_equal_oracle(gpu, oracle, scenes_lib, earth, name, n
     n, bounces, mats = util.compare_paths(lambda x, y, s: util.product_probe(gpu.debug_probe_path, gpu, sg, cam, p, x, y, s),
                                           lambda x, y, s: rto.probe_path(so, cam, p, x, y, s), pairs, tol=tol, growth=growth)
     assert n == n_pairs and bounces >= n_pairs and len(mats) >= 3
-    # the probe's own tail: the sample's radiance through path_step() (what the trace kernel runs) == the oracle's color()
+    # the probe's own tail: the sample's radiance through path_step() (the same steps the trace kernel runs) == the oracle's color()
     out = np.zeros(8 * util.PROBE_STRIDE + 4)
     for (x, y, s) in pairs[:20]:
         assert gpu.debug_probe_path(sg.handle, C.byref(cam), C.byref(p), x, y, s, out.ctypes.data, 8) >= 0

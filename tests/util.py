@@ -164,7 +164,7 @@ def compare_paths_reanchored(product_probe, oracle_scene, cam, p, pairs, eps, K=
       scatter  scattered or absorbed, attenuation.r, emitted.r, and record k+1's ray == the scattered ray
       end      a path that ended by a miss (fewer than max_depth and max_out records, the last one scattered): the oracle's
                continuation misses too
-      radiance the probe's tail (path_step(): what the trace kernels run) == sum_k emitted_k prod_{j<k} att_j of the oracle's three
+      radiance the probe's tail (path_step(): the steps the trace kernels run) == sum_k emitted_k prod_{j<k} att_j of the oracle's three
                channels along the product's path; the tail's bounce count == the records'
     CONTINUOUS values: the oracle is evaluated at the product's input and at its 12 one-coordinate perturbations (_ray_perturbations;
     for the scatter the direction's six and six of the hit point, +-K eps max(|p|, 1)): the product's value lies in the hull of those
