@@ -9,13 +9,9 @@ int rttnw_render_features(rttnw_scene* s, const rttnw_camera_desc* cam, const rt
     // the call's own arguments first, as rttnw_render_adaptive: their refusals need no device (nor a committed scene)
     if (!p) { rt::set_last_error("render_features: NULL argument"); return RTTNW_ERR_INVALID; }
     if (p->spp == 0) { rt::set_last_error("render_features: spp is 0"); return RTTNW_ERR_INVALID; }
-    if (p->reserved0 != 0) { rt::set_last_error("render_features: reserved0 must be 0"); return RTTNW_ERR_INVALID; }
-    if (p->tile_world != 1) { rt::set_last_error("render_features: host-output form needs tile_world == 1"); return RTTNW_ERR_INVALID; }
-    if (p->collect_counters != 0) { rt::set_last_error("render_features: collect_counters is not supported"); return RTTNW_ERR_UNSUPPORTED; }
+    if (int rc = rt::refuse_host_output_misuse("render_features", p->reserved0, p)) return rc;
     if (int rc = rt::validate(s, cam, p)) return rc;
-    return p->precision == RTTNW_F32          ? rt::render_features_t<float>(s, cam, p, out_albedo, out_normal, out_depth, out_alpha, stats)
-           : p->precision == RTTNW_F64_STRICT ? rt::ieee_strict::render_features_t<double>(s, cam, p, out_albedo, out_normal, out_depth, out_alpha, stats)
-                                              : rt::render_features_t<double>(s, cam, p, out_albedo, out_normal, out_depth, out_alpha, stats);
+    return RT_BY_PRECISION(p->precision, render_features_t, s, cam, p, out_albedo, out_normal, out_depth, out_alpha, stats);
 }
 
 int rttnw_denoise(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const double* albedo, const double* normal,

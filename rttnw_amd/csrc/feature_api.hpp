@@ -8,21 +8,10 @@
 namespace rt {
 
 // rttnw_render_features' device half: host outputs (each optional), blocking.  Arguments were checked by the caller.
-inline namespace RT_ARITH_NS {
-template <typename R>
-int render_features_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* out_albedo, double* out_normal, double* out_depth,
-                      double* out_alpha, rttnw_stats* stats);
-extern template int render_features_t<float>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, double*, double*, double*, double*, rttnw_stats*);
-extern template int render_features_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, double*, double*, double*, double*, rttnw_stats*);
-} // namespace RT_ARITH_NS
-#if !defined(RT_STRICT_F64)
-namespace ieee_strict {
-template <typename R>
-int render_features_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* out_albedo, double* out_normal, double* out_depth,
-                      double* out_alpha, rttnw_stats* stats);
-extern template int render_features_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, double*, double*, double*, double*, rttnw_stats*);
-} // namespace ieee_strict
-#endif
+#define RT_FEATURE_ENTRY_POINTS(X, R)                                                                                                          \
+    X(R, render_features_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* out_albedo, double* out_normal, \
+                             double* out_depth, double* out_alpha, rttnw_stats* stats))
+RT_DECLARE_BUILDS(RT_FEATURE_ENTRY_POINTS)
 
 // rttnw_denoise's device half (denoise.hip): host arrays in, host arrays out, blocking, on the current device.
 int denoise_device(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const double* albedo, const double* normal,

@@ -9,6 +9,6 @@
 
 namespace rt {
 inline namespace RT_ARITH_NS {
-template int render_features_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, double*, double*, double*, double*, rttnw_stats*);
+RT_FEATURE_ENTRY_POINTS(RT_INSTANTIATE_T, double)
 } // namespace RT_ARITH_NS
 } // namespace rt

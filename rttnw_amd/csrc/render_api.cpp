@@ -11,12 +11,10 @@
 
 namespace rt {
 
-// One precision's launch code, by rttnw_params::precision (RTTNW_F64_STRICT: the ieee_strict build of the f64 arithmetic, rt_core.hpp).
+// A plain render's launch code in the precision of `p`
 static int render_tiles_any(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
                             rttnw_stats* stats, bool sync_for_stats = true, bool prepare_only = false) {
-    if (p->precision == RTTNW_F32) return render_tiles_t<float>(s, d, cam, p, d_packed, stream, stats, sync_for_stats, prepare_only);
-    if (p->precision == RTTNW_F64_STRICT) return ieee_strict::render_tiles_t<double>(s, d, cam, p, d_packed, stream, stats, sync_for_stats, prepare_only);
-    return render_tiles_t<double>(s, d, cam, p, d_packed, stream, stats, sync_for_stats, prepare_only);
+    return RT_BY_PRECISION(p->precision, render_tiles_t, s, d, cam, p, d_packed, stream, stats, sync_for_stats, prepare_only, nullptr);
 }
 
 // The linear image of a blocking render (`linear`: d->linear or d->rg_linear, in the render's precision) to the caller's doubles: an f32 image is
@@ -27,6 +25,15 @@ static hipError_t copy_linear_out(const DevBuf<uint8_t>& linear, uint32_t precis
     const hipError_t e = hipMemcpy(tmp.data(), linear.p, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
     for (size_t i = 0; i < npx * 3; ++i) out[i] = double(tmp[i]);
     return e;
+}
+// What every host-output entry point ends with: the npx pixels of the image on the device to the caller's arrays (each optional), and a HIP error —
+// `e`: of the call's own steps before this one — as RTTNW_ERR_HIP under the call's name.
+static int copy_image_out(const char* what, const DevBuf<uint8_t>& rgba, const DevBuf<uint8_t>& linear, uint32_t precision, size_t npx, uint8_t* out_rgba8,
+                          double* out_linear, hipError_t e = hipSuccess) {
+    if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, rgba.p, npx * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_linear) e = copy_linear_out(linear, precision, npx, out_linear);
+    if (e != hipSuccess) { set_last_error(std::string(what) + ": " + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
+    return RTTNW_OK;
 }
 
 void device_release(DeviceState* d) {
@@ -190,9 +197,7 @@ int rttnw_debug_probe_path(rttnw_scene* s, const rttnw_camera_desc* cam, const r
                            uint32_t sample, double* out, uint32_t max_out) {
     if (int rc = rt::validate(s, cam, p)) return rc;
     if (!out || px >= p->width || row >= p->height) { rt::set_last_error("debug_probe_path: bad arguments"); return RTTNW_ERR_INVALID; }
-    if (p->precision == RTTNW_F64_STRICT) return rt::ieee_strict::probe_path_t<double>(s, cam, p, px, row, sample, out, max_out);
-    return p->precision == RTTNW_F32 ? rt::probe_path_t<float>(s, cam, p, px, row, sample, out, max_out)
-                                     : rt::probe_path_t<double>(s, cam, p, px, row, sample, out, max_out);
+    return RT_BY_PRECISION(p->precision, probe_path_t, s, cam, p, px, row, sample, out, max_out);
 }
 
 
@@ -254,15 +259,9 @@ int rttnw_render(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_param
     if (e == hipSuccess) e = d->linear.grow(npx * 3 * rsz);
     if (e == hipSuccess) e = d->rgba.grow(npx * 4);
     if (e != hipSuccess) { rt::set_last_error(std::string("render: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
-    int rc = rttnw_render_tiles_device(s, cam, p, d->packed.p, nullptr, stats);
-    if (rc) return rc;
-    rc = rttnw_untile_device(p->width, p->height, 1, p->precision, d->packed.p, d->linear.p, d->rgba.p, nullptr);
-    if (rc) return rc;
-    e = hipDeviceSynchronize();
-    if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, d->rgba.p, npx * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_linear_rgb) e = rt::copy_linear_out(d->linear, p->precision, npx, out_linear_rgb);
-    if (e != hipSuccess) { rt::set_last_error(std::string("render: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
-    return RTTNW_OK;
+    if (int rc = rttnw_render_tiles_device(s, cam, p, d->packed.p, nullptr, stats)) return rc;
+    if (int rc = rttnw_untile_device(p->width, p->height, 1, p->precision, d->packed.p, d->linear.p, d->rgba.p, nullptr)) return rc;
+    return rt::copy_image_out("render", d->rgba, d->linear, p->precision, npx, out_rgba8, out_linear_rgb, hipDeviceSynchronize());
 }
 
 int rttnw_render_adaptive(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, double* out_linear_rgb,
@@ -272,23 +271,15 @@ int rttnw_render_adaptive(rttnw_scene* s, const rttnw_camera_desc* cam, const rt
     if (a->pass_spp == 0) { rt::set_last_error("render_adaptive: pass_spp is 0"); return RTTNW_ERR_INVALID; }
     if (p->spp == 0 || p->spp % a->pass_spp != 0) { rt::set_last_error("render_adaptive: spp (the cap) must be a positive multiple of pass_spp"); return RTTNW_ERR_INVALID; }
     if (!(a->rel_error >= 0.0) || !(a->abs_error >= 0.0)) { rt::set_last_error("render_adaptive: rel_error and abs_error must be >= 0 (and not NaN)"); return RTTNW_ERR_INVALID; }
-    if (a->reserved0 != 0) { rt::set_last_error("render_adaptive: reserved0 must be 0"); return RTTNW_ERR_INVALID; }
-    if (p->tile_world != 1) { rt::set_last_error("render_adaptive: host-output form needs tile_world == 1"); return RTTNW_ERR_INVALID; }
-    if (p->collect_counters != 0) { rt::set_last_error("render_adaptive: collect_counters is not supported"); return RTTNW_ERR_UNSUPPORTED; }
+    if (int rc = rt::refuse_host_output_misuse("render_adaptive", a->reserved0, p)) return rc;
     if (int rc = rt::validate(s, cam, p)) return rc;
     rt::DeviceState* d = s->device;
-    int rc = p->precision == RTTNW_F32          ? rt::render_adaptive_t<float>(s, cam, p, a, stats)
-             : p->precision == RTTNW_F64_STRICT ? rt::ieee_strict::render_adaptive_t<double>(s, cam, p, a, stats)
-                                                : rt::render_adaptive_t<double>(s, cam, p, a, stats);
-    if (rc) return rc;
+    if (int rc = RT_BY_PRECISION(p->precision, render_adaptive_t, s, cam, p, a, stats)) return rc;
     const size_t npx = size_t(p->width) * p->height;
     hipError_t e = hipSuccess;
-    if (out_rgba8) e = hipMemcpy(out_rgba8, d->rgba.p, npx * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_spp) e = hipMemcpy(out_spp, d->ad_spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (out_spp) e = hipMemcpy(out_spp, d->ad_spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess && out_stderr_rgb) e = hipMemcpy(out_stderr_rgb, d->ad_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_linear_rgb) e = rt::copy_linear_out(d->linear, p->precision, npx, out_linear_rgb);
-    if (e != hipSuccess) { rt::set_last_error(std::string("render_adaptive: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
-    return RTTNW_OK;
+    return rt::copy_image_out("render_adaptive", d->rgba, d->linear, p->precision, npx, out_rgba8, out_linear_rgb, e);
 }
 
 int rttnw_render_region(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
@@ -299,21 +290,11 @@ int rttnw_render_region(rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
         rt::set_last_error("render_region: the window [x0, x1) x [y0, y1) must be non-empty and lie inside the width x height frame");
         return RTTNW_ERR_INVALID;
     }
-    if (p->reserved0 != 0) { rt::set_last_error("render_region: reserved0 must be 0"); return RTTNW_ERR_INVALID; }
-    if (p->tile_world != 1) { rt::set_last_error("render_region: host-output form needs tile_world == 1"); return RTTNW_ERR_INVALID; }
-    if (p->collect_counters != 0) { rt::set_last_error("render_region: collect_counters is not supported (the active-list kernels do not tally)"); return RTTNW_ERR_UNSUPPORTED; }
+    if (int rc = rt::refuse_host_output_misuse("render_region", p->reserved0, p, " (the active-list kernels do not tally)")) return rc;
     if (int rc = rt::validate(s, cam, p)) return rc;
-    rt::DeviceState* d = s->device;
-    int rc = p->precision == RTTNW_F32          ? rt::render_region_t<float>(s, cam, p, x0, y0, x1, y1, mask, stats)
-             : p->precision == RTTNW_F64_STRICT ? rt::ieee_strict::render_region_t<double>(s, cam, p, x0, y0, x1, y1, mask, stats)
-                                                : rt::render_region_t<double>(s, cam, p, x0, y0, x1, y1, mask, stats);
-    if (rc) return rc;
-    const size_t wpx = size_t(x1 - x0) * (y1 - y0);
-    hipError_t e = hipSuccess;
-    if (out_rgba8) e = hipMemcpy(out_rgba8, d->rg_rgba.p, wpx * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_linear_rgb) e = rt::copy_linear_out(d->rg_linear, p->precision, wpx, out_linear_rgb);
-    if (e != hipSuccess) { rt::set_last_error(std::string("render_region: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
-    return RTTNW_OK;
+    if (int rc = RT_BY_PRECISION(p->precision, render_region_t, s, cam, p, x0, y0, x1, y1, mask, stats)) return rc;
+    const rt::DeviceState* d = s->device;
+    return rt::copy_image_out("render_region", d->rg_rgba, d->rg_linear, p->precision, size_t(x1 - x0) * (y1 - y0), out_rgba8, out_linear_rgb);
 }
 
 } // extern "C"
@@ -351,7 +332,7 @@ struct Rccl {
 static Rccl g_rccl;
 struct MultiComms { // one communicator set per distinct list of devices, kept until rttnw_shutdown() / process exit
     std::vector<int> devices;
-    std::vector<ncclComm_t> comms;
+    std::vector<ncclComm_t> comms; // (empty: the set-up over these devices failed, comms_over)
     std::mutex in_use; // RCCL allows ONE thread at a time to issue operations on a communicator: held from GroupStart to GroupEnd
 };
 static std::vector<MultiComms*> g_comms;
@@ -386,6 +367,202 @@ static DeviceState* state_on(::rttnw_scene* s, int device, std::string& err) {
     s->more_devices.push_back(d);
     return d;
 }
+
+// The environment of a call, read once (a MultiPlan holds it).  The gather to the root is a device-to-device copy for ranks on the root's device; for the others one of
+// TWO transports over xGMI (RTTNW_MULTI_GATHER=rccl|peer, default rccl):
+//   rccl  a grouped ncclSend / ncclRecv per rank buffer (north_star's "RCCL gather over xGMI"; communicators cached per device list);
+//   peer  hipMemcpyPeerAsync of each rank's packed tiles into the root's gather buffer on the RANK's stream, an event behind it that the
+//         root's stream waits for — 5 MB per rank, no library, no communicator.  Also what the call FALLS THROUGH to when RCCL cannot be
+//         loaded or ncclCommInitAll fails (one stderr line; rttnw_stats.reserved bit 9 of rank 0), so that a node whose RCCL is broken
+//         still renders.  Bit 8 of stats[0].reserved: the gather went through peer copies.
+// RTTNW_MULTI_FORCE_TRANSPORT=1 (tests; RTTNW_MULTI_FORCE_RCCL=1 is the older name): the ranks on the root's device travel through the
+// transport too — the root sending to itself — so that the dlopen'ed entry points, the communicator set-up, the peer copies, the stream
+// ordering and the error paths run on a box with ONE GPU as well.  RTTNW_MULTI_FAIL_RCCL=1 (tests): the RCCL set-up reports failure.
+// RTTNW_DEBUG_MULTI: one stderr line per communicator set-up and per gather.
+struct MultiEnv {
+    bool force_transport = false, gather_peer = false, gather_invalid = false, fail_rccl = false, debug = false;
+    MultiEnv() {
+        const auto is_1 = [](const char* e) { return e && e[0] == '1'; };
+        force_transport = is_1(getenv("RTTNW_MULTI_FORCE_RCCL")) || is_1(getenv("RTTNW_MULTI_FORCE_TRANSPORT"));
+        const char* gather = getenv("RTTNW_MULTI_GATHER");
+        gather_peer = gather && std::string(gather) == "peer";
+        gather_invalid = gather && !gather_peer && std::string(gather) != "rccl";
+        fail_rccl = is_1(getenv("RTTNW_MULTI_FAIL_RCCL"));
+        debug = getenv("RTTNW_DEBUG_MULTI") != nullptr;
+    }
+};
+
+// Who traces what, and where: made once per call (multi_plan), read by every step.
+struct MultiPlan {
+    const MultiEnv env;
+    struct Rank { DeviceState* d; uint32_t dev, slot; }; // its device's state, index in `devices`, and its place among the ranks of that device
+    std::vector<Rank> ranks;
+    std::vector<int> devices;             // in order of first appearance; devices[0] = the root's (rank 0's) device
+    std::vector<DeviceState*> dev_state;  // per distinct device
+    std::vector<uint32_t> dev_ranks;      // ... and how many ranks live on it
+    DeviceState* root = nullptr;
+    size_t rsz = 0, chunk = 0, npx = 0;   // bytes of a real, of a rank's packed tiles; pixels of the image
+    bool transport() const { return devices.size() > 1 || env.force_transport; }         // some rank's tiles travel
+    bool local(uint32_t r) const { return !env.force_transport && ranks[r].dev == 0; }    // rank r's do not: a copy on the root's device
+    uint8_t* packed(uint32_t r) const { return ranks[r].d->multi_packed.p + chunk * ranks[r].slot; } // rank r's packed tiles, on its device
+    uint8_t* gathered(uint32_t r) const { return root->gathered.p + chunk * r; }                      // ... and their place on the root's
+};
+
+static int multi_plan(::rttnw_scene* s, const rttnw_params& p, uint32_t ngpu, const int32_t* device_ids, MultiPlan& m) {
+    std::string err;
+    m.ranks.resize(ngpu);
+    for (uint32_t r = 0; r < ngpu; ++r) {
+        DeviceState* d = state_on(s, device_ids[r], err);
+        if (!d) { set_last_error("render_multi: " + err); return RTTNW_ERR_HIP; }
+        uint32_t k = 0;
+        while (k < m.devices.size() && m.devices[k] != device_ids[r]) ++k;
+        if (k == m.devices.size()) { m.devices.push_back(device_ids[r]); m.dev_state.push_back(d); m.dev_ranks.push_back(0); }
+        m.ranks[r] = {d, k, m.dev_ranks[k]++};
+    }
+    rttnw_tile_layout L;
+    fill_layout(p.width, p.height, ngpu, L);
+    m.root = m.ranks[0].d;
+    m.rsz = p.precision == RTTNW_F32 ? sizeof(float) : sizeof(double);
+    m.chunk = size_t(L.pixels_per_rank) * 4 * m.rsz;
+    m.npx = size_t(p.width) * p.height;
+    return 0;
+}
+
+// Everything that allocates, before anything is launched (an allocation or a free between two ranks' launches would synchronise its whole
+// device): the streams, this layer's buffers, then per rank what a first use brings — scene uploads and workspace growth
+static int multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const MultiPlan& m) {
+    for (size_t k = 0; k < m.devices.size(); ++k) {
+        DeviceState* d = m.dev_state[k];
+        HIP_TRY(hipSetDevice(d->device));
+        if (!d->stream) HIP_TRY(create_stream(d->stream, hipStreamNonBlocking));
+        HIP_TRY(d->multi_packed.grow(m.chunk * m.dev_ranks[k]));
+    }
+    DeviceState* root = m.root;
+    HIP_TRY(hipSetDevice(root->device));
+    HIP_TRY(root->gathered.grow(m.chunk * m.ranks.size()));
+    HIP_TRY(root->linear.grow(m.npx * 3 * m.rsz));
+    HIP_TRY(root->rgba.grow(m.npx * 4));
+    for (uint32_t r = 0; r < m.ranks.size(); ++r) {
+        rttnw_params pr = p;
+        pr.tile_rank = r;
+        DeviceState* d = m.ranks[r].d;
+        if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), d->stream.get(), nullptr, false, true)) return rc;
+    }
+    return 0;
+}
+
+// Every rank traces its tiles, on its device's stream, between its two events of `ev`; ranks that share a device run one after the other
+static int multi_trace(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const MultiPlan& m, std::vector<Event>& ev, rttnw_stats* stats) {
+    for (uint32_t r = 0; r < m.ranks.size(); ++r) {
+        DeviceState* d = m.ranks[r].d;
+        HIP_TRY(hipSetDevice(d->device));
+        rttnw_params pr = p;
+        pr.tile_rank = r;
+        HIP_TRY(create_event(ev[2 * r]));
+        HIP_TRY(create_event(ev[2 * r + 1]));
+        HIP_TRY(hipEventRecord(ev[2 * r].get(), d->stream.get()));
+        if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), d->stream.get(), stats ? &stats[r] : nullptr, false)) return rc;
+        HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), d->stream.get()));
+    }
+    return 0;
+}
+
+// The communicator set over `devices`: found, or made at the first call over that list and kept (set-up costs ~100 ms; destroyed by
+// rttnw_shutdown() or at exit).  nullptr when there is none: a failed set-up says why on stderr, once, and is kept as well — an entry without
+// communicators —, so that later calls over that list go straight to the peer copies.  Called with g_comms_mutex held.
+static MultiComms* comms_over(const std::vector<int>& devices, const MultiEnv& env) {
+    for (MultiComms* c : g_comms)
+        if (c->devices == devices) return c->comms.empty() ? nullptr : c;
+    MultiComms* mc = new MultiComms();
+    mc->devices = devices;
+    g_comms.push_back(mc);
+    std::string why;
+    if (env.fail_rccl) why = "RTTNW_MULTI_FAIL_RCCL=1";
+    else if (g_rccl.load(why)) {
+        mc->comms.resize(devices.size());
+        const ncclResult_t nr = g_rccl.CommInitAll(mc->comms.data(), int(devices.size()), devices.data());
+        if (nr != ncclSuccess) { why = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(nr); mc->comms.clear(); }
+    }
+    if (mc->comms.empty()) {
+        fprintf(stderr, "[render_multi] RCCL gather unavailable (%s): gathering through peer copies\n", why.c_str());
+        return nullptr;
+    }
+    if (!g_comms_atexit) { g_comms_atexit = true; std::atexit(destroy_comms); }
+    if (env.debug) fprintf(stderr, "[render_multi] RCCL communicators over %zu device(s)\n", devices.size());
+    return mc;
+}
+
+// The two transports of the ranks' tiles to the root's gather buffer (MultiEnv has what they are).
+constexpr int GATHER_UNAVAILABLE = 1; // gather_rccl: there is no communicator set; nothing has been sent yet, so gather_peer can do the same job
+static int gather_rccl(const MultiPlan& m) {
+    std::unique_lock<std::mutex> comms_lock(g_comms_mutex);
+    MultiComms* mc = comms_over(m.devices, m.env);
+    if (!mc) return GATHER_UNAVAILABLE;
+    // (the list's lock is released, the set's own is taken: two host threads rendering over the SAME devices take turns on
+    // its communicators; threads over different device lists do not wait for each other)
+    std::unique_lock<std::mutex> use(mc->in_use);
+    comms_lock.unlock();
+    ncclResult_t nr = g_rccl.GroupStart();
+    uint32_t n_sent = 0;
+    for (uint32_t r = 0; r < m.ranks.size() && nr == ncclSuccess; ++r) {
+        if (m.local(r)) continue; // on the root's device: copied by multi_untile
+        const uint32_t k = m.ranks[r].dev;
+        nr = g_rccl.Send(m.packed(r), m.chunk, ncclChar, 0, mc->comms[k], m.ranks[r].d->stream.get());
+        if (nr == ncclSuccess) nr = g_rccl.Recv(m.gathered(r), m.chunk, ncclChar, int(k), mc->comms[0], m.root->stream.get());
+        ++n_sent;
+    }
+    ncclResult_t ne = g_rccl.GroupEnd();
+    if (nr == ncclSuccess) nr = ne;
+    if (nr != ncclSuccess) { set_last_error(std::string("RCCL gather: ") + g_rccl.GetErrorString(nr)); return RTTNW_ERR_HIP; }
+    if (m.env.debug) fprintf(stderr, "[render_multi] %u rank buffer(s) of %zu bytes through ncclSend / ncclRecv\n", n_sent, m.chunk);
+    return 0;
+}
+static int gather_peer(const MultiPlan& m) {
+    DeviceState* root = m.root;
+    // direct access root <- rank device where the fabric allows it (xGMI: every pair of a node); without it the copy is staged by the runtime
+    for (size_t k = 1; k < m.devices.size(); ++k) {
+        int can = 0;
+        if (hipDeviceCanAccessPeer(&can, m.devices[k], root->device) == hipSuccess && can) {
+            HIP_TRY(hipSetDevice(m.devices[k]));
+            const hipError_t e = hipDeviceEnablePeerAccess(root->device, 0);
+            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIP_TRY(e);
+            (void)hipGetLastError();
+        }
+    }
+    std::vector<Event> sent(m.ranks.size());
+    uint32_t n_sent = 0;
+    for (uint32_t r = 0; r < m.ranks.size(); ++r) {
+        if (m.local(r)) continue; // on the root's device: copied by multi_untile
+        DeviceState* d = m.ranks[r].d;
+        HIP_TRY(hipSetDevice(d->device));
+        HIP_TRY(hipMemcpyPeerAsync(m.gathered(r), root->device, m.packed(r), d->device, m.chunk, d->stream.get()));
+        HIP_TRY(create_event(sent[r], hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(sent[r].get(), d->stream.get()));
+        ++n_sent;
+    }
+    HIP_TRY(hipSetDevice(root->device));
+    for (uint32_t r = 0; r < m.ranks.size(); ++r)
+        if (sent[r]) HIP_TRY(hipStreamWaitEvent(root->stream.get(), sent[r].get(), 0)); // the un-tile reads what the ranks' streams have written
+    if (m.env.debug) fprintf(stderr, "[render_multi] %u rank buffer(s) of %zu bytes through hipMemcpyPeerAsync\n", n_sent, m.chunk);
+    // (the events are destroyed when this function ends: a recorded event may be destroyed while work waits on it — the wait was enqueued)
+    return 0;
+}
+
+// On the root's stream: the tiles of the ranks that live on its device (unless they went through the transport) join the gathered ones, and the
+// image is made of them.  Then every device's stream has finished.
+static int multi_untile(const rttnw_params& p, const MultiPlan& m) {
+    DeviceState* root = m.root;
+    HIP_TRY(hipSetDevice(root->device));
+    for (uint32_t r = 0; r < m.ranks.size(); ++r)
+        if (m.local(r)) HIP_TRY(hipMemcpyAsync(m.gathered(r), m.packed(r), m.chunk, hipMemcpyDeviceToDevice, root->stream.get()));
+    if (int rc = rttnw_untile_device(p.width, p.height, p.tile_world, p.precision, root->gathered.p, root->linear.p, root->rgba.p, root->stream.get())) return rc;
+    for (DeviceState* d : m.dev_state) {
+        HIP_TRY(hipSetDevice(d->device));
+        HIP_TRY(hipStreamSynchronize(d->stream.get()));
+    }
+    HIP_TRY(hipSetDevice(root->device));
+    return 0;
+}
 } // namespace rt
 
 extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p_in, uint32_t ngpu, const int32_t* device_ids,
@@ -398,184 +575,32 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
     const int n_dev = rttnw_device_count();
     for (uint32_t r = 0; r < ngpu; ++r)
         if (device_ids[r] < 0 || device_ids[r] >= n_dev) { set_last_error("render_multi: no such device"); return RTTNW_ERR_INVALID; }
-    DeviceGuard restore;
-
-    std::string err;
-    std::vector<DeviceState*> st(ngpu);
-    std::vector<int> distinct; // devices in order of first appearance; distinct[0] = the root's (rank 0's) device
-    std::vector<uint32_t> slot(ngpu), per_dev;
-    for (uint32_t r = 0; r < ngpu; ++r) {
-        st[r] = state_on(s, device_ids[r], err);
-        if (!st[r]) { set_last_error("render_multi: " + err); return RTTNW_ERR_HIP; }
-        size_t k = 0;
-        while (k < distinct.size() && distinct[k] != device_ids[r]) ++k;
-        if (k == distinct.size()) { distinct.push_back(device_ids[r]); per_dev.push_back(0); }
-        slot[r] = per_dev[k]++; // this rank's place among the ranks of its device
+    DeviceGuard restore; // (the caller's device is current again after EVERY return below, the error paths included)
+    MultiPlan m;
+    if (int rc = multi_plan(s, p, ngpu, device_ids, m)) return rc;
+    if (int rc = multi_prepare(s, cam, p, m)) return rc;
+    std::vector<Event> ev(size_t(ngpu) * 2); // per rank: before and behind its trace
+    if (int rc = multi_trace(s, cam, p, m, ev, stats)) return rc;
+    // (refused here, after the trace, as it always was)
+    if (m.env.gather_invalid) { set_last_error("render_multi: RTTNW_MULTI_GATHER must be rccl or peer"); return RTTNW_ERR_INVALID; }
+    bool use_peer = m.transport() && m.env.gather_peer, fell_back = false;
+    if (m.transport() && !use_peer) {
+        const int rc = gather_rccl(m);
+        if (rc == GATHER_UNAVAILABLE) use_peer = fell_back = true;
+        else if (rc) return rc;
     }
-    rttnw_tile_layout L;
-    fill_layout(p.width, p.height, ngpu, L);
-    const size_t rsz = p.precision == RTTNW_F32 ? sizeof(float) : sizeof(double);
-    const size_t chunk = size_t(L.pixels_per_rank) * 4 * rsz, npx = size_t(p.width) * p.height;
-    for (size_t k = 0; k < distinct.size(); ++k) {
-        DeviceState* d = state_on(s, distinct[k], err);
-        HIP_TRY(hipSetDevice(d->device));
-        if (!d->stream) HIP_TRY(create_stream(d->stream, hipStreamNonBlocking));
-        HIP_TRY(d->multi_packed.grow(chunk * per_dev[k]));
+    if (use_peer)
+        if (int rc = gather_peer(m)) return rc;
+    if (int rc = multi_untile(p, m)) return rc;
+    for (uint32_t r = 0; r < ngpu && stats; ++r) {
+        float ms = 0;
+        HIP_TRY(hipSetDevice(m.ranks[r].d->device));
+        HIP_TRY(hipEventElapsedTime(&ms, ev[2 * r].get(), ev[2 * r + 1].get()));
+        stats[r].kernel_ms = ms; // trace + resolve of this rank (the other fields are render_tiles_t's)
     }
-    DeviceState* root = st[0];
-    HIP_TRY(hipSetDevice(root->device));
-    HIP_TRY(root->gathered.grow(chunk * ngpu));
-    HIP_TRY(root->linear.grow(npx * 3 * rsz));
-    HIP_TRY(root->rgba.grow(npx * 4));
-
-    // ---- first use: scene uploads and workspace growth for EVERY rank, before anything is launched (an allocation or a
-    // free between two ranks' launches would synchronise its whole device)
-    for (uint32_t r = 0; r < ngpu; ++r) {
-        rttnw_params pr = p;
-        pr.tile_rank = r;
-        void* dst = st[r]->multi_packed.p + chunk * slot[r];
-        int rc = render_tiles_any(s, st[r], cam, &pr, dst, st[r]->stream.get(), nullptr, false, true);
-        if (rc) return rc;
-    }
-    // ---- every rank traces its tiles, on its device's stream; ranks that share a device run one after the other
-    std::vector<Event> ev(size_t(ngpu) * 2);
-    for (uint32_t r = 0; r < ngpu; ++r) {
-        DeviceState* d = st[r];
-        HIP_TRY(hipSetDevice(d->device));
-        rttnw_params pr = p;
-        pr.tile_rank = r;
-        void* dst = d->multi_packed.p + chunk * slot[r];
-        HIP_TRY(create_event(ev[2 * r]));
-        HIP_TRY(create_event(ev[2 * r + 1]));
-        HIP_TRY(hipEventRecord(ev[2 * r].get(), d->stream.get()));
-        int rc = render_tiles_any(s, d, cam, &pr, dst, d->stream.get(), stats ? &stats[r] : nullptr, false);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), d->stream.get()));
-    }
-
-    // ---- gather to the root: a device-to-device copy for ranks on the root's device; for the others one of TWO transports over xGMI
-    // (RTTNW_MULTI_GATHER=rccl|peer, default rccl):
-    //   rccl  a grouped ncclSend / ncclRecv per rank buffer (north_star's "RCCL gather over xGMI"; communicators cached per device list);
-    //   peer  hipMemcpyPeerAsync of each rank's packed tiles into the root's gather buffer on the RANK's stream, an event behind it that the
-    //         root's stream waits for — 5 MB per rank, no library, no communicator.  Also what the call FALLS THROUGH to when RCCL cannot be
-    //         loaded or ncclCommInitAll fails (one stderr line; rttnw_stats.reserved bit 9 of rank 0), so that a node whose RCCL is broken
-    //         still renders.  Bit 8 of stats[0].reserved: the gather went through peer copies.
-    // RTTNW_MULTI_FORCE_TRANSPORT=1 (tests; RTTNW_MULTI_FORCE_RCCL=1 is the older name): the ranks on the root's device travel through the
-    // transport too — the root sending to itself — so that the dlopen'ed entry points, the communicator set-up, the peer copies, the stream
-    // ordering and the error paths run on a box with ONE GPU as well.  RTTNW_MULTI_FAIL_RCCL=1 (tests): the RCCL set-up reports failure.
-    const char* force_env = getenv("RTTNW_MULTI_FORCE_RCCL");
-    const char* force_env2 = getenv("RTTNW_MULTI_FORCE_TRANSPORT");
-    const bool force_rccl = (force_env && force_env[0] == '1') || (force_env2 && force_env2[0] == '1'); // (every rank through the transport)
-    const char* gather_env = getenv("RTTNW_MULTI_GATHER");
-    bool use_peer = gather_env && std::string(gather_env) == "peer";
-    if (gather_env && !use_peer && std::string(gather_env) != "rccl") { set_last_error("render_multi: RTTNW_MULTI_GATHER must be rccl or peer"); return RTTNW_ERR_INVALID; }
-    bool fell_back = false;
-    const bool debug_multi = getenv("RTTNW_DEBUG_MULTI") != nullptr;
-    if ((distinct.size() > 1 || force_rccl) && !use_peer) {
-        std::unique_lock<std::mutex> comms_lock(g_comms_mutex);
-        MultiComms* mc = nullptr;
-        std::string why;
-        const char* fail_env = getenv("RTTNW_MULTI_FAIL_RCCL");
-        if (fail_env && fail_env[0] == '1') why = "RTTNW_MULTI_FAIL_RCCL=1";
-        else if (!g_rccl.load(err)) why = err;
-        if (why.empty()) {
-            for (MultiComms* c : g_comms)
-                if (c->devices == distinct) mc = c;
-            if (!mc) {
-                mc = new MultiComms();
-                mc->devices = distinct;
-                mc->comms.resize(distinct.size());
-                ncclResult_t nr = g_rccl.CommInitAll(mc->comms.data(), int(distinct.size()), distinct.data());
-                if (nr != ncclSuccess) {
-                    why = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(nr);
-                    delete mc;
-                    mc = nullptr;
-                } else {
-                    g_comms.push_back(mc); // kept: communicator set-up costs ~100 ms; destroyed by rttnw_shutdown() or at exit
-                    if (!g_comms_atexit) { g_comms_atexit = true; std::atexit(destroy_comms); }
-                    if (debug_multi) fprintf(stderr, "[render_multi] RCCL communicators over %zu device(s)\n", distinct.size());
-                }
-            }
-        }
-        if (!mc) {
-            // nothing has been sent yet: the peer transport does the same job
-            fprintf(stderr, "[render_multi] RCCL gather unavailable (%s): gathering through peer copies\n", why.c_str());
-            use_peer = fell_back = true;
-        } else {
-            // (the list's lock is released, the set's own is taken: two host threads rendering over the SAME devices take turns on
-            // its communicators; threads over different device lists do not wait for each other)
-            std::unique_lock<std::mutex> use(mc->in_use);
-            comms_lock.unlock();
-            ncclResult_t nr = g_rccl.GroupStart();
-            uint32_t n_sent = 0;
-            for (uint32_t r = 0; r < ngpu && nr == ncclSuccess; ++r) {
-                size_t k = 0;
-                while (distinct[k] != device_ids[r]) ++k;
-                if (k == 0 && !force_rccl) continue; // on the root's device: copied below
-                const void* src = st[r]->multi_packed.p + chunk * slot[r];
-                nr = g_rccl.Send(src, chunk, ncclChar, 0, mc->comms[k], st[r]->stream.get());
-                if (nr == ncclSuccess) nr = g_rccl.Recv(root->gathered.p + chunk * r, chunk, ncclChar, int(k), mc->comms[0], root->stream.get());
-                ++n_sent;
-            }
-            ncclResult_t ne = g_rccl.GroupEnd();
-            if (nr == ncclSuccess) nr = ne;
-            if (nr != ncclSuccess) { set_last_error(std::string("RCCL gather: ") + g_rccl.GetErrorString(nr)); return RTTNW_ERR_HIP; }
-            if (debug_multi) fprintf(stderr, "[render_multi] %u rank buffer(s) of %zu bytes through ncclSend / ncclRecv\n", n_sent, chunk);
-        }
-    }
-    if ((distinct.size() > 1 || force_rccl) && use_peer) {
-        // direct access root <- rank device where the fabric allows it (xGMI: every pair of a node); without it the copy is staged by the runtime
-        for (size_t k = 1; k < distinct.size(); ++k) {
-            int can = 0;
-            if (hipDeviceCanAccessPeer(&can, distinct[k], root->device) == hipSuccess && can) {
-                HIP_TRY(hipSetDevice(distinct[k]));
-                const hipError_t e = hipDeviceEnablePeerAccess(root->device, 0);
-                if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIP_TRY(e);
-                (void)hipGetLastError();
-            }
-        }
-        std::vector<Event> sent(ngpu);
-        uint32_t n_sent = 0;
-        for (uint32_t r = 0; r < ngpu; ++r) {
-            if (device_ids[r] == root->device && !force_rccl) continue; // on the root's device: copied below
-            HIP_TRY(hipSetDevice(st[r]->device));
-            const void* src = st[r]->multi_packed.p + chunk * slot[r];
-            HIP_TRY(hipMemcpyPeerAsync(root->gathered.p + chunk * r, root->device, src, st[r]->device, chunk, st[r]->stream.get()));
-            HIP_TRY(create_event(sent[r], hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(sent[r].get(), st[r]->stream.get()));
-            ++n_sent;
-        }
-        HIP_TRY(hipSetDevice(root->device));
-        for (uint32_t r = 0; r < ngpu; ++r)
-            if (sent[r]) HIP_TRY(hipStreamWaitEvent(root->stream.get(), sent[r].get(), 0)); // the un-tile below reads what the ranks' streams have written
-        if (debug_multi) fprintf(stderr, "[render_multi] %u rank buffer(s) of %zu bytes through hipMemcpyPeerAsync\n", n_sent, chunk);
-        // (the events are destroyed when this block ends: a recorded event may be destroyed while work waits on it — the wait was enqueued)
-    }
-    HIP_TRY(hipSetDevice(root->device));
-    if (!force_rccl)
-        for (uint32_t r = 0; r < ngpu; ++r)
-            if (device_ids[r] == root->device)
-                HIP_TRY(hipMemcpyAsync(root->gathered.p + chunk * r, root->multi_packed.p + chunk * slot[r], chunk, hipMemcpyDeviceToDevice, root->stream.get()));
-    int rc = rttnw_untile_device(p.width, p.height, ngpu, p.precision, root->gathered.p, root->linear.p, root->rgba.p, root->stream.get());
-    if (rc) return rc;
-    for (size_t k = 0; k < distinct.size(); ++k) {
-        DeviceState* d = state_on(s, distinct[k], err);
-        HIP_TRY(hipSetDevice(d->device));
-        HIP_TRY(hipStreamSynchronize(d->stream.get()));
-    }
-    HIP_TRY(hipSetDevice(root->device));
-    if (stats)
-        for (uint32_t r = 0; r < ngpu; ++r) {
-            float ms = 0;
-            HIP_TRY(hipSetDevice(st[r]->device));
-            HIP_TRY(hipEventElapsedTime(&ms, ev[2 * r].get(), ev[2 * r + 1].get()));
-            stats[r].kernel_ms = ms; // trace + resolve of this rank
-        }
-    if (stats && use_peer && (distinct.size() > 1 || force_rccl)) stats[0].reserved |= 0x100u | (fell_back ? 0x200u : 0u);
-    HIP_TRY(hipSetDevice(root->device));
-    if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, root->rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_linear_rgb) HIP_TRY(copy_linear_out(root->linear, p.precision, npx, out_linear_rgb));
-    return RTTNW_OK;
+    if (stats && use_peer) stats[0].reserved |= 0x100u | (fell_back ? 0x200u : 0u);
+    HIP_TRY(hipSetDevice(m.root->device));
+    return copy_image_out("render_multi", m.root->rgba, m.root->linear, p.precision, m.npx, out_rgba8, out_linear_rgb);
 }
 
 // Release what the library keeps for the life of the process (today: the RCCL communicator sets of rttnw_render_multi).  Scenes

@@ -266,11 +266,13 @@ struct DeviceState {
     DevBuf<uint8_t> gathered;       // root device: every rank's packed tiles
     // scratch for the blocking host-output render()
     DevBuf<uint8_t> packed, linear, rgba;
-    // rttnw_render_adaptive: per packed pixel the noise state (adaptive.hpp) and the active bit, the block list and its scan, the maps
-    DevBuf<uint8_t> ad_state, ad_active, ad_quads, ad_scan, ad_spp, ad_stderr;
+    // rttnw_render_adaptive: per packed pixel the noise state (adaptive.hpp) and the active bit, the maps
+    DevBuf<uint8_t> ad_state, ad_active, ad_spp, ad_stderr;
     // rttnw_render_region: the caller's mask (window-sized), the selection byte per packed pixel, the running sums per list slot and the
-    // window-sized outputs.  (The block list and its scan are ad_quads / ad_scan: scratch that every user builds anew before it reads it.)
+    // window-sized outputs
     DevBuf<uint8_t> rg_mask, rg_select, rg_sums, rg_linear, rg_rgba;
+    // both: the list of 2x2 blocks that hold a marked pixel and its scan (render_tiles.hpp build_quad_list), built anew before every use
+    DevBuf<uint8_t> list_quads, list_scan;
 };
 // What render_tiles_t needs to run a pass that is not a plain render's (render_tiles.hpp): a resolve step of the pass's own in place of
 // resolve_kernel and, with `quads`, the active-list instantiation of the scene's kernel over that list of 2x2 blocks.
@@ -294,6 +296,15 @@ int reference_frame_scene(::rttnw_scene* s, const FlatScene*& flat);
 
 void fill_layout(uint32_t w, uint32_t h, uint32_t world, rttnw_tile_layout& L);
 int validate(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p);
+// What the host-output entry points beyond rttnw_render refuse among their own arguments, before validate() (`reserved0`: the call's own reserved
+// field; `counters_why`: appended to the collect_counters refusal).
+inline int refuse_host_output_misuse(const char* prefix, uint32_t reserved0, const rttnw_params* p, const char* counters_why = "") {
+    const std::string call = std::string(prefix) + ": ";
+    if (reserved0 != 0) { set_last_error(call + "reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (p->tile_world != 1) { set_last_error(call + "host-output form needs tile_world == 1"); return RTTNW_ERR_INVALID; }
+    if (p->collect_counters != 0) { set_last_error(call + "collect_counters is not supported" + counters_why); return RTTNW_ERR_UNSUPPORTED; }
+    return 0;
+}
 
 // The launch code of one precision (render_tiles.hpp), instantiated in render_f32.hip / render_f64.hip — and, for double, a second
 // time in render_f64_strict.hip in the namespace rt::ieee_strict (rt_core.hpp: the two builds of the f64 arithmetic).
@@ -339,53 +350,41 @@ template <typename R> CameraRec<R> camera_of(const rttnw_camera_desc* cam) {
     o.lens_radius = R(c.lens_radius); o.open_time = R(c.open_time); o.close_time = R(c.close_time);
     return o;
 }
-
-template <typename R>
-int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
-                   rttnw_stats* stats, bool sync_for_stats = true, bool prepare_only = false, const ListPass* adaptive = nullptr);
-template <typename R>
-int probe_path_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t px, uint32_t row, uint32_t sample,
-                 double* out, uint32_t max_out);
-template <typename R>
-int untile_launch(uint32_t width, uint32_t height, uint32_t world, const void* d_gathered, void* d_linear_rgb, uint8_t* d_rgba8, hipStream_t stream);
-// rttnw_render_adaptive's device half: every pass, then the image (d->linear, d->rgba) and the maps (d->ad_spp, d->ad_stderr) on the device
-template <typename R>
-int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, rttnw_stats* stats);
-extern template int render_adaptive_t<float>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
-extern template int render_adaptive_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
-// rttnw_render_region's device half: selection, list, trace, resolve; the window's image on the device (d->rg_linear, d->rg_rgba)
-template <typename R>
-int render_region_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
-                    const uint8_t* mask, rttnw_stats* stats);
-extern template int render_region_t<float>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*, rttnw_stats*);
-extern template int render_region_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*, rttnw_stats*);
-extern template int render_tiles_t<float>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const ListPass*);
-extern template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const ListPass*);
-extern template int probe_path_t<float>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
-extern template int probe_path_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
-extern template int untile_launch<float>(uint32_t, uint32_t, uint32_t, const void*, void*, uint8_t*, hipStream_t);
-extern template int untile_launch<double>(uint32_t, uint32_t, uint32_t, const void*, void*, uint8_t*, hipStream_t);
 } // namespace RT_ARITH_NS
 
+// The per-precision entry points of render_tiles.hpp, ONE list: X(R, name, parameters).  It makes the declarations, the `extern template` lines of
+// both builds and what a precision's translation unit instantiates (RT_INSTANTIATE_PRECISION): a new entry point is one line here.
+//   render_adaptive_t  rttnw_render_adaptive's device half: every pass, then the image (d->linear, d->rgba) and the maps (d->ad_spp, d->ad_stderr) on the device
+//   render_region_t    rttnw_render_region's device half: selection, list, trace, resolve; the window's image on the device (d->rg_linear, d->rg_rgba)
+#define RT_PRECISION_ENTRY_POINTS(X, R)                                                                                                              \
+    X(R, render_tiles_t, (::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream, \
+                          rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const ListPass* ad))                                          \
+    X(R, probe_path_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t px, uint32_t row, uint32_t sample,           \
+                        double* out, uint32_t max_out))                                                                                              \
+    X(R, untile_launch, (uint32_t width, uint32_t height, uint32_t world, const void* d_gathered, void* d_linear_rgb, uint8_t* d_rgba8,              \
+                         hipStream_t stream))                                                                                                        \
+    X(R, render_adaptive_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, rttnw_stats* stats))    \
+    X(R, render_region_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t x0, uint32_t y0, uint32_t x1,             \
+                           uint32_t y1, const uint8_t* mask, rttnw_stats* stats))
+#define RT_DECLARE_T(R, name, params) template <typename> int name params;
+#define RT_EXTERN_T(R, name, params) extern template int name<R> params;
+#define RT_INSTANTIATE_T(R, name, params) template int name<R> params;
+#define RT_INSTANTIATE_PRECISION(R) RT_PRECISION_ENTRY_POINTS(RT_INSTANTIATE_T, R)
+// ... declared in this unit's build for float and double, and (for the host code) in the IEEE-strict build for double (render_f64_strict.hip)
+#define RT_DECLARE_BUILDS(LIST)                                                                              \
+    inline namespace RT_ARITH_NS { LIST(RT_DECLARE_T, ) LIST(RT_EXTERN_T, float) LIST(RT_EXTERN_T, double) } \
+    RT_DECLARE_STRICT_BUILD(LIST)
 #if !defined(RT_STRICT_F64)
-// what render_api.cpp calls for precision RTTNW_F64_STRICT (defined by render_f64_strict.hip)
-namespace ieee_strict {
-template <typename R>
-int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
-                   rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const ListPass* adaptive = nullptr);
-template <typename R>
-int probe_path_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t px, uint32_t row, uint32_t sample,
-                 double* out, uint32_t max_out);
-extern template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool, const ListPass*);
-extern template int probe_path_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
-template <typename R>
-int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, rttnw_stats* stats);
-extern template int render_adaptive_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);
-template <typename R>
-int render_region_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
-                    const uint8_t* mask, rttnw_stats* stats);
-extern template int render_region_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*, rttnw_stats*);
-} // namespace ieee_strict
+#define RT_DECLARE_STRICT_BUILD(LIST) namespace ieee_strict { LIST(RT_DECLARE_T, ) LIST(RT_EXTERN_T, double) }
+#else
+#define RT_DECLARE_STRICT_BUILD(LIST)
 #endif
+RT_DECLARE_BUILDS(RT_PRECISION_ENTRY_POINTS)
+
+// One precision's launch code, by rttnw_params::precision (RTTNW_F64_STRICT: the ieee_strict build of the f64 arithmetic, rt_core.hpp).
+#define RT_BY_PRECISION(precision, fn, ...)                                       \
+    ((precision) == RTTNW_F32          ? rt::fn<float>(__VA_ARGS__)               \
+     : (precision) == RTTNW_F64_STRICT ? rt::ieee_strict::fn<double>(__VA_ARGS__) \
+                                       : rt::fn<double>(__VA_ARGS__))
 
 } // namespace rt

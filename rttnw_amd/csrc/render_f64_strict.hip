@@ -12,6 +12,7 @@
 
 namespace rt {
 inline namespace RT_ARITH_NS {
+// (RT_INSTANTIATE_PRECISION's entry points, spelled out: this unit has always emitted them — so its kernels — in an order of its own)
 template int render_tiles_t<double>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, bool, bool,
                                     const ListPass*);
 template int untile_launch<double>(uint32_t, uint32_t, uint32_t, const void*, void*, uint8_t*, hipStream_t); // (render_adaptive_t's)

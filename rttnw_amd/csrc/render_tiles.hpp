@@ -51,6 +51,7 @@ inline DeviceCounters* counters_argument(DeviceState* d, const LaunchPlan& pl, c
 // then follows ITS size.
 template <typename R>
 int size_chunk_sums(DeviceState* d, uint64_t sum_pixels, uint32_t total_chunks, uint32_t& per_launch) {
+    const bool pinned = getenv("RTTNW_CHUNK_SUM_BUDGET") != nullptr; // (launch_chunks() then follows the environment, so no other budget is tried or remembered)
     for (uint64_t budget = d->chunk_budget;; budget /= 2) {
         per_launch = launch_chunks(sum_pixels, 3 * sizeof(R), total_chunks, budget);
         const size_t want = std::max<size_t>(size_t(sum_pixels) * std::min(per_launch, total_chunks), 1) * 3 * sizeof(R);
@@ -59,20 +60,27 @@ int size_chunk_sums(DeviceState* d, uint64_t sum_pixels, uint32_t total_chunks, 
         const hipError_t e = bigger.grow(want);
         if (e == hipSuccess) {
             d->partial = bigger;
-            if (!getenv("RTTNW_CHUNK_SUM_BUDGET")) d->chunk_budget = budget;
+            if (!pinned) d->chunk_budget = budget;
             break;
         }
         (void)hipGetLastError(); // clear the sticky out-of-memory
         const size_t one_group = size_t(sum_pixels) * std::min<uint32_t>(16u, total_chunks) * 3 * sizeof(R);
-        // (not under RTTNW_CHUNK_SUM_BUDGET: launch_chunks() would size the launches by the environment's budget again, not by the buffer in hand)
-        if (d->partial.p && d->partial.n >= one_group && !getenv("RTTNW_CHUNK_SUM_BUDGET")) { // no larger buffer to be had: split the render by the one in hand
+        // (not when pinned: launch_chunks() would size the launches by the environment's budget again, not by the buffer in hand)
+        if (d->partial.p && d->partial.n >= one_group && !pinned) { // no larger buffer to be had: split the render by the one in hand
             per_launch = launch_chunks(sum_pixels, 3 * sizeof(R), total_chunks, d->partial.n);
-            if (!getenv("RTTNW_CHUNK_SUM_BUDGET")) d->chunk_budget = std::max<uint64_t>(d->partial.n, 1ull << 30);
+            d->chunk_budget = std::max<uint64_t>(d->partial.n, 1ull << 30);
             break;
         }
-        if (budget <= (1ull << 30) || getenv("RTTNW_CHUNK_SUM_BUDGET")) { set_last_error(std::string("render: no memory for the chunk sums: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
+        if (budget <= (1ull << 30) || pinned) { set_last_error(std::string("render: no memory for the chunk sums: ") + hipGetErrorString(e)); return RTTNW_ERR_HIP; }
     }
     return 0;
+}
+
+// The launch plan of a render of `flat` in this precision (launch_plan.hpp plan_launch, which reads no environment itself) under the experiment
+// overrides: RTTNW_KERNEL=plain|plainglobal|wave names the form, RTTNW_WAVE_BLOCK=<threads> the decoupled LEAN flavour's block.
+template <typename R> LaunchPlan plan_for(const FlatScene& flat, bool count, bool listed) {
+    const char* wave_block = getenv("RTTNW_WAVE_BLOCK");
+    return plan_launch(flat, sizeof(R), count, listed, kernel_form_named(getenv("RTTNW_KERNEL")), wave_block ? atoi(wave_block) : 0);
 }
 
 // One trace launch over the rc.n_jobs jobs of a pass: the workspace its grid needs, then the plan's kernel (prepare_only: the workspace alone).
@@ -191,9 +199,7 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
     uint32_t per_launch = 0;
     if (int g = size_chunk_sums<R>(d, listed ? uint64_t(ad->n_quads) * 4 : uint64_t(rc.my_tiles) * 64, total_chunks, per_launch)) return g;
     const CameraRec<R> camr = camera_of<R>(cam);
-    // RTTNW_KERNEL=plain|plainglobal|wave overrides the plan's choice of form, RTTNW_WAVE_BLOCK=<threads> the decoupled LEAN flavour's block (experiments only)
-    const char* wave_block = getenv("RTTNW_WAVE_BLOCK");
-    const LaunchPlan pl = plan_launch(*flat, sizeof(R), count, listed, kernel_form_named(getenv("RTTNW_KERNEL")), wave_block ? atoi(wave_block) : 0);
+    const LaunchPlan pl = plan_for<R>(*flat, count, listed);
     rc.lds_nodes = pl.lds_nodes;
     for (int k = 0; k < 6; ++k) rc.lds_recs[k] = pl.lds_recs[k];
     if (!prepare_only) HIP_TRY(hipMemsetAsync(d->job_counter.p, 0, sizeof(unsigned long long) + sizeof(DeviceCounters), stream));
@@ -253,6 +259,28 @@ int untile_launch(uint32_t width, uint32_t height, uint32_t world, const void* d
     return RTTNW_OK;
 }
 
+// The list of the 2x2 blocks, of n_blocks, that hold a marked pixel (`marks`: a byte per packed pixel), built on the device in d->list_quads:
+// per wave of blocks the counts, their scan, then the compaction (trace_kernels.hpp; d->list_scan holds the waves' counts of blocks and of pixels,
+// the waves' bases and the two totals).  One 8-byte copy gives the host the list's length and the number of marked pixels.
+template <typename R>
+int build_quad_list(DeviceState* d, const uint8_t* marks, uint32_t n_blocks, hipStream_t stream, uint32_t& n_listed, uint32_t& n_marked) {
+    const uint32_t n_waves = (n_blocks + 63u) / 64u, grid = (n_blocks + 255u) / 256u;
+    HIP_TRY(d->list_quads.grow(size_t(n_blocks) * sizeof(uint32_t)));
+    HIP_TRY(d->list_scan.grow((size_t(n_waves) * 3 + 2) * sizeof(uint32_t)));
+    uint32_t* wave_counts = (uint32_t*)d->list_scan.p;
+    uint32_t* wave_base = wave_counts + 2 * size_t(n_waves);
+    uint32_t* totals = wave_base + n_waves;
+    hipLaunchKernelGGL(quad_count_kernel<R>, dim3(grid), dim3(256), 0, stream, marks, n_blocks, wave_counts);
+    hipLaunchKernelGGL(quad_scan_kernel<R>, dim3(1), dim3(QUAD_SCAN_BLOCK), 0, stream, (const uint32_t*)wave_counts, wave_base, n_waves, totals);
+    hipLaunchKernelGGL(quad_list_kernel<R>, dim3(grid), dim3(256), 0, stream, marks, n_blocks, (const uint32_t*)wave_base, (uint32_t*)d->list_quads.p);
+    HIP_TRY(hipGetLastError());
+    uint32_t count[2] = {0, 0}; // listed blocks, marked pixels
+    HIP_TRY(hipMemcpy(count, totals, sizeof(count), hipMemcpyDeviceToHost));
+    n_listed = count[0];
+    n_marked = count[1];
+    return 0;
+}
+
 // rttnw_render_adaptive (include/rttnw_hip.h has the contract, DESIGN.md "Adaptive sampling" the why).  Pass k traces samples
 // [sample_begin + kB, sample_begin + (k+1)B) of every active pixel with render_tiles_t's own kernel choice, chunk schedule and launch split:
 // pass 0 over every pixel, in the plain render's job numbering; pass k > 0 over the list of 2x2 blocks that hold an active pixel, built on the
@@ -264,20 +292,14 @@ int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
     rttnw_tile_layout L;
     fill_layout(p->width, p->height, 1, L);
     const size_t npx = size_t(p->width) * p->height;
-    const uint32_t n_blocks = L.n_tiles * 16u, n_waves = (n_blocks + 63u) / 64u;
+    const uint32_t n_blocks = L.n_tiles * 16u;
     HIP_TRY(d->packed.grow(size_t(L.pixels_per_rank) * 4 * sizeof(R)));
     HIP_TRY(d->linear.grow(npx * 3 * sizeof(R)));
     HIP_TRY(d->rgba.grow(npx * 4));
     HIP_TRY(d->ad_state.grow(size_t(L.pixels_per_rank) * sizeof(AdaptivePixel)));
     HIP_TRY(d->ad_active.grow(L.pixels_per_rank));
-    HIP_TRY(d->ad_quads.grow(size_t(n_blocks) * sizeof(uint32_t)));
-    HIP_TRY(d->ad_scan.grow((size_t(n_waves) * 3 + 2) * sizeof(uint32_t)));
     HIP_TRY(d->ad_spp.grow(npx * sizeof(uint32_t)));
     HIP_TRY(d->ad_stderr.grow(npx * 3 * sizeof(double)));
-    uint32_t* wave_counts = (uint32_t*)d->ad_scan.p;
-    uint32_t* wave_base = wave_counts + 2 * size_t(n_waves);
-    uint32_t* totals = wave_base + n_waves;
-    const uint32_t* quads = (const uint32_t*)d->ad_quads.p;
 
     ListPass ad;
     ad.state = (AdaptivePixel*)d->ad_state.p;
@@ -293,19 +315,12 @@ int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
     for (uint32_t k = 0; k < n_passes; ++k) {
         pass.sample_begin = p->sample_begin + k * a->pass_spp;
         if (k > 0) {
-            const uint32_t grid = (n_blocks + 255u) / 256u;
-            hipLaunchKernelGGL(quad_count_kernel<R>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)ad.active, n_blocks, wave_counts);
-            hipLaunchKernelGGL(quad_scan_kernel<R>, dim3(1), dim3(QUAD_SCAN_BLOCK), 0, stream, (const uint32_t*)wave_counts, wave_base, n_waves, totals);
-            hipLaunchKernelGGL(quad_list_kernel<R>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)ad.active, n_blocks, (const uint32_t*)wave_base,
-                               (uint32_t*)quads);
-            HIP_TRY(hipGetLastError());
-            uint32_t count[2] = {0, 0}; // listed blocks, active pixels
-            HIP_TRY(hipMemcpy(count, totals, sizeof(count), hipMemcpyDeviceToHost));
-            if (count[0] == 0) break; // every pixel is done
-            ad.quads = quads;
-            ad.n_quads = count[0];
+            uint32_t n_active = 0;
+            if (int rc = build_quad_list<R>(d, ad.active, n_blocks, stream, ad.n_quads, n_active)) return rc;
+            if (ad.n_quads == 0) break; // every pixel is done
+            ad.quads = (const uint32_t*)d->list_quads.p;
             ad.first = false;
-            samples += uint64_t(count[1]) * a->pass_spp;
+            samples += uint64_t(n_active) * a->pass_spp;
         }
         // (pass 0 fills `stats` as a plain render does — kernel form, scene sizes — and starts its clock)
         if (int rc = render_tiles_t<R>(s, d, cam, &pass, d->packed.p, stream, k == 0 ? stats : nullptr, false, false, &ad)) return rc;
@@ -342,47 +357,32 @@ int render_region_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_
     fill_layout(p->width, p->height, 1, L);
     const RenderConsts rc = base_consts(p, *flat, L);
     const size_t wpx = size_t(x1 - x0) * (y1 - y0);
-    const uint32_t n_blocks = L.n_tiles * 16u, n_waves = (n_blocks + 63u) / 64u;
     HIP_TRY(d->rg_select.grow(L.pixels_per_rank));
-    HIP_TRY(d->ad_quads.grow(size_t(n_blocks) * sizeof(uint32_t)));
-    HIP_TRY(d->ad_scan.grow((size_t(n_waves) * 3 + 2) * sizeof(uint32_t)));
     HIP_TRY(d->rg_linear.grow(wpx * 3 * sizeof(R)));
     HIP_TRY(d->rg_rgba.grow(wpx * 4));
     if (mask) HIP_TRY(d->rg_mask.grow(wpx));
-    uint32_t* wave_counts = (uint32_t*)d->ad_scan.p;
-    uint32_t* wave_base = wave_counts + 2 * size_t(n_waves);
-    uint32_t* totals = wave_base + n_waves;
-    uint32_t* quads = (uint32_t*)d->ad_quads.p;
     const hipStream_t stream = nullptr;
     if (stats) HIP_TRY(hipEventRecord(d->ev0.get(), stream));
     if (mask) HIP_TRY(hipMemcpy(d->rg_mask.p, mask, wpx, hipMemcpyHostToDevice)); // uploaded once, window-sized
     HIP_TRY(hipMemsetAsync(d->rg_linear.p, 0, wpx * 3 * sizeof(R), stream)); // what an unselected pixel of the window keeps
     HIP_TRY(hipMemsetAsync(d->rg_rgba.p, 0, wpx * 4, stream));
-    const uint32_t grid = (n_blocks + 255u) / 256u;
     hipLaunchKernelGGL(region_select_kernel<R>, dim3((L.pixels_per_rank + 255u) / 256u), dim3(256), 0, stream, mask ? (const uint8_t*)d->rg_mask.p : nullptr,
                        d->rg_select.p, rc, L.pixels_per_rank, x0, y0, x1, y1);
-    hipLaunchKernelGGL(quad_count_kernel<R>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)d->rg_select.p, n_blocks, wave_counts);
-    hipLaunchKernelGGL(quad_scan_kernel<R>, dim3(1), dim3(QUAD_SCAN_BLOCK), 0, stream, (const uint32_t*)wave_counts, wave_base, n_waves, totals);
-    hipLaunchKernelGGL(quad_list_kernel<R>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)d->rg_select.p, n_blocks, (const uint32_t*)wave_base, quads);
-    HIP_TRY(hipGetLastError());
-    uint32_t count[2] = {0, 0}; // listed blocks, selected pixels
-    HIP_TRY(hipMemcpy(count, totals, sizeof(count), hipMemcpyDeviceToHost));
-    if (count[0] != 0) {
-        HIP_TRY(d->rg_sums.grow(size_t(count[0]) * 4 * 4 * sizeof(R)));
-        ListPass list;
-        list.quads = quads;
-        list.n_quads = count[0];
+    ListPass list;
+    uint32_t n_selected = 0;
+    if (int g = build_quad_list<R>(d, d->rg_select.p, L.n_tiles * 16u, stream, list.n_quads, n_selected)) return g;
+    if (list.n_quads != 0) {
+        HIP_TRY(d->rg_sums.grow(size_t(list.n_quads) * 4 * 4 * sizeof(R)));
+        list.quads = (const uint32_t*)d->list_quads.p;
         list.clock_started = true;
         // (fills `stats` as a plain render does: kernel form, scene sizes)
         if (int g = render_tiles_t<R>(s, d, cam, p, d->rg_sums.p, stream, stats, false, false, &list)) return g;
-        hipLaunchKernelGGL(region_output_kernel<R>, dim3((count[0] * 4u + 255u) / 256u), dim3(256), 0, stream, (const R*)d->rg_sums.p, (const uint32_t*)quads,
-                           rc, count[0] * 4u, x0, y0, x1, y1, (R*)d->rg_linear.p, d->rg_rgba.p);
+        hipLaunchKernelGGL(region_output_kernel<R>, dim3((list.n_quads * 4u + 255u) / 256u), dim3(256), 0, stream, (const R*)d->rg_sums.p, list.quads, rc,
+                           list.n_quads * 4u, x0, y0, x1, y1, (R*)d->rg_linear.p, d->rg_rgba.p);
         HIP_TRY(hipGetLastError());
     } else if (stats) {
         // nothing selected: no trace launch; the stats say what a render of this scene would have run
-        const char* wave_block = getenv("RTTNW_WAVE_BLOCK");
-        const LaunchPlan pl = plan_launch(*flat, sizeof(R), false, true, kernel_form_named(getenv("RTTNW_KERNEL")), wave_block ? atoi(wave_block) : 0);
-        if (int g = fill_stats<R>(d, *ds, *flat, pl, rc, false, stream, stats)) return g;
+        if (int g = fill_stats<R>(d, *ds, *flat, plan_for<R>(*flat, false, true), rc, false, stream, stats)) return g;
     }
     if (stats) HIP_TRY(hipEventRecord(d->ev1.get(), stream));
     HIP_TRY(hipDeviceSynchronize());
@@ -390,20 +390,10 @@ int render_region_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, d->ev0.get(), d->ev1.get()));
         stats->kernel_ms = ms;
-        stats->samples = uint64_t(count[1]) * p->spp;
+        stats->samples = uint64_t(n_selected) * p->spp;
     }
     return RTTNW_OK;
 }
-
-// what a precision's translation unit instantiates
-#define RT_INSTANTIATE_PRECISION(R)                                                                                                             \
-    template int render_tiles_t<R>(::rttnw_scene*, DeviceState*, const rttnw_camera_desc*, const rttnw_params*, void*, hipStream_t, rttnw_stats*, \
-                                   bool, bool, const ListPass*);                                                                            \
-    template int probe_path_t<R>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t); \
-    template int untile_launch<R>(uint32_t, uint32_t, uint32_t, const void*, void*, uint8_t*, hipStream_t);                                       \
-    template int render_adaptive_t<R>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, const rttnw_adaptive*, rttnw_stats*);           \
-    template int render_region_t<R>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*, \
-                                    rttnw_stats*);
 
 } // namespace RT_ARITH_NS
 } // namespace rt

@@ -862,6 +862,41 @@ def test_render_multi_gather_transports_on_one_gpu(gpu, tmp_path, transport):
         assert "bits=[768]" in r.stdout, r.stdout[-500:]
 
 
+_RCCL_REMEMBERED_SCRIPT = r"""
+import sys
+sys.path.insert(0, %(root)r); sys.path.insert(0, %(root)r + "/tests")
+import numpy as np
+from rttnw_amd import abi, library, render, scene as S
+gpu, scenes = library.product(), library.scenes()
+sc, setup = S.build(gpu, scenes, "final_scene", S.load_earth())
+cam, p = S.params_for(setup, 104, 72, 6, precision=abi.F64, spp_chunk=3, seed=8)
+one, rgba, _ = render.render_host(sc, cam, p)
+for call in range(2):
+    lin, rg, st = render.render_multi(sc, cam, p, [0] * 3)
+    assert np.array_equal(lin, one) and np.array_equal(rg, rgba), call
+    assert int(st[0].reserved) & 0x300 == 0x300, (call, hex(st[0].reserved))
+print("REMEMBERED_LEG_OK")
+"""
+
+
+def test_render_multi_remembers_a_failed_rccl_setup(gpu, tmp_path):
+    """A failed RCCL set-up over a device list is remembered until rttnw_shutdown(): of two rttnw_render_multi calls of 3 ranks in one process
+    under RTTNW_MULTI_FAIL_RCCL=1, both gather through peer copies (two RTTNW_DEBUG_MULTI lines), both report bits 8 and 9 and both images equal
+    rttnw_render's bit for bit — but the "RCCL gather unavailable" line is printed ONCE.  (Before the set-up was remembered, every call tried it
+    again and printed the line again: twice here.)  A child process with a time limit, as the transports' test above."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = tmp_path / "remembered_leg.py"
+    script.write_text(_RCCL_REMEMBERED_SCRIPT % {"root": root})
+    env = dict(os.environ, RTTNW_MULTI_FORCE_TRANSPORT="1", RTTNW_MULTI_FAIL_RCCL="1", RTTNW_DEBUG_MULTI="1")
+    r = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "REMEMBERED_LEG_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    assert r.stderr.count("RCCL gather unavailable") == 1, r.stderr[-4000:]
+    assert r.stderr.count("through hipMemcpyPeerAsync") == 2, r.stderr[-4000:]
+
+
 def test_bench_line_through_torch_distributed_with_one_rank(gpu):
     """bench.py as the driver launches it for N > 1 — `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` — with
     N = 1 and RTTNW_BENCH_FORCE_DIST=1: RCCL process group over one rank, barrier-bracketed timing, max-over-ranks all-reduce,

@@ -113,6 +113,20 @@ def test_a_mask_selects_pixels(scenes, name, precision, kernel, monkeypatch):
     assert (l1 == 0.0).all() and (r1 == 0).all() and st1.samples == 0
 
 
+@pytest.mark.parametrize("precision", [abi.F64, abi.F32])
+def test_an_empty_selection_reports_the_render_it_skipped(scenes, precision, monkeypatch):
+    """A mask that selects nothing: no trace launch, so the stats come from a launch plan made for them alone — the kernel form (bits 0-5 of
+    `reserved`) and the scene sizes must be those of a region render of the same scene and precision that did trace."""
+    _kernel(monkeypatch, None)
+    win = (5, 3, 23, 18)
+    sc, cam, p = _params(scenes, "cornell_box", precision, spp=4)
+    _, _, traced = render.render_region(sc, cam, p, *win)
+    l, r, st = render.render_region(sc, cam, p, *win, mask=np.zeros((15, 18), dtype=bool))
+    assert (l == 0.0).all() and (r == 0).all() and st.samples == 0   # (alpha 0 as well)
+    assert traced.samples == 15 * 18 * 4
+    assert st.reserved & 0x3f == traced.reserved & 0x3f and st.n_nodes == traced.n_nodes > 0 and st.n_prims == traced.n_prims > 0
+
+
 @pytest.fixture(scope="module")
 def oracle_cornell(gpu, oracle, scenes_lib):
     """cornell_box 200x200 spp 50, default spp_chunk, RTTNW_F64_STRICT: the configuration test_config1_cornell_200_spp50_whole_frame holds
