@@ -9,6 +9,7 @@
 #include "rt_core.hpp"
 #include "adaptive.hpp"
 #include "scene_handle.hpp"
+#include "scene_narrow.hpp"
 #include "device_mem.hpp"
 
 #include <hip/hip_runtime.h>
@@ -159,14 +160,9 @@ template <typename R> struct DeviceScene {
         if (int rc = interleave_build_device(a, err)) { set_last_error(err); return rc; }
         // the other kinds' records keep their places; their material references move behind the sparse block
         std::vector<RectRec<R>> rq;
-        for (auto& r : f.rects) rq.push_back({R(r.a0), R(r.a1), R(r.b0), R(r.b1), R(r.k), r.plane, r.mat + int32_t(n_sparse), r.seq});
+        for (auto& r : f.rects) { rq.push_back(narrow<R>(r)); rq.back().mat += int32_t(n_sparse); }
         std::vector<BoxRec<R>> bq;
-        for (auto& b : f.boxes) {
-            BoxRec<R> o{};
-            for (int k = 0; k < 3; ++k) { o.mn[k] = R(b.mn[k]); o.mx[k] = R(b.mx[k]); }
-            o.mat = b.mat + int32_t(n_sparse); o.seq = b.seq;
-            bq.push_back(o);
-        }
+        for (auto& b : f.boxes) { bq.push_back(narrow<R>(b)); bq.back().mat += int32_t(n_sparse); }
         DevBuf<RectRec<R>> rects_buf;
         DevBuf<BoxRec<R>> boxes_buf;
         HIP_TRY(rects_buf.upload(rq));
@@ -188,51 +184,15 @@ template <typename R> struct DeviceScene {
     }
 
     int upload(const FlatScene& f) {
-        std::vector<SphereRec<R>> sp;
-        for (auto& s : f.spheres) sp.push_back({R(s.cx), R(s.cy), R(s.cz), R(s.r)});
-        std::vector<MovingSphereRec<R>> mv;
-        for (auto& m : f.moving) {
-            MovingSphereRec<R> o{};
-            for (int k = 0; k < 3; ++k) { o.c0[k] = R(m.c0[k]); o.c1[k] = R(m.c1[k]); }
-            o.r = R(m.r); o.t0 = R(m.t0); o.t1 = R(m.t1); o.mat = m.mat; o.seq = m.seq;
-            mv.push_back(o);
-        }
-        std::vector<RectRec<R>> rc_;
-        for (auto& r : f.rects) rc_.push_back({R(r.a0), R(r.a1), R(r.b0), R(r.b1), R(r.k), r.plane, r.mat, r.seq});
-        std::vector<BoxRec<R>> bx;
-        for (auto& b : f.boxes) {
-            BoxRec<R> o{};
-            for (int k = 0; k < 3; ++k) { o.mn[k] = R(b.mn[k]); o.mx[k] = R(b.mx[k]); }
-            o.mat = b.mat; o.seq = b.seq;
-            bx.push_back(o);
-        }
-        std::vector<InstanceRec<R>> in;
-        for (auto& i : f.insts) {
-            InstanceRec<R> o{};
-            o.n_ops = i.n_ops; o.root = i.root; o.single_leaf = i.single_leaf;
-            for (int k = 0; k < MAX_INSTANCE_OPS; ++k) {
-                o.ops[k].type = i.ops[k].type;
-                for (int c = 0; c < 3; ++c) o.ops[k].v[c] = R(i.ops[k].v[c]);
-            }
-            in.push_back(o);
-        }
-        std::vector<MediumRec<R>> md;
-        for (auto& m : f.media) md.push_back({m.b_first, m.b_count, m.inst, m.n_outer, m.mat, m.ref0, R(m.neg_inv_density)});
-        std::vector<MaterialRec<R>> mt;
-        for (auto& m : f.mats) mt.push_back({m.type, m.tex, {R(m.albedo[0]), R(m.albedo[1]), R(m.albedo[2])}, R(m.param)});
-        std::vector<TextureRec<R>> tx;
-        for (auto& t : f.texs) tx.push_back({t.type, t.a, t.b, 0, {R(t.color[0]), R(t.color[1]), R(t.color[2])}, R(t.scale)});
-        std::vector<R> pv;
-        for (double v : f.perlin_vec) pv.push_back(R(v));
-
+        const NarrowScene<R> n(f); // the records in this precision (scene_narrow.hpp)
         DeviceScene s; // taken over whole once every upload has succeeded
         if (int rc = upload_nodes(f, s.nodes)) return rc;
-        HIP_TRY(s.spheres.upload(sp));
+        HIP_TRY(s.spheres.upload(n.spheres));
         if (!f.sphere_mat_is_index) HIP_TRY(s.sphere_mat.upload(f.sphere_mat));
-        HIP_TRY(s.sphere_seq.upload(f.sphere_seq)); HIP_TRY(s.moving.upload(mv)); HIP_TRY(s.rects.upload(rc_)); HIP_TRY(s.boxes.upload(bx));
-        HIP_TRY(s.insts.upload(in)); HIP_TRY(s.media.upload(md)); HIP_TRY(s.medium_refs.upload(f.medium_refs)); HIP_TRY(s.mats.upload(mt));
-        HIP_TRY(s.texs.upload(tx)); HIP_TRY(s.images.upload(f.images)); HIP_TRY(s.texels.upload(f.texels));
-        HIP_TRY(s.perlin_vec.upload(pv)); HIP_TRY(s.perlin_perm.upload(f.perlin_perm));
+        HIP_TRY(s.sphere_seq.upload(f.sphere_seq)); HIP_TRY(s.moving.upload(n.moving)); HIP_TRY(s.rects.upload(n.rects)); HIP_TRY(s.boxes.upload(n.boxes));
+        HIP_TRY(s.insts.upload(n.insts)); HIP_TRY(s.media.upload(n.media)); HIP_TRY(s.medium_refs.upload(f.medium_refs)); HIP_TRY(s.mats.upload(n.mats));
+        HIP_TRY(s.texs.upload(n.texs)); HIP_TRY(s.images.upload(f.images)); HIP_TRY(s.texels.upload(f.texels));
+        HIP_TRY(s.perlin_vec.upload(n.perlin_vec)); HIP_TRY(s.perlin_perm.upload(f.perlin_perm));
         SceneView<R>& v = s.view;
         v.nodes = s.nodes.p; v.spheres = s.spheres.p; v.sphere_mat = f.sphere_mat_is_index ? nullptr : s.sphere_mat.p; v.sphere_seq = s.sphere_seq.p;
         v.moving = s.moving.p; v.rects = s.rects.p; v.boxes = s.boxes.p; v.insts = s.insts.p; v.media = s.media.p; v.medium_refs = s.medium_refs.p;
@@ -240,8 +200,8 @@ template <typename R> struct DeviceScene {
         v.perlin_vec = s.perlin_vec.p; v.perlin_perm = s.perlin_perm.p;
         v.top_root = f.top_root;
         v.n_media = int32_t(f.media.size());
-        s.bytes = size_t(f.total_nodes4()) * sizeof(Bvh4Node) + sp.size() * sizeof(SphereRec<R>) + mv.size() * sizeof(MovingSphereRec<R>) +
-                  rc_.size() * sizeof(RectRec<R>) + bx.size() * sizeof(BoxRec<R>) + in.size() * sizeof(InstanceRec<R>);
+        s.bytes = size_t(f.total_nodes4()) * sizeof(Bvh4Node) + n.spheres.size() * sizeof(SphereRec<R>) + n.moving.size() * sizeof(MovingSphereRec<R>) +
+                  n.rects.size() * sizeof(RectRec<R>) + n.boxes.size() * sizeof(BoxRec<R>) + n.insts.size() * sizeof(InstanceRec<R>);
         s.ready = true;
         *this = s;
         return 0;
@@ -337,18 +297,6 @@ inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, co
     rc.inv_width = 1.0 / double(p->width); rc.inv_height = 1.0 / double(p->height);
     rc.div_tiles_x = make_fastdiv(std::max<uint32_t>(1u, rc.tiles_x));
     return rc;
-}
-template <typename R> CameraRec<R> camera_of(const rttnw_camera_desc* cam) {
-    CameraRec<double> c;
-    make_camera(cam->lookfrom, cam->lookat, cam->view_up, cam->vertical_fov, cam->aspect_ratio, cam->aperture, cam->focus_distance, cam->open_time,
-                cam->close_time, c);
-    CameraRec<R> o;
-    for (int k = 0; k < 3; ++k) {
-        o.origin[k] = R(c.origin[k]); o.lower_left_corner[k] = R(c.lower_left_corner[k]);
-        o.horizontal[k] = R(c.horizontal[k]); o.vertical[k] = R(c.vertical[k]); o.u[k] = R(c.u[k]); o.v[k] = R(c.v[k]);
-    }
-    o.lens_radius = R(c.lens_radius); o.open_time = R(c.open_time); o.close_time = R(c.close_time);
-    return o;
 }
 } // namespace RT_ARITH_NS
 

@@ -1681,6 +1681,41 @@ RT_HD bool path_step(PathState<R>& ps, const SceneView<R>& sc, const RenderConst
     return path_shade(ps, sc, rc, background, t_min, found, closest, best, cnt);
 }
 
+// Debug probe (include/rttnw_hip.h rttnw_debug_probe_path): one sample's path, bounce by bounce.  Per bounce PROBE_STRIDE doubles into `out`: the hit
+// record (t, p, normal, material, u, v, front_face), the ray it was found with, the emitted red and the attenuation's red (-1: the path ends
+// here); at most max_out bounces.  Then the same sample again through path_step(), the walk and shade steps the trace kernels run: its radiance
+// (background black) and bounce count in the four doubles behind the last possible record.  Returns the number of records written.
+constexpr int PROBE_STRIDE = 20;
+template <typename R, typename Stack, typename Cnt>
+RT_HD uint32_t probe_path(const SceneView<R>& sc, const CameraRec<R>& cam, const RenderConsts& rc, R t_min, uint32_t px, uint32_t row, uint32_t sample,
+                          double* out, uint32_t max_out, Stack& stack, Cnt& cnt) {
+    PathState<R> ps;
+    path_begin(ps, cam, rc, px, row, sample);
+    uint32_t n = 0;
+    while (n < max_out) {
+        HitRecord<R> rec;
+        const Ray<R> ray = ps.ray;
+        if (!world_hit(sc, ps.ray, t_min, ps.key, ps.bounce, rc.quirks, rec, stack, cnt)) break;
+        double* o = out + size_t(n) * PROBE_STRIDE;
+        o[0] = rec.t; o[1] = rec.p.x; o[2] = rec.p.y; o[3] = rec.p.z;
+        o[4] = rec.normal.x; o[5] = rec.normal.y; o[6] = rec.normal.z; o[7] = double(rec.mat);
+        o[8] = rec.u; o[9] = rec.v; o[10] = rec.front_face ? 1.0 : 0.0;
+        o[11] = ray.o.x; o[12] = ray.o.y; o[13] = ray.o.z; o[14] = ray.d.x; o[15] = ray.d.y; o[16] = ray.d.z; o[17] = ray.time;
+        ++n;
+        V3<R> att, em;
+        const bool cont = shade(sc, rec, ps.key, ps.bounce, ps.ray, att, em, cnt);
+        o[18] = em.x; o[19] = cont ? att.x : -1.0;
+        if (!cont) break;
+        ps.bounce += 1;
+        if (ps.bounce >= rc.max_depth) break;
+    }
+    path_begin(ps, cam, rc, px, row, sample);
+    while (path_step(ps, sc, rc, V3<R>(), t_min, stack, cnt)) {}
+    double* tail = out + size_t(max_out) * PROBE_STRIDE;
+    tail[0] = ps.radiance.x; tail[1] = ps.radiance.y; tail[2] = ps.radiance.z; tail[3] = double(ps.bounce);
+    return n;
+}
+
 // Gamma + quantise — main.rs:219-225 (`as u8` saturates, NaN -> 0)
 RT_HD uint8_t quantise(double mean) {
     double x = sqrt(mean);

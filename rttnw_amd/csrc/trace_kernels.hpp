@@ -755,9 +755,7 @@ __global__ void adaptive_output_kernel(R* __restrict__ packed, const AdaptivePix
     for (int ch = 0; ch < 3; ++ch) stderr_map[o * 3ull + ch] = adaptive_stderr(a, ch);
 }
 
-// Debug probe: one lane walks one sample's path and dumps every hit record (t, p, normal, material, u, v,
-// front_face) plus the ray it was found with — the device half of the per-bounce CPU-vs-GPU vector tests.
-constexpr int PROBE_STRIDE = 20;
+// Debug probe: lane 0 walks one sample's path (rt_core.hpp probe_path) — the device half of the per-bounce CPU-vs-GPU vector tests.
 template <typename R>
 __global__ void probe_path_kernel(SceneView<R> sc, CameraRec<R> cam, RenderConsts rc, R t_min, uint32_t px, uint32_t row,
                                   uint32_t sample, double* __restrict__ out, uint32_t max_out, int32_t* __restrict__ n_out,
@@ -766,32 +764,7 @@ __global__ void probe_path_kernel(SceneView<R> sc, CameraRec<R> cam, RenderConst
     if (threadIdx.x != 0) return;
     LdsStack<64> stack{(LdsIntPtr)lds_stack, (GlobalIntPtr)spill, 1u};
     NoCounters cnt;
-    PathState<R> ps;
-    path_begin(ps, cam, rc, px, row, sample);
-    uint32_t n = 0;
-    while (n < max_out) {
-        HitRecord<R> rec;
-        const Ray<R> ray = ps.ray;
-        if (!world_hit(sc, ps.ray, t_min, ps.key, ps.bounce, rc.quirks, rec, stack, cnt)) break;
-        double* o = out + size_t(n) * PROBE_STRIDE;
-        o[0] = rec.t; o[1] = rec.p.x; o[2] = rec.p.y; o[3] = rec.p.z;
-        o[4] = rec.normal.x; o[5] = rec.normal.y; o[6] = rec.normal.z; o[7] = double(rec.mat);
-        o[8] = rec.u; o[9] = rec.v; o[10] = rec.front_face ? 1.0 : 0.0;
-        o[11] = ray.o.x; o[12] = ray.o.y; o[13] = ray.o.z; o[14] = ray.d.x; o[15] = ray.d.y; o[16] = ray.d.z; o[17] = ray.time;
-        ++n;
-        V3<R> att, em;
-        const bool cont = shade(sc, rec, ps.key, ps.bounce, ps.ray, att, em, cnt);
-        o[18] = em.x; o[19] = cont ? att.x : -1.0;
-        if (!cont) break;
-        ps.bounce += 1;
-        if (ps.bounce >= rc.max_depth) break;
-    }
-    *n_out = int32_t(n);
-    // the same sample again through path_step(), the same walk and shade steps the trace kernels run: radiance after `out`
-    path_begin(ps, cam, rc, px, row, sample);
-    while (path_step(ps, sc, rc, V3<R>(), t_min, stack, cnt)) {}
-    double* tail = out + size_t(max_out) * PROBE_STRIDE;
-    tail[0] = ps.radiance.x; tail[1] = ps.radiance.y; tail[2] = ps.radiance.z; tail[3] = double(ps.bounce);
+    *n_out = int32_t(probe_path(sc, cam, rc, t_min, px, row, sample, out, max_out, stack, cnt));
 }
 
 } // namespace RT_ARITH_NS

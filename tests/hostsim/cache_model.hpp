@@ -79,20 +79,12 @@ struct Params {
 template <typename R>
 static void run(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const Params& P, const uint32_t* node_perm,
                 const uint32_t* sphere_perm, uint64_t* out) {
-    HostScene<R> hs(s->flat);
+    HostSetup<R> su(s, cam, p);
+    su.plan_whole_frame(p);
+    HostScene<R>& hs = su.hs;
     hs.make_quant4(s->flat);
-    CameraRec<double> cam64;
-    make_camera(cam->lookfrom, cam->lookat, cam->view_up, cam->vertical_fov, cam->aspect_ratio, cam->aperture, cam->focus_distance,
-                cam->open_time, cam->close_time, cam64);
-    CameraRec<R> camr = narrow_camera<R>(cam64);
-    RenderConsts rc{};
-    rc.width = p->width; rc.height = p->height; rc.spp = p->spp; rc.max_depth = p->max_depth; rc.quirks = p->quirks; rc.seed = p->seed;
-    rc.sample_begin = p->sample_begin;
-    plan_chunks(rc, p->spp, p->spp_chunk);
-    rc.tiles_x = (rc.width + 7) / 8; rc.tiles_y = (rc.height + 7) / 8; rc.n_tiles = rc.tiles_x * rc.tiles_y;
-    rc.tile_rank = 0; rc.tile_world = 1; rc.my_tiles = rc.n_tiles;
-    rc.div_tiles_x = make_fastdiv(std::max<uint32_t>(1u, rc.tiles_x));
-    plan_jobs(rc);
+    const CameraRec<R>& camr = su.camr;
+    const RenderConsts& rc = su.rc;
     const V3<R> background(R(p->background[0]), R(p->background[1]), R(p->background[2]));
     const R t_min = R(p->t_min);
     NoCounters cnt;

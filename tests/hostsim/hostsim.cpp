@@ -6,6 +6,7 @@
 #include "../../rttnw_amd/csrc/rt_core.hpp"
 #include "../../rttnw_amd/csrc/bvh_quant.hpp"
 #include "../../rttnw_amd/csrc/scene_handle.hpp"
+#include "../../rttnw_amd/csrc/scene_narrow.hpp"
 #include "../../rttnw_amd/csrc/launch_plan.hpp"
 
 #include <algorithm>
@@ -76,16 +77,7 @@ struct HostStack4Q : HostStack { // the f64 decoupled kernel's: walks the quanti
     template <typename R> void fetch4q(const SceneView<R>& sc, int32_t i, uint32_t* w) const { std::memcpy(w, &sc.nodes4q[i], 64); }
 };
 
-template <typename R> struct HostScene {
-    std::vector<SphereRec<R>> spheres;
-    std::vector<MovingSphereRec<R>> moving;
-    std::vector<RectRec<R>> rects;
-    std::vector<BoxRec<R>> boxes;
-    std::vector<InstanceRec<R>> insts;
-    std::vector<MediumRec<R>> media;
-    std::vector<MaterialRec<R>> mats;
-    std::vector<TextureRec<R>> texs;
-    std::vector<R> perlin_vec;
+template <typename R> struct HostScene : NarrowScene<R> { // the records the device uploads (scene_narrow.hpp), walked where they lie
     SceneView<R> view;
     std::vector<Bvh4QNode> nodes4q; // HOSTSIM_QUANT=1: the f64 decoupled kernel's records, made by the same per-record function as on the device
     void make_quant4(const FlatScene& f) {
@@ -93,69 +85,40 @@ template <typename R> struct HostScene {
         for (size_t i = 0; i < f.nodes4.size(); ++i) quant4_make(f.nodes4.data(), int32_t(i), nodes4q[i]);
         view.nodes4q = nodes4q.data();
     }
-    explicit HostScene(const FlatScene& f) {
-        for (auto& s : f.spheres) spheres.push_back({R(s.cx), R(s.cy), R(s.cz), R(s.r)});
-        for (auto& m : f.moving) {
-            MovingSphereRec<R> o{};
-            for (int k = 0; k < 3; ++k) { o.c0[k] = R(m.c0[k]); o.c1[k] = R(m.c1[k]); }
-            o.r = R(m.r); o.t0 = R(m.t0); o.t1 = R(m.t1); o.mat = m.mat; o.seq = m.seq;
-            moving.push_back(o);
-        }
-        for (auto& r : f.rects) rects.push_back({R(r.a0), R(r.a1), R(r.b0), R(r.b1), R(r.k), r.plane, r.mat, r.seq});
-        for (auto& b : f.boxes) {
-            BoxRec<R> o{};
-            for (int k = 0; k < 3; ++k) { o.mn[k] = R(b.mn[k]); o.mx[k] = R(b.mx[k]); }
-            o.mat = b.mat; o.seq = b.seq;
-            boxes.push_back(o);
-        }
-        for (auto& i : f.insts) {
-            InstanceRec<R> o{};
-            o.n_ops = i.n_ops; o.root = i.root; o.single_leaf = i.single_leaf;
-            for (int k = 0; k < MAX_INSTANCE_OPS; ++k) {
-                o.ops[k].type = i.ops[k].type;
-                for (int c = 0; c < 3; ++c) o.ops[k].v[c] = R(i.ops[k].v[c]);
-            }
-            insts.push_back(o);
-        }
-        for (auto& m : f.media) media.push_back({m.b_first, m.b_count, m.inst, m.n_outer, m.mat, m.ref0, R(m.neg_inv_density)});
-        for (auto& m : f.mats) mats.push_back({m.type, m.tex, {R(m.albedo[0]), R(m.albedo[1]), R(m.albedo[2])}, R(m.param)});
-        for (auto& t : f.texs) texs.push_back({t.type, t.a, t.b, 0, {R(t.color[0]), R(t.color[1]), R(t.color[2])}, R(t.scale)});
-        for (double v : f.perlin_vec) perlin_vec.push_back(R(v));
-        view.nodes = f.nodes4.data();
-        view.nodes4q = nullptr;
-        view.spheres = spheres.data(); view.sphere_mat = f.sphere_mat_is_index ? nullptr : f.sphere_mat.data(); view.sphere_seq = f.sphere_seq.data();
-        view.moving = moving.data(); view.rects = rects.data(); view.boxes = boxes.data();
-        view.insts = insts.data(); view.media = media.data(); view.medium_refs = f.medium_refs.data(); view.mats = mats.data(); view.texs = texs.data();
-        view.images = f.images.data(); view.texels = f.texels.data();
-        view.perlin_vec = perlin_vec.data(); view.perlin_perm = f.perlin_perm.data();
-        view.top_root = f.top_root; view.n_media = int32_t(media.size());
-    }
+    explicit HostScene(const FlatScene& f) : NarrowScene<R>(f) { this->fill_view(f, view); }
 };
 
-template <typename R> CameraRec<R> narrow_camera(const CameraRec<double>& c) {
-    CameraRec<R> o;
-    for (int k = 0; k < 3; ++k) {
-        o.origin[k] = R(c.origin[k]); o.lower_left_corner[k] = R(c.lower_left_corner[k]);
-        o.horizontal[k] = R(c.horizontal[k]); o.vertical[k] = R(c.vertical[k]); o.u[k] = R(c.u[k]); o.v[k] = R(c.v[k]);
+// What every render and model below starts from: the scene's records, the camera and the constants of a render of `p` in precision R.
+// `rc` holds what all of them set — image size, spp, depth, quirks, seed; everything else stays 0 unless the caller sets it.
+template <typename R> struct HostSetup {
+    HostScene<R> hs;
+    CameraRec<R> camr;
+    RenderConsts rc{};
+    HostSetup(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p) : hs(s->flat), camr(camera_of<R>(cam)) {
+        rc.width = p->width; rc.height = p->height; rc.spp = p->spp; rc.max_depth = p->max_depth; rc.quirks = p->quirks; rc.seed = p->seed;
     }
-    o.lens_radius = R(c.lens_radius); o.open_time = R(c.open_time); o.close_time = R(c.close_time);
-    return o;
-}
+    // ... of a kernel model: the render's chunk schedule and the job numbering of one rank that owns the whole frame
+    void plan_whole_frame(const rttnw_params* p) {
+        rc.sample_begin = p->sample_begin;
+        plan_chunks(rc, p->spp, p->spp_chunk);
+        rc.tiles_x = (rc.width + 7) / 8; rc.tiles_y = (rc.height + 7) / 8; rc.n_tiles = rc.tiles_x * rc.tiles_y;
+        rc.tile_rank = 0; rc.tile_world = 1; rc.my_tiles = rc.n_tiles;
+        rc.div_tiles_x = make_fastdiv(std::max<uint32_t>(1u, rc.tiles_x));
+        plan_jobs(rc);
+    }
+};
 
 template <typename R, typename StackT>
 int render_t(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* out_linear, rttnw_stats* stats,
              int n_threads) {
-    HostScene<R> hs(s->flat);
+    HostSetup<R> su(s, cam, p);
+    HostScene<R>& hs = su.hs;
+    const CameraRec<R>& camr = su.camr;
+    RenderConsts& rc = su.rc;
     if (StackT::WIDE == NODES_Q8X4) hs.make_quant4(s->flat);
-    CameraRec<double> cam64;
-    make_camera(cam->lookfrom, cam->lookat, cam->view_up, cam->vertical_fov, cam->aspect_ratio, cam->aperture,
-                cam->focus_distance, cam->open_time, cam->close_time, cam64);
-    CameraRec<R> camr = narrow_camera<R>(cam64);
-    RenderConsts rc{};
-    rc.width = p->width; rc.height = p->height; rc.spp = p->spp; rc.max_depth = p->max_depth;
     rc.sample_begin = p->sample_begin;
     plan_chunks(rc, p->spp, p->spp_chunk); // the render's chunk schedule: a function of spp alone (rt_types.hpp)
-    rc.quirks = p->quirks; rc.seed = p->seed; rc.stack_depth = s->flat.stack_depth;
+    rc.stack_depth = s->flat.stack_depth;
     V3<R> background(R(p->background[0]), R(p->background[1]), R(p->background[2]));
     const R t_min = R(p->t_min);
     if (n_threads <= 0) n_threads = int(std::thread::hardware_concurrency());
@@ -207,52 +170,19 @@ int render_t(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p
 template <typename R>
 static int probe_path_t(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t px, uint32_t row,
                         uint32_t sample, double* out, uint32_t max_out) {
-    HostScene<R> hs(s->flat);
-    CameraRec<double> cam64;
-    make_camera(cam->lookfrom, cam->lookat, cam->view_up, cam->vertical_fov, cam->aspect_ratio, cam->aperture,
-                cam->focus_distance, cam->open_time, cam->close_time, cam64);
-    CameraRec<R> camr = narrow_camera<R>(cam64);
-    RenderConsts rc{};
-    rc.width = p->width; rc.height = p->height; rc.spp = p->spp; rc.max_depth = p->max_depth; rc.quirks = p->quirks; rc.seed = p->seed;
-    PathState<R> ps;
-    path_begin(ps, camr, rc, px, row, sample);
+    HostSetup<R> su(s, cam, p);
     HostStack stack; NoCounters cnt;
-    uint32_t n = 0;
-    while (n < max_out) { // same record layout as rttnw_debug_probe_path (include/rttnw_hip.h): 20 doubles per bounce
-        HitRecord<R> rec;
-        const Ray<R> ray = ps.ray;
-        if (!world_hit(hs.view, ps.ray, R(p->t_min), ps.key, ps.bounce, rc.quirks, rec, stack, cnt)) break;
-        double* o = out + size_t(n) * 20;
-        o[0] = rec.t; o[1] = rec.p.x; o[2] = rec.p.y; o[3] = rec.p.z; o[4] = rec.normal.x; o[5] = rec.normal.y; o[6] = rec.normal.z;
-        o[7] = double(rec.mat); o[8] = rec.u; o[9] = rec.v; o[10] = rec.front_face ? 1.0 : 0.0;
-        o[11] = ray.o.x; o[12] = ray.o.y; o[13] = ray.o.z; o[14] = ray.d.x; o[15] = ray.d.y; o[16] = ray.d.z; o[17] = ray.time;
-        ++n;
-        V3<R> att, em;
-        const bool cont = shade(hs.view, rec, ps.key, ps.bounce, ps.ray, att, em, cnt);
-        o[18] = em.x; o[19] = cont ? att.x : -1.0;
-        if (!cont) break;
-        ps.bounce += 1;
-        if (ps.bounce >= rc.max_depth) break;
-    }
-    // the same sample again through path_step(), as the device probe does: radiance (background black) and bounce count after `out`
-    path_begin(ps, camr, rc, px, row, sample);
-    while (path_step(ps, hs.view, rc, V3<R>(), R(p->t_min), stack, cnt)) {}
-    double* tail = out + size_t(max_out) * 20;
-    tail[0] = ps.radiance.x; tail[1] = ps.radiance.y; tail[2] = ps.radiance.z; tail[3] = double(ps.bounce);
-    return int(n);
+    return int(probe_path(su.hs.view, su.camr, su.rc, R(p->t_min), px, row, sample, out, max_out, stack, cnt));
 }
 
 // Walk-length statistics of a render: hist[k] = walks that took k trips round the walk loop of `node_steps` node steps + a
 // leaf step (what a wave's lanes do in lockstep); out2 = {walks, node visits, record tests}.  Experiment support.
 static void walk_histogram(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, int node_steps, uint64_t* hist,
                            uint64_t* out2) {
-    HostScene<float> hs(s->flat);
-    CameraRec<double> cam64;
-    make_camera(cam->lookfrom, cam->lookat, cam->view_up, cam->vertical_fov, cam->aspect_ratio, cam->aperture,
-                cam->focus_distance, cam->open_time, cam->close_time, cam64);
-    CameraRec<float> camr = narrow_camera<float>(cam64);
-    RenderConsts rc{};
-    rc.width = p->width; rc.height = p->height; rc.spp = p->spp; rc.max_depth = p->max_depth; rc.quirks = p->quirks; rc.seed = p->seed;
+    HostSetup<float> su(s, cam, p);
+    const HostScene<float>& hs = su.hs;
+    const CameraRec<float>& camr = su.camr;
+    const RenderConsts& rc = su.rc;
     V3<float> background(float(p->background[0]), float(p->background[1]), float(p->background[2]));
     HostStack stack; LaneCounters cnt;
     const int mode = node_steps / 100; // experiment: 1 = test the previous hit's primitive first when it was inside an instance
@@ -302,19 +232,11 @@ static void walk_histogram(rttnw_scene* s, const rttnw_camera_desc* cam, const r
 template <typename R>
 static void wave_model(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, int policy, int a, int b, uint32_t n_waves,
                        uint32_t jobs_per_wave, uint64_t* out) {
-    HostScene<R> hs(s->flat);
-    CameraRec<double> cam64;
-    make_camera(cam->lookfrom, cam->lookat, cam->view_up, cam->vertical_fov, cam->aspect_ratio, cam->aperture,
-                cam->focus_distance, cam->open_time, cam->close_time, cam64);
-    CameraRec<R> camr = narrow_camera<R>(cam64);
-    RenderConsts rc{};
-    rc.width = p->width; rc.height = p->height; rc.spp = p->spp; rc.max_depth = p->max_depth; rc.quirks = p->quirks; rc.seed = p->seed;
-    rc.sample_begin = p->sample_begin;
-    plan_chunks(rc, p->spp, p->spp_chunk);
-    rc.tiles_x = (rc.width + 7) / 8; rc.tiles_y = (rc.height + 7) / 8; rc.n_tiles = rc.tiles_x * rc.tiles_y;
-    rc.tile_rank = 0; rc.tile_world = 1; rc.my_tiles = rc.n_tiles;
-    rc.div_tiles_x = make_fastdiv(std::max<uint32_t>(1u, rc.tiles_x));
-    plan_jobs(rc);
+    HostSetup<R> su(s, cam, p);
+    su.plan_whole_frame(p);
+    const HostScene<R>& hs = su.hs;
+    const CameraRec<R>& camr = su.camr;
+    const RenderConsts& rc = su.rc;
     V3<R> background(R(p->background[0]), R(p->background[1]), R(p->background[2]));
     const R t_min = R(p->t_min);
     struct Lane {
