@@ -158,6 +158,17 @@ impl Scene {
         ok(unsafe { ffi::rttnw_render_adaptive(self.raw, cam, p, a, ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), &mut stats) })?;
         Ok((rgba, spp, stderr, stats))
     }
+    /// The same adaptive render from the GPUs `devices` of this node (`rttnw_render_adaptive_multi`): bit-identical outputs, one stats record
+    /// per rank (a device may repeat: logical ranks).
+    pub fn render_adaptive_multi(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, a: &ffi::rttnw_adaptive, devices: &[i32]) -> Result<(Vec<u8>, Vec<u32>, Vec<f64>, Vec<ffi::rttnw_stats>)> {
+        let n = p.width as usize * p.height as usize;
+        let mut rgba = vec![0u8; n * 4];
+        let mut spp = vec![0u32; n];
+        let mut stderr = vec![0f64; n * 3];
+        let mut stats = vec![ffi::rttnw_stats::default(); devices.len()];
+        ok(unsafe { ffi::rttnw_render_adaptive_multi(self.raw, cam, p, a, devices.len() as u32, devices.as_ptr(), ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), stats.as_mut_ptr()) })?;
+        Ok((rgba, spp, stderr, stats))
+    }
     /// First-hit feature buffers of the frame `render` renders (`rttnw_render_features`), row-major, top row first.
     pub fn render_features(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params) -> Result<Features> {
         let n = p.width as usize * p.height as usize;

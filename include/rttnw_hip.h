@@ -40,8 +40,8 @@ extern "C" {
 #define RTTNW_ABI_VERSION 3 /* 2: 4-wide node records (n_nodes, debug_scene_nodes4), rttnw_render_multi
                              * 3: RTTNW_F64_STRICT, rttnw_shutdown, RTTNW_BVH_AUTO (the default builder), rttnw_stats.reserved is a bit mask
                              *    (below), validate() rejects t_min < 0
-                             * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise and rttnw_render_region came later, without a
-                             *  version bump: a caller detects each by its symbol) */
+                             * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region and rttnw_render_adaptive_multi
+                             *  came later, without a version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -385,6 +385,32 @@ int rttnw_denoise(uint32_t width, uint32_t height, const double* linear_rgb, con
  * or ncclCommInitAll fails (stats[0].reserved bits 8 / 9). */
 int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t ngpu,
                        const int32_t* device_ids, double* out_linear_rgb, uint8_t* out_rgba8, rttnw_stats* stats);
+
+/* Adaptive sampling on the GPUs of ONE NODE: rttnw_render_adaptive over the ranks of rttnw_render_multi, in one call from one host thread.
+ * (Came without a version bump, like rttnw_render_adaptive: detect it by its symbol.)
+ *
+ * Contract.  The four outputs — linear image, RGBA8, samples map, standard-error map (the +inf of a pixel with fewer than two chunks included) —
+ *   are BIT-IDENTICAL to rttnw_render_adaptive(s, cam, p, a, ...): for every ngpu, every device list (a device may repeat: logical ranks, as in
+ *   rttnw_render_multi), both gather transports and the fall-through between them, every `precision`, every kernel form and every launch split
+ *   (RTTNW_CHUNK_SUM_BUDGET).  A pixel's stopping decision reads its own chunk sums only, so it does not matter which rank traces it.
+ * Ranks.  Rank r owns the tiles rttnw_render_multi gives it, on device device_ids[r].  Pass 0 traces them in the plain render's job numbering;
+ *   pass k > 0 traces the list of the rank's 2x2 blocks that still hold an active pixel.  Every pass is enqueued on all ranks that still have
+ *   active pixels before the host waits for any of them (ranks that share a device run one after the other on it); a rank whose list is empty
+ *   takes no further part.  `p->tile_rank` / `p->tile_world` are ignored, as in rttnw_render_multi.
+ * Gather.  Each rank's packed means and a second buffer of the same shape — standard error r, g, b and the sample count, 4 doubles per pixel —
+ *   reach rank 0's device by rttnw_render_multi's transports, under its environment (RTTNW_MULTI_GATHER), and are un-tiled there.
+ * Outputs as rttnw_render_adaptive (each optional).  `stats` (optional) points to ngpu records: stats[r].samples = the samples rank r traced
+ *   (their sum over r is the single call's stats.samples), kernel_ms = device time of all of rank r's passes, list building included, reserved =
+ *   the kernel form (rank 0 also carries bits 8 and 9, as in rttnw_render_multi), and the scene's sizes as usual.  Blocking.
+ * Refusals, before the device is touched, in this order: RTTNW_ERR_INVALID for a NULL p or a, ngpu == 0, ngpu > 64 or a NULL device_ids; what
+ *   rttnw_render_adaptive refuses among its own arguments, with its codes (pass_spp == 0, p->spp not a positive multiple of pass_spp, a negative
+ *   or NaN tolerance, a->reserved0 != 0: RTTNW_ERR_INVALID; collect_counters != 0: RTTNW_ERR_UNSUPPORTED) except its tile_world rule; whatever
+ *   rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes); RTTNW_ERR_INVALID for a device id outside
+ *   [0, rttnw_device_count()). */
+int rttnw_render_adaptive_multi(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
+                                uint32_t ngpu, const int32_t* device_ids,
+                                double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb,
+                                rttnw_stats* stats);
 
 /* Device-resident form, asynchronous on `hip_stream` (a hipStream_t; NULL = default stream).
  * Traces the tiles owned by (tile_rank, tile_world) and writes them in packed order into

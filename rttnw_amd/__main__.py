@@ -9,6 +9,8 @@ first-hit feature buffers of min(spp, 16) samples (and, with --noise, by the ada
 PREFIX_albedo.png, PREFIX_normal.png (n * 0.5 + 0.5), PREFIX_depth.png (normalised to the farthest hit) and PREFIX_alpha.png.
 --window X0,Y0,X1,Y1 renders pixels [X0, X1) x [Y0, Y1) of the frame only (rttnw_render_region) and writes that window as the image; it does
 not combine with --noise, --denoise, --features or --passes.
+--devices 0,1,2,... renders on those GPUs of the node (a device may repeat: logical ranks on one GPU): rttnw_render_multi, or with --noise
+rttnw_render_adaptive_multi — the same image either way.  It does not combine with --window, --features, --denoise or --passes.
 """
 import argparse
 import sys
@@ -38,6 +40,22 @@ def parse_window(text):
     return (x0, y0, x1, y1) if x0 < x1 and y0 < y1 else None
 
 
+def parse_devices(text):
+    """'0,1,2' -> [0, 1, 2]: 1 to 64 non-negative integers (repeats allowed), or None."""
+    parts = text.split(",")
+    if not 1 <= len(parts) <= 64 or not all(s.strip().isdigit() for s in parts):
+        return None
+    return [int(s) for s in parts]
+
+
+def node_ms(devices, stats):
+    """Device time of a multi-rank render: ranks that share a device run one after the other, devices side by side."""
+    per_device = {}
+    for dev, st in zip(devices, stats):
+        per_device[dev] = per_device.get(dev, 0.0) + st.kernel_ms
+    return max(per_device.values())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(add_help=True, usage=USAGE)
     ap.add_argument("scene", type=int)
@@ -58,11 +76,24 @@ def main(argv=None):
                     "PREFIX_normal.png, PREFIX_depth.png, PREFIX_alpha.png")
     ap.add_argument("--window", default=None, metavar="X0,Y0,X1,Y1", help="render pixels [X0, X1) x [Y0, Y1) of the frame only (row 0 = top) "
                     "and write that window as the image")
+    ap.add_argument("--devices", default=None, metavar="D0,D1,...", help="render on these GPUs of the node (repeats allowed: logical ranks); "
+                    "with --noise the adaptive render runs across them")
     try:
         args = ap.parse_args(argv)
     except SystemExit:
         print("There was an error", file=sys.stderr)   # DummyError, main.rs:260-268
         raise
+    devices = None
+    if args.devices is not None:
+        devices = parse_devices(args.devices)
+        if devices is None:
+            print("--devices wants D0,D1,...: 1 to 64 non-negative device numbers separated by commas, got %r" % args.devices, file=sys.stderr)
+            return 1
+        clash = [name for name, on in (("--window", args.window is not None), ("--features", args.features is not None), ("--denoise", args.denoise),
+                                       ("--passes", args.passes > 1)) if on]
+        if clash:
+            print("--devices does not combine with %s: it runs the plain and the adaptive render only" % ", ".join(clash), file=sys.stderr)
+            return 1
     window = None
     if args.window is not None:
         window = parse_window(args.window)
@@ -140,14 +171,20 @@ def main(argv=None):
             cap = (p.spp + args.pass_spp - 1) // args.pass_spp * args.pass_spp
             print("cap %d spp rounded up to %d, a multiple of --pass-spp %d" % (p.spp, cap, args.pass_spp))
             p.spp = cap
-        lin, rgba, spp_map, se, st = render.render_adaptive(sc, cam, p, args.pass_spp, args.noise, args.abs_noise)
+        per_rank = ""
+        if devices is not None:
+            lin, rgba, spp_map, se, sts = render.render_adaptive_multi(sc, cam, p, devices, args.pass_spp, args.noise, args.abs_noise)
+            st = abi.Stats(samples=sum(x.samples for x in sts), kernel_ms=node_ms(devices, sts))
+            per_rank = "; per rank: %s" % " ".join(str(x.samples) for x in sts)
+        else:
+            lin, rgba, spp_map, se, st = render.render_adaptive(sc, cam, p, args.pass_spp, args.noise, args.abs_noise)
         Image.fromarray(finish(lin, rgba, se), "RGBA").save(args.out)
         if args.spp_map:
             grey = np.minimum(spp_map.astype(np.float64) / p.spp * 255.0 + 0.5, 255.0).astype(np.uint8)
             Image.fromarray(grey, "L").save(args.spp_map)
         full = w * h * p.spp
-        print("%.3fs (adaptive: %d samples traced of %d = %dx%dx%d, %.1f %%; kernels %.1f ms)"
-              % (time.time() - t0, st.samples, full, w, h, p.spp, 100.0 * st.samples / full, st.kernel_ms))
+        print("%.3fs (adaptive: %d samples traced of %d = %dx%dx%d, %.1f %%; kernels %.1f ms%s)"
+              % (time.time() - t0, st.samples, full, w, h, p.spp, 100.0 * st.samples / full, st.kernel_ms, per_rank))
         return 0
     if args.passes > 1:
         def show(k, linear):
@@ -155,6 +192,13 @@ def main(argv=None):
             print("pass %d/%d written" % (k + 1, args.passes))
         _, rgba, _ = render.render_host_passes(sc, cam, p, args.passes, on_pass=show)
         print("%.3fs" % (time.time() - t0))
+        return 0
+    if devices is not None:
+        lin, rgba, sts = render.render_multi(sc, cam, p, devices)
+        Image.fromarray(np.ascontiguousarray(rgba), "RGBA").save(args.out)
+        ms = node_ms(devices, sts)
+        print("%.3fs (%d ranks, trace kernels %.1f ms, %.1f Msamples/s)" % (time.time() - t0, len(sts), ms,
+                                                                           sum(x.samples for x in sts) / max(ms, 1e-9) / 1e3))
         return 0
     lin, rgba, st = render.render_host(sc, cam, p)
     Image.fromarray(finish(lin, rgba, None), "RGBA").save(args.out)

@@ -1,5 +1,5 @@
 // render_api.cpp — the extern "C" half of the device side of include/rttnw_hip.h: device state, render entry points,
-// rttnw_render_multi (per-device streams, RCCL gather).  Host code only; the kernels and their launch code live in
+// rttnw_render_multi and rttnw_render_adaptive_multi (per-device streams, RCCL gather).  Host code only; the kernels and their launch code live in
 // render_f32.hip / render_f64.hip (render_common.hpp says why there are two).
 // No CPU fallback: every entry point needs a HIP device.
 #include "render_common.hpp"
@@ -13,8 +13,16 @@ namespace rt {
 
 // A plain render's launch code in the precision of `p`
 static int render_tiles_any(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream,
-                            rttnw_stats* stats, bool sync_for_stats = true, bool prepare_only = false) {
-    return RT_BY_PRECISION(p->precision, render_tiles_t, s, d, cam, p, d_packed, stream, stats, sync_for_stats, prepare_only, nullptr);
+                            rttnw_stats* stats, bool sync_for_stats = true, bool prepare_only = false, const ListPass* ad = nullptr) {
+    return RT_BY_PRECISION(p->precision, render_tiles_t, s, d, cam, p, d_packed, stream, stats, sync_for_stats, prepare_only, ad);
+}
+// What rttnw_render_adaptive and rttnw_render_adaptive_multi refuse among the adaptive arguments themselves (both non-NULL): no device needed
+static int refuse_adaptive_misuse(const char* prefix, const rttnw_params* p, const rttnw_adaptive* a) {
+    const std::string call = std::string(prefix) + ": ";
+    if (a->pass_spp == 0) { set_last_error(call + "pass_spp is 0"); return RTTNW_ERR_INVALID; }
+    if (p->spp == 0 || p->spp % a->pass_spp != 0) { set_last_error(call + "spp (the cap) must be a positive multiple of pass_spp"); return RTTNW_ERR_INVALID; }
+    if (!(a->rel_error >= 0.0) || !(a->abs_error >= 0.0)) { set_last_error(call + "rel_error and abs_error must be >= 0 (and not NaN)"); return RTTNW_ERR_INVALID; }
+    return 0;
 }
 
 // The linear image of a blocking render (`linear`: d->linear or d->rg_linear, in the render's precision) to the caller's doubles: an f32 image is
@@ -268,9 +276,7 @@ int rttnw_render_adaptive(rttnw_scene* s, const rttnw_camera_desc* cam, const rt
                           uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, rttnw_stats* stats) {
     // the adaptive arguments first: their refusals need no device (nor a committed scene)
     if (!p || !a) { rt::set_last_error("render_adaptive: NULL argument"); return RTTNW_ERR_INVALID; }
-    if (a->pass_spp == 0) { rt::set_last_error("render_adaptive: pass_spp is 0"); return RTTNW_ERR_INVALID; }
-    if (p->spp == 0 || p->spp % a->pass_spp != 0) { rt::set_last_error("render_adaptive: spp (the cap) must be a positive multiple of pass_spp"); return RTTNW_ERR_INVALID; }
-    if (!(a->rel_error >= 0.0) || !(a->abs_error >= 0.0)) { rt::set_last_error("render_adaptive: rel_error and abs_error must be >= 0 (and not NaN)"); return RTTNW_ERR_INVALID; }
+    if (int rc = rt::refuse_adaptive_misuse("render_adaptive", p, a)) return rc;
     if (int rc = rt::refuse_host_output_misuse("render_adaptive", a->reserved0, p)) return rc;
     if (int rc = rt::validate(s, cam, p)) return rc;
     rt::DeviceState* d = s->device;
@@ -402,18 +408,21 @@ struct MultiPlan {
     std::vector<uint32_t> dev_ranks;      // ... and how many ranks live on it
     DeviceState* root = nullptr;
     size_t rsz = 0, chunk = 0, npx = 0;   // bytes of a real, of a rank's packed tiles; pixels of the image
+    size_t aux_chunk = 0;                 // rttnw_render_adaptive_multi: bytes of a rank's auxiliary records, which travel with its tiles (0: a plain render)
     bool transport() const { return devices.size() > 1 || env.force_transport; }         // some rank's tiles travel
     bool local(uint32_t r) const { return !env.force_transport && ranks[r].dev == 0; }    // rank r's do not: a copy on the root's device
     uint8_t* packed(uint32_t r) const { return ranks[r].d->multi_packed.p + chunk * ranks[r].slot; } // rank r's packed tiles, on its device
     uint8_t* gathered(uint32_t r) const { return root->gathered.p + chunk * r; }                      // ... and their place on the root's
+    uint8_t* aux(uint32_t r) const { return ranks[r].d->multi_aux.p + aux_chunk * ranks[r].slot; }    // the same for its auxiliary records
+    uint8_t* gathered_aux(uint32_t r) const { return root->gathered_aux.p + aux_chunk * r; }
 };
 
-static int multi_plan(::rttnw_scene* s, const rttnw_params& p, uint32_t ngpu, const int32_t* device_ids, MultiPlan& m) {
+static int multi_plan(::rttnw_scene* s, const rttnw_params& p, uint32_t ngpu, const int32_t* device_ids, MultiPlan& m, const char* call = "render_multi") {
     std::string err;
     m.ranks.resize(ngpu);
     for (uint32_t r = 0; r < ngpu; ++r) {
         DeviceState* d = state_on(s, device_ids[r], err);
-        if (!d) { set_last_error("render_multi: " + err); return RTTNW_ERR_HIP; }
+        if (!d) { set_last_error(std::string(call) + ": " + err); return RTTNW_ERR_HIP; }
         uint32_t k = 0;
         while (k < m.devices.size() && m.devices[k] != device_ids[r]) ++k;
         if (k == m.devices.size()) { m.devices.push_back(device_ids[r]); m.dev_state.push_back(d); m.dev_ranks.push_back(0); }
@@ -430,7 +439,7 @@ static int multi_plan(::rttnw_scene* s, const rttnw_params& p, uint32_t ngpu, co
 
 // Everything that allocates, before anything is launched (an allocation or a free between two ranks' launches would synchronise its whole
 // device): the streams, this layer's buffers, then per rank what a first use brings — scene uploads and workspace growth
-static int multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const MultiPlan& m) {
+static int multi_prepare_buffers(const MultiPlan& m) {
     for (size_t k = 0; k < m.devices.size(); ++k) {
         DeviceState* d = m.dev_state[k];
         HIP_TRY(hipSetDevice(d->device));
@@ -442,6 +451,10 @@ static int multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam, const r
     HIP_TRY(root->gathered.grow(m.chunk * m.ranks.size()));
     HIP_TRY(root->linear.grow(m.npx * 3 * m.rsz));
     HIP_TRY(root->rgba.grow(m.npx * 4));
+    return 0;
+}
+static int multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const MultiPlan& m) {
+    if (int rc = multi_prepare_buffers(m)) return rc;
     for (uint32_t r = 0; r < m.ranks.size(); ++r) {
         rttnw_params pr = p;
         pr.tile_rank = r;
@@ -510,6 +523,10 @@ static int gather_rccl(const MultiPlan& m) {
         nr = g_rccl.Send(m.packed(r), m.chunk, ncclChar, 0, mc->comms[k], m.ranks[r].d->stream.get());
         if (nr == ncclSuccess) nr = g_rccl.Recv(m.gathered(r), m.chunk, ncclChar, int(k), mc->comms[0], m.root->stream.get());
         ++n_sent;
+        if (!m.aux_chunk) continue; // the rank's auxiliary records: a second send inside the one group
+        if (nr == ncclSuccess) nr = g_rccl.Send(m.aux(r), m.aux_chunk, ncclChar, 0, mc->comms[k], m.ranks[r].d->stream.get());
+        if (nr == ncclSuccess) nr = g_rccl.Recv(m.gathered_aux(r), m.aux_chunk, ncclChar, int(k), mc->comms[0], m.root->stream.get());
+        ++n_sent;
     }
     ncclResult_t ne = g_rccl.GroupEnd();
     if (nr == ncclSuccess) nr = ne;
@@ -536,6 +553,7 @@ static int gather_peer(const MultiPlan& m) {
         DeviceState* d = m.ranks[r].d;
         HIP_TRY(hipSetDevice(d->device));
         HIP_TRY(hipMemcpyPeerAsync(m.gathered(r), root->device, m.packed(r), d->device, m.chunk, d->stream.get()));
+        if (m.aux_chunk) { HIP_TRY(hipMemcpyPeerAsync(m.gathered_aux(r), root->device, m.aux(r), d->device, m.aux_chunk, d->stream.get())); ++n_sent; }
         HIP_TRY(create_event(sent[r], hipEventDisableTiming));
         HIP_TRY(hipEventRecord(sent[r].get(), d->stream.get()));
         ++n_sent;
@@ -553,15 +571,32 @@ static int gather_peer(const MultiPlan& m) {
 static int multi_untile(const rttnw_params& p, const MultiPlan& m) {
     DeviceState* root = m.root;
     HIP_TRY(hipSetDevice(root->device));
-    for (uint32_t r = 0; r < m.ranks.size(); ++r)
-        if (m.local(r)) HIP_TRY(hipMemcpyAsync(m.gathered(r), m.packed(r), m.chunk, hipMemcpyDeviceToDevice, root->stream.get()));
+    for (uint32_t r = 0; r < m.ranks.size(); ++r) {
+        if (!m.local(r)) continue;
+        HIP_TRY(hipMemcpyAsync(m.gathered(r), m.packed(r), m.chunk, hipMemcpyDeviceToDevice, root->stream.get()));
+        if (m.aux_chunk) HIP_TRY(hipMemcpyAsync(m.gathered_aux(r), m.aux(r), m.aux_chunk, hipMemcpyDeviceToDevice, root->stream.get()));
+    }
     if (int rc = rttnw_untile_device(p.width, p.height, p.tile_world, p.precision, root->gathered.p, root->linear.p, root->rgba.p, root->stream.get())) return rc;
+    if (m.aux_chunk) // ... and the samples and standard-error maps of the auxiliary records
+        if (int rc = RT_BY_PRECISION(p.precision, untile_aux_launch, p.width, p.height, p.tile_world, (const double*)root->gathered_aux.p, (uint32_t*)root->ad_spp.p,
+                                     (double*)root->ad_stderr.p, root->stream.get())) return rc;
     for (DeviceState* d : m.dev_state) {
         HIP_TRY(hipSetDevice(d->device));
         HIP_TRY(hipStreamSynchronize(d->stream.get()));
     }
     HIP_TRY(hipSetDevice(root->device));
     return 0;
+}
+// The ranks' buffers to the root's gather buffers, by the transport the call uses (MultiEnv), falling through from RCCL to the peer copies
+static int multi_gather(const MultiPlan& m, bool& use_peer, bool& fell_back) {
+    use_peer = m.transport() && m.env.gather_peer;
+    fell_back = false;
+    if (m.transport() && !use_peer) {
+        const int rc = gather_rccl(m);
+        if (rc == GATHER_UNAVAILABLE) use_peer = fell_back = true;
+        else if (rc) return rc;
+    }
+    return use_peer ? gather_peer(m) : 0;
 }
 } // namespace rt
 
@@ -583,14 +618,8 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
     if (int rc = multi_trace(s, cam, p, m, ev, stats)) return rc;
     // (refused here, after the trace, as it always was)
     if (m.env.gather_invalid) { set_last_error("render_multi: RTTNW_MULTI_GATHER must be rccl or peer"); return RTTNW_ERR_INVALID; }
-    bool use_peer = m.transport() && m.env.gather_peer, fell_back = false;
-    if (m.transport() && !use_peer) {
-        const int rc = gather_rccl(m);
-        if (rc == GATHER_UNAVAILABLE) use_peer = fell_back = true;
-        else if (rc) return rc;
-    }
-    if (use_peer)
-        if (int rc = gather_peer(m)) return rc;
+    bool use_peer = false, fell_back = false;
+    if (int rc = multi_gather(m, use_peer, fell_back)) return rc;
     if (int rc = multi_untile(p, m)) return rc;
     for (uint32_t r = 0; r < ngpu && stats; ++r) {
         float ms = 0;
@@ -601,6 +630,202 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
     if (stats && use_peer) stats[0].reserved |= 0x100u | (fell_back ? 0x200u : 0u);
     HIP_TRY(hipSetDevice(m.root->device));
     return copy_image_out("render_multi", m.root->rgba, m.root->linear, p.precision, m.npx, out_rgba8, out_linear_rgb);
+}
+
+// ---------------------------------------------------------------------------------------------
+// rttnw_render_adaptive_multi: rttnw_render_adaptive over the ranks of rttnw_render_multi (include/rttnw_hip.h has the contract, DESIGN.md §10a the
+// why).  Rank r runs render_adaptive_t's passes over ITS tiles — render_tiles_t with tile_rank = r — but the loop is pass-major, rank-minor: a pass
+// is enqueued on every live rank's stream before the host waits for any of them, so the devices of a node work side by side.
+// ---------------------------------------------------------------------------------------------
+namespace rt {
+// Where rank r keeps what lives across its passes: slots of its device's buffers, like MultiPlan::packed
+struct AdaptiveSlots {
+    rttnw_tile_layout L;
+    size_t state_chunk = 0, active_chunk = 0, list_chunk = 0; // bytes of a rank's noise state, active bytes, list + scan
+    uint32_t tiles(uint32_t r, uint32_t world) const { return L.n_tiles > r ? (L.n_tiles - r + world - 1) / world : 0; } // the tiles rank r owns (base_consts' my_tiles)
+    AdaptivePixel* state(const MultiPlan& m, uint32_t r) const { return (AdaptivePixel*)(m.ranks[r].d->multi_ad_state.p + state_chunk * m.ranks[r].slot); }
+    uint8_t* active(const MultiPlan& m, uint32_t r) const { return m.ranks[r].d->multi_ad_active.p + active_chunk * m.ranks[r].slot; }
+    uint32_t* quads(const MultiPlan& m, uint32_t r) const { return (uint32_t*)(m.ranks[r].d->multi_list.p + list_chunk * m.ranks[r].slot); }
+    uint32_t* scan(const MultiPlan& m, uint32_t r) const { return quads(m, r) + size_t(L.tiles_per_rank) * 16; }
+};
+static ListPass adaptive_rank_pass(const MultiPlan& m, const AdaptiveSlots& sl, uint32_t r, const rttnw_params& p, const rttnw_adaptive& a) {
+    ListPass ad;
+    ad.state = sl.state(m, r);
+    ad.active = sl.active(m, r);
+    ad.cap = p.spp;
+    ad.rel_error = a.rel_error;
+    ad.abs_error = a.abs_error;
+    return ad;
+}
+
+// multi_prepare for the adaptive passes: every buffer of every rank, and what a first use brings for pass 0 AND for a refinement pass over all of
+// the rank's blocks — a list never holds more, so no later pass allocates (a hipMalloc between two ranks' launches would synchronise the device)
+static int adaptive_multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const MultiPlan& m,
+                                  const AdaptiveSlots& sl) {
+    if (int rc = multi_prepare_buffers(m)) return rc;
+    for (size_t k = 0; k < m.devices.size(); ++k) {
+        DeviceState* d = m.dev_state[k];
+        HIP_TRY(hipSetDevice(d->device));
+        HIP_TRY(d->multi_ad_state.grow(sl.state_chunk * m.dev_ranks[k]));
+        HIP_TRY(d->multi_ad_active.grow(sl.active_chunk * m.dev_ranks[k]));
+        HIP_TRY(d->multi_list.grow(sl.list_chunk * m.dev_ranks[k]));
+        HIP_TRY(d->multi_aux.grow(m.aux_chunk * m.dev_ranks[k]));
+    }
+    DeviceState* root = m.root;
+    HIP_TRY(hipSetDevice(root->device));
+    HIP_TRY(root->gathered_aux.grow(m.aux_chunk * m.ranks.size()));
+    HIP_TRY(root->ad_spp.grow(m.npx * sizeof(uint32_t)));
+    HIP_TRY(root->ad_stderr.grow(m.npx * 3 * sizeof(double)));
+    rttnw_params pr = p;
+    pr.spp = a.pass_spp;
+    for (uint32_t r = 0; r < m.ranks.size(); ++r) {
+        pr.tile_rank = r;
+        DeviceState* d = m.ranks[r].d;
+        ListPass ad = adaptive_rank_pass(m, sl, r, p, a);
+        if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), d->stream.get(), nullptr, false, true, &ad)) return rc;
+        ad.quads = sl.quads(m, r);
+        ad.n_quads = sl.tiles(r, p.tile_world) * 16u;
+        ad.first = false;
+        if (ad.n_quads)
+            if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), d->stream.get(), nullptr, false, true, &ad)) return rc;
+    }
+    return 0;
+}
+
+struct HostFree { void operator()(void* q) const { (void)hipHostFree(q); } };
+
+// The passes.  Per pass and live rank, on its device's stream between its two events: the trace launches and the adaptive resolve (render_tiles_t),
+// the list of its blocks that still hold an active pixel — what its NEXT pass traces, in its own slot — and a copy of the list's two totals into
+// the rank's pinned words.  Only then does the host wait, once per device, and read the totals: a rank whose list is empty takes no further part.
+// `ms`: the ranks' device time so far; `refined`: samples they traced beyond pass 0.
+static int adaptive_multi_passes(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const MultiPlan& m,
+                                 const AdaptiveSlots& sl, std::vector<Event>& ev, uint32_t* counts, rttnw_stats* stats, std::vector<double>& ms,
+                                 std::vector<uint64_t>& refined) {
+    const uint32_t ngpu = uint32_t(m.ranks.size()), n_passes = p.spp / a.pass_spp;
+    std::vector<uint32_t> n_quads(ngpu, 0);
+    std::vector<char> live(ngpu);
+    for (uint32_t r = 0; r < ngpu; ++r) live[r] = sl.tiles(r, ngpu) != 0;
+    rttnw_params pr = p;
+    pr.spp = a.pass_spp;
+    for (uint32_t k = 0; k < n_passes; ++k) {
+        const bool more = k + 1 < n_passes; // the cap ends the loop: no list behind the last pass
+        pr.sample_begin = p.sample_begin + k * a.pass_spp;
+        std::vector<char> dev_live(m.devices.size(), 0);
+        for (uint32_t r = 0; r < ngpu; ++r) {
+            if (!live[r]) continue;
+            DeviceState* d = m.ranks[r].d;
+            const hipStream_t stream = d->stream.get();
+            HIP_TRY(hipSetDevice(d->device));
+            dev_live[m.ranks[r].dev] = 1;
+            pr.tile_rank = r;
+            ListPass ad = adaptive_rank_pass(m, sl, r, p, a);
+            if (k > 0) { ad.quads = sl.quads(m, r); ad.n_quads = n_quads[r]; ad.first = false; }
+            HIP_TRY(hipEventRecord(ev[2 * r].get(), stream));
+            // (pass 0 fills stats[r] as a plain render of the rank does: kernel form, scene sizes, the samples of its pixels)
+            if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), stream, k == 0 && stats ? &stats[r] : nullptr, false, false, &ad)) return rc;
+            if (more) {
+                uint32_t* scan = sl.scan(m, r);
+                const uint32_t n_blocks = sl.tiles(r, ngpu) * 16u; // (its own tiles only: no pass writes the active bytes of a pad tile)
+                if (int rc = RT_BY_PRECISION(p.precision, enqueue_quad_list, ad.active, n_blocks, scan, sl.quads(m, r), stream)) return rc;
+                HIP_TRY(hipMemcpyAsync(counts + 2 * r, quad_list_totals(scan, n_blocks), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            }
+            HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), stream));
+        }
+        for (size_t dk = 0; dk < m.devices.size(); ++dk) {
+            if (!dev_live[dk]) continue;
+            HIP_TRY(hipSetDevice(m.devices[dk]));
+            HIP_TRY(hipStreamSynchronize(m.dev_state[dk]->stream.get()));
+        }
+        bool any = false;
+        for (uint32_t r = 0; r < ngpu; ++r) {
+            if (!live[r]) continue;
+            float t = 0;
+            HIP_TRY(hipSetDevice(m.ranks[r].d->device));
+            HIP_TRY(hipEventElapsedTime(&t, ev[2 * r].get(), ev[2 * r + 1].get()));
+            ms[r] += t;
+            if (more) {
+                n_quads[r] = counts[2 * r];
+                refined[r] += uint64_t(counts[2 * r + 1]) * a.pass_spp; // its active pixels: what its next pass traces
+            }
+            live[r] = more && n_quads[r] != 0;
+            any = any || live[r];
+        }
+        if (!any) break; // every pixel of every rank is done
+    }
+    return 0;
+}
+} // namespace rt
+
+extern "C" int rttnw_render_adaptive_multi(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p_in, const rttnw_adaptive* a, uint32_t ngpu,
+                                           const int32_t* device_ids, double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb,
+                                           rttnw_stats* stats) {
+    using namespace rt;
+    // the refusals, in the header's order: none of them needs a device
+    if (!p_in || !a) { set_last_error("render_adaptive_multi: NULL argument (p or a)"); return RTTNW_ERR_INVALID; }
+    if (!ngpu || ngpu > 64) { set_last_error("render_adaptive_multi: ngpu must be 1 .. 64"); return RTTNW_ERR_INVALID; }
+    if (!device_ids) { set_last_error("render_adaptive_multi: device_ids is NULL"); return RTTNW_ERR_INVALID; }
+    if (int rc = refuse_adaptive_misuse("render_adaptive_multi", p_in, a)) return rc;
+    rttnw_params p = *p_in;
+    p.tile_rank = 0; p.tile_world = 1; // (the caller's are ignored, so the tile_world rule of the single call has nothing to refuse)
+    if (int rc = refuse_host_output_misuse("render_adaptive_multi", a->reserved0, &p)) return rc;
+    p.tile_world = ngpu;
+    if (int rc = validate(s, cam, &p)) return rc;
+    const int n_dev = rttnw_device_count();
+    for (uint32_t r = 0; r < ngpu; ++r)
+        if (device_ids[r] < 0 || device_ids[r] >= n_dev) { set_last_error("render_adaptive_multi: no such device in device_ids"); return RTTNW_ERR_INVALID; }
+    DeviceGuard restore; // (the caller's device is current again after EVERY return below, the error paths included)
+    MultiPlan m;
+    if (int rc = multi_plan(s, p, ngpu, device_ids, m, "render_adaptive_multi")) return rc;
+    if (m.env.gather_invalid) { set_last_error("render_adaptive_multi: RTTNW_MULTI_GATHER must be rccl or peer"); return RTTNW_ERR_INVALID; }
+    AdaptiveSlots sl;
+    fill_layout(p.width, p.height, ngpu, sl.L);
+    const auto padded = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+    sl.state_chunk = padded(size_t(sl.L.pixels_per_rank) * sizeof(AdaptivePixel));
+    sl.active_chunk = padded(sl.L.pixels_per_rank);
+    sl.list_chunk = padded((size_t(sl.L.tiles_per_rank) * 16 + quad_scan_words(sl.L.tiles_per_rank * 16u)) * sizeof(uint32_t));
+    m.aux_chunk = size_t(sl.L.pixels_per_rank) * 4 * sizeof(double);
+    // everything that allocates, before the first launch: buffers and workspaces, the ranks' events, their pinned words for the lists' totals
+    if (int rc = adaptive_multi_prepare(s, cam, p, *a, m, sl)) return rc;
+    std::vector<Event> ev(size_t(ngpu) * 2);
+    for (uint32_t r = 0; r < ngpu; ++r) {
+        HIP_TRY(hipSetDevice(m.ranks[r].d->device));
+        HIP_TRY(create_event(ev[2 * r]));
+        HIP_TRY(create_event(ev[2 * r + 1]));
+    }
+    void* pinned = nullptr;
+    HIP_TRY(hipHostMalloc(&pinned, size_t(ngpu) * 2 * sizeof(uint32_t), hipHostMallocPortable));
+    std::unique_ptr<void, HostFree> counts(pinned);
+    std::memset(pinned, 0, size_t(ngpu) * 2 * sizeof(uint32_t));
+    if (stats) std::memset(stats, 0, size_t(ngpu) * sizeof(*stats)); // (a rank without a tile runs nothing and keeps zeros)
+    std::vector<double> ms(ngpu, 0.0);
+    std::vector<uint64_t> refined(ngpu, 0);
+    if (int rc = adaptive_multi_passes(s, cam, p, *a, m, sl, ev, (uint32_t*)pinned, stats, ms, refined)) return rc;
+    // every rank's sums to means and auxiliary records (a rank without a tile: zeros), in its device time like adaptive_output_kernel in the single call's
+    for (uint32_t r = 0; r < ngpu; ++r) {
+        DeviceState* d = m.ranks[r].d;
+        HIP_TRY(hipSetDevice(d->device));
+        HIP_TRY(hipEventRecord(ev[2 * r].get(), d->stream.get()));
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_finish_launch, m.packed(r), sl.state(m, r), (double*)m.aux(r), sl.L.pixels_per_rank,
+                                     sl.tiles(r, ngpu) * 64u, d->stream.get())) return rc;
+        HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), d->stream.get()));
+    }
+    bool use_peer = false, fell_back = false;
+    if (int rc = multi_gather(m, use_peer, fell_back)) return rc;
+    if (int rc = multi_untile(p, m)) return rc;
+    for (uint32_t r = 0; r < ngpu && stats; ++r) {
+        float t = 0;
+        HIP_TRY(hipSetDevice(m.ranks[r].d->device));
+        HIP_TRY(hipEventElapsedTime(&t, ev[2 * r].get(), ev[2 * r + 1].get()));
+        stats[r].kernel_ms = ms[r] + t;
+        stats[r].samples += refined[r];
+    }
+    if (stats && use_peer) stats[0].reserved |= 0x100u | (fell_back ? 0x200u : 0u);
+    DeviceState* root = m.root;
+    HIP_TRY(hipSetDevice(root->device));
+    hipError_t e = hipSuccess;
+    if (out_spp) e = hipMemcpy(out_spp, root->ad_spp.p, m.npx * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_stderr_rgb) e = hipMemcpy(out_stderr_rgb, root->ad_stderr.p, m.npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    return copy_image_out("render_adaptive_multi", root->rgba, root->linear, p.precision, m.npx, out_rgba8, out_linear_rgb, e);
 }
 
 // Release what the library keeps for the life of the process (today: the RCCL communicator sets of rttnw_render_multi).  Scenes

@@ -233,7 +233,14 @@ struct DeviceState {
     DevBuf<uint8_t> rg_mask, rg_select, rg_sums, rg_linear, rg_rgba;
     // both: the list of 2x2 blocks that hold a marked pixel and its scan (render_tiles.hpp build_quad_list), built anew before every use
     DevBuf<uint8_t> list_quads, list_scan;
+    // rttnw_render_adaptive_multi: what lives across passes, per logical rank of this device (slotted like multi_packed) — the noise state, the
+    // active bytes, each rank's list and scan (a rank's list is built behind one pass and read by its next, with other ranks' work between) —
+    // and the ranks' auxiliary records (standard errors and samples, 4 doubles per packed pixel); on the root device, every rank's records
+    DevBuf<uint8_t> multi_ad_state, multi_ad_active, multi_list, multi_aux, gathered_aux;
 };
+// Words of build_quad_list's scan workspace over n_blocks blocks, and where its two totals (listed blocks, marked pixels) stand in it
+inline size_t quad_scan_words(uint32_t n_blocks) { return size_t((n_blocks + 63u) / 64u) * 3 + 2; }
+inline uint32_t* quad_list_totals(uint32_t* scan, uint32_t n_blocks) { return scan + size_t((n_blocks + 63u) / 64u) * 3; }
 // What render_tiles_t needs to run a pass that is not a plain render's (render_tiles.hpp): a resolve step of the pass's own in place of
 // resolve_kernel and, with `quads`, the active-list instantiation of the scene's kernel over that list of 2x2 blocks.
 //   state != nullptr  a pass of rttnw_render_adaptive (render_adaptive_t): adaptive_resolve_kernel, which keeps the noise state
@@ -304,6 +311,7 @@ inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, co
 // both builds and what a precision's translation unit instantiates (RT_INSTANTIATE_PRECISION): a new entry point is one line here.
 //   render_adaptive_t  rttnw_render_adaptive's device half: every pass, then the image (d->linear, d->rgba) and the maps (d->ad_spp, d->ad_stderr) on the device
 //   render_region_t    rttnw_render_region's device half: selection, list, trace, resolve; the window's image on the device (d->rg_linear, d->rg_rgba)
+//   enqueue_quad_list, adaptive_finish_launch, untile_aux_launch   what rttnw_render_adaptive_multi (render_api.cpp) enqueues beside render_tiles_t's passes
 #define RT_PRECISION_ENTRY_POINTS(X, R)                                                                                                              \
     X(R, render_tiles_t, (::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream, \
                           rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const ListPass* ad))                                          \
@@ -313,7 +321,12 @@ inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, co
                          hipStream_t stream))                                                                                                        \
     X(R, render_adaptive_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, rttnw_stats* stats))    \
     X(R, render_region_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t x0, uint32_t y0, uint32_t x1,             \
-                           uint32_t y1, const uint8_t* mask, rttnw_stats* stats))
+                           uint32_t y1, const uint8_t* mask, rttnw_stats* stats))                                                                    \
+    X(R, enqueue_quad_list, (const uint8_t* marks, uint32_t n_blocks, uint32_t* scan, uint32_t* quads, hipStream_t stream))                          \
+    X(R, adaptive_finish_launch, (void* d_packed, const void* d_state, double* d_aux, uint32_t pixels_per_rank, uint32_t rank_pixels,                \
+                                  hipStream_t stream))                                                                                               \
+    X(R, untile_aux_launch, (uint32_t width, uint32_t height, uint32_t world, const double* d_gathered_aux, uint32_t* d_spp, double* d_stderr,       \
+                             hipStream_t stream))
 #define RT_DECLARE_T(R, name, params) template <typename> int name params;
 #define RT_EXTERN_T(R, name, params) extern template int name<R> params;
 #define RT_INSTANTIATE_T(R, name, params) template int name<R> params;

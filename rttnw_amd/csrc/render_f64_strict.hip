@@ -20,5 +20,8 @@ template int render_adaptive_t<double>(::rttnw_scene*, const rttnw_camera_desc*,
 template int render_region_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*,
                                      rttnw_stats*);
 template int probe_path_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
+template int enqueue_quad_list<double>(const uint8_t*, uint32_t, uint32_t*, uint32_t*, hipStream_t);
+template int adaptive_finish_launch<double>(void*, const void*, double*, uint32_t, uint32_t, hipStream_t);
+template int untile_aux_launch<double>(uint32_t, uint32_t, uint32_t, const double*, uint32_t*, double*, hipStream_t);
 } // namespace RT_ARITH_NS
 } // namespace rt

@@ -259,23 +259,31 @@ int untile_launch(uint32_t width, uint32_t height, uint32_t world, const void* d
     return RTTNW_OK;
 }
 
-// The list of the 2x2 blocks, of n_blocks, that hold a marked pixel (`marks`: a byte per packed pixel), built on the device in d->list_quads:
-// per wave of blocks the counts, their scan, then the compaction (trace_kernels.hpp; d->list_scan holds the waves' counts of blocks and of pixels,
-// the waves' bases and the two totals).  One 8-byte copy gives the host the list's length and the number of marked pixels.
+// The list of the 2x2 blocks, of n_blocks > 0, that hold a marked pixel (`marks`: a byte per packed pixel), built on the device in `quads`
+// (n_blocks words): per wave of blocks the counts, their scan, then the compaction (trace_kernels.hpp; `scan`, quad_scan_words(n_blocks) words,
+// holds the waves' counts of blocks and of pixels, the waves' bases and, at quad_list_totals, the two totals).  Enqueued on `stream`, nothing else:
+// no allocation, no copy, no wait — rttnw_render_adaptive_multi builds every rank's list this way and reads the totals once per pass.
 template <typename R>
-int build_quad_list(DeviceState* d, const uint8_t* marks, uint32_t n_blocks, hipStream_t stream, uint32_t& n_listed, uint32_t& n_marked) {
+int enqueue_quad_list(const uint8_t* marks, uint32_t n_blocks, uint32_t* scan, uint32_t* quads, hipStream_t stream) {
     const uint32_t n_waves = (n_blocks + 63u) / 64u, grid = (n_blocks + 255u) / 256u;
-    HIP_TRY(d->list_quads.grow(size_t(n_blocks) * sizeof(uint32_t)));
-    HIP_TRY(d->list_scan.grow((size_t(n_waves) * 3 + 2) * sizeof(uint32_t)));
-    uint32_t* wave_counts = (uint32_t*)d->list_scan.p;
+    uint32_t* wave_counts = scan;
     uint32_t* wave_base = wave_counts + 2 * size_t(n_waves);
-    uint32_t* totals = wave_base + n_waves;
+    uint32_t* totals = quad_list_totals(scan, n_blocks);
     hipLaunchKernelGGL(quad_count_kernel<R>, dim3(grid), dim3(256), 0, stream, marks, n_blocks, wave_counts);
     hipLaunchKernelGGL(quad_scan_kernel<R>, dim3(1), dim3(QUAD_SCAN_BLOCK), 0, stream, (const uint32_t*)wave_counts, wave_base, n_waves, totals);
-    hipLaunchKernelGGL(quad_list_kernel<R>, dim3(grid), dim3(256), 0, stream, marks, n_blocks, (const uint32_t*)wave_base, (uint32_t*)d->list_quads.p);
+    hipLaunchKernelGGL(quad_list_kernel<R>, dim3(grid), dim3(256), 0, stream, marks, n_blocks, (const uint32_t*)wave_base, quads);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+// ... and the blocking form the single-device entry points use, in d->list_quads / d->list_scan (grown here): one 8-byte copy gives the host the
+// list's length and the number of marked pixels.
+template <typename R>
+int build_quad_list(DeviceState* d, const uint8_t* marks, uint32_t n_blocks, hipStream_t stream, uint32_t& n_listed, uint32_t& n_marked) {
+    HIP_TRY(d->list_quads.grow(size_t(n_blocks) * sizeof(uint32_t)));
+    HIP_TRY(d->list_scan.grow(quad_scan_words(n_blocks) * sizeof(uint32_t)));
+    if (int rc = enqueue_quad_list<R>(marks, n_blocks, (uint32_t*)d->list_scan.p, (uint32_t*)d->list_quads.p, stream)) return rc;
     uint32_t count[2] = {0, 0}; // listed blocks, marked pixels
-    HIP_TRY(hipMemcpy(count, totals, sizeof(count), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(count, quad_list_totals((uint32_t*)d->list_scan.p, n_blocks), sizeof(count), hipMemcpyDeviceToHost));
     n_listed = count[0];
     n_marked = count[1];
     return 0;
@@ -338,6 +346,25 @@ int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
         stats->kernel_ms = ms;
         stats->samples = samples;
     }
+    return RTTNW_OK;
+}
+
+// rttnw_render_adaptive_multi's two launches of its own (render_api.cpp has the pass loop; the passes themselves are render_tiles_t's): a rank's
+// packed sums and noise state to means and auxiliary records once its passes are over, and the gathered records to the two maps on the root.
+template <typename R>
+int adaptive_finish_launch(void* d_packed, const void* d_state, double* d_aux, uint32_t pixels_per_rank, uint32_t rank_pixels, hipStream_t stream) {
+    hipLaunchKernelGGL(adaptive_finish_packed_kernel<R>, dim3((pixels_per_rank + 255u) / 256u), dim3(256), 0, stream, (R*)d_packed,
+                       (const AdaptivePixel*)d_state, d_aux, pixels_per_rank, rank_pixels);
+    HIP_TRY(hipGetLastError());
+    return RTTNW_OK;
+}
+template <typename R>
+int untile_aux_launch(uint32_t width, uint32_t height, uint32_t world, const double* d_gathered_aux, uint32_t* d_spp, double* d_stderr, hipStream_t stream) {
+    rttnw_tile_layout L;
+    fill_layout(width, height, world, L);
+    dim3 block(32, 8), grid((width + 31) / 32, (height + 7) / 8);
+    hipLaunchKernelGGL(untile_aux_kernel<R>, grid, block, 0, stream, d_gathered_aux, d_spp, d_stderr, width, height, L.tiles_x, world, L.pixels_per_rank);
+    HIP_TRY(hipGetLastError());
     return RTTNW_OK;
 }
 

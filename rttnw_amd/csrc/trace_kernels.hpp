@@ -755,6 +755,45 @@ __global__ void adaptive_output_kernel(R* __restrict__ packed, const AdaptivePix
     for (int ch = 0; ch < 3; ++ch) stderr_map[o * 3ull + ch] = adaptive_stderr(a, ch);
 }
 
+// ---- rttnw_render_adaptive_multi: the same two steps where the pixels of a frame live on several ranks.
+// One rank's packed pixels after its last pass, one thread per packed pixel: the running sum becomes the mean by adaptive_output_kernel's own
+// division (alpha 1), and the pixel's auxiliary record — standard error r, g, b and double(n), the shape of a packed f64 pixel, so that the gather
+// moves it like one — goes to `aux`.  A pixel that traced nothing (n == 0: outside the image in an edge tile) and the pixels of pad tiles
+// (p >= rank_pixels: no pass ever wrote their state) are zero-filled in both, without a division.
+template <typename R>
+__global__ void adaptive_finish_packed_kernel(R* __restrict__ packed, const AdaptivePixel* __restrict__ state, double* __restrict__ aux,
+                                              uint32_t pixels_per_rank, uint32_t rank_pixels) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= pixels_per_rank) return;
+    R* dst = packed + (unsigned long long)p * 4ull;
+    double* rec = aux + (unsigned long long)p * 4ull;
+    AdaptivePixel a = {{0, 0, 0}, {0, 0, 0}, 0u, 0u};
+    if (p < rank_pixels) a = state[p];
+    if (a.n == 0u) {
+        dst[0] = R(0); dst[1] = R(0); dst[2] = R(0); dst[3] = R(0);
+        rec[0] = 0.0; rec[1] = 0.0; rec[2] = 0.0; rec[3] = 0.0;
+        return;
+    }
+    const R n = R(a.n);
+    dst[0] = dst[0] / n; dst[1] = dst[1] / n; dst[2] = dst[2] / n; dst[3] = R(1);
+    for (int ch = 0; ch < 3; ++ch) rec[ch] = adaptive_stderr(a, ch);
+    rec[3] = double(a.n); // (n <= 2^32: exact)
+}
+
+// Gathered auxiliary records (rank-major, untile_kernel's index arithmetic) -> the row-major, top-first samples and standard-error maps.
+template <typename R>
+__global__ void untile_aux_kernel(const double* __restrict__ gathered_aux, uint32_t* __restrict__ spp_map, double* __restrict__ stderr_map,
+                                  uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t world, uint32_t pixels_per_rank) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const uint32_t permuted = tile_permuted(x >> 3, y >> 3, tiles_x);
+    const uint32_t owner = permuted % world, local_tile = permuted / world;
+    const unsigned long long src = (unsigned long long)owner * pixels_per_rank + local_tile * 64ull + ((y & 7u) << 3) + (x & 7u);
+    const unsigned long long o = (unsigned long long)y * width + x;
+    spp_map[o] = uint32_t(gathered_aux[src * 4 + 3]);
+    for (int ch = 0; ch < 3; ++ch) stderr_map[o * 3ull + ch] = gathered_aux[src * 4 + ch];
+}
+
 // Debug probe: lane 0 walks one sample's path (rt_core.hpp probe_path) — the device half of the per-bounce CPU-vs-GPU vector tests.
 template <typename R>
 __global__ void probe_path_kernel(SceneView<R> sc, CameraRec<R> cam, RenderConsts rc, R t_min, uint32_t px, uint32_t row,

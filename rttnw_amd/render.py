@@ -62,6 +62,29 @@ def render_adaptive(scene, cam, params, pass_spp=64, rel_error=0.02, abs_error=0
     return lin, rgba, spp, se, st
 
 
+def render_adaptive_multi(scene, cam, params, device_ids, pass_spp=64, rel_error=0.02, abs_error=0.0):
+    """`rttnw_render_adaptive_multi`: `render_adaptive` over the GPUs (or logical ranks) of `device_ids`, bit-identical outputs; the same
+    `spp_chunk` default.  Returns (linear HxWx3 f64, rgba8 HxWx4 u8, spp_map HxW u32, stderr HxWx3 f64, [Stats per rank])."""
+    import copy
+    b = library.product()
+    p = copy.copy(params)
+    if p.spp_chunk == 0:
+        p.spp_chunk = max(1, pass_spp // 16)
+    h, w = p.height, p.width
+    lin = np.zeros((h, w, 3), dtype=np.float64)
+    rgba = np.zeros((h, w, 4), dtype=np.uint8)
+    spp = np.zeros((h, w), dtype=np.uint32)
+    se = np.zeros((h, w, 3), dtype=np.float64)
+    n = len(device_ids)
+    ids = (C.c_int32 * n)(*device_ids)
+    st = (Stats * n)()
+    a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
+    rc = b.render_adaptive_multi(scene.handle, C.byref(cam), C.byref(p), C.byref(a), n, ids, lin.ctypes.data, rgba.ctypes.data,
+                                 spp.ctypes.data, se.ctypes.data, C.cast(st, C.c_void_p))
+    check(rc, b, "rttnw_render_adaptive_multi")
+    return lin, rgba, spp, se, list(st)
+
+
 def render_features(scene, cam, params):
     """`rttnw_render_features`: the first hit of the render's own camera rays, averaged over `params.spp` samples per pixel.
     Returns {"albedo": HxWx3, "normal": HxWx3, "depth": HxW, "alpha": HxW (all f64), "stats": Stats}."""
