@@ -169,6 +169,25 @@ impl Scene {
         ok(unsafe { ffi::rttnw_render_adaptive_multi(self.raw, cam, p, a, devices.len() as u32, devices.as_ptr(), ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), stats.as_mut_ptr()) })?;
         Ok((rgba, spp, stderr, stats))
     }
+    /// The adaptive render begun from `state` (what an earlier call returned; `None`: a fresh render) and continued under `a` and the cap `p.spp`
+    /// (`rttnw_render_adaptive_resume`): with a cap and tolerances no looser than the state's, bit for bit the render that was never interrupted.
+    /// `devices` empty: the scene's device, one stats record; otherwise the ranks of `render_adaptive_multi`.  The state does not identify the
+    /// scene: resume on the scene it was made on.  Returns (RGBA8, samples per pixel, standard errors, stats, the state to resume from).
+    pub fn render_adaptive_resume(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, a: &ffi::rttnw_adaptive, devices: &[i32], state: Option<&[f64]>) -> Result<(Vec<u8>, Vec<u32>, Vec<f64>, Vec<ffi::rttnw_stats>, Vec<f64>)> {
+        let n = p.width as usize * p.height as usize;
+        let doubles = unsafe { ffi::rttnw_adaptive_state_doubles(p.width, p.height) } as usize;
+        if state.map_or(false, |s| s.len() != doubles) {
+            return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "render_adaptive_resume: the state does not have the frame's size".into() });
+        }
+        let mut rgba = vec![0u8; n * 4];
+        let mut spp = vec![0u32; n];
+        let mut stderr = vec![0f64; n * 3];
+        let mut stats = vec![ffi::rttnw_stats::default(); devices.len().max(1)];
+        let mut out = vec![0f64; doubles];
+        let ids = if devices.is_empty() { ptr::null() } else { devices.as_ptr() };
+        ok(unsafe { ffi::rttnw_render_adaptive_resume(self.raw, cam, p, a, devices.len() as u32, ids, state.map_or(ptr::null(), |s| s.as_ptr()), out.as_mut_ptr(), ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), stats.as_mut_ptr()) })?;
+        Ok((rgba, spp, stderr, stats, out))
+    }
     /// First-hit feature buffers of the frame `render` renders (`rttnw_render_features`), row-major, top row first.
     pub fn render_features(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params) -> Result<Features> {
         let n = p.width as usize * p.height as usize;

@@ -40,8 +40,9 @@ extern "C" {
 #define RTTNW_ABI_VERSION 3 /* 2: 4-wide node records (n_nodes, debug_scene_nodes4), rttnw_render_multi
                              * 3: RTTNW_F64_STRICT, rttnw_shutdown, RTTNW_BVH_AUTO (the default builder), rttnw_stats.reserved is a bit mask
                              *    (below), validate() rejects t_min < 0
-                             * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region and rttnw_render_adaptive_multi
-                             *  came later, without a version bump: a caller detects each by its symbol) */
+                             * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region, rttnw_render_adaptive_multi and
+                             *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles came later, without a version bump: a caller detects
+                             *  each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -411,6 +412,69 @@ int rttnw_render_adaptive_multi(rttnw_scene* s, const rttnw_camera_desc* cam, co
                                 uint32_t ngpu, const int32_t* device_ids,
                                 double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb,
                                 rttnw_stats* stats);
+
+/* An adaptive render that can be taken up again: rttnw_render_adaptive / rttnw_render_adaptive_multi begun from, and left as, a STATE — a preview at
+ * 5 % noise refined to 2 %, a cap that turned out too low raised, a long render that survives its process — without retracing a sample.
+ * (Came without a version bump, like rttnw_render_adaptive: detect it by its symbol.)
+ *
+ * The state is a host array of rttnw_adaptive_state_doubles(width, height) = 64 + 12 * width * height doubles; every integer in it is exact.
+ *   Header, doubles [0, 64), unused entries 0:
+ *     [0] RTTNW_ADAPTIVE_STATE_MAGIC   [1] RTTNW_ADAPTIVE_STATE_VERSION   [2] width   [3] height   [4] a->pass_spp
+ *     [5] p->spp_chunk as the caller passed it (0 allowed)   [6] sample_begin   [7] precision   [8] max_depth   [9] quirks
+ *     [10], [11] the low and the high 32 bits of seed   [12] t_min   [13..15] background   [16..30] the 15 doubles of rttnw_camera_desc, in field order
+ *   Per pixel, 12 doubles, row-major, top row first, the pixels of the image only:
+ *     [0..2] sum r, g, b   the running chunk-sum chain in the kernel's arithmetic type, widened to double (exact for RTTNW_F32: it narrows back exactly)
+ *     [3]    n             samples folded (n_q)
+ *     [4..6] mu r, g, b    the weighted mean of the chunk means (rttnw_render_adaptive's "Noise estimate")
+ *     [7]    k             chunks folded: (n / B) * the chunks of a pass of B samples under spp_chunk (spp_chunk c != 0: ceil(B / c); 0, the default
+ *                          schedule: with tail = B below 32 ? B : B / 32 and main = (B - tail) / 4, main + (B - 4 main) — B = 32: 11, B = 16: 16)
+ *     [8..10] m2 r, g, b   M2 = sum_c n_c (m_c - mu)^2
+ *     [11]   0
+ *   The state holds neither the tolerances nor the cap: those may change from call to call.  It does NOT identify the scene — nothing in it is
+ *   derived from the scene — so the caller resumes on the scene it started on; resuming on another is not detected and renders a mixture.
+ * Where it runs.  ngpu == 0 with device_ids == NULL: the scene's device, as rttnw_render_adaptive (`stats`: one record; tile_world must be 1).
+ *   ngpu 1 .. 64: rttnw_render_adaptive_multi's ranks, gather transports and environment (`stats`: ngpu records; tile_rank / tile_world ignored).
+ * state_in == NULL.  The four outputs and `stats` are rttnw_render_adaptive's (ngpu == 0) or rttnw_render_adaptive_multi's, BIT FOR BIT, and the state
+ *   the render ends in is written to state_out (optional).
+ * state_in != NULL.  Every pixel q starts from its record: sum, noise state and n_q samples.  Its active bit is decided anew under THIS call's
+ *   tolerances and cap, by the expression that ends a pass (value = sum / n_q in the kernel's type, then the stopping rule).  Passes go by LEVEL:
+ *   level k traces samples [sample_begin + kB, sample_begin + (k+1)B) of the pixels that are active and have n_q == kB, over the list of their 2x2
+ *   blocks — the jobs rttnw_render(spp = B, sample_begin = sample_begin + kB) runs for them.  Levels run from the lowest n_q / B of the state to
+ *   spp / B - 1; a level nobody stands at costs its list build and is skipped, and the loop ends once no pixel is active at any level.  In the
+ *   node-wide form every rank works at the same level, each level enqueued on all live ranks before the host waits for any.
+ * Contract.  Let S be the state of a run with cap C1 and tolerances (rel1, abs1).  Resumed with a cap C2 >= C1 and tolerances rel2 <= rel1,
+ *   abs2 <= abs1, the four outputs and state_out are BIT-IDENTICAL to those of ONE call with state_in == NULL, cap C2 and (rel2, abs2) — for every
+ *   `precision`, every kernel form, every launch split (RTTNW_CHUNK_SUM_BUDGET), every ngpu and device list on either side of the hand-over (the
+ *   state is row-major: begun on one GPU it continues on eight, and the reverse) and both gather transports.  Why: a pixel's samples are keyed by
+ *   (pixel, sample, seed), its sum is one chain in chunk order and its stopping decision reads its own chunk sums only; a tighter rule and a
+ *   higher cap can only stop a pixel LATER, so no pixel of S holds more samples than the uninterrupted run would have given it, and the passes
+ *   that remain are the ones that run had left.  With a LOOSER tolerance or a lower cap than the state was made under the call is still well
+ *   defined — a pixel keeps what it has and goes on only if it is active — but no longer equal to a fresh render: pixels may hold more samples
+ *   than the looser rule would have given them.
+ * No work.  When no pixel is active: RTTNW_OK, no trace kernel is launched, stats->samples == 0, the outputs are those of the state's own run.
+ * Outputs as rttnw_render_adaptive (each optional), and state_out (optional; state_in and state_out may be the SAME array).  `stats` (optional):
+ *   samples = what THIS call traced, not the state's (node-wide: per rank; over the ranks it is sum(out_spp) minus the state's n summed),
+ *   kernel_ms = device time of everything the call runs, the state's copy to the device and its conversion both ways included; reserved and the
+ *   scene's sizes as for rttnw_render_adaptive.  Apart from the state's copies and the one 8-byte copy per pass, no host round trip.  Blocking.
+ * Refusals, before the device is touched, in this order, each message naming render_adaptive_resume and the field:
+ *   1. RTTNW_ERR_INVALID for a NULL p or a;
+ *   2. RTTNW_ERR_INVALID for ngpu > 64, ngpu >= 1 with a NULL device_ids, ngpu == 0 with a non-NULL device_ids;
+ *   3. what rttnw_render_adaptive refuses among its own arguments, with its codes (its tile_world rule with ngpu == 0 only);
+ *   4. with a state_in, RTTNW_ERR_INVALID for a wrong magic number or version; for a header field that differs — compared bitwise — from this
+ *      call's: width, height, pass_spp, spp_chunk, sample_begin, precision, max_depth, quirks, seed, t_min, background, the camera's 15 doubles;
+ *      and (unless width or height is 0: the records are then not looked at) for a record whose n or k is not a finite integer, n < B, n not a
+ *      multiple of B, n > p->spp ("the state holds more samples than the cap"), or k != (n / B) * the chunks of a pass;
+ *   5. whatever rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes);
+ *   6. with ngpu >= 1, RTTNW_ERR_INVALID for a device id outside [0, rttnw_device_count()). */
+#define RTTNW_ADAPTIVE_STATE_MAGIC 1381256791u /* 0x52544E57, "RTNW" */
+#define RTTNW_ADAPTIVE_STATE_VERSION 1u
+#define RTTNW_ADAPTIVE_STATE_HEADER 64u /* doubles before the first record */
+#define RTTNW_ADAPTIVE_STATE_RECORD 12u /* doubles per pixel */
+uint64_t rttnw_adaptive_state_doubles(uint32_t width, uint32_t height);
+int rttnw_render_adaptive_resume(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
+                                 uint32_t ngpu, const int32_t* device_ids, const double* state_in, double* state_out,
+                                 double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb,
+                                 rttnw_stats* stats);
 
 /* Device-resident form, asynchronous on `hip_stream` (a hipStream_t; NULL = default stream).
  * Traces the tiles owned by (tile_rank, tile_world) and writes them in packed order into

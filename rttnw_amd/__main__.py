@@ -11,6 +11,9 @@ PREFIX_albedo.png, PREFIX_normal.png (n * 0.5 + 0.5), PREFIX_depth.png (normalis
 not combine with --noise, --denoise, --features or --passes.
 --devices 0,1,2,... renders on those GPUs of the node (a device may repeat: logical ranks on one GPU): rttnw_render_multi, or with --noise
 rttnw_render_adaptive_multi — the same image either way.  It does not combine with --window, --features, --denoise or --passes.
+--save-state FILE and --resume FILE (with --noise only; they combine with --devices): the adaptive render leaves its state — the double array of
+rttnw_render_adaptive_resume, as .npy — in FILE, and starts from the state in FILE: a preview refined under a tighter --noise or a higher --spp
+without retracing a sample, on the same scene, size, seed and --pass-spp.  They do not combine with --window or --passes.
 """
 import argparse
 import sys
@@ -78,6 +81,8 @@ def main(argv=None):
                     "and write that window as the image")
     ap.add_argument("--devices", default=None, metavar="D0,D1,...", help="render on these GPUs of the node (repeats allowed: logical ranks); "
                     "with --noise the adaptive render runs across them")
+    ap.add_argument("--save-state", default=None, metavar="FILE", help="adaptive sampling: leave the render's state in FILE (.npy) for a later --resume")
+    ap.add_argument("--resume", default=None, metavar="FILE", help="adaptive sampling: start from the state in FILE instead of from nothing")
     try:
         args = ap.parse_args(argv)
     except SystemExit:
@@ -93,6 +98,16 @@ def main(argv=None):
                                        ("--passes", args.passes > 1)) if on]
         if clash:
             print("--devices does not combine with %s: it runs the plain and the adaptive render only" % ", ".join(clash), file=sys.stderr)
+            return 1
+    for flag, value in (("--resume", args.resume), ("--save-state", args.save_state)):
+        if value is None:
+            continue
+        if args.noise is None:
+            print("%s needs --noise: only the adaptive render has a state" % flag, file=sys.stderr)
+            return 1
+        clash = [name for name, on in (("--window", args.window is not None), ("--passes", args.passes > 1)) if on]
+        if clash:
+            print("%s does not combine with %s" % (flag, ", ".join(clash)), file=sys.stderr)
             return 1
     window = None
     if args.window is not None:
@@ -172,7 +187,25 @@ def main(argv=None):
             print("cap %d spp rounded up to %d, a multiple of --pass-spp %d" % (p.spp, cap, args.pass_spp))
             p.spp = cap
         per_rank = ""
-        if devices is not None:
+        if args.resume is not None or args.save_state is not None:
+            state = None
+            if args.resume is not None:
+                try:
+                    state = np.load(args.resume)
+                except (OSError, ValueError) as e:
+                    print("--resume %s: %s" % (args.resume, e), file=sys.stderr)
+                    return 1
+            lin, rgba, spp_map, se, sts, state = render.render_adaptive_resume(sc, cam, p, state, devices, args.pass_spp, args.noise, args.abs_noise,
+                                                                               want_state=args.save_state is not None)
+            if devices is not None:
+                st = abi.Stats(samples=sum(x.samples for x in sts), kernel_ms=node_ms(devices, sts))
+                per_rank = "; per rank: %s" % " ".join(str(x.samples) for x in sts)
+            else:
+                st = sts
+            if args.save_state is not None:
+                with open(args.save_state, "wb") as f:    # (an open file: np.save would append .npy to a bare name)
+                    np.save(f, state)
+        elif devices is not None:
             lin, rgba, spp_map, se, sts = render.render_adaptive_multi(sc, cam, p, devices, args.pass_spp, args.noise, args.abs_noise)
             st = abi.Stats(samples=sum(x.samples for x in sts), kernel_ms=node_ms(devices, sts))
             per_rank = "; per rank: %s" % " ".join(str(x.samples) for x in sts)

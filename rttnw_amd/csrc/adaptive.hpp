@@ -34,6 +34,9 @@ struct AdaptivePixel {
     uint32_t k;   // chunks folded (K)
 };
 
+// Doubles of a pixel's record in the state of rttnw_render_adaptive_resume (include/rttnw_hip.h): its running sum r, g, b, then n, mu[3], k, m2[3], 0
+constexpr uint32_t STATE_RECORD_DOUBLES = 12;
+
 // Fold one chunk: its mean m[3] over n_c >= 1 samples.
 RT_HD void adaptive_fold(AdaptivePixel& a, const double m[3], uint32_t n_c) {
     const uint32_t n_new = a.n + n_c;

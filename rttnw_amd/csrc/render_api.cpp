@@ -409,8 +409,9 @@ struct MultiPlan {
     DeviceState* root = nullptr;
     size_t rsz = 0, chunk = 0, npx = 0;   // bytes of a real, of a rank's packed tiles; pixels of the image
     size_t aux_chunk = 0;                 // rttnw_render_adaptive_multi: bytes of a rank's auxiliary records, which travel with its tiles (0: a plain render)
-    bool transport() const { return devices.size() > 1 || env.force_transport; }         // some rank's tiles travel
-    bool local(uint32_t r) const { return !env.force_transport && ranks[r].dev == 0; }    // rank r's do not: a copy on the root's device
+    bool single = false;                  // rttnw_render_adaptive_resume with ngpu == 0: one rank on the scene's own device, which reads no gather environment
+    bool transport() const { return !single && (devices.size() > 1 || env.force_transport); } // some rank's tiles travel
+    bool local(uint32_t r) const { return single || (!env.force_transport && ranks[r].dev == 0); } // rank r's do not: a copy on the root's device
     uint8_t* packed(uint32_t r) const { return ranks[r].d->multi_packed.p + chunk * ranks[r].slot; } // rank r's packed tiles, on its device
     uint8_t* gathered(uint32_t r) const { return root->gathered.p + chunk * r; }                      // ... and their place on the root's
     uint8_t* aux(uint32_t r) const { return ranks[r].d->multi_aux.p + aux_chunk * ranks[r].slot; }    // the same for its auxiliary records
@@ -636,17 +637,85 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
 // rttnw_render_adaptive_multi: rttnw_render_adaptive over the ranks of rttnw_render_multi (include/rttnw_hip.h has the contract, DESIGN.md §10a the
 // why).  Rank r runs render_adaptive_t's passes over ITS tiles — render_tiles_t with tile_rank = r — but the loop is pass-major, rank-minor: a pass
 // is enqueued on every live rank's stream before the host waits for any of them, so the devices of a node work side by side.
+// rttnw_render_adaptive_resume is the same render begun from, and left as, a state (adaptive_node_render runs both): its passes go by LEVEL, the
+// number of passes a pixel has behind it.
 // ---------------------------------------------------------------------------------------------
 namespace rt {
+// ---- the state of rttnw_render_adaptive_resume on the host (include/rttnw_hip.h has the layout): its header, its checks, and the permutation between
+// its row-major records and the ranks' packed order
+constexpr uint32_t STATE_HEADER_DOUBLES = RTTNW_ADAPTIVE_STATE_HEADER, STATE_HEADER_FIELDS = 31;
+static_assert(STATE_RECORD_DOUBLES == RTTNW_ADAPTIVE_STATE_RECORD, "the kernels' record is the header's");
+static const char* const STATE_FIELD_NAMES[STATE_HEADER_FIELDS] = {
+    "magic", "version", "width", "height", "pass_spp", "spp_chunk", "sample_begin", "precision", "max_depth", "quirks", "seed", "seed", "t_min",
+    "background", "background", "background", "camera lookfrom", "camera lookfrom", "camera lookfrom", "camera lookat", "camera lookat", "camera lookat",
+    "camera view_up", "camera view_up", "camera view_up", "camera vertical_fov", "camera aspect_ratio", "camera aperture", "camera focus_distance",
+    "camera open_time", "camera close_time"};
+// The header this call's arguments make (cam == nullptr: validate() refuses the call next; its camera fields are then not compared)
+static void state_header(const rttnw_params& p, const rttnw_adaptive& a, const rttnw_camera_desc* cam, double h[STATE_HEADER_DOUBLES]) {
+    std::fill(h, h + STATE_HEADER_DOUBLES, 0.0);
+    h[0] = double(RTTNW_ADAPTIVE_STATE_MAGIC); h[1] = double(RTTNW_ADAPTIVE_STATE_VERSION);
+    h[2] = p.width; h[3] = p.height; h[4] = a.pass_spp; h[5] = p.spp_chunk; h[6] = p.sample_begin; h[7] = p.precision; h[8] = p.max_depth; h[9] = p.quirks;
+    h[10] = double(uint32_t(p.seed)); h[11] = double(uint32_t(p.seed >> 32));
+    h[12] = p.t_min;
+    for (int k = 0; k < 3; ++k) h[13 + k] = p.background[k];
+    static_assert(sizeof(rttnw_camera_desc) == 15 * sizeof(double), "the state's header holds the camera as 15 doubles");
+    if (cam) std::memcpy(h + 16, cam, sizeof(*cam));
+}
+// Where a call's level loop starts, and up to which level each rank must look even when a list comes back empty (a fresh render: level 0 only)
+struct LevelPlan {
+    bool resumed = false;
+    uint32_t first = 0;         // the lowest level n / B a pixel of the state stands at
+    std::vector<uint32_t> last; // per rank: the highest
+};
+// What rttnw_render_adaptive_resume refuses of a state_in (p and a have passed refuse_adaptive_misuse); `first`: the lowest level in it
+static int refuse_state_misuse(const rttnw_params& p, const rttnw_adaptive& a, const rttnw_camera_desc* cam, const double* st, uint32_t& first) {
+    const std::string call = "render_adaptive_resume: state_in: ";
+    double want[STATE_HEADER_DOUBLES];
+    state_header(p, a, cam, want);
+    for (uint32_t i = 0; i < (cam ? STATE_HEADER_FIELDS : 16u); ++i) {
+        if (std::memcmp(&st[i], &want[i], sizeof(double)) == 0) continue;
+        set_last_error(call + (i == 0 ? "wrong magic number: not a state of this library" : i == 1 ? "unknown format version"
+                                      : std::string(STATE_FIELD_NAMES[i]) + " differs from this call's"));
+        return RTTNW_ERR_INVALID;
+    }
+    first = 0;
+    if (!p.width || !p.height) return 0; // (validate() refuses the call next)
+    RenderConsts rc{};
+    plan_chunks(rc, a.pass_spp, p.spp_chunk);
+    const double B = a.pass_spp, cap = p.spp, chunks = rc.n_chunks;
+    const auto whole = [](double v) { return v >= 0.0 && v <= 4294967295.0 && v == std::floor(v); }; // (false for NaN and the infinities)
+    double lowest = cap;
+    const size_t npx = size_t(p.width) * p.height;
+    for (size_t q = 0; q < npx; ++q) {
+        const double n = st[STATE_HEADER_DOUBLES + q * STATE_RECORD_DOUBLES + 3], k = st[STATE_HEADER_DOUBLES + q * STATE_RECORD_DOUBLES + 7];
+        const char* why = !whole(n) ? "a record's n is not a finite integer" : !whole(k) ? "a record's k is not a finite integer"
+                        : n < B ? "a record's n is below pass_spp" : std::fmod(n, B) != 0.0 ? "a record's n is not a multiple of pass_spp"
+                        : n > cap ? "the state holds more samples than the cap (a record's n exceeds spp)"
+                        : k != n / B * chunks ? "a record's k is not its passes times the chunks of a pass" : nullptr;
+        if (why) { set_last_error(call + why + " (pixel " + std::to_string(q) + ")"); return RTTNW_ERR_INVALID; }
+        lowest = std::min(lowest, n);
+    }
+    first = uint32_t(lowest / B);
+    return 0;
+}
+// Packed index of framebuffer pixel (x, y) on its owner among `world` ranks (rt_core.hpp tile_permuted; rttnw_amd/tiles.py packed_index)
+static inline void packed_place(uint32_t x, uint32_t y, const rttnw_tile_layout& L, uint32_t world, uint32_t& owner, size_t& idx) {
+    const uint32_t permuted = tile_permuted(x >> 3, y >> 3, L.tiles_x);
+    owner = permuted % world;
+    idx = size_t(permuted / world) * 64 + ((y & 7u) << 3) + (x & 7u);
+}
 // Where rank r keeps what lives across its passes: slots of its device's buffers, like MultiPlan::packed
 struct AdaptiveSlots {
     rttnw_tile_layout L;
     size_t state_chunk = 0, active_chunk = 0, list_chunk = 0; // bytes of a rank's noise state, active bytes, list + scan
+    size_t records_chunk = 0;                                 // rttnw_render_adaptive_resume: bytes of a rank's packed state records
     uint32_t tiles(uint32_t r, uint32_t world) const { return L.n_tiles > r ? (L.n_tiles - r + world - 1) / world : 0; } // the tiles rank r owns (base_consts' my_tiles)
     AdaptivePixel* state(const MultiPlan& m, uint32_t r) const { return (AdaptivePixel*)(m.ranks[r].d->multi_ad_state.p + state_chunk * m.ranks[r].slot); }
     uint8_t* active(const MultiPlan& m, uint32_t r) const { return m.ranks[r].d->multi_ad_active.p + active_chunk * m.ranks[r].slot; }
     uint32_t* quads(const MultiPlan& m, uint32_t r) const { return (uint32_t*)(m.ranks[r].d->multi_list.p + list_chunk * m.ranks[r].slot); }
     uint32_t* scan(const MultiPlan& m, uint32_t r) const { return quads(m, r) + size_t(L.tiles_per_rank) * 16; }
+    double* records(const MultiPlan& m, uint32_t r) const { return (double*)(m.ranks[r].d->multi_ad_records.p + records_chunk * m.ranks[r].slot); }
+    uint8_t* marks(const MultiPlan& m, uint32_t r) const { return m.ranks[r].d->multi_ad_marks.p + active_chunk * m.ranks[r].slot; }
 };
 static ListPass adaptive_rank_pass(const MultiPlan& m, const AdaptiveSlots& sl, uint32_t r, const rttnw_params& p, const rttnw_adaptive& a) {
     ListPass ad;
@@ -660,8 +729,9 @@ static ListPass adaptive_rank_pass(const MultiPlan& m, const AdaptiveSlots& sl, 
 
 // multi_prepare for the adaptive passes: every buffer of every rank, and what a first use brings for pass 0 AND for a refinement pass over all of
 // the rank's blocks — a list never holds more, so no later pass allocates (a hipMalloc between two ranks' launches would synchronise the device)
+// (`resumed`: the render starts from a state, so it has no pass 0; `records`: a state comes in or goes out)
 static int adaptive_multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const MultiPlan& m,
-                                  const AdaptiveSlots& sl) {
+                                  const AdaptiveSlots& sl, bool resumed = false, bool records = false) {
     if (int rc = multi_prepare_buffers(m)) return rc;
     for (size_t k = 0; k < m.devices.size(); ++k) {
         DeviceState* d = m.dev_state[k];
@@ -670,6 +740,8 @@ static int adaptive_multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam
         HIP_TRY(d->multi_ad_active.grow(sl.active_chunk * m.dev_ranks[k]));
         HIP_TRY(d->multi_list.grow(sl.list_chunk * m.dev_ranks[k]));
         HIP_TRY(d->multi_aux.grow(m.aux_chunk * m.dev_ranks[k]));
+        if (records) HIP_TRY(d->multi_ad_records.grow(sl.records_chunk * m.dev_ranks[k]));
+        if (resumed) HIP_TRY(d->multi_ad_marks.grow(sl.active_chunk * m.dev_ranks[k]));
     }
     DeviceState* root = m.root;
     HIP_TRY(hipSetDevice(root->device));
@@ -682,7 +754,8 @@ static int adaptive_multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam
         pr.tile_rank = r;
         DeviceState* d = m.ranks[r].d;
         ListPass ad = adaptive_rank_pass(m, sl, r, p, a);
-        if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), d->stream.get(), nullptr, false, true, &ad)) return rc;
+        if (!resumed)
+            if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), d->stream.get(), nullptr, false, true, &ad)) return rc;
         ad.quads = sl.quads(m, r);
         ad.n_quads = sl.tiles(r, p.tile_world) * 16u;
         ad.first = false;
@@ -697,62 +770,210 @@ struct HostFree { void operator()(void* q) const { (void)hipHostFree(q); } };
 // The passes.  Per pass and live rank, on its device's stream between its two events: the trace launches and the adaptive resolve (render_tiles_t),
 // the list of its blocks that still hold an active pixel — what its NEXT pass traces, in its own slot — and a copy of the list's two totals into
 // the rank's pinned words.  Only then does the host wait, once per device, and read the totals: a rank whose list is empty takes no further part.
-// `ms`: the ranks' device time so far; `refined`: samples they traced beyond pass 0.
+// A render begun from a state (lv.resumed) has pixels at several LEVELS (passes behind them), and level k traces the active pixels that stand at it:
+// the step before the loop brings every rank's records in (`upload`: per rank, in its packed order) and lists level lv.first; each list is then
+// made of the level's marks (adaptive_level_select_kernel) instead of the active bytes, a rank with an empty list stays in the loop while its
+// state holds pixels at a higher level, and a rank with nothing to trace at a level launches no trace kernel.  A fresh render is the case of one
+// level: the launches it always had.
+// `ms`: the ranks' device time so far; `refined`: samples they traced beyond a fresh render's pass 0.
 static int adaptive_multi_passes(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const MultiPlan& m,
-                                 const AdaptiveSlots& sl, std::vector<Event>& ev, uint32_t* counts, rttnw_stats* stats, std::vector<double>& ms,
-                                 std::vector<uint64_t>& refined) {
+                                 const AdaptiveSlots& sl, const LevelPlan& lv, const std::vector<std::vector<double>>& upload, std::vector<Event>& ev,
+                                 uint32_t* counts, rttnw_stats* stats, std::vector<double>& ms, std::vector<uint64_t>& refined) {
     const uint32_t ngpu = uint32_t(m.ranks.size()), n_passes = p.spp / a.pass_spp;
     std::vector<uint32_t> n_quads(ngpu, 0);
     std::vector<char> live(ngpu);
     for (uint32_t r = 0; r < ngpu; ++r) live[r] = sl.tiles(r, ngpu) != 0;
     rttnw_params pr = p;
     pr.spp = a.pass_spp;
-    for (uint32_t k = 0; k < n_passes; ++k) {
-        const bool more = k + 1 < n_passes; // the cap ends the loop: no list behind the last pass
-        pr.sample_begin = p.sample_begin + k * a.pass_spp;
-        std::vector<char> dev_live(m.devices.size(), 0);
-        for (uint32_t r = 0; r < ngpu; ++r) {
-            if (!live[r]) continue;
-            DeviceState* d = m.ranks[r].d;
-            const hipStream_t stream = d->stream.get();
-            HIP_TRY(hipSetDevice(d->device));
-            dev_live[m.ranks[r].dev] = 1;
-            pr.tile_rank = r;
-            ListPass ad = adaptive_rank_pass(m, sl, r, p, a);
-            if (k > 0) { ad.quads = sl.quads(m, r); ad.n_quads = n_quads[r]; ad.first = false; }
-            HIP_TRY(hipEventRecord(ev[2 * r].get(), stream));
-            // (pass 0 fills stats[r] as a plain render of the rank does: kernel form, scene sizes, the samples of its pixels)
-            if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), stream, k == 0 && stats ? &stats[r] : nullptr, false, false, &ad)) return rc;
-            if (more) {
-                uint32_t* scan = sl.scan(m, r);
-                const uint32_t n_blocks = sl.tiles(r, ngpu) * 16u; // (its own tiles only: no pass writes the active bytes of a pad tile)
-                if (int rc = RT_BY_PRECISION(p.precision, enqueue_quad_list, ad.active, n_blocks, scan, sl.quads(m, r), stream)) return rc;
-                HIP_TRY(hipMemcpyAsync(counts + 2 * r, quad_list_totals(scan, n_blocks), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            }
-            HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), stream));
+    // on rank r's stream: the list of what it traces at `level`, and the copy of the list's totals
+    const auto enqueue_list = [&](uint32_t r, uint32_t level, hipStream_t stream) -> int {
+        uint32_t* scan = sl.scan(m, r);
+        const uint32_t n_blocks = sl.tiles(r, ngpu) * 16u; // (its own tiles only: no pass writes the active bytes of a pad tile)
+        const uint8_t* marks = sl.active(m, r);
+        if (lv.resumed) {
+            if (int rc = RT_BY_PRECISION(p.precision, adaptive_level_select_launch, marks, sl.state(m, r), sl.marks(m, r), n_blocks * 4u,
+                                         level * a.pass_spp, stream)) return rc;
+            marks = sl.marks(m, r);
         }
+        if (int rc = RT_BY_PRECISION(p.precision, enqueue_quad_list, marks, n_blocks, scan, sl.quads(m, r), stream)) return rc;
+        HIP_TRY(hipMemcpyAsync(counts + 2 * r, quad_list_totals(scan, n_blocks), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        return 0;
+    };
+    // the host waits for the step just enqueued, once per device with a live rank, and reads what it left: device time and — `listed`: the step
+    // built the lists of `level` — the lists' totals.  Whether any rank goes on.
+    const auto wait_for_step = [&](bool listed, uint32_t level, bool& any) -> int {
+        std::vector<char> dev_live(m.devices.size(), 0);
+        for (uint32_t r = 0; r < ngpu; ++r)
+            if (live[r]) dev_live[m.ranks[r].dev] = 1;
         for (size_t dk = 0; dk < m.devices.size(); ++dk) {
             if (!dev_live[dk]) continue;
             HIP_TRY(hipSetDevice(m.devices[dk]));
             HIP_TRY(hipStreamSynchronize(m.dev_state[dk]->stream.get()));
         }
-        bool any = false;
+        any = false;
         for (uint32_t r = 0; r < ngpu; ++r) {
             if (!live[r]) continue;
             float t = 0;
             HIP_TRY(hipSetDevice(m.ranks[r].d->device));
             HIP_TRY(hipEventElapsedTime(&t, ev[2 * r].get(), ev[2 * r + 1].get()));
             ms[r] += t;
-            if (more) {
+            if (listed) {
                 n_quads[r] = counts[2 * r];
-                refined[r] += uint64_t(counts[2 * r + 1]) * a.pass_spp; // its active pixels: what its next pass traces
+                refined[r] += uint64_t(counts[2 * r + 1]) * a.pass_spp; // the pixels it lists: what its pass at `level` traces
             }
-            live[r] = more && n_quads[r] != 0;
+            live[r] = listed && (n_quads[r] != 0 || level < lv.last[r]);
             any = any || live[r];
         }
-        if (!any) break; // every pixel of every rank is done
+        return 0;
+    };
+    uint32_t k = lv.first;
+    bool any = true;
+    if (lv.resumed) { // the state comes in: records, conversion, and the list of the lowest level
+        for (uint32_t r = 0; r < ngpu; ++r) {
+            if (!live[r]) continue;
+            DeviceState* d = m.ranks[r].d;
+            const hipStream_t stream = d->stream.get();
+            HIP_TRY(hipSetDevice(d->device));
+            HIP_TRY(hipEventRecord(ev[2 * r].get(), stream));
+            HIP_TRY(hipMemcpyAsync(sl.records(m, r), upload[r].data(), upload[r].size() * sizeof(double), hipMemcpyHostToDevice, stream));
+            if (int rc = RT_BY_PRECISION(p.precision, adaptive_state_import_launch, sl.records(m, r), m.packed(r), sl.state(m, r), sl.active(m, r),
+                                         sl.L.pixels_per_rank, p.spp, a.rel_error, a.abs_error, stream)) return rc;
+            if (k < n_passes)
+                if (int rc = enqueue_list(r, k, stream)) return rc;
+            HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), stream));
+        }
+        if (int rc = wait_for_step(k < n_passes, k, any)) return rc;
+    }
+    for (; k < n_passes && any; ++k) {
+        const bool more = k + 1 < n_passes; // the cap ends the loop: no list behind the last pass
+        pr.sample_begin = p.sample_begin + k * a.pass_spp;
+        for (uint32_t r = 0; r < ngpu; ++r) {
+            if (!live[r]) continue;
+            DeviceState* d = m.ranks[r].d;
+            const hipStream_t stream = d->stream.get();
+            HIP_TRY(hipSetDevice(d->device));
+            pr.tile_rank = r;
+            ListPass ad = adaptive_rank_pass(m, sl, r, p, a);
+            const bool pass0 = !lv.resumed && k == 0;
+            if (!pass0) { ad.quads = sl.quads(m, r); ad.n_quads = n_quads[r]; ad.first = false; }
+            HIP_TRY(hipEventRecord(ev[2 * r].get(), stream));
+            // (pass 0 fills stats[r] as a plain render of the rank does: kernel form, scene sizes, the samples of its pixels)
+            if (pass0 || ad.n_quads != 0)
+                if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), stream, pass0 && stats ? &stats[r] : nullptr, false, false, &ad)) return rc;
+            if (more)
+                if (int rc = enqueue_list(r, k + 1, stream)) return rc;
+            HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), stream));
+        }
+        if (int rc = wait_for_step(more, k + 1, any)) return rc; // (no rank goes on: every pixel of every rank is done)
     }
     return 0;
+}
+
+// The render behind rttnw_render_adaptive_multi and rttnw_render_adaptive_resume, its arguments checked by them (`p`: tile_world = the number of
+// ranks; `single`: rttnw_render_adaptive_resume's ngpu == 0, one rank on the scene's own device).  state_in / state_out (each optional): the
+// render starts from, and leaves, a state (include/rttnw_hip.h); without a state_in it is the fresh render, launch for launch.
+static int adaptive_node_render(const char* call, ::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive* a,
+                                uint32_t ngpu, const int32_t* device_ids, bool single, const double* state_in, uint32_t first_level, double* state_out,
+                                double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, rttnw_stats* stats) {
+    DeviceGuard restore; // (the caller's device is current again after EVERY return below, the error paths included)
+    MultiPlan m;
+    m.single = single;
+    if (int rc = multi_plan(s, p, ngpu, device_ids, m, call)) return rc;
+    if (m.env.gather_invalid && !single) { set_last_error(std::string(call) + ": RTTNW_MULTI_GATHER must be rccl or peer"); return RTTNW_ERR_INVALID; }
+    AdaptiveSlots sl;
+    fill_layout(p.width, p.height, ngpu, sl.L);
+    const auto padded = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+    sl.state_chunk = padded(size_t(sl.L.pixels_per_rank) * sizeof(AdaptivePixel));
+    sl.active_chunk = padded(sl.L.pixels_per_rank);
+    sl.list_chunk = padded((size_t(sl.L.tiles_per_rank) * 16 + quad_scan_words(sl.L.tiles_per_rank * 16u)) * sizeof(uint32_t));
+    sl.records_chunk = padded(size_t(sl.L.pixels_per_rank) * STATE_RECORD_DOUBLES * sizeof(double));
+    m.aux_chunk = size_t(sl.L.pixels_per_rank) * 4 * sizeof(double);
+    // a state_in: its row-major records to every rank's packed order, on the host (pixels outside the image and pad tiles keep zero records)
+    LevelPlan lv;
+    lv.resumed = state_in != nullptr;
+    lv.first = first_level;
+    lv.last.assign(ngpu, 0);
+    const size_t rank_doubles = size_t(sl.L.pixels_per_rank) * STATE_RECORD_DOUBLES;
+    std::vector<std::vector<double>> host_records(state_in || state_out ? ngpu : 0);
+    for (std::vector<double>& v : host_records) v.assign(rank_doubles, 0.0);
+    if (state_in)
+        for (uint32_t y = 0; y < p.height; ++y)
+            for (uint32_t x = 0; x < p.width; ++x) {
+                uint32_t owner;
+                size_t idx;
+                packed_place(x, y, sl.L, ngpu, owner, idx);
+                const double* rec = state_in + STATE_HEADER_DOUBLES + (size_t(y) * p.width + x) * STATE_RECORD_DOUBLES;
+                std::copy(rec, rec + STATE_RECORD_DOUBLES, host_records[owner].begin() + idx * STATE_RECORD_DOUBLES);
+                lv.last[owner] = std::max(lv.last[owner], uint32_t(rec[3]) / a->pass_spp);
+            }
+    // everything that allocates, before the first launch: buffers and workspaces, the ranks' events, their pinned words for the lists' totals
+    if (int rc = adaptive_multi_prepare(s, cam, p, *a, m, sl, lv.resumed, state_in || state_out)) return rc;
+    std::vector<Event> ev(size_t(ngpu) * 2);
+    for (uint32_t r = 0; r < ngpu; ++r) {
+        HIP_TRY(hipSetDevice(m.ranks[r].d->device));
+        HIP_TRY(create_event(ev[2 * r]));
+        HIP_TRY(create_event(ev[2 * r + 1]));
+    }
+    void* pinned = nullptr;
+    HIP_TRY(hipHostMalloc(&pinned, size_t(ngpu) * 2 * sizeof(uint32_t), hipHostMallocPortable));
+    std::unique_ptr<void, HostFree> counts(pinned);
+    std::memset(pinned, 0, size_t(ngpu) * 2 * sizeof(uint32_t));
+    if (stats) std::memset(stats, 0, size_t(ngpu) * sizeof(*stats)); // (a rank without a tile runs nothing and keeps zeros)
+    if (stats && lv.resumed) // no pass 0 fills them: the scene's sizes and the kernel form, no samples yet
+        for (uint32_t r = 0; r < ngpu; ++r) {
+            if (!sl.tiles(r, ngpu)) continue;
+            rttnw_params pr = p;
+            pr.tile_rank = r;
+            if (int rc = RT_BY_PRECISION(p.precision, adaptive_rank_stats_t, s, m.ranks[r].d, &pr, &stats[r])) return rc;
+        }
+    std::vector<double> ms(ngpu, 0.0);
+    std::vector<uint64_t> refined(ngpu, 0);
+    if (int rc = adaptive_multi_passes(s, cam, p, *a, m, sl, lv, host_records, ev, (uint32_t*)pinned, stats, ms, refined)) return rc;
+    // every rank's sums to means and auxiliary records (a rank without a tile: zeros), in its device time like adaptive_output_kernel in the single
+    // call's — and, before that, sums and noise state to its state records where the caller wants the state
+    for (uint32_t r = 0; r < ngpu; ++r) {
+        DeviceState* d = m.ranks[r].d;
+        HIP_TRY(hipSetDevice(d->device));
+        HIP_TRY(hipEventRecord(ev[2 * r].get(), d->stream.get()));
+        if (state_out)
+            if (int rc = RT_BY_PRECISION(p.precision, adaptive_state_export_launch, m.packed(r), sl.state(m, r), sl.records(m, r), sl.L.pixels_per_rank,
+                                         sl.tiles(r, ngpu) * 64u, d->stream.get())) return rc;
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_finish_launch, m.packed(r), sl.state(m, r), (double*)m.aux(r), sl.L.pixels_per_rank,
+                                     sl.tiles(r, ngpu) * 64u, d->stream.get())) return rc;
+        HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), d->stream.get()));
+    }
+    bool use_peer = false, fell_back = false;
+    if (int rc = multi_gather(m, use_peer, fell_back)) return rc;
+    if (int rc = multi_untile(p, m)) return rc;
+    for (uint32_t r = 0; r < ngpu && stats; ++r) {
+        float t = 0;
+        HIP_TRY(hipSetDevice(m.ranks[r].d->device));
+        HIP_TRY(hipEventElapsedTime(&t, ev[2 * r].get(), ev[2 * r + 1].get()));
+        stats[r].kernel_ms = ms[r] + t;
+        stats[r].samples += refined[r];
+    }
+    if (stats && use_peer) stats[0].reserved |= 0x100u | (fell_back ? 0x200u : 0u);
+    if (state_out) { // every stream has finished (multi_untile): the ranks' records come back and go to their row-major places behind the header
+        for (uint32_t r = 0; r < ngpu; ++r) {
+            HIP_TRY(hipSetDevice(m.ranks[r].d->device));
+            HIP_TRY(hipMemcpy(host_records[r].data(), sl.records(m, r), rank_doubles * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        state_header(p, *a, cam, state_out);
+        for (uint32_t y = 0; y < p.height; ++y)
+            for (uint32_t x = 0; x < p.width; ++x) {
+                uint32_t owner;
+                size_t idx;
+                packed_place(x, y, sl.L, ngpu, owner, idx);
+                const double* rec = host_records[owner].data() + idx * STATE_RECORD_DOUBLES;
+                std::copy(rec, rec + STATE_RECORD_DOUBLES, state_out + STATE_HEADER_DOUBLES + (size_t(y) * p.width + x) * STATE_RECORD_DOUBLES);
+            }
+    }
+    DeviceState* root = m.root;
+    HIP_TRY(hipSetDevice(root->device));
+    hipError_t e = hipSuccess;
+    if (out_spp) e = hipMemcpy(out_spp, root->ad_spp.p, m.npx * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_stderr_rgb) e = hipMemcpy(out_stderr_rgb, root->ad_stderr.p, m.npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    return copy_image_out(call, root->rgba, root->linear, p.precision, m.npx, out_rgba8, out_linear_rgb, e);
 }
 } // namespace rt
 
@@ -773,59 +994,39 @@ extern "C" int rttnw_render_adaptive_multi(rttnw_scene* s, const rttnw_camera_de
     const int n_dev = rttnw_device_count();
     for (uint32_t r = 0; r < ngpu; ++r)
         if (device_ids[r] < 0 || device_ids[r] >= n_dev) { set_last_error("render_adaptive_multi: no such device in device_ids"); return RTTNW_ERR_INVALID; }
-    DeviceGuard restore; // (the caller's device is current again after EVERY return below, the error paths included)
-    MultiPlan m;
-    if (int rc = multi_plan(s, p, ngpu, device_ids, m, "render_adaptive_multi")) return rc;
-    if (m.env.gather_invalid) { set_last_error("render_adaptive_multi: RTTNW_MULTI_GATHER must be rccl or peer"); return RTTNW_ERR_INVALID; }
-    AdaptiveSlots sl;
-    fill_layout(p.width, p.height, ngpu, sl.L);
-    const auto padded = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
-    sl.state_chunk = padded(size_t(sl.L.pixels_per_rank) * sizeof(AdaptivePixel));
-    sl.active_chunk = padded(sl.L.pixels_per_rank);
-    sl.list_chunk = padded((size_t(sl.L.tiles_per_rank) * 16 + quad_scan_words(sl.L.tiles_per_rank * 16u)) * sizeof(uint32_t));
-    m.aux_chunk = size_t(sl.L.pixels_per_rank) * 4 * sizeof(double);
-    // everything that allocates, before the first launch: buffers and workspaces, the ranks' events, their pinned words for the lists' totals
-    if (int rc = adaptive_multi_prepare(s, cam, p, *a, m, sl)) return rc;
-    std::vector<Event> ev(size_t(ngpu) * 2);
-    for (uint32_t r = 0; r < ngpu; ++r) {
-        HIP_TRY(hipSetDevice(m.ranks[r].d->device));
-        HIP_TRY(create_event(ev[2 * r]));
-        HIP_TRY(create_event(ev[2 * r + 1]));
-    }
-    void* pinned = nullptr;
-    HIP_TRY(hipHostMalloc(&pinned, size_t(ngpu) * 2 * sizeof(uint32_t), hipHostMallocPortable));
-    std::unique_ptr<void, HostFree> counts(pinned);
-    std::memset(pinned, 0, size_t(ngpu) * 2 * sizeof(uint32_t));
-    if (stats) std::memset(stats, 0, size_t(ngpu) * sizeof(*stats)); // (a rank without a tile runs nothing and keeps zeros)
-    std::vector<double> ms(ngpu, 0.0);
-    std::vector<uint64_t> refined(ngpu, 0);
-    if (int rc = adaptive_multi_passes(s, cam, p, *a, m, sl, ev, (uint32_t*)pinned, stats, ms, refined)) return rc;
-    // every rank's sums to means and auxiliary records (a rank without a tile: zeros), in its device time like adaptive_output_kernel in the single call's
-    for (uint32_t r = 0; r < ngpu; ++r) {
-        DeviceState* d = m.ranks[r].d;
-        HIP_TRY(hipSetDevice(d->device));
-        HIP_TRY(hipEventRecord(ev[2 * r].get(), d->stream.get()));
-        if (int rc = RT_BY_PRECISION(p.precision, adaptive_finish_launch, m.packed(r), sl.state(m, r), (double*)m.aux(r), sl.L.pixels_per_rank,
-                                     sl.tiles(r, ngpu) * 64u, d->stream.get())) return rc;
-        HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), d->stream.get()));
-    }
-    bool use_peer = false, fell_back = false;
-    if (int rc = multi_gather(m, use_peer, fell_back)) return rc;
-    if (int rc = multi_untile(p, m)) return rc;
-    for (uint32_t r = 0; r < ngpu && stats; ++r) {
-        float t = 0;
-        HIP_TRY(hipSetDevice(m.ranks[r].d->device));
-        HIP_TRY(hipEventElapsedTime(&t, ev[2 * r].get(), ev[2 * r + 1].get()));
-        stats[r].kernel_ms = ms[r] + t;
-        stats[r].samples += refined[r];
-    }
-    if (stats && use_peer) stats[0].reserved |= 0x100u | (fell_back ? 0x200u : 0u);
-    DeviceState* root = m.root;
-    HIP_TRY(hipSetDevice(root->device));
-    hipError_t e = hipSuccess;
-    if (out_spp) e = hipMemcpy(out_spp, root->ad_spp.p, m.npx * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_stderr_rgb) e = hipMemcpy(out_stderr_rgb, root->ad_stderr.p, m.npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    return copy_image_out("render_adaptive_multi", root->rgba, root->linear, p.precision, m.npx, out_rgba8, out_linear_rgb, e);
+    return adaptive_node_render("render_adaptive_multi", s, cam, p, a, ngpu, device_ids, false, nullptr, 0, nullptr, out_linear_rgb, out_rgba8, out_spp,
+                                out_stderr_rgb, stats);
+}
+
+extern "C" uint64_t rttnw_adaptive_state_doubles(uint32_t width, uint32_t height) {
+    return uint64_t(RTTNW_ADAPTIVE_STATE_HEADER) + uint64_t(RTTNW_ADAPTIVE_STATE_RECORD) * width * height;
+}
+
+// rttnw_render_adaptive_resume (include/rttnw_hip.h has the contract and the state's layout, DESIGN.md §10a "resumable form" the why)
+extern "C" int rttnw_render_adaptive_resume(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p_in, const rttnw_adaptive* a, uint32_t ngpu,
+                                            const int32_t* device_ids, const double* state_in, double* state_out, double* out_linear_rgb,
+                                            uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, rttnw_stats* stats) {
+    using namespace rt;
+    // the refusals, in the header's order: none of them needs a device
+    if (!p_in || !a) { set_last_error("render_adaptive_resume: NULL argument (p or a)"); return RTTNW_ERR_INVALID; }
+    if (ngpu > 64) { set_last_error("render_adaptive_resume: ngpu must be 0 .. 64"); return RTTNW_ERR_INVALID; }
+    if (ngpu && !device_ids) { set_last_error("render_adaptive_resume: device_ids is NULL with ngpu >= 1"); return RTTNW_ERR_INVALID; }
+    if (!ngpu && device_ids) { set_last_error("render_adaptive_resume: device_ids must be NULL with ngpu == 0 (the current device)"); return RTTNW_ERR_INVALID; }
+    if (int rc = refuse_adaptive_misuse("render_adaptive_resume", p_in, a)) return rc;
+    rttnw_params p = *p_in;
+    if (ngpu) { p.tile_rank = 0; p.tile_world = 1; } // (ngpu >= 1: the caller's are ignored, as in rttnw_render_adaptive_multi; ngpu == 0: tile_world must be 1)
+    if (int rc = refuse_host_output_misuse("render_adaptive_resume", a->reserved0, &p)) return rc;
+    uint32_t first_level = 0;
+    if (state_in)
+        if (int rc = refuse_state_misuse(*p_in, *a, cam, state_in, first_level)) return rc;
+    p.tile_rank = 0; p.tile_world = std::max(ngpu, 1u);
+    if (int rc = validate(s, cam, &p)) return rc;
+    const int n_dev = rttnw_device_count();
+    for (uint32_t r = 0; r < ngpu; ++r)
+        if (device_ids[r] < 0 || device_ids[r] >= n_dev) { set_last_error("render_adaptive_resume: no such device in device_ids"); return RTTNW_ERR_INVALID; }
+    const int32_t own = s->device->device; // ngpu == 0: one rank where rttnw_render_adaptive runs
+    return adaptive_node_render("render_adaptive_resume", s, cam, p, a, std::max(ngpu, 1u), ngpu ? device_ids : &own, ngpu == 0, state_in, first_level,
+                                state_out, out_linear_rgb, out_rgba8, out_spp, out_stderr_rgb, stats);
 }
 
 // Release what the library keeps for the life of the process (today: the RCCL communicator sets of rttnw_render_multi).  Scenes

@@ -237,6 +237,9 @@ struct DeviceState {
     // active bytes, each rank's list and scan (a rank's list is built behind one pass and read by its next, with other ranks' work between) —
     // and the ranks' auxiliary records (standard errors and samples, 4 doubles per packed pixel); on the root device, every rank's records
     DevBuf<uint8_t> multi_ad_state, multi_ad_active, multi_list, multi_aux, gathered_aux;
+    // rttnw_render_adaptive_resume, slotted the same way: the ranks' packed state records (12 doubles per packed pixel, copied from and to the host)
+    // and the marks of the level being listed (a byte per packed pixel)
+    DevBuf<uint8_t> multi_ad_records, multi_ad_marks;
 };
 // Words of build_quad_list's scan workspace over n_blocks blocks, and where its two totals (listed blocks, marked pixels) stand in it
 inline size_t quad_scan_words(uint32_t n_blocks) { return size_t((n_blocks + 63u) / 64u) * 3 + 2; }
@@ -312,6 +315,7 @@ inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, co
 //   render_adaptive_t  rttnw_render_adaptive's device half: every pass, then the image (d->linear, d->rgba) and the maps (d->ad_spp, d->ad_stderr) on the device
 //   render_region_t    rttnw_render_region's device half: selection, list, trace, resolve; the window's image on the device (d->rg_linear, d->rg_rgba)
 //   enqueue_quad_list, adaptive_finish_launch, untile_aux_launch   what rttnw_render_adaptive_multi (render_api.cpp) enqueues beside render_tiles_t's passes
+//   adaptive_state_import_launch, adaptive_state_export_launch, adaptive_level_select_launch, adaptive_rank_stats_t   what rttnw_render_adaptive_resume adds to those
 #define RT_PRECISION_ENTRY_POINTS(X, R)                                                                                                              \
     X(R, render_tiles_t, (::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream, \
                           rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const ListPass* ad))                                          \
@@ -326,7 +330,14 @@ inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, co
     X(R, adaptive_finish_launch, (void* d_packed, const void* d_state, double* d_aux, uint32_t pixels_per_rank, uint32_t rank_pixels,                \
                                   hipStream_t stream))                                                                                               \
     X(R, untile_aux_launch, (uint32_t width, uint32_t height, uint32_t world, const double* d_gathered_aux, uint32_t* d_spp, double* d_stderr,       \
-                             hipStream_t stream))
+                             hipStream_t stream))                                                                                                    \
+    X(R, adaptive_state_import_launch, (const double* d_records, void* d_packed, void* d_state, uint8_t* d_active, uint32_t pixels_per_rank,         \
+                                        uint32_t cap, double rel_error, double abs_error, hipStream_t stream))                                       \
+    X(R, adaptive_state_export_launch, (const void* d_packed, const void* d_state, double* d_records, uint32_t pixels_per_rank,                      \
+                                        uint32_t rank_pixels, hipStream_t stream))                                                                   \
+    X(R, adaptive_level_select_launch, (const uint8_t* d_active, const void* d_state, uint8_t* d_marks, uint32_t n_pixels, uint32_t level_n,         \
+                                        hipStream_t stream))                                                                                         \
+    X(R, adaptive_rank_stats_t, (::rttnw_scene* s, DeviceState* d, const rttnw_params* p, rttnw_stats* stats))
 #define RT_DECLARE_T(R, name, params) template <typename> int name params;
 #define RT_EXTERN_T(R, name, params) extern template int name<R> params;
 #define RT_INSTANTIATE_T(R, name, params) template int name<R> params;

@@ -23,5 +23,9 @@ template int probe_path_t<double>(::rttnw_scene*, const rttnw_camera_desc*, cons
 template int enqueue_quad_list<double>(const uint8_t*, uint32_t, uint32_t*, uint32_t*, hipStream_t);
 template int adaptive_finish_launch<double>(void*, const void*, double*, uint32_t, uint32_t, hipStream_t);
 template int untile_aux_launch<double>(uint32_t, uint32_t, uint32_t, const double*, uint32_t*, double*, hipStream_t);
+template int adaptive_state_import_launch<double>(const double*, void*, void*, uint8_t*, uint32_t, uint32_t, double, double, hipStream_t);
+template int adaptive_state_export_launch<double>(const void*, const void*, double*, uint32_t, uint32_t, hipStream_t);
+template int adaptive_level_select_launch<double>(const uint8_t*, const void*, uint8_t*, uint32_t, uint32_t, hipStream_t);
+template int adaptive_rank_stats_t<double>(::rttnw_scene*, DeviceState*, const rttnw_params*, rttnw_stats*);
 } // namespace RT_ARITH_NS
 } // namespace rt

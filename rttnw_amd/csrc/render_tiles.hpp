@@ -368,6 +368,46 @@ int untile_aux_launch(uint32_t width, uint32_t height, uint32_t world, const dou
     return RTTNW_OK;
 }
 
+// rttnw_render_adaptive_resume's launches of its own (render_api.cpp has the level loop): a rank's packed state records to its running sums, noise
+// state and active bytes; the same back, before adaptive_finish_launch turns the sums into means; and the marks of one level for the list build.
+template <typename R>
+int adaptive_state_import_launch(const double* d_records, void* d_packed, void* d_state, uint8_t* d_active, uint32_t pixels_per_rank, uint32_t cap,
+                                 double rel_error, double abs_error, hipStream_t stream) {
+    hipLaunchKernelGGL(adaptive_state_import_kernel<R>, dim3((pixels_per_rank + 255u) / 256u), dim3(256), 0, stream, d_records, (R*)d_packed,
+                       (AdaptivePixel*)d_state, d_active, pixels_per_rank, cap, rel_error, abs_error);
+    HIP_TRY(hipGetLastError());
+    return RTTNW_OK;
+}
+template <typename R>
+int adaptive_state_export_launch(const void* d_packed, const void* d_state, double* d_records, uint32_t pixels_per_rank, uint32_t rank_pixels,
+                                 hipStream_t stream) {
+    hipLaunchKernelGGL(adaptive_state_export_kernel<R>, dim3((pixels_per_rank + 255u) / 256u), dim3(256), 0, stream, (const R*)d_packed,
+                       (const AdaptivePixel*)d_state, d_records, pixels_per_rank, rank_pixels);
+    HIP_TRY(hipGetLastError());
+    return RTTNW_OK;
+}
+template <typename R>
+int adaptive_level_select_launch(const uint8_t* d_active, const void* d_state, uint8_t* d_marks, uint32_t n_pixels, uint32_t level_n, hipStream_t stream) {
+    hipLaunchKernelGGL(adaptive_level_select_kernel<R>, dim3((n_pixels + 255u) / 256u), dim3(256), 0, stream, d_active, (const AdaptivePixel*)d_state,
+                       d_marks, n_pixels, level_n);
+    HIP_TRY(hipGetLastError());
+    return RTTNW_OK;
+}
+// ... and the stats record of a rank that starts from a state: what pass 0 of a fresh render reports of the scene and the kernel form (its
+// plan: render_tiles_t's for a pass that is not listed), with no samples yet — a resumed render has no pass 0 to fill it.
+template <typename R>
+int adaptive_rank_stats_t(::rttnw_scene* s, DeviceState* d, const rttnw_params* p, rttnw_stats* stats) {
+    const FlatScene* flat = nullptr;
+    DeviceScene<R>* ds = nullptr;
+    if (int rc = bind_scene<R>(s, d, flat, ds)) return rc;
+    rttnw_tile_layout L;
+    fill_layout(p->width, p->height, p->tile_world, L);
+    const RenderConsts rc = base_consts(p, *flat, L);
+    if (int g = fill_stats<R>(d, *ds, *flat, plan_for<R>(*flat, false, false), rc, false, nullptr, stats)) return g;
+    stats->samples = 0;
+    return RTTNW_OK;
+}
+
 // rttnw_render_region (include/rttnw_hip.h has the contract, DESIGN.md §10c the why).  The selected pixels of the window become the list of 2x2
 // blocks that hold one (region_kernels.hpp region_select_kernel, then the compaction kernels of the adaptive passes; one 8-byte copy gives the host
 // the list's length), and render_tiles_t traces that list with its own kernel choice, chunk schedule and launch split — the jobs rttnw_render runs

@@ -650,6 +650,15 @@ __global__ void untile_kernel(const R* __restrict__ gathered, R* __restrict__ li
 // the active list (rt_core.hpp job_decode_list: slot = 4 * list position + pixel in block; `quads` != nullptr).  Per pixel, in chunk order:
 // the running sum in `packed` (the R chain: exactly resolve_kernel's additions, continued over launches AND passes), and the double state
 // of adaptive.hpp folded with the chunk's mean.  The pass's last launch decides whether the pixel takes part in the next pass.
+// The active bit of a pixel with running sum (r, g, b) and noise state `a`: its value as the render reports it — sum / R(n), in the kernel's
+// arithmetic type — held against the stopping rule.  ONE piece of code for the end of a pass (adaptive_resolve_kernel) and for a state taken up
+// again (adaptive_state_import_kernel): the contracted builds' division comes from here alone, so both decide from the same bits.
+template <typename R>
+__device__ __forceinline__ bool adaptive_pixel_active(const AdaptivePixel& a, R r, R g, R b, double rel_error, double abs_error, uint32_t cap) {
+    const R n = R(a.n);
+    const double value[3] = {double(r / n), double(g / n), double(b / n)};
+    return adaptive_active(a, value, rel_error, abs_error, cap);
+}
 template <typename R>
 __global__ void adaptive_resolve_kernel(const R* __restrict__ partial, R* __restrict__ packed, AdaptivePixel* __restrict__ state,
                                         uint8_t* __restrict__ active, const uint32_t* __restrict__ quads, RenderConsts rc, uint32_t n_slots,
@@ -683,11 +692,7 @@ __global__ void adaptive_resolve_kernel(const R* __restrict__ partial, R* __rest
     }
     dst[0] = r; dst[1] = g; dst[2] = b; dst[3] = R(0);
     state[p] = a;
-    if (last_of_pass) {
-        const R n = R(a.n);
-        const double value[3] = {double(r / n), double(g / n), double(b / n)};
-        active[p] = inside && adaptive_active(a, value, rel_error, abs_error, cap) ? 1u : 0u;
-    }
+    if (last_of_pass) active[p] = inside && adaptive_pixel_active<R>(a, r, g, b, rel_error, abs_error, cap) ? 1u : 0u;
 }
 
 // Compaction of the active pixels into the list of 2x2 blocks the next pass traces — deterministic, no atomics: (1) every wave counts its
@@ -792,6 +797,63 @@ __global__ void untile_aux_kernel(const double* __restrict__ gathered_aux, uint3
     const unsigned long long o = (unsigned long long)y * width + x;
     spp_map[o] = uint32_t(gathered_aux[src * 4 + 3]);
     for (int ch = 0; ch < 3; ++ch) stderr_map[o * 3ull + ch] = gathered_aux[src * 4 + ch];
+}
+
+// ---- rttnw_render_adaptive_resume: a render's state leaves the device and comes back (include/rttnw_hip.h has the record: 12 doubles per pixel —
+// sum r, g, b, n, mu r, g, b, k, m2 r, g, b, 0: adaptive.hpp STATE_RECORD_DOUBLES).  The host permutes between the row-major state and a rank's packed order, so these kernels see
+// one rank's packed records, one thread per packed pixel, in the single and the node-wide form alike.
+// record -> running sum (narrowed back to R: exact, it was widened from R), noise state and active byte under THIS call's tolerances and cap.
+// A record with n == 0 — the host leaves those for pixels outside the image and for pad tiles — gives zero state and an inactive pixel.
+template <typename R>
+__global__ void adaptive_state_import_kernel(const double* __restrict__ records, R* __restrict__ packed, AdaptivePixel* __restrict__ state,
+                                             uint8_t* __restrict__ active, uint32_t pixels_per_rank, uint32_t cap, double rel_error, double abs_error) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= pixels_per_rank) return;
+    const double* rec = records + (unsigned long long)p * STATE_RECORD_DOUBLES;
+    R* dst = packed + (unsigned long long)p * 4ull;
+    AdaptivePixel a = {{0, 0, 0}, {0, 0, 0}, 0u, 0u};
+    R r = 0, g = 0, b = 0;
+    bool on = false;
+    if (rec[3] != 0.0) {
+        r = R(rec[0]); g = R(rec[1]); b = R(rec[2]);
+        a.n = uint32_t(rec[3]);
+        a.k = uint32_t(rec[7]);
+        for (int ch = 0; ch < 3; ++ch) { a.mu[ch] = rec[4 + ch]; a.m2[ch] = rec[8 + ch]; }
+        on = adaptive_pixel_active<R>(a, r, g, b, rel_error, abs_error, cap);
+    }
+    dst[0] = r; dst[1] = g; dst[2] = b; dst[3] = R(0);
+    state[p] = a;
+    active[p] = on ? 1u : 0u;
+}
+// running sum (BEFORE adaptive_finish_packed_kernel turns it into the mean) and noise state -> record.  A pixel that traced nothing (n == 0) and
+// the pixels of pad tiles (p >= rank_pixels: a fresh render never wrote their state) get a zero record.
+template <typename R>
+__global__ void adaptive_state_export_kernel(const R* __restrict__ packed, const AdaptivePixel* __restrict__ state, double* __restrict__ records,
+                                             uint32_t pixels_per_rank, uint32_t rank_pixels) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= pixels_per_rank) return;
+    double* rec = records + (unsigned long long)p * STATE_RECORD_DOUBLES;
+    AdaptivePixel a = {{0, 0, 0}, {0, 0, 0}, 0u, 0u};
+    if (p < rank_pixels) a = state[p];
+    if (a.n == 0u) {
+        for (uint32_t i = 0; i < STATE_RECORD_DOUBLES; ++i) rec[i] = 0.0;
+        return;
+    }
+    const R* src = packed + (unsigned long long)p * 4ull;
+    rec[0] = double(src[0]); rec[1] = double(src[1]); rec[2] = double(src[2]);
+    rec[3] = double(a.n);
+    rec[7] = double(a.k);
+    for (int ch = 0; ch < 3; ++ch) { rec[4 + ch] = a.mu[ch]; rec[8 + ch] = a.m2[ch]; }
+    rec[11] = 0.0;
+}
+// What a resumed render traces at one level: the active pixels that hold exactly level_n = level * B samples, as the byte array the list
+// compaction reads.  (A fresh render has all its active pixels at one level and compacts the active bytes themselves.)
+template <typename R>
+__global__ void adaptive_level_select_kernel(const uint8_t* __restrict__ active, const AdaptivePixel* __restrict__ state, uint8_t* __restrict__ marks,
+                                             uint32_t n_pixels, uint32_t level_n) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pixels) return;
+    marks[p] = active[p] && state[p].n == level_n ? 1u : 0u;
 }
 
 // Debug probe: lane 0 walks one sample's path (rt_core.hpp probe_path) — the device half of the per-bounce CPU-vs-GPU vector tests.

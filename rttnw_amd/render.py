@@ -85,6 +85,39 @@ def render_adaptive_multi(scene, cam, params, device_ids, pass_spp=64, rel_error
     return lin, rgba, spp, se, list(st)
 
 
+def render_adaptive_resume(scene, cam, params, state=None, device_ids=None, pass_spp=64, rel_error=0.02, abs_error=0.0, want_state=True):
+    """`rttnw_render_adaptive_resume`: `render_adaptive` (device_ids None) or `render_adaptive_multi` begun from `state` — the double array an
+    earlier call returned, None for a fresh render — and continued under THIS call's tolerances and cap; the same `spp_chunk` default.  With a
+    cap and tolerances no looser than the state's, the result is bit for bit the render that was never interrupted.
+    Returns (linear HxWx3 f64, rgba8 HxWx4 u8, spp_map HxW u32, stderr HxWx3 f64, Stats or [Stats per rank], state or None)."""
+    import copy
+    b = library.product()
+    p = copy.copy(params)
+    if p.spp_chunk == 0:
+        p.spp_chunk = max(1, pass_spp // 16)
+    h, w = p.height, p.width
+    lin = np.zeros((h, w, 3), dtype=np.float64)
+    rgba = np.zeros((h, w, 4), dtype=np.uint8)
+    spp = np.zeros((h, w), dtype=np.uint32)
+    se = np.zeros((h, w, 3), dtype=np.float64)
+    n_doubles = int(b.adaptive_state_doubles(w, h))
+    st_in = None
+    if state is not None:
+        st_in = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
+        if st_in.size != n_doubles:
+            raise ValueError("render_adaptive_resume: a state of a %dx%d frame holds %d doubles, got %d" % (w, h, n_doubles, st_in.size))
+    st_out = np.zeros(n_doubles, dtype=np.float64) if want_state else None
+    n = 0 if device_ids is None else len(device_ids)
+    ids = None if device_ids is None else (C.c_int32 * max(n, 1))(*device_ids)
+    st = (Stats * max(n, 1))()
+    a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
+    rc = b.render_adaptive_resume(scene.handle, C.byref(cam), C.byref(p), C.byref(a), n, ids, None if st_in is None else st_in.ctypes.data,
+                                  None if st_out is None else st_out.ctypes.data, lin.ctypes.data, rgba.ctypes.data, spp.ctypes.data,
+                                  se.ctypes.data, C.cast(st, C.c_void_p))
+    check(rc, b, "rttnw_render_adaptive_resume")
+    return lin, rgba, spp, se, (st[0] if device_ids is None else list(st)), st_out
+
+
 def render_features(scene, cam, params):
     """`rttnw_render_features`: the first hit of the render's own camera rays, averaged over `params.spp` samples per pixel.
     Returns {"albedo": HxWx3, "normal": HxWx3, "depth": HxW, "alpha": HxW (all f64), "stats": Stats}."""
