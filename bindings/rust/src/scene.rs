@@ -188,6 +188,29 @@ impl Scene {
         ok(unsafe { ffi::rttnw_render_adaptive_resume(self.raw, cam, p, a, devices.len() as u32, ids, state.map_or(ptr::null(), |s| s.as_ptr()), out.as_mut_ptr(), ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), stats.as_mut_ptr()) })?;
         Ok((rgba, spp, stderr, stats, out))
     }
+    /// The adaptive render over pixels `[x0, x1) x [y0, y1)` of the frame, or those of them whose byte of `mask` (window-sized, row-major, top row
+    /// first) is nonzero (`rttnw_render_adaptive_region`), begun from `state` — frame-sized, as `render_adaptive_resume` returns it, a pixel never
+    /// sampled being a record of zeros; `None`: all zeros.  Only selected pixels are traced, each to the bits of a fresh whole-frame adaptive
+    /// render under `a` and the cap `p.spp`; the others keep their records.  `devices` as in `render_adaptive_resume`.
+    /// Returns (RGBA8, samples per pixel and standard errors of the window — a pixel without samples is zero, alpha included —, stats, the state).
+    pub fn render_adaptive_region(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, a: &ffi::rttnw_adaptive, x0: u32, y0: u32, x1: u32, y1: u32, mask: Option<&[u8]>, devices: &[i32], state: Option<&[f64]>) -> Result<(Vec<u8>, Vec<u32>, Vec<f64>, Vec<ffi::rttnw_stats>, Vec<f64>)> {
+        let n = (x1.saturating_sub(x0) as usize) * (y1.saturating_sub(y0) as usize);
+        if mask.map_or(false, |m| m.len() != n) {
+            return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "render_adaptive_region: the mask does not have the window's size".into() });
+        }
+        let doubles = unsafe { ffi::rttnw_adaptive_state_doubles(p.width, p.height) } as usize;
+        if state.map_or(false, |s| s.len() != doubles) {
+            return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "render_adaptive_region: the state does not have the frame's size".into() });
+        }
+        let mut rgba = vec![0u8; n * 4];
+        let mut spp = vec![0u32; n];
+        let mut stderr = vec![0f64; n * 3];
+        let mut stats = vec![ffi::rttnw_stats::default(); devices.len().max(1)];
+        let mut out = vec![0f64; doubles];
+        let ids = if devices.is_empty() { ptr::null() } else { devices.as_ptr() };
+        ok(unsafe { ffi::rttnw_render_adaptive_region(self.raw, cam, p, a, x0, y0, x1, y1, mask.map_or(ptr::null(), |m| m.as_ptr()), devices.len() as u32, ids, state.map_or(ptr::null(), |s| s.as_ptr()), out.as_mut_ptr(), ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), stats.as_mut_ptr()) })?;
+        Ok((rgba, spp, stderr, stats, out))
+    }
     /// First-hit feature buffers of the frame `render` renders (`rttnw_render_features`), row-major, top row first.
     pub fn render_features(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params) -> Result<Features> {
         let n = p.width as usize * p.height as usize;

@@ -40,9 +40,9 @@ extern "C" {
 #define RTTNW_ABI_VERSION 3 /* 2: 4-wide node records (n_nodes, debug_scene_nodes4), rttnw_render_multi
                              * 3: RTTNW_F64_STRICT, rttnw_shutdown, RTTNW_BVH_AUTO (the default builder), rttnw_stats.reserved is a bit mask
                              *    (below), validate() rejects t_min < 0
-                             * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region, rttnw_render_adaptive_multi and
-                             *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles came later, without a version bump: a caller detects
-                             *  each by its symbol) */
+                             * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region, rttnw_render_adaptive_multi,
+                             *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles and rttnw_render_adaptive_region came later, without a
+                             *  version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -472,6 +472,62 @@ int rttnw_render_adaptive_multi(rttnw_scene* s, const rttnw_camera_desc* cam, co
 #define RTTNW_ADAPTIVE_STATE_RECORD 12u /* doubles per pixel */
 uint64_t rttnw_adaptive_state_doubles(uint32_t width, uint32_t height);
 int rttnw_render_adaptive_resume(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
+                                 uint32_t ngpu, const int32_t* device_ids, const double* state_in, double* state_out,
+                                 double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb,
+                                 rttnw_stats* stats);
+
+/* Adaptive sampling of a window, or a pixel mask, of the frame: rttnw_render_adaptive_resume over the selection of rttnw_render_region — a preview of
+ * the area being worked on sampled to a noise target, the noisy patch of an adaptive preview brought to 2 % where one looks — at the cost of the
+ * selected pixels' samples.  (Came without a version bump, like rttnw_render_adaptive: detect it by its symbol.)
+ *
+ * Frame, window, mask.  As rttnw_render_region: the frame is the p->width x p->height frame of rttnw_render, with its camera and its keys (pixel,
+ *   sample, seed); the window is its pixels [x0, x1) x [y0, y1), row 0 = top; `mask` (optional): (x1-x0)*(y1-y0) bytes, row-major, top row first,
+ *   nonzero = selected; NULL selects every pixel of the window.  Selected pixels are the only ones this call may trace.
+ * Where it runs.  As rttnw_render_adaptive_resume: ngpu == 0 with device_ids == NULL on the scene's device (`stats`: one record; tile_world must
+ *   be 1); ngpu 1 .. 64 on rttnw_render_adaptive_multi's ranks, with its gather transports and environment (`stats`: ngpu records).
+ * State.  The state of rttnw_render_adaptive_resume: same magic, version, header and size rttnw_adaptive_state_doubles(width, height) — always
+ *   FRAME-sized and row-major, whatever the window.  One addition, for this entry point only: a record of twelve zeros means "this pixel holds no
+ *   samples yet".  state_in == NULL stands for a state whose records are all zero.  rttnw_render_adaptive_resume keeps refusing such records (n
+ *   below pass_spp); a partly filled state is completed by a call of this entry point over the whole frame, after which resume accepts it.
+ * What is traced.  Every pixel starts from its record.  A selected pixel with a zero record is active; a selected pixel with samples is active
+ *   by the expression that ends a pass (value = sum / n_q in the kernel's type, then the stopping rule) under THIS call's tolerances and cap; an
+ *   unselected pixel is never active, and its record goes to state_out unchanged, bit for bit.  Passes go by LEVEL, as in the resumed render:
+ *   level k traces samples [sample_begin + kB, sample_begin + (k+1)B) of the active pixels that hold exactly kB samples, over the list of their 2x2
+ *   blocks — level 0 too runs over a list, not in the plain render's job numbering.  Levels run from the lowest a selected pixel stands at to
+ *   spp / B - 1; a level nobody is active at costs its list build, and the loop ends once no pixel is active.
+ * Outputs (each optional, sized by the WINDOW; row-major, top row first): out_linear_rgb (x1-x0)*(y1-y0)*3 doubles, out_rgba8 *4 bytes, out_spp
+ *   *1 words, out_stderr_rgb *3 doubles.  They report every pixel of the window that holds samples in the state the call ends in, selected or not:
+ *   its mean (sum / n_q in the kernel's type, the adaptive render's division), RGBA8 with alpha 255, n_q, and its standard error (+inf with fewer
+ *   than two chunks).  A pixel of the window without samples gets 0, 0, 0, RGBA8 0, 0, 0, 0, spp 0 and stderr 0: alpha tells the two apart, as
+ *   in rttnw_render_region.  state_out (optional; may be the SAME array as state_in): the header, then every record of the frame.
+ * Contract.  Let F be the four outputs and the state of ONE rttnw_render_adaptive_resume(state_in = NULL) of the frame with cap C and tolerances
+ *   (rel, abs), and q a pixel this call selected and ended under cap C and (rel, abs), every earlier call that traced q having used a cap no higher
+ *   and tolerances no tighter.  Then q's record in state_out, its linear value, RGBA8, sample count and standard error are BIT-IDENTICAL to q's
+ *   in F — for every `precision`, every kernel form, every launch split (RTTNW_CHUNK_SUM_BUDGET), every ngpu and device list on either side of any
+ *   hand-over, and both gather transports.  Why: the resumable form's reason — a pixel's samples are keyed by (pixel, sample, seed), its sum is one
+ *   chain in chunk order (0 + c0 is that chain's first addition, so a list pass on a zero record is the plain pass 0), and its stopping decision
+ *   reads its own chunk sums only.  With a LOOSER rule than q was last traced under the call is still well defined — a pixel keeps what it has and
+ *   goes on only if it is active — but no longer equal to a fresh render: q may hold more samples than the looser rule would have given it.
+ * No work.  Nothing active (an all-zero mask, or every selected pixel done): RTTNW_OK, no trace kernel is launched, stats->samples == 0, and the
+ *   outputs are those of the incoming state — with no state and an all-zero mask all cleared, state_out a header over zero records.
+ * `stats` (optional), as rttnw_render_adaptive_resume: samples = what THIS call traced (node-wide: per rank), kernel_ms = device time of
+ *   everything the call runs, the state's copy to the device and its conversion both ways included; reserved and the scene's sizes as there.
+ *   Blocking.
+ * Memory.  The state, and per rank the packed means, noise state, active, selection and level bytes, the state records and the block list's
+ *   workspace (a word per 2x2 block of the rank) are FRAME-sized, as in the resumable form.  Chunk sums are sized by the blocks that hold a
+ *   selected pixel (4 per block and chunk), the mask and the four outputs by the window.  A window-sized state is out of scope.
+ * Refusals, before the device is touched, in this order, each message naming render_adaptive_region and the field:
+ *   1. RTTNW_ERR_INVALID for a NULL p or a;
+ *   2. RTTNW_ERR_INVALID for x0 >= x1, y0 >= y1, x1 > width or y1 > height;
+ *   3. RTTNW_ERR_INVALID for ngpu > 64, ngpu >= 1 with a NULL device_ids, ngpu == 0 with a non-NULL device_ids;
+ *   4. what rttnw_render_adaptive refuses among its own arguments, with its codes (its tile_world rule with ngpu == 0 only);
+ *   5. with a state_in, rttnw_render_adaptive_resume's state checks (the header compared bitwise; per record n and k finite integers, n a multiple
+ *      of B, n <= p->spp, k == (n / B) * the chunks of a pass) with two differences: a record with n == 0 is accepted if and only if all twelve
+ *      doubles are zero (RTTNW_ERR_INVALID for a zero n with anything else nonzero), and n < B is refused only for n != 0;
+ *   6. whatever rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes);
+ *   7. with ngpu >= 1, RTTNW_ERR_INVALID for a device id outside [0, rttnw_device_count()). */
+int rttnw_render_adaptive_region(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
+                                 uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const uint8_t* mask,
                                  uint32_t ngpu, const int32_t* device_ids, const double* state_in, double* state_out,
                                  double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb,
                                  rttnw_stats* stats);

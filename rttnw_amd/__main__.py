@@ -14,6 +14,10 @@ rttnw_render_adaptive_multi — the same image either way.  It does not combine 
 --save-state FILE and --resume FILE (with --noise only; they combine with --devices): the adaptive render leaves its state — the double array of
 rttnw_render_adaptive_resume, as .npy — in FILE, and starts from the state in FILE: a preview refined under a tighter --noise or a higher --spp
 without retracing a sample, on the same scene, size, seed and --pass-spp.  They do not combine with --window or --passes.
+--refine X0,Y0,X1,Y1 (with --noise only) brings pixels [X0, X1) x [Y0, Y1) of the frame to the noise bound (rttnw_render_adaptive_region) and writes
+that window as the image: alone it samples the window from nothing; with --resume it starts from the state in FILE — a preview's noisy patch refined
+where one looks, the rest of the state untouched — and --save-state leaves the frame-sized state, in which pixels never sampled are zero records.  It
+combines with --spp, --pass-spp, --devices and --spp-map, and not with --window, --passes, --features or --denoise.
 """
 import argparse
 import sys
@@ -79,6 +83,8 @@ def main(argv=None):
                     "PREFIX_normal.png, PREFIX_depth.png, PREFIX_alpha.png")
     ap.add_argument("--window", default=None, metavar="X0,Y0,X1,Y1", help="render pixels [X0, X1) x [Y0, Y1) of the frame only (row 0 = top) "
                     "and write that window as the image")
+    ap.add_argument("--refine", default=None, metavar="X0,Y0,X1,Y1", help="adaptive sampling: bring pixels [X0, X1) x [Y0, Y1) of the frame to the "
+                    "noise bound, from the --resume state if given, and write that window as the image")
     ap.add_argument("--devices", default=None, metavar="D0,D1,...", help="render on these GPUs of the node (repeats allowed: logical ranks); "
                     "with --noise the adaptive render runs across them")
     ap.add_argument("--save-state", default=None, metavar="FILE", help="adaptive sampling: leave the render's state in FILE (.npy) for a later --resume")
@@ -88,6 +94,20 @@ def main(argv=None):
     except SystemExit:
         print("There was an error", file=sys.stderr)   # DummyError, main.rs:260-268
         raise
+    refine = None
+    if args.refine is not None:
+        if args.noise is None:
+            print("--refine needs --noise: it brings a window to a noise bound", file=sys.stderr)
+            return 1
+        clash = [name for name, on in (("--window", args.window is not None), ("--passes", args.passes > 1), ("--features", args.features is not None),
+                                       ("--denoise", args.denoise)) if on]
+        if clash:
+            print("--refine does not combine with %s: it runs the adaptive render over a window of the frame" % ", ".join(clash), file=sys.stderr)
+            return 1
+        refine = parse_window(args.refine)
+        if refine is None:
+            print("--refine wants X0,Y0,X1,Y1: four non-negative integers with X0 < X1 and Y0 < Y1, got %r" % args.refine, file=sys.stderr)
+            return 1
     devices = None
     if args.devices is not None:
         devices = parse_devices(args.devices)
@@ -187,7 +207,10 @@ def main(argv=None):
             print("cap %d spp rounded up to %d, a multiple of --pass-spp %d" % (p.spp, cap, args.pass_spp))
             p.spp = cap
         per_rank = ""
-        if args.resume is not None or args.save_state is not None:
+        if refine is not None and (refine[2] > w or refine[3] > h):
+            print("--refine %s reaches outside the %dx%d frame" % (args.refine, w, h), file=sys.stderr)
+            return 1
+        if refine is not None or args.resume is not None or args.save_state is not None:
             state = None
             if args.resume is not None:
                 try:
@@ -195,8 +218,13 @@ def main(argv=None):
                 except (OSError, ValueError) as e:
                     print("--resume %s: %s" % (args.resume, e), file=sys.stderr)
                     return 1
-            lin, rgba, spp_map, se, sts, state = render.render_adaptive_resume(sc, cam, p, state, devices, args.pass_spp, args.noise, args.abs_noise,
-                                                                               want_state=args.save_state is not None)
+            if refine is not None:
+                lin, rgba, spp_map, se, sts, state = render.render_adaptive_region(sc, cam, p, *refine, state=state, device_ids=devices,
+                                                                                   pass_spp=args.pass_spp, rel_error=args.noise, abs_error=args.abs_noise,
+                                                                                   want_state=args.save_state is not None)
+            else:
+                lin, rgba, spp_map, se, sts, state = render.render_adaptive_resume(sc, cam, p, state, devices, args.pass_spp, args.noise, args.abs_noise,
+                                                                                   want_state=args.save_state is not None)
             if devices is not None:
                 st = abi.Stats(samples=sum(x.samples for x in sts), kernel_ms=node_ms(devices, sts))
                 per_rank = "; per rank: %s" % " ".join(str(x.samples) for x in sts)
@@ -216,6 +244,8 @@ def main(argv=None):
             grey = np.minimum(spp_map.astype(np.float64) / p.spp * 255.0 + 0.5, 255.0).astype(np.uint8)
             Image.fromarray(grey, "L").save(args.spp_map)
         full = w * h * p.spp
+        if refine is not None:
+            print("window %dx%d at (%d, %d) of %dx%d" % (refine[2] - refine[0], refine[3] - refine[1], refine[0], refine[1], w, h))
         print("%.3fs (adaptive: %d samples traced of %d = %dx%dx%d, %.1f %%; kernels %.1f ms%s)"
               % (time.time() - t0, st.samples, full, w, h, p.spp, 100.0 * st.samples / full, st.kernel_ms, per_rank))
         return 0

@@ -440,7 +440,8 @@ static int multi_plan(::rttnw_scene* s, const rttnw_params& p, uint32_t ngpu, co
 
 // Everything that allocates, before anything is launched (an allocation or a free between two ranks' launches would synchronise its whole
 // device): the streams, this layer's buffers, then per rank what a first use brings — scene uploads and workspace growth
-static int multi_prepare_buffers(const MultiPlan& m) {
+// (`frame_image`: the root un-tiles a frame-sized image; rttnw_render_adaptive_region writes a window-sized one instead)
+static int multi_prepare_buffers(const MultiPlan& m, bool frame_image = true) {
     for (size_t k = 0; k < m.devices.size(); ++k) {
         DeviceState* d = m.dev_state[k];
         HIP_TRY(hipSetDevice(d->device));
@@ -450,6 +451,7 @@ static int multi_prepare_buffers(const MultiPlan& m) {
     DeviceState* root = m.root;
     HIP_TRY(hipSetDevice(root->device));
     HIP_TRY(root->gathered.grow(m.chunk * m.ranks.size()));
+    if (!frame_image) return 0;
     HIP_TRY(root->linear.grow(m.npx * 3 * m.rsz));
     HIP_TRY(root->rgba.grow(m.npx * 4));
     return 0;
@@ -567,9 +569,8 @@ static int gather_peer(const MultiPlan& m) {
     return 0;
 }
 
-// On the root's stream: the tiles of the ranks that live on its device (unless they went through the transport) join the gathered ones, and the
-// image is made of them.  Then every device's stream has finished.
-static int multi_untile(const rttnw_params& p, const MultiPlan& m) {
+// On the root's stream: the tiles of the ranks that live on its device (unless they went through the transport) join the gathered ones ...
+static int multi_join_local(const MultiPlan& m) {
     DeviceState* root = m.root;
     HIP_TRY(hipSetDevice(root->device));
     for (uint32_t r = 0; r < m.ranks.size(); ++r) {
@@ -577,16 +578,26 @@ static int multi_untile(const rttnw_params& p, const MultiPlan& m) {
         HIP_TRY(hipMemcpyAsync(m.gathered(r), m.packed(r), m.chunk, hipMemcpyDeviceToDevice, root->stream.get()));
         if (m.aux_chunk) HIP_TRY(hipMemcpyAsync(m.gathered_aux(r), m.aux(r), m.aux_chunk, hipMemcpyDeviceToDevice, root->stream.get()));
     }
-    if (int rc = rttnw_untile_device(p.width, p.height, p.tile_world, p.precision, root->gathered.p, root->linear.p, root->rgba.p, root->stream.get())) return rc;
-    if (m.aux_chunk) // ... and the samples and standard-error maps of the auxiliary records
-        if (int rc = RT_BY_PRECISION(p.precision, untile_aux_launch, p.width, p.height, p.tile_world, (const double*)root->gathered_aux.p, (uint32_t*)root->ad_spp.p,
-                                     (double*)root->ad_stderr.p, root->stream.get())) return rc;
+    return 0;
+}
+// ... and, once the image is enqueued behind them, every device's stream has finished
+static int multi_finish_streams(const MultiPlan& m) {
     for (DeviceState* d : m.dev_state) {
         HIP_TRY(hipSetDevice(d->device));
         HIP_TRY(hipStreamSynchronize(d->stream.get()));
     }
-    HIP_TRY(hipSetDevice(root->device));
+    HIP_TRY(hipSetDevice(m.root->device));
     return 0;
+}
+// The frame's image (and, of auxiliary records, its samples and standard-error maps) made of the gathered tiles on the root
+static int multi_untile(const rttnw_params& p, const MultiPlan& m) {
+    DeviceState* root = m.root;
+    if (int rc = multi_join_local(m)) return rc;
+    if (int rc = rttnw_untile_device(p.width, p.height, p.tile_world, p.precision, root->gathered.p, root->linear.p, root->rgba.p, root->stream.get())) return rc;
+    if (m.aux_chunk) // ... and the samples and standard-error maps of the auxiliary records
+        if (int rc = RT_BY_PRECISION(p.precision, untile_aux_launch, p.width, p.height, p.tile_world, (const double*)root->gathered_aux.p, (uint32_t*)root->ad_spp.p,
+                                     (double*)root->ad_stderr.p, root->stream.get())) return rc;
+    return multi_finish_streams(m);
 }
 // The ranks' buffers to the root's gather buffers, by the transport the call uses (MultiEnv), falling through from RCCL to the peer copies
 static int multi_gather(const MultiPlan& m, bool& use_peer, bool& fell_back) {
@@ -638,7 +649,8 @@ extern "C" int rttnw_render_multi(rttnw_scene* s, const rttnw_camera_desc* cam, 
 // why).  Rank r runs render_adaptive_t's passes over ITS tiles — render_tiles_t with tile_rank = r — but the loop is pass-major, rank-minor: a pass
 // is enqueued on every live rank's stream before the host waits for any of them, so the devices of a node work side by side.
 // rttnw_render_adaptive_resume is the same render begun from, and left as, a state (adaptive_node_render runs both): its passes go by LEVEL, the
-// number of passes a pixel has behind it.
+// number of passes a pixel has behind it.  rttnw_render_adaptive_region is the resumed render over a SELECTION — a window of the frame, or a mask
+// inside it —, where a pixel may hold no samples yet: only selected pixels are ever active, and the outputs are the window's.
 // ---------------------------------------------------------------------------------------------
 namespace rt {
 // ---- the state of rttnw_render_adaptive_resume on the host (include/rttnw_hip.h has the layout): its header, its checks, and the permutation between
@@ -667,9 +679,11 @@ struct LevelPlan {
     uint32_t first = 0;         // the lowest level n / B a pixel of the state stands at
     std::vector<uint32_t> last; // per rank: the highest
 };
-// What rttnw_render_adaptive_resume refuses of a state_in (p and a have passed refuse_adaptive_misuse); `first`: the lowest level in it
-static int refuse_state_misuse(const rttnw_params& p, const rttnw_adaptive& a, const rttnw_camera_desc* cam, const double* st, uint32_t& first) {
-    const std::string call = "render_adaptive_resume: state_in: ";
+// What `caller` (rttnw_render_adaptive_resume, rttnw_render_adaptive_region) refuses of a state_in (p and a have passed refuse_adaptive_misuse);
+// `first`: the lowest level in it.  `allow_empty` (the region form): a record of twelve zeros — a pixel that holds no samples yet — is accepted.
+static int refuse_state_misuse(const char* caller, bool allow_empty, const rttnw_params& p, const rttnw_adaptive& a, const rttnw_camera_desc* cam,
+                               const double* st, uint32_t& first) {
+    const std::string call = std::string(caller) + ": state_in: ";
     double want[STATE_HEADER_DOUBLES];
     state_header(p, a, cam, want);
     for (uint32_t i = 0; i < (cam ? STATE_HEADER_FIELDS : 16u); ++i) {
@@ -687,7 +701,13 @@ static int refuse_state_misuse(const rttnw_params& p, const rttnw_adaptive& a, c
     double lowest = cap;
     const size_t npx = size_t(p.width) * p.height;
     for (size_t q = 0; q < npx; ++q) {
-        const double n = st[STATE_HEADER_DOUBLES + q * STATE_RECORD_DOUBLES + 3], k = st[STATE_HEADER_DOUBLES + q * STATE_RECORD_DOUBLES + 7];
+        const double* rec = st + STATE_HEADER_DOUBLES + q * STATE_RECORD_DOUBLES;
+        const double n = rec[3], k = rec[7];
+        if (allow_empty && n == 0.0) {
+            if (std::all_of(rec, rec + STATE_RECORD_DOUBLES, [](double v) { return v == 0.0; })) { lowest = 0.0; continue; }
+            set_last_error(call + "a record's n is 0 but the record is not empty (a pixel without samples is twelve zeros) (pixel " + std::to_string(q) + ")");
+            return RTTNW_ERR_INVALID;
+        }
         const char* why = !whole(n) ? "a record's n is not a finite integer" : !whole(k) ? "a record's k is not a finite integer"
                         : n < B ? "a record's n is below pass_spp" : std::fmod(n, B) != 0.0 ? "a record's n is not a multiple of pass_spp"
                         : n > cap ? "the state holds more samples than the cap (a record's n exceeds spp)"
@@ -716,6 +736,19 @@ struct AdaptiveSlots {
     uint32_t* scan(const MultiPlan& m, uint32_t r) const { return quads(m, r) + size_t(L.tiles_per_rank) * 16; }
     double* records(const MultiPlan& m, uint32_t r) const { return (double*)(m.ranks[r].d->multi_ad_records.p + records_chunk * m.ranks[r].slot); }
     uint8_t* marks(const MultiPlan& m, uint32_t r) const { return m.ranks[r].d->multi_ad_marks.p + active_chunk * m.ranks[r].slot; }
+    uint8_t* select(const MultiPlan& m, uint32_t r) const { return m.ranks[r].d->multi_ad_select.p + active_chunk * m.ranks[r].slot; }
+};
+// The selection of rttnw_render_adaptive_region: the window [x0, x1) x [y0, y1) of the frame and, optionally, the mask inside it (the caller's array)
+struct RegionSelection {
+    uint32_t x0, y0, x1, y1;
+    const uint8_t* mask;
+    size_t pixels() const { return size_t(x1 - x0) * (y1 - y0); }
+    bool has(uint32_t x, uint32_t y) const { return x >= x0 && x < x1 && y >= y0 && y < y1 && (!mask || mask[size_t(y - y0) * (x1 - x0) + (x - x0)] != 0); }
+    // is (x, y), a selected pixel, the first selected pixel of its 2x2 block in row-major order?  (counts the blocks a list can hold)
+    bool opens_block(uint32_t x, uint32_t y) const {
+        if ((x & 1u) && has(x - 1u, y)) return false;
+        return !((y & 1u) && (has(x & ~1u, y - 1u) || has(x | 1u, y - 1u)));
+    }
 };
 static ListPass adaptive_rank_pass(const MultiPlan& m, const AdaptiveSlots& sl, uint32_t r, const rttnw_params& p, const rttnw_adaptive& a) {
     ListPass ad;
@@ -729,10 +762,13 @@ static ListPass adaptive_rank_pass(const MultiPlan& m, const AdaptiveSlots& sl, 
 
 // multi_prepare for the adaptive passes: every buffer of every rank, and what a first use brings for pass 0 AND for a refinement pass over all of
 // the rank's blocks — a list never holds more, so no later pass allocates (a hipMalloc between two ranks' launches would synchronise the device)
-// (`resumed`: the render starts from a state, so it has no pass 0; `records`: a state comes in or goes out)
+// (`resumed`: the render starts from a state, so it has no pass 0; `records`: a state comes in or goes out; `sel`, with `sel_blocks`: the region form —
+// a rank's lists hold at most sel_blocks[r] blocks, those with a selected pixel, which sizes its chunk sums; the mask goes to every device once, the
+// ranks get their selection bytes and the root the window's outputs in place of the frame's)
 static int adaptive_multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const MultiPlan& m,
-                                  const AdaptiveSlots& sl, bool resumed = false, bool records = false) {
-    if (int rc = multi_prepare_buffers(m)) return rc;
+                                  const AdaptiveSlots& sl, bool resumed = false, bool records = false, const RegionSelection* sel = nullptr,
+                                  const std::vector<uint32_t>* sel_blocks = nullptr) {
+    if (int rc = multi_prepare_buffers(m, sel == nullptr)) return rc;
     for (size_t k = 0; k < m.devices.size(); ++k) {
         DeviceState* d = m.dev_state[k];
         HIP_TRY(hipSetDevice(d->device));
@@ -742,12 +778,24 @@ static int adaptive_multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam
         HIP_TRY(d->multi_aux.grow(m.aux_chunk * m.dev_ranks[k]));
         if (records) HIP_TRY(d->multi_ad_records.grow(sl.records_chunk * m.dev_ranks[k]));
         if (resumed) HIP_TRY(d->multi_ad_marks.grow(sl.active_chunk * m.dev_ranks[k]));
+        if (!sel) continue;
+        HIP_TRY(d->multi_ad_select.grow(sl.active_chunk * m.dev_ranks[k]));
+        if (!sel->mask) continue;
+        HIP_TRY(d->rg_mask.grow(sel->pixels()));
+        HIP_TRY(hipMemcpy(d->rg_mask.p, sel->mask, sel->pixels(), hipMemcpyHostToDevice));
     }
     DeviceState* root = m.root;
     HIP_TRY(hipSetDevice(root->device));
     HIP_TRY(root->gathered_aux.grow(m.aux_chunk * m.ranks.size()));
-    HIP_TRY(root->ad_spp.grow(m.npx * sizeof(uint32_t)));
-    HIP_TRY(root->ad_stderr.grow(m.npx * 3 * sizeof(double)));
+    if (sel) {
+        HIP_TRY(root->rg_linear.grow(sel->pixels() * 3 * m.rsz));
+        HIP_TRY(root->rg_rgba.grow(sel->pixels() * 4));
+        HIP_TRY(root->rg_spp.grow(sel->pixels() * sizeof(uint32_t)));
+        HIP_TRY(root->rg_stderr.grow(sel->pixels() * 3 * sizeof(double)));
+    } else {
+        HIP_TRY(root->ad_spp.grow(m.npx * sizeof(uint32_t)));
+        HIP_TRY(root->ad_stderr.grow(m.npx * 3 * sizeof(double)));
+    }
     rttnw_params pr = p;
     pr.spp = a.pass_spp;
     for (uint32_t r = 0; r < m.ranks.size(); ++r) {
@@ -757,7 +805,7 @@ static int adaptive_multi_prepare(::rttnw_scene* s, const rttnw_camera_desc* cam
         if (!resumed)
             if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), d->stream.get(), nullptr, false, true, &ad)) return rc;
         ad.quads = sl.quads(m, r);
-        ad.n_quads = sl.tiles(r, p.tile_world) * 16u;
+        ad.n_quads = sel_blocks ? (*sel_blocks)[r] : sl.tiles(r, p.tile_world) * 16u;
         ad.first = false;
         if (ad.n_quads)
             if (int rc = render_tiles_any(s, d, cam, &pr, m.packed(r), d->stream.get(), nullptr, false, true, &ad)) return rc;
@@ -774,11 +822,12 @@ struct HostFree { void operator()(void* q) const { (void)hipHostFree(q); } };
 // the step before the loop brings every rank's records in (`upload`: per rank, in its packed order) and lists level lv.first; each list is then
 // made of the level's marks (adaptive_level_select_kernel) instead of the active bytes, a rank with an empty list stays in the loop while its
 // state holds pixels at a higher level, and a rank with nothing to trace at a level launches no trace kernel.  A fresh render is the case of one
-// level: the launches it always had.
+// level: the launches it always had.  With a selection (`sel`: rttnw_render_adaptive_region) the same step leaves only selected pixels active, those
+// without samples among them, and lv.first / lv.last are the selected pixels' — level 0 is then a list pass like every other.
 // `ms`: the ranks' device time so far; `refined`: samples they traced beyond a fresh render's pass 0.
 static int adaptive_multi_passes(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const MultiPlan& m,
-                                 const AdaptiveSlots& sl, const LevelPlan& lv, const std::vector<std::vector<double>>& upload, std::vector<Event>& ev,
-                                 uint32_t* counts, rttnw_stats* stats, std::vector<double>& ms, std::vector<uint64_t>& refined) {
+                                 const AdaptiveSlots& sl, const LevelPlan& lv, const RegionSelection* sel, const std::vector<std::vector<double>>& upload,
+                                 std::vector<Event>& ev, uint32_t* counts, rttnw_stats* stats, std::vector<double>& ms, std::vector<uint64_t>& refined) {
     const uint32_t ngpu = uint32_t(m.ranks.size()), n_passes = p.spp / a.pass_spp;
     std::vector<uint32_t> n_quads(ngpu, 0);
     std::vector<char> live(ngpu);
@@ -838,6 +887,11 @@ static int adaptive_multi_passes(::rttnw_scene* s, const rttnw_camera_desc* cam,
             HIP_TRY(hipMemcpyAsync(sl.records(m, r), upload[r].data(), upload[r].size() * sizeof(double), hipMemcpyHostToDevice, stream));
             if (int rc = RT_BY_PRECISION(p.precision, adaptive_state_import_launch, sl.records(m, r), m.packed(r), sl.state(m, r), sl.active(m, r),
                                          sl.L.pixels_per_rank, p.spp, a.rel_error, a.abs_error, stream)) return rc;
+            if (sel) {
+                pr.tile_rank = r;
+                if (int rc = RT_BY_PRECISION(p.precision, adaptive_region_activate_launch, s, d, &pr, sel->mask ? (const uint8_t*)d->rg_mask.p : nullptr,
+                                             sl.select(m, r), sl.state(m, r), sl.active(m, r), sel->x0, sel->y0, sel->x1, sel->y1, stream)) return rc;
+            }
             if (k < n_passes)
                 if (int rc = enqueue_list(r, k, stream)) return rc;
             HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), stream));
@@ -872,9 +926,12 @@ static int adaptive_multi_passes(::rttnw_scene* s, const rttnw_camera_desc* cam,
 // The render behind rttnw_render_adaptive_multi and rttnw_render_adaptive_resume, its arguments checked by them (`p`: tile_world = the number of
 // ranks; `single`: rttnw_render_adaptive_resume's ngpu == 0, one rank on the scene's own device).  state_in / state_out (each optional): the
 // render starts from, and leaves, a state (include/rttnw_hip.h); without a state_in it is the fresh render, launch for launch.
+// `sel` (rttnw_render_adaptive_region): only its pixels are ever active, a missing state_in stands for zero records, the levels are those of the
+// selected pixels, and the four outputs are the window's.
 static int adaptive_node_render(const char* call, ::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive* a,
                                 uint32_t ngpu, const int32_t* device_ids, bool single, const double* state_in, uint32_t first_level, double* state_out,
-                                double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, rttnw_stats* stats) {
+                                double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, rttnw_stats* stats,
+                                const RegionSelection* sel = nullptr) {
     DeviceGuard restore; // (the caller's device is current again after EVERY return below, the error paths included)
     MultiPlan m;
     m.single = single;
@@ -890,11 +947,11 @@ static int adaptive_node_render(const char* call, ::rttnw_scene* s, const rttnw_
     m.aux_chunk = size_t(sl.L.pixels_per_rank) * 4 * sizeof(double);
     // a state_in: its row-major records to every rank's packed order, on the host (pixels outside the image and pad tiles keep zero records)
     LevelPlan lv;
-    lv.resumed = state_in != nullptr;
+    lv.resumed = state_in != nullptr || sel != nullptr;
     lv.first = first_level;
     lv.last.assign(ngpu, 0);
     const size_t rank_doubles = size_t(sl.L.pixels_per_rank) * STATE_RECORD_DOUBLES;
-    std::vector<std::vector<double>> host_records(state_in || state_out ? ngpu : 0);
+    std::vector<std::vector<double>> host_records(lv.resumed || state_out ? ngpu : 0);
     for (std::vector<double>& v : host_records) v.assign(rank_doubles, 0.0);
     if (state_in)
         for (uint32_t y = 0; y < p.height; ++y)
@@ -904,10 +961,26 @@ static int adaptive_node_render(const char* call, ::rttnw_scene* s, const rttnw_
                 packed_place(x, y, sl.L, ngpu, owner, idx);
                 const double* rec = state_in + STATE_HEADER_DOUBLES + (size_t(y) * p.width + x) * STATE_RECORD_DOUBLES;
                 std::copy(rec, rec + STATE_RECORD_DOUBLES, host_records[owner].begin() + idx * STATE_RECORD_DOUBLES);
-                lv.last[owner] = std::max(lv.last[owner], uint32_t(rec[3]) / a->pass_spp);
+                if (!sel) lv.last[owner] = std::max(lv.last[owner], uint32_t(rec[3]) / a->pass_spp);
             }
+    // a selection: the levels its pixels stand at (an unselected pixel is never active), and per rank the blocks that hold a selected pixel
+    std::vector<uint32_t> sel_blocks(sel ? ngpu : 0, 0);
+    if (sel) {
+        lv.first = p.spp / a->pass_spp; // (nothing selected: no level to run)
+        for (uint32_t y = sel->y0; y < sel->y1; ++y)
+            for (uint32_t x = sel->x0; x < sel->x1; ++x) {
+                if (!sel->has(x, y)) continue;
+                uint32_t owner;
+                size_t idx;
+                packed_place(x, y, sl.L, ngpu, owner, idx);
+                const uint32_t level = uint32_t(host_records[owner][idx * STATE_RECORD_DOUBLES + 3]) / a->pass_spp;
+                lv.first = std::min(lv.first, level);
+                lv.last[owner] = std::max(lv.last[owner], level);
+                if (sel->opens_block(x, y)) ++sel_blocks[owner];
+            }
+    }
     // everything that allocates, before the first launch: buffers and workspaces, the ranks' events, their pinned words for the lists' totals
-    if (int rc = adaptive_multi_prepare(s, cam, p, *a, m, sl, lv.resumed, state_in || state_out)) return rc;
+    if (int rc = adaptive_multi_prepare(s, cam, p, *a, m, sl, lv.resumed, lv.resumed || state_out, sel, sel ? &sel_blocks : nullptr)) return rc;
     std::vector<Event> ev(size_t(ngpu) * 2);
     for (uint32_t r = 0; r < ngpu; ++r) {
         HIP_TRY(hipSetDevice(m.ranks[r].d->device));
@@ -928,7 +1001,7 @@ static int adaptive_node_render(const char* call, ::rttnw_scene* s, const rttnw_
         }
     std::vector<double> ms(ngpu, 0.0);
     std::vector<uint64_t> refined(ngpu, 0);
-    if (int rc = adaptive_multi_passes(s, cam, p, *a, m, sl, lv, host_records, ev, (uint32_t*)pinned, stats, ms, refined)) return rc;
+    if (int rc = adaptive_multi_passes(s, cam, p, *a, m, sl, lv, sel, host_records, ev, (uint32_t*)pinned, stats, ms, refined)) return rc;
     // every rank's sums to means and auxiliary records (a rank without a tile: zeros), in its device time like adaptive_output_kernel in the single
     // call's — and, before that, sums and noise state to its state records where the caller wants the state
     for (uint32_t r = 0; r < ngpu; ++r) {
@@ -944,7 +1017,14 @@ static int adaptive_node_render(const char* call, ::rttnw_scene* s, const rttnw_
     }
     bool use_peer = false, fell_back = false;
     if (int rc = multi_gather(m, use_peer, fell_back)) return rc;
-    if (int rc = multi_untile(p, m)) return rc;
+    if (sel) { // the window's outputs in place of the frame's
+        DeviceState* root = m.root;
+        if (int rc = multi_join_local(m)) return rc;
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_region_window_launch, p.width, p.height, p.tile_world, root->gathered.p, (const double*)root->gathered_aux.p,
+                                     root->rg_linear.p, root->rg_rgba.p, (uint32_t*)root->rg_spp.p, (double*)root->rg_stderr.p, sel->x0, sel->y0, sel->x1,
+                                     sel->y1, root->stream.get())) return rc;
+        if (int rc = multi_finish_streams(m)) return rc;
+    } else if (int rc = multi_untile(p, m)) return rc;
     for (uint32_t r = 0; r < ngpu && stats; ++r) {
         float t = 0;
         HIP_TRY(hipSetDevice(m.ranks[r].d->device));
@@ -971,9 +1051,10 @@ static int adaptive_node_render(const char* call, ::rttnw_scene* s, const rttnw_
     DeviceState* root = m.root;
     HIP_TRY(hipSetDevice(root->device));
     hipError_t e = hipSuccess;
-    if (out_spp) e = hipMemcpy(out_spp, root->ad_spp.p, m.npx * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_stderr_rgb) e = hipMemcpy(out_stderr_rgb, root->ad_stderr.p, m.npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    return copy_image_out(call, root->rgba, root->linear, p.precision, m.npx, out_rgba8, out_linear_rgb, e);
+    const size_t out_px = sel ? sel->pixels() : m.npx;
+    if (out_spp) e = hipMemcpy(out_spp, (sel ? root->rg_spp : root->ad_spp).p, out_px * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_stderr_rgb) e = hipMemcpy(out_stderr_rgb, (sel ? root->rg_stderr : root->ad_stderr).p, out_px * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    return copy_image_out(call, sel ? root->rg_rgba : root->rgba, sel ? root->rg_linear : root->linear, p.precision, out_px, out_rgba8, out_linear_rgb, e);
 }
 } // namespace rt
 
@@ -1018,7 +1099,7 @@ extern "C" int rttnw_render_adaptive_resume(rttnw_scene* s, const rttnw_camera_d
     if (int rc = refuse_host_output_misuse("render_adaptive_resume", a->reserved0, &p)) return rc;
     uint32_t first_level = 0;
     if (state_in)
-        if (int rc = refuse_state_misuse(*p_in, *a, cam, state_in, first_level)) return rc;
+        if (int rc = refuse_state_misuse("render_adaptive_resume", false, *p_in, *a, cam, state_in, first_level)) return rc;
     p.tile_rank = 0; p.tile_world = std::max(ngpu, 1u);
     if (int rc = validate(s, cam, &p)) return rc;
     const int n_dev = rttnw_device_count();
@@ -1027,6 +1108,39 @@ extern "C" int rttnw_render_adaptive_resume(rttnw_scene* s, const rttnw_camera_d
     const int32_t own = s->device->device; // ngpu == 0: one rank where rttnw_render_adaptive runs
     return adaptive_node_render("render_adaptive_resume", s, cam, p, a, std::max(ngpu, 1u), ngpu ? device_ids : &own, ngpu == 0, state_in, first_level,
                                 state_out, out_linear_rgb, out_rgba8, out_spp, out_stderr_rgb, stats);
+}
+
+// rttnw_render_adaptive_region (include/rttnw_hip.h has the contract, DESIGN.md §10a "windowed form" the why): the resumed render over a selection
+extern "C" int rttnw_render_adaptive_region(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p_in, const rttnw_adaptive* a, uint32_t x0,
+                                            uint32_t y0, uint32_t x1, uint32_t y1, const uint8_t* mask, uint32_t ngpu, const int32_t* device_ids,
+                                            const double* state_in, double* state_out, double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp,
+                                            double* out_stderr_rgb, rttnw_stats* stats) {
+    using namespace rt;
+    // the refusals, in the header's order: none of them needs a device
+    if (!p_in || !a) { set_last_error("render_adaptive_region: NULL argument (p or a)"); return RTTNW_ERR_INVALID; }
+    if (x0 >= x1 || y0 >= y1 || x1 > p_in->width || y1 > p_in->height) {
+        set_last_error("render_adaptive_region: the window [x0, x1) x [y0, y1) must be non-empty and lie inside the width x height frame");
+        return RTTNW_ERR_INVALID;
+    }
+    if (ngpu > 64) { set_last_error("render_adaptive_region: ngpu must be 0 .. 64"); return RTTNW_ERR_INVALID; }
+    if (ngpu && !device_ids) { set_last_error("render_adaptive_region: device_ids is NULL with ngpu >= 1"); return RTTNW_ERR_INVALID; }
+    if (!ngpu && device_ids) { set_last_error("render_adaptive_region: device_ids must be NULL with ngpu == 0 (the current device)"); return RTTNW_ERR_INVALID; }
+    if (int rc = refuse_adaptive_misuse("render_adaptive_region", p_in, a)) return rc;
+    rttnw_params p = *p_in;
+    if (ngpu) { p.tile_rank = 0; p.tile_world = 1; } // (ngpu >= 1: the caller's are ignored; ngpu == 0: tile_world must be 1)
+    if (int rc = refuse_host_output_misuse("render_adaptive_region", a->reserved0, &p)) return rc;
+    uint32_t first_level = 0; // (not used: the levels are the selected pixels', adaptive_node_render)
+    if (state_in)
+        if (int rc = refuse_state_misuse("render_adaptive_region", true, *p_in, *a, cam, state_in, first_level)) return rc;
+    p.tile_rank = 0; p.tile_world = std::max(ngpu, 1u);
+    if (int rc = validate(s, cam, &p)) return rc;
+    const int n_dev = rttnw_device_count();
+    for (uint32_t r = 0; r < ngpu; ++r)
+        if (device_ids[r] < 0 || device_ids[r] >= n_dev) { set_last_error("render_adaptive_region: no such device in device_ids"); return RTTNW_ERR_INVALID; }
+    const int32_t own = s->device->device; // ngpu == 0: one rank where rttnw_render_adaptive runs
+    const RegionSelection sel{x0, y0, x1, y1, mask};
+    return adaptive_node_render("render_adaptive_region", s, cam, p, a, std::max(ngpu, 1u), ngpu ? device_ids : &own, ngpu == 0, state_in, 0, state_out,
+                                out_linear_rgb, out_rgba8, out_spp, out_stderr_rgb, stats, &sel);
 }
 
 // Release what the library keeps for the life of the process (today: the RCCL communicator sets of rttnw_render_multi).  Scenes

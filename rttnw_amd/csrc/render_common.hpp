@@ -240,6 +240,9 @@ struct DeviceState {
     // rttnw_render_adaptive_resume, slotted the same way: the ranks' packed state records (12 doubles per packed pixel, copied from and to the host)
     // and the marks of the level being listed (a byte per packed pixel)
     DevBuf<uint8_t> multi_ad_records, multi_ad_marks;
+    // rttnw_render_adaptive_region: the ranks' selection bytes (a byte per packed pixel, slotted like the active bytes; the mask is rg_mask, once per
+    // device) and, on the root, the window-sized samples and standard-error maps beside rg_linear / rg_rgba
+    DevBuf<uint8_t> multi_ad_select, rg_spp, rg_stderr;
 };
 // Words of build_quad_list's scan workspace over n_blocks blocks, and where its two totals (listed blocks, marked pixels) stand in it
 inline size_t quad_scan_words(uint32_t n_blocks) { return size_t((n_blocks + 63u) / 64u) * 3 + 2; }
@@ -316,6 +319,7 @@ inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, co
 //   render_region_t    rttnw_render_region's device half: selection, list, trace, resolve; the window's image on the device (d->rg_linear, d->rg_rgba)
 //   enqueue_quad_list, adaptive_finish_launch, untile_aux_launch   what rttnw_render_adaptive_multi (render_api.cpp) enqueues beside render_tiles_t's passes
 //   adaptive_state_import_launch, adaptive_state_export_launch, adaptive_level_select_launch, adaptive_rank_stats_t   what rttnw_render_adaptive_resume adds to those
+//   adaptive_region_activate_launch, adaptive_region_window_launch   ... and rttnw_render_adaptive_region to those: selection and first active bytes, the window's outputs
 #define RT_PRECISION_ENTRY_POINTS(X, R)                                                                                                              \
     X(R, render_tiles_t, (::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream, \
                           rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const ListPass* ad))                                          \
@@ -337,7 +341,13 @@ inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, co
                                         uint32_t rank_pixels, hipStream_t stream))                                                                   \
     X(R, adaptive_level_select_launch, (const uint8_t* d_active, const void* d_state, uint8_t* d_marks, uint32_t n_pixels, uint32_t level_n,         \
                                         hipStream_t stream))                                                                                         \
-    X(R, adaptive_rank_stats_t, (::rttnw_scene* s, DeviceState* d, const rttnw_params* p, rttnw_stats* stats))
+    X(R, adaptive_rank_stats_t, (::rttnw_scene* s, DeviceState* d, const rttnw_params* p, rttnw_stats* stats))                                      \
+    X(R, adaptive_region_activate_launch, (::rttnw_scene* s, DeviceState* d, const rttnw_params* p, const uint8_t* d_mask, uint8_t* d_select,       \
+                                           const void* d_state, uint8_t* d_active, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,               \
+                                           hipStream_t stream))                                                                                      \
+    X(R, adaptive_region_window_launch, (uint32_t width, uint32_t height, uint32_t world, const void* d_gathered, const double* d_gathered_aux,     \
+                                         void* d_linear_rgb, uint8_t* d_rgba8, uint32_t* d_spp, double* d_stderr, uint32_t x0, uint32_t y0,         \
+                                         uint32_t x1, uint32_t y1, hipStream_t stream))
 #define RT_DECLARE_T(R, name, params) template <typename> int name params;
 #define RT_EXTERN_T(R, name, params) extern template int name<R> params;
 #define RT_INSTANTIATE_T(R, name, params) template int name<R> params;

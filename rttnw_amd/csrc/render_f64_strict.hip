@@ -27,5 +27,9 @@ template int adaptive_state_import_launch<double>(const double*, void*, void*, u
 template int adaptive_state_export_launch<double>(const void*, const void*, double*, uint32_t, uint32_t, hipStream_t);
 template int adaptive_level_select_launch<double>(const uint8_t*, const void*, uint8_t*, uint32_t, uint32_t, hipStream_t);
 template int adaptive_rank_stats_t<double>(::rttnw_scene*, DeviceState*, const rttnw_params*, rttnw_stats*);
+template int adaptive_region_activate_launch<double>(::rttnw_scene*, DeviceState*, const rttnw_params*, const uint8_t*, uint8_t*, const void*, uint8_t*, uint32_t,
+                                                     uint32_t, uint32_t, uint32_t, hipStream_t);
+template int adaptive_region_window_launch<double>(uint32_t, uint32_t, uint32_t, const void*, const double*, void*, uint8_t*, uint32_t*, double*, uint32_t, uint32_t,
+                                                   uint32_t, uint32_t, hipStream_t);
 } // namespace RT_ARITH_NS
 } // namespace rt

@@ -3,6 +3,7 @@
 #pragma once
 #include "trace_kernels.hpp"
 #include "region_kernels.hpp"
+#include "adaptive_region_kernels.hpp"
 
 namespace rt {
 inline namespace RT_ARITH_NS {
@@ -405,6 +406,39 @@ int adaptive_rank_stats_t(::rttnw_scene* s, DeviceState* d, const rttnw_params* 
     const RenderConsts rc = base_consts(p, *flat, L);
     if (int g = fill_stats<R>(d, *ds, *flat, plan_for<R>(*flat, false, false), rc, false, nullptr, stats)) return g;
     stats->samples = 0;
+    return RTTNW_OK;
+}
+
+// rttnw_render_adaptive_region's launches of its own (render_api.cpp adaptive_node_render has the level loop, which is the resumed render's): behind
+// the state's import, the rank's selection bytes (region_select_kernel over ITS tiles: p->tile_rank / p->tile_world; d_mask: the window-sized mask on
+// this device, nullptr = the whole window) and the active bytes the call starts from; and, on the root, the window's four outputs from the gathered
+// means and auxiliary records.
+template <typename R>
+int adaptive_region_activate_launch(::rttnw_scene* s, DeviceState* d, const rttnw_params* p, const uint8_t* d_mask, uint8_t* d_select, const void* d_state,
+                                    uint8_t* d_active, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, hipStream_t stream) {
+    const FlatScene* flat = nullptr;
+    DeviceScene<R>* ds = nullptr;
+    if (int rc = bind_scene<R>(s, d, flat, ds)) return rc;
+    rttnw_tile_layout L;
+    fill_layout(p->width, p->height, p->tile_world, L);
+    const RenderConsts rc = base_consts(p, *flat, L);
+    const dim3 grid((L.pixels_per_rank + 255u) / 256u), block(256);
+    hipLaunchKernelGGL(region_select_kernel<R>, grid, block, 0, stream, d_mask, d_select, rc, L.pixels_per_rank, x0, y0, x1, y1);
+    hipLaunchKernelGGL(adaptive_region_activate_kernel<R>, grid, block, 0, stream, (const uint8_t*)d_select, (const AdaptivePixel*)d_state, d_active,
+                       L.pixels_per_rank);
+    HIP_TRY(hipGetLastError());
+    return RTTNW_OK;
+}
+template <typename R>
+int adaptive_region_window_launch(uint32_t width, uint32_t height, uint32_t world, const void* d_gathered, const double* d_gathered_aux, void* d_linear_rgb,
+                                  uint8_t* d_rgba8, uint32_t* d_spp, double* d_stderr, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                                  hipStream_t stream) {
+    rttnw_tile_layout L;
+    fill_layout(width, height, world, L);
+    dim3 block(32, 8), grid((x1 - x0 + 31) / 32, (y1 - y0 + 7) / 8);
+    hipLaunchKernelGGL(adaptive_region_window_kernel<R>, grid, block, 0, stream, (const R*)d_gathered, d_gathered_aux, (R*)d_linear_rgb, d_rgba8, d_spp,
+                       d_stderr, L.tiles_x, world, L.pixels_per_rank, x0, y0, x1, y1);
+    HIP_TRY(hipGetLastError());
     return RTTNW_OK;
 }
 

@@ -118,6 +118,47 @@ def render_adaptive_resume(scene, cam, params, state=None, device_ids=None, pass
     return lin, rgba, spp, se, (st[0] if device_ids is None else list(st)), st_out
 
 
+def render_adaptive_region(scene, cam, params, x0, y0, x1, y1, mask=None, state=None, device_ids=None, pass_spp=64, rel_error=0.02, abs_error=0.0,
+                           want_state=True):
+    """`rttnw_render_adaptive_region`: `render_adaptive_resume` over the pixels [x0, x1) x [y0, y1) of the frame — all of them, or those whose byte
+    of `mask` ((y1-y0) x (x1-x0), nonzero = selected) is set.  `state` is the frame-sized array an earlier call of this function or of
+    `render_adaptive_resume` returned, in which a pixel never sampled is a record of zeros; None stands for all zeros.  Only selected pixels are
+    traced, each to the bits a fresh whole-frame adaptive render under this cap and these tolerances gives it; the others keep their records.
+    The same `spp_chunk` default.  Returns (linear hxwx3 f64, rgba8 hxwx4 u8, spp_map hxw u32, stderr hxwx3 f64, Stats or [Stats per rank],
+    state or None), h = y1 - y0, w = x1 - x0; a pixel of the window without samples is zero everywhere, alpha included."""
+    import copy
+    b = library.product()
+    p = copy.copy(params)
+    if p.spp_chunk == 0:
+        p.spp_chunk = max(1, pass_spp // 16)
+    h, w = max(int(y1) - int(y0), 0), max(int(x1) - int(x0), 0)
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.shape != (h, w):
+            raise ValueError("render_adaptive_region: the mask must be (y1 - y0) x (x1 - x0) = %d x %d, got %s" % (h, w, m.shape))
+    lin = np.zeros((h, w, 3), dtype=np.float64)
+    rgba = np.zeros((h, w, 4), dtype=np.uint8)
+    spp = np.zeros((h, w), dtype=np.uint32)
+    se = np.zeros((h, w, 3), dtype=np.float64)
+    n_doubles = int(b.adaptive_state_doubles(p.width, p.height))
+    st_in = None
+    if state is not None:
+        st_in = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
+        if st_in.size != n_doubles:
+            raise ValueError("render_adaptive_region: a state of a %dx%d frame holds %d doubles, got %d" % (p.width, p.height, n_doubles, st_in.size))
+    st_out = np.zeros(n_doubles, dtype=np.float64) if want_state else None
+    n = 0 if device_ids is None else len(device_ids)
+    ids = None if device_ids is None else (C.c_int32 * max(n, 1))(*device_ids)
+    st = (Stats * max(n, 1))()
+    a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
+    rc = b.render_adaptive_region(scene.handle, C.byref(cam), C.byref(p), C.byref(a), x0, y0, x1, y1, None if m is None else m.ctypes.data, n, ids,
+                                  None if st_in is None else st_in.ctypes.data, None if st_out is None else st_out.ctypes.data, lin.ctypes.data,
+                                  rgba.ctypes.data, spp.ctypes.data, se.ctypes.data, C.cast(st, C.c_void_p))
+    check(rc, b, "rttnw_render_adaptive_region")
+    return lin, rgba, spp, se, (st[0] if device_ids is None else list(st)), st_out
+
+
 def render_features(scene, cam, params):
     """`rttnw_render_features`: the first hit of the render's own camera rays, averaged over `params.spp` samples per pixel.
     Returns {"albedo": HxWx3, "normal": HxWx3, "depth": HxW, "alpha": HxW (all f64), "stats": Stats}."""
