@@ -111,6 +111,15 @@ pub struct rttnw_denoise_params {
     pub sigma_depth: f64,
 }
 
+/// What `rttnw_render_adaptive_denoised` takes beside the stopping rule (include/rttnw_hip.h states the contract).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rttnw_guided {
+    pub feature_spp: u32,
+    pub reserved0: u32,
+    pub denoise: rttnw_denoise_params,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct rttnw_tile_layout {
@@ -200,6 +209,7 @@ extern "C" {
     pub fn rttnw_adaptive_state_doubles(width: u32, height: u32) -> u64;
     pub fn rttnw_render_adaptive_resume(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, ngpu: u32, device_ids: *const i32, state_in: *const f64, state_out: *mut f64, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_spp: *mut u32, out_stderr_rgb: *mut f64, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_render_adaptive_region(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, x0: u32, y0: u32, x1: u32, y1: u32, mask: *const u8, ngpu: u32, device_ids: *const i32, state_in: *const f64, state_out: *mut f64, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_spp: *mut u32, out_stderr_rgb: *mut f64, stats: *mut rttnw_stats) -> c_int;
+    pub fn rttnw_render_adaptive_denoised(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, g: *const rttnw_guided, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_spp: *mut u32, out_stderr_rgb: *mut f64, out_raw_linear_rgb: *mut f64, out_raw_stderr_rgb: *mut f64, state_out: *mut f64, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_render_features(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, out_albedo: *mut f64, out_normal: *mut f64, out_depth: *mut f64, out_alpha: *mut f64, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_render_region(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, x0: u32, y0: u32, x1: u32, y1: u32, mask: *const u8, out_linear_rgb: *mut f64, out_rgba8: *mut u8, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_denoise(width: u32, height: u32, linear_rgb: *const f64, variance_rgb: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, d: *const rttnw_denoise_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;

@@ -211,6 +211,20 @@ impl Scene {
         ok(unsafe { ffi::rttnw_render_adaptive_region(self.raw, cam, p, a, x0, y0, x1, y1, mask.map_or(ptr::null(), |m| m.as_ptr()), devices.len() as u32, ids, state.map_or(ptr::null(), |s| s.as_ptr()), out.as_mut_ptr(), ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), stats.as_mut_ptr()) })?;
         Ok((rgba, spp, stderr, stats, out))
     }
+    /// Adaptive sampling stopped on the noise of the FILTERED image (`rttnw_render_adaptive_denoised`): the adaptive rounds and `denoise`'s passes
+    /// alternate on the device, on one GPU.  Returns (the denoised image as RGBA8, samples per pixel, sqrt of the filtered variance, stats, the
+    /// state, which `render_adaptive_resume` accepts).
+    pub fn render_adaptive_denoised(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, a: &ffi::rttnw_adaptive, g: &ffi::rttnw_guided) -> Result<(Vec<u8>, Vec<u32>, Vec<f64>, ffi::rttnw_stats, Vec<f64>)> {
+        let n = p.width as usize * p.height as usize;
+        let doubles = unsafe { ffi::rttnw_adaptive_state_doubles(p.width, p.height) } as usize;
+        let mut rgba = vec![0u8; n * 4];
+        let mut spp = vec![0u32; n];
+        let mut stderr = vec![0f64; n * 3];
+        let mut stats = ffi::rttnw_stats::default();
+        let mut out = vec![0f64; doubles];
+        ok(unsafe { ffi::rttnw_render_adaptive_denoised(self.raw, cam, p, a, g, ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), out.as_mut_ptr(), &mut stats) })?;
+        Ok((rgba, spp, stderr, stats, out))
+    }
     /// First-hit feature buffers of the frame `render` renders (`rttnw_render_features`), row-major, top row first.
     pub fn render_features(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params) -> Result<Features> {
         let n = p.width as usize * p.height as usize;

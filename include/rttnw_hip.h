@@ -41,8 +41,8 @@ extern "C" {
                              * 3: RTTNW_F64_STRICT, rttnw_shutdown, RTTNW_BVH_AUTO (the default builder), rttnw_stats.reserved is a bit mask
                              *    (below), validate() rejects t_min < 0
                              * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region, rttnw_render_adaptive_multi,
-                             *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles and rttnw_render_adaptive_region came later, without a
-                             *  version bump: a caller detects each by its symbol) */
+                             *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region and
+                             *  rttnw_render_adaptive_denoised came later, without a version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -531,6 +531,58 @@ int rttnw_render_adaptive_region(rttnw_scene* s, const rttnw_camera_desc* cam, c
                                  uint32_t ngpu, const int32_t* device_ids, const double* state_in, double* state_out,
                                  double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb,
                                  rttnw_stats* stats);
+
+/* Adaptive sampling for an image that will be FILTERED: the adaptive render and rttnw_denoise alternate on the device, and a pixel stops on the
+ * standard error of the filtered image, not of its raw mean — smooth regions, where the filter averages many pixels, stop early; edges and
+ * detail, where it cannot, keep sampling (Rousselle et al. 2012; the variance travels through the filter as in SVGF).  One GPU, tile_world == 1,
+ * blocking.  (Came without a version bump, like rttnw_render_adaptive: detect it by its symbol.)
+ *
+ * Let B = a->pass_spp and the cap = p->spp, a positive multiple of B.
+ * Before round 0.  The features F of the frame are rttnw_render_features' with p->spp replaced by g->feature_spp (0 means B) and p's
+ *   sample_begin, seed and precision.  Every pixel is active.
+ * Round k = 0 .. cap / B - 1, while any pixel is active:
+ *   1. Trace.  Every active pixel gets samples [sample_begin + kB, sample_begin + (k+1)B): the jobs, chunk schedule, running-sum chain and
+ *      noise-state update of rttnw_render_adaptive's passes, as a list pass over the 2x2 blocks that hold an active pixel (round 0 included).  All
+ *      active pixels hold exactly kB samples, so a round is one level of rttnw_render_adaptive_resume's loop.
+ *   2. Raw values of EVERY pixel of the frame, stopped ones with their frozen values: mean = sum / n_q in the kernel's type, widened to double;
+ *      stderr as rttnw_render_adaptive defines it (+inf with fewer than two chunks); variance = stderr * stderr in double, not fused.
+ *   3. Filter.  (den, var_f) = rttnw_denoise's out_linear_rgb and out_variance_rgb on (mean, variance, F, g->denoise), bit for bit.
+ *   4. Stop.  An active pixel stops, for good, if its own stderr is 0 in r, g and b, or if for each of r, g, b var_f is finite and
+ *          sqrt(var_f) <= abs_error + rel_error * den             (linear radiance, den = the filtered value)
+ *      A stopped pixel is never reactivated.  Its decision depended on its neighbours' samples, so — unlike rttnw_render_adaptive — bit-identity
+ *      with a fresh render at another tolerance or cap is NOT promised, and neither is a resume contract of rttnw_render_adaptive_resume's kind.
+ * Outputs, of the last round that ran (each optional; row-major, top row first): out_linear_rgb w*h*3 the DENOISED image; out_rgba8 w*h*4 of
+ *   the denoised image (main.rs:219-225); out_spp w*h the n_q; out_stderr_rgb w*h*3 sqrt of the FILTERED variance; out_raw_linear_rgb w*h*3 the
+ *   unfiltered means (rttnw_render_adaptive's value); out_raw_stderr_rgb w*h*3 the unfiltered standard errors; state_out,
+ *   rttnw_adaptive_state_doubles(w, h) doubles: the ordinary adaptive state, which rttnw_render_adaptive_resume and rttnw_render_adaptive_region
+ *   accept.  `stats`: samples = sum_q n_q, kernel_ms = device time of everything the call runs, the feature pass and every denoise pass
+ *   included, reserved = the kernel form, the scene's sizes as usual.
+ * Contract.  The outputs are BIT-IDENTICAL to this host composition of entry points above, for every `precision`, kernel form and launch split
+ *   (RTTNW_CHUNK_SUM_BUDGET).  With active_0 = every pixel, round k calls
+ *     rttnw_render_adaptive_region(window = the whole frame, mask = active_k, ngpu = 0, cap (k+1)B, rel_error = abs_error = 0,
+ *                                  state_in = round k-1's state_out, NULL in round 0),
+ *     rttnw_denoise on that call's image and squared standard error, with F,
+ *   and applies step 4.  (Under a tolerance of 0 the region call itself leaves a pixel with zero stderr untraced: step 4's first condition is
+ *   what makes the two agree.)  With denoise.iterations == 0 the filter is the identity and out_spp, the raw and the filtered image, out_rgba8
+ *   and out_raw_stderr_rgb are rttnw_render_adaptive's under the same cap, B and tolerances.
+ * Where it lives.  Between rounds nothing frame-sized crosses to the host: per round the host reads 8 bytes, the length of the round's list and
+ *   the number of active pixels.  The composition pays a state copy both ways (96 bytes per pixel) and the six uploads of rttnw_denoise per round.
+ * Refusals, before the device is touched, in this order, each message naming render_adaptive_denoised and the field:
+ *   1. RTTNW_ERR_INVALID for a NULL p, a or g;
+ *   2. what rttnw_render_adaptive refuses among its own arguments, with its codes;
+ *   3. RTTNW_ERR_INVALID for g->reserved0 != 0, g->denoise.iterations > 8, g->denoise.reserved0 != 0, a negative or NaN sigma;
+ *   4. whatever rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes).
+ * Out of scope: a node-wide form (ngpu), a state_in, and windows or masks. */
+struct rttnw_guided {
+    uint32_t feature_spp;         /* samples per pixel of the feature buffers; 0 = a->pass_spp */
+    uint32_t reserved0;           /* must be 0 */
+    rttnw_denoise_params denoise; /* as rttnw_denoise: iterations 0 .. 8, sigmas (0 = the library default) */
+};
+typedef struct rttnw_guided rttnw_guided;
+int rttnw_render_adaptive_denoised(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
+                                   const rttnw_guided* g, double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp,
+                                   double* out_stderr_rgb, double* out_raw_linear_rgb, double* out_raw_stderr_rgb, double* state_out,
+                                   rttnw_stats* stats);
 
 /* Device-resident form, asynchronous on `hip_stream` (a hipStream_t; NULL = default stream).
  * Traces the tiles owned by (tile_rank, tile_world) and writes them in packed order into

@@ -18,6 +18,10 @@ without retracing a sample, on the same scene, size, seed and --pass-spp.  They 
 that window as the image: alone it samples the window from nothing; with --resume it starts from the state in FILE — a preview's noisy patch refined
 where one looks, the rest of the state untouched — and --save-state leaves the frame-sized state, in which pixels never sampled are zero records.  It
 combines with --spp, --pass-spp, --devices and --spp-map, and not with --window, --passes, --features or --denoise.
+--guided (with --noise only) stops pixels on the noise of the FILTERED image (rttnw_render_adaptive_denoised): the adaptive rounds and the denoiser
+alternate on the device, --denoise-iterations sets its passes, the image written is the denoised one (--denoise is implied), --spp-map and
+--save-state work as before, and the samples traced and the rounds run are printed.  It does not combine with --devices, --resume, --refine,
+--window or --passes.
 """
 import argparse
 import sys
@@ -79,6 +83,8 @@ def main(argv=None):
     ap.add_argument("--spp-map", default=None, help="adaptive sampling: also write a grey-scale PNG of samples / cap")
     ap.add_argument("--denoise", action="store_true", help="filter the image with the feature-guided denoiser (rttnw_denoise)")
     ap.add_argument("--denoise-iterations", type=int, default=5, help="a-trous passes of the denoiser (0..8)")
+    ap.add_argument("--guided", action="store_true", help="adaptive sampling: stop pixels on the noise of the denoised image "
+                    "(rttnw_render_adaptive_denoised); writes the denoised image")
     ap.add_argument("--features", default=None, metavar="PREFIX", help="write the first-hit feature buffers as PREFIX_albedo.png, "
                     "PREFIX_normal.png, PREFIX_depth.png, PREFIX_alpha.png")
     ap.add_argument("--window", default=None, metavar="X0,Y0,X1,Y1", help="render pixels [X0, X1) x [Y0, Y1) of the frame only (row 0 = top) "
@@ -94,6 +100,18 @@ def main(argv=None):
     except SystemExit:
         print("There was an error", file=sys.stderr)   # DummyError, main.rs:260-268
         raise
+    if args.guided:
+        if args.noise is None:
+            print("--guided needs --noise: it is the adaptive render stopped on the filtered image's noise", file=sys.stderr)
+            return 1
+        clash = [name for name, on in (("--devices", args.devices is not None), ("--resume", args.resume is not None), ("--refine", args.refine is not None),
+                                       ("--window", args.window is not None), ("--passes", args.passes > 1)) if on]
+        if clash:
+            print("--guided does not combine with %s: it runs on one GPU, over the whole frame, from nothing" % ", ".join(clash), file=sys.stderr)
+            return 1
+        if not 0 <= args.denoise_iterations <= 8:
+            print("--denoise-iterations must be 0 .. 8", file=sys.stderr)
+            return 1
     refine = None
     if args.refine is not None:
         if args.noise is None:
@@ -172,7 +190,7 @@ def main(argv=None):
               % (time.time() - t0, x1 - x0, y1 - y0, x0, y0, w, h, st.samples, st.kernel_ms))
         return 0
     features = None
-    if args.denoise or args.features:
+    if (args.denoise and not args.guided) or args.features:
         if args.denoise and args.passes > 1:
             print("--denoise does not combine with --passes", file=sys.stderr)
             return 1
@@ -192,7 +210,7 @@ def main(argv=None):
 
     def finish(linear, rgba, stderr):
         """The image as it is written: denoised when asked for."""
-        if not args.denoise:
+        if not args.denoise or args.guided:   # (--guided: the call's own image is the denoised one)
             return np.ascontiguousarray(rgba)
         _, out, _, ms = render.denoise(linear, features, stderr, iterations=args.denoise_iterations, want_ms=True)
         print("denoised: %d iterations, %.2f ms" % (args.denoise_iterations, ms))
@@ -210,7 +228,16 @@ def main(argv=None):
         if refine is not None and (refine[2] > w or refine[3] > h):
             print("--refine %s reaches outside the %dx%d frame" % (args.refine, w, h), file=sys.stderr)
             return 1
-        if refine is not None or args.resume is not None or args.save_state is not None:
+        rounds = ""
+        if args.guided:
+            g = render.render_adaptive_denoised(sc, cam, p, args.pass_spp, args.noise, args.abs_noise, iterations=args.denoise_iterations,
+                                                want_state=args.save_state is not None)
+            lin, rgba, spp_map, se, st = g["linear"], g["rgba8"], g["spp"], g["stderr"], g["stats"]
+            rounds = "; guided: %d rounds of %d, %d denoise iterations each" % (g["rounds"], p.spp // args.pass_spp, args.denoise_iterations)
+            if args.save_state is not None:
+                with open(args.save_state, "wb") as f:
+                    np.save(f, g["state"])
+        elif refine is not None or args.resume is not None or args.save_state is not None:
             state = None
             if args.resume is not None:
                 try:
@@ -246,8 +273,8 @@ def main(argv=None):
         full = w * h * p.spp
         if refine is not None:
             print("window %dx%d at (%d, %d) of %dx%d" % (refine[2] - refine[0], refine[3] - refine[1], refine[0], refine[1], w, h))
-        print("%.3fs (adaptive: %d samples traced of %d = %dx%dx%d, %.1f %%; kernels %.1f ms%s)"
-              % (time.time() - t0, st.samples, full, w, h, p.spp, 100.0 * st.samples / full, st.kernel_ms, per_rank))
+        print("%.3fs (adaptive: %d samples traced of %d = %dx%dx%d, %.1f %%; kernels %.1f ms%s%s)"
+              % (time.time() - t0, st.samples, full, w, h, p.spp, 100.0 * st.samples / full, st.kernel_ms, per_rank, rounds))
         return 0
     if args.passes > 1:
         def show(k, linear):

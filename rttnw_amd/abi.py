@@ -60,6 +60,11 @@ class Denoise(C.Structure):
                 ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
 
 
+class Guided(C.Structure):
+    """`rttnw_guided` — what `rttnw_render_adaptive_denoised` takes beside the stopping rule: the features' samples and the filter."""
+    _fields_ = [("feature_spp", C.c_uint32), ("reserved0", C.c_uint32), ("denoise", Denoise)]
+
+
 class TileLayout(C.Structure):
     _fields_ = [("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32), ("n_tiles", C.c_uint32),
                 ("tiles_per_rank", C.c_uint32), ("pixels_per_rank", C.c_uint32)]
@@ -119,6 +124,8 @@ PRODUCT_FUNCS = [
     ("render_adaptive_region", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("render_adaptive_denoised", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Guided), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("render_features", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.POINTER(Stats)]),
     ("render_region", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,

@@ -57,6 +57,38 @@ __global__ void denoise_finish_kernel(uint32_t n, uint32_t remodulate, const dou
         }                                                                                              \
     } while (0)
 
+// The passes on buffers that are already on the device (rttnw_denoise behind its uploads; rttnw_render_adaptive_denoised once per round):
+// prepare, `iterations` passes and the finish step, enqueued on `stream` — nothing else: no allocation, no copy, no wait.  d_c / d_v: the two
+// ping-pong buffers of w*h*3 doubles each (d_v unused without a variance), d_rgba w*h*4 bytes.  `out`: the linear image is left in d_c[out],
+// its variance in d_v[out].
+int denoise_passes_device(uint32_t width, uint32_t height, const double* d_in, const double* d_var, const double* d_albedo, const double* d_normal,
+                          const double* d_depth, const double* d_alpha, uint32_t iterations, const DenoiseParams& prm, double* const d_c[2],
+                          double* const d_v[2], uint8_t* d_rgba, hipStream_t stream, int& out) {
+    const uint32_t n = uint32_t(size_t(width) * height);
+    const bool has_var = d_var != nullptr;
+    const dim3 flat_block(256), value_grid((n * 3u + 255u) / 256u), pixel_grid((n + 255u) / 256u);
+    const dim3 block(32, 8), grid((width + 31) / 32, (height + 7) / 8);
+    int cur = 0; // d_c[cur] / d_v[cur] hold the current image once the first pass has run
+    const double *colour = d_in, *variance = d_var;
+    if (iterations > 0) {
+        // iterations == 0 is the identity: no demodulation either, the finish step only quantises
+        hipLaunchKernelGGL(denoise_prepare_kernel, value_grid, flat_block, 0, stream, n, d_in, variance, d_albedo, d_alpha, d_c[0], d_v[0]);
+        for (uint32_t i = 0; i < iterations; ++i) {
+            DenoiseView view{width, height, d_c[cur], has_var ? d_v[cur] : nullptr, d_normal, d_depth, d_alpha};
+            hipLaunchKernelGGL(denoise_pass_kernel, grid, block, 0, stream, view, prm, 1u << i, d_c[cur ^ 1], d_v[cur ^ 1]);
+            cur ^= 1;
+        }
+        colour = d_c[cur];
+        variance = has_var ? d_v[cur] : nullptr;
+    }
+    // (the finish step writes into the buffers the last pass read: never the ones it reads itself)
+    hipLaunchKernelGGL(denoise_finish_kernel, pixel_grid, flat_block, 0, stream, n, iterations > 0 ? 1u : 0u, colour, variance, d_albedo, d_alpha,
+                       d_c[cur ^ 1], d_rgba, d_v[cur ^ 1]);
+    DENOISE_TRY(hipGetLastError());
+    out = cur ^ 1;
+    return RTTNW_OK;
+}
+
 int denoise_device(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const double* albedo, const double* normal,
                    const double* depth, const double* alpha, uint32_t iterations, const DenoiseParams& prm, double* out_linear_rgb, uint8_t* out_rgba8,
                    double* out_variance_rgb, double* kernel_ms) {
@@ -66,8 +98,8 @@ int denoise_device(uint32_t width, uint32_t height, const double* linear_rgb, co
         return RTTNW_ERR_HIP;
     }
     const size_t npx = size_t(width) * height;
-    const uint32_t n = uint32_t(npx);
     const bool has_var = variance_rgb != nullptr;
+    // the upload step: the caller's arrays and the workspace on the device
     auto upload = [](DevBuf<double>& b, const double* src, size_t count) -> hipError_t {
         hipError_t e = b.alloc(count);
         if (e == hipSuccess) e = hipMemcpy(b.p, src, count * sizeof(double), hipMemcpyHostToDevice);
@@ -90,28 +122,14 @@ int denoise_device(uint32_t width, uint32_t height, const double* linear_rgb, co
     DENOISE_TRY(create_event(ev0));
     DENOISE_TRY(create_event(ev1));
 
+    // the passes step, between the two events
     const hipStream_t stream = nullptr;
-    const dim3 flat_block(256), value_grid((n * 3u + 255u) / 256u), pixel_grid((n + 255u) / 256u);
-    const dim3 block(32, 8), grid((width + 31) / 32, (height + 7) / 8);
+    double* const c[2] = {d_c[0].p, d_c[1].p};
+    double* const v[2] = {d_v[0].p, d_v[1].p};
+    int out = 0;
     DENOISE_TRY(hipEventRecord(ev0.get(), stream));
-    int cur = 0; // d_c[cur] / d_v[cur] hold the current image once the first pass has run
-    const double *colour = d_in.p, *variance = has_var ? d_var.p : nullptr;
-    if (iterations > 0) {
-        // iterations == 0 is the identity: no demodulation either, the finish step only quantises
-        hipLaunchKernelGGL(denoise_prepare_kernel, value_grid, flat_block, 0, stream, n, (const double*)d_in.p, variance, (const double*)d_albedo.p,
-                           (const double*)d_alpha.p, d_c[0].p, d_v[0].p);
-        for (uint32_t i = 0; i < iterations; ++i) {
-            DenoiseView view{width, height, d_c[cur].p, has_var ? d_v[cur].p : nullptr, d_normal.p, d_depth.p, d_alpha.p};
-            hipLaunchKernelGGL(denoise_pass_kernel, grid, block, 0, stream, view, prm, 1u << i, d_c[cur ^ 1].p, d_v[cur ^ 1].p);
-            cur ^= 1;
-        }
-        colour = d_c[cur].p;
-        variance = has_var ? d_v[cur].p : nullptr;
-    }
-    // (the finish step writes into the buffers the last pass read: never the ones it reads itself)
-    hipLaunchKernelGGL(denoise_finish_kernel, pixel_grid, flat_block, 0, stream, n, iterations > 0 ? 1u : 0u, colour, variance, (const double*)d_albedo.p,
-                       (const double*)d_alpha.p, d_c[cur ^ 1].p, d_rgba.p, d_v[cur ^ 1].p);
-    DENOISE_TRY(hipGetLastError());
+    if (int rc = denoise_passes_device(width, height, d_in.p, has_var ? d_var.p : nullptr, d_albedo.p, d_normal.p, d_depth.p, d_alpha.p, iterations, prm, c, v,
+                                       d_rgba.p, stream, out)) return rc;
     DENOISE_TRY(hipEventRecord(ev1.get(), stream));
     DENOISE_TRY(hipDeviceSynchronize());
     if (kernel_ms) {
@@ -119,9 +137,9 @@ int denoise_device(uint32_t width, uint32_t height, const double* linear_rgb, co
         DENOISE_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
         *kernel_ms = ms;
     }
-    if (out_linear_rgb) DENOISE_TRY(hipMemcpy(out_linear_rgb, d_c[cur ^ 1].p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_linear_rgb) DENOISE_TRY(hipMemcpy(out_linear_rgb, c[out], npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_rgba8) DENOISE_TRY(hipMemcpy(out_rgba8, d_rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_variance_rgb && has_var) DENOISE_TRY(hipMemcpy(out_variance_rgb, d_v[cur ^ 1].p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_variance_rgb && has_var) DENOISE_TRY(hipMemcpy(out_variance_rgb, v[out], npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
     return RTTNW_OK;
 }
 

@@ -7,15 +7,21 @@
 
 namespace rt {
 
-// rttnw_render_features' device half: host outputs (each optional), blocking.  Arguments were checked by the caller.
+// rttnw_render_features' device half: host outputs (each optional), blocking — and the same pass with its maps left on the device
+// (feature_kernels.hpp).  Arguments were checked by the caller.
 #define RT_FEATURE_ENTRY_POINTS(X, R)                                                                                                          \
     X(R, render_features_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* out_albedo, double* out_normal, \
-                             double* out_depth, double* out_alpha, rttnw_stats* stats))
+                             double* out_depth, double* out_alpha, rttnw_stats* stats))                                                       \
+    X(R, render_features_device_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* d_maps, hipStream_t stream))
 RT_DECLARE_BUILDS(RT_FEATURE_ENTRY_POINTS)
 
 // rttnw_denoise's device half (denoise.hip): host arrays in, host arrays out, blocking, on the current device.
 int denoise_device(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const double* albedo, const double* normal,
                    const double* depth, const double* alpha, uint32_t iterations, const DenoiseParams& prm, double* out_linear_rgb, uint8_t* out_rgba8,
                    double* out_variance_rgb, double* kernel_ms);
+// ... and its passes alone, enqueued on `stream` over buffers that are already on the device (the result: d_c[out], d_v[out], d_rgba)
+int denoise_passes_device(uint32_t width, uint32_t height, const double* d_in, const double* d_var, const double* d_albedo, const double* d_normal,
+                          const double* d_depth, const double* d_alpha, uint32_t iterations, const DenoiseParams& prm, double* const d_c[2],
+                          double* const d_v[2], uint8_t* d_rgba, hipStream_t stream, int& out);
 
 } // namespace rt

@@ -77,9 +77,12 @@ __global__ void feature_untile_kernel(const R* __restrict__ packed, double* __re
     alpha[o] = double(src[7]);
 }
 
+// The feature pass with its maps left ON THE DEVICE (rttnw_render_features behind it copies them out; rttnw_render_adaptive_denoised filters with
+// them round after round): `d_maps`, 8 * w * h doubles of the caller's on the scene's device — albedo w*h*3, normal w*h*3, depth w*h, alpha w*h,
+// row-major, top row first.  The two launches run between d->ev0 and d->ev1 on `stream`, and the stream has finished on return (the packed records
+// and the stack strip are this call's own).  Arguments were checked by the caller.
 template <typename R>
-int render_features_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* out_albedo, double* out_normal, double* out_depth,
-                      double* out_alpha, rttnw_stats* stats) {
+int render_features_device_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* d_maps, hipStream_t stream) {
     DeviceState* d = s->device;
     const FlatScene* flat = nullptr;
     DeviceScene<R>* ds = nullptr;
@@ -95,13 +98,10 @@ int render_features_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
     const size_t extra = rc.stack_depth > LDS_STACK_ENTRIES ? rc.stack_depth - LDS_STACK_ENTRIES : 0;
     DevBuf<R> packed;
     DevBuf<int32_t> spill;
-    DevBuf<double> maps; // albedo, normal, depth, alpha: 8 doubles per pixel
     HIP_TRY(packed.alloc(size_t(n_pixels) * FEATURE_CHANNELS));
     HIP_TRY(spill.alloc(threads * extra + threads)); // (+ threads: `spill + p` is a valid address for every lane even without extra entries)
-    HIP_TRY(maps.alloc(npx * 8));
-    double *m_albedo = maps.p, *m_normal = maps.p + npx * 3, *m_depth = maps.p + npx * 6, *m_alpha = maps.p + npx * 7;
+    double *m_albedo = d_maps, *m_normal = d_maps + npx * 3, *m_depth = d_maps + npx * 6, *m_alpha = d_maps + npx * 7;
 
-    const hipStream_t stream = nullptr;
     const size_t lds = size_t(LDS_STACK_ENTRIES + 1) * FEATURE_BLOCK * sizeof(int32_t);
     HIP_TRY(hipEventRecord(d->ev0.get(), stream));
     hipLaunchKernelGGL(feature_kernel<R>, dim3(grid), dim3(FEATURE_BLOCK), lds, stream, ds->view, camera_of<R>(cam), rc, R(p->background[0]),
@@ -112,12 +112,30 @@ int render_features_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
                        L.tiles_x);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(d->ev1.get(), stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return RTTNW_OK;
+}
+
+// rttnw_render_features: the pass above, then its maps to the caller's arrays and the stats
+template <typename R>
+int render_features_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* out_albedo, double* out_normal, double* out_depth,
+                      double* out_alpha, rttnw_stats* stats) {
+    DeviceState* d = s->device;
+    HIP_TRY(hipSetDevice(d->device));
+    const size_t npx = size_t(p->width) * p->height;
+    DevBuf<double> maps; // albedo, normal, depth, alpha: 8 doubles per pixel
+    HIP_TRY(maps.alloc(npx * 8));
+    if (int rc = render_features_device_t<R>(s, cam, p, maps.p, nullptr)) return rc;
     HIP_TRY(hipDeviceSynchronize());
+    const double *m_albedo = maps.p, *m_normal = maps.p + npx * 3, *m_depth = maps.p + npx * 6, *m_alpha = maps.p + npx * 7;
     if (out_albedo) HIP_TRY(hipMemcpy(out_albedo, m_albedo, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_normal) HIP_TRY(hipMemcpy(out_normal, m_normal, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_depth) HIP_TRY(hipMemcpy(out_depth, m_depth, npx * sizeof(double), hipMemcpyDeviceToHost));
     if (out_alpha) HIP_TRY(hipMemcpy(out_alpha, m_alpha, npx * sizeof(double), hipMemcpyDeviceToHost));
     if (stats) {
+        const FlatScene* flat = nullptr;
+        DeviceScene<R>* ds = nullptr;
+        if (int rc = bind_scene<R>(s, d, flat, ds)) return rc; // (uploaded by the pass: this only names the lowering and its arrays)
         std::memset(stats, 0, sizeof(*stats));
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, d->ev0.get(), d->ev1.get()));

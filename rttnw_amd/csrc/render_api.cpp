@@ -1,9 +1,12 @@
 // render_api.cpp — the extern "C" half of the device side of include/rttnw_hip.h: device state, render entry points,
-// rttnw_render_multi and rttnw_render_adaptive_multi (per-device streams, RCCL gather).  Host code only; the kernels and their launch code live in
-// render_f32.hip / render_f64.hip (render_common.hpp says why there are two).
+// rttnw_render_multi and rttnw_render_adaptive_multi (per-device streams, RCCL gather), rttnw_render_adaptive_denoised (the rounds that alternate the
+// adaptive passes with the denoiser's).  Host code only; the kernels and their launch code live in render_f32.hip / render_f64.hip (render_common.hpp
+// says why there are two), denoise.hip and guided.hip.
 // No CPU fallback: every entry point needs a HIP device.
 #include "render_common.hpp"
 #include "bvh_build.hpp"
+#include "feature_api.hpp"
+#include "guided.hpp"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -1141,6 +1144,157 @@ extern "C" int rttnw_render_adaptive_region(rttnw_scene* s, const rttnw_camera_d
     const RegionSelection sel{x0, y0, x1, y1, mask};
     return adaptive_node_render("render_adaptive_region", s, cam, p, a, std::max(ngpu, 1u), ngpu ? device_ids : &own, ngpu == 0, state_in, 0, state_out,
                                 out_linear_rgb, out_rgba8, out_spp, out_stderr_rgb, stats, &sel);
+}
+
+// ---------------------------------------------------------------------------------------------
+// rttnw_render_adaptive_denoised (include/rttnw_hip.h has the contract, DESIGN.md §10a "filter-guided form" the why): adaptive rounds whose stopping
+// rule reads the FILTERED image.  One rank on the scene's device, default stream.  A round is one level of the windowed form's loop — the list of the
+// 2x2 blocks that hold an alive pixel, render_tiles_t's list pass over it with the windowed form's arguments (a cap of (k+1)B and zero tolerances), the
+// running sums COPIED and turned into means and auxiliary records by adaptive_finish_launch (the sums themselves stay for the next round) — and then the
+// denoiser's passes and the stop kernel (guided.hpp), all on buffers that never leave the device: per round the host reads the list's two totals, 8
+// bytes, which are also the count of alive pixels.
+// ---------------------------------------------------------------------------------------------
+namespace rt {
+static int adaptive_denoised_render(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const rttnw_guided& g,
+                                    double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, double* out_raw_linear_rgb,
+                                    double* out_raw_stderr_rgb, double* state_out, rttnw_stats* stats) {
+    DeviceGuard restore; // (the caller's device is current again after EVERY return below, the error paths included)
+    DeviceState* d = s->device;
+    HIP_TRY(hipSetDevice(d->device));
+    rttnw_tile_layout L;
+    fill_layout(p.width, p.height, 1, L);
+    const size_t npx = size_t(p.width) * p.height, ppr = L.pixels_per_rank, rsz = p.precision == RTTNW_F32 ? sizeof(float) : sizeof(double);
+    const uint32_t n_blocks = L.n_tiles * 16u, B = a.pass_spp, n_rounds = p.spp / B;
+    const hipStream_t stream = nullptr;
+    // everything that allocates, before the first launch: the adaptive passes' buffers, this call's own, and what a list pass over every block needs
+    HIP_TRY(d->packed.grow(ppr * 4 * rsz));
+    HIP_TRY(d->ad_state.grow(ppr * sizeof(AdaptivePixel)));
+    HIP_TRY(d->ad_active.grow(ppr)); // (the resolve step's active bytes under the pass's own cap: not read here, the alive bytes decide)
+    HIP_TRY(d->list_quads.grow(size_t(n_blocks) * sizeof(uint32_t)));
+    HIP_TRY(d->list_scan.grow(quad_scan_words(n_blocks) * sizeof(uint32_t)));
+    DevBuf<uint8_t> alive, means, rgba;
+    DevBuf<uint32_t> spp;
+    DevBuf<double> aux, maps, mean, variance, raw_stderr, stderr_f, d_c[2], d_v[2], records;
+    HIP_TRY(alive.alloc(ppr));
+    HIP_TRY(means.alloc(ppr * 4 * rsz));
+    HIP_TRY(rgba.alloc(npx * 4));
+    HIP_TRY(spp.alloc(npx));
+    HIP_TRY(aux.alloc(ppr * 4));
+    HIP_TRY(maps.alloc(npx * 8));
+    HIP_TRY(mean.alloc(npx * 3));
+    HIP_TRY(variance.alloc(npx * 3));
+    HIP_TRY(raw_stderr.alloc(npx * 3));
+    HIP_TRY(stderr_f.alloc(npx * 3));
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(d_c[k].alloc(npx * 3));
+        HIP_TRY(d_v[k].alloc(npx * 3));
+    }
+    if (state_out) HIP_TRY(records.alloc(ppr * STATE_RECORD_DOUBLES));
+    Event ev0, ev1;
+    HIP_TRY(create_event(ev0));
+    HIP_TRY(create_event(ev1));
+    rttnw_params pass = p;
+    pass.spp = B;
+    ListPass ad;
+    ad.state = (AdaptivePixel*)d->ad_state.p;
+    ad.active = d->ad_active.p;
+    ad.quads = (const uint32_t*)d->list_quads.p;
+    ad.n_quads = n_blocks;
+    ad.first = false; // (round 0 too is a list pass on zero sums: 0 + c0 is the chain's first addition, as in the windowed form)
+    if (int rc = render_tiles_any(s, d, cam, &pass, d->packed.p, stream, nullptr, false, true, &ad)) return rc;
+    if (stats)
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_rank_stats_t, s, d, &p, stats)) return rc;
+
+    // before round 0: the feature maps, which stay on the device, and every pixel of the image alive on zero sums and zero noise state
+    rttnw_params pf = p;
+    pf.spp = g.feature_spp ? g.feature_spp : B;
+    if (int rc = RT_BY_PRECISION(p.precision, render_features_device_t, s, cam, &pf, maps.p, stream)) return rc;
+    float feature_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&feature_ms, d->ev0.get(), d->ev1.get()));
+    const double *m_albedo = maps.p, *m_normal = maps.p + npx * 3, *m_depth = maps.p + npx * 6, *m_alpha = maps.p + npx * 7;
+    const DenoiseParams prm = denoise_params(g.denoise.sigma_luminance, g.denoise.sigma_normal, g.denoise.sigma_depth, true);
+    double* const c[2] = {d_c[0].p, d_c[1].p};
+    double* const v[2] = {d_v[0].p, d_v[1].p};
+    HIP_TRY(hipEventRecord(ev0.get(), stream));
+    HIP_TRY(hipMemsetAsync(d->packed.p, 0, ppr * 4 * rsz, stream));
+    HIP_TRY(hipMemsetAsync(d->ad_state.p, 0, ppr * sizeof(AdaptivePixel), stream));
+    if (int rc = guided_begin_launch(alive.p, L.pixels_per_rank, p.width, p.height, stream)) return rc;
+    uint64_t samples = 0;
+    int out = 0;
+    for (uint32_t k = 0; k < n_rounds; ++k) {
+        // the list of this round — the alive bytes are its active AND its selection bytes — and, in one 8-byte copy, its length and the alive pixels
+        if (int rc = RT_BY_PRECISION(p.precision, enqueue_quad_list, alive.p, n_blocks, (uint32_t*)d->list_scan.p, (uint32_t*)d->list_quads.p, stream)) return rc;
+        uint32_t count[2] = {0, 0}; // listed blocks, alive pixels
+        HIP_TRY(hipMemcpy(count, quad_list_totals((uint32_t*)d->list_scan.p, n_blocks), sizeof(count), hipMemcpyDeviceToHost));
+        if (count[0] == 0) break; // every pixel has stopped
+        samples += uint64_t(count[1]) * B;
+        // 1. trace: the alive pixels, all of which hold exactly kB samples — one level
+        pass.sample_begin = p.sample_begin + k * B;
+        ad.n_quads = count[0];
+        ad.cap = (k + 1u) * B;
+        if (int rc = render_tiles_any(s, d, cam, &pass, d->packed.p, stream, nullptr, false, false, &ad)) return rc;
+        // 2. raw values of every pixel of the frame, by the adaptive render's own division on a copy of the sums
+        HIP_TRY(hipMemcpyAsync(means.p, d->packed.p, ppr * 4 * rsz, hipMemcpyDeviceToDevice, stream));
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_finish_launch, means.p, d->ad_state.p, aux.p, L.pixels_per_rank, L.n_tiles * 64u, stream)) return rc;
+        if (int rc = guided_raw_launch(p.precision, means.p, aux.p, mean.p, variance.p, raw_stderr.p, spp.p, p.width, p.height, stream)) return rc;
+        // 3. filter
+        if (int rc = denoise_passes_device(p.width, p.height, mean.p, variance.p, m_albedo, m_normal, m_depth, m_alpha, g.denoise.iterations, prm, c, v,
+                                           rgba.p, stream, out)) return rc;
+        // 4. stop
+        if (int rc = guided_stop_launch(c[out], v[out], raw_stderr.p, a.rel_error, a.abs_error, alive.p, stderr_f.p, p.width, p.height, stream)) return rc;
+    }
+    if (state_out)
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_state_export_launch, d->packed.p, d->ad_state.p, records.p, L.pixels_per_rank, L.n_tiles * 64u, stream)) return rc;
+    HIP_TRY(hipEventRecord(ev1.get(), stream));
+    HIP_TRY(hipDeviceSynchronize());
+    if (stats) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+        stats->kernel_ms = double(feature_ms) + double(ms);
+        stats->samples = samples;
+    }
+    // the outputs of the last round that ran
+    if (out_linear_rgb) HIP_TRY(hipMemcpy(out_linear_rgb, c[out], npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, rgba.p, npx * 4, hipMemcpyDeviceToHost));
+    if (out_spp) HIP_TRY(hipMemcpy(out_spp, spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_stderr_rgb) HIP_TRY(hipMemcpy(out_stderr_rgb, stderr_f.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_raw_linear_rgb) HIP_TRY(hipMemcpy(out_raw_linear_rgb, mean.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_raw_stderr_rgb) HIP_TRY(hipMemcpy(out_raw_stderr_rgb, raw_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (state_out) { // the packed records come back and go to their row-major places behind the header
+        std::vector<double> host_records(ppr * STATE_RECORD_DOUBLES);
+        HIP_TRY(hipMemcpy(host_records.data(), records.p, host_records.size() * sizeof(double), hipMemcpyDeviceToHost));
+        state_header(p, a, cam, state_out);
+        for (uint32_t y = 0; y < p.height; ++y)
+            for (uint32_t x = 0; x < p.width; ++x) {
+                uint32_t owner;
+                size_t idx;
+                packed_place(x, y, L, 1, owner, idx);
+                const double* rec = host_records.data() + idx * STATE_RECORD_DOUBLES;
+                std::copy(rec, rec + STATE_RECORD_DOUBLES, state_out + STATE_HEADER_DOUBLES + (size_t(y) * p.width + x) * STATE_RECORD_DOUBLES);
+            }
+    }
+    return RTTNW_OK;
+}
+} // namespace rt
+
+extern "C" int rttnw_render_adaptive_denoised(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, const rttnw_guided* g,
+                                              double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb,
+                                              double* out_raw_linear_rgb, double* out_raw_stderr_rgb, double* state_out, rttnw_stats* stats) {
+    using namespace rt;
+    // the refusals, in the header's order: none of them needs a device
+    if (!p || !a || !g) { set_last_error("render_adaptive_denoised: NULL argument (p, a or g)"); return RTTNW_ERR_INVALID; }
+    if (int rc = refuse_adaptive_misuse("render_adaptive_denoised", p, a)) return rc;
+    if (int rc = refuse_host_output_misuse("render_adaptive_denoised", a->reserved0, p)) return rc;
+    if (g->reserved0 != 0) { set_last_error("render_adaptive_denoised: g->reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (g->denoise.iterations > DENOISE_MAX_ITERATIONS) { set_last_error("render_adaptive_denoised: g->denoise.iterations: more than 8 iterations"); return RTTNW_ERR_INVALID; }
+    if (g->denoise.reserved0 != 0) { set_last_error("render_adaptive_denoised: g->denoise.reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (!(g->denoise.sigma_luminance >= 0.0) || !(g->denoise.sigma_normal >= 0.0) || !(g->denoise.sigma_depth >= 0.0)) {
+        set_last_error("render_adaptive_denoised: g->denoise: the sigmas (sigma_luminance, sigma_normal, sigma_depth) must be >= 0 (and not NaN)");
+        return RTTNW_ERR_INVALID;
+    }
+    if (int rc = validate(s, cam, p)) return rc;
+    return adaptive_denoised_render(s, cam, *p, *a, *g, out_linear_rgb, out_rgba8, out_spp, out_stderr_rgb, out_raw_linear_rgb, out_raw_stderr_rgb, state_out,
+                                    stats);
 }
 
 // Release what the library keeps for the life of the process (today: the RCCL communicator sets of rttnw_render_multi).  Scenes

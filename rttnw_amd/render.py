@@ -159,6 +159,38 @@ def render_adaptive_region(scene, cam, params, x0, y0, x1, y1, mask=None, state=
     return lin, rgba, spp, se, (st[0] if device_ids is None else list(st)), st_out
 
 
+def render_adaptive_denoised(scene, cam, params, pass_spp=64, rel_error=0.02, abs_error=0.0, iterations=5, feature_spp=0, sigma_luminance=0.0,
+                             sigma_normal=0.0, sigma_depth=0.0, want_state=True):
+    """`rttnw_render_adaptive_denoised`: adaptive rounds of `pass_spp` samples whose stopping rule reads the FILTERED image — after every round
+    the frame goes through `denoise`'s passes on the device (features of `feature_spp` samples, 0 = pass_spp) and a pixel stops once
+    sqrt(filtered variance) <= abs_error + rel_error * filtered value in every channel, or at `params.spp` samples.  The same `spp_chunk`
+    default as `render_adaptive`.  Returns a dict: "linear" HxWx3 f64 and "rgba8" HxWx4 u8 (the denoised image), "spp" HxW u32, "stderr" HxWx3
+    f64 (sqrt of the filtered variance), "raw_linear" and "raw_stderr" HxWx3 f64 (`render_adaptive`'s values), "state" (what
+    `render_adaptive_resume` takes, or None), "rounds" (rounds run) and "stats"."""
+    import copy
+    b = library.product()
+    p = copy.copy(params)
+    if p.spp_chunk == 0:
+        p.spp_chunk = max(1, pass_spp // 16)
+    h, w = p.height, p.width
+    out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "spp": np.zeros((h, w), dtype=np.uint32),
+           "stderr": np.zeros((h, w, 3)), "raw_linear": np.zeros((h, w, 3)), "raw_stderr": np.zeros((h, w, 3))}
+    state = np.zeros(int(b.adaptive_state_doubles(w, h)), dtype=np.float64) if want_state else None
+    st = Stats()
+    a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
+    g = abi.Guided(feature_spp=feature_spp, reserved0=0,
+                   denoise=abi.Denoise(iterations=iterations, reserved0=0, sigma_luminance=sigma_luminance, sigma_normal=sigma_normal,
+                                       sigma_depth=sigma_depth))
+    rc = b.render_adaptive_denoised(scene.handle, C.byref(cam), C.byref(p), C.byref(a), C.byref(g), out["linear"].ctypes.data,
+                                    out["rgba8"].ctypes.data, out["spp"].ctypes.data, out["stderr"].ctypes.data, out["raw_linear"].ctypes.data,
+                                    out["raw_stderr"].ctypes.data, None if state is None else state.ctypes.data, C.byref(st))
+    check(rc, b, "rttnw_render_adaptive_denoised")
+    out["state"] = state
+    out["rounds"] = int(out["spp"].max()) // pass_spp  # (every round traces its active pixels: the pixel that went furthest took part in all)
+    out["stats"] = st
+    return out
+
+
 def render_features(scene, cam, params):
     """`rttnw_render_features`: the first hit of the render's own camera rays, averaged over `params.spp` samples per pixel.
     Returns {"albedo": HxWx3, "normal": HxWx3, "depth": HxW, "alpha": HxW (all f64), "stats": Stats}."""
