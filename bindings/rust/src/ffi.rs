@@ -120,6 +120,15 @@ pub struct rttnw_guided {
     pub denoise: rttnw_denoise_params,
 }
 
+/// What `rttnw_render_preview` takes beside the stopping rule (include/rttnw_hip.h states the contract).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rttnw_preview {
+    pub level: u32,
+    pub feature_spp: u32,
+    pub denoise: rttnw_denoise_params,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct rttnw_tile_layout {
@@ -213,6 +222,8 @@ extern "C" {
     pub fn rttnw_render_features(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, out_albedo: *mut f64, out_normal: *mut f64, out_depth: *mut f64, out_alpha: *mut f64, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_render_region(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, x0: u32, y0: u32, x1: u32, y1: u32, mask: *const u8, out_linear_rgb: *mut f64, out_rgba8: *mut u8, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_denoise(width: u32, height: u32, linear_rgb: *const f64, variance_rgb: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, d: *const rttnw_denoise_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
+    pub fn rttnw_reconstruct(width: u32, height: u32, linear_rgb: *const f64, variance_rgb: *const f64, valid: *const u8, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, d: *const rttnw_denoise_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, out_valid: *mut u8, kernel_ms: *mut f64) -> c_int;
+    pub fn rttnw_render_preview(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, v: *const rttnw_preview, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_valid: *mut u8, out_spp: *mut u32, out_raw_linear_rgb: *mut f64, out_raw_stderr_rgb: *mut f64, state_out: *mut f64, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_render_tiles_device(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, d_packed: *mut c_void, hip_stream: *mut c_void, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_untile_device(width: u32, height: u32, world: u32, precision: u32, d_gathered: *const c_void, d_linear_rgb: *mut c_void, d_rgba8: *mut u8, hip_stream: *mut c_void) -> c_int;
     // ---- introspection

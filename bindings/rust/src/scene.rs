@@ -225,6 +225,21 @@ impl Scene {
         ok(unsafe { ffi::rttnw_render_adaptive_denoised(self.raw, cam, p, a, g, ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), out.as_mut_ptr(), &mut stats) })?;
         Ok((rgba, spp, stderr, stats, out))
     }
+    /// A frame from 1 pixel in 4^level (`rttnw_render_preview`): the adaptive render of the lattice `x % 2^level == 0 && y % 2^level == 0`, the
+    /// features of the whole frame and `reconstruct` over the two, on the device, on one GPU.  Returns (the reconstructed image as RGBA8, the
+    /// byte per pixel that says whether it holds a value, samples per pixel — 0 off the lattice —, stats, the state with zero records off the
+    /// lattice, which `render_adaptive_region` over the whole frame completes).
+    pub fn render_preview(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, a: &ffi::rttnw_adaptive, v: &ffi::rttnw_preview) -> Result<(Vec<u8>, Vec<u8>, Vec<u32>, ffi::rttnw_stats, Vec<f64>)> {
+        let n = p.width as usize * p.height as usize;
+        let doubles = unsafe { ffi::rttnw_adaptive_state_doubles(p.width, p.height) } as usize;
+        let mut rgba = vec![0u8; n * 4];
+        let mut valid = vec![0u8; n];
+        let mut spp = vec![0u32; n];
+        let mut stats = ffi::rttnw_stats::default();
+        let mut out = vec![0f64; doubles];
+        ok(unsafe { ffi::rttnw_render_preview(self.raw, cam, p, a, v, ptr::null_mut(), rgba.as_mut_ptr(), valid.as_mut_ptr(), spp.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), out.as_mut_ptr(), &mut stats) })?;
+        Ok((rgba, valid, spp, stats, out))
+    }
     /// First-hit feature buffers of the frame `render` renders (`rttnw_render_features`), row-major, top row first.
     pub fn render_features(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params) -> Result<Features> {
         let n = p.width as usize * p.height as usize;
@@ -282,6 +297,24 @@ pub fn denoise(linear: &[f64], variance: Option<&[f64]>, f: &Features, d: &ffi::
                            f.alpha.as_ptr(), d, out.as_mut_ptr(), rgba.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())
     })?;
     Ok((out, rgba))
+}
+
+/// `rttnw_reconstruct`: `denoise` over an image of which only the pixels with a nonzero byte in `valid` (w*h) hold a value; `linear` and
+/// `variance` are never read elsewhere.  Returns (linear w*h*3, RGBA8 w*h*4 with alpha 0 where nothing could be filled, the valid bytes).
+pub fn reconstruct(linear: &[f64], variance: Option<&[f64]>, valid: &[u8], f: &Features, d: &ffi::rttnw_denoise_params) -> Result<(Vec<f64>, Vec<u8>, Vec<u8>)> {
+    let n = f.width as usize * f.height as usize;
+    if linear.len() != n * 3 || variance.map_or(false, |v| v.len() != n * 3) || valid.len() != n || f.albedo.len() != n * 3 || f.normal.len() != n * 3 || f.depth.len() != n
+        || f.alpha.len() != n {
+        return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "reconstruct: array sizes do not match the image".into() });
+    }
+    let mut out = vec![0f64; n * 3];
+    let mut rgba = vec![0u8; n * 4];
+    let mut out_valid = vec![0u8; n];
+    ok(unsafe {
+        ffi::rttnw_reconstruct(f.width, f.height, linear.as_ptr(), variance.map_or(ptr::null(), |v| v.as_ptr()), valid.as_ptr(), f.albedo.as_ptr(), f.normal.as_ptr(),
+                               f.depth.as_ptr(), f.alpha.as_ptr(), d, out.as_mut_ptr(), rgba.as_mut_ptr(), ptr::null_mut(), out_valid.as_mut_ptr(), ptr::null_mut())
+    })?;
+    Ok((out, rgba, out_valid))
 }
 
 impl Drop for Scene {

@@ -41,8 +41,9 @@ extern "C" {
                              * 3: RTTNW_F64_STRICT, rttnw_shutdown, RTTNW_BVH_AUTO (the default builder), rttnw_stats.reserved is a bit mask
                              *    (below), validate() rejects t_min < 0
                              * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region, rttnw_render_adaptive_multi,
-                             *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region and
-                             *  rttnw_render_adaptive_denoised came later, without a version bump: a caller detects each by its symbol) */
+                             *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region,
+                             *  rttnw_render_adaptive_denoised, rttnw_reconstruct and rttnw_render_preview came later, without a version bump: a
+                             *  caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -583,6 +584,84 @@ int rttnw_render_adaptive_denoised(rttnw_scene* s, const rttnw_camera_desc* cam,
                                    const rttnw_guided* g, double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp,
                                    double* out_stderr_rgb, double* out_raw_linear_rgb, double* out_raw_stderr_rgb, double* state_out,
                                    rttnw_stats* stats);
+
+/* rttnw_denoise over an image of which only SOME pixels hold a value: a render of a mask or a lattice (rttnw_render_region,
+ * rttnw_render_adaptive_region), a state that is still being refined.  rttnw_denoise treats every pixel as a value — a pixel that was never
+ * sampled, linear 0, is averaged into its neighbours as black; this entry point drops the taps that hold nothing and FILLS the centres that hold
+ * nothing from the taps that remain.  Host arrays in and out, blocking, on the current device, no scene handle, no CPU fallback.  Everything is
+ * double.  (Came without a version bump: detect it by its symbol.)
+ *
+ * `valid`: w*h bytes, nonzero = the pixel holds a value.  The colour and the variance of a pixel with valid == 0 are NEVER READ (they may be NaN).
+ * Everything else is rttnw_denoise's contract — demodulation, the taps, the weights, the parameters and their defaults — with a flag H per
+ * pixel, H = (valid != 0) at first, carried through the passes:
+ * Prepare (only when iterations > 0).  A pixel with H is demodulated exactly as in rttnw_denoise.  A pixel without H and with alpha == 0 takes
+ *   c = albedo, variance 0 and H = 1: `albedo` is the background rttnw_render_features stores for a pixel whose every sample missed, which is what
+ *   every sample of a render returns there.  Any other pixel without H keeps H = 0.
+ * Pass i, stride 2^i, reads (c, v, H) and writes (c', v', H') into the other half of a ping-pong — H is ping-ponged like the colour, a pass never
+ *   reads a flag it writes.
+ *   A tap is dropped when it lies outside the image, has alpha == 0 or has H == 0 (so do the 3x3 taps of V, the centre's luminance variance).
+ *   A centre with alpha == 0 passes through, its flag included.
+ *   A centre with H: rttnw_denoise's operations, in its order, on the remaining taps; H' = 1 (a centre all of whose taps weigh 0 passes through).
+ *   A centre without H: tap weight w = h_x h_y * w_n * w_z — no colour stop, it has no colour to compare.  If sum w > 0: c' = sum w c / sum w
+ *     and H' = 1; with a variance input v' = sum w^2 var / (sum w)^2 over the accepted taps whose variance is finite, +inf if none is.
+ *     Otherwise c' = 0 and H' = 0.
+ *   Pass i reaches 2 * 2^i pixels to either side: a lattice of spacing 2^L is filled by pass L - 1 at the latest wherever the features let a
+ *   neighbour through.
+ * Finish.  A pixel with H is remodulated with its own albedo and alpha, as in rttnw_denoise; RGBA8 alpha 255, out_valid 1.  A pixel without H gets
+ *   linear 0, 0, 0, RGBA8 0, 0, 0, 0, variance +inf and out_valid 0.  With 0 iterations a valid pixel is copied as in rttnw_denoise (no
+ *   demodulation, no background fill) and an invalid one gets the outputs of a pixel without H.
+ * Outputs (each optional): out_linear_rgb w*h*3, out_rgba8 w*h*4, out_variance_rgb w*h*3 (written only when variance_rgb was given), out_valid
+ *   w*h bytes (0 or 1), kernel_ms: device time of the passes.
+ * Contract.  With every `valid` byte nonzero the three image outputs equal rttnw_denoise's bit for bit and out_valid is all 1.  The device code, a
+ *   host build of the same header (rttnw_amd/csrc/reconstruct.hpp) and a restatement in numpy give the same bits for every validity pattern.
+ * Refusals, before the device is touched, each message naming `reconstruct` and the field: rttnw_denoise's, with its codes (RTTNW_ERR_INVALID for a
+ *   NULL linear_rgb, albedo, normal, depth, alpha or d, width * height == 0, iterations > 8, reserved0 != 0, a negative or NaN sigma), and
+ *   RTTNW_ERR_INVALID for a NULL valid. */
+int rttnw_reconstruct(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const uint8_t* valid,
+                      const double* albedo, const double* normal, const double* depth, const double* alpha,
+                      const rttnw_denoise_params* d, double* out_linear_rgb, uint8_t* out_rgba8, double* out_variance_rgb,
+                      uint8_t* out_valid, double* kernel_ms);
+
+/* A frame from a fraction of its pixels: an adaptive render of the LATTICE x % 2^level == 0 && y % 2^level == 0 (frame coordinates, row 0 at the
+ * top; level 0 .. 6, so 1 pixel in 4^level), the features of the whole frame, and rttnw_reconstruct over the two — on the device.  A preview costs
+ * bounce 0 of every pixel (the features) plus 1 / 4^level of the trace.  One GPU, tile_world == 1, blocking.  (Came without a version bump: detect
+ * it by its symbol.)
+ *
+ * Contract.  Every output is BIT-IDENTICAL, for every `precision`, kernel form and launch split (RTTNW_CHUNK_SUM_BUDGET), to this host composition:
+ *   1. rttnw_render_adaptive_region(window = the whole frame, mask = the lattice, ngpu = 0, state_in = NULL) under p's cap and a's tolerances:
+ *      out_raw_linear_rgb, out_raw_stderr_rgb, out_spp and state_out are its image, standard errors, samples and state;
+ *   2. F = rttnw_render_features with p->spp replaced by v->feature_spp (0 means a->pass_spp);
+ *   3. rttnw_reconstruct(the raw image, variance_rgb = NULL, valid = (spp > 0), F, &v->denoise): out_linear_rgb, out_rgba8 and out_valid.
+ *   The adaptive rounds use the ordinary per-pixel stopping rule under the caller's tolerances, each lattice pixel to the bits a fresh
+ *   rttnw_render_adaptive gives it.  NO variance goes into the filter: at the sample counts of a preview the colour stop costs more than it protects
+ *   (DESIGN.md section 10b).
+ * feature_spp defaults to the pass size, not to a handful of samples: a lattice pixel's colour is DIVIDED by its albedo and the quotient is spread
+ *   to the pixels around it, so an albedo estimated from other, fewer samples than the colour — near zero where the colour is not, on a noise
+ *   texture — explodes there.  Features taken from the render's own first B samples are consistent with the colour they demodulate.
+ * Outputs (each optional; row-major, top row first): out_linear_rgb w*h*3 the reconstructed image; out_rgba8 w*h*4 of it, alpha 0 where
+ *   out_valid is 0; out_valid w*h bytes; out_spp w*h the n_q, 0 off the lattice; out_raw_linear_rgb / out_raw_stderr_rgb w*h*3 the unfiltered
+ *   means and standard errors, 0 off the lattice; state_out, rttnw_adaptive_state_doubles(w, h) doubles: the ordinary adaptive state, with zero
+ *   records off the lattice — rttnw_render_adaptive_region over the whole frame under the same cap and tolerances completes it to the fresh adaptive
+ *   render, by that entry point's contract.  `stats`: samples = sum_q n_q, kernel_ms = device time of everything the call runs, reserved = the
+ *   kernel form, the scene's sizes as usual.
+ * Where it lives.  Nothing frame-sized crosses to the host before the outputs: the raw means, the features and the flags stay on the device; per
+ *   round the host reads 8 bytes, the length of the round's list and the number of active pixels.
+ * Refusals, before the device is touched, in this order, each message naming render_preview and the field:
+ *   1. RTTNW_ERR_INVALID for a NULL p, a or v;
+ *   2. what rttnw_render_adaptive refuses among its own arguments, with its codes;
+ *   3. RTTNW_ERR_INVALID for v->level > 6, then v->denoise.iterations > 8, v->denoise.reserved0 != 0, a negative or NaN sigma;
+ *   4. whatever rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes).
+ * Out of scope: a state_in, a node-wide form (ngpu), and windows.  A coarse-to-fine chain — level 2, then level 1, then the frame — goes through
+ *   rttnw_render_adaptive_region with state_out as its state_in, and rttnw_reconstruct on what it returns. */
+struct rttnw_preview {
+    uint32_t level;               /* 0 .. 6: the lattice x % 2^level == 0 && y % 2^level == 0 */
+    uint32_t feature_spp;         /* samples per pixel of the feature buffers; 0 = a->pass_spp */
+    rttnw_denoise_params denoise; /* as rttnw_denoise: iterations 0 .. 8, sigmas (0 = the library default) */
+};
+typedef struct rttnw_preview rttnw_preview;
+int rttnw_render_preview(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
+                         const rttnw_preview* v, double* out_linear_rgb, uint8_t* out_rgba8, uint8_t* out_valid, uint32_t* out_spp,
+                         double* out_raw_linear_rgb, double* out_raw_stderr_rgb, double* state_out, rttnw_stats* stats);
 
 /* Device-resident form, asynchronous on `hip_stream` (a hipStream_t; NULL = default stream).
  * Traces the tiles owned by (tile_rank, tile_world) and writes them in packed order into

@@ -22,6 +22,10 @@ combines with --spp, --pass-spp, --devices and --spp-map, and not with --window,
 alternate on the device, --denoise-iterations sets its passes, the image written is the denoised one (--denoise is implied), --spp-map and
 --save-state work as before, and the samples traced and the rounds run are printed.  It does not combine with --devices, --resume, --refine,
 --window or --passes.
+--preview L (with --noise only; L = 0 .. 6) traces only the pixels with x % 2^L == 0 and y % 2^L == 0, 1 in 4^L, and reconstructs the frame from them
+(rttnw_render_preview): the image written is the reconstruction, --denoise-iterations sets its passes, --spp-map shows the lattice, and --save-state
+leaves the frame-sized state with zero records off the lattice — `--resume state.npy --refine 0,0,W,H` then completes the frame without retracing
+a sample.  It does not combine with --devices, --resume, --refine, --guided, --window or --passes.
 """
 import argparse
 import sys
@@ -85,6 +89,8 @@ def main(argv=None):
     ap.add_argument("--denoise-iterations", type=int, default=5, help="a-trous passes of the denoiser (0..8)")
     ap.add_argument("--guided", action="store_true", help="adaptive sampling: stop pixels on the noise of the denoised image "
                     "(rttnw_render_adaptive_denoised); writes the denoised image")
+    ap.add_argument("--preview", type=int, default=None, metavar="L", help="adaptive sampling: trace 1 pixel in 4^L (x %% 2^L == 0 and y %% 2^L == 0, "
+                    "L = 0 .. 6) and reconstruct the frame from them (rttnw_render_preview); writes the reconstruction")
     ap.add_argument("--features", default=None, metavar="PREFIX", help="write the first-hit feature buffers as PREFIX_albedo.png, "
                     "PREFIX_normal.png, PREFIX_depth.png, PREFIX_alpha.png")
     ap.add_argument("--window", default=None, metavar="X0,Y0,X1,Y1", help="render pixels [X0, X1) x [Y0, Y1) of the frame only (row 0 = top) "
@@ -100,6 +106,21 @@ def main(argv=None):
     except SystemExit:
         print("There was an error", file=sys.stderr)   # DummyError, main.rs:260-268
         raise
+    if args.preview is not None:
+        if args.noise is None:
+            print("--preview needs --noise: it is the adaptive render of a lattice of the frame, reconstructed", file=sys.stderr)
+            return 1
+        clash = [name for name, on in (("--devices", args.devices is not None), ("--resume", args.resume is not None), ("--refine", args.refine is not None),
+                                       ("--guided", args.guided), ("--window", args.window is not None), ("--passes", args.passes > 1)) if on]
+        if clash:
+            print("--preview does not combine with %s: it runs on one GPU, over the whole frame, from nothing" % ", ".join(clash), file=sys.stderr)
+            return 1
+        if not 0 <= args.preview <= 6:
+            print("--preview must be 0 .. 6", file=sys.stderr)
+            return 1
+        if not 0 <= args.denoise_iterations <= 8:
+            print("--denoise-iterations must be 0 .. 8", file=sys.stderr)
+            return 1
     if args.guided:
         if args.noise is None:
             print("--guided needs --noise: it is the adaptive render stopped on the filtered image's noise", file=sys.stderr)
@@ -190,7 +211,7 @@ def main(argv=None):
               % (time.time() - t0, x1 - x0, y1 - y0, x0, y0, w, h, st.samples, st.kernel_ms))
         return 0
     features = None
-    if (args.denoise and not args.guided) or args.features:
+    if (args.denoise and not args.guided and args.preview is None) or args.features:
         if args.denoise and args.passes > 1:
             print("--denoise does not combine with --passes", file=sys.stderr)
             return 1
@@ -210,7 +231,7 @@ def main(argv=None):
 
     def finish(linear, rgba, stderr):
         """The image as it is written: denoised when asked for."""
-        if not args.denoise or args.guided:   # (--guided: the call's own image is the denoised one)
+        if not args.denoise or args.guided or args.preview is not None:   # (--guided, --preview: the call's own image is the filtered one)
             return np.ascontiguousarray(rgba)
         _, out, _, ms = render.denoise(linear, features, stderr, iterations=args.denoise_iterations, want_ms=True)
         print("denoised: %d iterations, %.2f ms" % (args.denoise_iterations, ms))
@@ -234,6 +255,15 @@ def main(argv=None):
                                                 want_state=args.save_state is not None)
             lin, rgba, spp_map, se, st = g["linear"], g["rgba8"], g["spp"], g["stderr"], g["stats"]
             rounds = "; guided: %d rounds of %d, %d denoise iterations each" % (g["rounds"], p.spp // args.pass_spp, args.denoise_iterations)
+            if args.save_state is not None:
+                with open(args.save_state, "wb") as f:
+                    np.save(f, g["state"])
+        elif args.preview is not None:
+            g = render.render_preview(sc, cam, p, args.preview, args.pass_spp, args.noise, args.abs_noise, iterations=args.denoise_iterations,
+                                      want_state=args.save_state is not None)
+            lin, rgba, spp_map, se, st = g["linear"], g["rgba8"], g["spp"], g["raw_stderr"], g["stats"]
+            rounds = "; preview: 1 pixel in %d, %d of %d pixels hold a value, %d denoise iterations" % (4 ** args.preview, int(g["valid"].sum()), w * h,
+                                                                                                      args.denoise_iterations)
             if args.save_state is not None:
                 with open(args.save_state, "wb") as f:
                     np.save(f, g["state"])

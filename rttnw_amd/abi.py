@@ -65,6 +65,11 @@ class Guided(C.Structure):
     _fields_ = [("feature_spp", C.c_uint32), ("reserved0", C.c_uint32), ("denoise", Denoise)]
 
 
+class Preview(C.Structure):
+    """`rttnw_preview` — what `rttnw_render_preview` takes beside the stopping rule: the lattice, the features' samples and the filter."""
+    _fields_ = [("level", C.c_uint32), ("feature_spp", C.c_uint32), ("denoise", Denoise)]
+
+
 class TileLayout(C.Structure):
     _fields_ = [("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32), ("n_tiles", C.c_uint32),
                 ("tiles_per_rank", C.c_uint32), ("pixels_per_rank", C.c_uint32)]
@@ -132,6 +137,10 @@ PRODUCT_FUNCS = [
                                 C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("denoise", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.POINTER(Denoise), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    ("reconstruct", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.POINTER(Denoise), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    ("render_preview", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Preview), C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("render_tiles_device", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_void_p,
                                       C.c_void_p, C.POINTER(Stats)]),
     ("untile_device", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

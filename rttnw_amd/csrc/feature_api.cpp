@@ -1,5 +1,6 @@
-// feature_api.cpp — the extern "C" half of rttnw_render_features and rttnw_denoise (include/rttnw_hip.h): argument checks, then the
-// feature pass of the requested arithmetic build (feature_kernels.hpp) or the denoiser's device half (denoise.hip).  Host code only.
+// feature_api.cpp — the extern "C" half of rttnw_render_features, rttnw_denoise and rttnw_reconstruct (include/rttnw_hip.h): argument checks, then
+// the feature pass of the requested arithmetic build (feature_kernels.hpp), the denoiser's device half (denoise.hip) or the reconstruction's
+// (reconstruct.hip).  Host code only.
 #include "feature_api.hpp"
 
 extern "C" {
@@ -28,6 +29,30 @@ int rttnw_denoise(uint32_t width, uint32_t height, const double* linear_rgb, con
     const rt::DenoiseParams prm = rt::denoise_params(d->sigma_luminance, d->sigma_normal, d->sigma_depth, variance_rgb != nullptr);
     return rt::denoise_device(width, height, linear_rgb, variance_rgb, albedo, normal, depth, alpha, d->iterations, prm, out_linear_rgb, out_rgba8,
                               out_variance_rgb, kernel_ms);
+}
+
+int rttnw_reconstruct(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const uint8_t* valid, const double* albedo,
+                      const double* normal, const double* depth, const double* alpha, const rttnw_denoise_params* d, double* out_linear_rgb,
+                      uint8_t* out_rgba8, double* out_variance_rgb, uint8_t* out_valid, double* kernel_ms) {
+    // rttnw_denoise's refusals, with its codes, and the flags'
+    if (!linear_rgb || !albedo || !normal || !depth || !alpha || !d) {
+        rt::set_last_error("reconstruct: NULL argument (linear_rgb, albedo, normal, depth, alpha or d)");
+        return RTTNW_ERR_INVALID;
+    }
+    if (!valid) { rt::set_last_error("reconstruct: valid is NULL"); return RTTNW_ERR_INVALID; }
+    if (uint64_t(width) * height == 0 || uint64_t(width) * height > (1ull << 28)) {
+        rt::set_last_error("reconstruct: width * height: empty image (or more than 2^28 pixels)");
+        return RTTNW_ERR_INVALID;
+    }
+    if (d->iterations > rt::DENOISE_MAX_ITERATIONS) { rt::set_last_error("reconstruct: d->iterations: more than 8 iterations"); return RTTNW_ERR_INVALID; }
+    if (d->reserved0 != 0) { rt::set_last_error("reconstruct: d->reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (!(d->sigma_luminance >= 0.0) || !(d->sigma_normal >= 0.0) || !(d->sigma_depth >= 0.0)) {
+        rt::set_last_error("reconstruct: the sigmas (sigma_luminance, sigma_normal, sigma_depth) must be >= 0 (and not NaN)");
+        return RTTNW_ERR_INVALID;
+    }
+    const rt::DenoiseParams prm = rt::denoise_params(d->sigma_luminance, d->sigma_normal, d->sigma_depth, variance_rgb != nullptr);
+    return rt::reconstruct_device(width, height, linear_rgb, variance_rgb, valid, albedo, normal, depth, alpha, d->iterations, prm, out_linear_rgb,
+                                  out_rgba8, out_variance_rgb, out_valid, kernel_ms);
 }
 
 } // extern "C"

@@ -1155,6 +1155,23 @@ extern "C" int rttnw_render_adaptive_region(rttnw_scene* s, const rttnw_camera_d
 // bytes, which are also the count of alive pixels.
 // ---------------------------------------------------------------------------------------------
 namespace rt {
+// A frame that lives on ONE rank: its packed state records (adaptive_state_export_launch) come back from the device and go to their row-major places
+// behind the header (rttnw_render_adaptive_denoised, rttnw_render_preview)
+static int single_rank_state_out(const rttnw_params& p, const rttnw_adaptive& a, const rttnw_camera_desc* cam, const rttnw_tile_layout& L,
+                                 const double* d_records, double* state_out) {
+    std::vector<double> host_records(size_t(L.pixels_per_rank) * STATE_RECORD_DOUBLES);
+    HIP_TRY(hipMemcpy(host_records.data(), d_records, host_records.size() * sizeof(double), hipMemcpyDeviceToHost));
+    state_header(p, a, cam, state_out);
+    for (uint32_t y = 0; y < p.height; ++y)
+        for (uint32_t x = 0; x < p.width; ++x) {
+            uint32_t owner;
+            size_t idx;
+            packed_place(x, y, L, 1, owner, idx);
+            const double* rec = host_records.data() + idx * STATE_RECORD_DOUBLES;
+            std::copy(rec, rec + STATE_RECORD_DOUBLES, state_out + STATE_HEADER_DOUBLES + (size_t(y) * p.width + x) * STATE_RECORD_DOUBLES);
+        }
+    return RTTNW_OK;
+}
 static int adaptive_denoised_render(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const rttnw_guided& g,
                                     double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, double* out_raw_linear_rgb,
                                     double* out_raw_stderr_rgb, double* state_out, rttnw_stats* stats) {
@@ -1260,19 +1277,8 @@ static int adaptive_denoised_render(::rttnw_scene* s, const rttnw_camera_desc* c
     if (out_stderr_rgb) HIP_TRY(hipMemcpy(out_stderr_rgb, stderr_f.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_raw_linear_rgb) HIP_TRY(hipMemcpy(out_raw_linear_rgb, mean.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_raw_stderr_rgb) HIP_TRY(hipMemcpy(out_raw_stderr_rgb, raw_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (state_out) { // the packed records come back and go to their row-major places behind the header
-        std::vector<double> host_records(ppr * STATE_RECORD_DOUBLES);
-        HIP_TRY(hipMemcpy(host_records.data(), records.p, host_records.size() * sizeof(double), hipMemcpyDeviceToHost));
-        state_header(p, a, cam, state_out);
-        for (uint32_t y = 0; y < p.height; ++y)
-            for (uint32_t x = 0; x < p.width; ++x) {
-                uint32_t owner;
-                size_t idx;
-                packed_place(x, y, L, 1, owner, idx);
-                const double* rec = host_records.data() + idx * STATE_RECORD_DOUBLES;
-                std::copy(rec, rec + STATE_RECORD_DOUBLES, state_out + STATE_HEADER_DOUBLES + (size_t(y) * p.width + x) * STATE_RECORD_DOUBLES);
-            }
-    }
+    if (state_out)
+        if (int rc = single_rank_state_out(p, a, cam, L, records.p, state_out)) return rc;
     return RTTNW_OK;
 }
 } // namespace rt
@@ -1295,6 +1301,155 @@ extern "C" int rttnw_render_adaptive_denoised(rttnw_scene* s, const rttnw_camera
     if (int rc = validate(s, cam, p)) return rc;
     return adaptive_denoised_render(s, cam, *p, *a, *g, out_linear_rgb, out_rgba8, out_spp, out_stderr_rgb, out_raw_linear_rgb, out_raw_stderr_rgb, state_out,
                                     stats);
+}
+
+// ---------------------------------------------------------------------------------------------
+// rttnw_render_preview (include/rttnw_hip.h has the contract, DESIGN.md §10b "a frame from a fraction of its pixels" the why): the adaptive rounds of
+// the windowed form over a LATTICE of the frame, then the feature pass and rttnw_reconstruct's passes, all on buffers that never leave the device.
+// One rank on the scene's device, default stream.  The rounds are adaptive_denoised_render's, with two differences: the bytes that start alive are the
+// lattice's (preview_lattice_launch), and a round's list pass runs under the caller's cap and tolerances, so the resolve step's own stopping rule
+// writes the next round's bytes — the alive bytes ARE the pass's active bytes.  Every alive pixel holds exactly kB samples in round k, which is one
+// level of the windowed form's loop: list for list what rttnw_render_adaptive_region traces under mask = the lattice.
+// ---------------------------------------------------------------------------------------------
+namespace rt {
+static int preview_render(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const rttnw_preview& pv,
+                          double* out_linear_rgb, uint8_t* out_rgba8, uint8_t* out_valid, uint32_t* out_spp, double* out_raw_linear_rgb,
+                          double* out_raw_stderr_rgb, double* state_out, rttnw_stats* stats) {
+    DeviceGuard restore; // (the caller's device is current again after EVERY return below, the error paths included)
+    DeviceState* d = s->device;
+    HIP_TRY(hipSetDevice(d->device));
+    rttnw_tile_layout L;
+    fill_layout(p.width, p.height, 1, L);
+    const size_t npx = size_t(p.width) * p.height, ppr = L.pixels_per_rank, rsz = p.precision == RTTNW_F32 ? sizeof(float) : sizeof(double);
+    const uint32_t n_blocks = L.n_tiles * 16u, B = a.pass_spp, n_rounds = p.spp / B;
+    const hipStream_t stream = nullptr;
+    // everything that allocates, before the first launch: the adaptive passes' buffers, this call's own, and what a list pass over the lattice's blocks needs
+    HIP_TRY(d->packed.grow(ppr * 4 * rsz));
+    HIP_TRY(d->ad_state.grow(ppr * sizeof(AdaptivePixel)));
+    HIP_TRY(d->ad_active.grow(ppr));
+    HIP_TRY(d->list_quads.grow(size_t(n_blocks) * sizeof(uint32_t)));
+    HIP_TRY(d->list_scan.grow(quad_scan_words(n_blocks) * sizeof(uint32_t)));
+    DevBuf<uint8_t> means, rgba, valid, holds[2], valid_out;
+    DevBuf<uint32_t> spp;
+    DevBuf<double> aux, maps, mean, variance, raw_stderr, d_c[2], records;
+    HIP_TRY(means.alloc(ppr * 4 * rsz));
+    HIP_TRY(rgba.alloc(npx * 4));
+    HIP_TRY(valid.alloc(npx));
+    HIP_TRY(valid_out.alloc(npx));
+    HIP_TRY(spp.alloc(npx));
+    HIP_TRY(aux.alloc(ppr * 4));
+    HIP_TRY(maps.alloc(npx * 8));
+    HIP_TRY(mean.alloc(npx * 3));
+    HIP_TRY(variance.alloc(npx * 3));
+    HIP_TRY(raw_stderr.alloc(npx * 3));
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(d_c[k].alloc(npx * 3));
+        HIP_TRY(holds[k].alloc(npx));
+    }
+    if (state_out) HIP_TRY(records.alloc(ppr * STATE_RECORD_DOUBLES));
+    Event ev0, ev1, ev2, ev3;
+    HIP_TRY(create_event(ev0));
+    HIP_TRY(create_event(ev1));
+    HIP_TRY(create_event(ev2));
+    HIP_TRY(create_event(ev3));
+    // the blocks that hold a lattice pixel: every block at level 0 and 1, one in 4^(level-1) above
+    const uint32_t step = 1u << pv.level, block_step = std::max(step, 2u);
+    const uint32_t lattice_blocks = ((p.width + block_step - 1) / block_step) * ((p.height + block_step - 1) / block_step);
+    rttnw_params pass = p;
+    pass.spp = B;
+    ListPass ad;
+    ad.state = (AdaptivePixel*)d->ad_state.p;
+    ad.active = d->ad_active.p;
+    ad.quads = (const uint32_t*)d->list_quads.p;
+    ad.n_quads = std::min(lattice_blocks, n_blocks);
+    ad.first = false; // (round 0 too is a list pass on zero sums: 0 + c0 is the chain's first addition, as in the windowed form)
+    ad.cap = p.spp;
+    ad.rel_error = a.rel_error;
+    ad.abs_error = a.abs_error;
+    if (int rc = render_tiles_any(s, d, cam, &pass, d->packed.p, stream, nullptr, false, true, &ad)) return rc;
+    if (stats)
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_rank_stats_t, s, d, &p, stats)) return rc;
+
+    // before round 0: zero sums and zero noise state everywhere, and the lattice alive
+    HIP_TRY(hipEventRecord(ev0.get(), stream));
+    HIP_TRY(hipMemsetAsync(d->packed.p, 0, ppr * 4 * rsz, stream));
+    HIP_TRY(hipMemsetAsync(d->ad_state.p, 0, ppr * sizeof(AdaptivePixel), stream));
+    if (int rc = preview_lattice_launch(d->ad_active.p, L.pixels_per_rank, p.width, p.height, pv.level, stream)) return rc;
+    uint64_t samples = 0;
+    for (uint32_t k = 0; k < n_rounds; ++k) {
+        // the list of this round and, in one 8-byte copy, its length and the alive pixels
+        if (int rc = RT_BY_PRECISION(p.precision, enqueue_quad_list, d->ad_active.p, n_blocks, (uint32_t*)d->list_scan.p, (uint32_t*)d->list_quads.p, stream)) return rc;
+        uint32_t count[2] = {0, 0}; // listed blocks, alive pixels
+        HIP_TRY(hipMemcpy(count, quad_list_totals((uint32_t*)d->list_scan.p, n_blocks), sizeof(count), hipMemcpyDeviceToHost));
+        if (count[0] == 0) break; // every lattice pixel has stopped
+        samples += uint64_t(count[1]) * B;
+        // trace the alive pixels, all of which hold exactly kB samples; the resolve step decides, under the caller's rule, who is alive in round k + 1
+        pass.sample_begin = p.sample_begin + k * B;
+        ad.n_quads = count[0];
+        if (int rc = render_tiles_any(s, d, cam, &pass, d->packed.p, stream, nullptr, false, false, &ad)) return rc;
+    }
+    // the raw values of every pixel of the frame, by the adaptive render's own division on a copy of the sums; a pixel holds a value where it holds samples
+    if (state_out)
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_state_export_launch, d->packed.p, d->ad_state.p, records.p, L.pixels_per_rank, L.n_tiles * 64u, stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(means.p, d->packed.p, ppr * 4 * rsz, hipMemcpyDeviceToDevice, stream));
+    if (int rc = RT_BY_PRECISION(p.precision, adaptive_finish_launch, means.p, d->ad_state.p, aux.p, L.pixels_per_rank, L.n_tiles * 64u, stream)) return rc;
+    if (int rc = guided_raw_launch(p.precision, means.p, aux.p, mean.p, variance.p, raw_stderr.p, spp.p, p.width, p.height, stream)) return rc;
+    if (int rc = preview_valid_launch(spp.p, valid.p, p.width, p.height, stream)) return rc;
+    HIP_TRY(hipEventRecord(ev1.get(), stream));
+    // the features, which stay on the device (the pass times itself between d->ev0 and d->ev1 and waits for the stream) ...
+    rttnw_params pf = p;
+    pf.spp = pv.feature_spp ? pv.feature_spp : B;
+    if (int rc = RT_BY_PRECISION(p.precision, render_features_device_t, s, cam, &pf, maps.p, stream)) return rc;
+    float feature_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&feature_ms, d->ev0.get(), d->ev1.get()));
+    // ... and the reconstruction: no variance goes into the filter
+    const double *m_albedo = maps.p, *m_normal = maps.p + npx * 3, *m_depth = maps.p + npx * 6, *m_alpha = maps.p + npx * 7;
+    const DenoiseParams prm = denoise_params(pv.denoise.sigma_luminance, pv.denoise.sigma_normal, pv.denoise.sigma_depth, false);
+    double* const c[2] = {d_c[0].p, d_c[1].p};
+    double* const v[2] = {nullptr, nullptr};
+    uint8_t* const h[2] = {holds[0].p, holds[1].p};
+    int out = 0;
+    HIP_TRY(hipEventRecord(ev2.get(), stream));
+    if (int rc = reconstruct_passes_device(p.width, p.height, mean.p, nullptr, valid.p, m_albedo, m_normal, m_depth, m_alpha, pv.denoise.iterations, prm, c, v,
+                                           h, rgba.p, valid_out.p, stream, out)) return rc;
+    HIP_TRY(hipEventRecord(ev3.get(), stream));
+    HIP_TRY(hipDeviceSynchronize());
+    if (stats) {
+        float ms = 0, ms_r = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+        HIP_TRY(hipEventElapsedTime(&ms_r, ev2.get(), ev3.get()));
+        stats->kernel_ms = double(ms) + double(feature_ms) + double(ms_r);
+        stats->samples = samples;
+    }
+    if (out_linear_rgb) HIP_TRY(hipMemcpy(out_linear_rgb, c[out], npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, rgba.p, npx * 4, hipMemcpyDeviceToHost));
+    if (out_valid) HIP_TRY(hipMemcpy(out_valid, valid_out.p, npx, hipMemcpyDeviceToHost));
+    if (out_spp) HIP_TRY(hipMemcpy(out_spp, spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_raw_linear_rgb) HIP_TRY(hipMemcpy(out_raw_linear_rgb, mean.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_raw_stderr_rgb) HIP_TRY(hipMemcpy(out_raw_stderr_rgb, raw_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (state_out)
+        if (int rc = single_rank_state_out(p, a, cam, L, records.p, state_out)) return rc;
+    return RTTNW_OK;
+}
+} // namespace rt
+
+extern "C" int rttnw_render_preview(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, const rttnw_preview* v,
+                                    double* out_linear_rgb, uint8_t* out_rgba8, uint8_t* out_valid, uint32_t* out_spp, double* out_raw_linear_rgb,
+                                    double* out_raw_stderr_rgb, double* state_out, rttnw_stats* stats) {
+    using namespace rt;
+    // the refusals, in the header's order: none of them needs a device
+    if (!p || !a || !v) { set_last_error("render_preview: NULL argument (p, a or v)"); return RTTNW_ERR_INVALID; }
+    if (int rc = refuse_adaptive_misuse("render_preview", p, a)) return rc;
+    if (int rc = refuse_host_output_misuse("render_preview", a->reserved0, p)) return rc;
+    if (v->level > 6) { set_last_error("render_preview: v->level must be 0 .. 6"); return RTTNW_ERR_INVALID; }
+    if (v->denoise.iterations > DENOISE_MAX_ITERATIONS) { set_last_error("render_preview: v->denoise.iterations: more than 8 iterations"); return RTTNW_ERR_INVALID; }
+    if (v->denoise.reserved0 != 0) { set_last_error("render_preview: v->denoise.reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (!(v->denoise.sigma_luminance >= 0.0) || !(v->denoise.sigma_normal >= 0.0) || !(v->denoise.sigma_depth >= 0.0)) {
+        set_last_error("render_preview: v->denoise: the sigmas (sigma_luminance, sigma_normal, sigma_depth) must be >= 0 (and not NaN)");
+        return RTTNW_ERR_INVALID;
+    }
+    if (int rc = validate(s, cam, p)) return rc;
+    return preview_render(s, cam, *p, *a, *v, out_linear_rgb, out_rgba8, out_valid, out_spp, out_raw_linear_rgb, out_raw_stderr_rgb, state_out, stats);
 }
 
 // Release what the library keeps for the life of the process (today: the RCCL communicator sets of rttnw_render_multi).  Scenes

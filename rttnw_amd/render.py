@@ -249,6 +249,72 @@ def denoise(linear, features, stderr=None, iterations=5, sigma_luminance=0.0, si
     return (out, rgba, out_var, ms.value) if want_ms else (out, rgba, out_var)
 
 
+def lattice_mask(width, height, level):
+    """The lattice of a preview as a mask (HxW u8): 1 where x % 2^level == 0 and y % 2^level == 0, row 0 at the top."""
+    if not 0 <= int(level) <= 6:
+        raise ValueError("lattice_mask: level must be 0 .. 6, got %r" % (level,))
+    m = np.zeros((int(height), int(width)), dtype=np.uint8)
+    m[:: 1 << int(level), :: 1 << int(level)] = 1
+    return m
+
+
+def reconstruct(linear, valid, features, stderr=None, iterations=5, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0, want_ms=False):
+    """`rttnw_reconstruct`: `denoise` over an image of which only the pixels with a nonzero byte in `valid` (HxW) hold a value — the taps that
+    hold nothing are dropped, the pixels that hold nothing are filled from those that do.  `linear` and `stderr` are never read where `valid` is 0.
+    Returns (linear HxWx3 f64, rgba8 HxWx4 u8 with alpha 0 where nothing could be filled, variance HxWx3 f64 or None, valid HxW u8) — and the
+    device time in ms after them with `want_ms`."""
+    b = library.product()
+    lin = np.ascontiguousarray(linear, dtype=np.float64)
+    h, w = lin.shape[:2]
+    ok = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+    var = None if stderr is None else np.ascontiguousarray(np.square(np.asarray(stderr, dtype=np.float64)))
+    f = {k: np.ascontiguousarray(features[k], dtype=np.float64) for k in ("albedo", "normal", "depth", "alpha")}
+    assert lin.shape == (h, w, 3) and ok.shape == (h, w)
+    assert f["albedo"].shape == (h, w, 3) and f["normal"].shape == (h, w, 3) and f["depth"].shape == (h, w) and f["alpha"].shape == (h, w)
+    assert var is None or var.shape == (h, w, 3)
+    out = np.zeros((h, w, 3))
+    rgba = np.zeros((h, w, 4), dtype=np.uint8)
+    out_var = None if var is None else np.zeros((h, w, 3))
+    out_ok = np.zeros((h, w), dtype=np.uint8)
+    d = abi.Denoise(iterations=iterations, reserved0=0, sigma_luminance=sigma_luminance, sigma_normal=sigma_normal, sigma_depth=sigma_depth)
+    ms = C.c_double(0.0)
+    rc = b.reconstruct(w, h, lin.ctypes.data, None if var is None else var.ctypes.data, ok.ctypes.data, f["albedo"].ctypes.data,
+                       f["normal"].ctypes.data, f["depth"].ctypes.data, f["alpha"].ctypes.data, C.byref(d), out.ctypes.data, rgba.ctypes.data,
+                       None if out_var is None else out_var.ctypes.data, out_ok.ctypes.data, C.byref(ms))
+    check(rc, b, "rttnw_reconstruct")
+    return (out, rgba, out_var, out_ok, ms.value) if want_ms else (out, rgba, out_var, out_ok)
+
+
+def render_preview(scene, cam, params, level, pass_spp=64, rel_error=0.02, abs_error=0.0, iterations=5, feature_spp=0, sigma_luminance=0.0,
+                   sigma_normal=0.0, sigma_depth=0.0, want_state=True):
+    """`rttnw_render_preview`: the adaptive render of the lattice x % 2^level == 0, y % 2^level == 0 (1 pixel in 4^level), the features of the
+    whole frame (`feature_spp` samples, 0 = pass_spp) and `reconstruct` over the two, on the device.  The same `spp_chunk` default as
+    `render_adaptive`.  Returns a dict: "linear" HxWx3 f64 and "rgba8" HxWx4 u8 (the reconstructed image), "valid" HxW u8, "spp" HxW u32 (0 off
+    the lattice), "raw_linear" and "raw_stderr" HxWx3 f64 (the lattice's own values), "state" (the frame-sized adaptive state with zero records
+    off the lattice — `render_adaptive_region(..., 0, 0, W, H, state=...)` completes it — or None) and "stats"."""
+    import copy
+    b = library.product()
+    p = copy.copy(params)
+    if p.spp_chunk == 0:
+        p.spp_chunk = max(1, pass_spp // 16)
+    h, w = p.height, p.width
+    out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "valid": np.zeros((h, w), dtype=np.uint8),
+           "spp": np.zeros((h, w), dtype=np.uint32), "raw_linear": np.zeros((h, w, 3)), "raw_stderr": np.zeros((h, w, 3))}
+    state = np.zeros(int(b.adaptive_state_doubles(w, h)), dtype=np.float64) if want_state else None
+    st = Stats()
+    a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
+    v = abi.Preview(level=level, feature_spp=feature_spp,
+                    denoise=abi.Denoise(iterations=iterations, reserved0=0, sigma_luminance=sigma_luminance, sigma_normal=sigma_normal,
+                                        sigma_depth=sigma_depth))
+    rc = b.render_preview(scene.handle, C.byref(cam), C.byref(p), C.byref(a), C.byref(v), out["linear"].ctypes.data, out["rgba8"].ctypes.data,
+                          out["valid"].ctypes.data, out["spp"].ctypes.data, out["raw_linear"].ctypes.data, out["raw_stderr"].ctypes.data,
+                          None if state is None else state.ctypes.data, C.byref(st))
+    check(rc, b, "rttnw_render_preview")
+    out["state"] = state
+    out["stats"] = st
+    return out
+
+
 def render_host_passes(scene, cam, params, passes, on_pass=None):
     """The same image as `render_host`, in `passes` passes over disjoint sample ranges (`rttnw_params.sample_begin`):
     after every pass the running mean is a complete, displayable estimate — progressive display and a natural
