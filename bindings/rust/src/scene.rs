@@ -240,6 +240,25 @@ impl Scene {
         ok(unsafe { ffi::rttnw_render_preview(self.raw, cam, p, a, v, ptr::null_mut(), rgba.as_mut_ptr(), valid.as_mut_ptr(), spp.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), out.as_mut_ptr(), &mut stats) })?;
         Ok((rgba, valid, spp, stats, out))
     }
+    /// The adaptive render under a budget of samples (`rttnw_render_adaptive_budget`): at most `b.samples` camera paths, spent in rounds on the
+    /// pixels `budget_select` ranks worst under `a` and the cap `p.spp`, begun from `state` (frame-sized, a pixel never sampled being a record
+    /// of zeros; `None`: all zeros), on one GPU.  Returns (RGBA8, samples per pixel and standard errors — a pixel without samples is zero, alpha
+    /// included —, stats, the state, the rounds run).
+    pub fn render_adaptive_budget(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, a: &ffi::rttnw_adaptive, b: &ffi::rttnw_budget, state: Option<&[f64]>) -> Result<(Vec<u8>, Vec<u32>, Vec<f64>, ffi::rttnw_stats, Vec<f64>, u32)> {
+        let n = p.width as usize * p.height as usize;
+        let doubles = unsafe { ffi::rttnw_adaptive_state_doubles(p.width, p.height) } as usize;
+        if state.map_or(false, |s| s.len() != doubles) {
+            return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "render_adaptive_budget: the state does not have the frame's size".into() });
+        }
+        let mut rgba = vec![0u8; n * 4];
+        let mut spp = vec![0u32; n];
+        let mut stderr = vec![0f64; n * 3];
+        let mut stats = ffi::rttnw_stats::default();
+        let mut out = vec![0f64; doubles];
+        ok(unsafe { ffi::rttnw_render_adaptive_budget(self.raw, cam, p, a, b, state.map_or(ptr::null(), |s| s.as_ptr()), out.as_mut_ptr(), ptr::null_mut(), rgba.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), &mut stats) })?;
+        let rounds = stats.reserved >> 16;
+        Ok((rgba, spp, stderr, stats, out, rounds))
+    }
     /// First-hit feature buffers of the frame `render` renders (`rttnw_render_features`), row-major, top row first.
     pub fn render_features(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params) -> Result<Features> {
         let n = p.width as usize * p.height as usize;
@@ -315,6 +334,21 @@ pub fn reconstruct(linear: &[f64], variance: Option<&[f64]>, valid: &[u8], f: &F
                                f.depth.as_ptr(), f.alpha.as_ptr(), d, out.as_mut_ptr(), rgba.as_mut_ptr(), ptr::null_mut(), out_valid.as_mut_ptr(), ptr::null_mut())
     })?;
     Ok((out, rgba, out_valid))
+}
+
+/// `rttnw_budget_select`: which pixels get the next adaptive pass when only `max_pixels` of them can — the candidates under `cap` and the
+/// tolerances, ranked by standard error over tolerance, then by row-major index.  `linear` and `stderr` (w*h*3) are never read where `spp` (w*h)
+/// is 0.  Returns (the mask w*h, the priorities w*h — 0 for a non-candidate, +inf for a pixel without samples —, the number selected).
+pub fn budget_select(width: u32, height: u32, linear: &[f64], stderr: &[f64], spp: &[u32], cap: u32, rel_error: f64, abs_error: f64, max_pixels: u64) -> Result<(Vec<u8>, Vec<f64>, u64)> {
+    let n = width as usize * height as usize;
+    if linear.len() != n * 3 || stderr.len() != n * 3 || spp.len() != n {
+        return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "budget_select: array sizes do not match the image".into() });
+    }
+    let mut mask = vec![0u8; n];
+    let mut priority = vec![0f64; n];
+    let mut selected = 0u64;
+    ok(unsafe { ffi::rttnw_budget_select(width, height, linear.as_ptr(), stderr.as_ptr(), spp.as_ptr(), cap, rel_error, abs_error, max_pixels, mask.as_mut_ptr(), priority.as_mut_ptr(), &mut selected, ptr::null_mut()) })?;
+    Ok((mask, priority, selected))
 }
 
 impl Drop for Scene {

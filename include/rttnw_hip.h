@@ -42,8 +42,8 @@ extern "C" {
                              *    (below), validate() rejects t_min < 0
                              * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region, rttnw_render_adaptive_multi,
                              *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region,
-                             *  rttnw_render_adaptive_denoised, rttnw_reconstruct and rttnw_render_preview came later, without a version bump: a
-                             *  caller detects each by its symbol) */
+                             *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select and
+                             *  rttnw_render_adaptive_budget came later, without a version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -229,7 +229,7 @@ typedef struct rttnw_stats {
     uint32_t n_nodes;        /* flat scene size: 4-wide node records */
     uint32_t n_prims;
     uint32_t scene_bytes;    /* bytes of node+primitive arrays resident on the device */
-    uint32_t reserved;       /* render: kernel form that ran — bit 0: decoupled (else lane-owns-path), bit 1: node records resident in LDS, bit 2: three node steps per walk trip (tiny top trees), bit 3: the instantiation whose walk never changes frames (no Translate / YRotate group with a tree of its own), bit 4: ... but tests single wrapped records in place, bit 5: ... in the LEAN flavour (the scene has no MovingSphere, no ConstantMedium and only solid colours: their code is compiled out); bit 6: the decoupled kernel walked the interleaved node + sphere buffer of a big cloud; rttnw_render_multi, rank 0 only — bit 8: the gather went through peer copies (RTTNW_MULTI_GATHER=peer), bit 9: ... because the RCCL set-up failed; scene_info: stack depth */
+    uint32_t reserved;       /* render: kernel form that ran — bit 0: decoupled (else lane-owns-path), bit 1: node records resident in LDS, bit 2: three node steps per walk trip (tiny top trees), bit 3: the instantiation whose walk never changes frames (no Translate / YRotate group with a tree of its own), bit 4: ... but tests single wrapped records in place, bit 5: ... in the LEAN flavour (the scene has no MovingSphere, no ConstantMedium and only solid colours: their code is compiled out); bit 6: the decoupled kernel walked the interleaved node + sphere buffer of a big cloud; rttnw_render_multi, rank 0 only — bit 8: the gather went through peer copies (RTTNW_MULTI_GATHER=peer), bit 9: ... because the RCCL set-up failed; rttnw_render_adaptive_budget — bits 16 .. 31: the rounds it ran (saturating): a caller that compares kernel forms across entry points masks with 0xFFFF first; scene_info: stack depth */
 } rttnw_stats;
 
 /* Framebuffer partition: 8x8-pixel tiles, tile t owned by rank
@@ -662,6 +662,79 @@ typedef struct rttnw_preview rttnw_preview;
 int rttnw_render_preview(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
                          const rttnw_preview* v, double* out_linear_rgb, uint8_t* out_rgba8, uint8_t* out_valid, uint32_t* out_spp,
                          double* out_raw_linear_rgb, double* out_raw_stderr_rgb, double* state_out, rttnw_stats* stats);
+
+/* Which pixels get the next adaptive pass when not all of them can: an exact, deterministic top-m selection over a frame's pixels by noise
+ * relative to tolerance — the step rttnw_render_adaptive_budget runs once per round, on its own.  Host arrays in and out, blocking, on the current
+ * device, no scene handle, no CPU fallback.  (Came without a version bump: detect it by its symbol.)
+ *
+ * Inputs: the row-major maps every adaptive entry point returns — linear_rgb w*h*3 the means, stderr_rgb w*h*3 the standard errors (+inf with
+ *   fewer than two chunks), spp w*h the sample counts.  The colour and the error of a pixel with spp == 0 are NEVER READ (they may be NaN).
+ * Candidate.  Pixel q is a candidate if spp == 0, or if spp < cap and rttnw_render_adaptive's stopping rule does not hold: se_c <= abs_error +
+ *   rel_error * value_c fails in some channel (the product rounded on its own, nothing fused).
+ * Priority rho, a double: +inf for spp == 0; otherwise the maximum over r, g, b of e_c, where with t_c = abs_error + rel_error * value_c, e_c = 0
+ *   when se_c <= t_c and se_c / t_c otherwise — and +inf where that quotient is not a finite positive number.  One product, one sum, one IEEE
+ *   division and comparisons.  A candidate has rho in (1, +inf]; a non-candidate reports out_priority 0.
+ * Selection.  m = min(number of candidates, max_pixels).  The selected pixels are the first m candidates in the order rho descending, then
+ *   row-major index y * width + x ascending.
+ * Outputs (each optional): out_mask w*h bytes, 1 for the selected pixels and 0 elsewhere; out_priority w*h doubles; out_selected = m; kernel_ms:
+ *   device time of the selection.
+ * How.  Every pixel gets a 96-bit key — the bit pattern of rho above 0xFFFFFFFF - index, 0 for a non-candidate —, so the selection is "the m
+ *   largest keys" and has no ties; a most-significant-digit radix select finds the m-th largest with integer atomics only, so the result does not
+ *   depend on scheduling.  The device code, a host build of the same header (rttnw_amd/csrc/budget_select.hpp) with a plain sort, and a restatement
+ *   in numpy give the same bits.
+ * Refusals, before the device is touched, each message naming `budget_select` and the field: RTTNW_ERR_INVALID for a NULL linear_rgb, stderr_rgb
+ *   or spp, width * height == 0, cap == 0, a negative or NaN tolerance, both tolerances 0 (a priority relative to a tolerance of nothing ranks
+ *   every noisy pixel +inf); RTTNW_ERR_UNSUPPORTED for more than 2^32 - 1 pixels (the key holds the index in 32 bits). */
+int rttnw_budget_select(uint32_t width, uint32_t height, const double* linear_rgb, const double* stderr_rgb, const uint32_t* spp,
+                        uint32_t cap, double rel_error, double abs_error, uint64_t max_pixels,
+                        uint8_t* out_mask, double* out_priority, uint64_t* out_selected, double* kernel_ms);
+
+/* The adaptive render under a BUDGET of samples: the other entry points of this family stop each pixel at a noise tolerance and cost what they
+ * cost; this one traces at most b->samples camera paths and spends them on the worst pixels first.  One GPU, the whole frame, tile_world == 1,
+ * blocking.  (Came without a version bump: detect it by its symbol.)
+ *
+ * B = a->pass_spp; the cap p->spp is a positive multiple of B.  The state is rttnw_render_adaptive_region's: frame-sized, a record of twelve
+ * zeros means "no samples yet"; state_in == NULL stands for all zeros; state_in and state_out may be the same array.
+ * Rounds.  remaining = b->samples.  Round r = 0, 1, ... runs rttnw_budget_select on the current means, standard errors and counts of every pixel,
+ *   under the caller's cap and tolerances, with max_pixels = min(round_pixels, remaining / B) (integer division).  When that selects nothing the
+ *   call ends.  Each selected pixel q, holding n_q samples, gets its next pass and nothing else — samples [sample_begin + n_q, sample_begin + n_q +
+ *   B), with the jobs, chunk schedule, running-sum chain and noise-state update of the adaptive render's pass at level n_q / B — and remaining
+ *   -= m * B.  Pixels of one round stand at different levels: the round runs one list pass per occupied level, in ascending order, over the 2x2
+ *   blocks that hold a selected pixel of that level.
+ * Contract.  For every `precision`, kernel form and launch split (RTTNW_CHUNK_SUM_BUDGET) the four outputs and state_out are BIT-IDENTICAL to
+ *   this host composition: per round the selection restated on the host over the maps the previous step returned, then for each occupied level k,
+ *   ascending, rttnw_render_adaptive_region(window = the whole frame, mask = this round's pixels at level k, ngpu = 0, cap (k+1)B, rel_error =
+ *   abs_error = 0, state_in = the running state).  (That entry point refuses a state with a record above its cap: the records of the pixels
+ *   that stand above level k are set aside for the call — they are not selected, it would leave them alone — and put back behind it.)  The
+ *   value a pixel is ranked by is the one the adaptive render REPORTS — sum / n in the kernel's type, widened — not a division redone from the
+ *   state: the f32 build's division is not correctly rounded.
+ *   Two consequences.  When the budget never binds, the outputs and the state are those of rttnw_render_adaptive_resume(state_in = NULL) under the
+ *   same cap, B and tolerances, bit for bit, for any round_pixels: a pixel's record is a function of its own sample count alone.  And two calls of
+ *   N1 and N2 samples are NOT promised to equal one call of N1 + N2: the round the first call ended in was cut by its budget.
+ * Outputs (each optional): those of rttnw_render_adaptive_region over the whole frame on the state the call ends in — a pixel without samples is
+ *   zero everywhere, alpha included.  `stats`: samples = what THIS call traced, at most b->samples, and more than b->samples - B unless no
+ *   candidate was left; kernel_ms = device time of everything the call runs, the state's copies included; the scene's sizes as usual; reserved =
+ *   the kernel form in its low bits as usual and, in bits 16 .. 31, the rounds that traced something (saturating at 65535).
+ * Where it lives.  Between rounds nothing frame-sized crosses to the host: per round the host reads one small record in one copy — the number
+ *   selected and, per level, the length of the list over the selected pixels that stand at it (1 + cap / B words) — and runs only the occupied
+ *   levels.
+ * No work.  b->samples < B, or no candidate: RTTNW_OK, no trace kernel is launched, stats->samples == 0, the outputs are those of the incoming state.
+ * Refusals, before the device is touched, in this order, each message naming render_adaptive_budget and the field:
+ *   1. RTTNW_ERR_INVALID for a NULL p, a or b;
+ *   2. what rttnw_render_adaptive refuses among its own arguments, with its codes;
+ *   3. RTTNW_ERR_INVALID for b->reserved0 != 0, then for rel_error == abs_error == 0;
+ *   4. with a state_in, the state checks of rttnw_render_adaptive_region (a record of zeros is accepted);
+ *   5. whatever rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes).
+ * Out of scope: a node-wide form (ngpu), windows and masks, and ranking by the filtered error of rttnw_render_adaptive_denoised. */
+struct rttnw_budget {
+    uint64_t samples;      /* the most camera paths THIS call may trace */
+    uint32_t round_pixels; /* the most pixels one round refines; 0 = ceil(width * height / 2) */
+    uint32_t reserved0;    /* must be 0 */
+};
+typedef struct rttnw_budget rttnw_budget;
+int rttnw_render_adaptive_budget(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
+                                 const rttnw_budget* b, const double* state_in, double* state_out, double* out_linear_rgb,
+                                 uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, rttnw_stats* stats);
 
 /* Device-resident form, asynchronous on `hip_stream` (a hipStream_t; NULL = default stream).
  * Traces the tiles owned by (tile_rank, tile_world) and writes them in packed order into

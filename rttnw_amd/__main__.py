@@ -26,6 +26,10 @@ alternate on the device, --denoise-iterations sets its passes, the image written
 (rttnw_render_preview): the image written is the reconstruction, --denoise-iterations sets its passes, --spp-map shows the lattice, and --save-state
 leaves the frame-sized state with zero records off the lattice — `--resume state.npy --refine 0,0,W,H` then completes the frame without retracing
 a sample.  It does not combine with --devices, --resume, --refine, --guided, --window or --passes.
+--budget SAMPLES (with --noise only) traces at most SAMPLES camera paths and spends them on the noisiest pixels first (rttnw_render_adaptive_budget):
+rounds that give one more pass to the pixels furthest above the noise bound, --spp being the cap; pixels the budget never reached stay black.  It
+works with --resume, --save-state and --spp-map, prints the samples traced and the rounds run, and does not combine with --preview, --guided,
+--refine, --devices, --window or --passes.
 """
 import argparse
 import sys
@@ -91,6 +95,8 @@ def main(argv=None):
                     "(rttnw_render_adaptive_denoised); writes the denoised image")
     ap.add_argument("--preview", type=int, default=None, metavar="L", help="adaptive sampling: trace 1 pixel in 4^L (x %% 2^L == 0 and y %% 2^L == 0, "
                     "L = 0 .. 6) and reconstruct the frame from them (rttnw_render_preview); writes the reconstruction")
+    ap.add_argument("--budget", type=int, default=None, metavar="SAMPLES", help="adaptive sampling: trace at most SAMPLES camera paths, the noisiest "
+                    "pixels first (rttnw_render_adaptive_budget)")
     ap.add_argument("--features", default=None, metavar="PREFIX", help="write the first-hit feature buffers as PREFIX_albedo.png, "
                     "PREFIX_normal.png, PREFIX_depth.png, PREFIX_alpha.png")
     ap.add_argument("--window", default=None, metavar="X0,Y0,X1,Y1", help="render pixels [X0, X1) x [Y0, Y1) of the frame only (row 0 = top) "
@@ -106,6 +112,21 @@ def main(argv=None):
     except SystemExit:
         print("There was an error", file=sys.stderr)   # DummyError, main.rs:260-268
         raise
+    if args.budget is not None:
+        if args.noise is None:
+            print("--budget needs --noise: it is the adaptive render under a budget of samples", file=sys.stderr)
+            return 1
+        clash = [name for name, on in (("--preview", args.preview is not None), ("--guided", args.guided), ("--refine", args.refine is not None),
+                                       ("--devices", args.devices is not None), ("--window", args.window is not None), ("--passes", args.passes > 1)) if on]
+        if clash:
+            print("--budget does not combine with %s: it runs on one GPU, over the whole frame, on the raw noise" % ", ".join(clash), file=sys.stderr)
+            return 1
+        if args.budget < 0:
+            print("--budget must be at least 0", file=sys.stderr)
+            return 1
+        if not (args.noise > 0.0 or args.abs_noise > 0.0):
+            print("--budget needs a noise bound above 0 to rank pixels by (--noise or --abs-noise)", file=sys.stderr)
+            return 1
     if args.preview is not None:
         if args.noise is None:
             print("--preview needs --noise: it is the adaptive render of a lattice of the frame, reconstructed", file=sys.stderr)
@@ -267,6 +288,22 @@ def main(argv=None):
             if args.save_state is not None:
                 with open(args.save_state, "wb") as f:
                     np.save(f, g["state"])
+        elif args.budget is not None:
+            state = None
+            if args.resume is not None:
+                try:
+                    state = np.load(args.resume)
+                except (OSError, ValueError) as e:
+                    print("--resume %s: %s" % (args.resume, e), file=sys.stderr)
+                    return 1
+            lin, rgba, spp_map, se, st, state, n_rounds = render.render_adaptive_budget(sc, cam, p, args.budget, state=state, pass_spp=args.pass_spp,
+                                                                                       rel_error=args.noise, abs_error=args.abs_noise,
+                                                                                       want_state=args.save_state is not None)
+            rounds = "; budget: %d of %d samples in %d rounds, %d of %d pixels hold samples" % (st.samples, args.budget, n_rounds,
+                                                                                             int((spp_map > 0).sum()), w * h)
+            if args.save_state is not None:
+                with open(args.save_state, "wb") as f:
+                    np.save(f, state)
         elif refine is not None or args.resume is not None or args.save_state is not None:
             state = None
             if args.resume is not None:

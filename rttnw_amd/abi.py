@@ -70,6 +70,11 @@ class Preview(C.Structure):
     _fields_ = [("level", C.c_uint32), ("feature_spp", C.c_uint32), ("denoise", Denoise)]
 
 
+class Budget(C.Structure):
+    """`rttnw_budget` — what `rttnw_render_adaptive_budget` takes beside the stopping rule: the samples the call may trace and the size of a round."""
+    _fields_ = [("samples", C.c_uint64), ("round_pixels", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
 class TileLayout(C.Structure):
     _fields_ = [("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32), ("n_tiles", C.c_uint32),
                 ("tiles_per_rank", C.c_uint32), ("pixels_per_rank", C.c_uint32)]
@@ -141,6 +146,10 @@ PRODUCT_FUNCS = [
                               C.POINTER(Denoise), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("render_preview", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Preview), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    ("budget_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint64,
+                                C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("render_adaptive_budget", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Budget), C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("render_tiles_device", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_void_p,
                                       C.c_void_p, C.POINTER(Stats)]),
     ("untile_device", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

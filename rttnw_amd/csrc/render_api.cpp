@@ -1,12 +1,13 @@
 // render_api.cpp — the extern "C" half of the device side of include/rttnw_hip.h: device state, render entry points,
 // rttnw_render_multi and rttnw_render_adaptive_multi (per-device streams, RCCL gather), rttnw_render_adaptive_denoised (the rounds that alternate the
-// adaptive passes with the denoiser's).  Host code only; the kernels and their launch code live in render_f32.hip / render_f64.hip (render_common.hpp
-// says why there are two), denoise.hip and guided.hip.
+// adaptive passes with the denoiser's), rttnw_render_adaptive_budget (the rounds that alternate a selection with the passes it chose).  Host code only; the kernels and their launch code live in render_f32.hip / render_f64.hip (render_common.hpp
+// says why there are two), denoise.hip, guided.hip and budget.hip.
 // No CPU fallback: every entry point needs a HIP device.
 #include "render_common.hpp"
 #include "bvh_build.hpp"
 #include "feature_api.hpp"
 #include "guided.hpp"
+#include "budget.hpp"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -1450,6 +1451,178 @@ extern "C" int rttnw_render_preview(rttnw_scene* s, const rttnw_camera_desc* cam
     }
     if (int rc = validate(s, cam, p)) return rc;
     return preview_render(s, cam, *p, *a, *v, out_linear_rgb, out_rgba8, out_valid, out_spp, out_raw_linear_rgb, out_raw_stderr_rgb, state_out, stats);
+}
+
+// ---------------------------------------------------------------------------------------------
+// rttnw_budget_select and rttnw_render_adaptive_budget (include/rttnw_hip.h has the contracts, DESIGN.md §10a "budgeted form" the why): adaptive rounds
+// under a budget of samples.  One rank on the scene's device, default stream.  A round: the running sums COPIED and turned into means and auxiliary
+// records by adaptive_finish_launch (as in adaptive_denoised_render), the selection of the worst pixels the budget still pays for (budget.hpp) — which
+// leaves their bytes on the device and a small record for the host: how many, and per level the blocks that hold one — and then, per occupied level
+// in ascending order, the windowed form's list pass: adaptive_level_select_launch over the selection bytes, the list, render_tiles_t under a cap of
+// (k+1)B and zero tolerances.  The selection bytes are that pass's ACTIVE bytes: its resolve step clears the byte of every pixel it traced (n == its
+// cap), so a pixel that moved from level k to k + 1 is not listed a second time in the same round.
+// ---------------------------------------------------------------------------------------------
+extern "C" int rttnw_budget_select(uint32_t width, uint32_t height, const double* linear_rgb, const double* stderr_rgb, const uint32_t* spp, uint32_t cap,
+                                   double rel_error, double abs_error, uint64_t max_pixels, uint8_t* out_mask, double* out_priority,
+                                   uint64_t* out_selected, double* kernel_ms) {
+    using namespace rt;
+    if (!linear_rgb) { set_last_error("budget_select: linear_rgb is NULL"); return RTTNW_ERR_INVALID; }
+    if (!stderr_rgb) { set_last_error("budget_select: stderr_rgb is NULL"); return RTTNW_ERR_INVALID; }
+    if (!spp) { set_last_error("budget_select: spp is NULL"); return RTTNW_ERR_INVALID; }
+    if (!width || !height) { set_last_error("budget_select: width * height is 0"); return RTTNW_ERR_INVALID; }
+    if (cap == 0) { set_last_error("budget_select: cap is 0"); return RTTNW_ERR_INVALID; }
+    if (!(rel_error >= 0.0) || !(abs_error >= 0.0)) { set_last_error("budget_select: rel_error and abs_error must be >= 0 (and not NaN)"); return RTTNW_ERR_INVALID; }
+    if (rel_error == 0.0 && abs_error == 0.0) {
+        set_last_error("budget_select: rel_error and abs_error are both 0 (a priority relative to a tolerance of nothing ranks every noisy pixel +inf)");
+        return RTTNW_ERR_INVALID;
+    }
+    // (the key holds the row-major index in 32 bits)
+    if (uint64_t(width) * height > 0xFFFFFFFFull) { set_last_error("budget_select: width * height is limited to 2^32 - 1 pixels"); return RTTNW_ERR_UNSUPPORTED; }
+    return budget_select_device(width, height, linear_rgb, stderr_rgb, spp, cap, rel_error, abs_error, max_pixels, out_mask, out_priority, out_selected,
+                                kernel_ms);
+}
+
+namespace rt {
+static int adaptive_budget_render(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const rttnw_budget& bg,
+                                  const double* state_in, double* state_out, double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp,
+                                  double* out_stderr_rgb, rttnw_stats* stats) {
+    DeviceGuard restore; // (the caller's device is current again after EVERY return below, the error paths included)
+    DeviceState* d = s->device;
+    HIP_TRY(hipSetDevice(d->device));
+    rttnw_tile_layout L;
+    fill_layout(p.width, p.height, 1, L);
+    const size_t npx = size_t(p.width) * p.height, ppr = L.pixels_per_rank, rsz = p.precision == RTTNW_F32 ? sizeof(float) : sizeof(double);
+    const uint32_t n_blocks = L.n_tiles * 16u, B = a.pass_spp, n_levels = p.spp / B;
+    const uint64_t round_pixels = bg.round_pixels ? bg.round_pixels : (uint64_t(npx) + 1u) / 2u; // (half the frame: DESIGN.md §10a has the measurement)
+    const hipStream_t stream = nullptr;
+    // everything that allocates, before the first launch: the adaptive passes' buffers, this call's own, and what a list pass over every block needs
+    HIP_TRY(d->packed.grow(ppr * 4 * rsz));
+    HIP_TRY(d->ad_state.grow(ppr * sizeof(AdaptivePixel)));
+    HIP_TRY(d->list_quads.grow(size_t(n_blocks) * sizeof(uint32_t)));
+    HIP_TRY(d->list_scan.grow(quad_scan_words(n_blocks) * sizeof(uint32_t)));
+    HIP_TRY(d->rg_linear.grow(npx * 3 * rsz));
+    HIP_TRY(d->rg_rgba.grow(npx * 4));
+    HIP_TRY(d->rg_spp.grow(npx * sizeof(uint32_t)));
+    HIP_TRY(d->rg_stderr.grow(npx * 3 * sizeof(double)));
+    DevBuf<uint8_t> select, marks, means;
+    DevBuf<uint32_t> record;
+    DevBuf<double> aux, records;
+    BudgetWorkspace work;
+    HIP_TRY(select.alloc(ppr));
+    HIP_TRY(marks.alloc(ppr));
+    HIP_TRY(means.alloc(ppr * 4 * rsz));
+    HIP_TRY(record.alloc(1u + size_t(n_levels)));
+    HIP_TRY(aux.alloc(ppr * 4));
+    if (state_in || state_out) HIP_TRY(records.alloc(ppr * STATE_RECORD_DOUBLES));
+    HIP_TRY(work.alloc(npx));
+    Event ev0, ev1;
+    HIP_TRY(create_event(ev0));
+    HIP_TRY(create_event(ev1));
+    rttnw_params pass = p;
+    pass.spp = B;
+    ListPass ad;
+    ad.state = (AdaptivePixel*)d->ad_state.p;
+    ad.active = select.p;
+    ad.quads = (const uint32_t*)d->list_quads.p;
+    ad.n_quads = n_blocks;
+    ad.first = false; // (level 0 too is a list pass on zero sums: 0 + c0 is the chain's first addition, as in the windowed form)
+    if (int rc = render_tiles_any(s, d, cam, &pass, d->packed.p, stream, nullptr, false, true, &ad)) return rc;
+    if (stats)
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_rank_stats_t, s, d, &p, stats)) return rc;
+    // a state_in: its row-major records in the rank's packed order (pixels outside the image keep zero records)
+    std::vector<double> host_records;
+    if (state_in) {
+        host_records.assign(ppr * STATE_RECORD_DOUBLES, 0.0);
+        for (uint32_t y = 0; y < p.height; ++y)
+            for (uint32_t x = 0; x < p.width; ++x) {
+                uint32_t owner;
+                size_t idx;
+                packed_place(x, y, L, 1, owner, idx);
+                const double* rec = state_in + STATE_HEADER_DOUBLES + (size_t(y) * p.width + x) * STATE_RECORD_DOUBLES;
+                std::copy(rec, rec + STATE_RECORD_DOUBLES, host_records.begin() + idx * STATE_RECORD_DOUBLES);
+            }
+    }
+
+    // before round 0: the state comes in (or zero sums and zero noise state), and nothing is selected
+    HIP_TRY(hipEventRecord(ev0.get(), stream));
+    if (state_in) {
+        HIP_TRY(hipMemcpyAsync(records.p, host_records.data(), host_records.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        // (the import's active bytes, under the caller's rule, go to `marks` and are not read: the selection decides who is traced)
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_state_import_launch, records.p, d->packed.p, d->ad_state.p, marks.p, L.pixels_per_rank, p.spp,
+                                     a.rel_error, a.abs_error, stream)) return rc;
+    } else {
+        HIP_TRY(hipMemsetAsync(d->packed.p, 0, ppr * 4 * rsz, stream));
+        HIP_TRY(hipMemsetAsync(d->ad_state.p, 0, ppr * sizeof(AdaptivePixel), stream));
+    }
+    HIP_TRY(hipMemsetAsync(select.p, 0, ppr, stream)); // (the rest of an edge tile is never selected: a round writes the bytes of the image's pixels only)
+    uint64_t remaining = bg.samples, samples = 0, rounds = 0;
+    std::vector<uint32_t> census(1u + size_t(n_levels));
+    ad.rel_error = 0.0;
+    ad.abs_error = 0.0;
+    for (;;) {
+        // the values every pixel is ranked by — and the call's outputs, if this round selects nothing: the adaptive render's own division on a copy of the sums
+        HIP_TRY(hipMemcpyAsync(means.p, d->packed.p, ppr * 4 * rsz, hipMemcpyDeviceToDevice, stream));
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_finish_launch, means.p, d->ad_state.p, aux.p, L.pixels_per_rank, L.n_tiles * 64u, stream)) return rc;
+        const uint64_t max_pixels = std::min<uint64_t>(round_pixels, remaining / B);
+        if (max_pixels == 0) break; // the budget pays for no further pass
+        // the selection, and in one copy its record: the pixels selected and, per level, the length of the list over them
+        if (int rc = budget_round_launch(work, p.precision, means.p, aux.p, d->ad_state.p, p.width, p.height, p.spp, B, a.rel_error, a.abs_error, max_pixels,
+                                         select.p, record.p, stream)) return rc;
+        HIP_TRY(hipMemcpy(census.data(), record.p, census.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (census[0] == 0) break; // no candidate is left
+        ++rounds;
+        remaining -= uint64_t(census[0]) * B;
+        samples += uint64_t(census[0]) * B;
+        for (uint32_t k = 0; k < n_levels; ++k) {
+            if (census[1u + k] == 0) continue;
+            if (int rc = RT_BY_PRECISION(p.precision, adaptive_level_select_launch, select.p, d->ad_state.p, marks.p, n_blocks * 4u, k * B, stream)) return rc;
+            if (int rc = RT_BY_PRECISION(p.precision, enqueue_quad_list, marks.p, n_blocks, (uint32_t*)d->list_scan.p, (uint32_t*)d->list_quads.p, stream)) return rc;
+            pass.sample_begin = p.sample_begin + k * B;
+            ad.n_quads = census[1u + k];
+            ad.cap = (k + 1u) * B;
+            if (int rc = render_tiles_any(s, d, cam, &pass, d->packed.p, stream, nullptr, false, false, &ad)) return rc;
+        }
+    }
+    // the state the call ends in, and the whole frame as the windowed form reports a window (`means` and `aux` are those of that state)
+    if (state_out)
+        if (int rc = RT_BY_PRECISION(p.precision, adaptive_state_export_launch, d->packed.p, d->ad_state.p, records.p, L.pixels_per_rank, L.n_tiles * 64u, stream)) return rc;
+    if (int rc = RT_BY_PRECISION(p.precision, adaptive_region_window_launch, p.width, p.height, 1u, means.p, aux.p, d->rg_linear.p, d->rg_rgba.p,
+                                 (uint32_t*)d->rg_spp.p, (double*)d->rg_stderr.p, 0u, 0u, p.width, p.height, stream)) return rc;
+    HIP_TRY(hipEventRecord(ev1.get(), stream));
+    HIP_TRY(hipDeviceSynchronize());
+    if (stats) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+        stats->kernel_ms = ms;
+        stats->samples = samples;
+        stats->reserved |= uint32_t(std::min<uint64_t>(rounds, 0xFFFFu)) << 16;
+    }
+    if (out_spp) HIP_TRY(hipMemcpy(out_spp, d->rg_spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_stderr_rgb) HIP_TRY(hipMemcpy(out_stderr_rgb, d->rg_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (state_out)
+        if (int rc = single_rank_state_out(p, a, cam, L, records.p, state_out)) return rc;
+    return copy_image_out("render_adaptive_budget", d->rg_rgba, d->rg_linear, p.precision, npx, out_rgba8, out_linear_rgb);
+}
+} // namespace rt
+
+extern "C" int rttnw_render_adaptive_budget(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, const rttnw_budget* b,
+                                            const double* state_in, double* state_out, double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp,
+                                            double* out_stderr_rgb, rttnw_stats* stats) {
+    using namespace rt;
+    // the refusals, in the header's order: none of them needs a device
+    if (!p || !a || !b) { set_last_error("render_adaptive_budget: NULL argument (p, a or b)"); return RTTNW_ERR_INVALID; }
+    if (int rc = refuse_adaptive_misuse("render_adaptive_budget", p, a)) return rc;
+    if (int rc = refuse_host_output_misuse("render_adaptive_budget", a->reserved0, p)) return rc;
+    if (b->reserved0 != 0) { set_last_error("render_adaptive_budget: b->reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (a->rel_error == 0.0 && a->abs_error == 0.0) {
+        set_last_error("render_adaptive_budget: rel_error and abs_error are both 0 (a priority relative to a tolerance of nothing ranks every noisy pixel +inf)");
+        return RTTNW_ERR_INVALID;
+    }
+    uint32_t first_level = 0; // (not used: every round finds the levels of its own pixels)
+    if (state_in)
+        if (int rc = refuse_state_misuse("render_adaptive_budget", true, *p, *a, cam, state_in, first_level)) return rc;
+    if (int rc = validate(s, cam, p)) return rc;
+    return adaptive_budget_render(s, cam, *p, *a, *b, state_in, state_out, out_linear_rgb, out_rgba8, out_spp, out_stderr_rgb, stats);
 }
 
 // Release what the library keeps for the life of the process (today: the RCCL communicator sets of rttnw_render_multi).  Scenes

@@ -315,6 +315,59 @@ def render_preview(scene, cam, params, level, pass_spp=64, rel_error=0.02, abs_e
     return out
 
 
+def budget_select(linear, stderr, spp, cap, rel_error, abs_error, max_pixels, want_ms=False):
+    """`rttnw_budget_select`: which pixels get the next adaptive pass when only `max_pixels` of them can — the candidates (no samples yet, or
+    below `cap` and short of stderr <= abs_error + rel_error * mean in some channel) ranked by priority = max over r, g, b of stderr / tolerance,
+    descending, then by row-major index.  `linear` and `stderr` (HxWx3) are never read where `spp` (HxW) is 0.  Returns (mask HxW u8, priority HxW
+    f64 — 0 for a non-candidate, +inf for a pixel without samples —, the number selected) — and the device time in ms after them with `want_ms`."""
+    b = library.product()
+    n = np.ascontiguousarray(spp, dtype=np.uint32)
+    h, w = n.shape
+    lin = np.ascontiguousarray(linear, dtype=np.float64)
+    se = np.ascontiguousarray(stderr, dtype=np.float64)
+    assert lin.shape == (h, w, 3) and se.shape == (h, w, 3)
+    mask = np.zeros((h, w), dtype=np.uint8)
+    rho = np.zeros((h, w), dtype=np.float64)
+    m, ms = C.c_uint64(0), C.c_double(0.0)
+    rc = b.budget_select(w, h, lin.ctypes.data, se.ctypes.data, n.ctypes.data, cap, rel_error, abs_error, int(max_pixels), mask.ctypes.data,
+                         rho.ctypes.data, C.byref(m), C.byref(ms))
+    check(rc, b, "rttnw_budget_select")
+    return (mask, rho, int(m.value), ms.value) if want_ms else (mask, rho, int(m.value))
+
+
+def render_adaptive_budget(scene, cam, params, samples, round_pixels=0, state=None, pass_spp=64, rel_error=0.02, abs_error=0.0, want_state=True):
+    """`rttnw_render_adaptive_budget`: the adaptive render under a budget — at most `samples` camera paths, spent in rounds of at most
+    `round_pixels` pixels (0 = half the frame), each round giving one more pass of `pass_spp` samples to the pixels `budget_select` ranks
+    worst under the tolerances and `params.spp` (the cap).  `state` is the frame-sized array an adaptive call returned (a pixel never sampled is a
+    record of zeros); None stands for all zeros.  The same `spp_chunk` default as `render_adaptive`.  Returns (linear HxWx3 f64, rgba8 HxWx4 u8,
+    spp_map HxW u32, stderr HxWx3 f64, Stats, state or None, rounds run); a pixel without samples is zero everywhere, alpha included."""
+    import copy
+    b = library.product()
+    p = copy.copy(params)
+    if p.spp_chunk == 0:
+        p.spp_chunk = max(1, pass_spp // 16)
+    h, w = p.height, p.width
+    lin = np.zeros((h, w, 3), dtype=np.float64)
+    rgba = np.zeros((h, w, 4), dtype=np.uint8)
+    spp = np.zeros((h, w), dtype=np.uint32)
+    se = np.zeros((h, w, 3), dtype=np.float64)
+    n_doubles = int(b.adaptive_state_doubles(w, h))
+    st_in = None
+    if state is not None:
+        st_in = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
+        if st_in.size != n_doubles:
+            raise ValueError("render_adaptive_budget: a state of a %dx%d frame holds %d doubles, got %d" % (w, h, n_doubles, st_in.size))
+    st_out = np.zeros(n_doubles, dtype=np.float64) if want_state else None
+    st = Stats()
+    a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
+    bg = abi.Budget(samples=int(samples), round_pixels=int(round_pixels), reserved0=0)
+    rc = b.render_adaptive_budget(scene.handle, C.byref(cam), C.byref(p), C.byref(a), C.byref(bg), None if st_in is None else st_in.ctypes.data,
+                                  None if st_out is None else st_out.ctypes.data, lin.ctypes.data, rgba.ctypes.data, spp.ctypes.data,
+                                  se.ctypes.data, C.byref(st))
+    check(rc, b, "rttnw_render_adaptive_budget")
+    return lin, rgba, spp, se, st, st_out, st.reserved >> 16
+
+
 def render_host_passes(scene, cam, params, passes, on_pass=None):
     """The same image as `render_host`, in `passes` passes over disjoint sample ranges (`rttnw_params.sample_begin`):
     after every pass the running mean is a complete, displayable estimate — progressive display and a natural
