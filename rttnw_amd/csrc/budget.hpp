@@ -1,4 +1,4 @@
-// budget.hpp — what render_api.cpp calls for rttnw_budget_select and for the rounds of rttnw_render_adaptive_budget (include/rttnw_hip.h has the
+// budget.hpp — what render_adaptive_api.cpp calls for rttnw_budget_select and for the rounds of rttnw_render_adaptive_budget (include/rttnw_hip.h has the
 // contract, DESIGN.md §10a "budgeted form" the why): budget.hip holds the launch code, budget_kernels.hpp the kernels, budget_select.hpp the
 // arithmetic.  The *_launch functions enqueue on `stream` and nothing else — no allocation, no copy, no wait.
 #pragma once

@@ -33,7 +33,7 @@ int reconstruct_passes_device(uint32_t width, uint32_t height, const double* d_i
                               const double* d_normal, const double* d_depth, const double* d_alpha, uint32_t iterations, const DenoiseParams& prm,
                               double* const d_c[2], double* const d_v[2], uint8_t* const d_h[2], uint8_t* d_rgba, uint8_t* d_out_valid,
                               hipStream_t stream, int& out);
-// What rttnw_render_preview (render_api.cpp) enqueues around its rounds: the alive bytes of the lattice x % 2^level == 0 && y % 2^level == 0 in the
+// What rttnw_render_preview (render_adaptive_api.cpp) enqueues around its rounds: the alive bytes of the lattice x % 2^level == 0 && y % 2^level == 0 in the
 // packed order of a frame on one rank, in place of guided_begin_launch's all-alive bytes; and the valid byte (spp != 0) of every pixel of the frame
 int preview_lattice_launch(uint8_t* d_alive, uint32_t pixels_per_rank, uint32_t width, uint32_t height, uint32_t level, hipStream_t stream);
 int preview_valid_launch(const uint32_t* d_spp, uint8_t* d_valid, uint32_t width, uint32_t height, hipStream_t stream);

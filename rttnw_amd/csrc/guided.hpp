@@ -1,4 +1,4 @@
-// guided.hpp — what rttnw_render_adaptive_denoised (render_api.cpp; include/rttnw_hip.h has the contract, DESIGN.md §10a "filter-guided form" the
+// guided.hpp — what rttnw_render_adaptive_denoised (render_adaptive_api.cpp; include/rttnw_hip.h has the contract, DESIGN.md §10a "filter-guided form" the
 // why) launches between a round's trace and its filter, and behind the filter: guided.hip holds the launch code, guided_kernels.hpp the kernels.
 // Everything is enqueued on `stream` — no allocation, no copy, no wait — over buffers of the caller's on one device; the frame lives on ONE rank
 // (packed order: tile * 64 + y * 8 + x, tiles in the permuted order of a single rank).

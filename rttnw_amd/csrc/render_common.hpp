@@ -1,5 +1,8 @@
 // render_common.hpp — host-side state of the device half of include/rttnw_hip.h, shared by its translation units:
-//   render_api.cpp   the extern "C" entry points, device state, rttnw_render_multi + RCCL (host code only)
+//   render_api.cpp   device state, validation and the single-GPU extern "C" entry points (host code only, like the next two)
+//   render_multi.cpp rttnw_render_multi + RCCL; render_multi.hpp: its plan and steps, which the adaptive forms over ranks walk too
+//   render_adaptive_api.cpp  the adaptive family beyond rttnw_render_adaptive: multi, resume, region, denoised, preview, budget
+//                    (adaptive_state.hpp: the state's host side, plain C++)
 //   render_f32.hip   the F32 instantiation of the kernels (trace_kernels.hpp) and of their launch code (render_tiles.hpp)
 //   render_f64.hip   the F64 instantiation — a translation unit of its own because its code wants other compiler settings
 //                    than the f32 code (Makefile: machine LICM off, 1024-thread blocks) and because the two halves build in
@@ -317,7 +320,7 @@ inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, co
 // both builds and what a precision's translation unit instantiates (RT_INSTANTIATE_PRECISION): a new entry point is one line here.
 //   render_adaptive_t  rttnw_render_adaptive's device half: every pass, then the image (d->linear, d->rgba) and the maps (d->ad_spp, d->ad_stderr) on the device
 //   render_region_t    rttnw_render_region's device half: selection, list, trace, resolve; the window's image on the device (d->rg_linear, d->rg_rgba)
-//   enqueue_quad_list, adaptive_finish_launch, untile_aux_launch   what rttnw_render_adaptive_multi (render_api.cpp) enqueues beside render_tiles_t's passes
+//   enqueue_quad_list, adaptive_finish_launch, untile_aux_launch   what rttnw_render_adaptive_multi (render_adaptive_api.cpp) enqueues beside render_tiles_t's passes
 //   adaptive_state_import_launch, adaptive_state_export_launch, adaptive_level_select_launch, adaptive_rank_stats_t   what rttnw_render_adaptive_resume adds to those
 //   adaptive_region_activate_launch, adaptive_region_window_launch   ... and rttnw_render_adaptive_region to those: selection and first active bytes, the window's outputs
 #define RT_PRECISION_ENTRY_POINTS(X, R)                                                                                                              \

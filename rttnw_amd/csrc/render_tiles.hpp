@@ -350,7 +350,7 @@ int render_adaptive_t(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttn
     return RTTNW_OK;
 }
 
-// rttnw_render_adaptive_multi's two launches of its own (render_api.cpp has the pass loop; the passes themselves are render_tiles_t's): a rank's
+// rttnw_render_adaptive_multi's two launches of its own (render_adaptive_api.cpp has the pass loop; the passes themselves are render_tiles_t's): a rank's
 // packed sums and noise state to means and auxiliary records once its passes are over, and the gathered records to the two maps on the root.
 template <typename R>
 int adaptive_finish_launch(void* d_packed, const void* d_state, double* d_aux, uint32_t pixels_per_rank, uint32_t rank_pixels, hipStream_t stream) {
@@ -369,7 +369,7 @@ int untile_aux_launch(uint32_t width, uint32_t height, uint32_t world, const dou
     return RTTNW_OK;
 }
 
-// rttnw_render_adaptive_resume's launches of its own (render_api.cpp has the level loop): a rank's packed state records to its running sums, noise
+// rttnw_render_adaptive_resume's launches of its own (render_adaptive_api.cpp has the level loop): a rank's packed state records to its running sums, noise
 // state and active bytes; the same back, before adaptive_finish_launch turns the sums into means; and the marks of one level for the list build.
 template <typename R>
 int adaptive_state_import_launch(const double* d_records, void* d_packed, void* d_state, uint8_t* d_active, uint32_t pixels_per_rank, uint32_t cap,
@@ -409,7 +409,7 @@ int adaptive_rank_stats_t(::rttnw_scene* s, DeviceState* d, const rttnw_params* 
     return RTTNW_OK;
 }
 
-// rttnw_render_adaptive_region's launches of its own (render_api.cpp adaptive_node_render has the level loop, which is the resumed render's): behind
+// rttnw_render_adaptive_region's launches of its own (render_adaptive_api.cpp adaptive_node_render has the level loop, which is the resumed render's): behind
 // the state's import, the rank's selection bytes (region_select_kernel over ITS tiles: p->tile_rank / p->tile_world; d_mask: the window-sized mask on
 // this device, nullptr = the whole window) and the active bytes the call starts from; and, on the root, the window's four outputs from the gathered
 // means and auxiliary records.

@@ -159,6 +159,28 @@ def test_a_budget_that_never_binds_is_the_resumed_render(scenes, precision):
     assert rounds[1] == st.samples // B and rounds[0] < rounds[333] < rounds[1]
 
 
+@pytest.mark.parametrize("precision", [abi.F64, abi.F32], ids=["f64", "f32"])
+def test_its_state_resumes_over_three_ranks_with_nothing_left_to_do(scenes, precision):
+    """The two host paths of a state, crossed: state_out of the one-rank form (the whole frame in one packed order) goes in as state_in of
+    rttnw_render_adaptive_resume over device_ids [0, 0, 0] (three ranks' packed orders), under the same cap, B and tolerances.  cornell_box 45x37 —
+    edge tiles on both axes, 30 tiles over 3 ranks —, cap 32, B 8, a budget of w * h * cap samples, which never binds: every pixel has stopped or
+    stands at the cap, so the resumed call traces nothing, hands the state back bit for bit and reports the budget call's four outputs."""
+    w, h, cap, b = 45, 37, 32, 8
+    sc, setup = scenes["cornell_box"]
+    cam, p = S.params_for(setup, w, h, cap, precision=precision, spp_chunk=1)
+    lin, rgba, spp, se, st, state, rounds = render.render_adaptive_budget(sc, cam, p, w * h * cap, 0, pass_spp=b, rel_error=0.5, abs_error=TOL["ab"])
+    print("precision %d: %d rounds, n_q histogram %s" % (precision, rounds, _histogram(spp)))
+    assert state.shape == (64 + 12 * w * h,) and (spp >= b).all() and st.samples == int(spp.sum(dtype=np.uint64))
+    given = state.copy()
+    lin_r, rgba_r, spp_r, se_r, st_r, state_r = render.render_adaptive_resume(sc, cam, p, given, [0, 0, 0], pass_spp=b, rel_error=0.5,
+                                                                              abs_error=TOL["ab"])
+    assert np.array_equal(given, state)                                        # state_in is read only
+    assert np.array_equal(state_r.view(np.uint64), state.view(np.uint64))
+    assert sum(s.samples for s in st_r) == 0
+    for key, got, ref in (("linear", lin_r, lin), ("rgba8", rgba_r, rgba), ("spp", spp_r, spp), ("stderr", se_r, se)):
+        assert np.array_equal(got, ref, equal_nan=key == "stderr"), (key, int((got != ref).sum()))
+
+
 @pytest.mark.parametrize("precision", PRECISIONS, ids=["f64", "f32", "f64strict"])
 def test_from_a_preview_the_unsampled_pixels_come_first(scenes, precision):
     """state_in = rttnw_render_preview(level 2)'s state_out and a budget of exactly the missing pixels times B: every zero record is filled before
