@@ -75,6 +75,63 @@ def node_ms(devices, stats):
     return max(per_device.values())
 
 
+WANTS_WINDOW = "%s wants X0,Y0,X1,Y1: four non-negative integers with X0 < X1 and Y0 < Y1, got %r"
+
+
+def refusal(args, refine, devices, window):
+    """The first rule the flags break, as the line for stderr, or None.  `refine`, `devices` and `window` are the parsed values, None where malformed."""
+    on = {"--noise": args.noise is not None, "--budget": args.budget is not None, "--preview": args.preview is not None, "--guided": args.guided,
+          "--refine": args.refine is not None, "--devices": args.devices is not None, "--resume": args.resume is not None,
+          "--save-state": args.save_state is not None, "--window": args.window is not None, "--passes": args.passes > 1,
+          "--features": args.features is not None, "--denoise": args.denoise}
+    iterations = (0 <= args.denoise_iterations <= 8, "--denoise-iterations must be 0 .. 8")
+    state_needs, state_clashes = "only the adaptive render has a state", ("--window", "--passes")
+    # in the order they are checked: (flag, why it needs --noise or None, the flags it does not combine with, the reason given for that,
+    # [(holds, the message if not)] checked before all that, the same checked after it)
+    rules = [
+        ("--budget", "it is the adaptive render under a budget of samples", ("--preview", "--guided", "--refine", "--devices", "--window", "--passes"),
+         ": it runs on one GPU, over the whole frame, on the raw noise", [],
+         [(not on["--budget"] or args.budget >= 0, "--budget must be at least 0"),
+          ((args.noise or 0.0) > 0.0 or args.abs_noise > 0.0, "--budget needs a noise bound above 0 to rank pixels by (--noise or --abs-noise)")]),
+        ("--preview", "it is the adaptive render of a lattice of the frame, reconstructed",
+         ("--devices", "--resume", "--refine", "--guided", "--window", "--passes"), ": it runs on one GPU, over the whole frame, from nothing", [],
+         [(not on["--preview"] or 0 <= args.preview <= 6, "--preview must be 0 .. 6"), iterations]),
+        ("--guided", "it is the adaptive render stopped on the filtered image's noise", ("--devices", "--resume", "--refine", "--window", "--passes"),
+         ": it runs on one GPU, over the whole frame, from nothing", [], [iterations]),
+        ("--refine", "it brings a window to a noise bound", ("--window", "--passes", "--features", "--denoise"),
+         ": it runs the adaptive render over a window of the frame", [], [(refine is not None, WANTS_WINDOW % ("--refine", args.refine))]),
+        ("--devices", None, ("--window", "--features", "--denoise", "--passes"), ": it runs the plain and the adaptive render only",
+         [(devices is not None, "--devices wants D0,D1,...: 1 to 64 non-negative device numbers separated by commas, got %r" % args.devices)], []),
+        ("--resume", state_needs, state_clashes, "", [], []),
+        ("--save-state", state_needs, state_clashes, "", [], []),
+        ("--window", None, ("--noise", "--denoise", "--features", "--passes"), ": it renders pixels of the plain frame only",
+         [(window is not None, WANTS_WINDOW % ("--window", args.window))], []),
+    ]
+    for flag, needs_noise, clashes, why, before, after in rules:
+        if not on[flag]:
+            continue
+        clash = [name for name in clashes if on[name]]
+        for holds, message in before + [(on["--noise"] or needs_noise is None, "%s needs --noise: %s" % (flag, needs_noise)),
+                                        (not clash, "%s does not combine with %s%s" % (flag, ", ".join(clash), why))] + after:
+            if not holds:
+                return message
+    return None
+
+
+def save_state(path, state):
+    with open(path, "wb") as f:    # (an open file: np.save would append .npy to a bare name)
+        np.save(f, state)
+
+
+def load_state(path):
+    """The adaptive state in `path`, or None after saying on stderr why it cannot be read."""
+    try:
+        return np.load(path)
+    except (OSError, ValueError) as e:
+        print("--resume %s: %s" % (path, e), file=sys.stderr)
+        return None
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(add_help=True, usage=USAGE)
     ap.add_argument("scene", type=int)
@@ -112,94 +169,13 @@ def main(argv=None):
     except SystemExit:
         print("There was an error", file=sys.stderr)   # DummyError, main.rs:260-268
         raise
-    if args.budget is not None:
-        if args.noise is None:
-            print("--budget needs --noise: it is the adaptive render under a budget of samples", file=sys.stderr)
-            return 1
-        clash = [name for name, on in (("--preview", args.preview is not None), ("--guided", args.guided), ("--refine", args.refine is not None),
-                                       ("--devices", args.devices is not None), ("--window", args.window is not None), ("--passes", args.passes > 1)) if on]
-        if clash:
-            print("--budget does not combine with %s: it runs on one GPU, over the whole frame, on the raw noise" % ", ".join(clash), file=sys.stderr)
-            return 1
-        if args.budget < 0:
-            print("--budget must be at least 0", file=sys.stderr)
-            return 1
-        if not (args.noise > 0.0 or args.abs_noise > 0.0):
-            print("--budget needs a noise bound above 0 to rank pixels by (--noise or --abs-noise)", file=sys.stderr)
-            return 1
-    if args.preview is not None:
-        if args.noise is None:
-            print("--preview needs --noise: it is the adaptive render of a lattice of the frame, reconstructed", file=sys.stderr)
-            return 1
-        clash = [name for name, on in (("--devices", args.devices is not None), ("--resume", args.resume is not None), ("--refine", args.refine is not None),
-                                       ("--guided", args.guided), ("--window", args.window is not None), ("--passes", args.passes > 1)) if on]
-        if clash:
-            print("--preview does not combine with %s: it runs on one GPU, over the whole frame, from nothing" % ", ".join(clash), file=sys.stderr)
-            return 1
-        if not 0 <= args.preview <= 6:
-            print("--preview must be 0 .. 6", file=sys.stderr)
-            return 1
-        if not 0 <= args.denoise_iterations <= 8:
-            print("--denoise-iterations must be 0 .. 8", file=sys.stderr)
-            return 1
-    if args.guided:
-        if args.noise is None:
-            print("--guided needs --noise: it is the adaptive render stopped on the filtered image's noise", file=sys.stderr)
-            return 1
-        clash = [name for name, on in (("--devices", args.devices is not None), ("--resume", args.resume is not None), ("--refine", args.refine is not None),
-                                       ("--window", args.window is not None), ("--passes", args.passes > 1)) if on]
-        if clash:
-            print("--guided does not combine with %s: it runs on one GPU, over the whole frame, from nothing" % ", ".join(clash), file=sys.stderr)
-            return 1
-        if not 0 <= args.denoise_iterations <= 8:
-            print("--denoise-iterations must be 0 .. 8", file=sys.stderr)
-            return 1
-    refine = None
-    if args.refine is not None:
-        if args.noise is None:
-            print("--refine needs --noise: it brings a window to a noise bound", file=sys.stderr)
-            return 1
-        clash = [name for name, on in (("--window", args.window is not None), ("--passes", args.passes > 1), ("--features", args.features is not None),
-                                       ("--denoise", args.denoise)) if on]
-        if clash:
-            print("--refine does not combine with %s: it runs the adaptive render over a window of the frame" % ", ".join(clash), file=sys.stderr)
-            return 1
-        refine = parse_window(args.refine)
-        if refine is None:
-            print("--refine wants X0,Y0,X1,Y1: four non-negative integers with X0 < X1 and Y0 < Y1, got %r" % args.refine, file=sys.stderr)
-            return 1
-    devices = None
-    if args.devices is not None:
-        devices = parse_devices(args.devices)
-        if devices is None:
-            print("--devices wants D0,D1,...: 1 to 64 non-negative device numbers separated by commas, got %r" % args.devices, file=sys.stderr)
-            return 1
-        clash = [name for name, on in (("--window", args.window is not None), ("--features", args.features is not None), ("--denoise", args.denoise),
-                                       ("--passes", args.passes > 1)) if on]
-        if clash:
-            print("--devices does not combine with %s: it runs the plain and the adaptive render only" % ", ".join(clash), file=sys.stderr)
-            return 1
-    for flag, value in (("--resume", args.resume), ("--save-state", args.save_state)):
-        if value is None:
-            continue
-        if args.noise is None:
-            print("%s needs --noise: only the adaptive render has a state" % flag, file=sys.stderr)
-            return 1
-        clash = [name for name, on in (("--window", args.window is not None), ("--passes", args.passes > 1)) if on]
-        if clash:
-            print("%s does not combine with %s" % (flag, ", ".join(clash)), file=sys.stderr)
-            return 1
-    window = None
-    if args.window is not None:
-        window = parse_window(args.window)
-        if window is None:
-            print("--window wants X0,Y0,X1,Y1: four non-negative integers with X0 < X1 and Y0 < Y1, got %r" % args.window, file=sys.stderr)
-            return 1
-        clash = [name for name, on in (("--noise", args.noise is not None), ("--denoise", args.denoise), ("--features", args.features is not None),
-                                       ("--passes", args.passes > 1)) if on]
-        if clash:
-            print("--window does not combine with %s: it renders pixels of the plain frame only" % ", ".join(clash), file=sys.stderr)
-            return 1
+    refine = parse_window(args.refine) if args.refine is not None else None
+    devices = parse_devices(args.devices) if args.devices is not None else None
+    window = parse_window(args.window) if args.window is not None else None
+    refused = refusal(args, refine, devices, window)
+    if refused:
+        print(refused, file=sys.stderr)
+        return 1
     from PIL import Image
     from . import abi, library, render
     from .abi import CameraDesc
@@ -271,47 +247,29 @@ def main(argv=None):
             print("--refine %s reaches outside the %dx%d frame" % (args.refine, w, h), file=sys.stderr)
             return 1
         rounds = ""
+        state = None
+        if args.resume is not None:
+            state = load_state(args.resume)
+            if state is None:
+                return 1
         if args.guided:
             g = render.render_adaptive_denoised(sc, cam, p, args.pass_spp, args.noise, args.abs_noise, iterations=args.denoise_iterations,
                                                 want_state=args.save_state is not None)
-            lin, rgba, spp_map, se, st = g["linear"], g["rgba8"], g["spp"], g["stderr"], g["stats"]
+            lin, rgba, spp_map, se, st, state = g["linear"], g["rgba8"], g["spp"], g["stderr"], g["stats"], g["state"]
             rounds = "; guided: %d rounds of %d, %d denoise iterations each" % (g["rounds"], p.spp // args.pass_spp, args.denoise_iterations)
-            if args.save_state is not None:
-                with open(args.save_state, "wb") as f:
-                    np.save(f, g["state"])
         elif args.preview is not None:
             g = render.render_preview(sc, cam, p, args.preview, args.pass_spp, args.noise, args.abs_noise, iterations=args.denoise_iterations,
                                       want_state=args.save_state is not None)
-            lin, rgba, spp_map, se, st = g["linear"], g["rgba8"], g["spp"], g["raw_stderr"], g["stats"]
+            lin, rgba, spp_map, se, st, state = g["linear"], g["rgba8"], g["spp"], g["raw_stderr"], g["stats"], g["state"]
             rounds = "; preview: 1 pixel in %d, %d of %d pixels hold a value, %d denoise iterations" % (4 ** args.preview, int(g["valid"].sum()), w * h,
                                                                                                       args.denoise_iterations)
-            if args.save_state is not None:
-                with open(args.save_state, "wb") as f:
-                    np.save(f, g["state"])
         elif args.budget is not None:
-            state = None
-            if args.resume is not None:
-                try:
-                    state = np.load(args.resume)
-                except (OSError, ValueError) as e:
-                    print("--resume %s: %s" % (args.resume, e), file=sys.stderr)
-                    return 1
             lin, rgba, spp_map, se, st, state, n_rounds = render.render_adaptive_budget(sc, cam, p, args.budget, state=state, pass_spp=args.pass_spp,
                                                                                        rel_error=args.noise, abs_error=args.abs_noise,
                                                                                        want_state=args.save_state is not None)
             rounds = "; budget: %d of %d samples in %d rounds, %d of %d pixels hold samples" % (st.samples, args.budget, n_rounds,
                                                                                              int((spp_map > 0).sum()), w * h)
-            if args.save_state is not None:
-                with open(args.save_state, "wb") as f:
-                    np.save(f, state)
         elif refine is not None or args.resume is not None or args.save_state is not None:
-            state = None
-            if args.resume is not None:
-                try:
-                    state = np.load(args.resume)
-                except (OSError, ValueError) as e:
-                    print("--resume %s: %s" % (args.resume, e), file=sys.stderr)
-                    return 1
             if refine is not None:
                 lin, rgba, spp_map, se, sts, state = render.render_adaptive_region(sc, cam, p, *refine, state=state, device_ids=devices,
                                                                                    pass_spp=args.pass_spp, rel_error=args.noise, abs_error=args.abs_noise,
@@ -324,15 +282,14 @@ def main(argv=None):
                 per_rank = "; per rank: %s" % " ".join(str(x.samples) for x in sts)
             else:
                 st = sts
-            if args.save_state is not None:
-                with open(args.save_state, "wb") as f:    # (an open file: np.save would append .npy to a bare name)
-                    np.save(f, state)
         elif devices is not None:
             lin, rgba, spp_map, se, sts = render.render_adaptive_multi(sc, cam, p, devices, args.pass_spp, args.noise, args.abs_noise)
             st = abi.Stats(samples=sum(x.samples for x in sts), kernel_ms=node_ms(devices, sts))
             per_rank = "; per rank: %s" % " ".join(str(x.samples) for x in sts)
         else:
             lin, rgba, spp_map, se, st = render.render_adaptive(sc, cam, p, args.pass_spp, args.noise, args.abs_noise)
+        if args.save_state is not None:
+            save_state(args.save_state, state)
         Image.fromarray(finish(lin, rgba, se), "RGBA").save(args.out)
         if args.spp_map:
             grey = np.minimum(spp_map.astype(np.float64) / p.spp * 255.0 + 0.5, 255.0).astype(np.uint8)

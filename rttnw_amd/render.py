@@ -3,6 +3,7 @@
 PyTorch is plumbing here (device buffers, the current HIP stream, torch.distributed over RCCL);
 all tracing happens in the hand-written HIP kernels behind `rttnw_render_tiles_device`.
 """
+import copy
 import ctypes as C
 
 import numpy as np
@@ -39,21 +40,73 @@ def render_multi(scene, cam, params, device_ids, want_stats=True):
     return lin, rgba, list(st)
 
 
+def _pass_params(params, pass_spp):
+    """A copy of `params` — the caller's is never written to — with the adaptive drivers' default for a `spp_chunk` of 0: max(1, pass_spp // 16),
+    so that a pass of 16 k samples is exactly one job group of 16 chunks (64 -> 4)."""
+    p = copy.copy(params)
+    if p.spp_chunk == 0:
+        p.spp_chunk = max(1, pass_spp // 16)
+    return p
+
+
+def _frame_outputs(h, w):
+    """Zeroed (linear hxwx3 f64, rgba8 hxwx4 u8, spp_map hxw u32, stderr hxwx3 f64)."""
+    return (np.zeros((h, w, 3), dtype=np.float64), np.zeros((h, w, 4), dtype=np.uint8), np.zeros((h, w), dtype=np.uint32),
+            np.zeros((h, w, 3), dtype=np.float64))
+
+
+def _state_arrays(b, who, p, state, want_state):
+    """(state_in, state_out) of the frame of `p`, either of them None: `state` as contiguous doubles of the right count — a ValueError in the name of
+    `who` otherwise — and a zeroed array for the call to fill."""
+    n_doubles = int(b.adaptive_state_doubles(p.width, p.height))
+    st_in = None
+    if state is not None:
+        st_in = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
+        if st_in.size != n_doubles:
+            raise ValueError("%s: a state of a %dx%d frame holds %d doubles, got %d" % (who, p.width, p.height, n_doubles, st_in.size))
+    return st_in, (np.zeros(n_doubles, dtype=np.float64) if want_state else None)
+
+
+def _rank_args(device_ids):
+    """(ngpu, device_ids, stats) as the node-wide entry points take them; None is the single form: ngpu 0, no ids, one Stats."""
+    n = 0 if device_ids is None else len(device_ids)
+    ids = None if device_ids is None else (C.c_int32 * max(n, 1))(*device_ids)
+    return n, ids, (Stats * max(n, 1))()
+
+
+def _denoise_params(iterations, sigma_luminance, sigma_normal, sigma_depth):
+    return abi.Denoise(iterations=iterations, reserved0=0, sigma_luminance=sigma_luminance, sigma_normal=sigma_normal, sigma_depth=sigma_depth)
+
+
+def _feature_arrays(features, h, w):
+    """`render_features`' dict as contiguous f64 arrays of an hxw frame."""
+    f = {k: np.ascontiguousarray(features[k], dtype=np.float64) for k in ("albedo", "normal", "depth", "alpha")}
+    assert f["albedo"].shape == (h, w, 3) and f["normal"].shape == (h, w, 3) and f["depth"].shape == (h, w) and f["alpha"].shape == (h, w)
+    return f
+
+
+def _mask_array(who, mask, h, w):
+    """`mask` as hxw bytes of 0 and 1, or None; a ValueError in the name of `who` for another shape."""
+    if mask is None:
+        return None
+    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    if m.shape != (h, w):
+        raise ValueError("%s: the mask must be (y1 - y0) x (x1 - x0) = %d x %d, got %s" % (who, h, w, m.shape))
+    return m
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
 def render_adaptive(scene, cam, params, pass_spp=64, rel_error=0.02, abs_error=0.0):
     """`rttnw_render_adaptive`: passes of `pass_spp` samples per pixel, a pixel stopping once its standard error is at most
     abs_error + rel_error * mean in every channel, or at `params.spp` samples (the cap, a multiple of pass_spp).  A `params.spp_chunk`
     of 0 is taken as max(1, pass_spp // 16) here, so that a pass of 16 k samples is exactly one job group of 16 chunks (64 -> 4).
     Returns (linear HxWx3 f64, rgba8 HxWx4 u8, spp_map HxW u32, stderr HxWx3 f64, Stats)."""
-    import copy
     b = library.product()
-    p = copy.copy(params)
-    if p.spp_chunk == 0:
-        p.spp_chunk = max(1, pass_spp // 16)
-    h, w = p.height, p.width
-    lin = np.zeros((h, w, 3), dtype=np.float64)
-    rgba = np.zeros((h, w, 4), dtype=np.uint8)
-    spp = np.zeros((h, w), dtype=np.uint32)
-    se = np.zeros((h, w, 3), dtype=np.float64)
+    p = _pass_params(params, pass_spp)
+    lin, rgba, spp, se = _frame_outputs(p.height, p.width)
     st = Stats()
     a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
     rc = b.render_adaptive(scene.handle, C.byref(cam), C.byref(p), C.byref(a), lin.ctypes.data, rgba.ctypes.data, spp.ctypes.data,
@@ -65,19 +118,10 @@ def render_adaptive(scene, cam, params, pass_spp=64, rel_error=0.02, abs_error=0
 def render_adaptive_multi(scene, cam, params, device_ids, pass_spp=64, rel_error=0.02, abs_error=0.0):
     """`rttnw_render_adaptive_multi`: `render_adaptive` over the GPUs (or logical ranks) of `device_ids`, bit-identical outputs; the same
     `spp_chunk` default.  Returns (linear HxWx3 f64, rgba8 HxWx4 u8, spp_map HxW u32, stderr HxWx3 f64, [Stats per rank])."""
-    import copy
     b = library.product()
-    p = copy.copy(params)
-    if p.spp_chunk == 0:
-        p.spp_chunk = max(1, pass_spp // 16)
-    h, w = p.height, p.width
-    lin = np.zeros((h, w, 3), dtype=np.float64)
-    rgba = np.zeros((h, w, 4), dtype=np.uint8)
-    spp = np.zeros((h, w), dtype=np.uint32)
-    se = np.zeros((h, w, 3), dtype=np.float64)
-    n = len(device_ids)
-    ids = (C.c_int32 * n)(*device_ids)
-    st = (Stats * n)()
+    p = _pass_params(params, pass_spp)
+    lin, rgba, spp, se = _frame_outputs(p.height, p.width)
+    n, ids, st = _rank_args(device_ids)
     a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
     rc = b.render_adaptive_multi(scene.handle, C.byref(cam), C.byref(p), C.byref(a), n, ids, lin.ctypes.data, rgba.ctypes.data,
                                  spp.ctypes.data, se.ctypes.data, C.cast(st, C.c_void_p))
@@ -90,30 +134,14 @@ def render_adaptive_resume(scene, cam, params, state=None, device_ids=None, pass
     earlier call returned, None for a fresh render — and continued under THIS call's tolerances and cap; the same `spp_chunk` default.  With a
     cap and tolerances no looser than the state's, the result is bit for bit the render that was never interrupted.
     Returns (linear HxWx3 f64, rgba8 HxWx4 u8, spp_map HxW u32, stderr HxWx3 f64, Stats or [Stats per rank], state or None)."""
-    import copy
     b = library.product()
-    p = copy.copy(params)
-    if p.spp_chunk == 0:
-        p.spp_chunk = max(1, pass_spp // 16)
-    h, w = p.height, p.width
-    lin = np.zeros((h, w, 3), dtype=np.float64)
-    rgba = np.zeros((h, w, 4), dtype=np.uint8)
-    spp = np.zeros((h, w), dtype=np.uint32)
-    se = np.zeros((h, w, 3), dtype=np.float64)
-    n_doubles = int(b.adaptive_state_doubles(w, h))
-    st_in = None
-    if state is not None:
-        st_in = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
-        if st_in.size != n_doubles:
-            raise ValueError("render_adaptive_resume: a state of a %dx%d frame holds %d doubles, got %d" % (w, h, n_doubles, st_in.size))
-    st_out = np.zeros(n_doubles, dtype=np.float64) if want_state else None
-    n = 0 if device_ids is None else len(device_ids)
-    ids = None if device_ids is None else (C.c_int32 * max(n, 1))(*device_ids)
-    st = (Stats * max(n, 1))()
+    p = _pass_params(params, pass_spp)
+    lin, rgba, spp, se = _frame_outputs(p.height, p.width)
+    st_in, st_out = _state_arrays(b, "render_adaptive_resume", p, state, want_state)
+    n, ids, st = _rank_args(device_ids)
     a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
-    rc = b.render_adaptive_resume(scene.handle, C.byref(cam), C.byref(p), C.byref(a), n, ids, None if st_in is None else st_in.ctypes.data,
-                                  None if st_out is None else st_out.ctypes.data, lin.ctypes.data, rgba.ctypes.data, spp.ctypes.data,
-                                  se.ctypes.data, C.cast(st, C.c_void_p))
+    rc = b.render_adaptive_resume(scene.handle, C.byref(cam), C.byref(p), C.byref(a), n, ids, _ptr(st_in), _ptr(st_out), lin.ctypes.data,
+                                  rgba.ctypes.data, spp.ctypes.data, se.ctypes.data, C.cast(st, C.c_void_p))
     check(rc, b, "rttnw_render_adaptive_resume")
     return lin, rgba, spp, se, (st[0] if device_ids is None else list(st)), st_out
 
@@ -126,35 +154,16 @@ def render_adaptive_region(scene, cam, params, x0, y0, x1, y1, mask=None, state=
     traced, each to the bits a fresh whole-frame adaptive render under this cap and these tolerances gives it; the others keep their records.
     The same `spp_chunk` default.  Returns (linear hxwx3 f64, rgba8 hxwx4 u8, spp_map hxw u32, stderr hxwx3 f64, Stats or [Stats per rank],
     state or None), h = y1 - y0, w = x1 - x0; a pixel of the window without samples is zero everywhere, alpha included."""
-    import copy
     b = library.product()
-    p = copy.copy(params)
-    if p.spp_chunk == 0:
-        p.spp_chunk = max(1, pass_spp // 16)
+    p = _pass_params(params, pass_spp)
     h, w = max(int(y1) - int(y0), 0), max(int(x1) - int(x0), 0)
-    m = None
-    if mask is not None:
-        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-        if m.shape != (h, w):
-            raise ValueError("render_adaptive_region: the mask must be (y1 - y0) x (x1 - x0) = %d x %d, got %s" % (h, w, m.shape))
-    lin = np.zeros((h, w, 3), dtype=np.float64)
-    rgba = np.zeros((h, w, 4), dtype=np.uint8)
-    spp = np.zeros((h, w), dtype=np.uint32)
-    se = np.zeros((h, w, 3), dtype=np.float64)
-    n_doubles = int(b.adaptive_state_doubles(p.width, p.height))
-    st_in = None
-    if state is not None:
-        st_in = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
-        if st_in.size != n_doubles:
-            raise ValueError("render_adaptive_region: a state of a %dx%d frame holds %d doubles, got %d" % (p.width, p.height, n_doubles, st_in.size))
-    st_out = np.zeros(n_doubles, dtype=np.float64) if want_state else None
-    n = 0 if device_ids is None else len(device_ids)
-    ids = None if device_ids is None else (C.c_int32 * max(n, 1))(*device_ids)
-    st = (Stats * max(n, 1))()
+    m = _mask_array("render_adaptive_region", mask, h, w)
+    lin, rgba, spp, se = _frame_outputs(h, w)
+    st_in, st_out = _state_arrays(b, "render_adaptive_region", p, state, want_state)
+    n, ids, st = _rank_args(device_ids)
     a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
-    rc = b.render_adaptive_region(scene.handle, C.byref(cam), C.byref(p), C.byref(a), x0, y0, x1, y1, None if m is None else m.ctypes.data, n, ids,
-                                  None if st_in is None else st_in.ctypes.data, None if st_out is None else st_out.ctypes.data, lin.ctypes.data,
-                                  rgba.ctypes.data, spp.ctypes.data, se.ctypes.data, C.cast(st, C.c_void_p))
+    rc = b.render_adaptive_region(scene.handle, C.byref(cam), C.byref(p), C.byref(a), x0, y0, x1, y1, _ptr(m), n, ids, _ptr(st_in), _ptr(st_out),
+                                  lin.ctypes.data, rgba.ctypes.data, spp.ctypes.data, se.ctypes.data, C.cast(st, C.c_void_p))
     check(rc, b, "rttnw_render_adaptive_region")
     return lin, rgba, spp, se, (st[0] if device_ids is None else list(st)), st_out
 
@@ -167,23 +176,18 @@ def render_adaptive_denoised(scene, cam, params, pass_spp=64, rel_error=0.02, ab
     default as `render_adaptive`.  Returns a dict: "linear" HxWx3 f64 and "rgba8" HxWx4 u8 (the denoised image), "spp" HxW u32, "stderr" HxWx3
     f64 (sqrt of the filtered variance), "raw_linear" and "raw_stderr" HxWx3 f64 (`render_adaptive`'s values), "state" (what
     `render_adaptive_resume` takes, or None), "rounds" (rounds run) and "stats"."""
-    import copy
     b = library.product()
-    p = copy.copy(params)
-    if p.spp_chunk == 0:
-        p.spp_chunk = max(1, pass_spp // 16)
+    p = _pass_params(params, pass_spp)
     h, w = p.height, p.width
     out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "spp": np.zeros((h, w), dtype=np.uint32),
            "stderr": np.zeros((h, w, 3)), "raw_linear": np.zeros((h, w, 3)), "raw_stderr": np.zeros((h, w, 3))}
-    state = np.zeros(int(b.adaptive_state_doubles(w, h)), dtype=np.float64) if want_state else None
+    _, state = _state_arrays(b, "render_adaptive_denoised", p, None, want_state)
     st = Stats()
     a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
-    g = abi.Guided(feature_spp=feature_spp, reserved0=0,
-                   denoise=abi.Denoise(iterations=iterations, reserved0=0, sigma_luminance=sigma_luminance, sigma_normal=sigma_normal,
-                                       sigma_depth=sigma_depth))
+    g = abi.Guided(feature_spp=feature_spp, reserved0=0, denoise=_denoise_params(iterations, sigma_luminance, sigma_normal, sigma_depth))
     rc = b.render_adaptive_denoised(scene.handle, C.byref(cam), C.byref(p), C.byref(a), C.byref(g), out["linear"].ctypes.data,
                                     out["rgba8"].ctypes.data, out["spp"].ctypes.data, out["stderr"].ctypes.data, out["raw_linear"].ctypes.data,
-                                    out["raw_stderr"].ctypes.data, None if state is None else state.ctypes.data, C.byref(st))
+                                    out["raw_stderr"].ctypes.data, _ptr(state), C.byref(st))
     check(rc, b, "rttnw_render_adaptive_denoised")
     out["state"] = state
     out["rounds"] = int(out["spp"].max()) // pass_spp  # (every round traces its active pixels: the pixel that went furthest took part in all)
@@ -211,16 +215,10 @@ def render_region(scene, cam, params, x0, y0, x1, y1, mask=None):
     0, 0, 0 with alpha 0.  Returns (linear hxwx3 f64, rgba8 hxwx4 u8, Stats), h = y1 - y0, w = x1 - x0."""
     b = library.product()
     h, w = max(int(y1) - int(y0), 0), max(int(x1) - int(x0), 0)
-    m = None
-    if mask is not None:
-        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-        if m.shape != (h, w):
-            raise ValueError("render_region: the mask must be (y1 - y0) x (x1 - x0) = %d x %d, got %s" % (h, w, m.shape))
-    lin = np.zeros((h, w, 3), dtype=np.float64)
-    rgba = np.zeros((h, w, 4), dtype=np.uint8)
+    m = _mask_array("render_region", mask, h, w)
+    lin, rgba, _, _ = _frame_outputs(h, w)
     st = Stats()
-    rc = b.render_region(scene.handle, C.byref(cam), C.byref(params), x0, y0, x1, y1, None if m is None else m.ctypes.data,
-                         lin.ctypes.data, rgba.ctypes.data, C.byref(st))
+    rc = b.render_region(scene.handle, C.byref(cam), C.byref(params), x0, y0, x1, y1, _ptr(m), lin.ctypes.data, rgba.ctypes.data, C.byref(st))
     check(rc, b, "rttnw_render_region")
     return lin, rgba, st
 
@@ -234,17 +232,15 @@ def denoise(linear, features, stderr=None, iterations=5, sigma_luminance=0.0, si
     lin = np.ascontiguousarray(linear, dtype=np.float64)
     h, w = lin.shape[:2]
     var = None if stderr is None else np.ascontiguousarray(np.square(np.asarray(stderr, dtype=np.float64)))
-    f = {k: np.ascontiguousarray(features[k], dtype=np.float64) for k in ("albedo", "normal", "depth", "alpha")}
-    assert f["albedo"].shape == (h, w, 3) and f["normal"].shape == (h, w, 3) and f["depth"].shape == (h, w) and f["alpha"].shape == (h, w)
+    f = _feature_arrays(features, h, w)
     assert var is None or var.shape == (h, w, 3)
     out = np.zeros((h, w, 3))
     rgba = np.zeros((h, w, 4), dtype=np.uint8)
     out_var = None if var is None else np.zeros((h, w, 3))
-    d = abi.Denoise(iterations=iterations, reserved0=0, sigma_luminance=sigma_luminance, sigma_normal=sigma_normal, sigma_depth=sigma_depth)
+    d = _denoise_params(iterations, sigma_luminance, sigma_normal, sigma_depth)
     ms = C.c_double(0.0)
-    rc = b.denoise(w, h, lin.ctypes.data, None if var is None else var.ctypes.data, f["albedo"].ctypes.data, f["normal"].ctypes.data,
-                   f["depth"].ctypes.data, f["alpha"].ctypes.data, C.byref(d), out.ctypes.data, rgba.ctypes.data,
-                   None if out_var is None else out_var.ctypes.data, C.byref(ms))
+    rc = b.denoise(w, h, lin.ctypes.data, _ptr(var), f["albedo"].ctypes.data, f["normal"].ctypes.data, f["depth"].ctypes.data,
+                   f["alpha"].ctypes.data, C.byref(d), out.ctypes.data, rgba.ctypes.data, _ptr(out_var), C.byref(ms))
     check(rc, b, "rttnw_denoise")
     return (out, rgba, out_var, ms.value) if want_ms else (out, rgba, out_var)
 
@@ -268,19 +264,17 @@ def reconstruct(linear, valid, features, stderr=None, iterations=5, sigma_lumina
     h, w = lin.shape[:2]
     ok = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
     var = None if stderr is None else np.ascontiguousarray(np.square(np.asarray(stderr, dtype=np.float64)))
-    f = {k: np.ascontiguousarray(features[k], dtype=np.float64) for k in ("albedo", "normal", "depth", "alpha")}
     assert lin.shape == (h, w, 3) and ok.shape == (h, w)
-    assert f["albedo"].shape == (h, w, 3) and f["normal"].shape == (h, w, 3) and f["depth"].shape == (h, w) and f["alpha"].shape == (h, w)
+    f = _feature_arrays(features, h, w)
     assert var is None or var.shape == (h, w, 3)
     out = np.zeros((h, w, 3))
     rgba = np.zeros((h, w, 4), dtype=np.uint8)
     out_var = None if var is None else np.zeros((h, w, 3))
     out_ok = np.zeros((h, w), dtype=np.uint8)
-    d = abi.Denoise(iterations=iterations, reserved0=0, sigma_luminance=sigma_luminance, sigma_normal=sigma_normal, sigma_depth=sigma_depth)
+    d = _denoise_params(iterations, sigma_luminance, sigma_normal, sigma_depth)
     ms = C.c_double(0.0)
-    rc = b.reconstruct(w, h, lin.ctypes.data, None if var is None else var.ctypes.data, ok.ctypes.data, f["albedo"].ctypes.data,
-                       f["normal"].ctypes.data, f["depth"].ctypes.data, f["alpha"].ctypes.data, C.byref(d), out.ctypes.data, rgba.ctypes.data,
-                       None if out_var is None else out_var.ctypes.data, out_ok.ctypes.data, C.byref(ms))
+    rc = b.reconstruct(w, h, lin.ctypes.data, _ptr(var), ok.ctypes.data, f["albedo"].ctypes.data, f["normal"].ctypes.data, f["depth"].ctypes.data,
+                       f["alpha"].ctypes.data, C.byref(d), out.ctypes.data, rgba.ctypes.data, _ptr(out_var), out_ok.ctypes.data, C.byref(ms))
     check(rc, b, "rttnw_reconstruct")
     return (out, rgba, out_var, out_ok, ms.value) if want_ms else (out, rgba, out_var, out_ok)
 
@@ -292,23 +286,18 @@ def render_preview(scene, cam, params, level, pass_spp=64, rel_error=0.02, abs_e
     `render_adaptive`.  Returns a dict: "linear" HxWx3 f64 and "rgba8" HxWx4 u8 (the reconstructed image), "valid" HxW u8, "spp" HxW u32 (0 off
     the lattice), "raw_linear" and "raw_stderr" HxWx3 f64 (the lattice's own values), "state" (the frame-sized adaptive state with zero records
     off the lattice — `render_adaptive_region(..., 0, 0, W, H, state=...)` completes it — or None) and "stats"."""
-    import copy
     b = library.product()
-    p = copy.copy(params)
-    if p.spp_chunk == 0:
-        p.spp_chunk = max(1, pass_spp // 16)
+    p = _pass_params(params, pass_spp)
     h, w = p.height, p.width
     out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "valid": np.zeros((h, w), dtype=np.uint8),
            "spp": np.zeros((h, w), dtype=np.uint32), "raw_linear": np.zeros((h, w, 3)), "raw_stderr": np.zeros((h, w, 3))}
-    state = np.zeros(int(b.adaptive_state_doubles(w, h)), dtype=np.float64) if want_state else None
+    _, state = _state_arrays(b, "render_preview", p, None, want_state)
     st = Stats()
     a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
-    v = abi.Preview(level=level, feature_spp=feature_spp,
-                    denoise=abi.Denoise(iterations=iterations, reserved0=0, sigma_luminance=sigma_luminance, sigma_normal=sigma_normal,
-                                        sigma_depth=sigma_depth))
+    v = abi.Preview(level=level, feature_spp=feature_spp, denoise=_denoise_params(iterations, sigma_luminance, sigma_normal, sigma_depth))
     rc = b.render_preview(scene.handle, C.byref(cam), C.byref(p), C.byref(a), C.byref(v), out["linear"].ctypes.data, out["rgba8"].ctypes.data,
                           out["valid"].ctypes.data, out["spp"].ctypes.data, out["raw_linear"].ctypes.data, out["raw_stderr"].ctypes.data,
-                          None if state is None else state.ctypes.data, C.byref(st))
+                          _ptr(state), C.byref(st))
     check(rc, b, "rttnw_render_preview")
     out["state"] = state
     out["stats"] = st
@@ -341,29 +330,15 @@ def render_adaptive_budget(scene, cam, params, samples, round_pixels=0, state=No
     worst under the tolerances and `params.spp` (the cap).  `state` is the frame-sized array an adaptive call returned (a pixel never sampled is a
     record of zeros); None stands for all zeros.  The same `spp_chunk` default as `render_adaptive`.  Returns (linear HxWx3 f64, rgba8 HxWx4 u8,
     spp_map HxW u32, stderr HxWx3 f64, Stats, state or None, rounds run); a pixel without samples is zero everywhere, alpha included."""
-    import copy
     b = library.product()
-    p = copy.copy(params)
-    if p.spp_chunk == 0:
-        p.spp_chunk = max(1, pass_spp // 16)
-    h, w = p.height, p.width
-    lin = np.zeros((h, w, 3), dtype=np.float64)
-    rgba = np.zeros((h, w, 4), dtype=np.uint8)
-    spp = np.zeros((h, w), dtype=np.uint32)
-    se = np.zeros((h, w, 3), dtype=np.float64)
-    n_doubles = int(b.adaptive_state_doubles(w, h))
-    st_in = None
-    if state is not None:
-        st_in = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
-        if st_in.size != n_doubles:
-            raise ValueError("render_adaptive_budget: a state of a %dx%d frame holds %d doubles, got %d" % (w, h, n_doubles, st_in.size))
-    st_out = np.zeros(n_doubles, dtype=np.float64) if want_state else None
+    p = _pass_params(params, pass_spp)
+    lin, rgba, spp, se = _frame_outputs(p.height, p.width)
+    st_in, st_out = _state_arrays(b, "render_adaptive_budget", p, state, want_state)
     st = Stats()
     a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
     bg = abi.Budget(samples=int(samples), round_pixels=int(round_pixels), reserved0=0)
-    rc = b.render_adaptive_budget(scene.handle, C.byref(cam), C.byref(p), C.byref(a), C.byref(bg), None if st_in is None else st_in.ctypes.data,
-                                  None if st_out is None else st_out.ctypes.data, lin.ctypes.data, rgba.ctypes.data, spp.ctypes.data,
-                                  se.ctypes.data, C.byref(st))
+    rc = b.render_adaptive_budget(scene.handle, C.byref(cam), C.byref(p), C.byref(a), C.byref(bg), _ptr(st_in), _ptr(st_out), lin.ctypes.data,
+                                  rgba.ctypes.data, spp.ctypes.data, se.ctypes.data, C.byref(st))
     check(rc, b, "rttnw_render_adaptive_budget")
     return lin, rgba, spp, se, st, st_out, st.reserved >> 16
 

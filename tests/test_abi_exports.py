@@ -6,15 +6,13 @@ import re
 
 import pytest
 
+from abi_cases import ROOT, strip_c_comments
 from rttnw_amd import abi, library
 from rttnw_amd import scene as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 def declared(header, prefix):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = strip_c_comments(open(os.path.join(ROOT, "include", header)).read())
     return sorted(set(re.findall(r"\b(%s\w+)\s*\((?!\*)" % prefix, text)))
 
 

@@ -10,12 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_cases import FFI, HEADER, ROOT, adaptive, camera, exported, params
 from rttnw_amd import abi, library
 from rttnw_amd import scene as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rttnw_hip.h")).read(), flags=re.S)
-FFI = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")).read())
 
 
 class AdaptivePixel(C.Structure):
@@ -54,16 +51,13 @@ def test_struct_and_entry_point_are_declared_alike_everywhere():
     assert len(sig.split(",")) == 9
     rs_sig = re.search(r"pub fn rttnw_render_adaptive\((.*?)\) -> c_int;", FFI, flags=re.S).group(1)
     assert "a: *const rttnw_adaptive" in rs_sig and "out_spp: *mut u32" in rs_sig and "out_stderr_rgb: *mut f64" in rs_sig
-    assert "rttnw_render_adaptive" in abi.exported_symbols()
-    assert hasattr(C.CDLL(library.HIP_LIB), "rttnw_render_adaptive")
-    # the ABI version stays: the symbol is how a caller finds the feature
-    assert re.search(r"#define RTTNW_ABI_VERSION 3\b", HEADER)
+    exported("render_adaptive")
 
 
 # ---------------------------------------------------------------------------------------------- refusals
 
 def _call(b, sc, p, a):
-    cam = S.camera_desc((0, 0, 5), (0, 0, 0), 40.0, 1.0)
+    cam = camera()
     return b.render_adaptive(sc.handle, C.byref(cam), C.byref(p), C.byref(a) if a is not None else None,
                              None, None, None, None, None)
 
@@ -81,10 +75,7 @@ def _call(b, sc, p, a):
 def test_refusals_come_before_the_device(what, kw, adapt, code, msg):
     b = library.product()
     sc = S.Scene(b)                                   # never committed: a device would be needed for that
-    p = S.make_params(16, 16, kw.pop("spp", 128), **kw)
-    a = abi.Adaptive(pass_spp=64, reserved0=0, rel_error=0.05, abs_error=0.0)
-    for k, v in adapt.items():
-        setattr(a, k, v)
+    p, a = params(**kw), adaptive(**adapt)
     assert _call(b, sc, p, a) == code, what
     assert msg in b.last_error().decode(), (what, b.last_error())
 
@@ -92,9 +83,9 @@ def test_refusals_come_before_the_device(what, kw, adapt, code, msg):
 def test_valid_arguments_reach_the_scene_checks():
     b = library.product()
     sc = S.Scene(b)
-    p = S.make_params(16, 16, 128)
+    p = params()
     assert _call(b, sc, p, None) == abi.RTTNW_OK - 1          # NULL rule
-    a = abi.Adaptive(pass_spp=64, reserved0=0, rel_error=0.05, abs_error=0.0)
+    a = adaptive()
     assert _call(b, sc, p, a) == -2                           # RTTNW_ERR_STATE: the scene is not committed
     assert "not committed" in b.last_error().decode()
 

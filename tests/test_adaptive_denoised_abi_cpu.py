@@ -4,21 +4,15 @@ that was never committed, and on no scene at all — in the order the header sta
 the command line refuses --guided where it means nothing, before any scene is built.  (tests/test_gpu_adaptive_denoised.py has what a
 committed scene computes.)"""
 import ctypes as C
-import os
 import re
-import subprocess
-import sys
 
 import pytest
 
+from abi_cases import FFI, HEADER, HEADER_TEXT, INVALID, RUST_SCENE, STATE, UNSUPPORTED, camera, cli_refuses, declared_alike, exported, refused
+from abi_cases import adaptive as _adaptive, params as _params
 from rttnw_amd import abi, library
 from rttnw_amd import scene as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER_TEXT = open(os.path.join(ROOT, "include", "rttnw_hip.h")).read()
-HEADER = re.sub(r"/\*.*?\*/", "", HEADER_TEXT, flags=re.S)
-FFI = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")).read())
-INVALID, STATE, UNSUPPORTED = -1, -2, -3
 NAME = "render_adaptive_denoised"
 
 # the argument list, once: (name, C type, Rust type, ctypes type)
@@ -35,24 +29,10 @@ ARGS = [("s", "rttnw_scene*", "*mut rttnw_scene", abi.scene_p),
 
 
 def test_export_and_declarations():
-    lib = C.CDLL(library.HIP_LIB)
-    assert hasattr(lib, "rttnw_" + NAME) and "rttnw_" + NAME in abi.exported_symbols()
-    m = re.search(r"\bint rttnw_%s\((.*?)\);" % NAME, HEADER, flags=re.S)
-    assert m, "include/rttnw_hip.h does not declare rttnw_%s" % NAME
-    c_args = []
-    for a in " ".join(m.group(1).split()).split(","):
-        ctype, arg = re.match(r"(.+?)\s*(\w+)$", a.strip()).groups()
-        c_args.append((arg, ctype.replace(" *", "*")))
-    assert c_args == [(n, c) for n, c, _, _ in ARGS]
-    m = re.search(r"pub fn rttnw_%s\((.*?)\)\s*->\s*c_int;" % NAME, FFI, flags=re.S)
-    assert m, "bindings/rust/src/ffi.rs does not declare rttnw_%s" % NAME
-    assert [tuple(x.strip() for x in a.split(":", 1)) for a in m.group(1).split(",") if ":" in a] == [(n, r) for n, _, r, _ in ARGS]
-    proto = {n: (res, a) for n, res, a in abi.PRODUCT_FUNCS}[NAME]
-    assert proto[0] is C.c_int and list(proto[1]) == [t for _, _, _, t in ARGS]
-    assert re.search(r"#define RTTNW_ABI_VERSION 3\b", HEADER)      # no version bump: the symbol is how a caller finds the feature
-    assert lib.rttnw_abi_version() == 3 and abi.ABI_VERSION == 3
+    exported(NAME)
+    declared_alike(NAME, ARGS)
     assert "rttnw_" + NAME in HEADER_TEXT.split("typedef struct rttnw_scene")[0], "the comment at RTTNW_ABI_VERSION says how a caller detects the function"
-    assert "pub fn %s(" % NAME in open(os.path.join(ROOT, "bindings", "rust", "src", "scene.rs")).read(), "the crate's safe wrapper"
+    assert "pub fn %s(" % NAME in RUST_SCENE, "the crate's safe wrapper"
     contract = HEADER_TEXT.split("struct rttnw_guided {")[0].split("int rttnw_render_adaptive_region(", 1)[1]
     assert "NOT promised" in contract, "the header says that a stopped pixel's decision depended on its neighbours"
     assert "Out of scope: a node-wide form" in contract and "state_in" in contract and "windows" in contract
@@ -77,24 +57,6 @@ def test_guided_layout_agrees_in_header_ctypes_and_rust():
     assert [n for n, _ in re.findall(r"pub (\w+)\s*:\s*(\w+),", rs_d)] == [f[0] for f in abi.Denoise._fields_]
 
 
-W, H = 16, 16
-CAM = dict(lookfrom=(0, 0, 5), lookat=(0, 0, 0), vfov=40.0, aspect=1.0)
-
-
-def _params(**kw):
-    p = S.make_params(kw.pop("width", W), kw.pop("height", H), kw.pop("spp", 128))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def _adaptive(**kw):
-    a = abi.Adaptive(pass_spp=64, reserved0=0, rel_error=0.05, abs_error=0.0)
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
-
-
 def _guided(**kw):
     g = abi.Guided(feature_spp=0, reserved0=0, denoise=abi.Denoise(iterations=5, reserved0=0, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0))
     for k, v in kw.items():
@@ -106,7 +68,7 @@ def _guided(**kw):
 
 
 def _call(b, sc, p, a, g, scene=True):
-    cam = S.camera_desc(**CAM)
+    cam = camera()
     return b.render_adaptive_denoised(sc.handle if scene else None, C.byref(cam), C.byref(p) if p is not None else None,
                                       C.byref(a) if a is not None else None, C.byref(g) if g is not None else None, None, None, None, None, None, None,
                                       None, None)
@@ -144,16 +106,7 @@ def test_refusals_come_before_the_device(what, kw, adapt, guide, code, msg):
     p = None if kw is None else _params(**kw)
     a = None if adapt is None else _adaptive(**adapt)
     g = None if guide is None else _guided(**guide)
-    if code is None:
-        # validate() looks at the scene before the sizes: "not committed" on a scene, "NULL" without one — in either case before any device
-        assert _call(b, sc, p, a, g) == STATE and "not committed" in b.last_error().decode(), what
-        assert _call(b, sc, p, a, g, scene=False) == INVALID and "NULL" in b.last_error().decode(), what
-        return
-    assert _call(b, sc, p, a, g) == code, what
-    err = b.last_error().decode()
-    assert err and msg in err and NAME in err, (what, err)
-    assert _call(b, sc, p, a, g, scene=False) == code, what      # ... nor any scene at all
-    assert msg in b.last_error().decode(), what
+    refused(b, lambda scene: _call(b, sc, p, a, g, scene=scene), code, msg, NAME)
 
 
 def test_valid_arguments_reach_validate():
@@ -204,9 +157,4 @@ def test_refusals_come_in_the_stated_order():
     (["7", "--noise", "0.1", "--guided", "--denoise-iterations", "9"], "--denoise-iterations must be 0 .. 8"),
 ])
 def test_cli_refuses_before_any_scene_is_built(argv, msg, tmp_path):
-    out = tmp_path / "image.png"
-    r = subprocess.run([sys.executable, "-m", "rttnw_amd"] + argv + ["--out", str(out)], cwd=tmp_path, capture_output=True, text=True,
-                       env=dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", "")))
-    assert r.returncode == 1
-    assert msg in r.stderr, r.stderr
-    assert "Scene number" not in r.stdout and not out.exists() and not (tmp_path / "state.npy").exists()
+    cli_refuses(argv, msg, tmp_path, must_not_exist=("state.npy",))

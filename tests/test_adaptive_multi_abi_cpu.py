@@ -3,20 +3,15 @@ every argument refusal comes before the device is touched and in the order the h
 --devices and its combinations before any scene is built.  (The fourth refusal, a device id outside [0, rttnw_device_count()), stands behind
 validate() and so behind "scene is not committed": tests/test_gpu_adaptive_multi.py has it, on a committed scene.)"""
 import ctypes as C
-import os
-import re
-import subprocess
-import sys
 
 import pytest
 
+from abi_cases import HEADER_TEXT, INVALID, RUST_SCENE, STATE, UNSUPPORTED, camera, cli_refuses, declared_alike, exported, refused
+from abi_cases import adaptive as _adaptive, params as _params
 from rttnw_amd import abi, library
 from rttnw_amd import scene as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rttnw_hip.h")).read(), flags=re.S)
-FFI = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")).read())
-INVALID, STATE, UNSUPPORTED = -1, -2, -3
+NAME = "render_adaptive_multi"
 
 # the argument list, once: (name, C type, Rust type, ctypes type)
 ARGS = [("s", "rttnw_scene*", "*mut rttnw_scene", abi.scene_p),
@@ -31,45 +26,14 @@ ARGS = [("s", "rttnw_scene*", "*mut rttnw_scene", abi.scene_p),
 
 
 def test_export_and_declarations():
-    lib = C.CDLL(library.HIP_LIB)
-    assert hasattr(lib, "rttnw_render_adaptive_multi")
-    assert "rttnw_render_adaptive_multi" in abi.exported_symbols()
-    m = re.search(r"\bint rttnw_render_adaptive_multi\((.*?)\);", HEADER, flags=re.S)
-    assert m, "include/rttnw_hip.h does not declare rttnw_render_adaptive_multi"
-    c_args = []
-    for a in " ".join(m.group(1).split()).split(","):
-        ctype, name = re.match(r"(.+?)\s*(\w+)$", a.strip()).groups()
-        c_args.append((name, ctype.replace(" *", "*")))
-    assert c_args == [(n, c) for n, c, _, _ in ARGS]
-    m = re.search(r"pub fn rttnw_render_adaptive_multi\((.*?)\)\s*->\s*c_int;", FFI, flags=re.S)
-    assert m, "bindings/rust/src/ffi.rs does not declare rttnw_render_adaptive_multi"
-    rs_args = [tuple(x.strip() for x in a.split(":", 1)) for a in m.group(1).split(",") if ":" in a]
-    assert rs_args == [(n, r) for n, _, r, _ in ARGS]
-    proto = {n: (res, args) for n, res, args in abi.PRODUCT_FUNCS}["render_adaptive_multi"]
-    assert proto[0] is C.c_int and list(proto[1]) == [t for _, _, _, t in ARGS]
-    assert re.search(r"#define RTTNW_ABI_VERSION 3\b", HEADER)      # no version bump: the symbol is how a caller finds the feature
-    assert lib.rttnw_abi_version() == 3
-    assert "rttnw_render_adaptive_multi" in open(os.path.join(ROOT, "include", "rttnw_hip.h")).read().split("typedef struct rttnw_scene")[0], \
-        "the comment at RTTNW_ABI_VERSION says how a caller detects the function"
-    assert "render_adaptive_multi" in open(os.path.join(ROOT, "bindings", "rust", "src", "scene.rs")).read(), "the crate's safe wrapper"
-
-
-def _params(**kw):
-    p = S.make_params(16, 16, kw.pop("spp", 128))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def _adaptive(**kw):
-    a = abi.Adaptive(pass_spp=64, reserved0=0, rel_error=0.05, abs_error=0.0)
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
+    exported(NAME)
+    declared_alike(NAME, ARGS)
+    assert "rttnw_" + NAME in HEADER_TEXT.split("typedef struct rttnw_scene")[0], "the comment at RTTNW_ABI_VERSION says how a caller detects the function"
+    assert NAME in RUST_SCENE, "the crate's safe wrapper"
 
 
 def _call(b, sc, p, a, ngpu=2, ids=(0, 0), scene=True):
-    cam = S.camera_desc((0, 0, 5), (0, 0, 0), 40.0, 1.0)
+    cam = camera()
     dev = None if ids is None else (C.c_int32 * max(len(ids), 1))(*ids)
     return b.render_adaptive_multi(sc.handle if scene else None, C.byref(cam), C.byref(p) if p is not None else None,
                                    C.byref(a) if a is not None else None, ngpu, dev, None, None, None, None, None)
@@ -100,16 +64,7 @@ def test_refusals_come_before_the_device(what, kw, adapt, call, code, msg):
     sc = S.Scene(b)                                   # never committed: a device would be needed for that
     p = None if kw is None else _params(**kw)
     a = None if adapt is None else _adaptive(**adapt)
-    if code is None:
-        # validate() looks at the scene before the sizes: "not committed" on a scene, "NULL" without one — in either case before any device
-        assert _call(b, sc, p, a, **call) == STATE and "not committed" in b.last_error().decode(), what
-        assert _call(b, sc, p, a, scene=False, **call) == INVALID and "NULL" in b.last_error().decode(), what
-        return
-    assert _call(b, sc, p, a, **call) == code, what
-    err = b.last_error().decode()
-    assert err and msg in err and "render_adaptive_multi" in err, (what, err)
-    assert _call(b, sc, p, a, scene=False, **call) == code, what      # ... nor any scene at all
-    assert msg in b.last_error().decode(), what
+    refused(b, lambda scene: _call(b, sc, p, a, scene=scene, **call), code, msg, NAME)
 
 
 def test_tile_rank_and_tile_world_are_ignored():
@@ -159,8 +114,4 @@ def test_refusals_come_in_the_stated_order():
     (["7", "--devices", "0,0", "--noise", "0.05", "--denoise"], "--devices does not combine with --denoise"),
 ])
 def test_cli_refuses_before_any_scene_is_built(argv, msg, tmp_path):
-    out = tmp_path / "image.png"
-    r = subprocess.run([sys.executable, "-m", "rttnw_amd"] + argv + ["--out", str(out)], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode != 0
-    assert msg in r.stderr, r.stderr
-    assert "Scene number" not in r.stdout and not out.exists()
+    cli_refuses(argv, msg, tmp_path)

@@ -5,24 +5,14 @@ had; and the command line refuses --refine where it means nothing, before any sc
 [0, rttnw_device_count()), stands behind validate() and so behind "scene is not committed": tests/test_gpu_adaptive_region.py has the refusals
 of a committed scene.)"""
 import ctypes as C
-import os
-import re
-import struct
-import subprocess
-import sys
 
-import numpy as np
 import pytest
 
+from abi_cases import HEADER_TEXT, INVALID, RUST_SCENE, STATE, UNSUPPORTED, camera, cli_refuses, declared_alike, exported, refused
+from abi_cases import adaptive as _adaptive, break_state as _break, hand_made_state as _state, params as _params
 from rttnw_amd import abi, library
 from rttnw_amd import scene as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER_TEXT = open(os.path.join(ROOT, "include", "rttnw_hip.h")).read()
-HEADER = re.sub(r"/\*.*?\*/", "", HEADER_TEXT, flags=re.S)
-FFI = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")).read())
-INVALID, STATE, UNSUPPORTED = -1, -2, -3
-MAGIC, VERSION = 1381256791, 1
 NAME = "render_adaptive_region"
 
 # the argument list, once: (name, C type, Rust type, ctypes type)
@@ -41,69 +31,20 @@ ARGS = [("s", "rttnw_scene*", "*mut rttnw_scene", abi.scene_p),
         ("stats", "rttnw_stats*", "*mut rttnw_stats", C.c_void_p)]
 
 
-def _declared_alike(name, args, c_ret, rs_ret, ct_ret):
-    m = re.search(r"\b%s rttnw_%s\((.*?)\);" % (c_ret, name), HEADER, flags=re.S)
-    assert m, "include/rttnw_hip.h does not declare rttnw_%s" % name
-    c_args = []
-    for a in " ".join(m.group(1).split()).split(","):
-        ctype, arg = re.match(r"(.+?)\s*(\w+)$", a.strip()).groups()
-        c_args.append((arg, ctype.replace(" *", "*")))
-    assert c_args == [(n, c) for n, c, _, _ in args]
-    m = re.search(r"pub fn rttnw_%s\((.*?)\)\s*->\s*%s;" % (name, rs_ret), FFI, flags=re.S)
-    assert m, "bindings/rust/src/ffi.rs does not declare rttnw_%s" % name
-    rs_args = [tuple(x.strip() for x in a.split(":", 1)) for a in m.group(1).split(",") if ":" in a]
-    assert rs_args == [(n, r) for n, _, r, _ in args]
-    proto = {n: (res, a) for n, res, a in abi.PRODUCT_FUNCS}[name]
-    assert proto[0] is ct_ret and list(proto[1]) == [t for _, _, _, t in args]
-
-
 def test_export_and_declarations():
-    lib = C.CDLL(library.HIP_LIB)
-    assert hasattr(lib, "rttnw_" + NAME) and "rttnw_" + NAME in abi.exported_symbols()
-    _declared_alike(NAME, ARGS, "int", "c_int", C.c_int)
-    assert re.search(r"#define RTTNW_ABI_VERSION 3\b", HEADER)      # no version bump: the symbol is how a caller finds the feature
-    assert lib.rttnw_abi_version() == 3 and abi.ABI_VERSION == 3
+    exported(NAME)
+    declared_alike(NAME, ARGS)
     assert "rttnw_" + NAME in HEADER_TEXT.split("typedef struct rttnw_scene")[0], "the comment at RTTNW_ABI_VERSION says how a caller detects the function"
-    assert "pub fn %s(" % NAME in open(os.path.join(ROOT, "bindings", "rust", "src", "scene.rs")).read(), "the crate's safe wrapper"
+    assert "pub fn %s(" % NAME in RUST_SCENE, "the crate's safe wrapper"
     assert "A window-sized state is out of scope" in HEADER_TEXT, "the header says what scales with the frame"
 
 
 W, H = 16, 16
-CAM = dict(lookfrom=(0, 0, 5), lookat=(0, 0, 0), vfov=40.0, aspect=1.0)
 WIN = (3, 5, 12, 11)
 
 
-def _params(**kw):
-    p = S.make_params(kw.pop("width", W), kw.pop("height", H), kw.pop("spp", 128))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def _adaptive(**kw):
-    a = abi.Adaptive(pass_spp=64, reserved0=0, rel_error=0.05, abs_error=0.0)
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
-
-
-def _state(p, a, cam, n=None, k=None):
-    """A valid state made by hand: the header from the call's own arguments, every record n = B and k = the chunks of one pass (spp_chunk 4 of
-    B 64: 16) unless given — n = k = 0 makes every record empty."""
-    st = np.zeros(64 + 12 * p.width * p.height)
-    st[0:12] = [MAGIC, VERSION, p.width, p.height, a.pass_spp, p.spp_chunk, p.sample_begin, p.precision, p.max_depth, p.quirks,
-                p.seed & 0xFFFFFFFF, p.seed >> 32]
-    st[12] = p.t_min
-    st[13:16] = list(p.background)
-    st[16:31] = struct.unpack("15d", bytes(cam))
-    rec = st[64:].reshape(-1, 12)
-    rec[:, 3] = a.pass_spp if n is None else n
-    rec[:, 7] = -(-a.pass_spp // p.spp_chunk) if k is None else k
-    return st
-
-
 def _call(b, sc, p, a, win=WIN, ngpu=2, ids=(0, 0), scene=True, state=None, cam=None, resume=False):
-    cam = S.camera_desc(**CAM) if cam is None else cam
+    cam = camera() if cam is None else cam
     dev = None if ids is None else (C.c_int32 * max(len(ids), 1))(*ids)
     head = (sc.handle if scene else None, C.byref(cam), C.byref(p) if p is not None else None, C.byref(a) if a is not None else None)
     tail = (ngpu, dev, None if state is None else state.ctypes.data, None, None, None, None, None, None)
@@ -143,16 +84,7 @@ def test_refusals_come_before_the_device(what, kw, adapt, call, code, msg):
     sc = S.Scene(b)                                   # never committed: a device would be needed for that
     p = None if kw is None else _params(**kw)
     a = None if adapt is None else _adaptive(**adapt)
-    if code is None:
-        # validate() looks at the scene before the sizes: "not committed" on a scene, "NULL" without one — in either case before any device
-        assert _call(b, sc, p, a, **call) == STATE and "not committed" in b.last_error().decode(), what
-        assert _call(b, sc, p, a, scene=False, **call) == INVALID and "NULL" in b.last_error().decode(), what
-        return
-    assert _call(b, sc, p, a, **call) == code, what
-    err = b.last_error().decode()
-    assert err and msg in err and NAME in err, (what, err)
-    assert _call(b, sc, p, a, scene=False, **call) == code, what      # ... nor any scene at all
-    assert msg in b.last_error().decode(), what
+    refused(b, lambda scene: _call(b, sc, p, a, scene=scene, **call), code, msg, NAME)
 
 
 def test_tile_fields_are_ignored_with_ranks_and_the_single_form_reaches_validate():
@@ -162,17 +94,6 @@ def test_tile_fields_are_ignored_with_ranks_and_the_single_form_reaches_validate
     assert _call(b, sc, _params(), _adaptive(), ngpu=0, ids=None) == STATE and "not committed" in b.last_error().decode()
     assert _call(b, sc, _params(), _adaptive(), ngpu=64, ids=(0,) * 64) == STATE
     assert _call(b, sc, _params(), _adaptive(), win=(0, 0, W, H)) == STATE     # the whole frame is a window
-
-
-def _break(st, what):
-    st = st.copy()
-    rec = st[64:].reshape(-1, 12)
-    if isinstance(what, int):
-        st[what] = st[what] + 1.0 if st[what] == st[what] else 0.0
-    else:
-        field, value = what
-        rec[5, {"sum": 0, "n": 3, "mu": 5, "k": 7, "m2": 10, "pad": 11}[field]] = value
-    return st
 
 
 # 5. the state: (what is broken, header index or (record field, value), the word the message must hold)
@@ -190,7 +111,7 @@ STATE_BREAKS = [("magic", 0, "magic"), ("version", 1, "version"), ("width", 2, "
 def test_a_broken_state_is_refused_before_the_scene_is_looked_at(name, what, msg):
     b = library.product()
     sc = S.Scene(b)
-    p, a, cam = _params(spp_chunk=4), _adaptive(), S.camera_desc(**CAM)
+    p, a, cam = _params(spp_chunk=4), _adaptive(), camera()
     st = _break(_state(p, a, cam), what)
     for scene in (True, False):
         assert _call(b, sc, p, a, state=st, scene=scene) == INVALID, name
@@ -203,7 +124,7 @@ def test_empty_records_are_accepted_here_and_only_here():
     nonzero — a sum, a mean, a k, an M2, the pad — is refused; and rttnw_render_adaptive_resume refuses the all-zero state as it always did."""
     b = library.product()
     sc = S.Scene(b)
-    p, a, cam = _params(spp_chunk=4), _adaptive(), S.camera_desc(**CAM)
+    p, a, cam = _params(spp_chunk=4), _adaptive(), camera()
     empty = _state(p, a, cam, n=0, k=0)
     assert not empty[64:].any()
     for call in ({}, {"ngpu": 0, "ids": None}):
@@ -228,7 +149,7 @@ def test_refusals_come_in_the_stated_order():
     b = library.product()
     sc = S.Scene(b)
     err = lambda: b.last_error().decode()
-    p, a, cam = _params(spp_chunk=4), _adaptive(), S.camera_desc(**CAM)
+    p, a, cam = _params(spp_chunk=4), _adaptive(), camera()
     good = _state(p, a, cam)
     bad = _break(good, 0)
     off = (3, 5, W + 1, 11)
@@ -274,9 +195,4 @@ def test_refusals_come_in_the_stated_order():
     (["7", "--noise", "0.1", "--refine", "8,0,8,8", "--save-state", "state.npy"], "--refine wants X0,Y0,X1,Y1"),
 ])
 def test_cli_refuses_before_any_scene_is_built(argv, msg, tmp_path):
-    out = tmp_path / "image.png"
-    r = subprocess.run([sys.executable, "-m", "rttnw_amd"] + argv + ["--out", str(out)], cwd=tmp_path, capture_output=True, text=True,
-                       env=dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", "")))
-    assert r.returncode == 1
-    assert msg in r.stderr, r.stderr
-    assert "Scene number" not in r.stdout and not out.exists() and not (tmp_path / "state.npy").exists() and not (tmp_path / "f_albedo.png").exists()
+    cli_refuses(argv, msg, tmp_path, must_not_exist=("state.npy", "f_albedo.png"))

@@ -4,24 +4,16 @@ touched and in the order the header states; and the command line refuses --resum
 built.  (The sixth refusal, a device id outside [0, rttnw_device_count()), stands behind validate() and so behind "scene is not committed":
 tests/test_gpu_adaptive_resume.py has the refusals of a committed scene.)"""
 import ctypes as C
-import os
 import re
-import struct
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from abi_cases import (CAM, HEADER, HEADER_TEXT, INVALID, MAGIC, RUST_SCENE, STATE, STATE_HEADER_DOUBLES, STATE_RECORD_DOUBLES, UNSUPPORTED, VERSION,
+                       chunks_of_a_pass, cli_refuses, declared_alike, exported, refused)
+from abi_cases import adaptive as _adaptive, break_state as _break, hand_made_state as _state, params as _params
 from rttnw_amd import abi, library
 from rttnw_amd import scene as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER_TEXT = open(os.path.join(ROOT, "include", "rttnw_hip.h")).read()
-HEADER = re.sub(r"/\*.*?\*/", "", HEADER_TEXT, flags=re.S)
-FFI = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")).read())
-INVALID, STATE, UNSUPPORTED = -1, -2, -3
-MAGIC, VERSION, HEADER_DOUBLES, RECORD_DOUBLES = 1381256791, 1, 64, 12
 
 # the argument list, once: (name, C type, Rust type, ctypes type)
 ARGS = [("s", "rttnw_scene*", "*mut rttnw_scene", abi.scene_p),
@@ -37,82 +29,22 @@ ARGS = [("s", "rttnw_scene*", "*mut rttnw_scene", abi.scene_p),
 SIZE_ARGS = [("width", "uint32_t", "u32", C.c_uint32), ("height", "uint32_t", "u32", C.c_uint32)]
 
 
-def _declared_alike(name, args, c_ret, rs_ret, ct_ret):
-    m = re.search(r"\b%s rttnw_%s\((.*?)\);" % (c_ret, name), HEADER, flags=re.S)
-    assert m, "include/rttnw_hip.h does not declare rttnw_%s" % name
-    c_args = []
-    for a in " ".join(m.group(1).split()).split(","):
-        ctype, arg = re.match(r"(.+?)\s*(\w+)$", a.strip()).groups()
-        c_args.append((arg, ctype.replace(" *", "*")))
-    assert c_args == [(n, c) for n, c, _, _ in args]
-    m = re.search(r"pub fn rttnw_%s\((.*?)\)\s*->\s*%s;" % (name, rs_ret), FFI, flags=re.S)
-    assert m, "bindings/rust/src/ffi.rs does not declare rttnw_%s" % name
-    rs_args = [tuple(x.strip() for x in a.split(":", 1)) for a in m.group(1).split(",") if ":" in a]
-    assert rs_args == [(n, r) for n, _, r, _ in args]
-    proto = {n: (res, a) for n, res, a in abi.PRODUCT_FUNCS}[name]
-    assert proto[0] is ct_ret and list(proto[1]) == [t for _, _, _, t in args]
-
-
 def test_exports_and_declarations():
-    lib = C.CDLL(library.HIP_LIB)
-    for name in ("rttnw_render_adaptive_resume", "rttnw_adaptive_state_doubles"):
-        assert hasattr(lib, name) and name in abi.exported_symbols()
-    _declared_alike("render_adaptive_resume", ARGS, "int", "c_int", C.c_int)
-    _declared_alike("adaptive_state_doubles", SIZE_ARGS, "uint64_t", "u64", C.c_uint64)
-    assert re.search(r"#define RTTNW_ABI_VERSION 3\b", HEADER)      # no version bump: the symbol is how a caller finds the feature
-    assert lib.rttnw_abi_version() == 3
+    for name in ("render_adaptive_resume", "adaptive_state_doubles"):
+        exported(name)
+    declared_alike("render_adaptive_resume", ARGS)
+    declared_alike("adaptive_state_doubles", SIZE_ARGS, "uint64_t", "u64", C.c_uint64)
     assert "rttnw_render_adaptive_resume" in HEADER_TEXT.split("typedef struct rttnw_scene")[0], \
         "the comment at RTTNW_ABI_VERSION says how a caller detects the function"
-    assert "render_adaptive_resume" in open(os.path.join(ROOT, "bindings", "rust", "src", "scene.rs")).read(), "the crate's safe wrapper"
+    assert "render_adaptive_resume" in RUST_SCENE, "the crate's safe wrapper"
     assert "does NOT identify the scene" in HEADER_TEXT, "the header says what the state does not check"
-    for name, val in (("MAGIC", MAGIC), ("VERSION", VERSION), ("HEADER", HEADER_DOUBLES), ("RECORD", RECORD_DOUBLES)):
+    for name, val in (("MAGIC", MAGIC), ("VERSION", VERSION), ("HEADER", STATE_HEADER_DOUBLES), ("RECORD", STATE_RECORD_DOUBLES)):
         assert re.search(r"#define RTTNW_ADAPTIVE_STATE_%s %du\b" % (name, val), HEADER), name
 
 
 @pytest.mark.parametrize("w,h", [(1, 1), (40, 24), (45, 37), (0, 7), (7, 0), (0, 0), (65535, 65535)])
 def test_state_doubles(w, h):
     assert library.product().adaptive_state_doubles(w, h) == 64 + 12 * w * h
-
-
-def chunks_of_a_pass(B, spp_chunk):
-    """The chunks of a pass of B samples, by the rule in the header's comment at the record's k."""
-    if spp_chunk:
-        return -(-B // spp_chunk)
-    tail = B if B < 32 else B // 32
-    main = (B - tail) // 4
-    return main + (B - 4 * main)
-
-
-W, H = 16, 16
-CAM = dict(lookfrom=(0, 0, 5), lookat=(0, 0, 0), vfov=40.0, aspect=1.0)
-
-
-def _params(**kw):
-    p = S.make_params(kw.pop("width", W), kw.pop("height", H), kw.pop("spp", 128))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def _adaptive(**kw):
-    a = abi.Adaptive(pass_spp=64, reserved0=0, rel_error=0.05, abs_error=0.0)
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
-
-
-def _state(p, a, cam, n=None, k=None):
-    """A valid state made by hand: the header from the call's own arguments, every record n = B and k = the chunks of one pass."""
-    st = np.zeros(64 + 12 * p.width * p.height)
-    st[0:12] = [MAGIC, VERSION, p.width, p.height, a.pass_spp, p.spp_chunk, p.sample_begin, p.precision, p.max_depth, p.quirks,
-                p.seed & 0xFFFFFFFF, p.seed >> 32]
-    st[12] = p.t_min
-    st[13:16] = list(p.background)
-    st[16:31] = struct.unpack("15d", bytes(cam))
-    rec = st[64:].reshape(-1, 12)
-    rec[:, 3] = a.pass_spp if n is None else n
-    rec[:, 7] = chunks_of_a_pass(a.pass_spp, p.spp_chunk) if k is None else k
-    return st
 
 
 def _call(b, sc, p, a, ngpu=2, ids=(0, 0), scene=True, state=None, cam=None):
@@ -150,16 +82,7 @@ def test_refusals_come_before_the_device(what, kw, adapt, call, code, msg):
     sc = S.Scene(b)                                   # never committed: a device would be needed for that
     p = None if kw is None else _params(**kw)
     a = None if adapt is None else _adaptive(**adapt)
-    if code is None:
-        # validate() looks at the scene before the sizes: "not committed" on a scene, "NULL" without one — in either case before any device
-        assert _call(b, sc, p, a, **call) == STATE and "not committed" in b.last_error().decode(), what
-        assert _call(b, sc, p, a, scene=False, **call) == INVALID and "NULL" in b.last_error().decode(), what
-        return
-    assert _call(b, sc, p, a, **call) == code, what
-    err = b.last_error().decode()
-    assert err and msg in err and "render_adaptive_resume" in err, (what, err)
-    assert _call(b, sc, p, a, scene=False, **call) == code, what      # ... nor any scene at all
-    assert msg in b.last_error().decode(), what
+    refused(b, lambda scene: _call(b, sc, p, a, scene=scene, **call), code, msg, "render_adaptive_resume")
 
 
 def test_tile_fields_are_ignored_with_ranks_and_the_single_form_reaches_validate():
@@ -168,17 +91,6 @@ def test_tile_fields_are_ignored_with_ranks_and_the_single_form_reaches_validate
     assert _call(b, sc, _params(tile_world=2, tile_rank=1), _adaptive()) == STATE and "not committed" in b.last_error().decode()
     assert _call(b, sc, _params(), _adaptive(), ngpu=0, ids=None) == STATE and "not committed" in b.last_error().decode()
     assert _call(b, sc, _params(), _adaptive(), ngpu=64, ids=(0,) * 64) == STATE
-
-
-def _break(st, what):
-    st = st.copy()
-    rec = st[64:].reshape(-1, 12)
-    if isinstance(what, int):
-        st[what] = st[what] + 1.0 if st[what] == st[what] else 0.0
-    else:
-        field, value = what
-        rec[5, {"n": 3, "k": 7}[field]] = value
-    return st
 
 
 # 4. the state: (what is broken, header index or (record field, value), the word the message must hold)
@@ -309,9 +221,4 @@ def test_refusals_come_in_the_stated_order():
     (["7", "--noise", "0.1", "--save-state", "state.npy", "--window", "0,0,8,8"], "--save-state does not combine with --window"),
 ])
 def test_cli_refuses_before_any_scene_is_built(argv, msg, tmp_path):
-    out = tmp_path / "image.png"
-    r = subprocess.run([sys.executable, "-m", "rttnw_amd"] + argv + ["--out", str(out)], cwd=tmp_path, capture_output=True, text=True,
-                       env=dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", "")))
-    assert r.returncode != 0
-    assert msg in r.stderr, r.stderr
-    assert "Scene number" not in r.stdout and not out.exists() and not (tmp_path / "state.npy").exists()
+    cli_refuses(argv, msg, tmp_path, must_not_exist=("state.npy",))

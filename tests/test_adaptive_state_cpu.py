@@ -8,14 +8,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_cases
 from rttnw_amd import abi, library, tiles
 from rttnw_amd import scene as S
-import test_adaptive_resume_abi_cpu as resume_abi
+from test_adaptive_resume_abi_cpu import STATE_BREAKS, _call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FRAMES = [(8, 8), (45, 37), (96, 96)]      # one tile; edge tiles on both axes and 6 tile columns, so the permutation wraps; whole tiles
 WORLDS = [1, 2, 3, 5]                      # 5 leaves ranks with unequal tile counts
-HEADER, RECORD = resume_abi.HEADER_DOUBLES, resume_abi.RECORD_DOUBLES
+HEADER, RECORD = abi_cases.STATE_HEADER_DOUBLES, abi_cases.STATE_RECORD_DOUBLES
 
 
 @pytest.fixture(scope="module")
@@ -83,15 +84,15 @@ def test_no_state_is_zero_records_everywhere(host):
 
 def test_state_header_is_the_documented_layout(host):
     cam = S.camera_desc(lookfrom=(1.5, -2, 5), lookat=(0, 0.25, 0), vfov=37.0, aspect=45 / 37, aperture=0.1, focus=4.5)
-    p = resume_abi._params(width=45, height=37, spp=96, spp_chunk=4, sample_begin=32, max_depth=17, quirks=1, seed=(0xDEADBEEF << 32) | 0x80000001,
+    p = abi_cases.params(width=45, height=37, spp=96, spp_chunk=4, sample_begin=32, max_depth=17, quirks=1, seed=(0xDEADBEEF << 32) | 0x80000001,
                            t_min=1e-3, precision=abi.F32)
     p.background[0], p.background[1], p.background[2] = 0.25, -0.0, 3.0
-    a = resume_abi._adaptive(pass_spp=32)
+    a = abi_cases.adaptive(pass_spp=32)
     got = np.full(HEADER, np.nan)
     host.sh_header(C.byref(p), C.byref(a), C.byref(cam), got.ctypes.data)
-    want = resume_abi._state(p, a, cam)[:HEADER]                               # written from the header's comment, field by field
+    want = abi_cases.hand_made_state(p, a, cam)[:HEADER]                               # written from the header's comment, field by field
     assert (got.view(np.uint64) == want.view(np.uint64)).all()
-    assert got[0] == resume_abi.MAGIC and got[1] == resume_abi.VERSION and (got[31:] == 0).all()
+    assert got[0] == abi_cases.MAGIC and got[1] == abi_cases.VERSION and (got[31:] == 0).all()
     host.sh_header(C.byref(p), C.byref(a), None, got.ctypes.data)              # without a camera: its fields stay zero
     assert (got[:16].view(np.uint64) == want[:16].view(np.uint64)).all() and (got[16:] == 0).all()
 
@@ -107,24 +108,24 @@ def _refuse(host, p, a, cam, st, allow_empty=0):
     return rc, msg.value.decode(), first.value
 
 
-@pytest.mark.parametrize("name,what,msg", resume_abi.STATE_BREAKS, ids=[x[0] for x in resume_abi.STATE_BREAKS])
+@pytest.mark.parametrize("name,what,msg", STATE_BREAKS, ids=[x[0] for x in STATE_BREAKS])
 def test_refusals_are_the_exported_entry_points(host, name, what, msg):
     b = library.product()
     sc = S.Scene(b)
-    p, a, cam = resume_abi._params(spp_chunk=4), resume_abi._adaptive(), S.camera_desc(**resume_abi.CAM)
-    st = resume_abi._break(resume_abi._state(p, a, cam), what)
-    want_rc = resume_abi._call(b, sc, p, a, state=st)
+    p, a, cam = abi_cases.params(spp_chunk=4), abi_cases.adaptive(), abi_cases.camera()
+    st = abi_cases.break_state(abi_cases.hand_made_state(p, a, cam), what)
+    want_rc = _call(b, sc, p, a, state=st)
     want_msg = b.last_error().decode()
     rc, got, _ = _refuse(host, p, a, cam, st)
-    assert rc == want_rc == resume_abi.INVALID and got == want_msg and msg in got, (name, got, want_msg)
+    assert rc == want_rc == abi_cases.INVALID and got == want_msg and msg in got, (name, got, want_msg)
 
 
 def test_a_valid_state_passes_and_reports_its_lowest_level(host):
-    p, a, cam = resume_abi._params(spp_chunk=4), resume_abi._adaptive(), S.camera_desc(**resume_abi.CAM)
-    assert _refuse(host, p, a, cam, resume_abi._state(p, a, cam)) == (0, "", 1)
-    st = resume_abi._state(p, a, cam, n=128, k=32)
+    p, a, cam = abi_cases.params(spp_chunk=4), abi_cases.adaptive(), abi_cases.camera()
+    assert _refuse(host, p, a, cam, abi_cases.hand_made_state(p, a, cam)) == (0, "", 1)
+    st = abi_cases.hand_made_state(p, a, cam, n=128, k=32)
     assert _refuse(host, p, a, cam, st) == (0, "", 2)
     st[HEADER + 5 * RECORD:HEADER + 6 * RECORD] = 0.0                          # an empty record: the region and budget forms' only
     rc, got, _ = _refuse(host, p, a, cam, st)
-    assert rc == resume_abi.INVALID and "below pass_spp" in got
+    assert rc == abi_cases.INVALID and "below pass_spp" in got
     assert _refuse(host, p, a, cam, st, allow_empty=1) == (0, "", 0)

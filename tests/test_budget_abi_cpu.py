@@ -4,25 +4,15 @@ committed, and on no scene at all — in the order the header states, with a mes
 refuses --budget where it means nothing, before any scene is built.  (tests/test_gpu_budget_select.py and tests/test_gpu_adaptive_budget.py have
 what the device computes.)"""
 import ctypes as C
-import os
 import re
-import struct
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from abi_cases import FFI, HEADER, HEADER_TEXT, INVALID, RUST_SCENE, STATE, UNSUPPORTED, camera, cli_refuses, declared_alike, exported, refused
+from abi_cases import adaptive as _adaptive, break_state as _break, hand_made_state as _state, params as _params
 from rttnw_amd import abi, library
 from rttnw_amd import scene as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER_TEXT = open(os.path.join(ROOT, "include", "rttnw_hip.h")).read()
-HEADER = re.sub(r"/\*.*?\*/", "", HEADER_TEXT, flags=re.S)
-FFI = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")).read())
-RUST_SCENE = open(os.path.join(ROOT, "bindings", "rust", "src", "scene.rs")).read()
-INVALID, STATE, UNSUPPORTED = -1, -2, -3
-MAGIC, VERSION = 1381256791, 1
 
 # the argument lists, once: (name, C type, Rust type, ctypes type)
 _D, _U8, _U32 = ("double*", "*mut f64", C.c_void_p), ("uint8_t*", "*mut u8", C.c_void_p), ("uint32_t*", "*mut u32", C.c_void_p)
@@ -45,23 +35,8 @@ ARGS = {
 
 @pytest.mark.parametrize("name", ["budget_select", "render_adaptive_budget"])
 def test_export_and_declarations(name):
-    args = ARGS[name]
-    lib = C.CDLL(library.HIP_LIB)
-    assert hasattr(lib, "rttnw_" + name) and "rttnw_" + name in abi.exported_symbols()
-    m = re.search(r"\bint rttnw_%s\((.*?)\);" % name, HEADER, flags=re.S)
-    assert m, "include/rttnw_hip.h does not declare rttnw_%s" % name
-    c_args = []
-    for a in " ".join(m.group(1).split()).split(","):
-        ctype, arg = re.match(r"(.+?)\s*(\w+)$", a.strip()).groups()
-        c_args.append((arg, ctype.replace(" *", "*")))
-    assert c_args == [(n, c) for n, c, _, _ in args]
-    m = re.search(r"pub fn rttnw_%s\((.*?)\)\s*->\s*c_int;" % name, FFI, flags=re.S)
-    assert m, "bindings/rust/src/ffi.rs does not declare rttnw_%s" % name
-    assert [tuple(x.strip() for x in a.split(":", 1)) for a in m.group(1).split(",") if ":" in a] == [(n, r) for n, _, r, _ in args]
-    proto = {n: (res, a) for n, res, a in abi.PRODUCT_FUNCS}[name]
-    assert proto[0] is C.c_int and list(proto[1]) == [t for _, _, _, t in args]
-    assert re.search(r"#define RTTNW_ABI_VERSION 3\b", HEADER)      # no version bump: the symbol is how a caller finds the feature
-    assert lib.rttnw_abi_version() == 3 and abi.ABI_VERSION == 3
+    exported(name)
+    declared_alike(name, ARGS[name])
     head = HEADER_TEXT.split("typedef struct rttnw_scene")[0]
     assert "rttnw_" + name in head and "by its symbol" in head, "the comment at RTTNW_ABI_VERSION says how a caller detects the function"
     assert "pub fn %s(" % name in RUST_SCENE, "the crate's safe wrapper"
@@ -137,24 +112,6 @@ def test_select_refusals_come_in_the_stated_order():
 # ---------------------------------------------------------------- rttnw_render_adaptive_budget's refusals
 
 NAME = "render_adaptive_budget"
-W, H = 16, 16
-CAM = dict(lookfrom=(0, 0, 5), lookat=(0, 0, 0), vfov=40.0, aspect=1.0)
-
-
-def _params(**kw):
-    p = S.make_params(kw.pop("width", W), kw.pop("height", H), kw.pop("spp", 128))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def _adaptive(**kw):
-    a = abi.Adaptive(pass_spp=64, reserved0=0, rel_error=0.05, abs_error=0.0)
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
-
-
 def _budget(**kw):
     g = abi.Budget(samples=10000, round_pixels=0, reserved0=0)
     for k, v in kw.items():
@@ -162,22 +119,8 @@ def _budget(**kw):
     return g
 
 
-def _state(p, a, cam, n=None, k=None):
-    """A valid state made by hand: the header from the call's own arguments, every record n = B and k = the chunks of one pass unless given."""
-    st = np.zeros(64 + 12 * p.width * p.height)
-    st[0:12] = [MAGIC, VERSION, p.width, p.height, a.pass_spp, p.spp_chunk, p.sample_begin, p.precision, p.max_depth, p.quirks,
-                p.seed & 0xFFFFFFFF, p.seed >> 32]
-    st[12] = p.t_min
-    st[13:16] = list(p.background)
-    st[16:31] = struct.unpack("15d", bytes(cam))
-    rec = st[64:].reshape(-1, 12)
-    rec[:, 3] = a.pass_spp if n is None else n
-    rec[:, 7] = -(-a.pass_spp // p.spp_chunk) if k is None else k
-    return st
-
-
 def _call(b, sc, p, a, g, scene=True, state=None):
-    cam = S.camera_desc(**CAM)
+    cam = camera()
     return b.render_adaptive_budget(sc.handle if scene else None, C.byref(cam), C.byref(p) if p is not None else None,
                                     C.byref(a) if a is not None else None, C.byref(g) if g is not None else None,
                                     None if state is None else state.ctypes.data, None, None, None, None, None, None)
@@ -211,16 +154,7 @@ def test_render_refusals_come_before_the_device(what, kw, adapt, budget, code, m
     p = None if kw is None else _params(**kw)
     a = None if adapt is None else _adaptive(**adapt)
     g = None if budget is None else _budget(**budget)
-    if code is None:
-        # validate() looks at the scene before the sizes: "not committed" on a scene, "NULL" without one — in either case before any device
-        assert _call(b, sc, p, a, g) == STATE and "not committed" in b.last_error().decode(), what
-        assert _call(b, sc, p, a, g, scene=False) == INVALID and "NULL" in b.last_error().decode(), what
-        return
-    assert _call(b, sc, p, a, g) == code, what
-    err = b.last_error().decode()
-    assert err and msg in err and NAME in err, (what, err)
-    assert _call(b, sc, p, a, g, scene=False) == code, what      # ... nor any scene at all
-    assert msg in b.last_error().decode(), what
+    refused(b, lambda scene: _call(b, sc, p, a, g, scene=scene), code, msg, NAME)
 
 
 def test_valid_budget_arguments_reach_validate():
@@ -232,7 +166,7 @@ def test_valid_budget_arguments_reach_validate():
         assert _call(b, sc, _params(), _adaptive(), _budget(**budget)) == STATE and "not committed" in b.last_error().decode(), budget
     assert _call(b, sc, _params(), _adaptive(rel_error=0.0, abs_error=0.01), _budget()) == STATE
     assert _call(b, sc, _params(spp=64), _adaptive(), _budget()) == STATE                          # cap == B
-    p, a, cam = _params(spp_chunk=4), _adaptive(), S.camera_desc(**CAM)
+    p, a, cam = _params(spp_chunk=4), _adaptive(), camera()
     for st in (_state(p, a, cam), _state(p, a, cam, n=0, k=0)):
         assert _call(b, sc, p, a, _budget(), state=st) == STATE and "not committed" in b.last_error().decode()
         assert _call(b, sc, p, a, _budget(), state=st, scene=False) == INVALID and "NULL" in b.last_error().decode()
@@ -245,21 +179,11 @@ STATE_BREAKS = [("magic", 0, "magic"), ("version", 1, "version"), ("width", 2, "
                 ("k wrong", ("k", 15.0), "k is not")]
 
 
-def _break(st, what):
-    st = st.copy()
-    if isinstance(what, int):
-        st[what] = st[what] + 1.0
-    else:
-        field, value = what
-        st[64:].reshape(-1, 12)[5, {"n": 3, "k": 7}[field]] = value
-    return st
-
-
 @pytest.mark.parametrize("name,what,msg", STATE_BREAKS, ids=[x[0] for x in STATE_BREAKS])
 def test_a_broken_state_is_refused_before_the_scene_is_looked_at(name, what, msg):
     b = library.product()
     sc = S.Scene(b)
-    p, a, cam = _params(spp_chunk=4), _adaptive(), S.camera_desc(**CAM)
+    p, a, cam = _params(spp_chunk=4), _adaptive(), camera()
     st = _break(_state(p, a, cam), what)
     for scene in (True, False):
         assert _call(b, sc, p, a, _budget(), state=st, scene=scene) == INVALID, name
@@ -272,7 +196,7 @@ def test_render_refusals_come_in_the_stated_order():
     b = library.product()
     sc = S.Scene(b)
     err = lambda: b.last_error().decode()
-    p, a, cam = _params(spp_chunk=4), _adaptive(), S.camera_desc(**CAM)
+    p, a, cam = _params(spp_chunk=4), _adaptive(), camera()
     bad = _break(_state(p, a, cam), 0)
     # 1 before 2 and 3
     assert _call(b, sc, None, _adaptive(pass_spp=0), _budget(reserved0=1)) == INVALID and "NULL" in err()
@@ -312,9 +236,4 @@ def test_render_refusals_come_in_the_stated_order():
     (["7", "--noise", "0", "--budget", "100000"], "--budget needs a noise bound above 0"),
 ])
 def test_cli_refuses_before_any_scene_is_built(argv, msg, tmp_path):
-    out = tmp_path / "image.png"
-    r = subprocess.run([sys.executable, "-m", "rttnw_amd"] + argv + ["--out", str(out), "--save-state", str(tmp_path / "saved.npy")], cwd=tmp_path,
-                       capture_output=True, text=True, env=dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", "")))
-    assert r.returncode == 1
-    assert msg in r.stderr, r.stderr
-    assert "Scene number" not in r.stdout and not out.exists() and not (tmp_path / "saved.npy").exists()
+    cli_refuses(argv + ["--save-state", str(tmp_path / "saved.npy")], msg, tmp_path, must_not_exist=("saved.npy",))

@@ -1,25 +1,19 @@
 """rttnw_render_features and rttnw_denoise without a GPU: the exports exist and are declared alike in the header, the ctypes binding
 and the Rust binding, and every argument refusal comes before the device is touched."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
+from abi_cases import FFI, HEADER, camera, exported, params
 from rttnw_amd import abi, library
 from rttnw_amd import scene as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rttnw_hip.h")).read(), flags=re.S)
-FFI = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")).read())
-
 
 def test_exports_and_declarations():
-    lib = C.CDLL(library.HIP_LIB)
     for name in ("rttnw_render_features", "rttnw_denoise"):
-        assert hasattr(lib, name), name
-        assert name in abi.exported_symbols()
+        exported(name[len("rttnw_"):])
         assert re.search(r"\bint %s\(" % name, HEADER) and re.search(r"pub fn %s\(" % name, FFI)
     body = re.search(r"struct rttnw_denoise_params \{(.*?)\};", HEADER, flags=re.S).group(1)
     names = [n.strip() for _, group in re.findall(r"(uint32_t|double)\s+([\w, ]+);", body) for n in group.split(",")]
@@ -30,13 +24,12 @@ def test_exports_and_declarations():
                                                          ("sigma_normal", "f64"), ("sigma_depth", "f64")]
     assert [n for n, _ in abi.Denoise._fields_] == names
     assert C.sizeof(abi.Denoise) == 32 and abi.Denoise.sigma_luminance.offset == 8 and abi.Denoise.sigma_depth.offset == 24
-    assert re.search(r"#define RTTNW_ABI_VERSION 3\b", HEADER)      # the symbols are how a caller finds the feature
 
 
 # ---------------------------------------------------------------------------------------------- rttnw_render_features
 
 def _features(b, sc, p):
-    cam = S.camera_desc((0, 0, 5), (0, 0, 0), 40.0, 1.0)
+    cam = camera()
     return b.render_features(sc.handle, C.byref(cam), C.byref(p) if p is not None else None, None, None, None, None, None)
 
 
@@ -49,9 +42,8 @@ def _features(b, sc, p):
 def test_feature_refusals_come_before_the_device(what, kw, code, msg):
     b = library.product()
     sc = S.Scene(b)                                   # never committed: a device would be needed for that
-    p = S.make_params(16, 16, kw.pop("spp", 4))
-    for k, v in kw.items():
-        setattr(p, k, v)
+    kw.setdefault("spp", 4)
+    p = params(**kw)
     assert _features(b, sc, p) == code, what
     assert msg in b.last_error().decode(), (what, b.last_error())
 
@@ -60,10 +52,10 @@ def test_valid_feature_arguments_reach_the_scene_checks():
     b = library.product()
     sc = S.Scene(b)
     assert _features(b, sc, None) == -1 and "NULL" in b.last_error().decode()
-    assert _features(b, sc, S.make_params(16, 16, 4)) == -2   # RTTNW_ERR_STATE: the scene is not committed
+    assert _features(b, sc, params(spp=4)) == -2   # RTTNW_ERR_STATE: the scene is not committed
     assert "not committed" in b.last_error().decode()
-    cam = S.camera_desc((0, 0, 5), (0, 0, 0), 40.0, 1.0)
-    p = S.make_params(16, 16, 4)
+    cam = camera()
+    p = params(spp=4)
     assert b.render_features(None, C.byref(cam), C.byref(p), None, None, None, None, None) == -1
 
 

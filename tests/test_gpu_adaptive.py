@@ -10,7 +10,8 @@ import sys
 import numpy as np
 import pytest
 
-from rttnw_amd import abi, library, render
+from gpu_cases import build_scenes, use_kernel
+from rttnw_amd import abi, render
 from rttnw_amd import scene as S
 
 pytestmark = pytest.mark.gpu
@@ -20,13 +21,6 @@ RTOL = {abi.F64: 1e-12, abi.F64_STRICT: 1e-12, abi.F32: 1e-5}
 # refinement passes run the active-list form of the scene's kernel: the lane-owns-path one for these small scenes, the decoupled one
 # (which larger scenes take) when RTTNW_KERNEL=wave forces it
 KERNELS = [None, "wave"]
-
-
-def _kernel(monkeypatch, kernel):
-    if kernel:
-        monkeypatch.setenv("RTTNW_KERNEL", kernel)
-    else:
-        monkeypatch.delenv("RTTNW_KERNEL", raising=False)
 
 
 class AdaptivePixel(C.Structure):
@@ -50,11 +44,7 @@ def host():
 
 @pytest.fixture(scope="module")
 def scenes(gpu):
-    lib = library.scenes()
-    out = {}
-    for name in ("cornell_box", "simple_light", "final_scene"):
-        out[name] = S.build(gpu, lib, name, S.load_earth() if name == "final_scene" else None)
-    return out
+    return build_scenes(gpu, ("cornell_box", "simple_light", "final_scene"))
 
 
 def _params(scenes, name, w, spp, precision, **kw):
@@ -84,7 +74,7 @@ def test_pass0_is_the_plain_render(scenes, precision):
 @pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("name", ["cornell_box", "final_scene"])
 def test_pixels_compose_from_plain_passes(scenes, name, precision, kernel, monkeypatch):
-    _kernel(monkeypatch, kernel)
+    use_kernel(monkeypatch, kernel)
     B, cap = 16, 64
     sc, cam, p = _params(scenes, name, 32, cap, precision, spp_chunk=4)
     lin, rgba, spp, se, st = render.render_adaptive(sc, cam, p, pass_spp=B, rel_error=0.15, abs_error=0.01)
@@ -109,7 +99,7 @@ def test_device_state_is_the_host_harness_bit_for_bit(scenes, host, precision, k
     """The kernels' noise state and stopping decisions are those of the host build of adaptive.hpp, bit for bit: chunks of 4 and 2
     samples (B = 6, spp_chunk = 4), two passes.  A chunk's mean is a plain render of that chunk alone (a division by a power of two,
     exact in either precision), and a pixel's value after pass 0 is the plain render of its first B samples."""
-    _kernel(monkeypatch, kernel)
+    use_kernel(monkeypatch, kernel)
     B, cap, rel, ab = 6, 12, 0.3, 0.002
     sc, cam, p = _params(scenes, "cornell_box", 16, cap, precision, spp_chunk=4)
     _, _, spp, se, _ = render.render_adaptive(sc, cam, p, pass_spp=B, rel_error=rel, abs_error=ab)
@@ -147,7 +137,7 @@ def test_stderr_is_the_sample_standard_error(scenes, precision):
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_stopping_rule_prefix_and_launch_split(scenes, precision, kernel, monkeypatch):
-    _kernel(monkeypatch, kernel)
+    use_kernel(monkeypatch, kernel)
     B, cap, rel, ab = 16, 128, 0.1, 0.005
     sc, cam, p = _params(scenes, "simple_light", 32, cap, precision, spp_chunk=2)
     lin, rgba, spp, se, st = render.render_adaptive(sc, cam, p, pass_spp=B, rel_error=rel, abs_error=ab)

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 import budget_ref
+from gpu_cases import build_scenes
+from gpu_cases import hist as _histogram
 from rttnw_amd import abi, library, render
 from rttnw_amd import scene as S
 
@@ -28,8 +30,7 @@ MAPS = ("linear", "rgba8", "spp", "stderr")
 
 @pytest.fixture(scope="module")
 def scenes(gpu):
-    lib = library.scenes()
-    return {"cornell_box": S.build(gpu, lib, "cornell_box"), "final_scene": S.build(gpu, lib, "final_scene", S.load_earth())}
+    return build_scenes(gpu, ("cornell_box", "final_scene"))
 
 
 def _setup(scenes, name, precision, spp_chunk=1):
@@ -86,10 +87,6 @@ def _same(got, ref, what=""):
     for key in MAPS:
         assert np.array_equal(got[key], ref[key], equal_nan=key == "stderr"), (what, key, int((got[key] != ref[key]).sum()))
     assert np.array_equal(got["state"], ref["state"]), (what, "state")
-
-
-def _histogram(spp):
-    return {int(n): int((spp == n).sum()) for n in np.unique(spp)}
 
 
 @pytest.fixture(scope="module")

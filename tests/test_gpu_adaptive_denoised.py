@@ -15,7 +15,9 @@ import sys
 import numpy as np
 import pytest
 
-from rttnw_amd import abi, library, render
+from gpu_cases import build_scenes
+from gpu_cases import hist as _histogram
+from rttnw_amd import abi, render
 from rttnw_amd import scene as S
 
 pytestmark = pytest.mark.gpu
@@ -28,9 +30,7 @@ IMAGES = ("linear", "rgba8", "spp", "stderr", "raw_linear", "raw_stderr")
 
 @pytest.fixture(scope="module")
 def scenes(gpu):
-    lib = library.scenes()
-    return {"cornell_box": S.build(gpu, lib, "cornell_box"), "simple_light": S.build(gpu, lib, "simple_light"),
-            "final_scene": S.build(gpu, lib, "final_scene", S.load_earth())}
+    return build_scenes(gpu, ("cornell_box", "simple_light", "final_scene"))
 
 
 def _setup(scenes, name, precision, w=W, h=H, cap=CAP, spp_chunk=1):
@@ -71,10 +71,6 @@ def _same(got, ref, what=""):
     for key in IMAGES:
         assert np.array_equal(got[key], ref[key], equal_nan=key in ("stderr", "raw_stderr")), (what, key, int((got[key] != ref[key]).sum()))
     assert np.array_equal(got["state"], ref["state"]), (what, "state")
-
-
-def _histogram(spp):
-    return {int(n): int((spp == n).sum()) for n in np.unique(spp)}
 
 
 @pytest.fixture(scope="module")

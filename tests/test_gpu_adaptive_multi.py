@@ -8,59 +8,34 @@ import sys
 import numpy as np
 import pytest
 
-from rttnw_amd import abi, library, render, tiles
-from rttnw_amd import scene as S
+from gpu_cases import CASE1, CASE2, build_scenes, fresh_cache, use_kernel
+from gpu_cases import setup_case as _setup
+from rttnw_amd import abi, render, tiles
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRECISIONS = [abi.F64, abi.F32, abi.F64_STRICT]
 KERNELS = [None, "wave"]
-# case 1: the parameters of test_gpu_adaptive.py::test_stopping_rule_prefix_and_launch_split, on a 40x24 frame: 15 tiles, so 2 ranks have
-# unequal shares and 8 ranks have pad tiles
-CASE1 = dict(name="simple_light", w=40, h=24, B=16, cap=128, rel=0.1, ab=0.005, spp_chunk=2)
-# case 2: a frame that is no multiple of 8 (45x37: 30 tiles, 8 per rank of 4), test_pixels_compose_from_plain_passes' parameters
-CASE2 = dict(name="cornell_box", w=45, h=37, B=16, cap=64, rel=0.15, ab=0.01, spp_chunk=4)
+# (case 1 and case 2: tests/gpu_cases.py)
 # the tolerance of test_a_rank_that_finishes_early: of 8 ranks over case 1's frame, two stop after their first pass and the others after their
 # 2nd .. 7th (the samples of each rank's slowest pixel on the single-GPU result: 80, 16, 112, 80, 32, 48, 96, 16)
 EARLY_REL, EARLY_ABS = 0.5, 0.02
 
 
-def _kernel(monkeypatch, kernel):
-    if kernel:
-        monkeypatch.setenv("RTTNW_KERNEL", kernel)
-    else:
-        monkeypatch.delenv("RTTNW_KERNEL", raising=False)
-
-
 @pytest.fixture(scope="module")
 def scenes(gpu):
-    lib = library.scenes()
-    return {name: S.build(gpu, lib, name) for name in ("cornell_box", "simple_light")}
+    return build_scenes(gpu, ("cornell_box", "simple_light"))
+
+
+def _single(scenes, c, precision):
+    sc, cam, p = _setup(scenes, c, precision)
+    return render.render_adaptive(sc, cam, p, pass_spp=c["B"], rel_error=c["rel"], abs_error=c["ab"])
 
 
 @pytest.fixture(scope="module")
 def single(scenes):
     """rttnw_render_adaptive's result per (case, precision, kernel form): computed once, shared by the tests, never written to."""
-    cache = {}
-
-    def get(case, precision, kernel=None, **over):
-        c = dict(case, **over)
-        key = (tuple(sorted(c.items())), precision, kernel)
-        if key not in cache:
-            assert os.environ.get("RTTNW_KERNEL") == kernel and "RTTNW_CHUNK_SUM_BUDGET" not in os.environ
-            sc, cam, p = _setup(scenes, c, precision)
-            out = render.render_adaptive(sc, cam, p, pass_spp=c["B"], rel_error=c["rel"], abs_error=c["ab"])
-            for a in out[:4]:
-                a.setflags(write=False)
-            cache[key] = out
-        return cache[key]
-    return get
-
-
-def _setup(scenes, c, precision):
-    sc, setup = scenes[c["name"]]
-    cam, p = S.params_for(setup, c["w"], c["h"], c["cap"], precision=precision, spp_chunk=c["spp_chunk"])
-    return sc, cam, p
+    return fresh_cache(lambda c, precision: _single(scenes, c, precision))
 
 
 def _multi(scenes, c, precision, n):
@@ -92,7 +67,7 @@ def test_bit_identity_over_ranks(scenes, single, precision, kernel, monkeypatch)
     """Case 1 (simple_light 40x24, B = 16, cap = 128, rel_error 0.1, abs_error 0.005, spp_chunk 2) over 1, 2, 3 and 8 logical ranks.  The
     single-GPU result must hold pixels that stopped after the first pass, pixels at the cap and pixels in between, or the equalities
     would say little."""
-    _kernel(monkeypatch, kernel)
+    use_kernel(monkeypatch, kernel)
     ref = single(CASE1, precision, kernel)
     values = set(np.unique(ref[2]).tolist())
     print("samples map of the single call: %s" % dict(zip(*np.unique(ref[2], return_counts=True))))

@@ -3,7 +3,7 @@ under a cap and tolerances is, bit for bit, that pixel of ONE fresh whole-frame 
 standard error and state record — whatever the window, the mask, the calls before it, the precision, the kernel form, the launch split and the
 number of ranks on either side of a hand-over; an unselected pixel keeps its record, and a pixel without samples is zero everywhere, alpha included.
 The reference F is always render.render_adaptive_resume(state=None) of the frame: code that existed before this entry point, never the entry point
-itself.  One GPU, logical ranks: the device list repeats device 0.  The frames and parameters are those of tests/test_gpu_adaptive_resume.py."""
+itself.  One GPU, logical ranks: the device list repeats device 0.  The frames and parameters are those of tests/gpu_cases.py."""
 import os
 import subprocess
 import sys
@@ -11,38 +11,22 @@ import sys
 import numpy as np
 import pytest
 
-from rttnw_amd import abi, library, render
-from rttnw_amd import scene as S
+from gpu_cases import CASE1, CASE2, LOOSE_ABS, LOOSE_REL, build_scenes, fresh_cache, use_kernel
+from gpu_cases import hist as _hist, same_outputs, samples as _samples, setup_case as _setup
+from rttnw_amd import abi, render
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRECISIONS = [abi.F64, abi.F32, abi.F64_STRICT]
 KERNELS = [None, "wave"]
 RANKS = [None, [0, 0, 0]]
-CASE1 = dict(name="simple_light", w=40, h=24, B=16, cap=128, rel=0.1, ab=0.005, spp_chunk=2)
-CASE2 = dict(name="cornell_box", w=45, h=37, B=16, cap=64, rel=0.15, ab=0.01, spp_chunk=4)
-LOOSE_REL, LOOSE_ABS = 0.5, 0.02
 WINDOW = (3, 5, 30, 22)      # odd corners: aligned to neither the 2x2 blocks nor the 8x8 tiles; fits both frames
 LEFT, OVERLAP = (0, 0, 25, 37), (17, 9, 45, 30)  # case 2: the left part of the frame, and a window that overlaps it and reaches the right edge
 
 
-def _kernel(monkeypatch, kernel):
-    if kernel:
-        monkeypatch.setenv("RTTNW_KERNEL", kernel)
-    else:
-        monkeypatch.delenv("RTTNW_KERNEL", raising=False)
-
-
 @pytest.fixture(scope="module")
 def scenes(gpu):
-    lib = library.scenes()
-    return {name: S.build(gpu, lib, name) for name in ("cornell_box", "simple_light")}
-
-
-def _setup(scenes, c, precision):
-    sc, setup = scenes[c["name"]]
-    cam, p = S.params_for(setup, c["w"], c["h"], c["cap"], precision=precision, spp_chunk=c["spp_chunk"])
-    return sc, cam, p
+    return build_scenes(gpu, ("cornell_box", "simple_light"))
 
 
 def _frame(c):
@@ -61,20 +45,10 @@ def _region(scenes, c, precision, win, mask=None, state=None, ids=None, **over):
 def fresh(scenes):
     """F: the uninterrupted whole-frame call of rttnw_render_adaptive_resume (state_in NULL, ngpu 0) per (case, precision, kernel form): computed
     once, shared, never written to."""
-    cache = {}
-
-    def get(case, precision, kernel=None, **over):
-        c = dict(case, **over)
-        key = (tuple(sorted(c.items())), precision, kernel)
-        if key not in cache:
-            assert os.environ.get("RTTNW_KERNEL") == kernel and "RTTNW_CHUNK_SUM_BUDGET" not in os.environ
-            sc, cam, p = _setup(scenes, c, precision)
-            out = render.render_adaptive_resume(sc, cam, p, None, None, pass_spp=c["B"], rel_error=c["rel"], abs_error=c["ab"])
-            for a in out[:4] + out[5:]:
-                a.setflags(write=False)
-            cache[key] = out
-        return cache[key]
-    return get
+    def whole_frame(c, precision):
+        sc, cam, p = _setup(scenes, c, precision)
+        return render.render_adaptive_resume(sc, cam, p, None, None, pass_spp=c["B"], rel_error=c["rel"], abs_error=c["ab"])
+    return fresh_cache(whole_frame)
 
 
 def _crop(a, win):
@@ -93,26 +67,9 @@ def _inside(c, win, mask=None):
     return sel
 
 
-def _same_outputs(got, ref, where=None, what=""):
-    """The four outputs, bit for bit (+inf equal to +inf), at the pixels `where` (all of them by default)."""
-    w = np.ones(ref[2].shape, dtype=bool) if where is None else where
-    assert np.array_equal(got[0][w], ref[0][w]), (what, "linear")
-    assert np.array_equal(got[1][w], ref[1][w]), (what, "rgba8")
-    assert np.array_equal(got[2][w], ref[2][w]), (what, "samples", int((got[2][w] != ref[2][w]).sum()))
-    assert np.array_equal(got[3][w], ref[3][w], equal_nan=True), (what, "stderr")
-
-
 def _cleared(got, where, what=""):
     """A pixel without samples: 0, 0, 0, RGBA8 0, 0, 0, 0, spp 0, stderr 0."""
     assert not got[0][where].any() and not got[1][where].any() and not got[2][where].any() and not got[3][where].any(), what
-
-
-def _samples(stats):
-    return sum(x.samples for x in stats) if isinstance(stats, list) else stats.samples
-
-
-def _hist(spp):
-    return {int(k): int(v) for k, v in zip(*np.unique(spp, return_counts=True))}
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
@@ -121,10 +78,10 @@ def _hist(spp):
 def test_whole_frame(scenes, fresh, precision, ids, kernel, monkeypatch):
     """Window = frame, no mask, no state: the four outputs and the state of F (level 0 runs over a list here, in the plain job numbering there),
     and exactly F's samples."""
-    _kernel(monkeypatch, kernel)
+    use_kernel(monkeypatch, kernel)
     ref = fresh(CASE2, precision, kernel)
     got = _region(scenes, CASE2, precision, _frame(CASE2), ids=ids)
-    _same_outputs(got, ref, what="whole frame")
+    same_outputs(got, ref, what="whole frame")
     assert np.array_equal(got[5], ref[5], equal_nan=True), int((got[5] != ref[5]).sum())
     assert _samples(got[4]) == int(ref[2].sum())
     one = got[4][0] if ids else got[4]
@@ -143,7 +100,7 @@ def test_window(scenes, fresh, precision, ids):
     print("samples map of the crop: %s" % _hist(crop[2]))
     assert len(np.unique(crop[2])) >= 2, "more than one level must run"
     got = _region(scenes, CASE2, precision, WINDOW, ids=ids)
-    _same_outputs(got, crop, what="window")
+    same_outputs(got, crop, what="window")
     inside = _inside(CASE2, WINDOW)
     rec, ref_rec = _records(CASE2, got[5]), _records(CASE2, ref[5])
     assert np.array_equal(got[5][:64], ref[5][:64])
@@ -167,7 +124,7 @@ def test_mask(scenes, fresh, precision, ids):
     mask = _mask()
     assert 0.25 < mask.mean() < 0.42
     got = _region(scenes, CASE2, precision, WINDOW, mask=mask, ids=ids)
-    _same_outputs(got, crop, where=mask, what="mask")
+    same_outputs(got, crop, where=mask, what="mask")
     assert (got[1][mask][:, 3] == 255).all()
     _cleared(got, ~mask, "unselected")
     inside = _inside(CASE2, WINDOW, mask)
@@ -189,7 +146,7 @@ def test_all_zero_mask(scenes, fresh, ids):
     assert np.array_equal(got[5][:64], ref[5][:64]) and not got[5][64:].any()
     got = _region(scenes, CASE2, abi.F64, WINDOW, mask=nothing, state=ref[5], ids=ids)
     assert _samples(got[4]) == 0
-    _same_outputs(got, [_crop(a, WINDOW) for a in ref[:4]], what="the state's own outputs")
+    same_outputs(got, [_crop(a, WINDOW) for a in ref[:4]], what="the state's own outputs")
     assert np.array_equal(got[5], ref[5], equal_nan=True)
 
 
@@ -203,7 +160,7 @@ def test_paint_then_complete(scenes, fresh, precision):
     in_a = _inside(CASE2, LEFT)
     rec = _records(CASE2, a[5])
     assert not rec[~in_a].any() and np.array_equal(rec[in_a], ref_rec[in_a], equal_nan=True)
-    _same_outputs(a, [_crop(x, LEFT) for x in ref[:4]], what="A")
+    same_outputs(a, [_crop(x, LEFT) for x in ref[:4]], what="A")
     sc, cam, p = _setup(scenes, CASE2, precision)
     with pytest.raises(abi.RttnwError, match="render_adaptive_resume: state_in: a record's n is below pass_spp"):
         render.render_adaptive_resume(sc, cam, p, a[5], None, pass_spp=CASE2["B"], rel_error=CASE2["rel"], abs_error=CASE2["ab"])
@@ -211,14 +168,14 @@ def test_paint_then_complete(scenes, fresh, precision):
     in_ab = in_a | _inside(CASE2, OVERLAP)
     rec = _records(CASE2, b[5])
     assert not rec[~in_ab].any() and np.array_equal(rec[in_ab], ref_rec[in_ab], equal_nan=True)
-    _same_outputs(b, [_crop(x, OVERLAP) for x in ref[:4]], what="B")
+    same_outputs(b, [_crop(x, OVERLAP) for x in ref[:4]], what="B")
     assert _samples(b[4]) == int(ref[2][in_ab & ~in_a].sum())
     c = _region(scenes, CASE2, precision, _frame(CASE2), state=b[5])
-    _same_outputs(c, ref, what="C")
+    same_outputs(c, ref, what="C")
     assert np.array_equal(c[5], ref[5], equal_nan=True)
     assert _samples(a[4]) + _samples(b[4]) + _samples(c[4]) == int(ref[2].sum())
     again = render.render_adaptive_resume(sc, cam, p, c[5], None, pass_spp=CASE2["B"], rel_error=CASE2["rel"], abs_error=CASE2["ab"])
-    _same_outputs(again, ref, what="resume of the completed state")
+    same_outputs(again, ref, what="resume of the completed state")
     assert again[4].samples == 0 and np.array_equal(again[5], ref[5], equal_nan=True)
 
 
@@ -237,14 +194,14 @@ def test_refine_where_you_look(scenes, fresh, precision, ids):
     grew = inside & (ref[2] > loose[2])
     assert grew.any() and len(np.unique(loose[2][grew])) >= 2, "pixels at more than one level must go on"
     got = _region(scenes, CASE1, precision, WINDOW, state=loose[5], ids=ids)
-    _same_outputs(got, [_crop(a, WINDOW) for a in ref[:4]], what="refined window")
+    same_outputs(got, [_crop(a, WINDOW) for a in ref[:4]], what="refined window")
     rec, ref_rec, loose_rec = _records(CASE1, got[5]), _records(CASE1, ref[5]), _records(CASE1, loose[5])
     assert np.array_equal(rec[inside], ref_rec[inside], equal_nan=True)
     assert np.array_equal(rec[~inside], loose_rec[~inside], equal_nan=True)
     assert _samples(got[4]) == int(ref[2][inside].sum()) - int(loose[2][inside].sum()) > 0
     masked = _region(scenes, CASE1, precision, _frame(CASE1), mask=inside, state=loose[5], ids=ids)
-    _same_outputs(masked, ref, where=inside, what="mask over the frame, selected")
-    _same_outputs(masked, loose, where=~inside, what="mask over the frame, unselected")
+    same_outputs(masked, ref, where=inside, what="mask over the frame, selected")
+    same_outputs(masked, loose, where=~inside, what="mask over the frame, unselected")
     assert (masked[1][..., 3] == 255).all()
     assert np.array_equal(masked[5], got[5], equal_nan=True)
 
@@ -256,9 +213,9 @@ def test_hand_over_between_rank_counts(scenes, fresh, precision, first, second):
     ref = fresh(CASE2, precision)
     a = _region(scenes, CASE2, precision, LEFT, ids=first)
     b = _region(scenes, CASE2, precision, OVERLAP, state=a[5], ids=second)
-    _same_outputs(b, [_crop(x, OVERLAP) for x in ref[:4]], what="B")
+    same_outputs(b, [_crop(x, OVERLAP) for x in ref[:4]], what="B")
     c = _region(scenes, CASE2, precision, _frame(CASE2), state=b[5], ids=first)
-    _same_outputs(c, ref, what="C")
+    same_outputs(c, ref, what="C")
     assert np.array_equal(c[5], ref[5], equal_nan=True)
     assert _samples(a[4]) + _samples(b[4]) + _samples(c[4]) == int(ref[2].sum())
 
@@ -268,7 +225,7 @@ def test_peer_gather(scenes, fresh, monkeypatch):
     ref = fresh(CASE2, abi.F64)
     monkeypatch.setenv("RTTNW_MULTI_GATHER", "peer")
     got = _region(scenes, CASE2, abi.F64, WINDOW, ids=[0] * 4)
-    _same_outputs(got, [_crop(a, WINDOW) for a in ref[:4]], what="peer")
+    same_outputs(got, [_crop(a, WINDOW) for a in ref[:4]], what="peer")
 
 
 def test_launch_split(scenes, fresh, monkeypatch):
@@ -276,9 +233,9 @@ def test_launch_split(scenes, fresh, monkeypatch):
     ref = fresh(CASE2, abi.F64)
     monkeypatch.setenv("RTTNW_CHUNK_SUM_BUDGET", "1")
     got = _region(scenes, CASE2, abi.F64, WINDOW)
-    _same_outputs(got, [_crop(a, WINDOW) for a in ref[:4]], what="one-chunk launches, window")
+    same_outputs(got, [_crop(a, WINDOW) for a in ref[:4]], what="one-chunk launches, window")
     done = _region(scenes, CASE2, abi.F64, _frame(CASE2), state=got[5])
-    _same_outputs(done, ref, what="one-chunk launches, completed")
+    same_outputs(done, ref, what="one-chunk launches, completed")
     assert np.array_equal(done[5], ref[5], equal_nan=True)
 
 
@@ -290,7 +247,7 @@ def test_refusals_of_a_committed_scene(scenes, fresh):
     with pytest.raises(abi.RttnwError, match="render_adaptive_region: the window"):
         _region(scenes, CASE2, abi.F64, (3, 5, CASE2["w"] + 1, 22))
     got = _region(scenes, CASE2, abi.F64, WINDOW)
-    _same_outputs(got, [_crop(a, WINDOW) for a in ref[:4]], what="afterwards")
+    same_outputs(got, [_crop(a, WINDOW) for a in ref[:4]], what="afterwards")
 
 
 def test_cli_refine(gpu, tmp_path):

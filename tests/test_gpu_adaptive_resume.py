@@ -1,7 +1,7 @@
 """rttnw_render_adaptive_resume on the MI355X, held to its contract (include/rttnw_hip.h): a render continued from a state — to a higher cap, to a
 tighter tolerance, step by step, on another number of ranks — is the render that was never interrupted, bit for bit: linear image, RGBA8, samples
 map, standard-error map and the state itself.  One GPU, logical ranks: the device list repeats device 0.  The frames and parameters are those of
-tests/test_gpu_adaptive_multi.py."""
+tests/gpu_cases.py."""
 import os
 import subprocess
 import sys
@@ -9,35 +9,20 @@ import sys
 import numpy as np
 import pytest
 
-from rttnw_amd import abi, library, render, tiles
-from rttnw_amd import scene as S
+import abi_cases
+from gpu_cases import CASE1, CASE2, LOOSE_ABS, LOOSE_REL, build_scenes, fresh_cache, use_kernel
+from gpu_cases import hist as _hist, same_outputs, samples as _samples, setup_case as _setup
+from rttnw_amd import abi, render, tiles
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRECISIONS = [abi.F64, abi.F32, abi.F64_STRICT]
 KERNELS = [None, "wave"]
-CASE1 = dict(name="simple_light", w=40, h=24, B=16, cap=128, rel=0.1, ab=0.005, spp_chunk=2)
-CASE2 = dict(name="cornell_box", w=45, h=37, B=16, cap=64, rel=0.15, ab=0.01, spp_chunk=4)
-LOOSE_REL, LOOSE_ABS = 0.5, 0.02
-
-
-def _kernel(monkeypatch, kernel):
-    if kernel:
-        monkeypatch.setenv("RTTNW_KERNEL", kernel)
-    else:
-        monkeypatch.delenv("RTTNW_KERNEL", raising=False)
 
 
 @pytest.fixture(scope="module")
 def scenes(gpu):
-    lib = library.scenes()
-    return {name: S.build(gpu, lib, name) for name in ("cornell_box", "simple_light")}
-
-
-def _setup(scenes, c, precision):
-    sc, setup = scenes[c["name"]]
-    cam, p = S.params_for(setup, c["w"], c["h"], c["cap"], precision=precision, spp_chunk=c["spp_chunk"])
-    return sc, cam, p
+    return build_scenes(gpu, ("cornell_box", "simple_light"))
 
 
 def _resume(scenes, c, precision, state=None, ids=None, **over):
@@ -50,37 +35,7 @@ def _resume(scenes, c, precision, state=None, ids=None, **over):
 @pytest.fixture(scope="module")
 def fresh(scenes):
     """The uninterrupted call (state_in NULL, ngpu 0) per (case, precision, kernel form): computed once, shared, never written to."""
-    cache = {}
-
-    def get(case, precision, kernel=None, **over):
-        c = dict(case, **over)
-        key = (tuple(sorted(c.items())), precision, kernel)
-        if key not in cache:
-            assert os.environ.get("RTTNW_KERNEL") == kernel and "RTTNW_CHUNK_SUM_BUDGET" not in os.environ
-            out = _resume(scenes, c, precision)
-            for a in out[:4] + out[5:]:
-                a.setflags(write=False)
-            cache[key] = out
-        return cache[key]
-    return get
-
-
-def _same(got, ref, what=""):
-    """The four outputs and the state, bit for bit (+inf equal to +inf, NaN to NaN)."""
-    assert np.array_equal(got[0], ref[0]), (what, "linear", np.abs(got[0] - ref[0]).max())
-    assert np.array_equal(got[1], ref[1]), (what, "rgba8")
-    assert np.array_equal(got[2], ref[2]), (what, "samples", int((got[2] != ref[2]).sum()))
-    assert np.array_equal(got[3], ref[3], equal_nan=True), (what, "stderr")
-    if len(got) > 5 and len(ref) > 5:
-        assert np.array_equal(got[5], ref[5], equal_nan=True), (what, "state", int((got[5] != ref[5]).sum()))
-
-
-def _samples(stats):
-    return sum(x.samples for x in stats) if isinstance(stats, list) else stats.samples
-
-
-def _hist(spp):
-    return {int(k): int(v) for k, v in zip(*np.unique(spp, return_counts=True))}
+    return fresh_cache(lambda c, precision: _resume(scenes, c, precision))
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
@@ -89,12 +44,12 @@ def test_fresh_equals_the_existing_calls(scenes, fresh, precision):
     sc, cam, p = _setup(scenes, CASE1, precision)
     one = render.render_adaptive(sc, cam, p, pass_spp=CASE1["B"], rel_error=CASE1["rel"], abs_error=CASE1["ab"])
     got = fresh(CASE1, precision)
-    _same(got, one, "ngpu 0")
+    same_outputs(got, one, what="ngpu 0")
     assert got[4].samples == one[4].samples == int(one[2].sum())
     assert (got[4].reserved, got[4].n_nodes, got[4].n_prims, got[4].scene_bytes) == (one[4].reserved, one[4].n_nodes, one[4].n_prims, one[4].scene_bytes)
     assert got[4].kernel_ms > 0
     three = _resume(scenes, CASE1, precision, ids=[0, 0, 0])
-    _same(three, got, "three ranks")
+    same_outputs(three, got, what="three ranks")
     assert len(three[4]) == 3 and _samples(three[4]) == one[4].samples
 
 
@@ -103,13 +58,13 @@ def test_fresh_equals_the_existing_calls(scenes, fresh, precision):
 def test_checkpoint(scenes, fresh, precision, kernel, monkeypatch):
     """Case 1 stopped at a cap of 48, then resumed to 128: the one fresh call with cap 128.  At 48 some pixels had converged and some stood at
     the cap; the final map goes beyond it, so the resumed call had real work, and it traced exactly the difference."""
-    _kernel(monkeypatch, kernel)
+    use_kernel(monkeypatch, kernel)
     ref = fresh(CASE1, precision, kernel)
     part = fresh(CASE1, precision, kernel, cap=48)
     print("samples map at cap 48: %s; at cap 128: %s" % (_hist(part[2]), _hist(ref[2])))
     assert (part[2] < 48).any() and (part[2] == 48).any() and (ref[2] > 48).any()
     got = _resume(scenes, CASE1, precision, state=part[5])
-    _same(got, ref, "checkpoint")
+    same_outputs(got, ref, what="checkpoint")
     assert got[4].samples == int(ref[2].sum()) - int(part[2].sum()) > 0
 
 
@@ -127,7 +82,7 @@ def test_refine(scenes, fresh, precision):
     assert (ref[2] == loose[2]).any(), "some pixel keeps its count"
     assert (ref[2] >= loose[2]).all()
     got = _resume(scenes, CASE1, precision, state=loose[5])
-    _same(got, ref, "refine")
+    same_outputs(got, ref, what="refine")
     assert got[4].samples == int(ref[2].sum()) - int(loose[2].sum())
 
 
@@ -140,7 +95,7 @@ def test_progressive(scenes, fresh):
         got = _resume(scenes, CASE1, abi.F64, state=state, cap=cap)
         state = got[5]
         traced += got[4].samples
-    _same(got, ref, "progressive")
+    same_outputs(got, ref, what="progressive")
     assert traced == ref[4].samples == int(ref[2].sum())
 
 
@@ -149,14 +104,14 @@ def test_nothing_to_do(scenes, fresh):
     traced, the outputs of the call that made the state, the state unchanged."""
     ref = fresh(CASE1, abi.F64)
     got = _resume(scenes, CASE1, abi.F64, state=ref[5])
-    _same(got, ref, "unchanged arguments")
+    same_outputs(got, ref, what="unchanged arguments")
     assert got[4].samples == 0
     part = fresh(CASE1, abi.F64, cap=48)
     got = _resume(scenes, CASE1, abi.F64, state=part[5], cap=256, rel=1e9, ab=1e9)
-    _same(got, part, "tolerance 1e9")
+    same_outputs(got, part, what="tolerance 1e9")
     assert got[4].samples == 0
     ranks = _resume(scenes, CASE1, abi.F64, state=part[5], ids=[0, 0], cap=256, rel=1e9, ab=1e9)
-    _same(ranks, part, "tolerance 1e9, two ranks")
+    same_outputs(ranks, part, what="tolerance 1e9, two ranks")
     assert [x.samples for x in ranks[4]] == [0, 0]
 
 
@@ -177,12 +132,12 @@ def test_across_rank_counts(scenes, fresh, precision):
     assert (part[2] == 32).any() and (ref[2] > 32).any()
     for n in (4, 7):
         got = _resume(scenes, CASE2, precision, state=part[5], ids=[0] * n)
-        _same(got, ref, "%d ranks" % n)
+        same_outputs(got, ref, what="%d ranks" % n)
         _per_rank(CASE2, n, got[4], part[2], ref[2])
     part3 = _resume(scenes, CASE2, precision, ids=[0] * 3, cap=32)
-    _same(part3, part, "state made on 3 ranks")
+    same_outputs(part3, part, what="state made on 3 ranks")
     got = _resume(scenes, CASE2, precision, state=part3[5])
-    _same(got, ref, "3 ranks, then the single device")
+    same_outputs(got, ref, what="3 ranks, then the single device")
     assert got[4].samples == int(ref[2].sum()) - int(part[2].sum())
 
 
@@ -192,7 +147,7 @@ def test_peer_gather(scenes, fresh, monkeypatch):
     part = fresh(CASE2, abi.F64, cap=32)
     monkeypatch.setenv("RTTNW_MULTI_GATHER", "peer")
     got = _resume(scenes, CASE2, abi.F64, state=part[5], ids=[0] * 4)
-    _same(got, ref, "peer")
+    same_outputs(got, ref, what="peer")
     _per_rank(CASE2, 4, got[4], part[2], ref[2])
 
 
@@ -201,7 +156,7 @@ def test_launch_split(scenes, fresh, monkeypatch):
     ref = fresh(CASE1, abi.F64)
     part = fresh(CASE1, abi.F64, cap=48)
     monkeypatch.setenv("RTTNW_CHUNK_SUM_BUDGET", "1")
-    _same(_resume(scenes, CASE1, abi.F64, state=part[5]), ref, "one-chunk launches")
+    same_outputs(_resume(scenes, CASE1, abi.F64, state=part[5]), ref, what="one-chunk launches")
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
@@ -210,7 +165,7 @@ def test_the_state_says_what_the_outputs_say(fresh, precision):
     c = CASE1
     assert state.shape == (64 + 12 * c["w"] * c["h"],)
     head = state[:64]
-    assert head[0] == 1381256791 and head[1] == 1 and (head[2], head[3], head[4], head[5]) == (c["w"], c["h"], c["B"], c["spp_chunk"])
+    assert head[0] == abi_cases.MAGIC and head[1] == abi_cases.VERSION and (head[2], head[3], head[4], head[5]) == (c["w"], c["h"], c["B"], c["spp_chunk"])
     assert head[7] == precision and not head[31:].any()
     rec = state[64:].reshape(c["h"], c["w"], 12)
     n, k = rec[..., 3], rec[..., 7]
@@ -246,7 +201,7 @@ def test_a_state_of_another_render_is_refused(scenes, fresh):
     p.precision = abi.F64_STRICT
     with pytest.raises(abi.RttnwError, match="no such device"):
         render.render_adaptive_resume(sc, cam, p, ref[5], [0, -1], **kw)
-    _same(render.render_adaptive_resume(sc, cam, p, None, **kw), ref, "afterwards")
+    same_outputs(render.render_adaptive_resume(sc, cam, p, None, **kw), ref, what="afterwards")
 
 
 def test_state_in_and_state_out_may_be_one_array(gpu, scenes, fresh):

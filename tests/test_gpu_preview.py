@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from golden_cases import WINDOWS, load_windows
-from rttnw_amd import abi, library, render
+from gpu_cases import build_scenes
+from rttnw_amd import abi, render
 from rttnw_amd import scene as S
 
 pytestmark = pytest.mark.gpu
@@ -26,8 +27,7 @@ IMAGES = ("linear", "rgba8", "valid", "spp", "raw_linear", "raw_stderr")
 
 @pytest.fixture(scope="module")
 def scenes(gpu):
-    lib = library.scenes()
-    return {name: S.build(gpu, lib, name, S.load_earth() if name == "final_scene" else None) for name in ("cornell_box", "final_scene")}
+    return build_scenes(gpu, ("cornell_box", "final_scene"))
 
 
 def _setup(scenes, name, precision, size, cap=CAP):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import rto
+from gpu_cases import build_scenes, use_kernel
 from rttnw_amd import abi, library, render
 from rttnw_amd import scene as S
 
@@ -23,17 +24,9 @@ WINDOWS = [(5, 3, 23, 18),     # odd edges: splits 2x2 blocks, crosses tile bord
            (7, 7, 9, 9)]       # four blocks of four tiles, one pixel each
 
 
-def _kernel(monkeypatch, kernel):
-    if kernel:
-        monkeypatch.setenv("RTTNW_KERNEL", kernel)
-    else:
-        monkeypatch.delenv("RTTNW_KERNEL", raising=False)
-
-
 @pytest.fixture(scope="module")
 def scenes(gpu):
-    lib = library.scenes()
-    return {name: S.build(gpu, lib, name, S.load_earth() if name == "final_scene" else None) for name in NAMES}
+    return build_scenes(gpu, NAMES)
 
 
 def _params(scenes, name, precision, spp=32, w=W, h=H, **kw):
@@ -67,7 +60,7 @@ def _crop(a, win):
 @pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("name", NAMES)
 def test_a_window_is_the_crop_of_the_frame(scenes, name, precision, kernel, monkeypatch):
-    _kernel(monkeypatch, kernel)
+    use_kernel(monkeypatch, kernel)
     lin, rgba, form, _ = _frame(scenes, name, precision, kernel)
     sc, cam, p = _params(scenes, name, precision)
     for win in WINDOWS:
@@ -85,7 +78,7 @@ def test_a_window_is_the_crop_of_the_frame(scenes, name, precision, kernel, monk
 @pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("name", NAMES)
 def test_a_mask_selects_pixels(scenes, name, precision, kernel, monkeypatch):
-    _kernel(monkeypatch, kernel)
+    use_kernel(monkeypatch, kernel)
     win = (2, 1, 38, 27)
     mask = np.random.default_rng(7).random((26, 36)) < 0.3
     assert 0 < mask.sum() < mask.size
@@ -117,7 +110,7 @@ def test_a_mask_selects_pixels(scenes, name, precision, kernel, monkeypatch):
 def test_an_empty_selection_reports_the_render_it_skipped(scenes, precision, monkeypatch):
     """A mask that selects nothing: no trace launch, so the stats come from a launch plan made for them alone — the kernel form (bits 0-5 of
     `reserved`) and the scene sizes must be those of a region render of the same scene and precision that did trace."""
-    _kernel(monkeypatch, None)
+    use_kernel(monkeypatch, None)
     win = (5, 3, 23, 18)
     sc, cam, p = _params(scenes, "cornell_box", precision, spp=4)
     _, _, traced = render.render_region(sc, cam, p, *win)
@@ -185,7 +178,7 @@ def test_the_launch_split_changes_nothing(scenes, name, precision, monkeypatch):
 @pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("name", NAMES)
 def test_sample_ranges(scenes, name, precision, kernel, monkeypatch):
-    _kernel(monkeypatch, kernel)
+    use_kernel(monkeypatch, kernel)
     win = WINDOWS[0]
     lin, rgba, _, _ = _frame(scenes, name, precision, kernel, sample_begin=32)
     sc, cam, p = _params(scenes, name, precision, sample_begin=32)

@@ -4,23 +4,15 @@ on a scene that was never committed, and on no scene at all — in the order the
 field; and the command line refuses --preview where it means nothing, before any scene is built.  (tests/test_gpu_reconstruct.py and
 tests/test_gpu_preview.py have what the device computes.)"""
 import ctypes as C
-import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from abi_cases import FFI, HEADER, HEADER_TEXT, INVALID, RUST_SCENE, STATE, UNSUPPORTED, camera, cli_refuses, declared_alike, exported, refused
+from abi_cases import adaptive as _adaptive, params as _params
 from rttnw_amd import abi, library, render
 from rttnw_amd import scene as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER_TEXT = open(os.path.join(ROOT, "include", "rttnw_hip.h")).read()
-HEADER = re.sub(r"/\*.*?\*/", "", HEADER_TEXT, flags=re.S)
-FFI = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")).read())
-RUST_SCENE = open(os.path.join(ROOT, "bindings", "rust", "src", "scene.rs")).read()
-INVALID, STATE, UNSUPPORTED = -1, -2, -3
 
 # the argument lists, once: (name, C type, Rust type, ctypes type)
 _D, _U8, _U32 = ("double*", "*mut f64", C.c_void_p), ("uint8_t*", "*mut u8", C.c_void_p), ("uint32_t*", "*mut u32", C.c_void_p)
@@ -43,23 +35,8 @@ ARGS = {
 
 @pytest.mark.parametrize("name", ["reconstruct", "render_preview"])
 def test_export_and_declarations(name):
-    args = ARGS[name]
-    lib = C.CDLL(library.HIP_LIB)
-    assert hasattr(lib, "rttnw_" + name) and "rttnw_" + name in abi.exported_symbols()
-    m = re.search(r"\bint rttnw_%s\((.*?)\);" % name, HEADER, flags=re.S)
-    assert m, "include/rttnw_hip.h does not declare rttnw_%s" % name
-    c_args = []
-    for a in " ".join(m.group(1).split()).split(","):
-        ctype, arg = re.match(r"(.+?)\s*(\w+)$", a.strip()).groups()
-        c_args.append((arg, ctype.replace(" *", "*")))
-    assert c_args == [(n, c) for n, c, _, _ in args]
-    m = re.search(r"pub fn rttnw_%s\((.*?)\)\s*->\s*c_int;" % name, FFI, flags=re.S)
-    assert m, "bindings/rust/src/ffi.rs does not declare rttnw_%s" % name
-    assert [tuple(x.strip() for x in a.split(":", 1)) for a in m.group(1).split(",") if ":" in a] == [(n, r) for n, _, r, _ in args]
-    proto = {n: (res, a) for n, res, a in abi.PRODUCT_FUNCS}[name]
-    assert proto[0] is C.c_int and list(proto[1]) == [t for _, _, _, t in args]
-    assert re.search(r"#define RTTNW_ABI_VERSION 3\b", HEADER)      # no version bump: the symbol is how a caller finds the feature
-    assert lib.rttnw_abi_version() == 3 and abi.ABI_VERSION == 3
+    exported(name)
+    declared_alike(name, ARGS[name])
     assert "rttnw_" + name in HEADER_TEXT.split("typedef struct rttnw_scene")[0], "the comment at RTTNW_ABI_VERSION says how a caller detects the function"
     assert "pub fn %s(" % name in RUST_SCENE, "the crate's safe wrapper"
 
@@ -146,24 +123,6 @@ def test_reconstruct_refusals_come_in_rttnw_denoise_order():
 # ---------------------------------------------------------------- rttnw_render_preview's refusals
 
 NAME = "render_preview"
-W, H = 16, 16
-CAM = dict(lookfrom=(0, 0, 5), lookat=(0, 0, 0), vfov=40.0, aspect=1.0)
-
-
-def _params(**kw):
-    p = S.make_params(kw.pop("width", W), kw.pop("height", H), kw.pop("spp", 128))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def _adaptive(**kw):
-    a = abi.Adaptive(pass_spp=64, reserved0=0, rel_error=0.05, abs_error=0.0)
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
-
-
 def _preview(**kw):
     v = abi.Preview(level=2, feature_spp=0, denoise=abi.Denoise(iterations=5, reserved0=0, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0))
     for k, val in kw.items():
@@ -175,7 +134,7 @@ def _preview(**kw):
 
 
 def _call(b, sc, p, a, v, scene=True):
-    cam = S.camera_desc(**CAM)
+    cam = camera()
     return b.render_preview(sc.handle if scene else None, C.byref(cam), C.byref(p) if p is not None else None, C.byref(a) if a is not None else None,
                             C.byref(v) if v is not None else None, None, None, None, None, None, None, None, None)
 
@@ -212,16 +171,7 @@ def test_preview_refusals_come_before_the_device(what, kw, adapt, prev, code, ms
     p = None if kw is None else _params(**kw)
     a = None if adapt is None else _adaptive(**adapt)
     v = None if prev is None else _preview(**prev)
-    if code is None:
-        # validate() looks at the scene before the sizes: "not committed" on a scene, "NULL" without one — in either case before any device
-        assert _call(b, sc, p, a, v) == STATE and "not committed" in b.last_error().decode(), what
-        assert _call(b, sc, p, a, v, scene=False) == INVALID and "NULL" in b.last_error().decode(), what
-        return
-    assert _call(b, sc, p, a, v) == code, what
-    err = b.last_error().decode()
-    assert err and msg in err and NAME in err, (what, err)
-    assert _call(b, sc, p, a, v, scene=False) == code, what      # ... nor any scene at all
-    assert msg in b.last_error().decode(), what
+    refused(b, lambda scene: _call(b, sc, p, a, v, scene=scene), code, msg, NAME)
 
 
 def test_valid_preview_arguments_reach_validate():
@@ -274,9 +224,4 @@ def test_preview_refusals_come_in_the_stated_order():
     (["7", "--noise", "0.1", "--preview", "2", "--denoise-iterations", "9"], "--denoise-iterations must be 0 .. 8"),
 ])
 def test_cli_refuses_before_any_scene_is_built(argv, msg, tmp_path):
-    out = tmp_path / "image.png"
-    r = subprocess.run([sys.executable, "-m", "rttnw_amd"] + argv + ["--out", str(out), "--save-state", str(tmp_path / "saved.npy")], cwd=tmp_path,
-                       capture_output=True, text=True, env=dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", "")))
-    assert r.returncode == 1
-    assert msg in r.stderr, r.stderr
-    assert "Scene number" not in r.stdout and not out.exists() and not (tmp_path / "saved.npy").exists()
+    cli_refuses(argv + ["--save-state", str(tmp_path / "saved.npy")], msg, tmp_path, must_not_exist=("saved.npy",))

@@ -2,20 +2,12 @@
 every argument refusal comes before the device is touched and in the order the header states, and the command line refuses a malformed
 --window and its combination with --denoise before any render."""
 import ctypes as C
-import os
-import re
-import subprocess
-import sys
 
 import pytest
 
+from abi_cases import HEADER_TEXT, INVALID, STATE, UNSUPPORTED, camera, cli_refuses, declared_alike, exported, params
 from rttnw_amd import abi, library
 from rttnw_amd import scene as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rttnw_hip.h")).read(), flags=re.S)
-FFI = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")).read())
-INVALID, STATE, UNSUPPORTED = -1, -2, -3
 
 # the argument list, once: (name, C type, Rust type, ctypes type)
 ARGS = [("s", "rttnw_scene*", "*mut rttnw_scene", abi.scene_p),
@@ -29,37 +21,20 @@ ARGS = [("s", "rttnw_scene*", "*mut rttnw_scene", abi.scene_p),
 
 
 def test_export_and_declarations():
-    lib = C.CDLL(library.HIP_LIB)
-    assert hasattr(lib, "rttnw_render_region")
-    assert "rttnw_render_region" in abi.exported_symbols()
-    m = re.search(r"\bint rttnw_render_region\((.*?)\);", HEADER, flags=re.S)
-    assert m, "include/rttnw_hip.h does not declare rttnw_render_region"
-    c_args = []
-    for a in " ".join(m.group(1).split()).split(","):
-        ctype, name = re.match(r"(.+?)\s*(\w+)$", a.strip()).groups()
-        c_args.append((name, ctype.replace(" *", "*")))
-    assert c_args == [(n, c) for n, c, _, _ in ARGS]
-    m = re.search(r"pub fn rttnw_render_region\((.*?)\)\s*->\s*c_int;", FFI, flags=re.S)
-    assert m, "bindings/rust/src/ffi.rs does not declare rttnw_render_region"
-    rs_args = [tuple(x.strip() for x in a.split(":", 1)) for a in m.group(1).split(",") if ":" in a]
-    assert rs_args == [(n, r) for n, _, r, _ in ARGS]
-    proto = {n: (res, args) for n, res, args in abi.PRODUCT_FUNCS}["render_region"]
-    assert proto[0] is C.c_int and list(proto[1]) == [t for _, _, _, t in ARGS]
-    assert re.search(r"#define RTTNW_ABI_VERSION 3\b", HEADER)      # no version bump: the symbol is how a caller finds the feature
-    assert "rttnw_render_region" in open(os.path.join(ROOT, "include", "rttnw_hip.h")).read().split("typedef struct rttnw_scene")[0], \
+    exported("render_region")
+    declared_alike("render_region", ARGS)
+    assert "rttnw_render_region" in HEADER_TEXT.split("typedef struct rttnw_scene")[0], \
         "the comment at RTTNW_ABI_VERSION says how a caller detects the function"
 
 
 def _region(b, sc, p, window=(2, 3, 10, 12), scene=True):
-    cam = S.camera_desc((0, 0, 5), (0, 0, 0), 40.0, 1.0)
+    cam = camera()
     return b.render_region(sc.handle if scene else None, C.byref(cam), C.byref(p) if p is not None else None, *window, None, None, None, None)
 
 
 def _params(**kw):
-    p = S.make_params(16, 16, 4)
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    kw.setdefault("spp", 4)
+    return params(**kw)
 
 
 @pytest.mark.parametrize("what,window,kw,code,msg", [
@@ -115,8 +90,4 @@ def test_refusals_come_in_the_stated_order():
     (["7", "--window", "0,0,8,8", "--passes", "2"], "--window does not combine with --passes"),
 ])
 def test_cli_refuses_before_any_render(argv, msg, tmp_path):
-    out = tmp_path / "image.png"
-    r = subprocess.run([sys.executable, "-m", "rttnw_amd"] + argv + ["--out", str(out)], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode != 0
-    assert msg in r.stderr, r.stderr
-    assert "Scene number" not in r.stdout and not out.exists()          # refused before the scene was even built
+    cli_refuses(argv, msg, tmp_path)          # refused before the scene was even built

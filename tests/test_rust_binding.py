@@ -8,15 +8,10 @@ import ctypes as C
 import os
 import re
 
+from abi_cases import HEADER_TEXT as HEADER, ROOT, strip_c_comments as strip_c
 from rttnw_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "rttnw_hip.h")).read()
 FFI = open(os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")).read()
-
-
-def strip_c(text):
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
 
 
 def strip_rs(text):
