@@ -235,6 +235,7 @@ extern "C" {
     pub fn rttnw_render_preview(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, v: *const rttnw_preview, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_valid: *mut u8, out_spp: *mut u32, out_raw_linear_rgb: *mut f64, out_raw_stderr_rgb: *mut f64, state_out: *mut f64, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_budget_select(width: u32, height: u32, linear_rgb: *const f64, stderr_rgb: *const f64, spp: *const u32, cap: u32, rel_error: f64, abs_error: f64, max_pixels: u64, out_mask: *mut u8, out_priority: *mut f64, out_selected: *mut u64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_render_adaptive_budget(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, b: *const rttnw_budget, state_in: *const f64, state_out: *mut f64, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_spp: *mut u32, out_stderr_rgb: *mut f64, stats: *mut rttnw_stats) -> c_int;
+    pub fn rttnw_render_adaptive_budget_denoised(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, b: *const rttnw_budget, g: *const rttnw_guided, state_in: *const f64, state_out: *mut f64, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_valid: *mut u8, out_spp: *mut u32, out_stderr_rgb: *mut f64, out_raw_linear_rgb: *mut f64, out_raw_stderr_rgb: *mut f64, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_render_tiles_device(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, d_packed: *mut c_void, hip_stream: *mut c_void, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_untile_device(width: u32, height: u32, world: u32, precision: u32, d_gathered: *const c_void, d_linear_rgb: *mut c_void, d_rgba8: *mut u8, hip_stream: *mut c_void) -> c_int;
     // ---- introspection

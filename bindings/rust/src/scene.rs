@@ -259,6 +259,26 @@ impl Scene {
         let rounds = stats.reserved >> 16;
         Ok((rgba, spp, stderr, stats, out, rounds))
     }
+    /// The budgeted render ranked by the noise of the FILTERED image (`rttnw_render_adaptive_budget_denoised`): `render_adaptive_budget`'s rounds,
+    /// each of which runs `reconstruct`'s passes on the device and ranks pixels on the filtered image and sqrt of the filtered variance, begun
+    /// from `state` (`None`: all zeros), on one GPU.  Returns (the filtered image as RGBA8, the byte per pixel that says whether it holds a value,
+    /// samples per pixel, sqrt of the filtered variance, stats, the state, the rounds run).
+    pub fn render_adaptive_budget_denoised(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params, a: &ffi::rttnw_adaptive, b: &ffi::rttnw_budget, g: &ffi::rttnw_guided, state: Option<&[f64]>) -> Result<(Vec<u8>, Vec<u8>, Vec<u32>, Vec<f64>, ffi::rttnw_stats, Vec<f64>, u32)> {
+        let n = p.width as usize * p.height as usize;
+        let doubles = unsafe { ffi::rttnw_adaptive_state_doubles(p.width, p.height) } as usize;
+        if state.map_or(false, |s| s.len() != doubles) {
+            return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "render_adaptive_budget_denoised: the state does not have the frame's size".into() });
+        }
+        let mut rgba = vec![0u8; n * 4];
+        let mut valid = vec![0u8; n];
+        let mut spp = vec![0u32; n];
+        let mut stderr = vec![0f64; n * 3];
+        let mut stats = ffi::rttnw_stats::default();
+        let mut out = vec![0f64; doubles];
+        ok(unsafe { ffi::rttnw_render_adaptive_budget_denoised(self.raw, cam, p, a, b, g, state.map_or(ptr::null(), |s| s.as_ptr()), out.as_mut_ptr(), ptr::null_mut(), rgba.as_mut_ptr(), valid.as_mut_ptr(), spp.as_mut_ptr(), stderr.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), &mut stats) })?;
+        let rounds = stats.reserved >> 16;
+        Ok((rgba, valid, spp, stderr, stats, out, rounds))
+    }
     /// First-hit feature buffers of the frame `render` renders (`rttnw_render_features`), row-major, top row first.
     pub fn render_features(&self, cam: &ffi::rttnw_camera_desc, p: &ffi::rttnw_params) -> Result<Features> {
         let n = p.width as usize * p.height as usize;

@@ -42,8 +42,9 @@ extern "C" {
                              *    (below), validate() rejects t_min < 0
                              * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region, rttnw_render_adaptive_multi,
                              *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region,
-                             *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select and
-                             *  rttnw_render_adaptive_budget came later, without a version bump: a caller detects each by its symbol) */
+                             *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select,
+                             *  rttnw_render_adaptive_budget and rttnw_render_adaptive_budget_denoised came later, without a version bump: a
+                             *  caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -725,7 +726,8 @@ int rttnw_budget_select(uint32_t width, uint32_t height, const double* linear_rg
  *   3. RTTNW_ERR_INVALID for b->reserved0 != 0, then for rel_error == abs_error == 0;
  *   4. with a state_in, the state checks of rttnw_render_adaptive_region (a record of zeros is accepted);
  *   5. whatever rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes).
- * Out of scope: a node-wide form (ngpu), windows and masks, and ranking by the filtered error of rttnw_render_adaptive_denoised. */
+ * Out of scope: a node-wide form (ngpu), windows and masks, and ranking by the filtered error of rttnw_render_adaptive_denoised (that is
+ *   rttnw_render_adaptive_budget_denoised, below). */
 struct rttnw_budget {
     uint64_t samples;      /* the most camera paths THIS call may trace */
     uint32_t round_pixels; /* the most pixels one round refines; 0 = ceil(width * height / 2) */
@@ -735,6 +737,63 @@ typedef struct rttnw_budget rttnw_budget;
 int rttnw_render_adaptive_budget(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
                                  const rttnw_budget* b, const double* state_in, double* state_out, double* out_linear_rgb,
                                  uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, rttnw_stats* stats);
+
+/* The budgeted render ranked by the noise of the FILTERED image: rttnw_render_adaptive_budget keeps sampling smooth walls the denoiser would have
+ * cleaned for free, rttnw_render_adaptive_denoised has a noise target and no budget; this one spends at most b->samples camera paths where the
+ * denoised image is worst.  One GPU, the whole frame, tile_world == 1, blocking.  rttnw_budget and rttnw_guided are reused as they are.  (Came
+ * without a version bump: detect it by its symbol.)
+ *
+ * Let B = a->pass_spp and the cap = p->spp, a positive multiple of B.  The state is rttnw_render_adaptive_region's: frame-sized, a record of twelve
+ * zeros means "no samples yet"; state_in == NULL stands for all zeros; state_in and state_out may be the same array.  No "stopped" flag survives a
+ * round — candidates are recomputed from the maps each round —, which is why a state_in is possible here and not in rttnw_render_adaptive_denoised.
+ * Before round 0.  The features F of the frame are rttnw_render_features' with p->spp replaced by g->feature_spp (0 means B), as in
+ *   rttnw_render_adaptive_denoised.  remaining = b->samples.
+ * Round r = 0, 1, ...:
+ *   1. Raw maps of EVERY pixel from the running state: mean = sum / n_q in the kernel's type, widened to double; se, the standard error as
+ *      rttnw_render_adaptive defines it (+inf with fewer than two chunks); spp = n_q; valid = (spp > 0); variance = se * se in double, not fused.  A
+ *      pixel without samples reports zeros.
+ *   2. Filter.  (den, var_f, H) = rttnw_reconstruct's out_linear_rgb, out_variance_rgb and out_valid on (mean, variance, valid, F, g->denoise), bit
+ *      for bit.  (With every pixel valid that is rttnw_denoise, by that entry point's contract.)
+ *   3. Rank.  se_f = sqrt(var_f).  spp' = the cap for a pixel with spp > 0 whose OWN se is 0 in r, g and b — the "own stderr is 0" stop of
+ *      rttnw_render_adaptive_denoised: such a pixel has nothing to gain, whatever leaks in from its neighbours —, spp' = spp otherwise.  Then
+ *      rttnw_budget_select(den, se_f, spp', cap, rel_error, abs_error, max_pixels = min(round_pixels, remaining / B)) (integer division), its rules
+ *      unchanged: a pixel with spp == 0 ranks +inf and its colour is never read, a quotient that is not a finite positive number ranks +inf, ties
+ *      go by row-major index.
+ *   4. End or trace.  When that selects nothing the call ends.  Otherwise each selected pixel q gets its next pass, at level n_q / B — one list pass
+ *      per occupied level, in ascending order, exactly as in rttnw_render_adaptive_budget — and remaining -= m * B.
+ *   The filter therefore runs once more than the number of rounds, and once even when there is no work.
+ * Outputs, of the last filter that ran — the one whose selection was empty (each optional; row-major, top row first): out_linear_rgb w*h*3,
+ *   out_rgba8 w*h*4 and out_valid w*h bytes are rttnw_reconstruct's, alpha 0 where out_valid is 0; out_stderr_rgb w*h*3 is se_f, +inf where
+ *   out_valid is 0; out_raw_linear_rgb, out_raw_stderr_rgb w*h*3 and out_spp w*h are the raw maps of step 1; state_out,
+ *   rttnw_adaptive_state_doubles(w, h) doubles: the ordinary adaptive state.  `stats`: samples = what THIS call traced, at most b->samples, and
+ *   more than b->samples - B unless no candidate was left; kernel_ms = device time of everything the call runs — the feature pass, every filter,
+ *   every selection and the state's copies included; the scene's sizes as usual; reserved = the kernel form in its low bits as usual and, in bits
+ *   16 .. 31, the rounds that traced something (saturating at 65535), as in rttnw_render_adaptive_budget.
+ * Contract.  For every `precision`, kernel form and launch split (RTTNW_CHUNK_SUM_BUDGET) all outputs and state_out are BIT-IDENTICAL to the host
+ *   composition of steps 1 - 4 from entry points above: rttnw_render_features; rttnw_reconstruct; the selection restated on the host; and per
+ *   occupied level k, ascending, rttnw_render_adaptive_region(window = the whole frame, mask = this round's pixels at level k, ngpu = 0, cap (k+1)B,
+ *   rel_error = abs_error = 0, state_in = the running state), the records above that cap set aside and put back as rttnw_render_adaptive_budget's
+ *   comment describes; the raw maps of step 1 are that entry point's image, standard errors and samples over the whole frame.
+ *   With g->denoise.iterations == 0 the filter is the identity and sqrt(se * se) == se in IEEE double away from underflow: out_spp, state_out,
+ *   the rounds, the samples and the raw maps are rttnw_render_adaptive_budget's under the same arguments, and out_linear_rgb equals the raw image.
+ *   NOT promised: that two calls of N1 and N2 samples equal one call of N1 + N2 (as in rttnw_render_adaptive_budget), or equality with
+ *   rttnw_render_adaptive_denoised (whose stops are sticky).
+ * Where it lives.  Between rounds nothing frame-sized crosses to the host: per round the host reads the budgeted form's one small record in one
+ *   copy (the number selected, then the list length per level, 1 + cap / B words).
+ * No work.  b->samples < B, or no candidate: RTTNW_OK, no trace kernel is launched, stats->samples == 0, the outputs are the filter of the incoming
+ *   state — with no state that is rttnw_reconstruct of nothing: only the background fill of the pixels with alpha == 0.
+ * Refusals, before the device is touched, in this order, each message naming render_adaptive_budget_denoised and the field:
+ *   1. RTTNW_ERR_INVALID for a NULL p, a, b or g;
+ *   2. what rttnw_render_adaptive refuses among its own arguments, with its codes;
+ *   3. RTTNW_ERR_INVALID for b->reserved0 != 0, then for rel_error == abs_error == 0;
+ *   4. RTTNW_ERR_INVALID for g->reserved0 != 0, g->denoise.iterations > 8, g->denoise.reserved0 != 0, a negative or NaN sigma, in this order;
+ *   5. with a state_in, the state checks of rttnw_render_adaptive_region (a record of zeros is accepted);
+ *   6. whatever rttnw_render refuses (NULL scene / camera, a scene not committed, bad sizes).
+ * Out of scope: a node-wide form (ngpu), and windows and masks. */
+int rttnw_render_adaptive_budget_denoised(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
+                                          const rttnw_budget* b, const rttnw_guided* g, const double* state_in, double* state_out,
+                                          double* out_linear_rgb, uint8_t* out_rgba8, uint8_t* out_valid, uint32_t* out_spp,
+                                          double* out_stderr_rgb, double* out_raw_linear_rgb, double* out_raw_stderr_rgb, rttnw_stats* stats);
 
 /* Device-resident form, asynchronous on `hip_stream` (a hipStream_t; NULL = default stream).
  * Traces the tiles owned by (tile_rank, tile_world) and writes them in packed order into

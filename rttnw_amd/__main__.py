@@ -30,6 +30,11 @@ a sample.  It does not combine with --devices, --resume, --refine, --guided, --w
 rounds that give one more pass to the pixels furthest above the noise bound, --spp being the cap; pixels the budget never reached stay black.  It
 works with --resume, --save-state and --spp-map, prints the samples traced and the rounds run, and does not combine with --preview, --guided,
 --refine, --devices, --window or --passes.
+--guided-budget SAMPLES (with --noise only) is --budget ranked by the noise of the FILTERED image (rttnw_render_adaptive_budget_denoised): each round
+filters the frame on the device and gives one more pass to the pixels whose filtered value stands furthest above the noise bound; the image
+written is the filtered one, --denoise-iterations sets its passes, and a pixel nothing could be filled into stays transparent.  It works with
+--resume, --save-state and --spp-map, prints the samples traced and the rounds run, and does not combine with --budget, --guided, --preview,
+--refine, --devices, --window or --passes.
 """
 import argparse
 import sys
@@ -80,7 +85,8 @@ WANTS_WINDOW = "%s wants X0,Y0,X1,Y1: four non-negative integers with X0 < X1 an
 
 def refusal(args, refine, devices, window):
     """The first rule the flags break, as the line for stderr, or None.  `refine`, `devices` and `window` are the parsed values, None where malformed."""
-    on = {"--noise": args.noise is not None, "--budget": args.budget is not None, "--preview": args.preview is not None, "--guided": args.guided,
+    on = {"--noise": args.noise is not None, "--guided-budget": args.guided_budget is not None, "--budget": args.budget is not None,
+          "--preview": args.preview is not None, "--guided": args.guided,
           "--refine": args.refine is not None, "--devices": args.devices is not None, "--resume": args.resume is not None,
           "--save-state": args.save_state is not None, "--window": args.window is not None, "--passes": args.passes > 1,
           "--features": args.features is not None, "--denoise": args.denoise}
@@ -88,11 +94,17 @@ def refusal(args, refine, devices, window):
     state_needs, state_clashes = "only the adaptive render has a state", ("--window", "--passes")
     # in the order they are checked: (flag, why it needs --noise or None, the flags it does not combine with, the reason given for that,
     # [(holds, the message if not)] checked before all that, the same checked after it)
+    noise_above_0 = "%s needs a noise bound above 0 to rank pixels by (--noise or --abs-noise)"
     rules = [
+        ("--guided-budget", "it is the adaptive render under a budget of samples, ranked by the filtered image's noise",
+         ("--budget", "--guided", "--preview", "--refine", "--devices", "--window", "--passes"),
+         ": it runs on one GPU, over the whole frame, on the filtered noise", [],
+         [(not on["--guided-budget"] or args.guided_budget >= 0, "--guided-budget must be at least 0"),
+          ((args.noise or 0.0) > 0.0 or args.abs_noise > 0.0, noise_above_0 % "--guided-budget"), iterations]),
         ("--budget", "it is the adaptive render under a budget of samples", ("--preview", "--guided", "--refine", "--devices", "--window", "--passes"),
          ": it runs on one GPU, over the whole frame, on the raw noise", [],
          [(not on["--budget"] or args.budget >= 0, "--budget must be at least 0"),
-          ((args.noise or 0.0) > 0.0 or args.abs_noise > 0.0, "--budget needs a noise bound above 0 to rank pixels by (--noise or --abs-noise)")]),
+          ((args.noise or 0.0) > 0.0 or args.abs_noise > 0.0, noise_above_0 % "--budget")]),
         ("--preview", "it is the adaptive render of a lattice of the frame, reconstructed",
          ("--devices", "--resume", "--refine", "--guided", "--window", "--passes"), ": it runs on one GPU, over the whole frame, from nothing", [],
          [(not on["--preview"] or 0 <= args.preview <= 6, "--preview must be 0 .. 6"), iterations]),
@@ -154,6 +166,8 @@ def main(argv=None):
                     "L = 0 .. 6) and reconstruct the frame from them (rttnw_render_preview); writes the reconstruction")
     ap.add_argument("--budget", type=int, default=None, metavar="SAMPLES", help="adaptive sampling: trace at most SAMPLES camera paths, the noisiest "
                     "pixels first (rttnw_render_adaptive_budget)")
+    ap.add_argument("--guided-budget", type=int, default=None, metavar="SAMPLES", help="adaptive sampling: trace at most SAMPLES camera paths, the "
+                    "pixels whose DENOISED value is noisiest first (rttnw_render_adaptive_budget_denoised); writes the filtered image")
     ap.add_argument("--features", default=None, metavar="PREFIX", help="write the first-hit feature buffers as PREFIX_albedo.png, "
                     "PREFIX_normal.png, PREFIX_depth.png, PREFIX_alpha.png")
     ap.add_argument("--window", default=None, metavar="X0,Y0,X1,Y1", help="render pixels [X0, X1) x [Y0, Y1) of the frame only (row 0 = top) "
@@ -208,7 +222,8 @@ def main(argv=None):
               % (time.time() - t0, x1 - x0, y1 - y0, x0, y0, w, h, st.samples, st.kernel_ms))
         return 0
     features = None
-    if (args.denoise and not args.guided and args.preview is None) or args.features:
+    own_filter = args.guided or args.preview is not None or args.guided_budget is not None   # the call's own image is the filtered one
+    if (args.denoise and not own_filter) or args.features:
         if args.denoise and args.passes > 1:
             print("--denoise does not combine with --passes", file=sys.stderr)
             return 1
@@ -228,7 +243,7 @@ def main(argv=None):
 
     def finish(linear, rgba, stderr):
         """The image as it is written: denoised when asked for."""
-        if not args.denoise or args.guided or args.preview is not None:   # (--guided, --preview: the call's own image is the filtered one)
+        if not args.denoise or own_filter:
             return np.ascontiguousarray(rgba)
         _, out, _, ms = render.denoise(linear, features, stderr, iterations=args.denoise_iterations, want_ms=True)
         print("denoised: %d iterations, %.2f ms" % (args.denoise_iterations, ms))
@@ -263,6 +278,13 @@ def main(argv=None):
             lin, rgba, spp_map, se, st, state = g["linear"], g["rgba8"], g["spp"], g["raw_stderr"], g["stats"], g["state"]
             rounds = "; preview: 1 pixel in %d, %d of %d pixels hold a value, %d denoise iterations" % (4 ** args.preview, int(g["valid"].sum()), w * h,
                                                                                                       args.denoise_iterations)
+        elif args.guided_budget is not None:
+            g = render.render_adaptive_budget_denoised(sc, cam, p, args.guided_budget, state=state, pass_spp=args.pass_spp, rel_error=args.noise,
+                                                       abs_error=args.abs_noise, iterations=args.denoise_iterations,
+                                                       want_state=args.save_state is not None)
+            lin, rgba, spp_map, se, st, state = g["linear"], g["rgba8"], g["spp"], g["stderr"], g["stats"], g["state"]
+            rounds = "; guided budget: %d of %d samples in %d rounds, %d of %d pixels hold samples, %d denoise iterations each" % (
+                st.samples, args.guided_budget, g["rounds"], int((spp_map > 0).sum()), w * h, args.denoise_iterations)
         elif args.budget is not None:
             lin, rgba, spp_map, se, st, state, n_rounds = render.render_adaptive_budget(sc, cam, p, args.budget, state=state, pass_spp=args.pass_spp,
                                                                                        rel_error=args.noise, abs_error=args.abs_noise,

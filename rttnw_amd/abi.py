@@ -61,7 +61,8 @@ class Denoise(C.Structure):
 
 
 class Guided(C.Structure):
-    """`rttnw_guided` — what `rttnw_render_adaptive_denoised` takes beside the stopping rule: the features' samples and the filter."""
+    """`rttnw_guided` — what `rttnw_render_adaptive_denoised` and `rttnw_render_adaptive_budget_denoised` take beside the stopping rule: the
+    features' samples and the filter."""
     _fields_ = [("feature_spp", C.c_uint32), ("reserved0", C.c_uint32), ("denoise", Denoise)]
 
 
@@ -150,6 +151,9 @@ PRODUCT_FUNCS = [
                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     ("render_adaptive_budget", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Budget), C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    ("render_adaptive_budget_denoised", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Budget),
+                                                  C.POINTER(Guided), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("render_tiles_device", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.c_void_p,
                                       C.c_void_p, C.POINTER(Stats)]),
     ("untile_device", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

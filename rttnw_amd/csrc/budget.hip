@@ -1,7 +1,8 @@
-// budget.hip — the device half of rttnw_budget_select and of the rounds of rttnw_render_adaptive_budget (budget.hpp): the launch code of
-// budget_kernels.hpp.  One translation unit for every precision, double only, built without -ffp-contract=fast like guided.hip and denoise.hip.
+// budget.hip — the device half of rttnw_budget_select and of the rounds of rttnw_render_adaptive_budget and rttnw_render_adaptive_budget_denoised
+// (budget.hpp): the launch code of budget_kernels.hpp and guided_budget_kernels.hpp.  One translation unit for every precision, double only, built without -ffp-contract=fast like guided.hip and denoise.hip.
 #include "budget.hpp"
 #include "budget_kernels.hpp"
+#include "guided_budget_kernels.hpp"
 
 namespace rt {
 
@@ -28,6 +29,23 @@ static void budget_select_launch(const BudgetWorkspace& w, uint64_t max_pixels, 
     }
 }
 
+// What a round runs behind its keys (w.key_hi, row-major): the select of min(candidates, max_pixels) of them, the selection byte of every pixel of
+// the image at its packed place, and the round's record
+int budget_keys_round_launch(const BudgetWorkspace& w, const void* d_state, uint32_t width, uint32_t height, uint32_t cap, uint32_t pass_spp,
+                             uint64_t max_pixels, uint8_t* d_select, uint32_t* d_record, hipStream_t stream) {
+    rttnw_tile_layout L;
+    fill_layout(width, height, 1, L);
+    budget_select_launch(w, max_pixels, stream);
+    const BudgetSelectState* st = (const BudgetSelectState*)w.st.p;
+    hipLaunchKernelGGL(budget_mask_kernel, budget_grid(w.n), dim3(BUDGET_BLOCK), 0, stream, w.n, w.key_hi.p, st, width, L.tiles_x, d_select);
+    const uint32_t n_blocks = L.n_tiles * 16u, n_levels = cap / pass_spp;
+    HIP_TRY(hipMemsetAsync(d_record, 0, (1u + size_t(n_levels)) * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(budget_census_kernel, dim3((n_blocks + BUDGET_BLOCK - 1u) / BUDGET_BLOCK), dim3(BUDGET_BLOCK), 0, stream, d_select,
+                       (const AdaptivePixel*)d_state, n_blocks, pass_spp, n_levels, st, d_record);
+    HIP_TRY(hipGetLastError());
+    return RTTNW_OK;
+}
+
 int budget_round_launch(const BudgetWorkspace& w, uint32_t precision, const void* d_means, const double* d_aux, const void* d_state, uint32_t width,
                         uint32_t height, uint32_t cap, uint32_t pass_spp, double rel_error, double abs_error, uint64_t max_pixels, uint8_t* d_select,
                         uint32_t* d_record, hipStream_t stream) {
@@ -40,13 +58,28 @@ int budget_round_launch(const BudgetWorkspace& w, uint32_t precision, const void
     else
         hipLaunchKernelGGL(budget_keys_packed_kernel<double>, grid, block, 0, stream, (const double*)d_means, d_aux, width, height, L.tiles_x, cap, rel_error,
                            abs_error, w.key_hi.p);
-    budget_select_launch(w, max_pixels, stream);
-    const BudgetSelectState* st = (const BudgetSelectState*)w.st.p;
-    hipLaunchKernelGGL(budget_mask_kernel, budget_grid(w.n), dim3(BUDGET_BLOCK), 0, stream, w.n, w.key_hi.p, st, width, L.tiles_x, d_select);
-    const uint32_t n_blocks = L.n_tiles * 16u, n_levels = cap / pass_spp;
-    HIP_TRY(hipMemsetAsync(d_record, 0, (1u + size_t(n_levels)) * sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(budget_census_kernel, dim3((n_blocks + BUDGET_BLOCK - 1u) / BUDGET_BLOCK), dim3(BUDGET_BLOCK), 0, stream, d_select,
-                       (const AdaptivePixel*)d_state, n_blocks, pass_spp, n_levels, st, d_record);
+    return budget_keys_round_launch(w, d_state, width, height, cap, pass_spp, max_pixels, d_select, d_record, stream);
+}
+
+int guided_budget_raw_launch(uint32_t precision, const void* d_means, const double* d_aux, double* d_mean, double* d_variance, double* d_raw_stderr,
+                             uint32_t* d_spp, uint8_t* d_valid, uint32_t width, uint32_t height, hipStream_t stream) {
+    rttnw_tile_layout L;
+    fill_layout(width, height, 1, L);
+    const dim3 block(32, 8), grid((width + 31) / 32, (height + 7) / 8);
+    if (precision == RTTNW_F32)
+        hipLaunchKernelGGL(guided_budget_raw_kernel<float>, grid, block, 0, stream, (const float*)d_means, d_aux, d_mean, d_variance, d_raw_stderr, d_spp,
+                           d_valid, width, height, L.tiles_x);
+    else
+        hipLaunchKernelGGL(guided_budget_raw_kernel<double>, grid, block, 0, stream, (const double*)d_means, d_aux, d_mean, d_variance, d_raw_stderr, d_spp,
+                           d_valid, width, height, L.tiles_x);
+    HIP_TRY(hipGetLastError());
+    return RTTNW_OK;
+}
+
+int guided_budget_rank_launch(const BudgetWorkspace& w, const double* d_den, const double* d_var_f, const double* d_raw_stderr, const uint32_t* d_spp,
+                              uint32_t cap, double rel_error, double abs_error, double* d_stderr_f, hipStream_t stream) {
+    hipLaunchKernelGGL(guided_budget_rank_kernel, budget_grid(w.n), dim3(BUDGET_BLOCK), 0, stream, w.n, d_den, d_var_f, d_raw_stderr, d_spp, cap, rel_error,
+                       abs_error, d_stderr_f, w.key_hi.p);
     HIP_TRY(hipGetLastError());
     return RTTNW_OK;
 }

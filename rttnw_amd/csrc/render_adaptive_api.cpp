@@ -1,5 +1,5 @@
 // render_adaptive_api.cpp — the adaptive family beyond rttnw_render_adaptive: the forms over the ranks of a node (multi, resume, region), the round driver
-// of the forms that run one rank on the scene's device (RankRounds) and those forms (denoised, preview, budget), and rttnw_budget_select.  Host code
+// of the forms that run one rank on the scene's device (RankRounds) and those forms (denoised, preview, budget, budget_denoised), and rttnw_budget_select.  Host code
 // only; the kernels live in render_f32.hip / render_f64.hip, denoise.hip, reconstruct.hip, guided.hip and budget.hip.
 #include "render_multi.hpp"
 #include "adaptive_state.hpp"
@@ -423,8 +423,8 @@ extern "C" int rttnw_render_adaptive_region(rttnw_scene* s, const rttnw_camera_d
 }
 
 // ---------------------------------------------------------------------------------------------
-// The adaptive forms that run ONE rank on the scene's device, on the default stream: rttnw_render_adaptive_denoised, rttnw_render_preview and
-// rttnw_render_adaptive_budget.  RankRounds owns what they share — the rank's sums and noise state in the scene's workspaces, the list pass, the raw
+// The adaptive forms that run ONE rank on the scene's device, on the default stream: rttnw_render_adaptive_denoised, rttnw_render_preview,
+// rttnw_render_adaptive_budget and rttnw_render_adaptive_budget_denoised.  RankRounds owns what they share — the rank's sums and noise state in the scene's workspaces, the list pass, the raw
 // values, the state going in and out — as steps that each form calls in its own order; what differs between the forms (who is alive, what a round
 // runs besides its trace, the clocks, the outputs) stays in the form.
 // ---------------------------------------------------------------------------------------------
@@ -737,6 +737,20 @@ extern "C" int rttnw_budget_select(uint32_t width, uint32_t height, const double
 }
 
 namespace rt {
+// What a round of either budgeted form traces once its census is on the host (census[0] pixels selected, census[1 + k] blocks listed at level k):
+// per occupied level, ascending, the level's marks out of the selection bytes, the list, and the pass over it.  Counts the round's samples.
+static int budget_round_trace(RankRounds& r, const std::vector<uint32_t>& census, uint8_t* select, uint8_t* marks) {
+    const uint32_t B = r.B, n_levels = r.p.spp / B;
+    r.samples += uint64_t(census[0]) * B;
+    for (uint32_t k = 0; k < n_levels; ++k) { // (a level's list length comes with the census: the list's own totals are not read)
+        if (census[1u + k] == 0) continue;
+        if (int rc = RT_BY_PRECISION(r.p.precision, adaptive_level_select_launch, select, r.d->ad_state.p, marks, r.n_blocks * 4u, k * B, r.stream)) return rc;
+        if (int rc = r.enqueue_list(marks)) return rc;
+        if (int rc = r.trace(k, census[1u + k], (k + 1u) * B, 0.0, 0.0)) return rc;
+    }
+    return 0;
+}
+
 static int adaptive_budget_render(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a, const rttnw_budget& bg,
                                   const double* state_in, double* state_out, double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp,
                                   double* out_stderr_rgb, rttnw_stats* stats) {
@@ -775,13 +789,7 @@ static int adaptive_budget_render(::rttnw_scene* s, const rttnw_camera_desc* cam
         if (census[0] == 0) break; // no candidate is left
         ++rounds;
         remaining -= uint64_t(census[0]) * B;
-        r.samples += uint64_t(census[0]) * B;
-        for (uint32_t k = 0; k < n_levels; ++k) { // (a level's list length comes with the census: the list's own totals are not read)
-            if (census[1u + k] == 0) continue;
-            if (int rc = RT_BY_PRECISION(p.precision, adaptive_level_select_launch, select.p, d->ad_state.p, marks.p, r.n_blocks * 4u, k * B, stream)) return rc;
-            if (int rc = r.enqueue_list(marks.p)) return rc;
-            if (int rc = r.trace(k, census[1u + k], (k + 1u) * B, 0.0, 0.0)) return rc;
-        }
+        if (int rc = budget_round_trace(r, census, select.p, marks.p)) return rc;
     }
     // the state the call ends in, and the whole frame as the windowed form reports a window (`means` and `aux` are those of that state)
     if (state_out)
@@ -824,4 +832,121 @@ extern "C" int rttnw_render_adaptive_budget(rttnw_scene* s, const rttnw_camera_d
         if (int rc = refuse_state_misuse("render_adaptive_budget", true, *p, *a, cam, state_in, first_level, err)) { set_last_error(err); return rc; }
     if (int rc = validate(s, cam, p)) return rc;
     return adaptive_budget_render(s, cam, *p, *a, *b, state_in, state_out, out_linear_rgb, out_rgba8, out_spp, out_stderr_rgb, stats);
+}
+
+// ---------------------------------------------------------------------------------------------
+// rttnw_render_adaptive_budget_denoised (include/rttnw_hip.h has the contract, DESIGN.md §10a "filter-guided budgeted form" the why): the budgeted
+// form's rounds, ranked by the noise of the FILTERED image.  One rank on the scene's device, default stream.  Before round 0 the feature maps, which
+// stay on the device.  A round: the raw maps of every pixel with their valid bytes (raw(), guided_budget_raw_launch), rttnw_reconstruct's passes over
+// them — a pixel may hold nothing yet —, the rank (sqrt of the filtered variance, and the selection's keys on the filtered maps), and from the keys on
+// the budgeted form's own round: the select, the selection bytes, the census, one list pass per occupied level (budget_round_trace).  No byte
+// survives a round — candidates are recomputed from the maps —, which is why a state can come in.  The filter that selects nothing is the call's
+// output: it runs once more than the rounds, and once when there is no work.
+// ---------------------------------------------------------------------------------------------
+namespace rt {
+static int adaptive_budget_denoised_render(::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params& p, const rttnw_adaptive& a,
+                                           const rttnw_budget& bg, const rttnw_guided& g, const double* state_in, double* state_out, double* out_linear_rgb,
+                                           uint8_t* out_rgba8, uint8_t* out_valid, uint32_t* out_spp, double* out_stderr_rgb, double* out_raw_linear_rgb,
+                                           double* out_raw_stderr_rgb, rttnw_stats* stats) {
+    RankRounds r(s, cam, p, a);
+    DeviceState* d = r.d;
+    const size_t npx = r.npx;
+    const uint32_t B = r.B, n_levels = p.spp / B;
+    const uint64_t round_pixels = bg.round_pixels ? bg.round_pixels : (uint64_t(npx) + 1u) / 2u;
+    const hipStream_t stream = r.stream;
+    // everything that allocates, before the first launch: the shared part with what a list pass over every block needs (the selection bytes are that
+    // pass's active bytes), and this call's own
+    DevBuf<uint8_t> select, marks, rgba, valid, valid_out, holds[2];
+    DevBuf<uint32_t> record, spp;
+    DevBuf<double> maps, mean, variance, raw_stderr, stderr_f, d_c[2], d_v[2];
+    BudgetWorkspace work;
+    if (int rc = r.open(select, r.n_blocks, state_in, state_out != nullptr, stats)) return rc;
+    HIP_TRY(marks.alloc(r.ppr)); HIP_TRY(record.alloc(1u + size_t(n_levels))); HIP_TRY(work.alloc(npx));
+    HIP_TRY(rgba.alloc(npx * 4)); HIP_TRY(valid.alloc(npx)); HIP_TRY(valid_out.alloc(npx)); HIP_TRY(spp.alloc(npx)); HIP_TRY(maps.alloc(npx * 8));
+    HIP_TRY(mean.alloc(npx * 3)); HIP_TRY(variance.alloc(npx * 3)); HIP_TRY(raw_stderr.alloc(npx * 3)); HIP_TRY(stderr_f.alloc(npx * 3));
+    for (int k = 0; k < 2; ++k) { HIP_TRY(d_c[k].alloc(npx * 3)); HIP_TRY(d_v[k].alloc(npx * 3)); HIP_TRY(holds[k].alloc(npx)); }
+
+    // before round 0: the feature maps (the pass times itself between d->ev0 and d->ev1 and waits for the stream), the state that came in (or zero
+    // sums and zero noise state; the import's active bytes go to `marks` and are not read), and nothing selected
+    rttnw_params pf = p;
+    pf.spp = g.feature_spp ? g.feature_spp : B;
+    if (int rc = RT_BY_PRECISION(p.precision, render_features_device_t, s, cam, &pf, maps.p, stream)) return rc;
+    float feature_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&feature_ms, d->ev0.get(), d->ev1.get()));
+    const double *m_albedo = maps.p, *m_normal = maps.p + npx * 3, *m_depth = maps.p + npx * 6, *m_alpha = maps.p + npx * 7;
+    const DenoiseParams prm = denoise_params(g.denoise.sigma_luminance, g.denoise.sigma_normal, g.denoise.sigma_depth, true);
+    double* const c[2] = {d_c[0].p, d_c[1].p};
+    double* const v[2] = {d_v[0].p, d_v[1].p};
+    uint8_t* const h[2] = {holds[0].p, holds[1].p};
+    HIP_TRY(hipEventRecord(r.ev0.get(), stream));
+    if (int rc = r.start(marks.p)) return rc;
+    HIP_TRY(hipMemsetAsync(select.p, 0, r.ppr, stream)); // (the rest of an edge tile is never selected: a round writes the bytes of the image's pixels only)
+    uint64_t remaining = bg.samples, rounds = 0;
+    std::vector<uint32_t> census(1u + size_t(n_levels));
+    int out = 0;
+    for (;;) {
+        // 1. the raw maps of every pixel, 2. the filter, 3. the rank — the call's outputs, if this round selects nothing
+        if (int rc = r.raw()) return rc;
+        if (int rc = guided_budget_raw_launch(p.precision, r.means.p, r.aux.p, mean.p, variance.p, raw_stderr.p, spp.p, valid.p, p.width, p.height, stream)) return rc;
+        if (int rc = reconstruct_passes_device(p.width, p.height, mean.p, variance.p, valid.p, m_albedo, m_normal, m_depth, m_alpha, g.denoise.iterations, prm, c,
+                                               v, h, rgba.p, valid_out.p, stream, out)) return rc;
+        if (int rc = guided_budget_rank_launch(work, c[out], v[out], raw_stderr.p, spp.p, p.spp, a.rel_error, a.abs_error, stderr_f.p, stream)) return rc;
+        const uint64_t max_pixels = std::min<uint64_t>(round_pixels, remaining / B);
+        if (max_pixels == 0) break; // the budget pays for no further pass
+        // the selection on the rank's keys, and in one copy its record: the pixels selected and, per level, the length of the list over them
+        if (int rc = budget_keys_round_launch(work, d->ad_state.p, p.width, p.height, p.spp, B, max_pixels, select.p, record.p, stream)) return rc;
+        HIP_TRY(hipMemcpy(census.data(), record.p, census.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (census[0] == 0) break; // no candidate is left
+        ++rounds;
+        remaining -= uint64_t(census[0]) * B;
+        // 4. trace
+        if (int rc = budget_round_trace(r, census, select.p, marks.p)) return rc;
+    }
+    if (state_out)
+        if (int rc = r.export_state()) return rc;
+    HIP_TRY(hipEventRecord(r.ev1.get(), stream));
+    HIP_TRY(hipDeviceSynchronize());
+    if (stats) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, r.ev0.get(), r.ev1.get()));
+        stats->kernel_ms = double(feature_ms) + double(ms);
+        stats->samples = r.samples;
+        stats->reserved |= uint32_t(std::min<uint64_t>(rounds, 0xFFFFu)) << 16;
+    }
+    // the outputs of the last filter that ran
+    if (out_linear_rgb) HIP_TRY(hipMemcpy(out_linear_rgb, c[out], npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, rgba.p, npx * 4, hipMemcpyDeviceToHost));
+    if (out_valid) HIP_TRY(hipMemcpy(out_valid, valid_out.p, npx, hipMemcpyDeviceToHost));
+    if (out_spp) HIP_TRY(hipMemcpy(out_spp, spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_stderr_rgb) HIP_TRY(hipMemcpy(out_stderr_rgb, stderr_f.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_raw_linear_rgb) HIP_TRY(hipMemcpy(out_raw_linear_rgb, mean.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_raw_stderr_rgb) HIP_TRY(hipMemcpy(out_raw_stderr_rgb, raw_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return state_out ? r.state_out(state_out) : RTTNW_OK;
+}
+} // namespace rt
+
+extern "C" int rttnw_render_adaptive_budget_denoised(rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a,
+                                                     const rttnw_budget* b, const rttnw_guided* g, const double* state_in, double* state_out,
+                                                     double* out_linear_rgb, uint8_t* out_rgba8, uint8_t* out_valid, uint32_t* out_spp, double* out_stderr_rgb,
+                                                     double* out_raw_linear_rgb, double* out_raw_stderr_rgb, rttnw_stats* stats) {
+    using namespace rt;
+    const char* const call = "render_adaptive_budget_denoised";
+    // the refusals, in the header's order: none of them needs a device
+    if (!p || !a || !b || !g) { set_last_error(std::string(call) + ": NULL argument (p, a, b or g)"); return RTTNW_ERR_INVALID; }
+    if (int rc = refuse_adaptive_misuse(call, p, a)) return rc;
+    if (int rc = refuse_host_output_misuse(call, a->reserved0, p)) return rc;
+    if (b->reserved0 != 0) { set_last_error(std::string(call) + ": b->reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (a->rel_error == 0.0 && a->abs_error == 0.0) {
+        set_last_error(std::string(call) + ": rel_error and abs_error are both 0 (a priority relative to a tolerance of nothing ranks every noisy pixel +inf)");
+        return RTTNW_ERR_INVALID;
+    }
+    if (g->reserved0 != 0) { set_last_error(std::string(call) + ": g->reserved0 must be 0"); return RTTNW_ERR_INVALID; }
+    if (int rc = refuse_denoise_misuse(call, "g->", g->denoise)) return rc;
+    uint32_t first_level = 0; // (not used: every round finds the levels of its own pixels)
+    std::string err;
+    if (state_in)
+        if (int rc = refuse_state_misuse(call, true, *p, *a, cam, state_in, first_level, err)) { set_last_error(err); return rc; }
+    if (int rc = validate(s, cam, p)) return rc;
+    return adaptive_budget_denoised_render(s, cam, *p, *a, *b, *g, state_in, state_out, out_linear_rgb, out_rgba8, out_valid, out_spp, out_stderr_rgb,
+                                           out_raw_linear_rgb, out_raw_stderr_rgb, stats);
 }

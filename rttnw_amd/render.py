@@ -343,6 +343,34 @@ def render_adaptive_budget(scene, cam, params, samples, round_pixels=0, state=No
     return lin, rgba, spp, se, st, st_out, st.reserved >> 16
 
 
+def render_adaptive_budget_denoised(scene, cam, params, samples, round_pixels=0, state=None, pass_spp=64, rel_error=0.02, abs_error=0.0, iterations=5,
+                                    feature_spp=0, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0, want_state=True):
+    """`rttnw_render_adaptive_budget_denoised`: `render_adaptive_budget` whose rounds rank pixels by the noise of the FILTERED image — each round the
+    frame goes through `reconstruct`'s passes on the device (features of `feature_spp` samples, 0 = pass_spp; a pixel may hold nothing yet) and
+    `budget_select` runs on the filtered image and sqrt(filtered variance), a pixel whose own standard error is 0 set aside.  `state` as in
+    `render_adaptive_budget`.  The same `spp_chunk` default as `render_adaptive`.  Returns a dict like `render_preview`'s: "linear" HxWx3 f64, "rgba8"
+    HxWx4 u8 and "valid" HxW u8 (the filtered image), "stderr" HxWx3 f64 (sqrt of the filtered variance, +inf where nothing is valid), "spp" HxW u32,
+    "raw_linear" and "raw_stderr" HxWx3 f64 (`render_adaptive_budget`'s values), "state" (or None), "rounds" (rounds that traced) and "stats"."""
+    b = library.product()
+    p = _pass_params(params, pass_spp)
+    h, w = p.height, p.width
+    out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "valid": np.zeros((h, w), dtype=np.uint8),
+           "spp": np.zeros((h, w), dtype=np.uint32), "stderr": np.zeros((h, w, 3)), "raw_linear": np.zeros((h, w, 3)), "raw_stderr": np.zeros((h, w, 3))}
+    st_in, st_out = _state_arrays(b, "render_adaptive_budget_denoised", p, state, want_state)
+    st = Stats()
+    a = abi.Adaptive(pass_spp=pass_spp, reserved0=0, rel_error=rel_error, abs_error=abs_error)
+    bg = abi.Budget(samples=int(samples), round_pixels=int(round_pixels), reserved0=0)
+    g = abi.Guided(feature_spp=feature_spp, reserved0=0, denoise=_denoise_params(iterations, sigma_luminance, sigma_normal, sigma_depth))
+    rc = b.render_adaptive_budget_denoised(scene.handle, C.byref(cam), C.byref(p), C.byref(a), C.byref(bg), C.byref(g), _ptr(st_in), _ptr(st_out),
+                                           out["linear"].ctypes.data, out["rgba8"].ctypes.data, out["valid"].ctypes.data, out["spp"].ctypes.data,
+                                           out["stderr"].ctypes.data, out["raw_linear"].ctypes.data, out["raw_stderr"].ctypes.data, C.byref(st))
+    check(rc, b, "rttnw_render_adaptive_budget_denoised")
+    out["state"] = st_out
+    out["rounds"] = st.reserved >> 16
+    out["stats"] = st
+    return out
+
+
 def render_host_passes(scene, cam, params, passes, on_pass=None):
     """The same image as `render_host`, in `passes` passes over disjoint sample ranges (`rttnw_params.sample_begin`):
     after every pass the running mean is a complete, displayable estimate — progressive display and a natural
