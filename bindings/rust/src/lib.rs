@@ -6,3 +6,6 @@
 //!   `render()` as one call.
 pub mod ffi;
 pub mod scene;
+
+/// The filters that need no scene handle, at the crate's root: the feature-guided one and non-local means over two half-buffers.
+pub use scene::{denoise, denoise_nlm, NlmOutput};

@@ -338,6 +338,30 @@ pub fn denoise(linear: &[f64], variance: Option<&[f64]>, f: &Features, d: &ffi::
     Ok((out, rgba))
 }
 
+/// What `denoise_nlm` returns: the filtered image (linear w*h*3 and RGBA8 w*h*4), the two cross-filtered halves and (a' - b')^2 / 4, w*h*3 each.
+pub struct NlmOutput {
+    pub linear: Vec<f64>,
+    pub rgba8: Vec<u8>,
+    pub half_a: Vec<f64>,
+    pub half_b: Vec<f64>,
+    pub error: Vec<f64>,
+}
+
+/// `rttnw_denoise_nlm`: non-local means over two half-buffers (w*h*3 each: the means of two disjoint, equally large sample sets); the weights that
+/// average one half are patch distances measured in the other.  `variances`: the variance of each half's pixel means, or None for the pair variance.
+pub fn denoise_nlm(width: u32, height: u32, half_a: &[f64], half_b: &[f64], variances: Option<(&[f64], &[f64])>, d: &ffi::rttnw_nlm_params) -> Result<NlmOutput> {
+    let n = width as usize * height as usize;
+    if half_a.len() != n * 3 || half_b.len() != n * 3 || variances.map_or(false, |(va, vb)| va.len() != n * 3 || vb.len() != n * 3) {
+        return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "denoise_nlm: array sizes do not match the image".into() });
+    }
+    let mut out = NlmOutput { linear: vec![0f64; n * 3], rgba8: vec![0u8; n * 4], half_a: vec![0f64; n * 3], half_b: vec![0f64; n * 3], error: vec![0f64; n * 3] };
+    ok(unsafe {
+        ffi::rttnw_denoise_nlm(width, height, half_a.as_ptr(), half_b.as_ptr(), variances.map_or(ptr::null(), |v| v.0.as_ptr()), variances.map_or(ptr::null(), |v| v.1.as_ptr()),
+                               d, out.linear.as_mut_ptr(), out.rgba8.as_mut_ptr(), out.half_a.as_mut_ptr(), out.half_b.as_mut_ptr(), out.error.as_mut_ptr(), ptr::null_mut())
+    })?;
+    Ok(out)
+}
+
 /// `rttnw_reconstruct`: `denoise` over an image of which only the pixels with a nonzero byte in `valid` (w*h) hold a value; `linear` and
 /// `variance` are never read elsewhere.  Returns (linear w*h*3, RGBA8 w*h*4 with alpha 0 where nothing could be filled, the valid bytes).
 pub fn reconstruct(linear: &[f64], variance: Option<&[f64]>, valid: &[u8], f: &Features, d: &ffi::rttnw_denoise_params) -> Result<(Vec<f64>, Vec<u8>, Vec<u8>)> {

@@ -43,8 +43,8 @@ extern "C" {
                              * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region, rttnw_render_adaptive_multi,
                              *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region,
                              *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select,
-                             *  rttnw_render_adaptive_budget and rttnw_render_adaptive_budget_denoised came later, without a version bump: a
-                             *  caller detects each by its symbol) */
+                             *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised and rttnw_denoise_nlm came later, without a
+                             *  version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -374,6 +374,53 @@ int rttnw_denoise(uint32_t width, uint32_t height, const double* linear_rgb, con
                   const double* albedo, const double* normal, const double* depth, const double* alpha,
                   const rttnw_denoise_params* d, double* out_linear_rgb, uint8_t* out_rgba8, double* out_variance_rgb,
                   double* kernel_ms);
+
+/* A second denoiser, which reads NO feature buffer: non-local means over two half-buffers (Rousselle, Knaus and Zwicker 2012, "Adaptive
+ * rendering with non-local means filtering").  rttnw_denoise is steered by the first hit; what a mirror shows, what lies behind glass, a
+ * procedural texture on one surface is not in first-hit features.  Here the weights come from the colour itself:
+ * half_a and half_b are the means of two disjoint, equally large sample sets of one frame (two rttnw_render calls of spp / 2 samples at
+ * sample_begin and sample_begin + spp / 2), small patches of pixels are compared in ONE half, and the weights found there average the OTHER
+ * half — so no weight depends on the noise it averages.  Calling convention as rttnw_denoise: host arrays in and out (row-major, top row
+ * first), blocking, on the current device, no scene handle; no CPU fallback: RTTNW_ERR_HIP without a device.  Everything is double.
+ *
+ * Coordinates.  A value "at" a coordinate outside the image is the value of the nearest pixel inside: every coordinate below — patch taps,
+ *   candidates, the taps of the variance's 3x3 — is clamped to the image on its own (x = clamp(p + n), q = clamp(p + n + o)).
+ * Variance.  V_a, V_b are the guides' variances: var_a and var_b (the variance of each half's pixel MEAN) when given; otherwise both are the
+ *   pair variance, per channel  V(x) = (sum over the 3x3 around x, row-major, of (a - b)^2 * 0.5) / 9.
+ * Pixel distance in guide g with variance V, for offset o, q = x + o, per channel c:
+ *     delta_c(x, o) = ((g_x - g_q)^2 - (V_x + min(V_x, V_q))) / (1e-10 + k^2 * (V_x + V_q))          k^2 = k * k, rounded once
+ *     delta(x, o)   = (delta_r + delta_g) + delta_b                    the sum over the channels; their mean is taken with the patch's
+ * Patch distance.  R(x, o) = sum over nx = -f .. f, left to right, of delta(x + (nx, 0), o): the row sums;
+ *     D(p, o) = (sum over ny = -f .. f, top to bottom, of R(p + (0, ny), o)) / (3 * (2f + 1)^2): the mean over channels and patch taps.
+ * Weight.  t = 1 / (1 + 0.25 * m), m = 0 where D < 0 and D otherwise;  w = (t * t) * (t * t).  The centre offset weighs exactly 1, whatever
+ *   its D, so the sum of weights is never 0.
+ * Cross filtering.  a'(p) = (sum_o w_B(p, o) * a(p + o)) / (sum_o w_B(p, o)) with the weights of guide b and V_b, over the (2r+1)^2 offsets
+ *   row-major (oy outer, ox inner); b'(p) likewise with the weights of guide a and V_a.
+ * Outputs (each optional): out_linear_rgb w*h*3 = (a' + b') * 0.5; out_rgba8 w*h*4 of it after main.rs:219-225, alpha 255; out_half_a and
+ *   out_half_b w*h*3 = a' and b'; out_error_rgb w*h*3 = (a' - b')^2 * 0.25, an estimate of the output's variance; kernel_ms: device time of
+ *   the call's kernels.
+ * Every sum starts from 0.0 and adds its terms in the order stated; no product is fused into a sum; + - * / and comparisons only, no
+ *   transcendental function (the square root of the RGBA8 output aside).  So the device code, a host build of the same header
+ *   (rttnw_amd/csrc/nlm.hpp) and a restatement in numpy give the same bits.  Swapping (half_a, var_a) with (half_b, var_b) swaps out_half_a
+ *   with out_half_b and leaves the other outputs bit-identical.  A pixel's outputs depend on the inputs within r + f + 1 pixels of it only.
+ * Non-finite values.  A value or a variance that is not finite is not special-cased: it propagates through every sum it enters (D < 0 is
+ *   false for a NaN, so a NaN distance makes a NaN weight).
+ * Parameters.  0 means the library default: search_radius 7 (15x15 candidates), patch_radius 3 (7x7 patches), k 0.7.
+ * Refusals, before the device is touched, each message naming denoise_nlm and the argument: RTTNW_ERR_INVALID for a NULL half_a, half_b or
+ *   d, exactly one of var_a / var_b, width * height == 0, search_radius > 16, patch_radius > 4, a reserved field that is not 0, a negative
+ *   or NaN k.
+ * Out of scope: multiplying the first-hit normal and depth stops into the weight, albedo demodulation, steering the adaptive rounds by
+ *   out_error_rgb, a node-wide form. */
+struct rttnw_nlm_params {
+    uint32_t search_radius; /* r: candidates q = p + o, o in [-r, r]^2; 0 = default 7; 1 .. 16 */
+    uint32_t patch_radius;  /* f: (2f+1)^2 patch; 0 = default 3; 1 .. 4 */
+    double k;               /* distance scale; 0 = default 0.7; negative or NaN refused */
+    uint32_t reserved0, reserved1; /* must be 0 */
+};
+typedef struct rttnw_nlm_params rttnw_nlm_params;
+int rttnw_denoise_nlm(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a,
+                      const double* var_b, const rttnw_nlm_params* d, double* out_linear_rgb, uint8_t* out_rgba8,
+                      double* out_half_a, double* out_half_b, double* out_error_rgb, double* kernel_ms);
 
 /* `render()` on the GPUs of ONE NODE, in one call from one host thread ("library owns its HIP
  * streams / RCCL comms"): the framebuffer's 8x8 tiles are interleaved over `ngpu` ranks, rank r traces its tiles on

@@ -35,6 +35,10 @@ filters the frame on the device and gives one more pass to the pixels whose filt
 written is the filtered one, --denoise-iterations sets its passes, and a pixel nothing could be filled into stays transparent.  It works with
 --resume, --save-state and --spp-map, prints the samples traced and the rounds run, and does not combine with --budget, --guided, --preview,
 --refine, --devices, --window or --passes.
+--denoise-nlm [--nlm-search-radius R] [--nlm-patch-radius F] [--nlm-k K] renders the frame as two halves of spp / 2 samples over disjoint sample
+ranges and filters them with rttnw_denoise_nlm, non-local means whose weights for one half are measured in the other: no feature buffer, so what a
+mirror shows or a texture paints is filtered like anything else.  --spp must be even.  It does not combine with --noise, --denoise, --features,
+--devices, --window or --passes.
 """
 import argparse
 import sys
@@ -89,13 +93,18 @@ def refusal(args, refine, devices, window):
           "--preview": args.preview is not None, "--guided": args.guided,
           "--refine": args.refine is not None, "--devices": args.devices is not None, "--resume": args.resume is not None,
           "--save-state": args.save_state is not None, "--window": args.window is not None, "--passes": args.passes > 1,
-          "--features": args.features is not None, "--denoise": args.denoise}
+          "--features": args.features is not None, "--denoise": args.denoise, "--denoise-nlm": args.denoise_nlm}
     iterations = (0 <= args.denoise_iterations <= 8, "--denoise-iterations must be 0 .. 8")
     state_needs, state_clashes = "only the adaptive render has a state", ("--window", "--passes")
     # in the order they are checked: (flag, why it needs --noise or None, the flags it does not combine with, the reason given for that,
     # [(holds, the message if not)] checked before all that, the same checked after it)
     noise_above_0 = "%s needs a noise bound above 0 to rank pixels by (--noise or --abs-noise)"
     rules = [
+        ("--denoise-nlm", None, ("--noise", "--denoise", "--features", "--devices", "--window", "--passes"),
+         ": it filters two plain half renders of the whole frame, on one GPU", [],
+         [(0 <= args.nlm_search_radius <= 16, "--nlm-search-radius must be 0 .. 16 (0: the default, 7)"),
+          (0 <= args.nlm_patch_radius <= 4, "--nlm-patch-radius must be 0 .. 4 (0: the default, 3)"),
+          (args.nlm_k >= 0.0, "--nlm-k must be at least 0 (0: the default, 0.7)")]),
         ("--guided-budget", "it is the adaptive render under a budget of samples, ranked by the filtered image's noise",
          ("--budget", "--guided", "--preview", "--refine", "--devices", "--window", "--passes"),
          ": it runs on one GPU, over the whole frame, on the filtered noise", [],
@@ -160,6 +169,11 @@ def main(argv=None):
     ap.add_argument("--spp-map", default=None, help="adaptive sampling: also write a grey-scale PNG of samples / cap")
     ap.add_argument("--denoise", action="store_true", help="filter the image with the feature-guided denoiser (rttnw_denoise)")
     ap.add_argument("--denoise-iterations", type=int, default=5, help="a-trous passes of the denoiser (0..8)")
+    ap.add_argument("--denoise-nlm", action="store_true", help="render two halves of spp / 2 samples and filter them with non-local means "
+                    "(rttnw_denoise_nlm): no feature buffer")
+    ap.add_argument("--nlm-search-radius", type=int, default=0, help="non-local means: candidates within this many pixels (1..16; 0 = 7)")
+    ap.add_argument("--nlm-patch-radius", type=int, default=0, help="non-local means: patches of (2F+1)^2 pixels (1..4; 0 = 3)")
+    ap.add_argument("--nlm-k", type=float, default=0.0, help="non-local means: the distance scale (0 = 0.7)")
     ap.add_argument("--guided", action="store_true", help="adaptive sampling: stop pixels on the noise of the denoised image "
                     "(rttnw_render_adaptive_denoised); writes the denoised image")
     ap.add_argument("--preview", type=int, default=None, metavar="L", help="adaptive sampling: trace 1 pixel in 4^L (x %% 2^L == 0 and y %% 2^L == 0, "
@@ -335,6 +349,17 @@ def main(argv=None):
         ms = node_ms(devices, sts)
         print("%.3fs (%d ranks, trace kernels %.1f ms, %.1f Msamples/s)" % (time.time() - t0, len(sts), ms,
                                                                            sum(x.samples for x in sts) / max(ms, 1e-9) / 1e3))
+        return 0
+    if args.denoise_nlm:
+        if p.spp < 2 or p.spp % 2:
+            print("--denoise-nlm needs an even --spp (two halves of spp / 2 samples), got %d" % p.spp, file=sys.stderr)
+            return 1
+        (lin_a, _, st_a), (lin_b, _, st_b) = render.render_halves(sc, cam, p)
+        out = render.denoise_nlm(lin_a, lin_b, search_radius=args.nlm_search_radius, patch_radius=args.nlm_patch_radius, k=args.nlm_k, want_ms=True)
+        Image.fromarray(out["rgba8"], "RGBA").save(args.out)
+        ms = st_a.kernel_ms + st_b.kernel_ms
+        print("%.3fs (two halves of %d spp: trace kernels %.1f ms, %.1f Msamples/s; non-local means %.2f ms)"
+              % (time.time() - t0, p.spp // 2, ms, (st_a.samples + st_b.samples) / max(ms, 1e-9) / 1e3, out["ms"]))
         return 0
     lin, rgba, st = render.render_host(sc, cam, p)
     Image.fromarray(finish(lin, rgba, None), "RGBA").save(args.out)

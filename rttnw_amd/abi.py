@@ -60,6 +60,12 @@ class Denoise(C.Structure):
                 ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
 
 
+class Nlm(C.Structure):
+    """`rttnw_nlm_params` — the parameters of `rttnw_denoise_nlm` (0: the library default)."""
+    _fields_ = [("search_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("k", C.c_double), ("reserved0", C.c_uint32),
+                ("reserved1", C.c_uint32)]
+
+
 class Guided(C.Structure):
     """`rttnw_guided` — what `rttnw_render_adaptive_denoised` and `rttnw_render_adaptive_budget_denoised` take beside the stopping rule: the
     features' samples and the filter."""
@@ -145,6 +151,8 @@ PRODUCT_FUNCS = [
                           C.POINTER(Denoise), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("reconstruct", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.POINTER(Denoise), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    ("denoise_nlm", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Nlm), C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("render_preview", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Preview), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("budget_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint64,

@@ -1,7 +1,8 @@
-// feature_api.cpp — the extern "C" half of rttnw_render_features, rttnw_denoise and rttnw_reconstruct (include/rttnw_hip.h): argument checks, then
-// the feature pass of the requested arithmetic build (feature_kernels.hpp), the denoiser's device half (denoise.hip) or the reconstruction's
-// (reconstruct.hip).  Host code only.
+// feature_api.cpp — the extern "C" half of rttnw_render_features, rttnw_denoise, rttnw_denoise_nlm and rttnw_reconstruct (include/rttnw_hip.h):
+// argument checks, then the feature pass of the requested arithmetic build (feature_kernels.hpp), the denoiser's device half (denoise.hip), the
+// non-local-means filter's (nlm.hip) or the reconstruction's (reconstruct.hip).  Host code only.
 #include "feature_api.hpp"
+#include "nlm.hpp"
 
 extern "C" {
 
@@ -29,6 +30,23 @@ int rttnw_denoise(uint32_t width, uint32_t height, const double* linear_rgb, con
     const rt::DenoiseParams prm = rt::denoise_params(d->sigma_luminance, d->sigma_normal, d->sigma_depth, variance_rgb != nullptr);
     return rt::denoise_device(width, height, linear_rgb, variance_rgb, albedo, normal, depth, alpha, d->iterations, prm, out_linear_rgb, out_rgba8,
                               out_variance_rgb, kernel_ms);
+}
+
+int rttnw_denoise_nlm(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b,
+                      const rttnw_nlm_params* d, double* out_linear_rgb, uint8_t* out_rgba8, double* out_half_a, double* out_half_b, double* out_error_rgb,
+                      double* kernel_ms) {
+    if (!half_a || !half_b || !d) { rt::set_last_error("denoise_nlm: NULL argument (half_a, half_b or d)"); return RTTNW_ERR_INVALID; }
+    if ((var_a == nullptr) != (var_b == nullptr)) { rt::set_last_error("denoise_nlm: var_a and var_b go together: both or neither"); return RTTNW_ERR_INVALID; }
+    if (uint64_t(width) * height == 0 || uint64_t(width) * height > (1ull << 28)) {
+        rt::set_last_error("denoise_nlm: width * height: empty image (or more than 2^28 pixels)");
+        return RTTNW_ERR_INVALID;
+    }
+    if (d->search_radius > rt::NLM_MAX_SEARCH_RADIUS) { rt::set_last_error("denoise_nlm: d->search_radius is more than 16"); return RTTNW_ERR_INVALID; }
+    if (d->patch_radius > rt::NLM_MAX_PATCH_RADIUS) { rt::set_last_error("denoise_nlm: d->patch_radius is more than 4"); return RTTNW_ERR_INVALID; }
+    if (d->reserved0 != 0 || d->reserved1 != 0) { rt::set_last_error("denoise_nlm: d->reserved0 and d->reserved1 must be 0"); return RTTNW_ERR_INVALID; }
+    if (!(d->k >= 0.0)) { rt::set_last_error("denoise_nlm: d->k must be >= 0 (and not NaN)"); return RTTNW_ERR_INVALID; }
+    return rt::nlm_device(width, height, half_a, half_b, var_a, var_b, rt::nlm_params(d->search_radius, d->patch_radius, d->k), out_linear_rgb, out_rgba8,
+                          out_half_a, out_half_b, out_error_rgb, kernel_ms);
 }
 
 int rttnw_reconstruct(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const uint8_t* valid, const double* albedo,

@@ -1,0 +1,176 @@
+// nlm.hip — the device half of rttnw_denoise_nlm (include/rttnw_hip.h) around the arithmetic of nlm.hpp, double throughout:
+//   nlm_variance_kernel  the pair variance (only when the caller gave none), one thread per channel value
+//   nlm_filter_kernel    one block per TxT tile and direction (blockIdx.z 0: guide B weighs half A; 1: guide A weighs half B), one thread per pixel
+//   nlm_finish_kernel    the mean of the two filtered halves, its RGBA8 and the error estimate
+// The filter kernel stages the tile's guide and variance, with a halo of r + f, in LDS as six planes (r, g, b of each: consecutive lanes read
+// consecutive doubles, which ds_read_b64 serves without a bank conflict), then walks the (2r+1)^2 offsets row-major.  Per offset: every
+// delta(x, o) of the tile and its patch halo is formed ONCE into LDS ((T + 2f)^2 of them: three f64 divisions each — what bounds the kernel),
+// the row sums of the patches are built from those, and each pixel's thread adds 2f + 1 row sums, turns them into its weight and accumulates
+// the candidate of the other half, which it reads from global memory (a 3-double read per offset and pixel, L1/L2-resident).  Two barriers
+// per offset.  T = 32 where its LDS fits a CU (148 KiB at the default radii: one block of 16 waves per CU; 1.4 deltas per pixel and offset),
+// T = 16 otherwise (155 KiB at r 16, f 4; 1.9 and more deltas per pixel and offset).  DESIGN.md §10b has the measured times.
+#include "feature_api.hpp"
+#include "nlm.hpp"
+
+namespace rt {
+namespace {
+
+
+__global__ void nlm_variance_kernel(uint32_t width, uint32_t height, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; // one thread per channel value
+    if (i >= width * height * 3u) return;
+    const uint32_t pixel = i / 3u;
+    out[i] = nlm_pair_variance(width, height, a, b, pixel % width, pixel / width, int(i - pixel * 3u));
+}
+
+template <int T> // the tile's side; one thread per pixel of the tile
+__global__ __launch_bounds__(T * T) void nlm_filter_kernel(NlmView in, NlmParams prm, double* __restrict__ out_a, double* __restrict__ out_b) {
+    extern __shared__ __attribute__((aligned(16))) double nlm_lds[];
+    constexpr int NLM_BLOCK = T * T;
+    const int r = int(prm.r), f = int(prm.f), halo = r + f;
+    const int E = T + 2 * halo, P = T + 2 * f, plane = E * E; // the staged region's side, the delta region's side
+    double* G = nlm_lds;                                       // [3][E][E] the guide
+    double* V = nlm_lds + 3 * plane;                           // [3][E][E] its variance
+    double* Dl = nlm_lds + 6 * plane;                          // [P][P] delta(x, o) of the current offset
+    double* Rl = Dl + P * P;                                   // [P][T] the row sums
+    const bool second = blockIdx.z != 0;
+    const double* __restrict__ guide = second ? in.a : in.b;
+    const double* __restrict__ var = second ? in.var_a : in.var_b;
+    const double* __restrict__ src = second ? in.b : in.a;
+    const int x0 = int(blockIdx.x) * T, y0 = int(blockIdx.y) * T;
+    const int tid = int(threadIdx.x);
+
+    for (int i = tid; i < plane; i += NLM_BLOCK) {
+        const int ey = i / E, ex = i - ey * E;
+        const size_t q = (size_t(nlm_clamp(y0 - halo, ey, in.height)) * in.width + nlm_clamp(x0 - halo, ex, in.width)) * 3;
+        for (int ch = 0; ch < 3; ++ch) {
+            G[ch * plane + i] = guide[q + ch];
+            V[ch * plane + i] = var[q + ch];
+        }
+    }
+    __syncthreads();
+
+    const int px = tid % T, py = tid / T;
+    double sum_w = 0.0, sum_c[3] = {0.0, 0.0, 0.0};
+    for (int oy = -r; oy <= r; ++oy)
+        for (int ox = -r; ox <= r; ++ox) {
+            double w = 1.0; // the centre offset
+            if (ox != 0 || oy != 0) { // (uniform over the block: the barriers below are reached by all of its threads or by none)
+                for (int i = tid; i < P * P; i += NLM_BLOCK) {
+                    const int dy = i / P, dx = i - dy * P;
+                    const int xs = (dy + r) * E + dx + r, qs = xs + oy * E + ox; // 0 <= dy + r + oy, dx + r + ox < E
+                    const double d0 = nlm_delta_channel(G[xs], G[qs], V[xs], V[qs], prm.k2);
+                    const double d1 = nlm_delta_channel(G[plane + xs], G[plane + qs], V[plane + xs], V[plane + qs], prm.k2);
+                    const double d2 = nlm_delta_channel(G[2 * plane + xs], G[2 * plane + qs], V[2 * plane + xs], V[2 * plane + qs], prm.k2);
+                    Dl[i] = nlm_delta(d0, d1, d2);
+                }
+                __syncthreads();
+                for (int i = tid; i < P * T; i += NLM_BLOCK) {
+                    const int ry = i / T, rx = i - ry * T;
+                    double sum = 0.0;
+                    for (int n = 0; n <= 2 * f; ++n) sum = sum + Dl[ry * P + rx + n];
+                    Rl[i] = sum;
+                }
+                __syncthreads();
+                double column = 0.0;
+                for (int n = 0; n <= 2 * f; ++n) column = column + Rl[(py + n) * T + px];
+                w = nlm_weight(column, prm.patch_taps);
+            }
+            const size_t q = (size_t(nlm_clamp(y0 + py, oy, in.height)) * in.width + nlm_clamp(x0 + px, ox, in.width)) * 3;
+            sum_w = sum_w + w;
+            for (int ch = 0; ch < 3; ++ch) sum_c[ch] = sum_c[ch] + unfused_mul(w, src[q + ch]);
+        }
+    const uint32_t x = uint32_t(x0 + px), y = uint32_t(y0 + py);
+    if (x >= in.width || y >= in.height) return;
+    double* dst = (second ? out_b : out_a) + (size_t(y) * in.width + x) * 3;
+    for (int ch = 0; ch < 3; ++ch) dst[ch] = sum_c[ch] / sum_w;
+}
+
+__global__ void nlm_finish_kernel(uint32_t n, const double* __restrict__ fa, const double* __restrict__ fb, double* __restrict__ out,
+                                  uint8_t* __restrict__ out_rgba8, double* __restrict__ out_error) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; // one thread per channel value
+    if (i >= n * 3u) return;
+    const uint32_t pixel = i / 3u, ch = i - pixel * 3u;
+    const double c = nlm_mean(fa[i], fb[i]);
+    out[i] = c;
+    out_error[i] = nlm_error(fa[i], fb[i]);
+    out_rgba8[pixel * 4u + ch] = denoise_quantise(c);
+    if (ch == 0u) out_rgba8[pixel * 4u + 3u] = 255;
+}
+
+} // namespace
+
+#define NLM_TRY(expr)                                                                                  \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) {                                                                        \
+            set_last_error(std::string("denoise_nlm: " #expr ": ") + hipGetErrorString(e_));          \
+            return RTTNW_ERR_HIP;                                                                      \
+        }                                                                                              \
+    } while (0)
+
+int nlm_device(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b, const NlmParams& prm,
+               double* out_linear_rgb, uint8_t* out_rgba8, double* out_half_a, double* out_half_b, double* out_error_rgb, double* kernel_ms) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
+        set_last_error("denoise_nlm: no HIP device available (this library has no CPU fallback)");
+        return RTTNW_ERR_HIP;
+    }
+    const size_t npx = size_t(width) * height;
+    const bool has_var = var_a != nullptr;
+    auto upload = [](DevBuf<double>& b, const double* src, size_t count) -> hipError_t {
+        hipError_t e = b.alloc(count);
+        if (e == hipSuccess) e = hipMemcpy(b.p, src, count * sizeof(double), hipMemcpyHostToDevice);
+        return e;
+    };
+    DevBuf<double> d_a, d_b, d_va, d_vb, d_fa, d_fb, d_out, d_err;
+    DevBuf<uint8_t> d_rgba;
+    NLM_TRY(upload(d_a, half_a, npx * 3));
+    NLM_TRY(upload(d_b, half_b, npx * 3));
+    if (has_var) {
+        NLM_TRY(upload(d_va, var_a, npx * 3));
+        NLM_TRY(upload(d_vb, var_b, npx * 3));
+    } else {
+        NLM_TRY(d_va.alloc(npx * 3)); // the pair variance: one array for both guides
+    }
+    NLM_TRY(d_fa.alloc(npx * 3));
+    NLM_TRY(d_fb.alloc(npx * 3));
+    NLM_TRY(d_out.alloc(npx * 3));
+    NLM_TRY(d_err.alloc(npx * 3));
+    NLM_TRY(d_rgba.alloc(npx * 4));
+    // the large tile where its LDS fits a CU, the small one — which fits at every radius the entry point accepts — otherwise
+    const bool large = nlm_lds_bytes(NLM_TILE_LARGE, prm.r, prm.f) <= NLM_LDS_BYTES;
+    const uint32_t tile = large ? NLM_TILE_LARGE : NLM_TILE_SMALL;
+    const size_t lds_bytes = nlm_lds_bytes(tile, prm.r, prm.f);
+    void (*const filter)(NlmView, NlmParams, double*, double*) = large ? nlm_filter_kernel<int(NLM_TILE_LARGE)> : nlm_filter_kernel<int(NLM_TILE_SMALL)>;
+    NLM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(filter), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+    Event ev0, ev1;
+    NLM_TRY(create_event(ev0));
+    NLM_TRY(create_event(ev1));
+
+    const hipStream_t stream = nullptr;
+    const dim3 flat_block(256), value_grid(uint32_t((npx * 3 + 255) / 256));
+    const dim3 tiles((width + tile - 1) / tile, (height + tile - 1) / tile, 2);
+    NLM_TRY(hipEventRecord(ev0.get(), stream));
+    if (!has_var) hipLaunchKernelGGL(nlm_variance_kernel, value_grid, flat_block, 0, stream, width, height, d_a.p, d_b.p, d_va.p);
+    const NlmView view{width, height, d_a.p, d_b.p, d_va.p, has_var ? d_vb.p : d_va.p};
+    hipLaunchKernelGGL(filter, tiles, dim3(tile * tile), lds_bytes, stream, view, prm, d_fa.p, d_fb.p);
+    hipLaunchKernelGGL(nlm_finish_kernel, value_grid, flat_block, 0, stream, uint32_t(npx), d_fa.p, d_fb.p, d_out.p, d_rgba.p, d_err.p);
+    NLM_TRY(hipGetLastError());
+    NLM_TRY(hipEventRecord(ev1.get(), stream));
+    NLM_TRY(hipDeviceSynchronize());
+    if (kernel_ms) {
+        float ms = 0;
+        NLM_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+        *kernel_ms = ms;
+    }
+    const size_t bytes = npx * 3 * sizeof(double);
+    if (out_linear_rgb) NLM_TRY(hipMemcpy(out_linear_rgb, d_out.p, bytes, hipMemcpyDeviceToHost));
+    if (out_rgba8) NLM_TRY(hipMemcpy(out_rgba8, d_rgba.p, npx * 4, hipMemcpyDeviceToHost));
+    if (out_half_a) NLM_TRY(hipMemcpy(out_half_a, d_fa.p, bytes, hipMemcpyDeviceToHost));
+    if (out_half_b) NLM_TRY(hipMemcpy(out_half_b, d_fb.p, bytes, hipMemcpyDeviceToHost));
+    if (out_error_rgb) NLM_TRY(hipMemcpy(out_error_rgb, d_err.p, bytes, hipMemcpyDeviceToHost));
+    return RTTNW_OK;
+}
+
+} // namespace rt

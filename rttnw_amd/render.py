@@ -245,6 +245,50 @@ def denoise(linear, features, stderr=None, iterations=5, sigma_luminance=0.0, si
     return (out, rgba, out_var, ms.value) if want_ms else (out, rgba, out_var)
 
 
+def render_halves(scene, cam, params):
+    """The two half-buffers `denoise_nlm` takes: two `render_host` calls of `params.spp // 2` samples each, at `sample_begin` and
+    `sample_begin + spp // 2` — disjoint sample ranges, so their mean is the render of `params.spp` samples up to rounding.  An odd spp is a
+    ValueError.  Returns ((linear_a, rgba8_a, Stats_a), (linear_b, rgba8_b, Stats_b))."""
+    if params.spp < 2 or params.spp % 2:
+        raise ValueError("render_halves: spp must be even and at least 2 (two halves of spp // 2 samples), got %d" % params.spp)
+    halves = []
+    for k in range(2):
+        p = copy.copy(params)
+        p.spp = params.spp // 2
+        p.sample_begin = params.sample_begin + k * p.spp
+        halves.append(render_host(scene, cam, p))
+    return tuple(halves)
+
+
+def denoise_nlm(half_a, half_b, var_a=None, var_b=None, search_radius=0, patch_radius=0, k=0.0, want_ms=False):
+    """`rttnw_denoise_nlm`: non-local means over two half-buffers (HxWx3 each, the means of two disjoint, equally large sample sets — what
+    `render_halves` returns): the weights that average one half are patch distances measured in the other.  No feature buffer.  `var_a`, `var_b`
+    (HxWx3, both or neither) are the variances of each half's pixel means — the square of `render_adaptive`'s stderr of that half; without them
+    the filter estimates one from the difference of the halves.  A parameter of 0 is the library default (search radius 7, patch radius 3,
+    k 0.7).  Returns a dict: "linear" HxWx3 f64 and "rgba8" HxWx4 u8 (the filtered image), "half_a" and "half_b" HxWx3 (the two cross-filtered
+    halves), "error" HxWx3 ((a' - b')^2 / 4) — and "ms", the device time, with `want_ms`."""
+    b = library.product()
+    a_, b_ = np.ascontiguousarray(half_a, dtype=np.float64), np.ascontiguousarray(half_b, dtype=np.float64)
+    h, w = a_.shape[:2]
+    if (var_a is None) != (var_b is None):
+        raise ValueError("denoise_nlm: var_a and var_b go together: both or neither")
+    va = None if var_a is None else np.ascontiguousarray(var_a, dtype=np.float64)
+    vb = None if var_b is None else np.ascontiguousarray(var_b, dtype=np.float64)
+    for arr in (a_, b_, va, vb):
+        if arr is not None and arr.shape != (h, w, 3):
+            raise ValueError("denoise_nlm: every input is HxWx3 of one frame, got %s beside %s" % (arr.shape, (h, w, 3)))
+    out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "half_a": np.zeros((h, w, 3)),
+           "half_b": np.zeros((h, w, 3)), "error": np.zeros((h, w, 3))}
+    d = abi.Nlm(search_radius=search_radius, patch_radius=patch_radius, k=k, reserved0=0, reserved1=0)
+    ms = C.c_double(0.0)
+    rc = b.denoise_nlm(w, h, a_.ctypes.data, b_.ctypes.data, _ptr(va), _ptr(vb), C.byref(d), out["linear"].ctypes.data, out["rgba8"].ctypes.data,
+                       out["half_a"].ctypes.data, out["half_b"].ctypes.data, out["error"].ctypes.data, C.byref(ms))
+    check(rc, b, "rttnw_denoise_nlm")
+    if want_ms:
+        out["ms"] = ms.value
+    return out
+
+
 def lattice_mask(width, height, level):
     """The lattice of a preview as a mask (HxW u8): 1 where x % 2^level == 0 and y % 2^level == 0, row 0 at the top."""
     if not 0 <= int(level) <= 6:
