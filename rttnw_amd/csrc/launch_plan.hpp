@@ -33,6 +33,7 @@ namespace rt {
 inline namespace RT_ARITH_NS {
 
 constexpr int TRACE_BLOCK = 256;
+constexpr int RUN_AHEAD_STEPS = 3; // node steps per trip with run-ahead (final_scene f64: two 1645, three 1704 against 1664 Msamples/s without; profiles/LEDGER.md)
 constexpr uint32_t SLOTS_PER_WAVE = RT_SLOTS; // paths owned by one wave64: 64 being traversed + up to 64 queued
 constexpr uint32_t QCAP = RT_SLOTS;           // capacity of a wave's ray queue and hit queue (entries)
 static_assert(QCAP == SLOTS_PER_WAVE, "a slot has at most one ray or hit in flight: the queues never hold more entries than the wave has slots");
@@ -63,14 +64,15 @@ inline KernelForm kernel_form_named(const char* v) {
     return !v ? KernelForm::AUTO : !std::strcmp(v, "plain") ? KernelForm::PLAIN : !std::strcmp(v, "plainglobal") ? KernelForm::PLAINGLOBAL : !std::strcmp(v, "wave") ? KernelForm::WAVE : KernelForm::AUTO;
 }
 
-// Bits 0-6 of rttnw_stats.reserved: which kernel form a render ran (the tests and bench.py's roofline read them).  Bits 0-5 are LaunchPlan::form_bits,
-// bit 6 is known only once the scene's records are on the device; bits 8 / 9 belong to rttnw_render_multi's gather.
+// Bits 0-7 of rttnw_stats.reserved: which kernel form a render ran (the tests and bench.py's roofline read them).  Bits 0-5 are LaunchPlan::form_bits,
+// bit 6 is known only once the scene's records are on the device, bit 7 is LaunchPlan::run_ahead; bits 8 / 9 belong to rttnw_render_multi's gather.
 //   0 the decoupled kernel (else lane-owns-path)   1 node records resident in LDS (the form bench.py's roofline calls issue-bound)   2 three node steps per
-//   trip (tiny top trees)   3 a walk that never changes frames (rt_core.hpp SHAPES_NONE / SHAPES_SINGLE)   4 ... the one that tests single wrapped records in
+//   trip WITHOUT run-ahead (tiny top trees; with bit 7 a trip has RUN_AHEAD_STEPS = three node steps whatever this bit says)   3 a walk that never changes frames (rt_core.hpp SHAPES_NONE / SHAPES_SINGLE)   4 ... the one that tests single wrapped records in
 //   place (SHAPES_SINGLE)   5 ... in the LEAN flavour (SHAPES_*_NT)   6 the decoupled kernel walked the interleaved node + sphere buffer (render_common.hpp)
+//   7 the lane-owns-path kernel's trips ran with run-ahead (rt_core.hpp trav_trip_ahead) — the launch's own instantiation: never set by a counting render
 // Bits 3-5 say what the SCENE is eligible for: a counting render (collect_counters) runs the SHAPES_FAST / SHAPES_GENERAL instantiation — the only ones
 // that tally — and still reports them as its timed twin would.
-enum : uint32_t { FORM_DECOUPLED = 1u, FORM_LDS_NODES = 2u, FORM_THREE_STEPS = 4u, FORM_NO_FRAMES = 8u, FORM_SINGLE = 16u, FORM_LEAN = 32u, FORM_INTERLEAVED = 64u };
+enum : uint32_t { FORM_DECOUPLED = 1u, FORM_LDS_NODES = 2u, FORM_THREE_STEPS = 4u, FORM_NO_FRAMES = 8u, FORM_SINGLE = 16u, FORM_LEAN = 32u, FORM_INTERLEAVED = 64u, FORM_RUN_AHEAD = 128u };
 
 // Everything a render decides about its trace launches before it touches the device, which adds the occupancy answer and its CUs (the grid) and bit 6.
 struct LaunchPlan {
@@ -80,7 +82,9 @@ struct LaunchPlan {
     bool list;      // the active-list instantiation (rttnw_render_adaptive's refinement passes; non-counting forms only)
     bool quantised; // the kernel walks the quantised node records (DeviceScene::ensure_quant4)
     int shapes;     // rt_core.hpp SHAPES_*
-    int steps;      // node steps per walk trip of the lane-owns-path kernel
+    int steps;      // node steps per walk trip of the lane-owns-path kernel (its trips without run-ahead)
+    bool run_ahead; // ... whose trips put one-record leaves aside and walk on, and are then RUN_AHEAD_STEPS node steps long (trace_kernel_plain RUN_AHEAD;
+                    // bit 7 of rttnw_stats.reserved)
     int block;      // threads per block
     uint32_t lds_nodes, lds_recs[6]; // RenderConsts::lds_nodes / lds_recs
     uint32_t staged_bytes;           // LDS bytes of the arrays staged behind the stacks (Perlin tables, record arrays)
@@ -100,8 +104,9 @@ struct LaunchPlan {
 // (later in round 5 — the decoupled kernel keeps a slot's ray in LDS, +5 .. 9 %: f32 5.7 k nodes 7216 / 7620, 7.6 k 6101 / 6840, 9.9 k 5410 / 6371; f64
 // 5.7 k 6974 / 6577, 7.6 k 5919 / 5817, 9.9 k 5150 / 5318, 15.4 k 3941 / 4450; RTTNW_F64_STRICT 7.6 k 5945 / 5783, 9.9 k 5195 / 5224: f32 crosses
 // at ~5 k records, f64 at ~9 k)
-// real_bytes: sizeof the arithmetic type; wave_block: RTTNW_WAVE_BLOCK=<threads> (experiments), 0 = unset.
-inline LaunchPlan plan_launch(const FlatScene& flat, size_t real_bytes, bool count, bool listed, KernelForm forced, int wave_block) {
+// real_bytes: sizeof the arithmetic type; wave_block: RTTNW_WAVE_BLOCK=<threads> (experiments), 0 = unset; run_ahead: RTTNW_RUN_AHEAD (experiments and
+// tests) 0 = off, 1 = on wherever an instantiation has it, -1 = unset: the plan's own choice.
+inline LaunchPlan plan_launch(const FlatScene& flat, size_t real_bytes, bool count, bool listed, KernelForm forced, int wave_block, int run_ahead = -1) {
     LaunchPlan pl{};
     pl.count = count; pl.list = listed && !count; pl.steps = RT_NODE_STEPS;
     const uint32_t n4 = flat.total_nodes4();
@@ -148,6 +153,11 @@ inline LaunchPlan plan_launch(const FlatScene& flat, size_t real_bytes, bool cou
                     : !no_frames || count  ? SHAPES_FAST
                     : flat.has_instance_leaves ? (lean ? SHAPES_SINGLE_NT : SHAPES_SINGLE)
                                                : (lean ? SHAPES_NONE_NT : SHAPES_NONE);
+        // RUN-AHEAD: only the timed instantiations of a walk that never changes frames have it (a record put aside is tested with the walk's one ray); the
+        // counting ones keep the canonical sequence of steps, whose counts the tests pin.  Left to itself the plan gives it to the scenes that meet no
+        // instance leaf at all (SHAPES_NONE / SHAPES_NONE_NT: final_scene); the override turns it on for the SINGLE family too, or off.
+        const bool can_run_ahead = no_frames && !count && !gen;
+        pl.run_ahead = can_run_ahead && (run_ahead < 0 ? !flat.has_instance_leaves : run_ahead != 0);
         const bool in_lds = pl.lds_nodes != 0u, eligible = no_frames && in_lds;
         pl.form_bits = (in_lds ? FORM_LDS_NODES : 0u) | (three_steps ? FORM_THREE_STEPS : 0u) | (eligible ? FORM_NO_FRAMES : 0u) |
                        (eligible && flat.has_instance_leaves ? FORM_SINGLE : 0u) | (eligible && lean ? FORM_LEAN : 0u);

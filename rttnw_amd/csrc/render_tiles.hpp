@@ -13,6 +13,8 @@ template <typename R, bool LDSN, int SHAPES, bool LIST> const void* plain_kernel
     constexpr int BLOCK = !LDSN ? TRACE_BLOCK : sizeof(R) == 4 ? 1024 : RT_F64_BLOCK;
     if constexpr (!LIST && (SHAPES == SHAPES_FAST || SHAPES == SHAPES_GENERAL)) // (the only shapes that tally)
         if (pl.count) return (const void*)trace_kernel_plain<R, true, BLOCK, LDSN, SHAPES>;
+    if constexpr (LDSN && SHAPES != SHAPES_FAST && SHAPES != SHAPES_GENERAL) // (run-ahead: the walks that never change frames, launch_plan.hpp)
+        if (pl.run_ahead) return (const void*)trace_kernel_plain<R, false, BLOCK, true, SHAPES, RUN_AHEAD_STEPS, LIST, true>;
     if constexpr (LDSN)
         if (pl.steps == RT_TINY_TREE_STEPS) return (const void*)trace_kernel_plain<R, false, BLOCK, true, SHAPES, RT_TINY_TREE_STEPS, LIST>;
     return (const void*)trace_kernel_plain<R, false, BLOCK, LDSN, SHAPES, RT_NODE_STEPS, LIST>;
@@ -78,10 +80,13 @@ int size_chunk_sums(DeviceState* d, uint64_t sum_pixels, uint32_t total_chunks, 
 }
 
 // The launch plan of a render of `flat` in this precision (launch_plan.hpp plan_launch, which reads no environment itself) under the experiment
-// overrides: RTTNW_KERNEL=plain|plainglobal|wave names the form, RTTNW_WAVE_BLOCK=<threads> the decoupled LEAN flavour's block.
+// overrides: RTTNW_KERNEL=plain|plainglobal|wave names the form, RTTNW_WAVE_BLOCK=<threads> the decoupled LEAN flavour's block, RTTNW_RUN_AHEAD=0|1
+// run-ahead in the lane-owns-path kernel's trips (launch_plan.hpp plan_launch).
 template <typename R> LaunchPlan plan_for(const FlatScene& flat, bool count, bool listed) {
     const char* wave_block = getenv("RTTNW_WAVE_BLOCK");
-    return plan_launch(flat, sizeof(R), count, listed, kernel_form_named(getenv("RTTNW_KERNEL")), wave_block ? atoi(wave_block) : 0);
+    const char* ahead = getenv("RTTNW_RUN_AHEAD"); // 0 | 1: run-ahead off / on wherever an instantiation has it
+    return plan_launch(flat, sizeof(R), count, listed, kernel_form_named(getenv("RTTNW_KERNEL")), wave_block ? atoi(wave_block) : 0,
+                       ahead && (ahead[0] == '0' || ahead[0] == '1') && !ahead[1] ? ahead[0] - '0' : -1);
 }
 
 // One trace launch over the rc.n_jobs jobs of a pass: the workspace its grid needs, then the plan's kernel (prepare_only: the workspace alone).
@@ -173,7 +178,7 @@ int fill_stats(DeviceState* d, const DeviceScene<R>& ds, const FlatScene& flat, 
     stats->n_nodes = flat.total_nodes4();
     stats->n_prims = flat.n_prims_in_bvh;
     stats->scene_bytes = uint32_t(std::min<size_t>(ds.bytes, 0xFFFFFFFFu));
-    stats->reserved = pl.form_bits | (pl.decoupled && ds.interleaved ? FORM_INTERLEAVED : 0u); // which kernel form ran (launch_plan.hpp FORM_*)
+    stats->reserved = pl.form_bits | (pl.decoupled && ds.interleaved ? FORM_INTERLEAVED : 0u) | (pl.run_ahead ? FORM_RUN_AHEAD : 0u); // which kernel form ran (launch_plan.hpp FORM_*)
     return 0;
 }
 
@@ -202,6 +207,8 @@ int render_tiles_t(::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* ca
     const CameraRec<R> camr = camera_of<R>(cam);
     const LaunchPlan pl = plan_for<R>(*flat, count, listed);
     rc.lds_nodes = pl.lds_nodes;
+    // (a counting render at level >= 2 tallies the trips its timed twin takes: trace_tally.hpp; levels 0 and 1 keep the canonical walk and its counts)
+    if (count && rc.profile >= 2u && plan_for<R>(*flat, false, listed).run_ahead) rc.scene_flags |= SCENE_TALLY_AHEAD;
     for (int k = 0; k < 6; ++k) rc.lds_recs[k] = pl.lds_recs[k];
     if (!prepare_only) HIP_TRY(hipMemsetAsync(d->job_counter.p, 0, sizeof(unsigned long long) + sizeof(DeviceCounters), stream));
     if (stats && !prepare_only && !(ad && ad->clock_started)) HIP_TRY(hipEventRecord(d->ev0.get(), stream));

@@ -1176,14 +1176,18 @@ template <bool G = false, bool NO_TIME = false, bool FRAME_RAY = false, typename
     hit = prim_t<NO_TIME, FRAME_RAY>(sc, kind, idx, ray, t_min, tr.closest, t, aux, tr.sr);
     if (hit) trav_accept(tr, sc, kind, idx, t, aux, inst);
 }
-template <typename R, typename Stack, typename Cnt>
-RT_HD void trav_leaf_step(Trav<R>& tr, const SceneView<R>& sc, const Ray<R>& wray, R t_min, Stack& stack, Cnt& cnt) {
+// AHEAD (run-ahead, below): a record the lane put aside in `stash` (0: none) is tested instead of the leaf it stands at, which waits for the next
+// leaf step; ONE copy of the record tests serves both.  AHEAD = false is the step as it always was.
+template <bool AHEAD, typename R, typename Stack, typename Cnt>
+RT_HD void trav_leaf_step_t(Trav<R>& tr, int32_t& stash, const SceneView<R>& sc, const Ray<R>& wray, R t_min, Stack& stack, Cnt& cnt) {
     constexpr bool NI = Cnt::NO_INST;
     // (the fast cube test where the walk's plane distances are to hand and cubes are what a leaf step meets: not in the decoupled kernel — big trees of
     // spheres, whose LEAN flavour is held to 128 registers: spheres_1m strict 484 -> 479 with the code aboard)
     constexpr bool FAST_CUBES = Stack::WIDE != NODES_Q8X4;
-    if (tr.node == CHILD_EMPTY) { trav_pop<NI>(tr, wray, stack); return; }
-    const uint32_t kind = leaf_kind(tr.node), count = leaf_count(tr.node), first = leaf_first(tr.node);
+    const bool from_stash = AHEAD && stash != 0;
+    const int32_t leaf = from_stash ? stash : tr.node;
+    if (leaf == CHILD_EMPTY) { trav_pop<NI>(tr, wray, stack); return; }
+    const uint32_t kind = leaf_kind(leaf), count = leaf_count(leaf), first = leaf_first(leaf);
     if (!Cnt::NO_INST_LEAF && kind == PRIM_INSTANCE) { // Translate / YRotate wrappers: continue in object space (hittable.rs:599-606,686-699)
         cnt.prim();
         const InstanceRec<R>& in_rec = sc.insts[first];
@@ -1209,8 +1213,52 @@ RT_HD void trav_leaf_step(Trav<R>& tr, const SceneView<R>& sc, const Ray<R>& wra
         return;
     }
     cnt.prim();
-    trav_test_record<Cnt::GENERAL, Cnt::NO_TIME, FAST_CUBES>(tr, sc, kind, first + tr.leaf_k, t_min, NI ? wray : tr.ray, NI ? -1 : tr.cur_inst);
+    trav_test_record<Cnt::GENERAL, Cnt::NO_TIME, FAST_CUBES>(tr, sc, kind, first + (from_stash ? 0u : tr.leaf_k), t_min, NI ? wray : tr.ray, NI ? -1 : tr.cur_inst);
+    if constexpr (AHEAD)
+        if (from_stash) { stash = 0; return; } // (its pop was made when it was put aside)
     if (++tr.leaf_k >= count) trav_pop<NI>(tr, wray, stack);
+}
+template <typename R, typename Stack, typename Cnt>
+RT_HD void trav_leaf_step(Trav<R>& tr, const SceneView<R>& sc, const Ray<R>& wray, R t_min, Stack& stack, Cnt& cnt) {
+    int32_t none = 0;
+    trav_leaf_step_t<false>(tr, none, sc, wray, t_min, stack, cnt);
+}
+
+// ---- RUN-AHEAD: a trip of the lane-owns-path kernel in which a lane at a leaf does not sit out the node steps (trace_kernels.hpp trace_kernel_plain
+// RUN_AHEAD; the host drivers of tests/run_ahead_host run the same functions).  At a STASH POINT a lane that stands at a leaf of ONE record that is no instance,
+// with its register empty, puts the leaf aside, takes its next pending subtree off the stack and goes on with node steps; the trip's leaf step tests
+// the record put aside.  A stash point could stand before any node step of a trip; the kernel has the one at the trip's START, where
+// the lanes stand that the last leaf step's pop brought to a leaf — a stash point costs ~50 instructions a trip, and the later ones served too few
+// lanes to pay for theirs (profiles/LEDGER.md: final_scene f64, three node steps per trip: +2.4 % with the first alone, +1.6 % with two, +-0 with three).
+// The order of a lane's record tests is the canonical walk's; the node steps in between see a `closest` that is one test stale, so they cull a little less and never anything the canonical walk visits: closest hit with the prim_seq tie rule does not depend on the
+// order or on extra visits (an extra leaf's box lies beyond the hit, its test fails).  The register is set and consumed inside ONE trip: it does not
+// live across a shade phase, and the deepest push is the canonical walk's (the lane holds one leaf OUTSIDE the stack).  Only for walks that never change
+// frames (Cnt::NO_INST, or a scene without such instances under the general counters): the record is tested with the walk's one ray.
+constexpr bool trav_stash_point_before(int k) { return k == 0; } // which node steps of a trip have a stash point before them
+template <bool NO_INST_LEAF = false> RT_HD bool leaf_can_be_stashed(int32_t node) {
+    // leaf bits ~node = kind << 28 | (count - 1) << 26 | first; an inner node reads as "kind" >= 8, TRAV_DONE / CHILD_EMPTY / the sentinel as kind 7
+    const uint32_t v = uint32_t(~node) >> 26; // kind << 2 | count - 1
+    return (v & 3u) == 0u && v < (uint32_t(PRIM_NONE) << 2) && (NO_INST_LEAF || v != (uint32_t(PRIM_INSTANCE) << 2));
+}
+template <bool NO_INST, bool NO_INST_LEAF, typename R, typename Stack>
+RT_HD bool trav_stash_point(Trav<R>& tr, int32_t& stash, const Ray<R>& wray, Stack& stack) {
+    if (stash != 0 || !leaf_can_be_stashed<NO_INST_LEAF>(tr.node)) return false;
+    stash = tr.node;
+    trav_pop<NO_INST>(tr, wray, stack);
+    return true;
+}
+// a lane takes the trip's leaf step when it has a record put aside or stands at a leaf; its walk is over once it is DONE with nothing put aside
+RT_HD bool trav_wants_leaf_step(int32_t node, int32_t stash) { return stash != 0 || (node < 0 && node != TRAV_DONE); }
+RT_HD bool trav_unfinished(int32_t node, int32_t stash) { return node != TRAV_DONE || stash != 0; }
+// One trip with run-ahead, as the kernel runs it for a lane: NSTEPS x (stash point where one stands, node step), then the leaf step.
+template <int NSTEPS, typename R, typename Stack, typename Cnt>
+RT_HD void trav_trip_ahead(Trav<R>& tr, int32_t& stash, const SceneView<R>& sc, const Ray<R>& wray, R t_min, Stack& stack, Cnt& cnt) {
+#pragma unroll
+    for (int k = 0; k < NSTEPS; ++k) {
+        if (trav_stash_point_before(k)) trav_stash_point<Cnt::NO_INST, Cnt::NO_INST_LEAF>(tr, stash, wray, stack);
+        if (tr.node >= 0) trav_node_step(tr, sc, wray, t_min, stack, cnt);
+    }
+    if (trav_wants_leaf_step(tr.node, stash)) trav_leaf_step_t<true>(tr, stash, sc, wray, t_min, stack, cnt);
 }
 
 template <typename R, typename Stack, typename Cnt>

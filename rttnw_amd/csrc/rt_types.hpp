@@ -252,7 +252,8 @@ struct RenderConsts {
     uint32_t pad0;
     double inv_width, inv_height; // 1 / width, 1 / height: the contracted f64 build multiplies where main.rs:213-214 divides (the strict build divides)
 };
-enum : uint32_t { SCENE_NO_TIME = 1u };
+enum : uint32_t { SCENE_NO_TIME = 1u,
+                  SCENE_TALLY_AHEAD = 2u }; // counting variant at collect_counters >= 2: the tallied phase takes the run-ahead trips of the scene's timed kernel (trace_tally.hpp)
 
 // A pixel's samples are split into CHUNKS; a job = (pixel, chunk) folds its samples sequentially (main.rs:211-216) and
 // the resolve step adds a pixel's chunk sums, in chunk order, onto the pixel's running sum: ONE chain per pixel,

@@ -431,7 +431,9 @@ RT_WAVE_DECL_LIST(SHAPES_FAST) RT_WAVE_DECL_LIST(SHAPES_GENERAL) RT_WAVE_DECL_LI
 // their cursor and walk on beside them.  Kept beside the decoupled kernel because which of the two is faster depends on the scene
 // (render_tiles.hpp: the crossover is at ~13 000 four-wide records; KERNELS.md).
 // NSTEPS: node steps per trip round the walk loop (rt_core.hpp closest_solid): RT_NODE_STEPS, or 3 for tiny top trees (render_tiles.hpp).
-template <typename R, bool COUNT, int BLOCK, bool LDSN, int GENERAL, int NSTEPS = RT_NODE_STEPS, bool LIST = false> // GENERAL: SHAPES_FAST / SHAPES_GENERAL / SHAPES_NONE, as above
+// RUN_AHEAD (walks that never change frames, non-counting forms; launch_plan.hpp decides): the trips run rt_core.hpp's run-ahead — a lane at a one-record
+// leaf puts it aside before a node step and walks on, the trip's leaf step tests it.  Off, the kernel is what it was, instruction for instruction.
+template <typename R, bool COUNT, int BLOCK, bool LDSN, int GENERAL, int NSTEPS = RT_NODE_STEPS, bool LIST = false, bool RUN_AHEAD = false> // GENERAL: SHAPES_FAST / SHAPES_GENERAL / SHAPES_NONE, as above
 // (the 256-thread form — nodes in global memory — asks for at least 3 waves/SIMD like the decoupled kernel: its f64 code,
 // allowed 256 VGPRs, ran at 2: a 20 000-sphere scene 29.9 -> 13.7 ms per 67 Msamples)
 __global__ __launch_bounds__(BLOCK, BLOCK == 256 ? 3 : 1) void trace_kernel_plain(SceneView<R> sc_arg, CameraRec<R> cam, RenderConsts rc, R bg_r, R bg_g,
@@ -561,14 +563,21 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 256 ? 3 : 1) void trace_kernel_plai
             if (fresh_walk) trav_reject_unwalkable(tr, ps.ray);
             for (;;) { // trips (rt_core.hpp closest_solid's loop body) until few enough walks are unfinished
                 const bool unfinished = walking && tr.node != TRAV_DONE;
-                if (unfinished) {
+                if constexpr (RUN_AHEAD) {
+                    static_assert(!COUNT && CounterSel<COUNT, GENERAL>::type::NO_INST, "run-ahead tests a record put aside with the walk's one ray");
+                    // (the register lives inside the trip: set at a stash point, emptied by the leaf step — a lane with a record put aside is never
+                    // seen by the ballots below, and nothing of it lives through a shade phase)
+                    int32_t stash = 0;
+                    if (unfinished) trav_trip_ahead<NSTEPS>(tr, stash, sc, ps.ray, t_min, stack, cnt);
+                } else if (unfinished) {
 #pragma unroll
                     for (int k = 0; k < NSTEPS; ++k)
                         if (tr.node >= 0) trav_node_step(tr, sc, ps.ray, t_min, stack, cnt);
                 }
                 // (serving the lanes at a leaf by CLASS of record kind — the cube's ~200 instructions run for 2 lanes of 64 on final_scene — only once enough
                 // lanes wait at a class was modelled at -8.8 % instructions and measured at -1.4 % / -4.5 % (f64 / f32): profiles/r05/README.md)
-                if (unfinished && tr.node < 0 && tr.node != TRAV_DONE) trav_leaf_step(tr, sc, ps.ray, t_min, stack, cnt);
+                if constexpr (!RUN_AHEAD)
+                    if (unfinished && tr.node < 0 && tr.node != TRAV_DONE) trav_leaf_step(tr, sc, ps.ray, t_min, stack, cnt);
                 const unsigned long long um = __ballot(walking && tr.node != TRAV_DONE);
                 if (um == 0ull) break;
                 if (uint32_t(__popcll(um)) <= uint32_t(RT_ASYNC_SLACK) && __ballot(walking && tr.node == TRAV_DONE) != 0ull) break;

@@ -2,7 +2,10 @@
 // wave clock read between its parts and the trips of its walk loop tallied.  Compiled into the COUNT = true instantiations only
 // (rttnw_params.collect_counters != 0: the untimed counting pass of bench.py, RTTNW_DEBUG_SCHED); the product kernels never contain it.
 // One PHASE = start the walks of the lanes that have none, trips until at most RT_ASYNC_SLACK walks are unfinished, shade the finished ones:
-// the steps of the kernel's own phase, in the same order.
+// the steps of the kernel's own phase, in the same order.  The trips are the CANONICAL ones (NSTEPS node steps + a leaf step: the counts the tests pin)
+// unless rc.scene_flags has SCENE_TALLY_AHEAD — collect_counters >= 2 on a scene whose timed kernel runs RUN-AHEAD (render_tiles.hpp) —: then they are
+// that kernel's (rt_core.hpp trav_trip_ahead: a stash point, RUN_AHEAD_STEPS node steps, the leaf step that tests a record put aside), so that lanes per
+// step, visits and record tests are the timed kernel's.
 //   prof[0..3]  wave clock: job hand-out / path begin / BVH walk / shade;  [15] media + hit record part of shade
 //   prof[4]     trips of the walk loop ([7] with a node lane, [8] with a leaf lane), [5] / [6] lane steps served (node / leaf)
 //   prof[9]     phases, [10] lanes a phase shaded, [11] phases that began paths, [12] paths begun
@@ -34,6 +37,7 @@ __device__ __forceinline__ void plain_phase_tallied(bool done, bool& alive, bool
     else if (fresh_walk) trav_set_ray(tr, ps.ray, stack);
     if (fresh_walk) trav_reject_unwalkable(tr, ps.ray);
     uint32_t phase_trips = 0;
+    const bool ahead = (rc.scene_flags & SCENE_TALLY_AHEAD) != 0u; // (wave-uniform)
     for (;;) {
         const bool unfinished = walking && tr.node != TRAV_DONE;
         const unsigned long long act = __ballot(unfinished);
@@ -42,24 +46,34 @@ __device__ __forceinline__ void plain_phase_tallied(bool done, bool& alive, bool
             unsigned long long n_node = 0, n_leaf = 0;
             bool any_node = false;
             const long long q0 = clock64();
+            int32_t stash = 0; // (run-ahead: lives inside the trip, trav_trip_ahead)
             if (unfinished) {
                 ++my_trips;
+                if (ahead) {
 #pragma unroll
-                for (int k = 0; k < NSTEPS; ++k)
-                    if (tr.node >= 0) { ++n_node; trav_node_step(tr, sc, ps.ray, t_min, stack, cnt); }
+                    for (int k = 0; k < RUN_AHEAD_STEPS; ++k) {
+                        if (trav_stash_point_before(k)) trav_stash_point<Cnt::NO_INST, Cnt::NO_INST_LEAF>(tr, stash, ps.ray, stack);
+                        if (tr.node >= 0) { ++n_node; trav_node_step(tr, sc, ps.ray, t_min, stack, cnt); }
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < NSTEPS; ++k)
+                        if (tr.node >= 0) { ++n_node; trav_node_step(tr, sc, ps.ray, t_min, stack, cnt); }
+                }
             }
             any_node = __ballot(n_node != 0ull) != 0ull;
             const long long q1 = clock64();
-            const bool is_leaf = unfinished && tr.node < 0 && tr.node != TRAV_DONE;
+            const bool is_leaf = unfinished && trav_wants_leaf_step(tr.node, stash); // (nothing put aside: the lanes at a leaf)
             const unsigned long long lm = __ballot(is_leaf);
             uint32_t kmask = 0;
             if (rc.profile == 2u) {
-                const uint32_t kd = tr.node == CHILD_EMPTY ? 5u : leaf_kind(tr.node);
+                const int32_t lf = stash != 0 ? stash : tr.node;
+                const uint32_t kd = lf == CHILD_EMPTY ? 5u : leaf_kind(lf);
 #pragma unroll
                 for (uint32_t k = 0; k < 6; ++k) kmask |= __ballot(is_leaf && kd == k) != 0ull ? (1u << k) : 0u;
             }
             const long long q1b = clock64();
-            if (is_leaf) { ++n_leaf; trav_leaf_step(tr, sc, ps.ray, t_min, stack, cnt); }
+            if (is_leaf) { ++n_leaf; trav_leaf_step_t<true>(tr, stash, sc, ps.ray, t_min, stack, cnt); } // (with nothing put aside: trav_leaf_step)
             const long long q2 = clock64();
             prof[5] += n_node;
             prof[6] += n_leaf;
