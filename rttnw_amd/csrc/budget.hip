@@ -1,8 +1,7 @@
 // budget.hip — the device half of rttnw_budget_select and of the rounds of rttnw_render_adaptive_budget and rttnw_render_adaptive_budget_denoised
-// (budget.hpp): the launch code of budget_kernels.hpp and guided_budget_kernels.hpp.  One translation unit for every precision, double only, built without -ffp-contract=fast like guided.hip and denoise.hip.
+// (budget.hpp): the launch code of budget_kernels.hpp.  One translation unit for every precision, double only, built without -ffp-contract=fast like guided.hip and denoise.hip.
 #include "budget.hpp"
 #include "budget_kernels.hpp"
-#include "guided_budget_kernels.hpp"
 
 namespace rt {
 
@@ -61,21 +60,6 @@ int budget_round_launch(const BudgetWorkspace& w, uint32_t precision, const void
     return budget_keys_round_launch(w, d_state, width, height, cap, pass_spp, max_pixels, d_select, d_record, stream);
 }
 
-int guided_budget_raw_launch(uint32_t precision, const void* d_means, const double* d_aux, double* d_mean, double* d_variance, double* d_raw_stderr,
-                             uint32_t* d_spp, uint8_t* d_valid, uint32_t width, uint32_t height, hipStream_t stream) {
-    rttnw_tile_layout L;
-    fill_layout(width, height, 1, L);
-    const dim3 block(32, 8), grid((width + 31) / 32, (height + 7) / 8);
-    if (precision == RTTNW_F32)
-        hipLaunchKernelGGL(guided_budget_raw_kernel<float>, grid, block, 0, stream, (const float*)d_means, d_aux, d_mean, d_variance, d_raw_stderr, d_spp,
-                           d_valid, width, height, L.tiles_x);
-    else
-        hipLaunchKernelGGL(guided_budget_raw_kernel<double>, grid, block, 0, stream, (const double*)d_means, d_aux, d_mean, d_variance, d_raw_stderr, d_spp,
-                           d_valid, width, height, L.tiles_x);
-    HIP_TRY(hipGetLastError());
-    return RTTNW_OK;
-}
-
 int guided_budget_rank_launch(const BudgetWorkspace& w, const double* d_den, const double* d_var_f, const double* d_raw_stderr, const uint32_t* d_spp,
                               uint32_t cap, double rel_error, double abs_error, double* d_stderr_f, hipStream_t stream) {
     hipLaunchKernelGGL(guided_budget_rank_kernel, budget_grid(w.n), dim3(BUDGET_BLOCK), 0, stream, w.n, d_den, d_var_f, d_raw_stderr, d_spp, cap, rel_error,
@@ -84,60 +68,48 @@ int guided_budget_rank_launch(const BudgetWorkspace& w, const double* d_den, con
     return RTTNW_OK;
 }
 
-#define BUDGET_TRY(expr)                                                                                 \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) {                                                                          \
-            set_last_error(std::string("budget_select: " #expr ": ") + hipGetErrorString(e_));          \
-            return RTTNW_ERR_HIP;                                                                        \
-        }                                                                                                \
-    } while (0)
-
 int budget_select_device(uint32_t width, uint32_t height, const double* linear_rgb, const double* stderr_rgb, const uint32_t* spp, uint32_t cap,
                          double rel_error, double abs_error, uint64_t max_pixels, uint8_t* out_mask, double* out_priority, uint64_t* out_selected,
                          double* kernel_ms) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        set_last_error("budget_select: no HIP device available (this library has no CPU fallback)");
-        return RTTNW_ERR_HIP;
-    }
+    if (int rc = require_device("budget_select")) return rc;
+    const char* const at = "budget_select: ";
     const unsigned long long n = (unsigned long long)width * height;
     DevBuf<double> d_value, d_se, d_priority;
     DevBuf<uint32_t> d_spp;
     DevBuf<uint8_t> d_mask;
     BudgetWorkspace w;
-    BUDGET_TRY(d_value.alloc(size_t(n) * 3));
-    BUDGET_TRY(d_se.alloc(size_t(n) * 3));
-    BUDGET_TRY(d_spp.alloc(size_t(n)));
-    BUDGET_TRY(d_mask.alloc(size_t(n)));
-    if (out_priority) BUDGET_TRY(d_priority.alloc(size_t(n)));
-    BUDGET_TRY(w.alloc(n));
-    BUDGET_TRY(hipMemcpy(d_value.p, linear_rgb, size_t(n) * 3 * sizeof(double), hipMemcpyHostToDevice));
-    BUDGET_TRY(hipMemcpy(d_se.p, stderr_rgb, size_t(n) * 3 * sizeof(double), hipMemcpyHostToDevice));
-    BUDGET_TRY(hipMemcpy(d_spp.p, spp, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, d_value.alloc(size_t(n) * 3));
+    HIP_TRY_AS(at, d_se.alloc(size_t(n) * 3));
+    HIP_TRY_AS(at, d_spp.alloc(size_t(n)));
+    HIP_TRY_AS(at, d_mask.alloc(size_t(n)));
+    if (out_priority) HIP_TRY_AS(at, d_priority.alloc(size_t(n)));
+    HIP_TRY_AS(at, w.alloc(n));
+    HIP_TRY_AS(at, hipMemcpy(d_value.p, linear_rgb, size_t(n) * 3 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(d_se.p, stderr_rgb, size_t(n) * 3 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(d_spp.p, spp, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice));
     Event ev0, ev1;
-    BUDGET_TRY(create_event(ev0));
-    BUDGET_TRY(create_event(ev1));
+    HIP_TRY_AS(at, create_event(ev0));
+    HIP_TRY_AS(at, create_event(ev1));
     const hipStream_t stream = nullptr;
     const BudgetSelectState* st = (const BudgetSelectState*)w.st.p;
-    BUDGET_TRY(hipEventRecord(ev0.get(), stream));
+    HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
     hipLaunchKernelGGL(budget_keys_maps_kernel, budget_grid(n), dim3(BUDGET_BLOCK), 0, stream, n, d_value.p, d_se.p, d_spp.p, cap, rel_error, abs_error,
                        w.key_hi.p, out_priority ? d_priority.p : nullptr);
     budget_select_launch(w, max_pixels, stream);
     hipLaunchKernelGGL(budget_mask_kernel, budget_grid(n), dim3(BUDGET_BLOCK), 0, stream, n, w.key_hi.p, st, width, 0u, d_mask.p);
-    BUDGET_TRY(hipGetLastError());
-    BUDGET_TRY(hipEventRecord(ev1.get(), stream));
-    BUDGET_TRY(hipDeviceSynchronize());
+    HIP_TRY_AS(at, hipGetLastError());
+    HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
+    HIP_TRY_AS(at, hipDeviceSynchronize());
     if (kernel_ms) {
         float ms = 0;
-        BUDGET_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+        HIP_TRY_AS(at, hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
         *kernel_ms = ms;
     }
-    if (out_mask) BUDGET_TRY(hipMemcpy(out_mask, d_mask.p, size_t(n), hipMemcpyDeviceToHost));
-    if (out_priority) BUDGET_TRY(hipMemcpy(out_priority, d_priority.p, size_t(n) * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_mask) HIP_TRY_AS(at, hipMemcpy(out_mask, d_mask.p, size_t(n), hipMemcpyDeviceToHost));
+    if (out_priority) HIP_TRY_AS(at, hipMemcpy(out_priority, d_priority.p, size_t(n) * sizeof(double), hipMemcpyDeviceToHost));
     if (out_selected) {
         BudgetSelectState host;
-        BUDGET_TRY(hipMemcpy(&host, w.st.p, sizeof(host), hipMemcpyDeviceToHost));
+        HIP_TRY_AS(at, hipMemcpy(&host, w.st.p, sizeof(host), hipMemcpyDeviceToHost));
         *out_selected = host.selected;
     }
     return RTTNW_OK;

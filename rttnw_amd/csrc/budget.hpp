@@ -1,6 +1,6 @@
 // budget.hpp — what render_adaptive_api.cpp calls for rttnw_budget_select and for the rounds of rttnw_render_adaptive_budget and
 // rttnw_render_adaptive_budget_denoised (include/rttnw_hip.h has the contracts, DESIGN.md §10a "budgeted form" and "filter-guided budgeted form" the
-// why): budget.hip holds the launch code, budget_kernels.hpp and guided_budget_kernels.hpp the kernels, budget_select.hpp the arithmetic.  The *_launch functions enqueue on `stream` and nothing else — no allocation, no copy, no wait.
+// why): budget.hip holds the launch code, budget_kernels.hpp the kernels, budget_select.hpp the arithmetic.  The *_launch functions enqueue on `stream` and nothing else — no allocation, no copy, no wait.
 #pragma once
 #include "render_common.hpp"
 
@@ -27,10 +27,7 @@ int budget_round_launch(const BudgetWorkspace& w, uint32_t precision, const void
                         uint32_t height, uint32_t cap, uint32_t pass_spp, double rel_error, double abs_error, uint64_t max_pixels, uint8_t* d_select,
                         uint32_t* d_record, hipStream_t stream);
 
-// rttnw_render_adaptive_budget_denoised's own steps (guided_budget_kernels.hpp), over row-major maps of the frame on one device.
-// Behind a round's raw(): guided_raw_launch (guided.hpp) with the valid byte (count > 0) of every pixel, w*h bytes, beside its maps.
-int guided_budget_raw_launch(uint32_t precision, const void* d_means, const double* d_aux, double* d_mean, double* d_variance, double* d_raw_stderr,
-                             uint32_t* d_spp, uint8_t* d_valid, uint32_t width, uint32_t height, hipStream_t stream);
+// rttnw_render_adaptive_budget_denoised's own selection steps, over row-major maps of the frame on one device.
 // Behind a round's filter: sqrt of the filtered variance of every pixel (w*h*3) and, in w.key_hi, the keys of rttnw_budget_select on (d_den, that
 // root, spp') — spp' = cap for a pixel with samples whose own standard error (d_raw_stderr) is 0 in r, g and b.
 int guided_budget_rank_launch(const BudgetWorkspace& w, const double* d_den, const double* d_var_f, const double* d_raw_stderr, const uint32_t* d_spp,

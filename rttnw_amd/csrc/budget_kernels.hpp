@@ -10,11 +10,6 @@ namespace rt {
 
 constexpr uint32_t BUDGET_BLOCK = 256u;
 
-// Packed index of pixel (x, y) of a frame that lives on one rank (untile_kernel's addressing with world == 1)
-__device__ __forceinline__ unsigned long long budget_packed_index(uint32_t x, uint32_t y, uint32_t tiles_x) {
-    return tile_permuted(x >> 3, y >> 3, tiles_x) * 64ull + ((y & 7u) << 3) + (x & 7u);
-}
-
 // What a selection leaves on the device between its launches
 struct BudgetSelectState {
     BudgetKey prefix;  // the digits fixed so far, zeros below; behind the last digit: the smallest selected key
@@ -44,7 +39,7 @@ __global__ void budget_keys_packed_kernel(const R* __restrict__ means, const dou
                                           uint32_t cap, double rel_error, double abs_error, uint64_t* __restrict__ key_hi) {
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= width || y >= height) return;
-    const unsigned long long src = budget_packed_index(x, y, tiles_x), q = (unsigned long long)y * width + x;
+    const unsigned long long src = packed_index(x, y, tiles_x), q = (unsigned long long)y * width + x;
     const uint32_t s = uint32_t(aux[src * 4 + 3]);
     double v[3] = {0.0, 0.0, 0.0}, e[3] = {0.0, 0.0, 0.0};
     if (s != 0u)
@@ -128,7 +123,7 @@ __global__ void __launch_bounds__(BUDGET_BLOCK) budget_mask_kernel(unsigned long
     for (unsigned long long q = blockIdx.x * (unsigned long long)BUDGET_BLOCK + threadIdx.x; q < n; q += gridDim.x * (unsigned long long)BUDGET_BLOCK) {
         const BudgetKey k = {key_hi[q], 0xFFFFFFFFu - uint32_t(q)};
         const uint8_t on = any && k.hi != 0ull && budget_key_ge(k, threshold) ? 1u : 0u;
-        const unsigned long long dst = tiles_x ? budget_packed_index(uint32_t(q % width), uint32_t(q / width), tiles_x) : q;
+        const unsigned long long dst = tiles_x ? packed_index(uint32_t(q % width), uint32_t(q / width), tiles_x) : q;
         mask[dst] = on;
     }
 }
@@ -164,6 +159,32 @@ __global__ void __launch_bounds__(BUDGET_BLOCK) budget_census_kernel(const uint8
         for (uint32_t i = threadIdx.x; i < BUDGET_LDS_LEVELS && base + i < n_levels; i += BUDGET_BLOCK)
             if (bins[i] != 0u) atomicAdd(&record[1u + base + i], bins[i]);
         __syncthreads();
+    }
+}
+
+// ---- rttnw_render_adaptive_budget_denoised's keys (DESIGN.md §10a "filter-guided budgeted form"), between a round's filter and its selection.
+// The rank: se_f = sqrt(var_f) of every pixel (+inf where the filter left nothing: its variance there is +inf), and the high word of the key
+// rttnw_budget_select gives the pixel on (den, se_f, spp') — spp' = cap, "not a candidate", for a pixel that holds samples and whose OWN standard
+// error is 0 in r, g and b, spp otherwise.  As in budget_keys_maps_kernel the colour and the error of a pixel without samples are never read into
+// the key.  Row-major maps in, row-major keys out (the mask kernel takes them to packed places).
+__global__ void __launch_bounds__(BUDGET_BLOCK) guided_budget_rank_kernel(unsigned long long n, const double* __restrict__ den, const double* __restrict__ var_f,
+                                                                          const double* __restrict__ raw_stderr, const uint32_t* __restrict__ spp,
+                                                                          uint32_t cap, double rel_error, double abs_error,
+                                                                          double* __restrict__ stderr_f, uint64_t* __restrict__ key_hi) {
+    for (unsigned long long q = blockIdx.x * (unsigned long long)BUDGET_BLOCK + threadIdx.x; q < n; q += gridDim.x * (unsigned long long)BUDGET_BLOCK) {
+        const uint32_t s = spp[q];
+        double v[3] = {0.0, 0.0, 0.0}, e[3] = {0.0, 0.0, 0.0};
+        bool own_zero = s != 0u;
+        for (int ch = 0; ch < 3; ++ch) {
+            const double se = sqrt(var_f[q * 3ull + ch]);
+            stderr_f[q * 3ull + ch] = se;
+            if (s != 0u) {
+                v[ch] = den[q * 3ull + ch];
+                e[ch] = se;
+                own_zero = own_zero && raw_stderr[q * 3ull + ch] == 0.0;
+            }
+        }
+        key_hi[q] = budget_key(budget_priority(v, e, own_zero ? cap : s, cap, rel_error, abs_error), uint32_t(q)).hi;
     }
 }
 

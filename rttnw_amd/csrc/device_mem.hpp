@@ -72,6 +72,13 @@ template <typename T> struct DevBuf {
     }
 };
 
+// A caller's host array to a fresh buffer of exactly `count` elements (DevBuf::upload is the padded form for record vectors)
+template <typename T> hipError_t upload(DevBuf<T>& b, const T* src, size_t count) {
+    hipError_t e = b.alloc(count);
+    if (e == hipSuccess) e = hipMemcpy(b.p, src, count * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+}
+
 struct EventDestroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
 struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
 using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;

@@ -1,6 +1,6 @@
 // feature_api.cpp — the extern "C" half of rttnw_render_features, rttnw_denoise, rttnw_denoise_nlm and rttnw_reconstruct (include/rttnw_hip.h):
-// argument checks, then the feature pass of the requested arithmetic build (feature_kernels.hpp), the denoiser's device half (denoise.hip), the
-// non-local-means filter's (nlm.hip) or the reconstruction's (reconstruct.hip).  Host code only.
+// argument checks, then the feature pass of the requested arithmetic build (feature_kernels.hpp), the device half of the denoiser and of the
+// reconstruction (denoise.hip) or the non-local-means filter's (nlm.hip).  Host code only.
 #include "feature_api.hpp"
 #include "nlm.hpp"
 
@@ -28,8 +28,8 @@ int rttnw_denoise(uint32_t width, uint32_t height, const double* linear_rgb, con
         return RTTNW_ERR_INVALID;
     }
     const rt::DenoiseParams prm = rt::denoise_params(d->sigma_luminance, d->sigma_normal, d->sigma_depth, variance_rgb != nullptr);
-    return rt::denoise_device(width, height, linear_rgb, variance_rgb, albedo, normal, depth, alpha, d->iterations, prm, out_linear_rgb, out_rgba8,
-                              out_variance_rgb, kernel_ms);
+    return rt::atrous_device("denoise", width, height, linear_rgb, variance_rgb, nullptr, albedo, normal, depth, alpha, d->iterations, prm, out_linear_rgb,
+                             out_rgba8, out_variance_rgb, nullptr, kernel_ms);
 }
 
 int rttnw_denoise_nlm(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b,
@@ -69,8 +69,8 @@ int rttnw_reconstruct(uint32_t width, uint32_t height, const double* linear_rgb,
         return RTTNW_ERR_INVALID;
     }
     const rt::DenoiseParams prm = rt::denoise_params(d->sigma_luminance, d->sigma_normal, d->sigma_depth, variance_rgb != nullptr);
-    return rt::reconstruct_device(width, height, linear_rgb, variance_rgb, valid, albedo, normal, depth, alpha, d->iterations, prm, out_linear_rgb,
-                                  out_rgba8, out_variance_rgb, out_valid, kernel_ms);
+    return rt::atrous_device("reconstruct", width, height, linear_rgb, variance_rgb, valid, albedo, normal, depth, alpha, d->iterations, prm, out_linear_rgb,
+                             out_rgba8, out_variance_rgb, out_valid, kernel_ms);
 }
 
 } // extern "C"

@@ -1,6 +1,6 @@
 // feature_api.hpp — what feature_api.cpp (the extern "C" half of rttnw_render_features and rttnw_denoise) calls: the feature pass's launch
 // code per arithmetic build (feature_kernels.hpp, instantiated in features_f32.hip / features_f64.hip / features_f64_strict.hip) and the
-// denoiser's device half (denoise.hip), and rttnw_reconstruct's (reconstruct.hip).  Kept out of render_common.hpp: the render kernels' translation units do not read it.
+// device half of the denoiser and of rttnw_reconstruct (denoise.hip).  Kept out of render_common.hpp: the render kernels' translation units do not read it.
 #pragma once
 #include "render_common.hpp"
 #include "denoise.hpp"
@@ -15,27 +15,17 @@ namespace rt {
     X(R, render_features_device_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, double* d_maps, hipStream_t stream))
 RT_DECLARE_BUILDS(RT_FEATURE_ENTRY_POINTS)
 
-// rttnw_denoise's device half (denoise.hip): host arrays in, host arrays out, blocking, on the current device.
-int denoise_device(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const double* albedo, const double* normal,
-                   const double* depth, const double* alpha, uint32_t iterations, const DenoiseParams& prm, double* out_linear_rgb, uint8_t* out_rgba8,
-                   double* out_variance_rgb, double* kernel_ms);
-// ... and its passes alone, enqueued on `stream` over buffers that are already on the device (the result: d_c[out], d_v[out], d_rgba)
-int denoise_passes_device(uint32_t width, uint32_t height, const double* d_in, const double* d_var, const double* d_albedo, const double* d_normal,
-                          const double* d_depth, const double* d_alpha, uint32_t iterations, const DenoiseParams& prm, double* const d_c[2],
-                          double* const d_v[2], uint8_t* d_rgba, hipStream_t stream, int& out);
-
-// rttnw_reconstruct's device half (reconstruct.hip): rttnw_denoise's with a "holds a value" byte per pixel in and out (reconstruct.hpp)
-int reconstruct_device(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const uint8_t* valid, const double* albedo,
-                       const double* normal, const double* depth, const double* alpha, uint32_t iterations, const DenoiseParams& prm,
-                       double* out_linear_rgb, uint8_t* out_rgba8, double* out_variance_rgb, uint8_t* out_valid, double* kernel_ms);
-// ... and its passes alone, enqueued on `stream` (the result: d_c[out], d_v[out], d_rgba, d_out_valid; d_h: the two ping-pong flag buffers, w*h bytes each)
-int reconstruct_passes_device(uint32_t width, uint32_t height, const double* d_in, const double* d_var, const uint8_t* d_valid, const double* d_albedo,
-                              const double* d_normal, const double* d_depth, const double* d_alpha, uint32_t iterations, const DenoiseParams& prm,
-                              double* const d_c[2], double* const d_v[2], uint8_t* const d_h[2], uint8_t* d_rgba, uint8_t* d_out_valid,
-                              hipStream_t stream, int& out);
-// What rttnw_render_preview (render_adaptive_api.cpp) enqueues around its rounds: the alive bytes of the lattice x % 2^level == 0 && y % 2^level == 0 in the
-// packed order of a frame on one rank, in place of guided_begin_launch's all-alive bytes; and the valid byte (spp != 0) of every pixel of the frame
-int preview_lattice_launch(uint8_t* d_alive, uint32_t pixels_per_rank, uint32_t width, uint32_t height, uint32_t level, hipStream_t stream);
-int preview_valid_launch(const uint32_t* d_spp, uint8_t* d_valid, uint32_t width, uint32_t height, hipStream_t stream);
+// rttnw_denoise's and rttnw_reconstruct's device half (denoise.hip): host arrays in, host arrays out (each optional), blocking, on the current
+// device.  `call`: "denoise" with valid == nullptr (out_valid is then not written), "reconstruct" with the "holds a value" byte of every pixel.
+int atrous_device(const char* call, uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const uint8_t* valid,
+                  const double* albedo, const double* normal, const double* depth, const double* alpha, uint32_t iterations, const DenoiseParams& prm,
+                  double* out_linear_rgb, uint8_t* out_rgba8, double* out_variance_rgb, uint8_t* out_valid, double* kernel_ms);
+// ... and its passes alone, enqueued on `stream` over buffers that are already on the device (the result: d_c[out], d_v[out], d_rgba and, with
+// flags, d_out_valid).  d_valid == nullptr: no flags, rttnw_denoise's kernels; d_h (the two ping-pong flag buffers, w*h bytes each) and
+// d_out_valid may then be nullptr.
+int atrous_passes_device(uint32_t width, uint32_t height, const double* d_in, const double* d_var, const uint8_t* d_valid, const double* d_albedo,
+                         const double* d_normal, const double* d_depth, const double* d_alpha, uint32_t iterations, const DenoiseParams& prm,
+                         double* const d_c[2], double* const d_v[2], uint8_t* const d_h[2], uint8_t* d_rgba, uint8_t* d_out_valid, hipStream_t stream,
+                         int& out);
 
 } // namespace rt

@@ -1,4 +1,4 @@
-// guided.hip — the device half of rttnw_render_adaptive_denoised's own steps (guided.hpp): the launch code of guided_kernels.hpp.  One
+// guided.hip — the device half of the filtering adaptive forms' own steps (guided.hpp): the launch code of guided_kernels.hpp.  One
 // translation unit for every precision: its kernels only widen the packed means, so they need no copy per arithmetic build.
 #include "guided.hpp"
 #include "guided_kernels.hpp"
@@ -7,25 +7,25 @@ namespace rt {
 
 static dim3 guided_grid(uint32_t width, uint32_t height) { return dim3((width + 31) / 32, (height + 7) / 8); }
 
-int guided_begin_launch(uint8_t* d_alive, uint32_t pixels_per_rank, uint32_t width, uint32_t height, hipStream_t stream) {
+int guided_lattice_launch(uint8_t* d_alive, uint32_t pixels_per_rank, uint32_t width, uint32_t height, uint32_t level, hipStream_t stream) {
     rttnw_tile_layout L;
     fill_layout(width, height, 1, L);
     HIP_TRY(hipMemsetAsync(d_alive, 0, pixels_per_rank, stream));
-    hipLaunchKernelGGL(guided_begin_kernel, guided_grid(width, height), dim3(32, 8), 0, stream, d_alive, width, height, L.tiles_x);
+    hipLaunchKernelGGL(guided_lattice_kernel, guided_grid(width, height), dim3(32, 8), 0, stream, d_alive, width, height, L.tiles_x, level);
     HIP_TRY(hipGetLastError());
     return RTTNW_OK;
 }
 
 int guided_raw_launch(uint32_t precision, const void* d_means, const double* d_aux, double* d_mean, double* d_variance, double* d_raw_stderr, uint32_t* d_spp,
-                      uint32_t width, uint32_t height, hipStream_t stream) {
+                      uint8_t* d_valid, uint32_t width, uint32_t height, hipStream_t stream) {
     rttnw_tile_layout L;
     fill_layout(width, height, 1, L);
     if (precision == RTTNW_F32)
         hipLaunchKernelGGL(guided_raw_kernel<float>, guided_grid(width, height), dim3(32, 8), 0, stream, (const float*)d_means, d_aux, d_mean, d_variance,
-                           d_raw_stderr, d_spp, width, height, L.tiles_x);
+                           d_raw_stderr, d_spp, d_valid, width, height, L.tiles_x);
     else
         hipLaunchKernelGGL(guided_raw_kernel<double>, guided_grid(width, height), dim3(32, 8), 0, stream, (const double*)d_means, d_aux, d_mean, d_variance,
-                           d_raw_stderr, d_spp, width, height, L.tiles_x);
+                           d_raw_stderr, d_spp, d_valid, width, height, L.tiles_x);
     HIP_TRY(hipGetLastError());
     return RTTNW_OK;
 }

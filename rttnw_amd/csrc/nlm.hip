@@ -100,76 +100,59 @@ __global__ void nlm_finish_kernel(uint32_t n, const double* __restrict__ fa, con
 
 } // namespace
 
-#define NLM_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            set_last_error(std::string("denoise_nlm: " #expr ": ") + hipGetErrorString(e_));          \
-            return RTTNW_ERR_HIP;                                                                      \
-        }                                                                                              \
-    } while (0)
-
 int nlm_device(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b, const NlmParams& prm,
                double* out_linear_rgb, uint8_t* out_rgba8, double* out_half_a, double* out_half_b, double* out_error_rgb, double* kernel_ms) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        set_last_error("denoise_nlm: no HIP device available (this library has no CPU fallback)");
-        return RTTNW_ERR_HIP;
-    }
+    if (int rc = require_device("denoise_nlm")) return rc;
+    const char* const at = "denoise_nlm: ";
     const size_t npx = size_t(width) * height;
     const bool has_var = var_a != nullptr;
-    auto upload = [](DevBuf<double>& b, const double* src, size_t count) -> hipError_t {
-        hipError_t e = b.alloc(count);
-        if (e == hipSuccess) e = hipMemcpy(b.p, src, count * sizeof(double), hipMemcpyHostToDevice);
-        return e;
-    };
     DevBuf<double> d_a, d_b, d_va, d_vb, d_fa, d_fb, d_out, d_err;
     DevBuf<uint8_t> d_rgba;
-    NLM_TRY(upload(d_a, half_a, npx * 3));
-    NLM_TRY(upload(d_b, half_b, npx * 3));
+    HIP_TRY_AS(at, upload(d_a, half_a, npx * 3));
+    HIP_TRY_AS(at, upload(d_b, half_b, npx * 3));
     if (has_var) {
-        NLM_TRY(upload(d_va, var_a, npx * 3));
-        NLM_TRY(upload(d_vb, var_b, npx * 3));
+        HIP_TRY_AS(at, upload(d_va, var_a, npx * 3));
+        HIP_TRY_AS(at, upload(d_vb, var_b, npx * 3));
     } else {
-        NLM_TRY(d_va.alloc(npx * 3)); // the pair variance: one array for both guides
+        HIP_TRY_AS(at, d_va.alloc(npx * 3)); // the pair variance: one array for both guides
     }
-    NLM_TRY(d_fa.alloc(npx * 3));
-    NLM_TRY(d_fb.alloc(npx * 3));
-    NLM_TRY(d_out.alloc(npx * 3));
-    NLM_TRY(d_err.alloc(npx * 3));
-    NLM_TRY(d_rgba.alloc(npx * 4));
+    HIP_TRY_AS(at, d_fa.alloc(npx * 3));
+    HIP_TRY_AS(at, d_fb.alloc(npx * 3));
+    HIP_TRY_AS(at, d_out.alloc(npx * 3));
+    HIP_TRY_AS(at, d_err.alloc(npx * 3));
+    HIP_TRY_AS(at, d_rgba.alloc(npx * 4));
     // the large tile where its LDS fits a CU, the small one — which fits at every radius the entry point accepts — otherwise
     const bool large = nlm_lds_bytes(NLM_TILE_LARGE, prm.r, prm.f) <= NLM_LDS_BYTES;
     const uint32_t tile = large ? NLM_TILE_LARGE : NLM_TILE_SMALL;
     const size_t lds_bytes = nlm_lds_bytes(tile, prm.r, prm.f);
     void (*const filter)(NlmView, NlmParams, double*, double*) = large ? nlm_filter_kernel<int(NLM_TILE_LARGE)> : nlm_filter_kernel<int(NLM_TILE_SMALL)>;
-    NLM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(filter), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+    HIP_TRY_AS(at, hipFuncSetAttribute(reinterpret_cast<const void*>(filter), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
     Event ev0, ev1;
-    NLM_TRY(create_event(ev0));
-    NLM_TRY(create_event(ev1));
+    HIP_TRY_AS(at, create_event(ev0));
+    HIP_TRY_AS(at, create_event(ev1));
 
     const hipStream_t stream = nullptr;
     const dim3 flat_block(256), value_grid(uint32_t((npx * 3 + 255) / 256));
     const dim3 tiles((width + tile - 1) / tile, (height + tile - 1) / tile, 2);
-    NLM_TRY(hipEventRecord(ev0.get(), stream));
+    HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
     if (!has_var) hipLaunchKernelGGL(nlm_variance_kernel, value_grid, flat_block, 0, stream, width, height, d_a.p, d_b.p, d_va.p);
     const NlmView view{width, height, d_a.p, d_b.p, d_va.p, has_var ? d_vb.p : d_va.p};
     hipLaunchKernelGGL(filter, tiles, dim3(tile * tile), lds_bytes, stream, view, prm, d_fa.p, d_fb.p);
     hipLaunchKernelGGL(nlm_finish_kernel, value_grid, flat_block, 0, stream, uint32_t(npx), d_fa.p, d_fb.p, d_out.p, d_rgba.p, d_err.p);
-    NLM_TRY(hipGetLastError());
-    NLM_TRY(hipEventRecord(ev1.get(), stream));
-    NLM_TRY(hipDeviceSynchronize());
+    HIP_TRY_AS(at, hipGetLastError());
+    HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
+    HIP_TRY_AS(at, hipDeviceSynchronize());
     if (kernel_ms) {
         float ms = 0;
-        NLM_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+        HIP_TRY_AS(at, hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
         *kernel_ms = ms;
     }
     const size_t bytes = npx * 3 * sizeof(double);
-    if (out_linear_rgb) NLM_TRY(hipMemcpy(out_linear_rgb, d_out.p, bytes, hipMemcpyDeviceToHost));
-    if (out_rgba8) NLM_TRY(hipMemcpy(out_rgba8, d_rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_half_a) NLM_TRY(hipMemcpy(out_half_a, d_fa.p, bytes, hipMemcpyDeviceToHost));
-    if (out_half_b) NLM_TRY(hipMemcpy(out_half_b, d_fb.p, bytes, hipMemcpyDeviceToHost));
-    if (out_error_rgb) NLM_TRY(hipMemcpy(out_error_rgb, d_err.p, bytes, hipMemcpyDeviceToHost));
+    if (out_linear_rgb) HIP_TRY_AS(at, hipMemcpy(out_linear_rgb, d_out.p, bytes, hipMemcpyDeviceToHost));
+    if (out_rgba8) HIP_TRY_AS(at, hipMemcpy(out_rgba8, d_rgba.p, npx * 4, hipMemcpyDeviceToHost));
+    if (out_half_a) HIP_TRY_AS(at, hipMemcpy(out_half_a, d_fa.p, bytes, hipMemcpyDeviceToHost));
+    if (out_half_b) HIP_TRY_AS(at, hipMemcpy(out_half_b, d_fb.p, bytes, hipMemcpyDeviceToHost));
+    if (out_error_rgb) HIP_TRY_AS(at, hipMemcpy(out_error_rgb, d_err.p, bytes, hipMemcpyDeviceToHost));
     return RTTNW_OK;
 }
 

@@ -1,6 +1,7 @@
 // render_adaptive_api.cpp — the adaptive family beyond rttnw_render_adaptive: the forms over the ranks of a node (multi, resume, region), the round driver
 // of the forms that run one rank on the scene's device (RankRounds) and those forms (denoised, preview, budget, budget_denoised), and rttnw_budget_select.  Host code
-// only; the kernels live in render_f32.hip / render_f64.hip, denoise.hip, reconstruct.hip, guided.hip and budget.hip.
+// only; the kernels live in render_f32.hip / render_f64.hip, denoise.hip (the filter, with and without flags), guided.hip (the filtering forms' own
+// steps) and budget.hip (the selection).
 #include "render_multi.hpp"
 #include "adaptive_state.hpp"
 #include "feature_api.hpp"
@@ -523,6 +524,77 @@ struct RankRounds {
     }
 };
 
+// The filter half of the forms that filter (denoised, preview, budget_denoised), beside a RankRounds: the workspace of the à-trous passes, the
+// feature pass that guides them, the raw maps they read, the passes themselves and the copies of what they leave to the host.  Row-major buffers
+// of the frame on the scene's device; when a form runs each step — per round, or once behind its rounds — stays in the form.
+struct FilterStage {
+    RankRounds& r;
+    const size_t npx;
+    const bool flags, with_variance; // a pixel may hold no value yet (rttnw_reconstruct's passes); a variance goes through the filter
+    DevBuf<double> maps, mean, variance, raw_stderr, stderr_f, d_c[2], d_v[2]; // stderr_f: the form's own step behind the filter writes it
+    DevBuf<uint32_t> spp;
+    DevBuf<uint8_t> rgba, valid, valid_out, holds[2];
+    float feature_ms = 0;
+    int out = 0; // filter(): the image is left in d_c[out], its variance in d_v[out]
+
+    FilterStage(RankRounds& r, bool flags, bool with_variance) : r(r), npx(r.npx), flags(flags), with_variance(with_variance) {}
+    // Everything of the stage that allocates, before the first launch: a form without flags or without a variance has no buffers for them
+    int open() {
+        HIP_TRY(maps.alloc(npx * 8)); HIP_TRY(mean.alloc(npx * 3)); HIP_TRY(variance.alloc(npx * 3)); HIP_TRY(raw_stderr.alloc(npx * 3));
+        HIP_TRY(spp.alloc(npx)); HIP_TRY(rgba.alloc(npx * 4));
+        if (with_variance) HIP_TRY(stderr_f.alloc(npx * 3));
+        if (flags) { HIP_TRY(valid.alloc(npx)); HIP_TRY(valid_out.alloc(npx)); }
+        for (int k = 0; k < 2; ++k) {
+            HIP_TRY(d_c[k].alloc(npx * 3));
+            if (with_variance) HIP_TRY(d_v[k].alloc(npx * 3));
+            if (flags) HIP_TRY(holds[k].alloc(npx));
+        }
+        return 0;
+    }
+    // The feature maps, which stay on the device (the pass times itself between d->ev0 and d->ev1 and waits for the stream)
+    int features(uint32_t feature_spp) {
+        rttnw_params pf = r.p;
+        pf.spp = feature_spp ? feature_spp : r.B;
+        if (int rc = RT_BY_PRECISION(r.p.precision, render_features_device_t, r.s, r.cam, &pf, maps.p, r.stream)) return rc;
+        HIP_TRY(hipEventElapsedTime(&feature_ms, r.d->ev0.get(), r.d->ev1.get()));
+        return 0;
+    }
+    const double* albedo() const { return maps.p; }
+    const double* normal() const { return maps.p + npx * 3; }
+    const double* depth() const { return maps.p + npx * 6; }
+    const double* alpha() const { return maps.p + npx * 7; }
+    // The raw maps of every pixel of the frame (with flags: and the valid byte of those that hold samples)
+    int raw() {
+        if (int rc = r.raw()) return rc;
+        return guided_raw_launch(r.p.precision, r.means.p, r.aux.p, mean.p, variance.p, raw_stderr.p, spp.p, flags ? valid.p : nullptr, r.p.width, r.p.height,
+                                 r.stream);
+    }
+    // The passes over the raw maps
+    int filter(const rttnw_denoise_params& dn) {
+        const DenoiseParams prm = denoise_params(dn.sigma_luminance, dn.sigma_normal, dn.sigma_depth, with_variance);
+        double* const c[2] = {d_c[0].p, d_c[1].p};
+        double* const v[2] = {d_v[0].p, d_v[1].p};
+        uint8_t* const h[2] = {holds[0].p, holds[1].p};
+        return atrous_passes_device(r.p.width, r.p.height, mean.p, with_variance ? variance.p : nullptr, flags ? valid.p : nullptr, albedo(), normal(), depth(),
+                                    alpha(), dn.iterations, prm, c, v, h, rgba.p, valid_out.p, r.stream, out);
+    }
+    const double* filtered() const { return d_c[out].p; }
+    const double* filtered_variance() const { return d_v[out].p; }
+    // What the last filter() and raw() left, to the host arrays the caller gave (the device is idle: the form has waited)
+    int copy_out(double* out_linear_rgb, uint8_t* out_rgba8, uint8_t* out_valid, uint32_t* out_spp, double* out_stderr_rgb, double* out_raw_linear_rgb,
+                 double* out_raw_stderr_rgb) {
+        const size_t rgb_bytes = npx * 3 * sizeof(double);
+        if (out_linear_rgb) HIP_TRY(hipMemcpy(out_linear_rgb, filtered(), rgb_bytes, hipMemcpyDeviceToHost));
+        if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, rgba.p, npx * 4, hipMemcpyDeviceToHost));
+        if (out_valid) HIP_TRY(hipMemcpy(out_valid, valid_out.p, npx, hipMemcpyDeviceToHost));
+        if (out_spp) HIP_TRY(hipMemcpy(out_spp, spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (out_stderr_rgb) HIP_TRY(hipMemcpy(out_stderr_rgb, stderr_f.p, rgb_bytes, hipMemcpyDeviceToHost));
+        if (out_raw_linear_rgb) HIP_TRY(hipMemcpy(out_raw_linear_rgb, mean.p, rgb_bytes, hipMemcpyDeviceToHost));
+        if (out_raw_stderr_rgb) HIP_TRY(hipMemcpy(out_raw_stderr_rgb, raw_stderr.p, rgb_bytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+
 // rttnw_render_adaptive_denoised (include/rttnw_hip.h has the contract, DESIGN.md §10a "filter-guided form" the why): adaptive rounds whose stopping
 // rule reads the FILTERED image.  A round is one level of the windowed form's loop — the list of the 2x2 blocks that hold an alive pixel, the list pass
 // over it with the windowed form's arguments (a cap of (k+1)B and zero tolerances), the raw values — and then the denoiser's passes and the stop kernel
@@ -531,33 +603,21 @@ static int adaptive_denoised_render(::rttnw_scene* s, const rttnw_camera_desc* c
                                     double* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, double* out_stderr_rgb, double* out_raw_linear_rgb,
                                     double* out_raw_stderr_rgb, double* state_out, rttnw_stats* stats) {
     RankRounds r(s, cam, p, a);
+    FilterStage f(r, false, true);
     DeviceState* d = r.d;
-    const size_t npx = r.npx;
     const hipStream_t stream = r.stream;
     // everything that allocates, before the first launch (d->ad_active: the resolve step's active bytes under the pass's own cap — not read here, the
     // alive bytes decide)
     if (int rc = r.open(d->ad_active, r.n_blocks, nullptr, state_out != nullptr, stats)) return rc;
-    DevBuf<uint8_t> alive, rgba;
-    DevBuf<uint32_t> spp;
-    DevBuf<double> maps, mean, variance, raw_stderr, stderr_f, d_c[2], d_v[2];
-    HIP_TRY(alive.alloc(r.ppr)); HIP_TRY(rgba.alloc(npx * 4)); HIP_TRY(spp.alloc(npx)); HIP_TRY(maps.alloc(npx * 8));
-    HIP_TRY(mean.alloc(npx * 3)); HIP_TRY(variance.alloc(npx * 3)); HIP_TRY(raw_stderr.alloc(npx * 3)); HIP_TRY(stderr_f.alloc(npx * 3));
-    for (int k = 0; k < 2; ++k) { HIP_TRY(d_c[k].alloc(npx * 3)); HIP_TRY(d_v[k].alloc(npx * 3)); }
+    if (int rc = f.open()) return rc;
+    DevBuf<uint8_t> alive;
+    HIP_TRY(alive.alloc(r.ppr));
 
-    // before round 0: the feature maps, which stay on the device, and every pixel of the image alive on zero sums and zero noise state
-    rttnw_params pf = p;
-    pf.spp = g.feature_spp ? g.feature_spp : r.B;
-    if (int rc = RT_BY_PRECISION(p.precision, render_features_device_t, s, cam, &pf, maps.p, stream)) return rc;
-    float feature_ms = 0;
-    HIP_TRY(hipEventElapsedTime(&feature_ms, d->ev0.get(), d->ev1.get()));
-    const double *m_albedo = maps.p, *m_normal = maps.p + npx * 3, *m_depth = maps.p + npx * 6, *m_alpha = maps.p + npx * 7;
-    const DenoiseParams prm = denoise_params(g.denoise.sigma_luminance, g.denoise.sigma_normal, g.denoise.sigma_depth, true);
-    double* const c[2] = {d_c[0].p, d_c[1].p};
-    double* const v[2] = {d_v[0].p, d_v[1].p};
+    // before round 0: the feature maps, and every pixel of the image alive on zero sums and zero noise state
+    if (int rc = f.features(g.feature_spp)) return rc;
     HIP_TRY(hipEventRecord(r.ev0.get(), stream));
     if (int rc = r.start(nullptr)) return rc;
-    if (int rc = guided_begin_launch(alive.p, r.L.pixels_per_rank, p.width, p.height, stream)) return rc;
-    int out = 0;
+    if (int rc = guided_lattice_launch(alive.p, r.L.pixels_per_rank, p.width, p.height, 0u, stream)) return rc;
     for (uint32_t k = 0; k < p.spp / r.B; ++k) {
         // the list of this round: the alive bytes are its active AND its selection bytes
         uint32_t count[2] = {0, 0}; // listed blocks, alive pixels
@@ -565,14 +625,12 @@ static int adaptive_denoised_render(::rttnw_scene* s, const rttnw_camera_desc* c
         if (count[0] == 0) break; // every pixel has stopped
         // 1. trace: the alive pixels, all of which hold exactly kB samples — one level
         if (int rc = r.trace(k, count[0], (k + 1u) * r.B, 0.0, 0.0)) return rc;
-        // 2. raw values of every pixel of the frame
-        if (int rc = r.raw()) return rc;
-        if (int rc = guided_raw_launch(p.precision, r.means.p, r.aux.p, mean.p, variance.p, raw_stderr.p, spp.p, p.width, p.height, stream)) return rc;
-        // 3. filter
-        if (int rc = denoise_passes_device(p.width, p.height, mean.p, variance.p, m_albedo, m_normal, m_depth, m_alpha, g.denoise.iterations, prm, c, v,
-                                           rgba.p, stream, out)) return rc;
+        // 2. raw values of every pixel of the frame, 3. filter
+        if (int rc = f.raw()) return rc;
+        if (int rc = f.filter(g.denoise)) return rc;
         // 4. stop
-        if (int rc = guided_stop_launch(c[out], v[out], raw_stderr.p, a.rel_error, a.abs_error, alive.p, stderr_f.p, p.width, p.height, stream)) return rc;
+        if (int rc = guided_stop_launch(f.filtered(), f.filtered_variance(), f.raw_stderr.p, a.rel_error, a.abs_error, alive.p, f.stderr_f.p, p.width, p.height,
+                                        stream)) return rc;
     }
     if (state_out)
         if (int rc = r.export_state()) return rc;
@@ -581,16 +639,11 @@ static int adaptive_denoised_render(::rttnw_scene* s, const rttnw_camera_desc* c
     if (stats) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, r.ev0.get(), r.ev1.get()));
-        stats->kernel_ms = double(feature_ms) + double(ms);
+        stats->kernel_ms = double(f.feature_ms) + double(ms);
         stats->samples = r.samples;
     }
     // the outputs of the last round that ran
-    if (out_linear_rgb) HIP_TRY(hipMemcpy(out_linear_rgb, c[out], npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_spp) HIP_TRY(hipMemcpy(out_spp, spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_stderr_rgb) HIP_TRY(hipMemcpy(out_stderr_rgb, stderr_f.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_raw_linear_rgb) HIP_TRY(hipMemcpy(out_raw_linear_rgb, mean.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_raw_stderr_rgb) HIP_TRY(hipMemcpy(out_raw_stderr_rgb, raw_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (int rc = f.copy_out(out_linear_rgb, out_rgba8, nullptr, out_spp, out_stderr_rgb, out_raw_linear_rgb, out_raw_stderr_rgb)) return rc;
     return state_out ? r.state_out(state_out) : RTTNW_OK;
 }
 } // namespace rt
@@ -614,7 +667,7 @@ extern "C" int rttnw_render_adaptive_denoised(rttnw_scene* s, const rttnw_camera
 // rttnw_render_preview (include/rttnw_hip.h has the contract, DESIGN.md §10b "a frame from a fraction of its pixels" the why): the adaptive rounds of
 // the windowed form over a LATTICE of the frame, then the feature pass and rttnw_reconstruct's passes, all on buffers that never leave the device.
 // One rank on the scene's device, default stream.  The rounds are adaptive_denoised_render's, with two differences: the bytes that start alive are the
-// lattice's (preview_lattice_launch), and a round's list pass runs under the caller's cap and tolerances, so the resolve step's own stopping rule
+// lattice's (guided_lattice_launch at the caller's level), and a round's list pass runs under the caller's cap and tolerances, so the resolve step's own stopping rule
 // writes the next round's bytes — the alive bytes ARE the pass's active bytes.  Every alive pixel holds exactly kB samples in round k, which is one
 // level of the windowed form's loop: list for list what rttnw_render_adaptive_region traces under mask = the lattice.
 // ---------------------------------------------------------------------------------------------
@@ -623,27 +676,22 @@ static int preview_render(::rttnw_scene* s, const rttnw_camera_desc* cam, const 
                           double* out_linear_rgb, uint8_t* out_rgba8, uint8_t* out_valid, uint32_t* out_spp, double* out_raw_linear_rgb,
                           double* out_raw_stderr_rgb, double* state_out, rttnw_stats* stats) {
     RankRounds r(s, cam, p, a);
+    FilterStage f(r, true, false); // no variance goes into the filter
     DeviceState* d = r.d;
-    const size_t npx = r.npx;
     const hipStream_t stream = r.stream;
     // the blocks that hold a lattice pixel: every block at level 0 and 1, one in 4^(level-1) above
     const uint32_t step = 1u << pv.level, block_step = std::max(step, 2u);
     const uint32_t lattice_blocks = ((p.width + block_step - 1) / block_step) * ((p.height + block_step - 1) / block_step);
     // everything that allocates, before the first launch: the shared part with what a list pass over the lattice's blocks needs, and this call's own
     if (int rc = r.open(d->ad_active, std::min(lattice_blocks, r.n_blocks), nullptr, state_out != nullptr, stats)) return rc;
-    DevBuf<uint8_t> rgba, valid, holds[2], valid_out;
-    DevBuf<uint32_t> spp;
-    DevBuf<double> maps, mean, variance, raw_stderr, d_c[2];
-    HIP_TRY(rgba.alloc(npx * 4)); HIP_TRY(valid.alloc(npx)); HIP_TRY(valid_out.alloc(npx)); HIP_TRY(spp.alloc(npx)); HIP_TRY(maps.alloc(npx * 8));
-    HIP_TRY(mean.alloc(npx * 3)); HIP_TRY(variance.alloc(npx * 3)); HIP_TRY(raw_stderr.alloc(npx * 3));
-    for (int k = 0; k < 2; ++k) { HIP_TRY(d_c[k].alloc(npx * 3)); HIP_TRY(holds[k].alloc(npx)); }
+    if (int rc = f.open()) return rc;
     Event ev2, ev3; // the reconstruction's clock
     HIP_TRY(create_event(ev2)); HIP_TRY(create_event(ev3));
 
     // before round 0: zero sums and zero noise state everywhere, and the lattice alive
     HIP_TRY(hipEventRecord(r.ev0.get(), stream));
     if (int rc = r.start(nullptr)) return rc;
-    if (int rc = preview_lattice_launch(d->ad_active.p, r.L.pixels_per_rank, p.width, p.height, pv.level, stream)) return rc;
+    if (int rc = guided_lattice_launch(d->ad_active.p, r.L.pixels_per_rank, p.width, p.height, pv.level, stream)) return rc;
     for (uint32_t k = 0; k < p.spp / r.B; ++k) {
         uint32_t count[2] = {0, 0}; // listed blocks, alive pixels
         if (int rc = r.list(d->ad_active.p, count)) return rc;
@@ -654,41 +702,22 @@ static int preview_render(::rttnw_scene* s, const rttnw_camera_desc* cam, const 
     // the raw values of every pixel of the frame; a pixel holds a value where it holds samples
     if (state_out)
         if (int rc = r.export_state()) return rc;
-    if (int rc = r.raw()) return rc;
-    if (int rc = guided_raw_launch(p.precision, r.means.p, r.aux.p, mean.p, variance.p, raw_stderr.p, spp.p, p.width, p.height, stream)) return rc;
-    if (int rc = preview_valid_launch(spp.p, valid.p, p.width, p.height, stream)) return rc;
+    if (int rc = f.raw()) return rc;
     HIP_TRY(hipEventRecord(r.ev1.get(), stream));
-    // the features, which stay on the device (the pass times itself between d->ev0 and d->ev1 and waits for the stream) ...
-    rttnw_params pf = p;
-    pf.spp = pv.feature_spp ? pv.feature_spp : r.B;
-    if (int rc = RT_BY_PRECISION(p.precision, render_features_device_t, s, cam, &pf, maps.p, stream)) return rc;
-    float feature_ms = 0;
-    HIP_TRY(hipEventElapsedTime(&feature_ms, d->ev0.get(), d->ev1.get()));
-    // ... and the reconstruction: no variance goes into the filter
-    const double *m_albedo = maps.p, *m_normal = maps.p + npx * 3, *m_depth = maps.p + npx * 6, *m_alpha = maps.p + npx * 7;
-    const DenoiseParams prm = denoise_params(pv.denoise.sigma_luminance, pv.denoise.sigma_normal, pv.denoise.sigma_depth, false);
-    double* const c[2] = {d_c[0].p, d_c[1].p};
-    double* const v[2] = {nullptr, nullptr};
-    uint8_t* const h[2] = {holds[0].p, holds[1].p};
-    int out = 0;
+    // the features, and the reconstruction on its own clock
+    if (int rc = f.features(pv.feature_spp)) return rc;
     HIP_TRY(hipEventRecord(ev2.get(), stream));
-    if (int rc = reconstruct_passes_device(p.width, p.height, mean.p, nullptr, valid.p, m_albedo, m_normal, m_depth, m_alpha, pv.denoise.iterations, prm, c, v,
-                                           h, rgba.p, valid_out.p, stream, out)) return rc;
+    if (int rc = f.filter(pv.denoise)) return rc;
     HIP_TRY(hipEventRecord(ev3.get(), stream));
     HIP_TRY(hipDeviceSynchronize());
     if (stats) {
         float ms = 0, ms_r = 0;
         HIP_TRY(hipEventElapsedTime(&ms, r.ev0.get(), r.ev1.get()));
         HIP_TRY(hipEventElapsedTime(&ms_r, ev2.get(), ev3.get()));
-        stats->kernel_ms = double(ms) + double(feature_ms) + double(ms_r);
+        stats->kernel_ms = double(ms) + double(f.feature_ms) + double(ms_r);
         stats->samples = r.samples;
     }
-    if (out_linear_rgb) HIP_TRY(hipMemcpy(out_linear_rgb, c[out], npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_valid) HIP_TRY(hipMemcpy(out_valid, valid_out.p, npx, hipMemcpyDeviceToHost));
-    if (out_spp) HIP_TRY(hipMemcpy(out_spp, spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_raw_linear_rgb) HIP_TRY(hipMemcpy(out_raw_linear_rgb, mean.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_raw_stderr_rgb) HIP_TRY(hipMemcpy(out_raw_stderr_rgb, raw_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (int rc = f.copy_out(out_linear_rgb, out_rgba8, out_valid, out_spp, nullptr, out_raw_linear_rgb, out_raw_stderr_rgb)) return rc;
     return state_out ? r.state_out(state_out) : RTTNW_OK;
 }
 } // namespace rt
@@ -837,7 +866,7 @@ extern "C" int rttnw_render_adaptive_budget(rttnw_scene* s, const rttnw_camera_d
 // ---------------------------------------------------------------------------------------------
 // rttnw_render_adaptive_budget_denoised (include/rttnw_hip.h has the contract, DESIGN.md §10a "filter-guided budgeted form" the why): the budgeted
 // form's rounds, ranked by the noise of the FILTERED image.  One rank on the scene's device, default stream.  Before round 0 the feature maps, which
-// stay on the device.  A round: the raw maps of every pixel with their valid bytes (raw(), guided_budget_raw_launch), rttnw_reconstruct's passes over
+// stay on the device.  A round: the raw maps of every pixel with their valid bytes (FilterStage::raw), rttnw_reconstruct's passes over
 // them — a pixel may hold nothing yet —, the rank (sqrt of the filtered variance, and the selection's keys on the filtered maps), and from the keys on
 // the budgeted form's own round: the select, the selection bytes, the census, one list pass per occupied level (budget_round_trace).  No byte
 // survives a round — candidates are recomputed from the maps —, which is why a state can come in.  The filter that selects nothing is the call's
@@ -855,42 +884,29 @@ static int adaptive_budget_denoised_render(::rttnw_scene* s, const rttnw_camera_
     const uint64_t round_pixels = bg.round_pixels ? bg.round_pixels : (uint64_t(npx) + 1u) / 2u;
     const hipStream_t stream = r.stream;
     // everything that allocates, before the first launch: the shared part with what a list pass over every block needs (the selection bytes are that
-    // pass's active bytes), and this call's own
-    DevBuf<uint8_t> select, marks, rgba, valid, valid_out, holds[2];
-    DevBuf<uint32_t> record, spp;
-    DevBuf<double> maps, mean, variance, raw_stderr, stderr_f, d_c[2], d_v[2];
+    // pass's active bytes), the filter's, and this call's own
+    FilterStage f(r, true, true);
+    DevBuf<uint8_t> select, marks;
+    DevBuf<uint32_t> record;
     BudgetWorkspace work;
     if (int rc = r.open(select, r.n_blocks, state_in, state_out != nullptr, stats)) return rc;
+    if (int rc = f.open()) return rc;
     HIP_TRY(marks.alloc(r.ppr)); HIP_TRY(record.alloc(1u + size_t(n_levels))); HIP_TRY(work.alloc(npx));
-    HIP_TRY(rgba.alloc(npx * 4)); HIP_TRY(valid.alloc(npx)); HIP_TRY(valid_out.alloc(npx)); HIP_TRY(spp.alloc(npx)); HIP_TRY(maps.alloc(npx * 8));
-    HIP_TRY(mean.alloc(npx * 3)); HIP_TRY(variance.alloc(npx * 3)); HIP_TRY(raw_stderr.alloc(npx * 3)); HIP_TRY(stderr_f.alloc(npx * 3));
-    for (int k = 0; k < 2; ++k) { HIP_TRY(d_c[k].alloc(npx * 3)); HIP_TRY(d_v[k].alloc(npx * 3)); HIP_TRY(holds[k].alloc(npx)); }
 
-    // before round 0: the feature maps (the pass times itself between d->ev0 and d->ev1 and waits for the stream), the state that came in (or zero
-    // sums and zero noise state; the import's active bytes go to `marks` and are not read), and nothing selected
-    rttnw_params pf = p;
-    pf.spp = g.feature_spp ? g.feature_spp : B;
-    if (int rc = RT_BY_PRECISION(p.precision, render_features_device_t, s, cam, &pf, maps.p, stream)) return rc;
-    float feature_ms = 0;
-    HIP_TRY(hipEventElapsedTime(&feature_ms, d->ev0.get(), d->ev1.get()));
-    const double *m_albedo = maps.p, *m_normal = maps.p + npx * 3, *m_depth = maps.p + npx * 6, *m_alpha = maps.p + npx * 7;
-    const DenoiseParams prm = denoise_params(g.denoise.sigma_luminance, g.denoise.sigma_normal, g.denoise.sigma_depth, true);
-    double* const c[2] = {d_c[0].p, d_c[1].p};
-    double* const v[2] = {d_v[0].p, d_v[1].p};
-    uint8_t* const h[2] = {holds[0].p, holds[1].p};
+    // before round 0: the feature maps, the state that came in (or zero sums and zero noise state; the import's active bytes go to `marks` and are
+    // not read), and nothing selected
+    if (int rc = f.features(g.feature_spp)) return rc;
     HIP_TRY(hipEventRecord(r.ev0.get(), stream));
     if (int rc = r.start(marks.p)) return rc;
     HIP_TRY(hipMemsetAsync(select.p, 0, r.ppr, stream)); // (the rest of an edge tile is never selected: a round writes the bytes of the image's pixels only)
     uint64_t remaining = bg.samples, rounds = 0;
     std::vector<uint32_t> census(1u + size_t(n_levels));
-    int out = 0;
     for (;;) {
         // 1. the raw maps of every pixel, 2. the filter, 3. the rank — the call's outputs, if this round selects nothing
-        if (int rc = r.raw()) return rc;
-        if (int rc = guided_budget_raw_launch(p.precision, r.means.p, r.aux.p, mean.p, variance.p, raw_stderr.p, spp.p, valid.p, p.width, p.height, stream)) return rc;
-        if (int rc = reconstruct_passes_device(p.width, p.height, mean.p, variance.p, valid.p, m_albedo, m_normal, m_depth, m_alpha, g.denoise.iterations, prm, c,
-                                               v, h, rgba.p, valid_out.p, stream, out)) return rc;
-        if (int rc = guided_budget_rank_launch(work, c[out], v[out], raw_stderr.p, spp.p, p.spp, a.rel_error, a.abs_error, stderr_f.p, stream)) return rc;
+        if (int rc = f.raw()) return rc;
+        if (int rc = f.filter(g.denoise)) return rc;
+        if (int rc = guided_budget_rank_launch(work, f.filtered(), f.filtered_variance(), f.raw_stderr.p, f.spp.p, p.spp, a.rel_error, a.abs_error, f.stderr_f.p,
+                                               stream)) return rc;
         const uint64_t max_pixels = std::min<uint64_t>(round_pixels, remaining / B);
         if (max_pixels == 0) break; // the budget pays for no further pass
         // the selection on the rank's keys, and in one copy its record: the pixels selected and, per level, the length of the list over them
@@ -909,18 +925,12 @@ static int adaptive_budget_denoised_render(::rttnw_scene* s, const rttnw_camera_
     if (stats) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, r.ev0.get(), r.ev1.get()));
-        stats->kernel_ms = double(feature_ms) + double(ms);
+        stats->kernel_ms = double(f.feature_ms) + double(ms);
         stats->samples = r.samples;
         stats->reserved |= uint32_t(std::min<uint64_t>(rounds, 0xFFFFu)) << 16;
     }
     // the outputs of the last filter that ran
-    if (out_linear_rgb) HIP_TRY(hipMemcpy(out_linear_rgb, c[out], npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_rgba8) HIP_TRY(hipMemcpy(out_rgba8, rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_valid) HIP_TRY(hipMemcpy(out_valid, valid_out.p, npx, hipMemcpyDeviceToHost));
-    if (out_spp) HIP_TRY(hipMemcpy(out_spp, spp.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_stderr_rgb) HIP_TRY(hipMemcpy(out_stderr_rgb, stderr_f.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_raw_linear_rgb) HIP_TRY(hipMemcpy(out_raw_linear_rgb, mean.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_raw_stderr_rgb) HIP_TRY(hipMemcpy(out_raw_stderr_rgb, raw_stderr.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (int rc = f.copy_out(out_linear_rgb, out_rgba8, out_valid, out_spp, out_stderr_rgb, out_raw_linear_rgb, out_raw_stderr_rgb)) return rc;
     return state_out ? r.state_out(state_out) : RTTNW_OK;
 }
 } // namespace rt

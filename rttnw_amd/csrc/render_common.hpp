@@ -30,14 +30,27 @@
 
 namespace rt {
 
-#define HIP_TRY(expr)                                                                      \
+// A HIP call that must succeed: on failure the last error becomes "<text><hip's words>" and the function returns RTTNW_ERR_HIP.  HIP_TRY's text
+// is the call as written, HIP_TRY_AS's the same behind a prefix such as "denoise: " (a string, known at run time or not).  (Both stringify
+// their own argument: handed from one macro to the other it would be macro-expanded first.)
+#define HIP_TRY_TEXT(text, expr)                                                           \
     do {                                                                                   \
         hipError_t e_ = (expr);                                                            \
         if (e_ != hipSuccess) {                                                            \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(e_));             \
+            set_last_error(text + hipGetErrorString(e_));                                  \
             return RTTNW_ERR_HIP;                                                          \
         }                                                                                  \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_TEXT(std::string(#expr) + ": ", expr)
+#define HIP_TRY_AS(prefix, expr) HIP_TRY_TEXT(std::string(prefix) + #expr ": ", expr)
+
+// What the image filters' device halves start with (`call`: "denoise", ...): they take host arrays, not a scene that already found its device
+inline int require_device(const char* call) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) == hipSuccess && count > 0) return 0;
+    set_last_error(std::string(call) + ": no HIP device available (this library has no CPU fallback)");
+    return RTTNW_ERR_HIP;
+}
 
 // A scene's arrays on one device.  A scene is uploaded whole or not at all (upload), and the decoupled kernels' records are added whole or not at
 // all (ensure_quant4): every step builds into local owners, which the members take over only once all of them have succeeded.  An empty

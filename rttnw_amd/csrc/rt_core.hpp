@@ -1787,6 +1787,10 @@ RT_HD uint8_t quantise(float mean) {
 // Tile partition (include/rttnw_hip.h rttnw_tile_layout): rows are rotated by ty so that a column of
 // tiles is spread over all ranks.
 RT_HD uint32_t tile_permuted(uint32_t tx, uint32_t ty, uint32_t tiles_x) { return ty * tiles_x + (tx + ty) % tiles_x; }
+// Packed index of pixel (x, y) of a frame that lives on ONE rank: tile * 64 + y * 8 + x (untile_kernel's addressing with world == 1)
+RT_HD unsigned long long packed_index(uint32_t x, uint32_t y, uint32_t tiles_x) {
+    return tile_permuted(x >> 3, y >> 3, tiles_x) * 64ull + ((y & 7u) << 3) + (x & 7u);
+}
 RT_HD void tile_unpermute(uint32_t permuted, uint32_t tiles_x, uint32_t& tx, uint32_t& ty) {
     ty = permuted / tiles_x;
     uint32_t c = permuted % tiles_x;
