@@ -1,4 +1,4 @@
-"""Host overhead of the six adaptive entry points (multi, resume, region, denoised, preview, budget), two builds of librttnw_hip.so side by side.
+"""Host overhead of seven adaptive entry points (adaptive, multi, resume, region, denoised, preview, budget), two builds of librttnw_hip.so side by side.
 
   python profiles/adaptive_host_overhead.py --parent /path/to/parent/librttnw_hip.so [--new PATH] [--rounds 6] [--reps 2] [--out result.json]
 
@@ -18,7 +18,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W = H = 512
 CAP, B, REL, ABS = 64, 16, 0.05, 0.01
-CALLS = ("multi", "resume", "region", "denoised", "preview", "budget")
+CALLS = ("adaptive", "multi", "resume", "region", "denoised", "preview", "budget")
 
 
 def measure(reps):
@@ -31,6 +31,7 @@ def measure(reps):
     tol = dict(pass_spp=B, rel_error=REL, abs_error=ABS)
     ms = lambda st: float(sum(s.kernel_ms for s in st)) if isinstance(st, list) else float(st.kernel_ms)
     calls = {
+        "adaptive": lambda: ms(render.render_adaptive(sc, cam, p, **tol)[4]),
         "multi": lambda: ms(render.render_adaptive_multi(sc, cam, p, [0], **tol)[4]),
         "resume": lambda: ms(render.render_adaptive_resume(sc, cam, p, None, None, **tol)[4]),
         "region": lambda: ms(render.render_adaptive_region(sc, cam, p, 0, 0, W, H, **tol)[4]),

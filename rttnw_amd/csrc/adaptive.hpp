@@ -1,5 +1,5 @@
 // adaptive.hpp — the per-pixel noise estimate and stopping rule of rttnw_render_adaptive (include/rttnw_hip.h), shared by the device
-// kernels (trace_kernels.hpp adaptive_resolve_kernel) and the host test harness (tests/adaptive_host).
+// kernels (adaptive_kernels.hpp adaptive_resolve_kernel) and the host test harness (tests/adaptive_host).
 //
 // A pixel's chunk sums are independent estimates of its mean: chunk c holds n_c samples with mean m_c.  Over the K chunks of all
 // passes so far (N = sum n_c samples) the state is folded chunk by chunk with the weighted incremental update (West 1979):

@@ -1,8 +1,9 @@
 // render_adaptive_api.cpp — the adaptive family beyond rttnw_render_adaptive: the forms over the ranks of a node (multi, resume, region), the round driver
 // of the forms that run one rank on the scene's device (RankRounds) and those forms (denoised, preview, budget, budget_denoised), and rttnw_budget_select.  Host code
-// only; the kernels live in render_f32.hip / render_f64.hip, denoise.hip (the filter, with and without flags), guided.hip (the filtering forms' own
-// steps) and budget.hip (the selection).
+// only; the kernels live in render_f32.hip / render_f64.hip, pixel_lists.hip (selection, marks and lists: one build for every precision), denoise.hip
+// (the filter, with and without flags), guided.hip (the filtering forms' own steps) and budget.hip (the selection).
 #include "render_multi.hpp"
+#include "pixel_lists.hpp"
 #include "adaptive_state.hpp"
 #include "feature_api.hpp"
 #include "guided.hpp"
@@ -168,11 +169,10 @@ static int adaptive_multi_passes(::rttnw_scene* s, const rttnw_camera_desc* cam,
         const uint32_t n_blocks = sl.tiles(r, ngpu) * 16u; // (its own tiles only: no pass writes the active bytes of a pad tile)
         const uint8_t* marks = sl.active(m, r);
         if (lv.resumed) {
-            if (int rc = RT_BY_PRECISION(p.precision, adaptive_level_select_launch, marks, sl.state(m, r), sl.marks(m, r), n_blocks * 4u,
-                                         level * a.pass_spp, stream)) return rc;
+            if (int rc = adaptive_level_select_launch(marks, sl.state(m, r), sl.marks(m, r), n_blocks * 4u, level * a.pass_spp, stream)) return rc;
             marks = sl.marks(m, r);
         }
-        if (int rc = RT_BY_PRECISION(p.precision, enqueue_quad_list, marks, n_blocks, scan, sl.quads(m, r), stream)) return rc;
+        if (int rc = enqueue_quad_list(marks, n_blocks, scan, sl.quads(m, r), stream)) return rc;
         HIP_TRY(hipMemcpyAsync(counts + 2 * r, quad_list_totals(scan, n_blocks), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         return 0;
     };
@@ -215,11 +215,9 @@ static int adaptive_multi_passes(::rttnw_scene* s, const rttnw_camera_desc* cam,
             HIP_TRY(hipMemcpyAsync(sl.records(m, r), upload[r].data(), upload[r].size() * sizeof(double), hipMemcpyHostToDevice, stream));
             if (int rc = RT_BY_PRECISION(p.precision, adaptive_state_import_launch, sl.records(m, r), m.packed(r), sl.state(m, r), sl.active(m, r),
                                          sl.L.pixels_per_rank, p.spp, a.rel_error, a.abs_error, stream)) return rc;
-            if (sel) {
-                pr.tile_rank = r;
-                if (int rc = RT_BY_PRECISION(p.precision, adaptive_region_activate_launch, s, d, &pr, sel->mask ? (const uint8_t*)d->rg_mask.p : nullptr,
-                                             sl.select(m, r), sl.state(m, r), sl.active(m, r), sel->x0, sel->y0, sel->x1, sel->y1, stream)) return rc;
-            }
+            if (sel)
+                if (int rc = adaptive_region_activate_launch(p.width, p.height, r, ngpu, sel->mask ? (const uint8_t*)d->rg_mask.p : nullptr, sl.select(m, r),
+                                                             sl.state(m, r), sl.active(m, r), sel->x0, sel->y0, sel->x1, sel->y1, stream)) return rc;
             if (k < n_passes)
                 if (int rc = enqueue_list(r, k, stream)) return rc;
             HIP_TRY(hipEventRecord(ev[2 * r + 1].get(), stream));
@@ -489,7 +487,7 @@ struct RankRounds {
     }
     // The list of the 2x2 blocks that hold a marked pixel ...
     int enqueue_list(const uint8_t* marks) {
-        return RT_BY_PRECISION(p.precision, enqueue_quad_list, marks, n_blocks, (uint32_t*)d->list_scan.p, (uint32_t*)d->list_quads.p, stream);
+        return enqueue_quad_list(marks, n_blocks, (uint32_t*)d->list_scan.p, (uint32_t*)d->list_quads.p, stream);
     }
     // ... and, in one 8-byte copy the host waits for, its totals: listed blocks, marked pixels — the pixels the pass over it traces
     int list(const uint8_t* marks, uint32_t count[2]) {
@@ -773,7 +771,7 @@ static int budget_round_trace(RankRounds& r, const std::vector<uint32_t>& census
     r.samples += uint64_t(census[0]) * B;
     for (uint32_t k = 0; k < n_levels; ++k) { // (a level's list length comes with the census: the list's own totals are not read)
         if (census[1u + k] == 0) continue;
-        if (int rc = RT_BY_PRECISION(r.p.precision, adaptive_level_select_launch, select, r.d->ad_state.p, marks, r.n_blocks * 4u, k * B, r.stream)) return rc;
+        if (int rc = adaptive_level_select_launch(select, r.d->ad_state.p, marks, r.n_blocks * 4u, k * B, r.stream)) return rc;
         if (int rc = r.enqueue_list(marks)) return rc;
         if (int rc = r.trace(k, census[1u + k], (k + 1u) * B, 0.0, 0.0)) return rc;
     }

@@ -3,7 +3,8 @@
 //   render_multi.cpp rttnw_render_multi + RCCL; render_multi.hpp: its plan and steps, which the adaptive forms over ranks walk too
 //   render_adaptive_api.cpp  the adaptive family beyond rttnw_render_adaptive: multi, resume, region, denoised, preview, budget
 //                    (adaptive_state.hpp: the state's host side, plain C++)
-//   render_f32.hip   the F32 instantiation of the kernels (trace_kernels.hpp) and of their launch code (render_tiles.hpp)
+//   render_f32.hip   the F32 instantiation of the kernels (trace_kernels.hpp, adaptive_kernels.hpp) and of their launch code (render_tiles.hpp,
+//                    adaptive_launch.hpp)
 //   render_f64.hip   the F64 instantiation — a translation unit of its own because its code wants other compiler settings
 //                    than the f32 code (Makefile: machine LICM off, 1024-thread blocks) and because the two halves build in
 //                    parallel.
@@ -247,7 +248,7 @@ struct DeviceState {
     // rttnw_render_region: the caller's mask (window-sized), the selection byte per packed pixel, the running sums per list slot and the
     // window-sized outputs
     DevBuf<uint8_t> rg_mask, rg_select, rg_sums, rg_linear, rg_rgba;
-    // both: the list of 2x2 blocks that hold a marked pixel and its scan (render_tiles.hpp build_quad_list), built anew before every use
+    // both: the list of 2x2 blocks that hold a marked pixel and its scan (adaptive_launch.hpp build_quad_list), built anew before every use
     DevBuf<uint8_t> list_quads, list_scan;
     // rttnw_render_adaptive_multi: what lives across passes, per logical rank of this device (slotted like multi_packed) — the noise state, the
     // active bytes, each rank's list and scan (a rank's list is built behind one pass and read by its next, with other ranks' work between) —
@@ -295,7 +296,7 @@ inline int refuse_host_output_misuse(const char* prefix, uint32_t reserved0, con
     return 0;
 }
 
-// The launch code of one precision (render_tiles.hpp), instantiated in render_f32.hip / render_f64.hip — and, for double, a second
+// The launch code of one precision (render_tiles.hpp, adaptive_launch.hpp), instantiated in render_f32.hip / render_f64.hip — and, for double, a second
 // time in render_f64_strict.hip in the namespace rt::ieee_strict (rt_core.hpp: the two builds of the f64 arithmetic).
 inline namespace RT_ARITH_NS {
 // What every entry point that launches over a scene starts with: the device made current, the lowering this build walks and its arrays on the
@@ -329,13 +330,14 @@ inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, co
 }
 } // namespace RT_ARITH_NS
 
-// The per-precision entry points of render_tiles.hpp, ONE list: X(R, name, parameters).  It makes the declarations, the `extern template` lines of
-// both builds and what a precision's translation unit instantiates (RT_INSTANTIATE_PRECISION): a new entry point is one line here.
+// The per-precision entry points of render_tiles.hpp and adaptive_launch.hpp, ONE list: X(R, name, parameters).  It makes the declarations, the
+// `extern template` lines of both builds and what a precision's translation unit instantiates (RT_INSTANTIATE_PRECISION): a new entry point is one
+// line here.  (What computes nothing in R is no entry point of a precision: pixel_lists.hpp.)
 //   render_adaptive_t  rttnw_render_adaptive's device half: every pass, then the image (d->linear, d->rgba) and the maps (d->ad_spp, d->ad_stderr) on the device
 //   render_region_t    rttnw_render_region's device half: selection, list, trace, resolve; the window's image on the device (d->rg_linear, d->rg_rgba)
-//   enqueue_quad_list, adaptive_finish_launch, untile_aux_launch   what rttnw_render_adaptive_multi (render_adaptive_api.cpp) enqueues beside render_tiles_t's passes
-//   adaptive_state_import_launch, adaptive_state_export_launch, adaptive_level_select_launch, adaptive_rank_stats_t   what rttnw_render_adaptive_resume adds to those
-//   adaptive_region_activate_launch, adaptive_region_window_launch   ... and rttnw_render_adaptive_region to those: selection and first active bytes, the window's outputs
+//   adaptive_finish_launch   what rttnw_render_adaptive_multi (render_adaptive_api.cpp) enqueues behind render_tiles_t's passes
+//   adaptive_state_import_launch, adaptive_state_export_launch, adaptive_rank_stats_t   what rttnw_render_adaptive_resume adds to it
+//   adaptive_region_window_launch   ... and rttnw_render_adaptive_region to those: the window's outputs
 #define RT_PRECISION_ENTRY_POINTS(X, R)                                                                                                              \
     X(R, render_tiles_t, (::rttnw_scene* s, DeviceState* d, const rttnw_camera_desc* cam, const rttnw_params* p, void* d_packed, hipStream_t stream, \
                           rttnw_stats* stats, bool sync_for_stats, bool prepare_only, const ListPass* ad))                                          \
@@ -346,21 +348,13 @@ inline RenderConsts base_consts(const rttnw_params* p, const FlatScene& flat, co
     X(R, render_adaptive_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_adaptive* a, rttnw_stats* stats))    \
     X(R, render_region_t, (::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint32_t x0, uint32_t y0, uint32_t x1,             \
                            uint32_t y1, const uint8_t* mask, rttnw_stats* stats))                                                                    \
-    X(R, enqueue_quad_list, (const uint8_t* marks, uint32_t n_blocks, uint32_t* scan, uint32_t* quads, hipStream_t stream))                          \
     X(R, adaptive_finish_launch, (void* d_packed, const void* d_state, double* d_aux, uint32_t pixels_per_rank, uint32_t rank_pixels,                \
                                   hipStream_t stream))                                                                                               \
-    X(R, untile_aux_launch, (uint32_t width, uint32_t height, uint32_t world, const double* d_gathered_aux, uint32_t* d_spp, double* d_stderr,       \
-                             hipStream_t stream))                                                                                                    \
     X(R, adaptive_state_import_launch, (const double* d_records, void* d_packed, void* d_state, uint8_t* d_active, uint32_t pixels_per_rank,         \
                                         uint32_t cap, double rel_error, double abs_error, hipStream_t stream))                                       \
     X(R, adaptive_state_export_launch, (const void* d_packed, const void* d_state, double* d_records, uint32_t pixels_per_rank,                      \
                                         uint32_t rank_pixels, hipStream_t stream))                                                                   \
-    X(R, adaptive_level_select_launch, (const uint8_t* d_active, const void* d_state, uint8_t* d_marks, uint32_t n_pixels, uint32_t level_n,         \
-                                        hipStream_t stream))                                                                                         \
     X(R, adaptive_rank_stats_t, (::rttnw_scene* s, DeviceState* d, const rttnw_params* p, rttnw_stats* stats))                                      \
-    X(R, adaptive_region_activate_launch, (::rttnw_scene* s, DeviceState* d, const rttnw_params* p, const uint8_t* d_mask, uint8_t* d_select,       \
-                                           const void* d_state, uint8_t* d_active, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,               \
-                                           hipStream_t stream))                                                                                      \
     X(R, adaptive_region_window_launch, (uint32_t width, uint32_t height, uint32_t world, const void* d_gathered, const double* d_gathered_aux,     \
                                          void* d_linear_rgb, uint8_t* d_rgba8, uint32_t* d_spp, double* d_stderr, uint32_t x0, uint32_t y0,         \
                                          uint32_t x1, uint32_t y1, hipStream_t stream))

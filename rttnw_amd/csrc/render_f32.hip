@@ -1,5 +1,5 @@
 // render_f32.hip — the F32 (throughput) kernels and their launch code: one translation unit per precision (render_common.hpp).
-#include "render_tiles.hpp"
+#include "adaptive_launch.hpp"
 
 namespace rt {
 inline namespace RT_ARITH_NS {

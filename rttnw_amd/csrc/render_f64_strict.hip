@@ -8,7 +8,7 @@
 #error "render_f64_strict.hip must not be built with fast-math flags: its results are the CPU reference's bit for bit"
 #endif
 #pragma clang fp contract(off) // (beside the Makefile's trailing -ffp-contract=off: honoured should the unit ever be built under fast-honor-pragmas)
-#include "render_tiles.hpp"
+#include "adaptive_launch.hpp"
 
 namespace rt {
 inline namespace RT_ARITH_NS {
@@ -20,15 +20,10 @@ template int render_adaptive_t<double>(::rttnw_scene*, const rttnw_camera_desc*,
 template int render_region_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*,
                                      rttnw_stats*);
 template int probe_path_t<double>(::rttnw_scene*, const rttnw_camera_desc*, const rttnw_params*, uint32_t, uint32_t, uint32_t, double*, uint32_t);
-template int enqueue_quad_list<double>(const uint8_t*, uint32_t, uint32_t*, uint32_t*, hipStream_t);
 template int adaptive_finish_launch<double>(void*, const void*, double*, uint32_t, uint32_t, hipStream_t);
-template int untile_aux_launch<double>(uint32_t, uint32_t, uint32_t, const double*, uint32_t*, double*, hipStream_t);
 template int adaptive_state_import_launch<double>(const double*, void*, void*, uint8_t*, uint32_t, uint32_t, double, double, hipStream_t);
 template int adaptive_state_export_launch<double>(const void*, const void*, double*, uint32_t, uint32_t, hipStream_t);
-template int adaptive_level_select_launch<double>(const uint8_t*, const void*, uint8_t*, uint32_t, uint32_t, hipStream_t);
 template int adaptive_rank_stats_t<double>(::rttnw_scene*, DeviceState*, const rttnw_params*, rttnw_stats*);
-template int adaptive_region_activate_launch<double>(::rttnw_scene*, DeviceState*, const rttnw_params*, const uint8_t*, uint8_t*, const void*, uint8_t*, uint32_t,
-                                                     uint32_t, uint32_t, uint32_t, hipStream_t);
 template int adaptive_region_window_launch<double>(uint32_t, uint32_t, uint32_t, const void*, const double*, void*, uint8_t*, uint32_t*, double*, uint32_t, uint32_t,
                                                    uint32_t, uint32_t, hipStream_t);
 } // namespace RT_ARITH_NS

@@ -1,6 +1,7 @@
 // render_multi.cpp — rttnw_render_multi: the whole of main.rs:202-229 on the GPUs of one node, in one call (per-device streams, RCCL gather), as named
 // steps over a MultiPlan (render_multi.hpp) that the adaptive forms over ranks (render_adaptive_api.cpp) walk too; and rttnw_shutdown.  Host code only.
 #include "render_multi.hpp"
+#include "pixel_lists.hpp"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -249,8 +250,8 @@ int multi_untile(const rttnw_params& p, const MultiPlan& m) {
     if (int rc = multi_join_local(m)) return rc;
     if (int rc = rttnw_untile_device(p.width, p.height, p.tile_world, p.precision, root->gathered.p, root->linear.p, root->rgba.p, root->stream.get())) return rc;
     if (m.aux_chunk) // ... and the samples and standard-error maps of the auxiliary records
-        if (int rc = RT_BY_PRECISION(p.precision, untile_aux_launch, p.width, p.height, p.tile_world, (const double*)root->gathered_aux.p, (uint32_t*)root->ad_spp.p,
-                                     (double*)root->ad_stderr.p, root->stream.get())) return rc;
+        if (int rc = untile_aux_launch(p.width, p.height, p.tile_world, (const double*)root->gathered_aux.p, (uint32_t*)root->ad_spp.p, (double*)root->ad_stderr.p,
+                                       root->stream.get())) return rc;
     return multi_finish_streams(m);
 }
 // The ranks' buffers to the root's gather buffers, by the transport the call uses (MultiEnv), falling through from RCCL to the peer copies

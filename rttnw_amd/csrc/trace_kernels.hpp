@@ -653,218 +653,6 @@ __global__ void untile_kernel(const R* __restrict__ gathered, R* __restrict__ li
     }
 }
 
-// ---- rttnw_render_adaptive (include/rttnw_hip.h; DESIGN.md "Adaptive sampling").
-// The adaptive resolve step: resolve_kernel's chain for the pixels a pass traced, plus the pixel's noise estimate and its active bit.
-// One thread per SLOT of the launch's chunk sums: pass 0 numbers them like a plain render (slot = packed pixel), a refinement pass by
-// the active list (rt_core.hpp job_decode_list: slot = 4 * list position + pixel in block; `quads` != nullptr).  Per pixel, in chunk order:
-// the running sum in `packed` (the R chain: exactly resolve_kernel's additions, continued over launches AND passes), and the double state
-// of adaptive.hpp folded with the chunk's mean.  The pass's last launch decides whether the pixel takes part in the next pass.
-// The active bit of a pixel with running sum (r, g, b) and noise state `a`: its value as the render reports it — sum / R(n), in the kernel's
-// arithmetic type — held against the stopping rule.  ONE piece of code for the end of a pass (adaptive_resolve_kernel) and for a state taken up
-// again (adaptive_state_import_kernel): the contracted builds' division comes from here alone, so both decide from the same bits.
-template <typename R>
-__device__ __forceinline__ bool adaptive_pixel_active(const AdaptivePixel& a, R r, R g, R b, double rel_error, double abs_error, uint32_t cap) {
-    const R n = R(a.n);
-    const double value[3] = {double(r / n), double(g / n), double(b / n)};
-    return adaptive_active(a, value, rel_error, abs_error, cap);
-}
-template <typename R>
-__global__ void adaptive_resolve_kernel(const R* __restrict__ partial, R* __restrict__ packed, AdaptivePixel* __restrict__ state,
-                                        uint8_t* __restrict__ active, const uint32_t* __restrict__ quads, RenderConsts rc, uint32_t n_slots,
-                                        uint32_t first_of_render, uint32_t last_of_pass, uint32_t cap, double rel_error, double abs_error) {
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= n_slots) return;
-    uint32_t p = slot;
-    if (quads) {
-        const uint32_t e = quads[slot >> 2];
-        if (((e >> QUAD_MASK_SHIFT) >> (slot & 3u) & 1u) == 0u) return; // a converged pixel of a listed block: it traced nothing
-        p = block_pixel(e & QUAD_INDEX_MASK, slot & 3u);
-    }
-    uint32_t tx, ty;
-    tile_unpermute(rc.tile_rank + (p >> 6) * rc.tile_world, rc.div_tiles_x, tx, ty);
-    const bool inside = tx * 8u + (p & 7u) < rc.width && ty * 8u + ((p >> 3) & 7u) < rc.height;
-    R* dst = packed + (unsigned long long)p * 4ull;
-    R r = 0, g = 0, b = 0;
-    AdaptivePixel a = {{0, 0, 0}, {0, 0, 0}, 0u, 0u};
-    if (!first_of_render) { r = dst[0]; g = dst[1]; b = dst[2]; a = state[p]; }
-    if (inside) {
-        for (uint32_t c = 0; c < rc.n_chunks; ++c) {
-            const R* src = partial + ((unsigned long long)c * n_slots + slot) * 3ull;
-            const R sr = src[0], sg = src[1], sb = src[2];
-            r = r + sr; g = g + sg; b = b + sb;
-            uint32_t s0, s1;
-            chunk_samples(rc, rc.chunk_base + c, s0, s1);
-            const double n_c = double(s1 - s0);
-            const double m[3] = {double(sr) / n_c, double(sg) / n_c, double(sb) / n_c};
-            adaptive_fold(a, m, s1 - s0);
-        }
-    }
-    dst[0] = r; dst[1] = g; dst[2] = b; dst[3] = R(0);
-    state[p] = a;
-    if (last_of_pass) active[p] = inside && adaptive_pixel_active<R>(a, r, g, b, rel_error, abs_error, cap) ? 1u : 0u;
-}
-
-// Compaction of the active pixels into the list of 2x2 blocks the next pass traces — deterministic, no atomics: (1) every wave counts its
-// blocks with an active pixel (ballot + popcount) and their active pixels, (2) one workgroup scans the waves' counts, (3) every wave writes
-// its entries at its base, in block order.  Block b of the rank is thread b; its entry is b | pixel mask << QUAD_MASK_SHIFT.
-__device__ __forceinline__ uint32_t block_active_mask(const uint8_t* active, uint32_t b, uint32_t n_blocks) {
-    uint32_t mask = 0;
-    if (b < n_blocks)
-        for (uint32_t pp = 0; pp < 4u; ++pp) mask |= active[block_pixel(b, pp)] ? 1u << pp : 0u;
-    return mask;
-}
-template <typename R>
-__global__ void quad_count_kernel(const uint8_t* __restrict__ active, uint32_t n_blocks, uint32_t* __restrict__ wave_counts) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x, wave = b >> 6;
-    const uint32_t mask = block_active_mask(active, b, n_blocks);
-    const unsigned long long listed = __ballot(mask != 0u);
-    uint32_t px = uint32_t(__popc(mask));
-    for (int off = 32; off > 0; off >>= 1) px += __shfl_xor(px, off);
-    if ((threadIdx.x & 63u) == 0u && wave * 64u < n_blocks) { wave_counts[2u * wave] = uint32_t(__popcll(listed)); wave_counts[2u * wave + 1u] = px; }
-}
-constexpr uint32_t QUAD_SCAN_BLOCK = 1024;
-template <typename R>
-__global__ void __launch_bounds__(QUAD_SCAN_BLOCK) quad_scan_kernel(const uint32_t* __restrict__ wave_counts, uint32_t* __restrict__ wave_base,
-                                                                    uint32_t n_waves, uint32_t* __restrict__ totals) {
-    __shared__ uint32_t sq[QUAD_SCAN_BLOCK], sp[QUAD_SCAN_BLOCK];
-    const uint32_t t = threadIdx.x, per = (n_waves + QUAD_SCAN_BLOCK - 1u) / QUAD_SCAN_BLOCK;
-    const uint32_t w0 = t * per < n_waves ? t * per : n_waves, w1 = w0 + per < n_waves ? w0 + per : n_waves;
-    uint32_t q = 0, px = 0;
-    for (uint32_t w = w0; w < w1; ++w) { q += wave_counts[2u * w]; px += wave_counts[2u * w + 1u]; }
-    sq[t] = q; sp[t] = px;
-    __syncthreads();
-    for (uint32_t off = 1; off < QUAD_SCAN_BLOCK; off <<= 1) { // inclusive scan over the threads' segments
-        const uint32_t aq = t >= off ? sq[t - off] : 0u, ap = t >= off ? sp[t - off] : 0u;
-        __syncthreads();
-        sq[t] += aq; sp[t] += ap;
-        __syncthreads();
-    }
-    uint32_t base = sq[t] - q;
-    for (uint32_t w = w0; w < w1; ++w) { wave_base[w] = base; base += wave_counts[2u * w]; }
-    if (t == QUAD_SCAN_BLOCK - 1u) { totals[0] = sq[t]; totals[1] = sp[t]; }
-}
-template <typename R>
-__global__ void quad_list_kernel(const uint8_t* __restrict__ active, uint32_t n_blocks, const uint32_t* __restrict__ wave_base,
-                                 uint32_t* __restrict__ quads) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x, wave = b >> 6;
-    const uint32_t mask = block_active_mask(active, b, n_blocks);
-    const unsigned long long listed = __ballot(mask != 0u);
-    if (mask) quads[wave_base[wave] + uint32_t(__popcll(listed & ((1ull << (threadIdx.x & 63u)) - 1ull)))] = b | (mask << QUAD_MASK_SHIFT);
-}
-
-// After the last pass: the packed running sums become the pixel means (sum / n_q, resolve_kernel's division) for untile_kernel, and the
-// samples and standard errors go to row-major, top-first maps.
-template <typename R>
-__global__ void adaptive_output_kernel(R* __restrict__ packed, const AdaptivePixel* __restrict__ state, uint32_t* __restrict__ spp_map,
-                                       double* __restrict__ stderr_map, uint32_t width, uint32_t height, uint32_t tiles_x) {
-    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= width || y >= height) return;
-    const unsigned long long src = tile_permuted(x >> 3, y >> 3, tiles_x) * 64ull + ((y & 7u) << 3) + (x & 7u);
-    const AdaptivePixel a = state[src];
-    R* dst = packed + src * 4ull;
-    const R n = R(a.n);
-    dst[0] = dst[0] / n; dst[1] = dst[1] / n; dst[2] = dst[2] / n; dst[3] = R(1);
-    const unsigned long long o = (unsigned long long)y * width + x;
-    spp_map[o] = a.n;
-    for (int ch = 0; ch < 3; ++ch) stderr_map[o * 3ull + ch] = adaptive_stderr(a, ch);
-}
-
-// ---- rttnw_render_adaptive_multi: the same two steps where the pixels of a frame live on several ranks.
-// One rank's packed pixels after its last pass, one thread per packed pixel: the running sum becomes the mean by adaptive_output_kernel's own
-// division (alpha 1), and the pixel's auxiliary record — standard error r, g, b and double(n), the shape of a packed f64 pixel, so that the gather
-// moves it like one — goes to `aux`.  A pixel that traced nothing (n == 0: outside the image in an edge tile) and the pixels of pad tiles
-// (p >= rank_pixels: no pass ever wrote their state) are zero-filled in both, without a division.
-template <typename R>
-__global__ void adaptive_finish_packed_kernel(R* __restrict__ packed, const AdaptivePixel* __restrict__ state, double* __restrict__ aux,
-                                              uint32_t pixels_per_rank, uint32_t rank_pixels) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= pixels_per_rank) return;
-    R* dst = packed + (unsigned long long)p * 4ull;
-    double* rec = aux + (unsigned long long)p * 4ull;
-    AdaptivePixel a = {{0, 0, 0}, {0, 0, 0}, 0u, 0u};
-    if (p < rank_pixels) a = state[p];
-    if (a.n == 0u) {
-        dst[0] = R(0); dst[1] = R(0); dst[2] = R(0); dst[3] = R(0);
-        rec[0] = 0.0; rec[1] = 0.0; rec[2] = 0.0; rec[3] = 0.0;
-        return;
-    }
-    const R n = R(a.n);
-    dst[0] = dst[0] / n; dst[1] = dst[1] / n; dst[2] = dst[2] / n; dst[3] = R(1);
-    for (int ch = 0; ch < 3; ++ch) rec[ch] = adaptive_stderr(a, ch);
-    rec[3] = double(a.n); // (n <= 2^32: exact)
-}
-
-// Gathered auxiliary records (rank-major, untile_kernel's index arithmetic) -> the row-major, top-first samples and standard-error maps.
-template <typename R>
-__global__ void untile_aux_kernel(const double* __restrict__ gathered_aux, uint32_t* __restrict__ spp_map, double* __restrict__ stderr_map,
-                                  uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t world, uint32_t pixels_per_rank) {
-    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= width || y >= height) return;
-    const uint32_t permuted = tile_permuted(x >> 3, y >> 3, tiles_x);
-    const uint32_t owner = permuted % world, local_tile = permuted / world;
-    const unsigned long long src = (unsigned long long)owner * pixels_per_rank + local_tile * 64ull + ((y & 7u) << 3) + (x & 7u);
-    const unsigned long long o = (unsigned long long)y * width + x;
-    spp_map[o] = uint32_t(gathered_aux[src * 4 + 3]);
-    for (int ch = 0; ch < 3; ++ch) stderr_map[o * 3ull + ch] = gathered_aux[src * 4 + ch];
-}
-
-// ---- rttnw_render_adaptive_resume: a render's state leaves the device and comes back (include/rttnw_hip.h has the record: 12 doubles per pixel —
-// sum r, g, b, n, mu r, g, b, k, m2 r, g, b, 0: adaptive.hpp STATE_RECORD_DOUBLES).  The host permutes between the row-major state and a rank's packed order, so these kernels see
-// one rank's packed records, one thread per packed pixel, in the single and the node-wide form alike.
-// record -> running sum (narrowed back to R: exact, it was widened from R), noise state and active byte under THIS call's tolerances and cap.
-// A record with n == 0 — the host leaves those for pixels outside the image and for pad tiles — gives zero state and an inactive pixel.
-template <typename R>
-__global__ void adaptive_state_import_kernel(const double* __restrict__ records, R* __restrict__ packed, AdaptivePixel* __restrict__ state,
-                                             uint8_t* __restrict__ active, uint32_t pixels_per_rank, uint32_t cap, double rel_error, double abs_error) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= pixels_per_rank) return;
-    const double* rec = records + (unsigned long long)p * STATE_RECORD_DOUBLES;
-    R* dst = packed + (unsigned long long)p * 4ull;
-    AdaptivePixel a = {{0, 0, 0}, {0, 0, 0}, 0u, 0u};
-    R r = 0, g = 0, b = 0;
-    bool on = false;
-    if (rec[3] != 0.0) {
-        r = R(rec[0]); g = R(rec[1]); b = R(rec[2]);
-        a.n = uint32_t(rec[3]);
-        a.k = uint32_t(rec[7]);
-        for (int ch = 0; ch < 3; ++ch) { a.mu[ch] = rec[4 + ch]; a.m2[ch] = rec[8 + ch]; }
-        on = adaptive_pixel_active<R>(a, r, g, b, rel_error, abs_error, cap);
-    }
-    dst[0] = r; dst[1] = g; dst[2] = b; dst[3] = R(0);
-    state[p] = a;
-    active[p] = on ? 1u : 0u;
-}
-// running sum (BEFORE adaptive_finish_packed_kernel turns it into the mean) and noise state -> record.  A pixel that traced nothing (n == 0) and
-// the pixels of pad tiles (p >= rank_pixels: a fresh render never wrote their state) get a zero record.
-template <typename R>
-__global__ void adaptive_state_export_kernel(const R* __restrict__ packed, const AdaptivePixel* __restrict__ state, double* __restrict__ records,
-                                             uint32_t pixels_per_rank, uint32_t rank_pixels) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= pixels_per_rank) return;
-    double* rec = records + (unsigned long long)p * STATE_RECORD_DOUBLES;
-    AdaptivePixel a = {{0, 0, 0}, {0, 0, 0}, 0u, 0u};
-    if (p < rank_pixels) a = state[p];
-    if (a.n == 0u) {
-        for (uint32_t i = 0; i < STATE_RECORD_DOUBLES; ++i) rec[i] = 0.0;
-        return;
-    }
-    const R* src = packed + (unsigned long long)p * 4ull;
-    rec[0] = double(src[0]); rec[1] = double(src[1]); rec[2] = double(src[2]);
-    rec[3] = double(a.n);
-    rec[7] = double(a.k);
-    for (int ch = 0; ch < 3; ++ch) { rec[4 + ch] = a.mu[ch]; rec[8 + ch] = a.m2[ch]; }
-    rec[11] = 0.0;
-}
-// What a resumed render traces at one level: the active pixels that hold exactly level_n = level * B samples, as the byte array the list
-// compaction reads.  (A fresh render has all its active pixels at one level and compacts the active bytes themselves.)
-template <typename R>
-__global__ void adaptive_level_select_kernel(const uint8_t* __restrict__ active, const AdaptivePixel* __restrict__ state, uint8_t* __restrict__ marks,
-                                             uint32_t n_pixels, uint32_t level_n) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pixels) return;
-    marks[p] = active[p] && state[p].n == level_n ? 1u : 0u;
-}
-
 // Debug probe: lane 0 walks one sample's path (rt_core.hpp probe_path) — the device half of the per-bounce CPU-vs-GPU vector tests.
 template <typename R>
 __global__ void probe_path_kernel(SceneView<R> sc, CameraRec<R> cam, RenderConsts rc, R t_min, uint32_t px, uint32_t row,
