@@ -7,5 +7,6 @@
 pub mod ffi;
 pub mod scene;
 
-/// The filters that need no scene handle, at the crate's root: the feature-guided one and non-local means over two half-buffers.
-pub use scene::{denoise, denoise_nlm, NlmOutput};
+/// The filters that need no scene handle, at the crate's root: the feature-guided one, non-local means over two half-buffers and the
+/// per-pixel choice between the two.
+pub use scene::{denoise, denoise_nlm, denoise_select, NlmOutput, SelectOutput};

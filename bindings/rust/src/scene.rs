@@ -362,6 +362,37 @@ pub fn denoise_nlm(width: u32, height: u32, half_a: &[f64], half_b: &[f64], vari
     Ok(out)
 }
 
+/// What `denoise_select` returns: the blended image (linear w*h*3 and RGBA8 w*h*4), the weight of non-local means per pixel (w*h, 0 .. 1), the
+/// mean of each filter's two filtered halves and the error estimate, w*h*3 each.
+pub struct SelectOutput {
+    pub linear: Vec<f64>,
+    pub rgba8: Vec<u8>,
+    pub blend: Vec<f64>,
+    pub feature: Vec<f64>,
+    pub nlm: Vec<f64>,
+    pub error: Vec<f64>,
+}
+
+/// `rttnw_denoise_select`: per pixel, the better of `denoise` (guided by `f`) and `denoise_nlm` over two half-buffers (w*h*3 each): a filtered
+/// half is scored against the other, raw half.  `variances`: the variance of each half's pixel means, given to both filters, or None.
+pub fn denoise_select(half_a: &[f64], half_b: &[f64], variances: Option<(&[f64], &[f64])>, f: &Features, dn: &ffi::rttnw_denoise_params, nl: &ffi::rttnw_nlm_params,
+                      sel: &ffi::rttnw_select_params) -> Result<SelectOutput> {
+    let n = f.width as usize * f.height as usize;
+    if half_a.len() != n * 3 || half_b.len() != n * 3 || variances.map_or(false, |(va, vb)| va.len() != n * 3 || vb.len() != n * 3) || f.albedo.len() != n * 3
+        || f.normal.len() != n * 3 || f.depth.len() != n || f.alpha.len() != n {
+        return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "denoise_select: array sizes do not match the image".into() });
+    }
+    let mut out = SelectOutput { linear: vec![0f64; n * 3], rgba8: vec![0u8; n * 4], blend: vec![0f64; n], feature: vec![0f64; n * 3], nlm: vec![0f64; n * 3],
+                                 error: vec![0f64; n * 3] };
+    ok(unsafe {
+        ffi::rttnw_denoise_select(f.width, f.height, half_a.as_ptr(), half_b.as_ptr(), variances.map_or(ptr::null(), |v| v.0.as_ptr()),
+                                  variances.map_or(ptr::null(), |v| v.1.as_ptr()), f.albedo.as_ptr(), f.normal.as_ptr(), f.depth.as_ptr(), f.alpha.as_ptr(), dn, nl, sel,
+                                  out.linear.as_mut_ptr(), out.rgba8.as_mut_ptr(), out.blend.as_mut_ptr(), out.feature.as_mut_ptr(), out.nlm.as_mut_ptr(),
+                                  out.error.as_mut_ptr(), ptr::null_mut())
+    })?;
+    Ok(out)
+}
+
 /// `rttnw_reconstruct`: `denoise` over an image of which only the pixels with a nonzero byte in `valid` (w*h) hold a value; `linear` and
 /// `variance` are never read elsewhere.  Returns (linear w*h*3, RGBA8 w*h*4 with alpha 0 where nothing could be filled, the valid bytes).
 pub fn reconstruct(linear: &[f64], variance: Option<&[f64]>, valid: &[u8], f: &Features, d: &ffi::rttnw_denoise_params) -> Result<(Vec<f64>, Vec<u8>, Vec<u8>)> {

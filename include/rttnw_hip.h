@@ -43,8 +43,8 @@ extern "C" {
                              * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region, rttnw_render_adaptive_multi,
                              *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region,
                              *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select,
-                             *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised and rttnw_denoise_nlm came later, without a
-                             *  version bump: a caller detects each by its symbol) */
+                             *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised, rttnw_denoise_nlm and
+                             *  rttnw_denoise_select came later, without a version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -421,6 +421,60 @@ typedef struct rttnw_nlm_params rttnw_nlm_params;
 int rttnw_denoise_nlm(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a,
                       const double* var_b, const rttnw_nlm_params* d, double* out_linear_rgb, uint8_t* out_rgba8,
                       double* out_half_a, double* out_half_b, double* out_error_rgb, double* kernel_ms);
+
+/* A choice, per pixel, between the two denoisers above.  rttnw_denoise wins where the first hit describes the surface (a wall's normal and
+ * depth say "same surface" with no noise at all), rttnw_denoise_nlm where it does not (a procedural texture, what a mirror shows); a real frame
+ * holds both kinds of region (DESIGN.md section 10b has the measurements).  The two halves are independent estimates of one frame, so a
+ * filtered half can be scored against the OTHER, raw half: that half's own noise enters both filters' scores alike and cancels in their
+ * difference.  This is the selection step of Rousselle, Knaus and Zwicker 2012.  Calling convention as the two filters: host arrays in and out
+ * (row-major, top row first), blocking, on the current device, no scene handle; no CPU fallback: RTTNW_ERR_HIP without a device.  Everything is
+ * double.  a, b are half_a, half_b.
+ *
+ * 1. Feature-guided halves.  Fa = the out_linear_rgb of rttnw_denoise(half_a, var_a or NULL, albedo, normal, depth, alpha, dn), Fb = the same of
+ *    half_b and var_b: bit for bit what that entry point returns.
+ * 2. Non-local-means halves.  Na, Nb = out_half_a, out_half_b of rttnw_denoise_nlm(half_a, half_b, var_a, var_b, nl), bit for bit.
+ * 3. Cross-validated error, per pixel.  For channel c  tF_c = (Fa_c - b_c) * (Fa_c - b_c) + (Fb_c - a_c) * (Fb_c - a_c);
+ *    E_F = (tF_r + tF_g) + tF_b;  E_N likewise from Na, Nb;  d = (E_F - E_N) / (1e-10 + (E_F + E_N)), a value in [-1, 1]: normalised, so that
+ *    a bright region's errors do not outvote its neighbours inside the window.
+ * 4. Window sum.  Coordinates are clamped to the image, each on its own, as in rttnw_denoise_nlm.  R(x, y) = sum over ox = -s .. s, left to
+ *    right, of d(clamp(x + ox), y);  S(p) = sum over oy = -s .. s, top to bottom, of R(x, clamp(y + oy)); both sums start from 0.0.
+ *    m(p) = 1.0 where S(p) > margin * double((2s+1)^2) (the product rounded once), otherwise 0.0: a NaN S compares false and chooses the
+ *    feature-guided filter.
+ * 5. Blend weight.  beta(p) = (the same two-stage clamped sum of m with radius t) / double((2t+1)^2): a window of all ones gives exactly
+ *    1.0, a window of all zeros exactly 0.0.
+ * 6. Output.  F_c = (Fa_c + Fb_c) * 0.5, N_c = (Na_c + Nb_c) * 0.5.  blend(n, f) = f where beta == 0, n where beta == 1, otherwise
+ *    beta * n + (1.0 - beta) * f: two products and one sum, not fused.  The branches keep a non-finite value of the filter that was not
+ *    chosen out of the pixel (with t <= s, a NaN d makes m 0 on every pixel of its blend window, so beta is exactly 0 there; a blend window
+ *    wider than the error window can reach past that).  out_linear_rgb w*h*3 = blend(N_c, F_c); out_rgba8 w*h*4 of it after main.rs:219-225, alpha 255; out_blend
+ *    w*h = beta; out_feature_rgb w*h*3 = F; out_nlm_rgb w*h*3 = N; out_error_rgb w*h*3 = (A_c - B_c) * (A_c - B_c) * 0.25 with
+ *    A_c = blend(Na_c, Fa_c), B_c = blend(Nb_c, Fb_c): the analogue of rttnw_denoise_nlm's error output; kernel_ms: device time of every
+ *    kernel of the call.  Each output is optional.
+ * 7. Arithmetic.  + - * / and comparisons only in steps 3 to 6 (the square root of the RGBA8 output aside); no product is fused into a sum;
+ *    every sum adds its terms in the order stated.  So the device code, a host build of the same header (rttnw_amd/csrc/select.hpp) and a
+ *    restatement in numpy give the same bits.  Swapping (half_a, var_a) with (half_b, var_b) leaves every output bit-identical.  A pixel's
+ *    outputs depend on the inputs within max(r + f + 1, 2 * (2^iterations - 1)) + s + t pixels of it only.
+ * Parameters.  error_radius 0 = 5, blend_radius 0 = 2.  A margin of 0 is meaningful (the filter with the smaller summed error wins), so the
+ *   default margin has a flag of its own: use_default_margin != 0 takes 0.01 and ignores `margin`.  DESIGN.md section 10b says why it is not 0.
+ *   margin 2 chooses the feature-guided filter everywhere (S <= (2s+1)^2 always), margin -2 non-local means everywhere a window holds no NaN.
+ * Refusals, before the device is touched, each message naming denoise_select and the argument: RTTNW_ERR_INVALID for everything the two
+ *   filters refuse for their own arguments — a NULL half_a, half_b, albedo, normal, depth, alpha, dn or nl, exactly one of var_a / var_b,
+ *   width * height == 0, dn->iterations > 8, dn->reserved0 != 0, a negative or NaN sigma, nl->search_radius > 16, nl->patch_radius > 4, a
+ *   reserved field of nl that is not 0, a negative or NaN nl->k — and for a NULL sel, error_radius > 16, blend_radius > 8, a margin outside
+ *   [-2, 2] or NaN (where it is not ignored), sel->reserved0 != 0.
+ * Out of scope: steering the adaptive rounds by out_blend or out_error_rgb, a node-wide form, the native rttnw program, a third candidate
+ *   filter. */
+struct rttnw_select_params {
+    uint32_t error_radius;  /* s: the error difference is summed over (2s+1)^2 pixels; 0 = default 5; 1 .. 16 */
+    uint32_t blend_radius;  /* t: the binary choice is averaged over (2t+1)^2 pixels; 0 = default 2; 1 .. 8 */
+    double margin;          /* tau in [-2, 2]: non-local means is chosen where the mean normalised error difference exceeds it */
+    uint32_t use_default_margin, reserved0; /* use_default_margin != 0: margin is ignored and 0.01 is used; reserved0 must be 0 */
+};
+typedef struct rttnw_select_params rttnw_select_params;
+int rttnw_denoise_select(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a,
+                         const double* var_b, const double* albedo, const double* normal, const double* depth, const double* alpha,
+                         const rttnw_denoise_params* dn, const rttnw_nlm_params* nl, const rttnw_select_params* sel,
+                         double* out_linear_rgb, uint8_t* out_rgba8, double* out_blend, double* out_feature_rgb, double* out_nlm_rgb,
+                         double* out_error_rgb, double* kernel_ms);
 
 /* `render()` on the GPUs of ONE NODE, in one call from one host thread ("library owns its HIP
  * streams / RCCL comms"): the framebuffer's 8x8 tiles are interleaved over `ngpu` ranks, rank r traces its tiles on

@@ -39,6 +39,12 @@ written is the filtered one, --denoise-iterations sets its passes, and a pixel n
 ranges and filters them with rttnw_denoise_nlm, non-local means whose weights for one half are measured in the other: no feature buffer, so what a
 mirror shows or a texture paints is filtered like anything else.  --spp must be even.  It does not combine with --noise, --denoise, --features,
 --devices, --window or --passes.
+--denoise-select [--select-margin X] [--blend-map FILE] renders the same two halves and the first-hit features of min(spp, 16) samples, filters
+each half with rttnw_denoise and with non-local means, and takes per pixel the filter that lies closer to the other, raw half
+(rttnw_denoise_select): walls go to the feature-guided filter, textures and reflections to non-local means.  X is the margin non-local means
+must win by (-2 .. 2; without the flag the library default, 0.01); FILE receives the blend weight as a grey PNG (white: non-local means).
+--denoise-iterations and the --nlm- flags set the two filters.  --spp must be even.  It does not combine with --noise, --denoise,
+--denoise-nlm, --features, --devices, --window or --passes.
 """
 import argparse
 import sys
@@ -84,6 +90,7 @@ def node_ms(devices, stats):
     return max(per_device.values())
 
 
+EVEN_SPP = "%s needs an even --spp (two halves of spp / 2 samples), got %d"
 WANTS_WINDOW = "%s wants X0,Y0,X1,Y1: four non-negative integers with X0 < X1 and Y0 < Y1, got %r"
 
 
@@ -93,18 +100,26 @@ def refusal(args, refine, devices, window):
           "--preview": args.preview is not None, "--guided": args.guided,
           "--refine": args.refine is not None, "--devices": args.devices is not None, "--resume": args.resume is not None,
           "--save-state": args.save_state is not None, "--window": args.window is not None, "--passes": args.passes > 1,
-          "--features": args.features is not None, "--denoise": args.denoise, "--denoise-nlm": args.denoise_nlm}
+          "--features": args.features is not None, "--denoise": args.denoise, "--denoise-nlm": args.denoise_nlm,
+          "--denoise-select": args.denoise_select}
     iterations = (0 <= args.denoise_iterations <= 8, "--denoise-iterations must be 0 .. 8")
     state_needs, state_clashes = "only the adaptive render has a state", ("--window", "--passes")
     # in the order they are checked: (flag, why it needs --noise or None, the flags it does not combine with, the reason given for that,
     # [(holds, the message if not)] checked before all that, the same checked after it)
     noise_above_0 = "%s needs a noise bound above 0 to rank pixels by (--noise or --abs-noise)"
+    nlm_parameters = [(0 <= args.nlm_search_radius <= 16, "--nlm-search-radius must be 0 .. 16 (0: the default, 7)"),
+                      (0 <= args.nlm_patch_radius <= 4, "--nlm-patch-radius must be 0 .. 4 (0: the default, 3)"),
+                      (args.nlm_k >= 0.0, "--nlm-k must be at least 0 (0: the default, 0.7)")]
+    if args.blend_map is not None and not args.denoise_select:
+        return "--blend-map needs --denoise-select: only that call has a blend weight"
     rules = [
+        ("--denoise-select", None, ("--noise", "--denoise", "--denoise-nlm", "--features", "--devices", "--window", "--passes"),
+         ": it filters two plain half renders of the whole frame with both filters, on one GPU", [],
+         [(args.spp == 0 or (args.spp >= 2 and args.spp % 2 == 0), EVEN_SPP % ("--denoise-select", args.spp)),
+          (args.select_margin is None or -2.0 <= args.select_margin <= 2.0, "--select-margin must be -2 .. 2 (without it: the default, 0.01)"),
+          iterations] + nlm_parameters),
         ("--denoise-nlm", None, ("--noise", "--denoise", "--features", "--devices", "--window", "--passes"),
-         ": it filters two plain half renders of the whole frame, on one GPU", [],
-         [(0 <= args.nlm_search_radius <= 16, "--nlm-search-radius must be 0 .. 16 (0: the default, 7)"),
-          (0 <= args.nlm_patch_radius <= 4, "--nlm-patch-radius must be 0 .. 4 (0: the default, 3)"),
-          (args.nlm_k >= 0.0, "--nlm-k must be at least 0 (0: the default, 0.7)")]),
+         ": it filters two plain half renders of the whole frame, on one GPU", [], nlm_parameters),
         ("--guided-budget", "it is the adaptive render under a budget of samples, ranked by the filtered image's noise",
          ("--budget", "--guided", "--preview", "--refine", "--devices", "--window", "--passes"),
          ": it runs on one GPU, over the whole frame, on the filtered noise", [],
@@ -174,6 +189,12 @@ def main(argv=None):
     ap.add_argument("--nlm-search-radius", type=int, default=0, help="non-local means: candidates within this many pixels (1..16; 0 = 7)")
     ap.add_argument("--nlm-patch-radius", type=int, default=0, help="non-local means: patches of (2F+1)^2 pixels (1..4; 0 = 3)")
     ap.add_argument("--nlm-k", type=float, default=0.0, help="non-local means: the distance scale (0 = 0.7)")
+    ap.add_argument("--denoise-select", action="store_true", help="render two halves and the first-hit features, filter each half with both "
+                    "denoisers and take per pixel the one closer to the other half (rttnw_denoise_select)")
+    ap.add_argument("--select-margin", type=float, default=None, metavar="X", help="selection: the margin non-local means must win by (-2..2; "
+                    "default 0.01)")
+    ap.add_argument("--blend-map", default=None, metavar="FILE", help="selection: also write the blend weight as a grey-scale PNG (white: "
+                    "non-local means)")
     ap.add_argument("--guided", action="store_true", help="adaptive sampling: stop pixels on the noise of the denoised image "
                     "(rttnw_render_adaptive_denoised); writes the denoised image")
     ap.add_argument("--preview", type=int, default=None, metavar="L", help="adaptive sampling: trace 1 pixel in 4^L (x %% 2^L == 0 and y %% 2^L == 0, "
@@ -225,6 +246,9 @@ def main(argv=None):
     cam.aspect_ratio = setup.width / setup.height
     p = make_params(w, h, args.spp or setup.spp, background=tuple(setup.background), seed=args.seed,
                     precision={"f32": abi.F32, "f64": abi.F64, "f64strict": abi.F64_STRICT}[args.precision])
+    if args.denoise_select and (p.spp < 2 or p.spp % 2):   # (the scene's own spp: a given --spp was refused above)
+        print(EVEN_SPP % ("--denoise-select", p.spp), file=sys.stderr)
+        return 1
     if window is not None:
         x0, y0, x1, y1 = window
         if x1 > w or y1 > h:
@@ -237,7 +261,7 @@ def main(argv=None):
         return 0
     features = None
     own_filter = args.guided or args.preview is not None or args.guided_budget is not None   # the call's own image is the filtered one
-    if (args.denoise and not own_filter) or args.features:
+    if (args.denoise and not own_filter) or args.features or args.denoise_select:
         if args.denoise and args.passes > 1:
             print("--denoise does not combine with --passes", file=sys.stderr)
             return 1
@@ -352,7 +376,7 @@ def main(argv=None):
         return 0
     if args.denoise_nlm:
         if p.spp < 2 or p.spp % 2:
-            print("--denoise-nlm needs an even --spp (two halves of spp / 2 samples), got %d" % p.spp, file=sys.stderr)
+            print(EVEN_SPP % ("--denoise-nlm", p.spp), file=sys.stderr)
             return 1
         (lin_a, _, st_a), (lin_b, _, st_b) = render.render_halves(sc, cam, p)
         out = render.denoise_nlm(lin_a, lin_b, search_radius=args.nlm_search_radius, patch_radius=args.nlm_patch_radius, k=args.nlm_k, want_ms=True)
@@ -360,6 +384,20 @@ def main(argv=None):
         ms = st_a.kernel_ms + st_b.kernel_ms
         print("%.3fs (two halves of %d spp: trace kernels %.1f ms, %.1f Msamples/s; non-local means %.2f ms)"
               % (time.time() - t0, p.spp // 2, ms, (st_a.samples + st_b.samples) / max(ms, 1e-9) / 1e3, out["ms"]))
+        return 0
+    if args.denoise_select:
+        (lin_a, _, st_a), (lin_b, _, st_b) = render.render_halves(sc, cam, p)
+        out = render.denoise_select(lin_a, lin_b, features, iterations=args.denoise_iterations, search_radius=args.nlm_search_radius,
+                                    patch_radius=args.nlm_patch_radius, k=args.nlm_k, margin=args.select_margin, want_ms=True)
+        Image.fromarray(out["rgba8"], "RGBA").save(args.out)
+        if args.blend_map:
+            Image.fromarray(np.minimum(out["blend"] * 255.0 + 0.5, 255.0).astype(np.uint8), "L").save(args.blend_map)
+        ms = st_a.kernel_ms + st_b.kernel_ms
+        print("%.3fs (two halves of %d spp: trace kernels %.1f ms, %.1f Msamples/s; features %.1f ms; both filters and the selection %.2f ms)"
+              % (time.time() - t0, p.spp // 2, ms, (st_a.samples + st_b.samples) / max(ms, 1e-9) / 1e3, features["stats"].kernel_ms, out["ms"]))
+        print("selection: %.1f %% of the pixels took non-local means, %.1f %% the feature-guided filter, %.1f %% a blend of the two"
+              % (100.0 * (out["blend"] == 1.0).mean(), 100.0 * (out["blend"] == 0.0).mean(),
+                 100.0 * ((out["blend"] > 0.0) & (out["blend"] < 1.0)).mean()))
         return 0
     lin, rgba, st = render.render_host(sc, cam, p)
     Image.fromarray(finish(lin, rgba, None), "RGBA").save(args.out)

@@ -66,6 +66,13 @@ class Nlm(C.Structure):
                 ("reserved1", C.c_uint32)]
 
 
+class Select(C.Structure):
+    """`rttnw_select_params` — the parameters of `rttnw_denoise_select` (a radius of 0: the library default; `use_default_margin` != 0: the
+    default margin, `margin` ignored)."""
+    _fields_ = [("error_radius", C.c_uint32), ("blend_radius", C.c_uint32), ("margin", C.c_double), ("use_default_margin", C.c_uint32),
+                ("reserved0", C.c_uint32)]
+
+
 class Guided(C.Structure):
     """`rttnw_guided` — what `rttnw_render_adaptive_denoised` and `rttnw_render_adaptive_budget_denoised` take beside the stopping rule: the
     features' samples and the filter."""
@@ -153,6 +160,9 @@ PRODUCT_FUNCS = [
                               C.POINTER(Denoise), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("denoise_nlm", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Nlm), C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    ("denoise_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.POINTER(Denoise), C.POINTER(Nlm), C.POINTER(Select), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("render_preview", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Preview), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("budget_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint64,

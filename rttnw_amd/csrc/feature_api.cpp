@@ -1,8 +1,8 @@
-// feature_api.cpp — the extern "C" half of rttnw_render_features, rttnw_denoise, rttnw_denoise_nlm and rttnw_reconstruct (include/rttnw_hip.h):
-// argument checks, then the feature pass of the requested arithmetic build (feature_kernels.hpp), the device half of the denoiser and of the
-// reconstruction (denoise.hip) or the non-local-means filter's (nlm.hip).  Host code only.
+// feature_api.cpp — the extern "C" half of rttnw_render_features, rttnw_denoise, rttnw_denoise_nlm, rttnw_denoise_select and rttnw_reconstruct
+// (include/rttnw_hip.h): argument checks, then the feature pass of the requested arithmetic build (feature_kernels.hpp), the device half of the
+// denoiser and of the reconstruction (denoise.hip), the non-local-means filter's (nlm.hip) or the per-pixel choice between the two (select.hip).
+// Host code only.
 #include "feature_api.hpp"
-#include "nlm.hpp"
 
 extern "C" {
 
@@ -47,6 +47,38 @@ int rttnw_denoise_nlm(uint32_t width, uint32_t height, const double* half_a, con
     if (!(d->k >= 0.0)) { rt::set_last_error("denoise_nlm: d->k must be >= 0 (and not NaN)"); return RTTNW_ERR_INVALID; }
     return rt::nlm_device(width, height, half_a, half_b, var_a, var_b, rt::nlm_params(d->search_radius, d->patch_radius, d->k), out_linear_rgb, out_rgba8,
                           out_half_a, out_half_b, out_error_rgb, kernel_ms);
+}
+
+int rttnw_denoise_select(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b,
+                         const double* albedo, const double* normal, const double* depth, const double* alpha, const rttnw_denoise_params* dn,
+                         const rttnw_nlm_params* nl, const rttnw_select_params* sel, double* out_linear_rgb, uint8_t* out_rgba8, double* out_blend,
+                         double* out_feature_rgb, double* out_nlm_rgb, double* out_error_rgb, double* kernel_ms) {
+    // what rttnw_denoise_nlm and rttnw_denoise refuse for their own arguments, then the selection's
+    const auto refuse = [](const char* what) { rt::set_last_error(std::string("denoise_select: ") + what); return int(RTTNW_ERR_INVALID); };
+    if (!half_a || !half_b) return refuse("NULL argument (half_a or half_b)");
+    if (!albedo || !normal || !depth || !alpha) return refuse("NULL argument (albedo, normal, depth or alpha)");
+    if (!dn || !nl) return refuse("NULL argument (dn or nl)");
+    if (!sel) return refuse("sel is NULL");
+    if ((var_a == nullptr) != (var_b == nullptr)) return refuse("var_a and var_b go together: both or neither");
+    if (uint64_t(width) * height == 0 || uint64_t(width) * height > (1ull << 28)) return refuse("width * height: empty image (or more than 2^28 pixels)");
+    if (dn->iterations > rt::DENOISE_MAX_ITERATIONS) return refuse("dn->iterations: more than 8 iterations");
+    if (dn->reserved0 != 0) return refuse("dn->reserved0 must be 0");
+    if (!(dn->sigma_luminance >= 0.0) || !(dn->sigma_normal >= 0.0) || !(dn->sigma_depth >= 0.0)) {
+        return refuse("the sigmas (dn->sigma_luminance, sigma_normal, sigma_depth) must be >= 0 (and not NaN)");
+    }
+    if (nl->search_radius > rt::NLM_MAX_SEARCH_RADIUS) return refuse("nl->search_radius is more than 16");
+    if (nl->patch_radius > rt::NLM_MAX_PATCH_RADIUS) return refuse("nl->patch_radius is more than 4");
+    if (nl->reserved0 != 0 || nl->reserved1 != 0) return refuse("nl->reserved0 and nl->reserved1 must be 0");
+    if (!(nl->k >= 0.0)) return refuse("nl->k must be >= 0 (and not NaN)");
+    if (sel->error_radius > rt::SELECT_MAX_ERROR_RADIUS) return refuse("sel->error_radius is more than 16");
+    if (sel->blend_radius > rt::SELECT_MAX_BLEND_RADIUS) return refuse("sel->blend_radius is more than 8");
+    if (sel->reserved0 != 0) return refuse("sel->reserved0 must be 0");
+    if (sel->use_default_margin == 0 && !(sel->margin >= -2.0 && sel->margin <= 2.0)) return refuse("sel->margin must lie in [-2, 2] (and not be NaN)");
+    return rt::select_device(width, height, half_a, half_b, var_a, var_b, albedo, normal, depth, alpha, dn->iterations,
+                             rt::denoise_params(dn->sigma_luminance, dn->sigma_normal, dn->sigma_depth, var_a != nullptr),
+                             rt::nlm_params(nl->search_radius, nl->patch_radius, nl->k),
+                             rt::select_params(sel->error_radius, sel->blend_radius, sel->margin, sel->use_default_margin != 0), out_linear_rgb, out_rgba8,
+                             out_blend, out_feature_rgb, out_nlm_rgb, out_error_rgb, kernel_ms);
 }
 
 int rttnw_reconstruct(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const uint8_t* valid, const double* albedo,

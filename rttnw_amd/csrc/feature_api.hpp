@@ -1,9 +1,12 @@
 // feature_api.hpp — what feature_api.cpp (the extern "C" half of rttnw_render_features and rttnw_denoise) calls: the feature pass's launch
 // code per arithmetic build (feature_kernels.hpp, instantiated in features_f32.hip / features_f64.hip / features_f64_strict.hip) and the
-// device half of the denoiser and of rttnw_reconstruct (denoise.hip).  Kept out of render_common.hpp: the render kernels' translation units do not read it.
+// device halves of the denoiser and of rttnw_reconstruct (denoise.hip), of rttnw_denoise_nlm (nlm.hip) and of rttnw_denoise_select (select.hip).
+// Kept out of render_common.hpp: the render kernels' translation units do not read it.
 #pragma once
 #include "render_common.hpp"
 #include "denoise.hpp"
+#include "nlm.hpp"
+#include "select.hpp"
 
 namespace rt {
 
@@ -27,5 +30,22 @@ int atrous_passes_device(uint32_t width, uint32_t height, const double* d_in, co
                          const double* d_normal, const double* d_depth, const double* d_alpha, uint32_t iterations, const DenoiseParams& prm,
                          double* const d_c[2], double* const d_v[2], uint8_t* const d_h[2], uint8_t* d_rgba, uint8_t* d_out_valid, hipStream_t stream,
                          int& out);
+
+// rttnw_denoise_nlm's kernels alone (nlm.hip), in the shape of atrous_passes_device: nlm_plan_device picks the filter kernel of the call's radii
+// and admits its dynamic LDS — before the caller starts its clock —, nlm_passes_device enqueues the kernels on `stream` over buffers that are
+// already on the device: nothing allocated, nothing copied, no wait.  d_var_a / d_var_b: the guides' variances, or both nullptr: the pair
+// variance is then formed into d_pair_var (w*h*3).  d_fa / d_fb (w*h*3) take the two cross-filtered halves; d_out, d_err (w*h*3) and d_rgba
+// (w*h*4) the mean, the error estimate and the RGBA8 — with d_out == nullptr the finish step is not run.  `at`: the prefix of an error's message.
+int nlm_plan_device(const char* at, const NlmParams& prm, NlmPlan& plan);
+int nlm_passes_device(const char* at, uint32_t width, uint32_t height, const double* d_a, const double* d_b, const double* d_var_a, const double* d_var_b,
+                      double* d_pair_var, const NlmParams& prm, const NlmPlan& plan, double* d_fa, double* d_fb, double* d_out, uint8_t* d_rgba,
+                      double* d_err, hipStream_t stream);
+
+// rttnw_denoise_select's device half (select.hip): host arrays in, host arrays out (each optional), blocking, on the current device: two à-trous
+// runs, the non-local-means step and the selection (select.hpp) over one set of device buffers.  Arguments were checked by the caller.
+int select_device(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b,
+                  const double* albedo, const double* normal, const double* depth, const double* alpha, uint32_t iterations, const DenoiseParams& dn,
+                  const NlmParams& nl, const SelectParams& sel, double* out_linear_rgb, uint8_t* out_rgba8, double* out_blend, double* out_feature_rgb,
+                  double* out_nlm_rgb, double* out_error_rgb, double* kernel_ms);
 
 } // namespace rt

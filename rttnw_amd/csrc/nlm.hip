@@ -100,6 +100,39 @@ __global__ void nlm_finish_kernel(uint32_t n, const double* __restrict__ fa, con
 
 } // namespace
 
+// The filter kernel a call's radii take, with its dynamic LDS admitted: what a caller settles before it starts its clock.
+int nlm_plan_device(const char* at, const NlmParams& prm, NlmPlan& plan) {
+    // the large tile where its LDS fits a CU, the small one — which fits at every radius the entry point accepts — otherwise
+    const bool large = nlm_lds_bytes(NLM_TILE_LARGE, prm.r, prm.f) <= NLM_LDS_BYTES;
+    plan.tile = large ? NLM_TILE_LARGE : NLM_TILE_SMALL;
+    plan.lds_bytes = nlm_lds_bytes(plan.tile, prm.r, prm.f);
+    plan.filter = large ? nlm_filter_kernel<int(NLM_TILE_LARGE)> : nlm_filter_kernel<int(NLM_TILE_SMALL)>;
+    HIP_TRY_AS(at, hipFuncSetAttribute(reinterpret_cast<const void*>(plan.filter), hipFuncAttributeMaxDynamicSharedMemorySize, int(plan.lds_bytes)));
+    return RTTNW_OK;
+}
+
+// The filter's kernels on buffers that are already on the device (rttnw_denoise_nlm behind its uploads; rttnw_denoise_select between its à-trous
+// runs and its selection), enqueued on `stream` — nothing else: no allocation, no copy, no wait.  d_var_a / d_var_b: the guides' variances, or
+// both nullptr: the pair variance is then formed into d_pair_var (w*h*3), which serves both guides.  d_fa / d_fb (w*h*3 each) take the two
+// cross-filtered halves.  d_out, d_err (w*h*3) and d_rgba (w*h*4) take the mean, the error estimate and the RGBA8 — or d_out == nullptr: the
+// finish step is not run and the other two are not used.
+int nlm_passes_device(const char* at, uint32_t width, uint32_t height, const double* d_a, const double* d_b, const double* d_var_a, const double* d_var_b,
+                      double* d_pair_var, const NlmParams& prm, const NlmPlan& plan, double* d_fa, double* d_fb, double* d_out, uint8_t* d_rgba,
+                      double* d_err, hipStream_t stream) {
+    const size_t npx = size_t(width) * height;
+    const bool has_var = d_var_a != nullptr;
+    const dim3 flat_block(256), value_grid(uint32_t((npx * 3 + 255) / 256));
+    const dim3 tiles((width + plan.tile - 1) / plan.tile, (height + plan.tile - 1) / plan.tile, 2);
+    if (!has_var) hipLaunchKernelGGL(nlm_variance_kernel, value_grid, flat_block, 0, stream, width, height, d_a, d_b, d_pair_var);
+    const NlmView view{width, height, d_a, d_b, has_var ? d_var_a : d_pair_var, has_var ? d_var_b : d_pair_var};
+    hipLaunchKernelGGL(plan.filter, tiles, dim3(plan.tile * plan.tile), plan.lds_bytes, stream, view, prm, d_fa, d_fb);
+    if (d_out) hipLaunchKernelGGL(nlm_finish_kernel, value_grid, flat_block, 0, stream, uint32_t(npx), d_fa, d_fb, d_out, d_rgba, d_err);
+    HIP_TRY_AS(at, hipGetLastError());
+    return RTTNW_OK;
+}
+
+// rttnw_denoise_nlm's device half: the caller's arrays and the workspace on the device, the kernels between two events, the outputs the
+// caller asked for.
 int nlm_device(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b, const NlmParams& prm,
                double* out_linear_rgb, uint8_t* out_rgba8, double* out_half_a, double* out_half_b, double* out_error_rgb, double* kernel_ms) {
     if (int rc = require_device("denoise_nlm")) return rc;
@@ -121,25 +154,16 @@ int nlm_device(uint32_t width, uint32_t height, const double* half_a, const doub
     HIP_TRY_AS(at, d_out.alloc(npx * 3));
     HIP_TRY_AS(at, d_err.alloc(npx * 3));
     HIP_TRY_AS(at, d_rgba.alloc(npx * 4));
-    // the large tile where its LDS fits a CU, the small one — which fits at every radius the entry point accepts — otherwise
-    const bool large = nlm_lds_bytes(NLM_TILE_LARGE, prm.r, prm.f) <= NLM_LDS_BYTES;
-    const uint32_t tile = large ? NLM_TILE_LARGE : NLM_TILE_SMALL;
-    const size_t lds_bytes = nlm_lds_bytes(tile, prm.r, prm.f);
-    void (*const filter)(NlmView, NlmParams, double*, double*) = large ? nlm_filter_kernel<int(NLM_TILE_LARGE)> : nlm_filter_kernel<int(NLM_TILE_SMALL)>;
-    HIP_TRY_AS(at, hipFuncSetAttribute(reinterpret_cast<const void*>(filter), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+    NlmPlan plan;
+    if (int rc = nlm_plan_device(at, prm, plan)) return rc;
     Event ev0, ev1;
     HIP_TRY_AS(at, create_event(ev0));
     HIP_TRY_AS(at, create_event(ev1));
 
     const hipStream_t stream = nullptr;
-    const dim3 flat_block(256), value_grid(uint32_t((npx * 3 + 255) / 256));
-    const dim3 tiles((width + tile - 1) / tile, (height + tile - 1) / tile, 2);
     HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
-    if (!has_var) hipLaunchKernelGGL(nlm_variance_kernel, value_grid, flat_block, 0, stream, width, height, d_a.p, d_b.p, d_va.p);
-    const NlmView view{width, height, d_a.p, d_b.p, d_va.p, has_var ? d_vb.p : d_va.p};
-    hipLaunchKernelGGL(filter, tiles, dim3(tile * tile), lds_bytes, stream, view, prm, d_fa.p, d_fb.p);
-    hipLaunchKernelGGL(nlm_finish_kernel, value_grid, flat_block, 0, stream, uint32_t(npx), d_fa.p, d_fb.p, d_out.p, d_rgba.p, d_err.p);
-    HIP_TRY_AS(at, hipGetLastError());
+    if (int rc = nlm_passes_device(at, width, height, d_a.p, d_b.p, has_var ? d_va.p : nullptr, has_var ? d_vb.p : nullptr, has_var ? nullptr : d_va.p, prm,
+                                   plan, d_fa.p, d_fb.p, d_out.p, d_rgba.p, d_err.p, stream)) return rc;
     HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
     HIP_TRY_AS(at, hipDeviceSynchronize());
     if (kernel_ms) {

@@ -100,6 +100,13 @@ constexpr size_t nlm_lds_bytes(uint32_t tile, uint32_t r, uint32_t f) {
 static_assert(nlm_lds_bytes(NLM_TILE_SMALL, NLM_MAX_SEARCH_RADIUS, NLM_MAX_PATCH_RADIUS) <= NLM_LDS_BYTES, "the small tile must fit the LDS at the largest radii");
 static_assert(nlm_lds_bytes(NLM_TILE_LARGE, NLM_SEARCH_RADIUS, NLM_PATCH_RADIUS) <= NLM_LDS_BYTES, "the large tile must fit the LDS at the default radii");
 
+// The filter kernel a call's radii take (nlm.hip nlm_plan_device): the tile, its dynamic LDS and the instantiation
+struct NlmPlan {
+    void (*filter)(NlmView, NlmParams, double*, double*);
+    uint32_t tile;
+    size_t lds_bytes;
+};
+
 // rttnw_denoise_nlm's device half (nlm.hip): host arrays in, host arrays out, blocking, on the current device.  Arguments were checked by the caller.
 int nlm_device(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b, const NlmParams& prm,
                double* out_linear_rgb, uint8_t* out_rgba8, double* out_half_a, double* out_half_b, double* out_error_rgb, double* kernel_ms);

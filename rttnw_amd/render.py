@@ -289,6 +289,48 @@ def denoise_nlm(half_a, half_b, var_a=None, var_b=None, search_radius=0, patch_r
     return out
 
 
+SELECT_OUTPUTS = ("linear", "rgba8", "blend", "feature", "nlm", "error")
+
+
+def denoise_select(half_a, half_b, features, var_a=None, var_b=None, iterations=5, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0,
+                   search_radius=0, patch_radius=0, k=0.0, error_radius=0, blend_radius=0, margin=None, want_ms=False):
+    """`rttnw_denoise_select`: per pixel, the better of `denoise` (guided by `features`, what `render_features` returns) and `denoise_nlm` over
+    the two half-buffers `render_halves` returns.  Each half is filtered by both; a filtered half is scored against the other, raw half, the
+    normalised error difference is summed over (2 error_radius + 1)^2 pixels, non-local means is chosen where its mean exceeds `margin`, and the
+    choice is averaged over (2 blend_radius + 1)^2 pixels into the blend weight.  `var_a`, `var_b` (HxWx3, both or neither): the variances of
+    each half's pixel means, given to both filters.  `margin` None is the library default (0.01); a margin of 0 is a margin of 0.  The other
+    parameters are the two filters' own.  Returns a dict: "linear" HxWx3 f64 and "rgba8" HxWx4 u8 (the blended image), "blend" HxW (the weight
+    of non-local means, 0 .. 1), "feature" and "nlm" HxWx3 (the mean of each filter's two filtered halves), "error" HxWx3 — and "ms", the
+    device time, with `want_ms`."""
+    b = library.product()
+    a_, b_ = np.ascontiguousarray(half_a, dtype=np.float64), np.ascontiguousarray(half_b, dtype=np.float64)
+    h, w = a_.shape[:2]
+    if (var_a is None) != (var_b is None):
+        raise ValueError("denoise_select: var_a and var_b go together: both or neither")
+    va = None if var_a is None else np.ascontiguousarray(var_a, dtype=np.float64)
+    vb = None if var_b is None else np.ascontiguousarray(var_b, dtype=np.float64)
+    for arr in (a_, b_, va, vb):
+        if arr is not None and arr.shape != (h, w, 3):
+            raise ValueError("denoise_select: every half and variance is HxWx3 of one frame, got %s beside %s" % (arr.shape, (h, w, 3)))
+    if margin is not None and not -2.0 <= margin <= 2.0:
+        raise ValueError("denoise_select: margin must lie in [-2, 2] (None: the default, 0.01), got %r" % (margin,))
+    f = _feature_arrays(features, h, w)
+    out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "blend": np.zeros((h, w)), "feature": np.zeros((h, w, 3)),
+           "nlm": np.zeros((h, w, 3)), "error": np.zeros((h, w, 3))}
+    dn = _denoise_params(iterations, sigma_luminance, sigma_normal, sigma_depth)
+    nl = abi.Nlm(search_radius=search_radius, patch_radius=patch_radius, k=k, reserved0=0, reserved1=0)
+    sel = abi.Select(error_radius=error_radius, blend_radius=blend_radius, margin=0.0 if margin is None else margin,
+                     use_default_margin=1 if margin is None else 0, reserved0=0)
+    ms = C.c_double(0.0)
+    rc = b.denoise_select(w, h, a_.ctypes.data, b_.ctypes.data, _ptr(va), _ptr(vb), f["albedo"].ctypes.data, f["normal"].ctypes.data,
+                          f["depth"].ctypes.data, f["alpha"].ctypes.data, C.byref(dn), C.byref(nl), C.byref(sel),
+                          *[out[name].ctypes.data for name in SELECT_OUTPUTS], C.byref(ms))
+    check(rc, b, "rttnw_denoise_select")
+    if want_ms:
+        out["ms"] = ms.value
+    return out
+
+
 def lattice_mask(width, height, level):
     """The lattice of a preview as a mask (HxW u8): 1 where x % 2^level == 0 and y % 2^level == 0, row 0 at the top."""
     if not 0 <= int(level) <= 6:
