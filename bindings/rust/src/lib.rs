@@ -7,6 +7,6 @@
 pub mod ffi;
 pub mod scene;
 
-/// The filters that need no scene handle, at the crate's root: the feature-guided one, non-local means over two half-buffers and the
-/// per-pixel choice between the two.
-pub use scene::{denoise, denoise_nlm, denoise_select, NlmOutput, SelectOutput};
+/// The filters that need no scene handle, at the crate's root: the feature-guided one, non-local means over two half-buffers, the
+/// per-pixel choice between the two, and the accumulation of a frame with the reprojected previous one.
+pub use scene::{denoise, denoise_nlm, denoise_select, temporal_accumulate, NlmOutput, SelectOutput, TemporalHistory, TemporalOutput};

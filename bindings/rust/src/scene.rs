@@ -393,6 +393,52 @@ pub fn denoise_select(half_a: &[f64], half_b: &[f64], variances: Option<(&[f64],
     Ok(out)
 }
 
+/// What `temporal_accumulate` returns, and what the next call takes as its history beside that frame's features and camera: the accumulated image
+/// (linear w*h*3 and RGBA8 w*h*4), its variance (w*h*3, with variances only), the frames each pixel's history counts (w*h) and where each pixel was
+/// in the previous frame (w*h*2, NaN without a history: a motion-vector map).
+pub struct TemporalOutput {
+    pub linear: Vec<f64>,
+    pub rgba8: Vec<u8>,
+    pub variance: Option<Vec<f64>>,
+    pub length: Vec<f64>,
+    pub prev_xy: Vec<f64>,
+}
+
+/// The previous frame as `temporal_accumulate` reads it: the previous call's output, that frame's features and its camera.
+pub struct TemporalHistory<'a> {
+    pub output: &'a TemporalOutput,
+    pub features: &'a Features,
+    pub cam: &'a ffi::rttnw_camera_desc,
+}
+
+/// `rttnw_temporal_accumulate`: this frame (`linear` w*h*3, `variance` of its pixel means or None, its features `f`, its camera) blended with the
+/// history, which is fetched from where each pixel's surface point was in the previous frame; None starts a sequence.  Beside a history the
+/// variances come both or neither.
+pub fn temporal_accumulate(linear: &[f64], variance: Option<&[f64]>, f: &Features, cam: &ffi::rttnw_camera_desc, history: Option<&TemporalHistory>,
+                           t: &ffi::rttnw_temporal_params) -> Result<TemporalOutput> {
+    let n = f.width as usize * f.height as usize;
+    let fits = |g: &Features| g.width == f.width && g.height == f.height && g.normal.len() == n * 3 && g.depth.len() == n && g.alpha.len() == n;
+    if linear.len() != n * 3 || variance.map_or(false, |v| v.len() != n * 3) || !fits(f)
+        || history.map_or(false, |h| !fits(h.features) || h.output.linear.len() != n * 3 || h.output.length.len() != n
+                                     || h.output.variance.as_ref().map_or(false, |v| v.len() != n * 3)) {
+        return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "temporal_accumulate: array sizes do not match the image".into() });
+    }
+    let mut out = TemporalOutput { linear: vec![0f64; n * 3], rgba8: vec![0u8; n * 4], variance: variance.map(|_| vec![0f64; n * 3]), length: vec![0f64; n],
+                                   prev_xy: vec![0f64; n * 2] };
+    let null = ptr::null::<f64>();
+    ok(unsafe {
+        ffi::rttnw_temporal_accumulate(f.width, f.height, cam, history.map_or(ptr::null(), |h| h.cam as *const _), linear.as_ptr(),
+                                       variance.map_or(null, |v| v.as_ptr()), f.normal.as_ptr(), f.depth.as_ptr(), f.alpha.as_ptr(),
+                                       history.map_or(null, |h| h.output.linear.as_ptr()),
+                                       history.and_then(|h| h.output.variance.as_ref()).map_or(null, |v| v.as_ptr()),
+                                       history.map_or(null, |h| h.output.length.as_ptr()), history.map_or(null, |h| h.features.normal.as_ptr()),
+                                       history.map_or(null, |h| h.features.depth.as_ptr()), history.map_or(null, |h| h.features.alpha.as_ptr()), t,
+                                       out.linear.as_mut_ptr(), out.rgba8.as_mut_ptr(), out.variance.as_mut().map_or(ptr::null_mut(), |v| v.as_mut_ptr()),
+                                       out.length.as_mut_ptr(), out.prev_xy.as_mut_ptr(), ptr::null_mut())
+    })?;
+    Ok(out)
+}
+
 /// `rttnw_reconstruct`: `denoise` over an image of which only the pixels with a nonzero byte in `valid` (w*h) hold a value; `linear` and
 /// `variance` are never read elsewhere.  Returns (linear w*h*3, RGBA8 w*h*4 with alpha 0 where nothing could be filled, the valid bytes).
 pub fn reconstruct(linear: &[f64], variance: Option<&[f64]>, valid: &[u8], f: &Features, d: &ffi::rttnw_denoise_params) -> Result<(Vec<f64>, Vec<u8>, Vec<u8>)> {

@@ -43,8 +43,8 @@ extern "C" {
                              * (rttnw_render_adaptive, rttnw_render_features / rttnw_denoise, rttnw_render_region, rttnw_render_adaptive_multi,
                              *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region,
                              *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select,
-                             *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised, rttnw_denoise_nlm and
-                             *  rttnw_denoise_select came later, without a version bump: a caller detects each by its symbol) */
+                             *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised, rttnw_denoise_nlm,
+                             *  rttnw_denoise_select and rttnw_temporal_accumulate came later, without a version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -475,6 +475,70 @@ int rttnw_denoise_select(uint32_t width, uint32_t height, const double* half_a, 
                          const rttnw_denoise_params* dn, const rttnw_nlm_params* nl, const rttnw_select_params* sel,
                          double* out_linear_rgb, uint8_t* out_rgba8, double* out_blend, double* out_feature_rgb, double* out_nlm_rgb,
                          double* out_error_rgb, double* kernel_ms);
+
+/* Temporal accumulation: this frame blended with the previous call's result, fetched from where each pixel's surface point was in the previous
+ * frame.  The scene is static and the camera moves (a turntable, a fly-through), so the point behind a pixel was, almost always, seen by the
+ * previous frame as well: its accumulated colour is more samples per pixel at no trace cost.  This is the temporal stage of SVGF (Schied et al.
+ * 2017), whose spatial half is rttnw_denoise.  Calling convention as rttnw_denoise: host arrays in and out (row-major, top row first), blocking,
+ * on the current device, no scene handle; no CPU fallback: RTTNW_ERR_HIP without a device.  Everything is double.
+ *
+ * Arrays.  linear_rgb w*h*3, normal w*h*3, depth w*h, alpha w*h: this frame's render and its rttnw_render_features maps (depth is the distance
+ *   from the ray origin to the first hit, summed over the samples that hit and divided by all samples, like alpha).  prev_linear_rgb,
+ *   prev_variance_rgb, prev_length: the previous call's out_linear_rgb, out_variance_rgb, out_length; prev_normal, prev_depth, prev_alpha: the
+ *   previous frame's feature maps.  prev_length w*h: the frames a pixel's history counts; 0 means "no history here".
+ * Cameras.  Both descriptors become the camera record the renders use (Camera::new, camera.rs:32-61): origin o, lower_left_corner llc,
+ *   horizontal H, vertical V; subscript p marks the previous frame's.  The arithmetic below starts from those records.  The lens is taken at its
+ *   centre: an aperture above 0 is ignored.  Shutter times are not read.
+ * No history.  prev_linear_rgb, prev_variance_rgb, prev_length, prev_normal, prev_depth and prev_alpha all NULL (prev_cam may then be NULL):
+ *   every pixel gets out = this frame, out_length 1, the variance copied, out_prev_xy NaN.
+ * A pixel with alpha == 0 passes through the same way (colour and variance copied, length 1, out_prev_xy NaN): the background is exact there.
+ * 1. Where the pixel was.  dot(a, b) = (a0 * b0 + a1 * b1) + a2 * b2, everywhere.  For pixel (x, y) with alpha != 0, component by component:
+ *    s = (x + 0.5) / w;  t = ((h - 1 - y) + 0.5) / h;  d = ((llc + s * H) + t * V) - o;  z = depth / alpha, the mean distance of the samples
+ *    that hit;  P = o + d * (z / sqrt(dot(d, d))).  Against the previous record:  q = P - o_p;  n = H_p x V_p, that is
+ *    (H1 * V2 - H2 * V1, H2 * V0 - H0 * V2, H0 * V1 - H1 * V0);  e = llc_p - o_p;  lambda = dot(e, n) / dot(q, n);  r = lambda * q - e;
+ *    s' = dot(r, H_p) / dot(H_p, H_p);  t' = dot(r, V_p) / dot(V_p, V_p);  fx = s' * w - 0.5;  fy = (h - t' * h) - 0.5;  zq = sqrt(dot(q, q)).
+ *    The pixel has no history (out = this frame, length 1, out_prev_xy NaN) when lambda > 0 is false, when fx or fy is not finite, or when
+ *    -1 < fx < w or -1 < fy < h is false.  Otherwise out_prev_xy = (fx, fy) — also when every tap below is rejected: the output doubles as a
+ *    motion-vector map.
+ * 2. Bitwise-equal cameras.  When the 15 doubles of the two descriptors are bitwise equal the geometry is skipped: fx = x, fy = y, zq = z
+ *    exactly, so a static camera accumulates pixel on pixel, with no bilinear blur (the general formulas leave a residual of 1e-14 pixels).
+ * 3. Taps.  x0 = floor(fx), ax = fx - x0, y0 = floor(fy), ay = fy - y0.  The four taps (x0 + i, y0 + j) have weights
+ *    (i ? ax : 1 - ax) * (j ? ay : 1 - ay) and are visited in the order 00, 10, 01, 11 (i first).  A tap is dropped when it lies outside the
+ *    image, when its prev_alpha == 0, when its prev_length > 0 is false, when abs(prev_depth / prev_alpha - zq) <= depth_tolerance * zq is
+ *    false, or when dot(n, n') >= normal_min * sqrt(dot(n, n) * dot(n', n')) is false — n this pixel's normal, n' the tap's, both as stored:
+ *    stored normals are short on silhouettes, hence the normalised test.  With normal_min == -1 the normal test is not made.
+ * 4. Blend.  Every sum starts from 0.0 and adds the accepted taps in the order of step 3.  W = the sum of the accepted weights.  W > 0 false:
+ *    reset — out = this frame, length 1, the variance copied.  Otherwise hist = (sum w * c') / W per channel, L = (sum w * len') / W and, with
+ *    variances, vh = (sum w * var') / W: the plain weighted mean, because an accumulated history's taps are correlated and the independent-tap
+ *    formula would understate it.  N = min(L + 1, double(max_history)) (L + 1 where it is the smaller, otherwise — a NaN too — max_history);
+ *    a = 1.0 / N;  out = (1 - a) * hist + a * cur: two products and one sum, not fused;  out_var = ((1 - a) * (1 - a)) * vh + (a * a) * var;
+ *    out_length = N.  Non-finite colours and variances are not special-cased: they propagate through the sums they enter.
+ * 5. Outputs, each optional: out_linear_rgb w*h*3; out_rgba8 w*h*4 of it after main.rs:219-225, alpha 255; out_variance_rgb w*h*3, written
+ *    only when variance_rgb was given; out_length w*h; out_prev_xy w*h*2 (fx, fy); kernel_ms: device time of the kernel alone.
+ * 6. Arithmetic.  + - * /, sqrt, floor, abs and comparisons only; no product is fused into a sum; every expression is evaluated in the order
+ *    written above.  So the device code, a host build of the same header (rttnw_amd/csrc/temporal.hpp) and a restatement in numpy give the
+ *    same bits.
+ * Variances.  variance_rgb (of this frame's pixel means) is optional; beside a history variance_rgb and prev_variance_rgb come both or neither.
+ * Refusals, before the device is touched, each message naming temporal_accumulate and the argument: RTTNW_ERR_INVALID for a NULL cam,
+ *   linear_rgb, normal, depth, alpha or t, width * height == 0, some but not all of the prev_* arrays, a history with a NULL prev_cam, exactly
+ *   one of variance_rgb / prev_variance_rgb beside a history, max_history > 65535, reserved0 != 0, a negative or NaN depth_tolerance, a
+ *   normal_min that is NaN or outside [-1, 1].
+ * Out of scope: moving geometry beyond what one shutter interval blurs; reflections and refractions, which are reprojected with their surface
+ *   and will ghost (SVGF's known limit); albedo demodulation of the history; feeding the filtered image back into the history; colour
+ *   clamping; a device-resident chain between frames; a node-wide form; the native rttnw program. */
+struct rttnw_temporal_params {
+    uint32_t max_history;    /* the most frames a pixel's history counts; 0 = default 32; 1 .. 65535 */
+    uint32_t reserved0;      /* must be 0 */
+    double depth_tolerance;  /* relative; 0 = default 0.05; negative or NaN refused */
+    double normal_min;       /* in [-1, 1]; 0 = default 0.9; -1 switches the test off; NaN or outside refused */
+};
+typedef struct rttnw_temporal_params rttnw_temporal_params;
+int rttnw_temporal_accumulate(uint32_t width, uint32_t height, const rttnw_camera_desc* cam, const rttnw_camera_desc* prev_cam,
+                              const double* linear_rgb, const double* variance_rgb, const double* normal, const double* depth,
+                              const double* alpha, const double* prev_linear_rgb, const double* prev_variance_rgb,
+                              const double* prev_length, const double* prev_normal, const double* prev_depth, const double* prev_alpha,
+                              const rttnw_temporal_params* t, double* out_linear_rgb, uint8_t* out_rgba8, double* out_variance_rgb,
+                              double* out_length, double* out_prev_xy, double* kernel_ms);
 
 /* `render()` on the GPUs of ONE NODE, in one call from one host thread ("library owns its HIP
  * streams / RCCL comms"): the framebuffer's 8x8 tiles are interleaved over `ngpu` ranks, rank r traces its tiles on

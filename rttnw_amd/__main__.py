@@ -45,6 +45,13 @@ each half with rttnw_denoise and with non-local means, and takes per pixel the f
 must win by (-2 .. 2; without the flag the library default, 0.01); FILE receives the blend weight as a grey PNG (white: non-local means).
 --denoise-iterations and the --nlm- flags set the two filters.  --spp must be even.  It does not combine with --noise, --denoise,
 --denoise-nlm, --features, --devices, --window or --passes.
+--orbit K [--orbit-step DEG] [--temporal] [--denoise] renders K frames of --spp samples each from a camera that turns about the axis through
+lookat along view_up, DEG degrees a frame (default 1.0), and ENDS at the scene's own camera: frame k's lookfrom is the scene's, turned by
+(k - (K - 1)) * DEG degrees.  Frame k takes its samples at sample_begin = k * spp, so the frames are independent estimates.  With --temporal
+every frame is blended with the previous result, fetched from where each pixel's surface point was in the previous frame
+(rttnw_temporal_accumulate, guided by first-hit features of min(spp, 16) samples); with --denoise the frame written is rttnw_denoise of it,
+and the history stays unfiltered.  The frames are written as frame_000.png, frame_001.png, ... beside --out.  --orbit does not combine with
+--noise, --window, --devices, --denoise-nlm, --denoise-select, --features or --passes; --temporal needs --orbit.
 """
 import argparse
 import sys
@@ -101,7 +108,7 @@ def refusal(args, refine, devices, window):
           "--refine": args.refine is not None, "--devices": args.devices is not None, "--resume": args.resume is not None,
           "--save-state": args.save_state is not None, "--window": args.window is not None, "--passes": args.passes > 1,
           "--features": args.features is not None, "--denoise": args.denoise, "--denoise-nlm": args.denoise_nlm,
-          "--denoise-select": args.denoise_select}
+          "--denoise-select": args.denoise_select, "--orbit": args.orbit is not None}
     iterations = (0 <= args.denoise_iterations <= 8, "--denoise-iterations must be 0 .. 8")
     state_needs, state_clashes = "only the adaptive render has a state", ("--window", "--passes")
     # in the order they are checked: (flag, why it needs --noise or None, the flags it does not combine with, the reason given for that,
@@ -112,7 +119,13 @@ def refusal(args, refine, devices, window):
                       (args.nlm_k >= 0.0, "--nlm-k must be at least 0 (0: the default, 0.7)")]
     if args.blend_map is not None and not args.denoise_select:
         return "--blend-map needs --denoise-select: only that call has a blend weight"
+    if args.temporal and not on["--orbit"]:
+        return "--temporal needs --orbit: it accumulates the frames of a sequence"
     rules = [
+        ("--orbit", None, ("--noise", "--window", "--devices", "--denoise-nlm", "--denoise-select", "--features", "--passes"),
+         ": it renders a sequence of plain frames of the whole image, on one GPU", [],
+         [(not on["--orbit"] or 1 <= args.orbit <= 1000, "--orbit must be 1 .. 1000 frames"),
+          (args.orbit_step == args.orbit_step and abs(args.orbit_step) <= 360.0, "--orbit-step must be -360 .. 360 degrees"), iterations]),
         ("--denoise-select", None, ("--noise", "--denoise", "--denoise-nlm", "--features", "--devices", "--window", "--passes"),
          ": it filters two plain half renders of the whole frame with both filters, on one GPU", [],
          [(args.spp == 0 or (args.spp >= 2 and args.spp % 2 == 0), EVEN_SPP % ("--denoise-select", args.spp)),
@@ -195,6 +208,11 @@ def main(argv=None):
                     "default 0.01)")
     ap.add_argument("--blend-map", default=None, metavar="FILE", help="selection: also write the blend weight as a grey-scale PNG (white: "
                     "non-local means)")
+    ap.add_argument("--orbit", type=int, default=None, metavar="K", help="render K frames from a camera that turns about lookat and ends at the "
+                    "scene's own; writes frame_000.png, ... beside --out")
+    ap.add_argument("--orbit-step", type=float, default=1.0, metavar="DEG", help="orbit: degrees per frame (default 1.0)")
+    ap.add_argument("--temporal", action="store_true", help="orbit: blend every frame with the reprojected previous result "
+                    "(rttnw_temporal_accumulate)")
     ap.add_argument("--guided", action="store_true", help="adaptive sampling: stop pixels on the noise of the denoised image "
                     "(rttnw_render_adaptive_denoised); writes the denoised image")
     ap.add_argument("--preview", type=int, default=None, metavar="L", help="adaptive sampling: trace 1 pixel in 4^L (x %% 2^L == 0 and y %% 2^L == 0, "
@@ -258,6 +276,24 @@ def main(argv=None):
         Image.fromarray(np.ascontiguousarray(rgba), "RGBA").save(args.out)
         print("%.3fs (window %dx%d at (%d, %d) of %dx%d: %d samples, kernels %.1f ms)"
               % (time.time() - t0, x1 - x0, y1 - y0, x0, y0, w, h, st.samples, st.kernel_ms))
+        return 0
+    if args.orbit is not None:
+        import os
+        where = os.path.dirname(args.out) or "."
+        trace_ms = [0.0]
+
+        def write(k, frame):
+            trace_ms[0] += frame["stats"].kernel_ms
+            Image.fromarray(np.ascontiguousarray(frame["rgba8"]), "RGBA").save(os.path.join(where, "frame_%03d.png" % k))
+
+        frames = render.render_sequence(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, temporal=args.temporal, denoise=args.denoise,
+                                        iterations=args.denoise_iterations, on_frame=write)
+        print("%.3fs (%d frames of %d spp, %g degrees apart: trace kernels %.1f ms; written to %s)"
+              % (time.time() - t0, args.orbit, p.spp, args.orbit_step, trace_ms[0], os.path.join(where, "frame_000.png ...")))
+        if args.temporal:
+            length = frames[-1]["length"]
+            print("temporal: the last frame's history counts %.2f frames on average, %.1f %% of its pixels were reset"
+                  % (length.mean(), 100.0 * (length == 1.0).mean() if args.orbit > 1 else 0.0))
         return 0
     features = None
     own_filter = args.guided or args.preview is not None or args.guided_budget is not None   # the call's own image is the filtered one

@@ -73,6 +73,11 @@ class Select(C.Structure):
                 ("reserved0", C.c_uint32)]
 
 
+class Temporal(C.Structure):
+    """`rttnw_temporal_params` — the parameters of `rttnw_temporal_accumulate` (a 0: the library default; `normal_min` -1: no normal test)."""
+    _fields_ = [("max_history", C.c_uint32), ("reserved0", C.c_uint32), ("depth_tolerance", C.c_double), ("normal_min", C.c_double)]
+
+
 class Guided(C.Structure):
     """`rttnw_guided` — what `rttnw_render_adaptive_denoised` and `rttnw_render_adaptive_budget_denoised` take beside the stopping rule: the
     features' samples and the filter."""
@@ -163,6 +168,8 @@ PRODUCT_FUNCS = [
     ("denoise_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.POINTER(Denoise), C.POINTER(Nlm), C.POINTER(Select), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    ("temporal_accumulate", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(CameraDesc), C.POINTER(CameraDesc)] + [C.c_void_p] * 11 +
+                                     [C.POINTER(Temporal)] + [C.c_void_p] * 5 + [C.POINTER(C.c_double)]),
     ("render_preview", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Preview), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("budget_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint64,

@@ -1,12 +1,14 @@
 // feature_api.hpp — what feature_api.cpp (the extern "C" half of rttnw_render_features and rttnw_denoise) calls: the feature pass's launch
 // code per arithmetic build (feature_kernels.hpp, instantiated in features_f32.hip / features_f64.hip / features_f64_strict.hip) and the
-// device halves of the denoiser and of rttnw_reconstruct (denoise.hip), of rttnw_denoise_nlm (nlm.hip) and of rttnw_denoise_select (select.hip).
+// device halves of the denoiser and of rttnw_reconstruct (denoise.hip), of rttnw_denoise_nlm (nlm.hip), of rttnw_denoise_select (select.hip) and of
+// rttnw_temporal_accumulate (temporal.hip).
 // Kept out of render_common.hpp: the render kernels' translation units do not read it.
 #pragma once
 #include "render_common.hpp"
 #include "denoise.hpp"
 #include "nlm.hpp"
 #include "select.hpp"
+#include "temporal.hpp"
 
 namespace rt {
 
@@ -47,5 +49,13 @@ int select_device(uint32_t width, uint32_t height, const double* half_a, const d
                   const double* albedo, const double* normal, const double* depth, const double* alpha, uint32_t iterations, const DenoiseParams& dn,
                   const NlmParams& nl, const SelectParams& sel, double* out_linear_rgb, uint8_t* out_rgba8, double* out_blend, double* out_feature_rgb,
                   double* out_nlm_rgb, double* out_error_rgb, double* kernel_ms);
+
+// rttnw_temporal_accumulate's device half (temporal.hip): host arrays in, host arrays out (each optional), blocking, on the current device: one
+// kernel (temporal.hpp).  The prev_* arrays are read only with prm.has_history, the variances only with prm.has_variance.  Arguments were checked
+// by the caller.
+int temporal_device(uint32_t width, uint32_t height, const TemporalParams& prm, const double* linear_rgb, const double* variance_rgb, const double* normal,
+                    const double* depth, const double* alpha, const double* prev_linear_rgb, const double* prev_variance_rgb, const double* prev_length,
+                    const double* prev_normal, const double* prev_depth, const double* prev_alpha, double* out_linear_rgb, uint8_t* out_rgba8,
+                    double* out_variance_rgb, double* out_length, double* out_prev_xy, double* kernel_ms);
 
 } // namespace rt

@@ -331,6 +331,116 @@ def denoise_select(half_a, half_b, features, var_a=None, var_b=None, iterations=
     return out
 
 
+TEMPORAL_OUTPUTS = ("linear", "rgba8", "variance", "length", "prev_xy")
+
+
+def temporal_accumulate(linear, features, cam, history=None, variance=None, max_history=0, depth_tolerance=0.0, normal_min=0.0, want_ms=False):
+    """`rttnw_temporal_accumulate`: this frame (`linear` HxWx3, its `features` as `render_features` returns them, its camera `cam`) blended with the
+    previous call's result, which is fetched from where each pixel's surface point was in the previous frame, through four bilinear taps that
+    are kept only where depth and normal say "same surface".  `history`: the dict a previous call returned (it carries that frame's features and
+    camera), or None to start a sequence.  `variance` (HxWx3): the variance of this frame's pixel means; beside a history both frames have one or
+    neither.  A parameter of 0 is the library default (32 frames, depth within 5 %, a normalised normal product of 0.9); `normal_min` -1 switches
+    the normal test off.  Returns a dict: "linear" HxWx3 f64 and "rgba8" HxWx4 u8 (the accumulated image), "variance" HxWx3 or None, "length" HxW
+    (the frames each pixel's history counts), "prev_xy" HxWx2 (where the pixel was in the previous frame; NaN without a history), "features" and
+    "cam" as given — and "ms", the kernel's time, with `want_ms`."""
+    who = "temporal_accumulate"
+    lin = np.ascontiguousarray(linear, dtype=np.float64)
+    if lin.ndim != 3 or lin.shape[2] != 3:
+        raise ValueError("%s: the frame is HxWx3, got %s" % (who, lin.shape))
+    h, w = lin.shape[:2]
+    var = None if variance is None else np.ascontiguousarray(variance, dtype=np.float64)
+    if not 0 <= int(max_history) <= 65535:
+        raise ValueError("%s: max_history must be 0 .. 65535 (0: the default, 32), got %r" % (who, max_history))
+    if not depth_tolerance >= 0.0:
+        raise ValueError("%s: depth_tolerance must be at least 0 (0: the default, 0.05), got %r" % (who, depth_tolerance))
+    if not -1.0 <= normal_min <= 1.0:
+        raise ValueError("%s: normal_min must lie in [-1, 1] (0: the default, 0.9; -1: no normal test), got %r" % (who, normal_min))
+    prev = [None] * 6
+    prev_cam = None
+    if history is not None:
+        missing = [k for k in ("linear", "length", "features", "cam") if history.get(k) is None]
+        if missing:
+            raise ValueError("%s: the history is a previous call's result (it lacks %s)" % (who, ", ".join(missing)))
+        if (var is None) != (history.get("variance") is None):
+            raise ValueError("%s: beside a history both frames have a variance or neither has" % who)
+        pf = history["features"]
+        prev = [None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+                for a in (history["linear"], history.get("variance"), history["length"], pf["normal"], pf["depth"], pf["alpha"])]
+        prev_cam = history["cam"]
+    f = {k: np.ascontiguousarray(features[k], dtype=np.float64) for k in ("normal", "depth", "alpha")}
+    for arr, shape in ((var, (h, w, 3)), (f["normal"], (h, w, 3)), (f["depth"], (h, w)), (f["alpha"], (h, w)), (prev[0], (h, w, 3)), (prev[1], (h, w, 3)),
+                       (prev[2], (h, w)), (prev[3], (h, w, 3)), (prev[4], (h, w)), (prev[5], (h, w))):
+        if arr is not None and arr.shape != shape:
+            raise ValueError("%s: every array is of one %dx%d frame, got %s where %s was expected" % (who, w, h, arr.shape, shape))
+    b = library.product()
+    out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "variance": None if var is None else np.zeros((h, w, 3)),
+           "length": np.zeros((h, w)), "prev_xy": np.zeros((h, w, 2))}
+    t = abi.Temporal(max_history=int(max_history), reserved0=0, depth_tolerance=depth_tolerance, normal_min=normal_min)
+    ms = C.c_double(0.0)
+    rc = b.temporal_accumulate(w, h, C.byref(cam), None if prev_cam is None else C.byref(prev_cam), lin.ctypes.data, _ptr(var), f["normal"].ctypes.data,
+                               f["depth"].ctypes.data, f["alpha"].ctypes.data, *[_ptr(a) for a in prev], C.byref(t),
+                               *[_ptr(out[name]) for name in TEMPORAL_OUTPUTS], C.byref(ms))
+    check(rc, b, "rttnw_temporal_accumulate")
+    out["features"], out["cam"] = features, cam
+    if want_ms:
+        out["ms"] = ms.value
+    return out
+
+
+def orbit_cameras(cam, frames, step_degrees):
+    """The cameras of an orbit of `frames` frames that ENDS at `cam`: frame k's lookfrom is `cam`'s, turned about the axis through lookat along
+    view_up by (k - (frames - 1)) * step_degrees degrees (Rodrigues' formula); everything else is `cam`'s."""
+    if int(frames) < 1:
+        raise ValueError("orbit_cameras: at least one frame, got %r" % (frames,))
+    at, up = np.array(cam.lookat[:], dtype=np.float64), np.array(cam.view_up[:], dtype=np.float64)
+    axis = up / np.sqrt(np.dot(up, up))
+    arm = np.array(cam.lookfrom[:], dtype=np.float64) - at
+    cams = []
+    for k in range(int(frames)):
+        c = type(cam).from_buffer_copy(cam)
+        if k != frames - 1:                      # the last frame is `cam`, bit for bit
+            a = np.deg2rad((k - (frames - 1)) * step_degrees)
+            turned = arm * np.cos(a) + np.cross(axis, arm) * np.sin(a) + axis * (np.dot(axis, arm) * (1.0 - np.cos(a)))
+            for i in range(3):
+                c.lookfrom[i] = at[i] + turned[i]
+        cams.append(c)
+    return cams
+
+
+_spatial_denoise = denoise   # (render_sequence has a parameter of that name)
+
+
+def render_sequence(scene, cams, params, temporal=True, denoise=False, iterations=5, max_history=0, depth_tolerance=0.0, normal_min=0.0,
+                    on_frame=None):
+    """One frame per camera of `cams`: frame k is `render_host` with `sample_begin = params.sample_begin + k * params.spp` (so the frames are
+    independent estimates), its `render_features` of min(spp, 16) samples, and — with `temporal` — `temporal_accumulate` over the previous
+    frame's result.  With `denoise` the image shown is `rttnw_denoise` of the accumulated one; the history stays unfiltered.  Returns a list of
+    dicts: "linear" and "rgba8" (the image to show), "raw" (the frame alone), "length" (None without `temporal`), "accumulated" (the
+    `temporal_accumulate` result, None without `temporal`), "features", "cam", "stats" (the render's Stats).  `on_frame(k, frame)` is called
+    as each frame is done."""
+    frames, history = [], None
+    for k, cam in enumerate(cams):
+        p = copy.copy(params)
+        p.sample_begin = params.sample_begin + k * params.spp
+        raw, rgba, st = render_host(scene, cam, p)
+        pf = copy.copy(p)
+        pf.spp = min(p.spp, 16)
+        features = render_features(scene, cam, pf)
+        lin = raw
+        if temporal:
+            history = temporal_accumulate(raw, features, cam, history=history, max_history=max_history, depth_tolerance=depth_tolerance,
+                                          normal_min=normal_min)
+            lin, rgba = history["linear"], history["rgba8"]
+        if denoise:
+            lin, rgba, _ = _spatial_denoise(lin, features, None, iterations=iterations)
+        frame = {"linear": lin, "rgba8": rgba, "raw": raw, "length": history["length"] if temporal else None,
+                 "accumulated": history if temporal else None, "features": features, "cam": cam, "stats": st}
+        frames.append(frame)
+        if on_frame is not None:
+            on_frame(k, frame)
+    return frames
+
+
 def lattice_mask(width, height, level):
     """The lattice of a preview as a mask (HxW u8): 1 where x % 2^level == 0 and y % 2^level == 0, row 0 at the top."""
     if not 0 <= int(level) <= 6:
