@@ -145,6 +145,19 @@ pub struct rttnw_temporal_params {
     pub normal_min: f64,
 }
 
+/// What `rttnw_temporal_variance` takes beside `rttnw_temporal_params` (include/rttnw_hip.h states the contract); a 0 is the library default (a
+/// history of 4 frames is trusted, a window of radius 3, `rttnw_denoise`'s sigmas for normal and depth).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rttnw_variance_params {
+    pub min_temporal: u32,
+    pub radius: u32,
+    pub sigma_normal: f64,
+    pub sigma_depth: f64,
+    pub reserved0: u32,
+    pub reserved1: u32,
+}
+
 /// What `rttnw_render_adaptive_denoised` takes beside the stopping rule (include/rttnw_hip.h states the contract).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -268,6 +281,7 @@ extern "C" {
     pub fn rttnw_denoise_nlm(width: u32, height: u32, half_a: *const f64, half_b: *const f64, var_a: *const f64, var_b: *const f64, d: *const rttnw_nlm_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_half_a: *mut f64, out_half_b: *mut f64, out_error_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_denoise_select(width: u32, height: u32, half_a: *const f64, half_b: *const f64, var_a: *const f64, var_b: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, dn: *const rttnw_denoise_params, nl: *const rttnw_nlm_params, sel: *const rttnw_select_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_blend: *mut f64, out_feature_rgb: *mut f64, out_nlm_rgb: *mut f64, out_error_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_temporal_accumulate(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, linear_rgb: *const f64, variance_rgb: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, prev_linear_rgb: *const f64, prev_variance_rgb: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, out_length: *mut f64, out_prev_xy: *mut f64, kernel_ms: *mut f64) -> c_int;
+    pub fn rttnw_temporal_variance(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, linear_rgb: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, prev_linear_rgb: *const f64, prev_moment2_rgb: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, v: *const rttnw_variance_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_moment2_rgb: *mut f64, out_length: *mut f64, out_prev_xy: *mut f64, out_variance_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_reconstruct(width: u32, height: u32, linear_rgb: *const f64, variance_rgb: *const f64, valid: *const u8, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, d: *const rttnw_denoise_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, out_valid: *mut u8, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_render_preview(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, v: *const rttnw_preview, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_valid: *mut u8, out_spp: *mut u32, out_raw_linear_rgb: *mut f64, out_raw_stderr_rgb: *mut f64, state_out: *mut f64, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_budget_select(width: u32, height: u32, linear_rgb: *const f64, stderr_rgb: *const f64, spp: *const u32, cap: u32, rel_error: f64, abs_error: f64, max_pixels: u64, out_mask: *mut u8, out_priority: *mut f64, out_selected: *mut u64, kernel_ms: *mut f64) -> c_int;

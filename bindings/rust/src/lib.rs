@@ -8,5 +8,7 @@ pub mod ffi;
 pub mod scene;
 
 /// The filters that need no scene handle, at the crate's root: the feature-guided one, non-local means over two half-buffers, the
-/// per-pixel choice between the two, and the accumulation of a frame with the reprojected previous one.
-pub use scene::{denoise, denoise_nlm, denoise_select, temporal_accumulate, NlmOutput, SelectOutput, TemporalHistory, TemporalOutput};
+/// per-pixel choice between the two, the accumulation of a frame with the reprojected previous one, and that accumulation with the variance
+/// of every pixel's mean estimated from the history.
+pub use scene::{denoise, denoise_nlm, denoise_select, temporal_accumulate, temporal_variance, NlmOutput, SelectOutput, TemporalHistory, TemporalOutput,
+                VarianceHistory, VarianceOutput};

@@ -439,6 +439,50 @@ pub fn temporal_accumulate(linear: &[f64], variance: Option<&[f64]>, f: &Feature
     Ok(out)
 }
 
+/// What `temporal_variance` returns, and what the next call takes as its history beside that frame's features and camera: the accumulated image
+/// (linear w*h*3 and RGBA8 w*h*4), the accumulated second moment of the colour (w*h*3), the frames each pixel's history counts (w*h), where each
+/// pixel was in the previous frame (w*h*2, NaN without a history) and the variance of the pixel means (w*h*3), which `denoise` takes as its variance.
+pub struct VarianceOutput {
+    pub linear: Vec<f64>,
+    pub rgba8: Vec<u8>,
+    pub moment2: Vec<f64>,
+    pub length: Vec<f64>,
+    pub prev_xy: Vec<f64>,
+    pub variance: Vec<f64>,
+}
+
+/// The previous frame as `temporal_variance` reads it: the previous call's output, that frame's features and its camera.
+pub struct VarianceHistory<'a> {
+    pub output: &'a VarianceOutput,
+    pub features: &'a Features,
+    pub cam: &'a ffi::rttnw_camera_desc,
+}
+
+/// `rttnw_temporal_variance`: `temporal_accumulate` of this frame without variances, the colour's second moment carried along the same history, and
+/// the variance of every pixel's accumulated mean: from the two moments where the history is long enough, from a window guided by normal and depth
+/// elsewhere.  None starts a sequence.
+pub fn temporal_variance(linear: &[f64], f: &Features, cam: &ffi::rttnw_camera_desc, history: Option<&VarianceHistory>, t: &ffi::rttnw_temporal_params,
+                         v: &ffi::rttnw_variance_params) -> Result<VarianceOutput> {
+    let n = f.width as usize * f.height as usize;
+    let fits = |g: &Features| g.width == f.width && g.height == f.height && g.normal.len() == n * 3 && g.depth.len() == n && g.alpha.len() == n;
+    if linear.len() != n * 3 || !fits(f)
+        || history.map_or(false, |h| !fits(h.features) || h.output.linear.len() != n * 3 || h.output.moment2.len() != n * 3 || h.output.length.len() != n) {
+        return Err(Error { code: ffi::RTTNW_ERR_INVALID, message: "temporal_variance: array sizes do not match the image".into() });
+    }
+    let mut out = VarianceOutput { linear: vec![0f64; n * 3], rgba8: vec![0u8; n * 4], moment2: vec![0f64; n * 3], length: vec![0f64; n],
+                                   prev_xy: vec![0f64; n * 2], variance: vec![0f64; n * 3] };
+    let null = ptr::null::<f64>();
+    ok(unsafe {
+        ffi::rttnw_temporal_variance(f.width, f.height, cam, history.map_or(ptr::null(), |h| h.cam as *const _), linear.as_ptr(), f.normal.as_ptr(),
+                                     f.depth.as_ptr(), f.alpha.as_ptr(), history.map_or(null, |h| h.output.linear.as_ptr()),
+                                     history.map_or(null, |h| h.output.moment2.as_ptr()), history.map_or(null, |h| h.output.length.as_ptr()),
+                                     history.map_or(null, |h| h.features.normal.as_ptr()), history.map_or(null, |h| h.features.depth.as_ptr()),
+                                     history.map_or(null, |h| h.features.alpha.as_ptr()), t, v, out.linear.as_mut_ptr(), out.rgba8.as_mut_ptr(),
+                                     out.moment2.as_mut_ptr(), out.length.as_mut_ptr(), out.prev_xy.as_mut_ptr(), out.variance.as_mut_ptr(), ptr::null_mut())
+    })?;
+    Ok(out)
+}
+
 /// `rttnw_reconstruct`: `denoise` over an image of which only the pixels with a nonzero byte in `valid` (w*h) hold a value; `linear` and
 /// `variance` are never read elsewhere.  Returns (linear w*h*3, RGBA8 w*h*4 with alpha 0 where nothing could be filled, the valid bytes).
 pub fn reconstruct(linear: &[f64], variance: Option<&[f64]>, valid: &[u8], f: &Features, d: &ffi::rttnw_denoise_params) -> Result<(Vec<f64>, Vec<u8>, Vec<u8>)> {

@@ -44,7 +44,8 @@ extern "C" {
                              *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region,
                              *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select,
                              *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised, rttnw_denoise_nlm,
-                             *  rttnw_denoise_select and rttnw_temporal_accumulate came later, without a version bump: a caller detects each by its symbol) */
+                             *  rttnw_denoise_select, rttnw_temporal_accumulate and rttnw_temporal_variance came later, without a version bump: a caller
+                             *  detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -539,6 +540,62 @@ int rttnw_temporal_accumulate(uint32_t width, uint32_t height, const rttnw_camer
                               const double* prev_length, const double* prev_normal, const double* prev_depth, const double* prev_alpha,
                               const rttnw_temporal_params* t, double* out_linear_rgb, uint8_t* out_rgba8, double* out_variance_rgb,
                               double* out_length, double* out_prev_xy, double* kernel_ms);
+
+/* Temporal accumulation with a variance estimate: rttnw_temporal_accumulate's blend, the second moment of the colour carried along the same
+ * reprojected history, and from the two moments the variance of each pixel's accumulated mean — the variance estimation of SVGF (Schied et al.
+ * 2017, section 4.2), the piece between its temporal stage and its spatial one.  A sequence of plain renders has no per-pixel variance; this
+ * call makes one from the frame history, and where the history is too short to trust (a disoccluded pixel, the first frames) from a window of
+ * neighbours guided by normal and depth.  Calling convention as rttnw_temporal_accumulate: host arrays in and out (row-major, top row first),
+ * blocking, on the current device, no scene handle; no CPU fallback: RTTNW_ERR_HIP without a device.  Everything is double.
+ *
+ * Arrays.  linear_rgb, normal, depth, alpha, prev_linear_rgb, prev_length, prev_normal, prev_depth, prev_alpha and the two cameras: as
+ *   rttnw_temporal_accumulate.  prev_moment2_rgb w*h*3: the previous call's out_moment2_rgb.  No history: all six prev_* arrays NULL,
+ *   prev_moment2_rgb among them (prev_cam may then be NULL).
+ * Stage A, accumulate.  Steps 1 - 4 of rttnw_temporal_accumulate are followed without variances: out_linear_rgb, out_rgba8, out_length and
+ *   out_prev_xy are bit-identical to that entry point's for the same inputs.  A third quantity rides on the same accepted taps, in the same
+ *   order and with the same weights wt: h2 = (sum wt * m2') / W per channel, m2' the tap's prev_moment2_rgb.  With s = cur * cur (rounded once)
+ *   out_m2 = (1 - a) * h2 + a * s: two products and one sum, not fused.  out_m2 = s in every case in which the colour passes through: no
+ *   history, alpha == 0, no place in the previous frame, W > 0 false.
+ * Stage B, estimate.  It reads stage A's outputs — m1 = out_linear_rgb, m2 = out_m2, N = out_length — and this frame's normal, depth and
+ *   alpha.  pos(x) = x < 0 ? 0 : x, so a NaN stays a NaN.  Per pixel and channel:
+ *   alpha == 0: var = 0 — the background is exact.
+ *   N >= min_temporal: var = pos(m2 - m1 * m1) / (N - 1).  m2 - m1 * m1 is the biased per-frame variance of N frame values; times N / (N - 1) it
+ *     is unbiased, and over N it is the variance of their mean.
+ *   Otherwise the spatial estimate, over the window dy = -radius .. radius (outer), dx = -radius .. radius (inner), the centre among the taps.
+ *     Taps outside the image, or whose alpha == 0, are dropped.  A tap weighs w = w_n * w_z, rttnw_denoise's two feature weights in its
+ *     expressions, n and z the centre's normal and depth, n' and z' the tap's, both as stored:
+ *       w_n = (n0 * n'0 + n1 * n'1) + n2 * n'2, replaced by 0 where w_n > 0 is false, then squared k times, 2^k the smallest power of two
+ *         >= sigma_normal (k at most 10);
+ *       qz = (z - z') / ((sigma_depth * (abs(z) + abs(z'))) * 0.5 + 1e-12);  r = 1 / (1 + qz * qz);  w_z = r * r.
+ *     There is no B-spline factor and no colour stop.  Sw = sum w;  M1 = (sum w * m1') / Sw;  M2 = (sum w * m2') / Sw;
+ *     var = pos(M2 - M1 * M1) / N.  Sw > 0 false: var = pos(m2 - m1 * m1) / N.
+ * Arithmetic.  Every sum starts from 0.0 and adds in the order stated; no product is fused into a sum; only + - * /, the functions stage A
+ *   already uses, and comparisons.  Non-finite values are not special-cased: they propagate through the sums they enter.  So the device code, a
+ *   host build of the same header (rttnw_amd/csrc/variance.hpp) and a restatement in numpy give the same bits.
+ * out_variance_rgb is the variance of the pixel means in rttnw_denoise's sense and can be handed to it as variance_rgb.
+ * Outputs, each optional: out_linear_rgb w*h*3, out_rgba8 w*h*4, out_length w*h, out_prev_xy w*h*2 as rttnw_temporal_accumulate's;
+ *   out_moment2_rgb w*h*3; out_variance_rgb w*h*3; kernel_ms: device time of both kernels.
+ * Refusals, before the device is touched, each message naming temporal_variance and the argument: RTTNW_ERR_INVALID for everything
+ *   rttnw_temporal_accumulate refuses for the arguments they share (a NULL cam, linear_rgb, normal, depth, alpha or t, width * height == 0, a
+ *   history with a NULL prev_cam, t's fields), some but not all of the six prev_* arrays, a NULL v, min_temporal == 1 or > 65535, radius > 4, a
+ *   reserved field that is not 0, a negative or NaN sigma.
+ * Out of scope: albedo-demodulated moments — a texture inside the window reads as variance, SVGF's known overestimate; luminance-only
+ *   moments; a device-resident chain between frames; feeding the filtered image back into the history; a node-wide form; the native rttnw
+ *   program. */
+struct rttnw_variance_params {
+    uint32_t min_temporal;  /* a history of at least this many frames is trusted; 0 = default 4; 2 .. 65535 */
+    uint32_t radius;        /* the spatial window is (2 radius + 1)^2; 0 = default 3; 1 .. 4 */
+    double sigma_normal, sigma_depth; /* as rttnw_denoise_params: 0 = that filter's defaults (64, 0.1) */
+    uint32_t reserved0, reserved1;    /* must be 0 */
+};
+typedef struct rttnw_variance_params rttnw_variance_params;
+int rttnw_temporal_variance(uint32_t width, uint32_t height, const rttnw_camera_desc* cam, const rttnw_camera_desc* prev_cam,
+                            const double* linear_rgb, const double* normal, const double* depth, const double* alpha,
+                            const double* prev_linear_rgb, const double* prev_moment2_rgb, const double* prev_length,
+                            const double* prev_normal, const double* prev_depth, const double* prev_alpha,
+                            const rttnw_temporal_params* t, const rttnw_variance_params* v,
+                            double* out_linear_rgb, uint8_t* out_rgba8, double* out_moment2_rgb, double* out_length, double* out_prev_xy,
+                            double* out_variance_rgb, double* kernel_ms);
 
 /* `render()` on the GPUs of ONE NODE, in one call from one host thread ("library owns its HIP
  * streams / RCCL comms"): the framebuffer's 8x8 tiles are interleaved over `ngpu` ranks, rank r traces its tiles on

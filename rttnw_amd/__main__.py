@@ -52,6 +52,9 @@ every frame is blended with the previous result, fetched from where each pixel's
 (rttnw_temporal_accumulate, guided by first-hit features of min(spp, 16) samples); with --denoise the frame written is rttnw_denoise of it,
 and the history stays unfiltered.  The frames are written as frame_000.png, frame_001.png, ... beside --out.  --orbit does not combine with
 --noise, --window, --devices, --denoise-nlm, --denoise-select, --features or --passes; --temporal needs --orbit.
+--temporal-variance (it implies --temporal and needs --orbit) carries the colour's second moment along the same history and estimates the
+variance of every pixel's accumulated mean (rttnw_temporal_variance: from the two moments where the history counts 4 frames, from a 7x7 window
+guided by normal and depth elsewhere); with --denoise that variance is rttnw_denoise's colour stop: accumulate, estimate, filter.
 """
 import argparse
 import sys
@@ -119,6 +122,8 @@ def refusal(args, refine, devices, window):
                       (args.nlm_k >= 0.0, "--nlm-k must be at least 0 (0: the default, 0.7)")]
     if args.blend_map is not None and not args.denoise_select:
         return "--blend-map needs --denoise-select: only that call has a blend weight"
+    if args.temporal_variance and not on["--orbit"]:
+        return "--temporal-variance needs --orbit: it estimates the variance from the accumulated frames of a sequence"
     if args.temporal and not on["--orbit"]:
         return "--temporal needs --orbit: it accumulates the frames of a sequence"
     rules = [
@@ -213,6 +218,8 @@ def main(argv=None):
     ap.add_argument("--orbit-step", type=float, default=1.0, metavar="DEG", help="orbit: degrees per frame (default 1.0)")
     ap.add_argument("--temporal", action="store_true", help="orbit: blend every frame with the reprojected previous result "
                     "(rttnw_temporal_accumulate)")
+    ap.add_argument("--temporal-variance", action="store_true", help="orbit: --temporal, and estimate the variance of every pixel's accumulated "
+                    "mean from the frame history (rttnw_temporal_variance); --denoise then filters with it")
     ap.add_argument("--guided", action="store_true", help="adaptive sampling: stop pixels on the noise of the denoised image "
                     "(rttnw_render_adaptive_denoised); writes the denoised image")
     ap.add_argument("--preview", type=int, default=None, metavar="L", help="adaptive sampling: trace 1 pixel in 4^L (x %% 2^L == 0 and y %% 2^L == 0, "
@@ -243,6 +250,7 @@ def main(argv=None):
     if refused:
         print(refused, file=sys.stderr)
         return 1
+    args.temporal = args.temporal or args.temporal_variance
     from PIL import Image
     from . import abi, library, render
     from .abi import CameraDesc
@@ -287,13 +295,17 @@ def main(argv=None):
             Image.fromarray(np.ascontiguousarray(frame["rgba8"]), "RGBA").save(os.path.join(where, "frame_%03d.png" % k))
 
         frames = render.render_sequence(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, temporal=args.temporal, denoise=args.denoise,
-                                        iterations=args.denoise_iterations, on_frame=write)
+                                        iterations=args.denoise_iterations, on_frame=write, variance=args.temporal_variance)
         print("%.3fs (%d frames of %d spp, %g degrees apart: trace kernels %.1f ms; written to %s)"
               % (time.time() - t0, args.orbit, p.spp, args.orbit_step, trace_ms[0], os.path.join(where, "frame_000.png ...")))
         if args.temporal:
             length = frames[-1]["length"]
             print("temporal: the last frame's history counts %.2f frames on average, %.1f %% of its pixels were reset"
                   % (length.mean(), 100.0 * (length == 1.0).mean() if args.orbit > 1 else 0.0))
+        if args.temporal_variance:
+            var = frames[-1]["accumulated"]["variance"]
+            print("temporal-variance: the last frame's mean standard error is %.4g; %.1f %% of its pixels took the spatial estimate"
+                  % (np.sqrt(var).mean(), 100.0 * ((length < 4.0) & (frames[-1]["features"]["alpha"] != 0.0)).mean()))
         return 0
     features = None
     own_filter = args.guided or args.preview is not None or args.guided_budget is not None   # the call's own image is the filtered one

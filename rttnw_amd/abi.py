@@ -78,6 +78,12 @@ class Temporal(C.Structure):
     _fields_ = [("max_history", C.c_uint32), ("reserved0", C.c_uint32), ("depth_tolerance", C.c_double), ("normal_min", C.c_double)]
 
 
+class Variance(C.Structure):
+    """`rttnw_variance_params` — what `rttnw_temporal_variance` takes beside `rttnw_temporal_params` (a 0: the library default)."""
+    _fields_ = [("min_temporal", C.c_uint32), ("radius", C.c_uint32), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double),
+                ("reserved0", C.c_uint32), ("reserved1", C.c_uint32)]
+
+
 class Guided(C.Structure):
     """`rttnw_guided` — what `rttnw_render_adaptive_denoised` and `rttnw_render_adaptive_budget_denoised` take beside the stopping rule: the
     features' samples and the filter."""
@@ -170,6 +176,8 @@ PRODUCT_FUNCS = [
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("temporal_accumulate", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(CameraDesc), C.POINTER(CameraDesc)] + [C.c_void_p] * 11 +
                                      [C.POINTER(Temporal)] + [C.c_void_p] * 5 + [C.POINTER(C.c_double)]),
+    ("temporal_variance", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(CameraDesc), C.POINTER(CameraDesc)] + [C.c_void_p] * 10 +
+                                   [C.POINTER(Temporal), C.POINTER(Variance)] + [C.c_void_p] * 6 + [C.POINTER(C.c_double)]),
     ("render_preview", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Preview), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("budget_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint64,

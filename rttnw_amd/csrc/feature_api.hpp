@@ -1,7 +1,7 @@
 // feature_api.hpp — what feature_api.cpp (the extern "C" half of rttnw_render_features and rttnw_denoise) calls: the feature pass's launch
 // code per arithmetic build (feature_kernels.hpp, instantiated in features_f32.hip / features_f64.hip / features_f64_strict.hip) and the
-// device halves of the denoiser and of rttnw_reconstruct (denoise.hip), of rttnw_denoise_nlm (nlm.hip), of rttnw_denoise_select (select.hip) and of
-// rttnw_temporal_accumulate (temporal.hip).
+// device halves of the denoiser and of rttnw_reconstruct (denoise.hip), of rttnw_denoise_nlm (nlm.hip), of rttnw_denoise_select (select.hip), of
+// rttnw_temporal_accumulate (temporal.hip) and of rttnw_temporal_variance (variance.hip).
 // Kept out of render_common.hpp: the render kernels' translation units do not read it.
 #pragma once
 #include "render_common.hpp"
@@ -9,6 +9,7 @@
 #include "nlm.hpp"
 #include "select.hpp"
 #include "temporal.hpp"
+#include "variance.hpp"
 
 namespace rt {
 
@@ -57,5 +58,13 @@ int temporal_device(uint32_t width, uint32_t height, const TemporalParams& prm, 
                     const double* depth, const double* alpha, const double* prev_linear_rgb, const double* prev_variance_rgb, const double* prev_length,
                     const double* prev_normal, const double* prev_depth, const double* prev_alpha, double* out_linear_rgb, uint8_t* out_rgba8,
                     double* out_variance_rgb, double* out_length, double* out_prev_xy, double* kernel_ms);
+
+// rttnw_temporal_variance's device half (variance.hip): host arrays in, host arrays out (each optional), blocking, on the current device: the
+// accumulation with the second moment, then the estimate (variance.hpp).  The prev_* arrays are read only with prm.has_history.  Arguments were
+// checked by the caller.
+int variance_device(uint32_t width, uint32_t height, const TemporalParams& prm, const VarianceParams& vprm, const double* linear_rgb, const double* normal,
+                    const double* depth, const double* alpha, const double* prev_linear_rgb, const double* prev_moment2_rgb, const double* prev_length,
+                    const double* prev_normal, const double* prev_depth, const double* prev_alpha, double* out_linear_rgb, uint8_t* out_rgba8,
+                    double* out_moment2_rgb, double* out_length, double* out_prev_xy, double* out_variance_rgb, double* kernel_ms);
 
 } // namespace rt

@@ -223,15 +223,20 @@ def render_region(scene, cam, params, x0, y0, x1, y1, mask=None):
     return lin, rgba, st
 
 
-def denoise(linear, features, stderr=None, iterations=5, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0, want_ms=False):
+def denoise(linear, features, stderr=None, iterations=5, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0, want_ms=False, variance=None):
     """`rttnw_denoise`: the edge-avoiding a-trous filter over `linear` (HxWx3), guided by `features` (what `render_features` returns)
-    and, when `stderr` (HxWx3, `render_adaptive`'s standard errors of the pixel means) is given, by their variance.  A sigma of 0 is
+    and, when `stderr` (HxWx3, `render_adaptive`'s standard errors of the pixel means) is given, by their variance — or by `variance` (HxWx3, in
+    place of `stderr`: the variance of the pixel means as it stands, `temporal_variance`'s for one).  A sigma of 0 is
     the library default.  Returns (linear HxWx3 f64, rgba8 HxWx4 u8, variance HxWx3 f64 or None) — and the device time in ms after
     them with `want_ms`."""
     b = library.product()
     lin = np.ascontiguousarray(linear, dtype=np.float64)
     h, w = lin.shape[:2]
+    if stderr is not None and variance is not None:
+        raise ValueError("denoise: stderr or variance, not both")
     var = None if stderr is None else np.ascontiguousarray(np.square(np.asarray(stderr, dtype=np.float64)))
+    if variance is not None:
+        var = np.ascontiguousarray(variance, dtype=np.float64)
     f = _feature_arrays(features, h, w)
     assert var is None or var.shape == (h, w, 3)
     out = np.zeros((h, w, 3))
@@ -334,6 +339,20 @@ def denoise_select(half_a, half_b, features, var_a=None, var_b=None, iterations=
 TEMPORAL_OUTPUTS = ("linear", "rgba8", "variance", "length", "prev_xy")
 
 
+def _temporal_frame(who, linear, max_history, depth_tolerance, normal_min):
+    """What `temporal_accumulate` and `temporal_variance` check first: the frame as a contiguous HxWx3 array, behind the three parameters' ranges."""
+    lin = np.ascontiguousarray(linear, dtype=np.float64)
+    if lin.ndim != 3 or lin.shape[2] != 3:
+        raise ValueError("%s: the frame is HxWx3, got %s" % (who, lin.shape))
+    if not 0 <= int(max_history) <= 65535:
+        raise ValueError("%s: max_history must be 0 .. 65535 (0: the default, 32), got %r" % (who, max_history))
+    if not depth_tolerance >= 0.0:
+        raise ValueError("%s: depth_tolerance must be at least 0 (0: the default, 0.05), got %r" % (who, depth_tolerance))
+    if not -1.0 <= normal_min <= 1.0:
+        raise ValueError("%s: normal_min must lie in [-1, 1] (0: the default, 0.9; -1: no normal test), got %r" % (who, normal_min))
+    return lin
+
+
 def temporal_accumulate(linear, features, cam, history=None, variance=None, max_history=0, depth_tolerance=0.0, normal_min=0.0, want_ms=False):
     """`rttnw_temporal_accumulate`: this frame (`linear` HxWx3, its `features` as `render_features` returns them, its camera `cam`) blended with the
     previous call's result, which is fetched from where each pixel's surface point was in the previous frame, through four bilinear taps that
@@ -344,17 +363,9 @@ def temporal_accumulate(linear, features, cam, history=None, variance=None, max_
     (the frames each pixel's history counts), "prev_xy" HxWx2 (where the pixel was in the previous frame; NaN without a history), "features" and
     "cam" as given — and "ms", the kernel's time, with `want_ms`."""
     who = "temporal_accumulate"
-    lin = np.ascontiguousarray(linear, dtype=np.float64)
-    if lin.ndim != 3 or lin.shape[2] != 3:
-        raise ValueError("%s: the frame is HxWx3, got %s" % (who, lin.shape))
+    lin = _temporal_frame(who, linear, max_history, depth_tolerance, normal_min)
     h, w = lin.shape[:2]
     var = None if variance is None else np.ascontiguousarray(variance, dtype=np.float64)
-    if not 0 <= int(max_history) <= 65535:
-        raise ValueError("%s: max_history must be 0 .. 65535 (0: the default, 32), got %r" % (who, max_history))
-    if not depth_tolerance >= 0.0:
-        raise ValueError("%s: depth_tolerance must be at least 0 (0: the default, 0.05), got %r" % (who, depth_tolerance))
-    if not -1.0 <= normal_min <= 1.0:
-        raise ValueError("%s: normal_min must lie in [-1, 1] (0: the default, 0.9; -1: no normal test), got %r" % (who, normal_min))
     prev = [None] * 6
     prev_cam = None
     if history is not None:
@@ -387,6 +398,57 @@ def temporal_accumulate(linear, features, cam, history=None, variance=None, max_
     return out
 
 
+VARIANCE_OUTPUTS = ("linear", "rgba8", "moment2", "length", "prev_xy", "variance")
+
+
+def temporal_variance(linear, features, cam, history=None, min_temporal=0, radius=0, sigma_normal=0.0, sigma_depth=0.0, max_history=0,
+                      depth_tolerance=0.0, normal_min=0.0, want_ms=False):
+    """`rttnw_temporal_variance`: `temporal_accumulate` of this frame without variances, the second moment of the colour carried along the same
+    reprojected history, and the variance of each pixel's accumulated mean read off the two moments — where the history counts at least
+    `min_temporal` frames; elsewhere from a (2 radius + 1)^2 window of neighbours weighted by normal and depth as `denoise` weighs them
+    (`sigma_normal`, `sigma_depth`).  `history`: the dict a previous call returned, or None to start a sequence.  A parameter of 0 is the library
+    default (4 frames, radius 3, the filter's sigmas; `temporal_accumulate`'s for the other three).  Returns that function's dict with "moment2"
+    HxWx3 in place of its "variance", and "variance" HxWx3: the variance of the pixel means, which `denoise` takes as its `variance`."""
+    who = "temporal_variance"
+    lin = _temporal_frame(who, linear, max_history, depth_tolerance, normal_min)
+    h, w = lin.shape[:2]
+    if int(min_temporal) == 1 or not 0 <= int(min_temporal) <= 65535:
+        raise ValueError("%s: min_temporal must be 0 (the default, 4) or 2 .. 65535, got %r" % (who, min_temporal))
+    if not 0 <= int(radius) <= 4:
+        raise ValueError("%s: radius must be 0 .. 4 (0: the default, 3), got %r" % (who, radius))
+    if not sigma_normal >= 0.0 or not sigma_depth >= 0.0:
+        raise ValueError("%s: sigma_normal and sigma_depth must be at least 0 (0: the defaults, 64 and 0.1), got %r, %r" % (who, sigma_normal, sigma_depth))
+    prev = [None] * 6
+    prev_cam = None
+    if history is not None:
+        missing = [k for k in ("linear", "moment2", "length", "features", "cam") if history.get(k) is None]
+        if missing:
+            raise ValueError("%s: the history is a previous call's result (it lacks %s)" % (who, ", ".join(missing)))
+        pf = history["features"]
+        prev = [np.ascontiguousarray(a, dtype=np.float64) for a in (history["linear"], history["moment2"], history["length"], pf["normal"], pf["depth"],
+                                                                    pf["alpha"])]
+        prev_cam = history["cam"]
+    f = {k: np.ascontiguousarray(features[k], dtype=np.float64) for k in ("normal", "depth", "alpha")}
+    for arr, shape in ((f["normal"], (h, w, 3)), (f["depth"], (h, w)), (f["alpha"], (h, w)), (prev[0], (h, w, 3)), (prev[1], (h, w, 3)), (prev[2], (h, w)),
+                       (prev[3], (h, w, 3)), (prev[4], (h, w)), (prev[5], (h, w))):
+        if arr is not None and arr.shape != shape:
+            raise ValueError("%s: every array is of one %dx%d frame, got %s where %s was expected" % (who, w, h, arr.shape, shape))
+    b = library.product()
+    out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "moment2": np.zeros((h, w, 3)), "length": np.zeros((h, w)),
+           "prev_xy": np.zeros((h, w, 2)), "variance": np.zeros((h, w, 3))}
+    t = abi.Temporal(max_history=int(max_history), reserved0=0, depth_tolerance=depth_tolerance, normal_min=normal_min)
+    v = abi.Variance(min_temporal=int(min_temporal), radius=int(radius), sigma_normal=sigma_normal, sigma_depth=sigma_depth, reserved0=0, reserved1=0)
+    ms = C.c_double(0.0)
+    rc = b.temporal_variance(w, h, C.byref(cam), None if prev_cam is None else C.byref(prev_cam), lin.ctypes.data, f["normal"].ctypes.data,
+                             f["depth"].ctypes.data, f["alpha"].ctypes.data, *[_ptr(a) for a in prev], C.byref(t), C.byref(v),
+                             *[_ptr(out[name]) for name in VARIANCE_OUTPUTS], C.byref(ms))
+    check(rc, b, "rttnw_temporal_variance")
+    out["features"], out["cam"] = features, cam
+    if want_ms:
+        out["ms"] = ms.value
+    return out
+
+
 def orbit_cameras(cam, frames, step_degrees):
     """The cameras of an orbit of `frames` frames that ENDS at `cam`: frame k's lookfrom is `cam`'s, turned about the axis through lookat along
     view_up by (k - (frames - 1)) * step_degrees degrees (Rodrigues' formula); everything else is `cam`'s."""
@@ -411,13 +473,17 @@ _spatial_denoise = denoise   # (render_sequence has a parameter of that name)
 
 
 def render_sequence(scene, cams, params, temporal=True, denoise=False, iterations=5, max_history=0, depth_tolerance=0.0, normal_min=0.0,
-                    on_frame=None):
+                    on_frame=None, variance=False):
     """One frame per camera of `cams`: frame k is `render_host` with `sample_begin = params.sample_begin + k * params.spp` (so the frames are
     independent estimates), its `render_features` of min(spp, 16) samples, and — with `temporal` — `temporal_accumulate` over the previous
     frame's result.  With `denoise` the image shown is `rttnw_denoise` of the accumulated one; the history stays unfiltered.  Returns a list of
     dicts: "linear" and "rgba8" (the image to show), "raw" (the frame alone), "length" (None without `temporal`), "accumulated" (the
     `temporal_accumulate` result, None without `temporal`), "features", "cam", "stats" (the render's Stats).  `on_frame(k, frame)` is called
-    as each frame is done."""
+    as each frame is done.  With `variance` (which needs `temporal`) the frame goes through `temporal_variance` instead — accumulate, estimate,
+    filter, the three stages of SVGF — and `rttnw_denoise` receives its "variance" for the colour stop; "accumulated" then carries "moment2"
+    and "variance"."""
+    if variance and not temporal:
+        raise ValueError("render_sequence: variance needs temporal: the variance is estimated from the accumulated history")
     frames, history = [], None
     for k, cam in enumerate(cams):
         p = copy.copy(params)
@@ -428,11 +494,11 @@ def render_sequence(scene, cams, params, temporal=True, denoise=False, iteration
         features = render_features(scene, cam, pf)
         lin = raw
         if temporal:
-            history = temporal_accumulate(raw, features, cam, history=history, max_history=max_history, depth_tolerance=depth_tolerance,
-                                          normal_min=normal_min)
+            accumulate = temporal_variance if variance else temporal_accumulate
+            history = accumulate(raw, features, cam, history=history, max_history=max_history, depth_tolerance=depth_tolerance, normal_min=normal_min)
             lin, rgba = history["linear"], history["rgba8"]
         if denoise:
-            lin, rgba, _ = _spatial_denoise(lin, features, None, iterations=iterations)
+            lin, rgba, _ = _spatial_denoise(lin, features, None, iterations=iterations, variance=history["variance"] if variance else None)
         frame = {"linear": lin, "rgba8": rgba, "raw": raw, "length": history["length"] if temporal else None,
                  "accumulated": history if temporal else None, "features": features, "cam": cam, "stats": st}
         frames.append(frame)
