@@ -158,6 +158,48 @@ pub struct rttnw_variance_params {
     pub reserved1: u32,
 }
 
+/// Opaque handle of the SVGF loop (`rttnw_svgf_create`): a sequence's history on the device.
+#[repr(C)]
+pub struct rttnw_svgf {
+    _private: [u8; 0],
+}
+
+/// The settings of an `rttnw_svgf` handle (include/rttnw_hip.h states the contract): the loop's own, then the three stages' parameter blocks, in
+/// which a 0 is that stage's default.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rttnw_svgf_params {
+    pub feedback_iterations: u32,
+    pub demodulate: u32,
+    pub feature_spp: u32,
+    pub reserved0: u32,
+    pub t: rttnw_temporal_params,
+    pub v: rttnw_variance_params,
+    pub d: rttnw_denoise_params,
+}
+
+/// The host arrays a call of `rttnw_svgf_push` / `rttnw_svgf_frame` fills; a null pointer is an output not asked for.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rttnw_svgf_out {
+    pub linear_rgb: *mut f64,
+    pub rgba8: *mut u8,
+    pub accumulated_rgb: *mut f64,
+    pub variance_rgb: *mut f64,
+    pub filtered_variance_rgb: *mut f64,
+    pub length: *mut f64,
+    pub prev_xy: *mut f64,
+    pub moment1_rgb: *mut f64,
+    pub moment2_rgb: *mut f64,
+    pub history_rgb: *mut f64,
+    pub raw_rgb: *mut f64,
+    pub albedo: *mut f64,
+    pub normal: *mut f64,
+    pub depth: *mut f64,
+    pub alpha: *mut f64,
+    pub image_ms: *mut f64,
+}
+
 /// What `rttnw_render_adaptive_denoised` takes beside the stopping rule (include/rttnw_hip.h states the contract).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -281,6 +323,11 @@ extern "C" {
     pub fn rttnw_denoise_nlm(width: u32, height: u32, half_a: *const f64, half_b: *const f64, var_a: *const f64, var_b: *const f64, d: *const rttnw_nlm_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_half_a: *mut f64, out_half_b: *mut f64, out_error_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_denoise_select(width: u32, height: u32, half_a: *const f64, half_b: *const f64, var_a: *const f64, var_b: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, dn: *const rttnw_denoise_params, nl: *const rttnw_nlm_params, sel: *const rttnw_select_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_blend: *mut f64, out_feature_rgb: *mut f64, out_nlm_rgb: *mut f64, out_error_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_temporal_accumulate(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, linear_rgb: *const f64, variance_rgb: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, prev_linear_rgb: *const f64, prev_variance_rgb: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, out_length: *mut f64, out_prev_xy: *mut f64, kernel_ms: *mut f64) -> c_int;
+    pub fn rttnw_svgf_create(width: u32, height: u32, q: *const rttnw_svgf_params, out: *mut *mut rttnw_svgf) -> c_int;
+    pub fn rttnw_svgf_destroy(q: *mut rttnw_svgf);
+    pub fn rttnw_svgf_reset(q: *mut rttnw_svgf) -> c_int;
+    pub fn rttnw_svgf_push(q: *mut rttnw_svgf, cam: *const rttnw_camera_desc, linear_rgb: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, out: *const rttnw_svgf_out) -> c_int;
+    pub fn rttnw_svgf_frame(q: *mut rttnw_svgf, s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, out: *const rttnw_svgf_out, stats: *mut rttnw_stats) -> c_int;
     pub fn rttnw_temporal_variance(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, linear_rgb: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, prev_linear_rgb: *const f64, prev_moment2_rgb: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, v: *const rttnw_variance_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_moment2_rgb: *mut f64, out_length: *mut f64, out_prev_xy: *mut f64, out_variance_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_reconstruct(width: u32, height: u32, linear_rgb: *const f64, variance_rgb: *const f64, valid: *const u8, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, d: *const rttnw_denoise_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, out_valid: *mut u8, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_render_preview(s: *mut rttnw_scene, cam: *const rttnw_camera_desc, p: *const rttnw_params, a: *const rttnw_adaptive, v: *const rttnw_preview, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_valid: *mut u8, out_spp: *mut u32, out_raw_linear_rgb: *mut f64, out_raw_stderr_rgb: *mut f64, state_out: *mut f64, stats: *mut rttnw_stats) -> c_int;

@@ -44,8 +44,8 @@ extern "C" {
                              *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region,
                              *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select,
                              *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised, rttnw_denoise_nlm,
-                             *  rttnw_denoise_select, rttnw_temporal_accumulate and rttnw_temporal_variance came later, without a version bump: a caller
-                             *  detects each by its symbol) */
+                             *  rttnw_denoise_select, rttnw_temporal_accumulate, rttnw_temporal_variance and the rttnw_svgf_create family came later,
+                             *  without a version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -596,6 +596,91 @@ int rttnw_temporal_variance(uint32_t width, uint32_t height, const rttnw_camera_
                             const rttnw_temporal_params* t, const rttnw_variance_params* v,
                             double* out_linear_rgb, uint8_t* out_rgba8, double* out_moment2_rgb, double* out_length, double* out_prev_xy,
                             double* out_variance_rgb, double* kernel_ms);
+
+/* The SVGF loop on the device: one handle that owns a sequence's history on the device, and one call per frame that runs render, features,
+ * accumulate, estimate, filter and feed back on it — rttnw_temporal_variance, rttnw_temporal_accumulate and rttnw_denoise joined without the
+ * host between them, with the two things their own scope left out: the filtered image fed back into the colour history, and albedo
+ * demodulation of everything the history holds.  rttnw_svgf_push takes a frame the caller rendered, as host arrays (row-major, top row first)
+ * like rttnw_temporal_variance; rttnw_svgf_frame renders it itself — rttnw_render's trace (one rank, every precision) and
+ * rttnw_render_features' pass at feature_spp samples and the same sample_begin — and neither result leaves the device.  The handle belongs to the
+ * device that is current at rttnw_svgf_create; every buffer, ping-pong state included, is allocated there and then, and the estimate kernel's
+ * dynamic LDS is admitted: the handle's own stages allocate nothing in a frame call (the trace and the feature pass keep the workspaces they have
+ * in rttnw_render and rttnw_render_features), run on one stream, and the call waits once behind them, before it copies out the outputs the caller
+ * asked for; an output that is NULL is not copied.  No CPU fallback: rttnw_svgf_create returns RTTNW_ERR_HIP without a device.  Everything
+ * behind the trace is double.
+ *
+ * The contract is a composition of the existing entry points.  The state after a call is {H, M1, M2, L, the frame's normal / depth / alpha, its
+ * camera}; it is empty after rttnw_svgf_create and after rttnw_svgf_reset.  In a call the frame has colour C, features F and camera cam; cam' is
+ * the state's camera.
+ * 0. Demodulate, only with `demodulate`.  For a pixel with alpha != 0 and a channel whose albedo > 1e-3, c = C / albedo — rttnw_denoise's rule;
+ *    everywhere else c = C.  A1 is an albedo map of all 1.0.  Without `demodulate` c = C and A1 = F.albedo.
+ * 1. Accumulate and estimate.  TV = rttnw_temporal_variance(cam, cam', c, F, prev_linear_rgb = M1, prev_moment2_rgb = M2, prev_length = L, the
+ *    state's normal, depth and alpha, t, v); with an empty state the no-history call.  The new M1, M2 and L, prev_xy and var are its
+ *    out_linear_rgb, out_moment2_rgb, out_length, out_prev_xy and out_variance_rgb, bit for bit.
+ * 2. Colour history.  With feedback_iterations > 0 and a state, A = rttnw_temporal_accumulate(cam, cam', c, no variances, F, prev_linear_rgb = H,
+ *    prev_length = L, the state's normal, depth and alpha, t).out_linear_rgb; its length and prev_xy are TV's, bit for bit: the taps are the same
+ *    (on the device they are computed once and carry the three quantities).  Otherwise A = M1.
+ * 3. Filter.  D, Dv = the out_linear_rgb and out_variance_rgb of rttnw_denoise(A, var, A1, F.normal, F.depth, F.alpha, d).
+ * 4. Feed back.  With feedback_iterations = j > 0 the new H is the out_linear_rgb of the same rttnw_denoise call with iterations = j.  A pass
+ *    does not depend on how many follow it: on the device this is a tap of the pass loop, not a second run.  With j = 0 no H is kept.
+ * 5. Emit.  linear_rgb = D * albedo on the channels step 0 divided, D elsewhere; accumulated_rgb is A treated likewise; rgba8 is linear_rgb after
+ *    main.rs:219-225 with alpha 255; variance_rgb = var and filtered_variance_rgb = Dv, both in the filter's units (of c, not of C);
+ *    length, prev_xy as TV's; moment1_rgb = M1, moment2_rgb = M2, history_rgb = H (M1 with j = 0): the state the next call reprojects, in the
+ *    filter's units; raw_rgb, albedo, normal, depth, alpha: C and F as the call took or rendered them; image_ms: device time of steps 0 - 5.
+ * rttnw_svgf_frame is rttnw_svgf_push of rttnw_render's out_linear_rgb and of rttnw_render_features' maps taken with spp = feature_spp (0:
+ *   min(p->spp, 16)) and the same sample_begin; raw_rgb and the four maps are those calls' outputs, bit for bit.  p->width and p->height must equal
+ *   the handle's, p->tile_world must be 1, the scene's device must be the handle's; the caller chooses p->sample_begin per frame.  stats
+ *   (optional) is rttnw_render's, its `samples` and `rays` increased by the w * h * feature_spp camera rays of the feature pass.
+ * Arithmetic: the neighbours'.  Only + - * /, sqrt, floor, abs and comparisons; no product is fused into a sum; every sum in the order the composed
+ *   contracts state; non-finite values are not special-cased.  The device code, a host build of the same headers (rttnw_amd/csrc/svgf.hpp and
+ *   those it composes) and a restatement in numpy give the same bits, and they are the bits of the composition above made with the three entry points.
+ * A known approximation.  With feedback, var is the variance of the raw running mean M1, not of the cleaner A: the moments are accumulated apart
+ *   from the colour, as SVGF does.  The filter's colour stop is therefore conservative.
+ * Refusals, before the device is touched, each message naming the call and the argument, RTTNW_ERR_INVALID: a NULL q, `out` handle pointer, cam or
+ *   p; a NULL input array (the rttnw_svgf_out pointer itself may be NULL: the call then only advances the state); width * height == 0;
+ *   everything rttnw_temporal_variance, rttnw_temporal_accumulate and rttnw_denoise refuse for t, v and d; feedback_iterations > d.iterations;
+ *   demodulate > 1; reserved0 != 0; for rttnw_svgf_frame a size that differs from the handle's or tile_world != 1.
+ * One call at a time per handle; handles are independent of each other.
+ * Out of scope: a node-wide form; adaptive sampling inside the sequence; colour clamping of the history; the non-local-means and select filters
+ *   as the spatial stage; the native rttnw program; moving geometry. */
+typedef struct rttnw_svgf rttnw_svgf; /* opaque */
+struct rttnw_svgf_params {
+    uint32_t feedback_iterations; /* 0: the history is the unfiltered accumulation; j >= 1: the colour history is the filter's result after j
+                                     passes (SVGF: 1); must be <= d.iterations */
+    uint32_t demodulate;          /* 0 / 1: accumulate, estimate and filter colour / albedo; any other value refused */
+    uint32_t feature_spp;         /* rttnw_svgf_frame only: samples of the feature pass; 0 = min(p->spp, 16) */
+    uint32_t reserved0;           /* must be 0 */
+    rttnw_temporal_params t;      /* each field as in its own entry point, 0 = its default */
+    rttnw_variance_params v;
+    rttnw_denoise_params d;
+};
+typedef struct rttnw_svgf_params rttnw_svgf_params;
+struct rttnw_svgf_out { /* host arrays, each optional */
+    double* linear_rgb;            /* w*h*3: the frame to show */
+    uint8_t* rgba8;                /* w*h*4 */
+    double* accumulated_rgb;       /* w*h*3: the filter's input, remodulated */
+    double* variance_rgb;          /* w*h*3: the estimate handed to the filter, in the filter's units */
+    double* filtered_variance_rgb; /* w*h*3: rttnw_denoise's out_variance_rgb, same units */
+    double* length;                /* w*h, as rttnw_temporal_variance's out_length */
+    double* prev_xy;               /* w*h*2, as its out_prev_xy */
+    double* moment1_rgb;           /* w*h*3 each: the state the next call reprojects (filter's units) */
+    double* moment2_rgb;
+    double* history_rgb;
+    double* raw_rgb;               /* w*h*3: the frame's colour before step 0 */
+    double* albedo;                /* w*h*3, w*h*3, w*h, w*h: its features */
+    double* normal;
+    double* depth;
+    double* alpha;
+    double* image_ms;              /* one double: device time of everything behind the trace and the feature pass */
+};
+typedef struct rttnw_svgf_out rttnw_svgf_out;
+int rttnw_svgf_create(uint32_t width, uint32_t height, const rttnw_svgf_params* q, rttnw_svgf** out);
+void rttnw_svgf_destroy(rttnw_svgf* q);
+int rttnw_svgf_reset(rttnw_svgf* q); /* drop the history: the next call is a first frame */
+int rttnw_svgf_push(rttnw_svgf* q, const rttnw_camera_desc* cam, const double* linear_rgb, const double* albedo, const double* normal,
+                    const double* depth, const double* alpha, const rttnw_svgf_out* out);
+int rttnw_svgf_frame(rttnw_svgf* q, rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_svgf_out* out,
+                     rttnw_stats* stats);
 
 /* `render()` on the GPUs of ONE NODE, in one call from one host thread ("library owns its HIP
  * streams / RCCL comms"): the framebuffer's 8x8 tiles are interleaved over `ngpu` ranks, rank r traces its tiles on

@@ -55,6 +55,10 @@ and the history stays unfiltered.  The frames are written as frame_000.png, fram
 --temporal-variance (it implies --temporal and needs --orbit) carries the colour's second moment along the same history and estimates the
 variance of every pixel's accumulated mean (rttnw_temporal_variance: from the two moments where the history counts 4 frames, from a 7x7 window
 guided by normal and depth elsewhere); with --denoise that variance is rttnw_denoise's colour stop: accumulate, estimate, filter.
+--svgf [--feedback J] [--demodulate] (it needs --orbit) runs that whole loop on the device, the history never leaving it (rttnw_svgf_frame):
+the frames of --orbit K --temporal-variance --denoise, bit for bit, without the copies between the stages.  --feedback J feeds the filter's
+result after J passes (0 .. --denoise-iterations; SVGF: 1) back into the colour history; --demodulate accumulates, estimates and filters
+colour / albedo, so textures neither blur in the reprojection nor read as variance.  --feedback and --demodulate need --svgf.
 """
 import argparse
 import sys
@@ -122,6 +126,10 @@ def refusal(args, refine, devices, window):
                       (args.nlm_k >= 0.0, "--nlm-k must be at least 0 (0: the default, 0.7)")]
     if args.blend_map is not None and not args.denoise_select:
         return "--blend-map needs --denoise-select: only that call has a blend weight"
+    if args.svgf and not on["--orbit"]:
+        return "--svgf needs --orbit: it runs the accumulate, estimate, filter loop over the frames of a sequence"
+    if (args.feedback or args.demodulate) and not args.svgf:
+        return "--feedback and --demodulate need --svgf: only the loop on the device has them"
     if args.temporal_variance and not on["--orbit"]:
         return "--temporal-variance needs --orbit: it estimates the variance from the accumulated frames of a sequence"
     if args.temporal and not on["--orbit"]:
@@ -130,7 +138,8 @@ def refusal(args, refine, devices, window):
         ("--orbit", None, ("--noise", "--window", "--devices", "--denoise-nlm", "--denoise-select", "--features", "--passes"),
          ": it renders a sequence of plain frames of the whole image, on one GPU", [],
          [(not on["--orbit"] or 1 <= args.orbit <= 1000, "--orbit must be 1 .. 1000 frames"),
-          (args.orbit_step == args.orbit_step and abs(args.orbit_step) <= 360.0, "--orbit-step must be -360 .. 360 degrees"), iterations]),
+          (args.orbit_step == args.orbit_step and abs(args.orbit_step) <= 360.0, "--orbit-step must be -360 .. 360 degrees"), iterations,
+          (0 <= args.feedback <= max(args.denoise_iterations, 0), "--feedback must be 0 .. --denoise-iterations (%d)" % args.denoise_iterations)]),
         ("--denoise-select", None, ("--noise", "--denoise", "--denoise-nlm", "--features", "--devices", "--window", "--passes"),
          ": it filters two plain half renders of the whole frame with both filters, on one GPU", [],
          [(args.spp == 0 or (args.spp >= 2 and args.spp % 2 == 0), EVEN_SPP % ("--denoise-select", args.spp)),
@@ -220,6 +229,11 @@ def main(argv=None):
                     "(rttnw_temporal_accumulate)")
     ap.add_argument("--temporal-variance", action="store_true", help="orbit: --temporal, and estimate the variance of every pixel's accumulated "
                     "mean from the frame history (rttnw_temporal_variance); --denoise then filters with it")
+    ap.add_argument("--svgf", action="store_true", help="orbit: accumulate, estimate and filter every frame on the device, the history never leaving "
+                    "it (rttnw_svgf_frame)")
+    ap.add_argument("--feedback", type=int, default=0, metavar="J", help="svgf: feed the filter's result after J passes back into the colour history "
+                    "(0 .. --denoise-iterations; default 0: the unfiltered accumulation)")
+    ap.add_argument("--demodulate", action="store_true", help="svgf: accumulate, estimate and filter colour / albedo")
     ap.add_argument("--guided", action="store_true", help="adaptive sampling: stop pixels on the noise of the denoised image "
                     "(rttnw_render_adaptive_denoised); writes the denoised image")
     ap.add_argument("--preview", type=int, default=None, metavar="L", help="adaptive sampling: trace 1 pixel in 4^L (x %% 2^L == 0 and y %% 2^L == 0, "
@@ -294,14 +308,22 @@ def main(argv=None):
             trace_ms[0] += frame["stats"].kernel_ms
             Image.fromarray(np.ascontiguousarray(frame["rgba8"]), "RGBA").save(os.path.join(where, "frame_%03d.png" % k))
 
-        frames = render.render_sequence(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, temporal=args.temporal, denoise=args.denoise,
-                                        iterations=args.denoise_iterations, on_frame=write, variance=args.temporal_variance)
+        if args.svgf:
+            frames = render.render_sequence_device(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, feedback=args.feedback,
+                                                   demodulate=args.demodulate, iterations=args.denoise_iterations, on_frame=write)
+            args.temporal = args.temporal_variance = True
+        else:
+            frames = render.render_sequence(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, temporal=args.temporal, denoise=args.denoise,
+                                            iterations=args.denoise_iterations, on_frame=write, variance=args.temporal_variance)
         print("%.3fs (%d frames of %d spp, %g degrees apart: trace kernels %.1f ms; written to %s)"
               % (time.time() - t0, args.orbit, p.spp, args.orbit_step, trace_ms[0], os.path.join(where, "frame_000.png ...")))
         if args.temporal:
             length = frames[-1]["length"]
             print("temporal: the last frame's history counts %.2f frames on average, %.1f %% of its pixels were reset"
                   % (length.mean(), 100.0 * (length == 1.0).mean() if args.orbit > 1 else 0.0))
+        if args.svgf:
+            print("svgf: feedback %d, %s; %.3f ms a frame on the device behind the trace and the feature pass"
+                  % (args.feedback, "colour / albedo" if args.demodulate else "colour", sum(f["image_ms"] for f in frames) / len(frames)))
         if args.temporal_variance:
             var = frames[-1]["accumulated"]["variance"]
             print("temporal-variance: the last frame's mean standard error is %.4g; %.1f %% of its pixels took the spatial estimate"

@@ -84,6 +84,21 @@ class Variance(C.Structure):
                 ("reserved0", C.c_uint32), ("reserved1", C.c_uint32)]
 
 
+class Svgf(C.Structure):
+    """`rttnw_svgf_params` — the settings of an `rttnw_svgf` handle: the loop's own, then the three stages' blocks (a 0: that stage's default)."""
+    _fields_ = [("feedback_iterations", C.c_uint32), ("demodulate", C.c_uint32), ("feature_spp", C.c_uint32), ("reserved0", C.c_uint32),
+                ("t", Temporal), ("v", Variance), ("d", Denoise)]
+
+
+SVGF_OUTPUTS = ("linear_rgb", "rgba8", "accumulated_rgb", "variance_rgb", "filtered_variance_rgb", "length", "prev_xy", "moment1_rgb", "moment2_rgb",
+                "history_rgb", "raw_rgb", "albedo", "normal", "depth", "alpha", "image_ms")
+
+
+class SvgfOut(C.Structure):
+    """`rttnw_svgf_out` — the host arrays a call of `rttnw_svgf_push` / `rttnw_svgf_frame` fills, each optional."""
+    _fields_ = [(name, C.c_void_p) for name in SVGF_OUTPUTS]
+
+
 class Guided(C.Structure):
     """`rttnw_guided` — what `rttnw_render_adaptive_denoised` and `rttnw_render_adaptive_budget_denoised` take beside the stopping rule: the
     features' samples and the filter."""
@@ -178,6 +193,11 @@ PRODUCT_FUNCS = [
                                      [C.POINTER(Temporal)] + [C.c_void_p] * 5 + [C.POINTER(C.c_double)]),
     ("temporal_variance", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(CameraDesc), C.POINTER(CameraDesc)] + [C.c_void_p] * 10 +
                                    [C.POINTER(Temporal), C.POINTER(Variance)] + [C.c_void_p] * 6 + [C.POINTER(C.c_double)]),
+    ("svgf_create", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(Svgf), C.POINTER(C.c_void_p)]),
+    ("svgf_destroy", None, [C.c_void_p]),
+    ("svgf_reset", C.c_int, [C.c_void_p]),
+    ("svgf_push", C.c_int, [C.c_void_p, C.POINTER(CameraDesc)] + [C.c_void_p] * 5 + [C.POINTER(SvgfOut)]),
+    ("svgf_frame", C.c_int, [C.c_void_p, scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(SvgfOut), C.POINTER(Stats)]),
     ("render_preview", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Preview), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("budget_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint64,

@@ -74,7 +74,8 @@ __global__ void atrous_finish_kernel(uint32_t n, uint32_t remodulate, const doub
 template <bool FLAGS>
 void atrous_enqueue(uint32_t width, uint32_t height, const double* d_in, const double* d_var, const uint8_t* d_valid, const double* d_albedo,
                     const double* d_normal, const double* d_depth, const double* d_alpha, uint32_t iterations, const DenoiseParams& prm,
-                    double* const d_c[2], double* const d_v[2], uint8_t* const d_h[2], uint8_t* d_rgba, uint8_t* d_out_valid, hipStream_t stream, int& out) {
+                    double* const d_c[2], double* const d_v[2], uint8_t* const d_h[2], uint8_t* d_rgba, uint8_t* d_out_valid, hipStream_t stream, int& out,
+                    uint32_t tap_after = 0, double* d_tap = nullptr) {
     const auto flags = [](auto* p) { if constexpr (FLAGS) return p; else return NoFlags{}; };
     uint8_t* const no_h[2] = {nullptr, nullptr};
     uint8_t* const* h = FLAGS ? d_h : no_h;
@@ -96,6 +97,12 @@ void atrous_enqueue(uint32_t width, uint32_t height, const double* d_in, const d
                                    h[cur ^ 1]);
             else hipLaunchKernelGGL(atrous_pass_kernel<>, grid, block, 0, stream, img, prm, 1u << i, d_c[cur ^ 1], d_v[cur ^ 1]);
             cur ^= 1;
+            // the tap (atrous_passes_tap_device): what the call would return with i + 1 iterations, the finish step's colour alone.  d_rgba is
+            // written again by the last finish step, behind this one on the stream.
+            if constexpr (!FLAGS)
+                if (d_tap && i + 1 == tap_after)
+                    hipLaunchKernelGGL(atrous_finish_kernel<false>, pixel_grid, flat_block, 0, stream, n, 1u, d_c[cur], nullptr, d_albedo, d_alpha, d_tap, d_rgba,
+                                       nullptr, NoFlags{}, NoFlags{});
         }
         colour = d_c[cur];
         variance = has_var ? d_v[cur] : nullptr;
@@ -119,8 +126,20 @@ int atrous_passes_device(uint32_t width, uint32_t height, const double* d_in, co
                          double* const d_c[2], double* const d_v[2], uint8_t* const d_h[2], uint8_t* d_rgba, uint8_t* d_out_valid, hipStream_t stream,
                          int& out) {
     (d_valid ? atrous_enqueue<true> : atrous_enqueue<false>)(width, height, d_in, d_var, d_valid, d_albedo, d_normal, d_depth, d_alpha, iterations, prm, d_c,
-                                                              d_v, d_h, d_rgba, d_out_valid, stream, out);
+                                                              d_v, d_h, d_rgba, d_out_valid, stream, out, 0u, nullptr);
     HIP_TRY_AS(d_valid ? "reconstruct: " : "denoise: ", hipGetLastError());
+    return RTTNW_OK;
+}
+
+// rttnw_denoise's passes with a TAP of the pass loop (rttnw_svgf_push's feedback): beside everything atrous_passes_device leaves, d_tap (w*h*3)
+// receives the linear image the same call would return with `tap_after` iterations, 1 <= tap_after <= iterations — a pass does not depend on how
+// many follow it, so this is one more finish step behind pass tap_after, not a second run.  No flags: every pixel holds a value.
+int atrous_passes_tap_device(uint32_t width, uint32_t height, const double* d_in, const double* d_var, const double* d_albedo, const double* d_normal,
+                             const double* d_depth, const double* d_alpha, uint32_t iterations, const DenoiseParams& prm, double* const d_c[2],
+                             double* const d_v[2], uint8_t* d_rgba, uint32_t tap_after, double* d_tap, hipStream_t stream, int& out) {
+    atrous_enqueue<false>(width, height, d_in, d_var, nullptr, d_albedo, d_normal, d_depth, d_alpha, iterations, prm, d_c, d_v, nullptr, d_rgba, nullptr,
+                          stream, out, tap_after, d_tap);
+    HIP_TRY_AS("svgf: ", hipGetLastError());
     return RTTNW_OK;
 }
 

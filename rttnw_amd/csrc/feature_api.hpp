@@ -66,5 +66,20 @@ int variance_device(uint32_t width, uint32_t height, const TemporalParams& prm, 
                     const double* depth, const double* alpha, const double* prev_linear_rgb, const double* prev_moment2_rgb, const double* prev_length,
                     const double* prev_normal, const double* prev_depth, const double* prev_alpha, double* out_linear_rgb, uint8_t* out_rgba8,
                     double* out_moment2_rgb, double* out_length, double* out_prev_xy, double* out_variance_rgb, double* kernel_ms);
+// ... and its kernels alone, in the shape of atrous_passes_device: variance_admit_lds admits the estimate kernel's dynamic LDS for a radius — before
+// the caller starts its clock —, variance_passes_device enqueues the kernels on `stream` over buffers that are already on the device: nothing
+// allocated, nothing copied, no wait.  prm == nullptr: the estimate alone, over a stage A's outputs that d_out, d_m2 and d_len already hold
+// (rttnw_svgf_push's accumulate kernel writes them); d_lin, the d_p* buffers, d_rgba and d_xy are then not used.  `at`: the prefix of an error's message.
+int variance_admit_lds(const char* at, uint32_t radius);
+int variance_passes_device(const char* at, uint32_t width, uint32_t height, const TemporalParams* prm, const VarianceParams& vprm, const double* d_lin,
+                           const double* d_normal, const double* d_depth, const double* d_alpha, const double* d_plin, const double* d_pm2,
+                           const double* d_plen, const double* d_pnormal, const double* d_pdepth, const double* d_palpha, double* d_out, uint8_t* d_rgba,
+                           double* d_m2, double* d_len, double* d_xy, double* d_var, hipStream_t stream);
+
+// rttnw_denoise's passes with a tap of the pass loop (denoise.hip): atrous_passes_device without flags, and d_tap (w*h*3) receives the linear image
+// the same call would return with `tap_after` iterations, 1 <= tap_after <= iterations.  rttnw_svgf_push's feedback.
+int atrous_passes_tap_device(uint32_t width, uint32_t height, const double* d_in, const double* d_var, const double* d_albedo, const double* d_normal,
+                             const double* d_depth, const double* d_alpha, uint32_t iterations, const DenoiseParams& prm, double* const d_c[2],
+                             double* const d_v[2], uint8_t* d_rgba, uint32_t tap_after, double* d_tap, hipStream_t stream, int& out);
 
 } // namespace rt

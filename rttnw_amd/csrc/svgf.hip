@@ -1,0 +1,319 @@
+// svgf.hip — rttnw_svgf_create / _destroy / _reset / _push / _frame (include/rttnw_hip.h): the SVGF loop over a history that stays on the device,
+// around the arithmetic of svgf.hpp, double throughout.  The handle owns every buffer from rttnw_svgf_create on; a frame call enqueues, on one
+// stream and without allocating,
+//   svgf_ingest_kernel      one thread per pixel, blocks of 32 x 8: the frame's colour — the trace's packed tiles (reals of the render's precision,
+//                           tile * 64 + y * 8 + x, four reals a pixel: guided_raw_kernel's order) or the doubles rttnw_svgf_push uploaded — to
+//                           row-major doubles, divided by the albedo with `demodulate`, and the per-channel "was divided" bytes
+//   svgf_accumulate_kernel  one thread per pixel, blocks of 64 x 4 like variance_accumulate_kernel: the reprojection and the four taps once,
+//                           M1, M2 and — with feedback — the colour over H on them; plain global loads, no LDS
+//   variance_estimate_kernel (variance.hip) and the à-trous passes (denoise.hip) as they are, the feedback a tap of the pass loop
+//   svgf_emit_kernel        one thread per pixel: the result and the accumulation multiplied back, and the RGBA8
+// then waits once and copies out what the caller asked for.  No atomics.
+#include "feature_api.hpp"
+#include "render_multi.hpp"
+#include "svgf.hpp"
+
+struct rttnw_svgf {
+    int device = -1;
+    uint32_t width = 0, height = 0;
+    rttnw_svgf_params q = {};
+    rt::VarianceParams vprm = {};
+    rt::DenoiseParams dprm = {};
+    bool has_state = false;
+    int cur = 0; // maps[cur], m1[cur], m2[cur], len[cur] are the state; the other halves are written by the next call
+    rttnw_camera_desc cam = {};
+    rt::DevBuf<uint8_t> packed, flags, rgba, scratch_rgba;
+    rt::DevBuf<double> raw, c, maps[2], m1[2], m2[2], len[2], hist, acc, xy, var, ones, fc[2], fv[2], out_lin, out_acc;
+    rt::Event ev0, ev1;
+};
+
+namespace rt {
+namespace {
+
+// T: the reals the colour comes in; PACKED: the trace's tiles (four reals a pixel) or a row-major image (three)
+template <typename T, bool PACKED>
+__global__ void svgf_ingest_kernel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t demodulate, const T* __restrict__ colour,
+                                   const double* __restrict__ albedo, const double* __restrict__ alpha, double* __restrict__ out_raw,
+                                   double* __restrict__ out_c, uint8_t* __restrict__ out_flags) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const size_t p = size_t(y) * width + x;
+    const T* src = PACKED ? colour + (tile_permuted(x >> 3, y >> 3, tiles_x) * 64ull + ((y & 7u) << 3) + (x & 7u)) * 4ull : colour + p * 3;
+    const double a = alpha[p];
+    for (int ch = 0; ch < 3; ++ch) {
+        const double v = double(src[ch]);
+        uint8_t divided;
+        if (PACKED) out_raw[p * 3 + ch] = v;
+        out_c[p * 3 + ch] = svgf_ingest_value(demodulate != 0u, v, albedo[p * 3 + ch], a, divided);
+        out_flags[p * 3 + ch] = divided;
+    }
+}
+
+__global__ __launch_bounds__(int(SVGF_BLOCK_X* SVGF_BLOCK_Y)) void svgf_accumulate_kernel(
+    uint32_t width, uint32_t height, TemporalParams prm, uint32_t feedback, const double* __restrict__ linear, const double* __restrict__ normal,
+    const double* __restrict__ depth, const double* __restrict__ alpha, const double* __restrict__ prev_moment1, const double* __restrict__ prev_moment2,
+    const double* __restrict__ prev_history, const double* __restrict__ prev_length, const double* __restrict__ prev_normal,
+    const double* __restrict__ prev_depth, const double* __restrict__ prev_alpha, double* __restrict__ out_moment1, double* __restrict__ out_moment2,
+    double* __restrict__ out_acc, double* __restrict__ out_length, double* __restrict__ out_prev_xy) {
+    const uint32_t x = blockIdx.x * SVGF_BLOCK_X + threadIdx.x, y = blockIdx.y * SVGF_BLOCK_Y + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const SvgfAccumulated px = svgf_accumulate_pixel(width, height, x, y, prm, feedback != 0u, linear, normal, depth, alpha, prev_moment1, prev_moment2,
+                                                     prev_history, prev_length, prev_normal, prev_depth, prev_alpha);
+    const size_t p = size_t(y) * width + x;
+    for (int ch = 0; ch < 3; ++ch) {
+        out_moment1[p * 3 + ch] = px.m1[ch];
+        out_moment2[p * 3 + ch] = px.m2[ch];
+        out_acc[p * 3 + ch] = px.a[ch];
+    }
+    out_length[p] = px.length;
+    out_prev_xy[p * 2] = px.xy[0];
+    out_prev_xy[p * 2 + 1] = px.xy[1];
+}
+
+__global__ void svgf_emit_kernel(uint32_t n, const double* __restrict__ filtered, const double* __restrict__ accumulated, const double* __restrict__ albedo,
+                                 const uint8_t* __restrict__ flags, double* __restrict__ out_linear, double* __restrict__ out_accumulated,
+                                 uint8_t* __restrict__ out_rgba8) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; // one thread per pixel
+    if (i >= n) return;
+    const size_t o = size_t(i) * 3;
+    for (int ch = 0; ch < 3; ++ch) {
+        const double lin = svgf_emit_value(filtered[o + ch], albedo[o + ch], flags[o + ch]);
+        out_linear[o + ch] = lin;
+        out_accumulated[o + ch] = svgf_emit_value(accumulated[o + ch], albedo[o + ch], flags[o + ch]);
+        out_rgba8[size_t(i) * 4 + ch] = denoise_quantise(lin);
+    }
+    out_rgba8[size_t(i) * 4 + 3] = 255;
+}
+
+__global__ void svgf_fill_kernel(size_t n, double value, double* __restrict__ out) {
+    const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = value;
+}
+
+int refuse(const char* call, const char* what) {
+    set_last_error(std::string(call) + ": " + what);
+    return RTTNW_ERR_INVALID;
+}
+
+// What rttnw_temporal_variance, rttnw_temporal_accumulate and rttnw_denoise refuse for their parameter blocks, then the loop's own
+int refuse_params(const char* call, const rttnw_svgf_params* q) {
+    const rttnw_temporal_params& t = q->t;
+    const rttnw_variance_params& v = q->v;
+    const rttnw_denoise_params& d = q->d;
+    if (t.max_history > TEMPORAL_HISTORY_LIMIT) return refuse(call, "q->t.max_history is more than 65535");
+    if (t.reserved0 != 0) return refuse(call, "q->t.reserved0 must be 0");
+    if (!(t.depth_tolerance >= 0.0)) return refuse(call, "q->t.depth_tolerance must be >= 0 (and not NaN)");
+    if (!(t.normal_min >= -1.0 && t.normal_min <= 1.0)) return refuse(call, "q->t.normal_min must lie in [-1, 1] (and not be NaN)");
+    if (v.min_temporal == 1 || v.min_temporal > TEMPORAL_HISTORY_LIMIT) return refuse(call, "q->v.min_temporal must be 0 (the default, 4) or 2 .. 65535");
+    if (v.radius > VARIANCE_MAX_RADIUS) return refuse(call, "q->v.radius is more than 4");
+    if (v.reserved0 != 0 || v.reserved1 != 0) return refuse(call, "q->v.reserved0 and q->v.reserved1 must be 0");
+    if (!(v.sigma_normal >= 0.0) || !(v.sigma_depth >= 0.0)) return refuse(call, "the sigmas (q->v.sigma_normal, q->v.sigma_depth) must be >= 0 (and not NaN)");
+    if (d.iterations > DENOISE_MAX_ITERATIONS) return refuse(call, "q->d.iterations: more than 8 iterations");
+    if (d.reserved0 != 0) return refuse(call, "q->d.reserved0 must be 0");
+    if (!(d.sigma_luminance >= 0.0) || !(d.sigma_normal >= 0.0) || !(d.sigma_depth >= 0.0)) {
+        return refuse(call, "the sigmas (q->d.sigma_luminance, sigma_normal, sigma_depth) must be >= 0 (and not NaN)");
+    }
+    if (q->feedback_iterations > d.iterations) return refuse(call, "q->feedback_iterations is more than q->d.iterations");
+    if (q->demodulate > 1) return refuse(call, "q->demodulate must be 0 or 1");
+    if (q->reserved0 != 0) return refuse(call, "q->reserved0 must be 0");
+    return 0;
+}
+
+// Steps 0 - 5 of the contract behind a frame whose features are in maps[cur ^ 1]: ingest (`packed`: the trace's tiles of `precision`, or the
+// uploaded doubles), accumulate, estimate, filter with the tap, emit — enqueued between the handle's events —, the one wait, the outputs.
+int svgf_run(const char* call, ::rttnw_svgf* g, const rttnw_camera_desc* cam, bool packed, uint32_t precision, const rttnw_svgf_out* out) {
+    const std::string at = std::string(call) + ": ";
+    const uint32_t w = g->width, h = g->height;
+    const size_t npx = size_t(w) * h;
+    const int nxt = g->cur ^ 1, old = g->cur;
+    const hipStream_t stream = nullptr;
+    double* maps = g->maps[nxt].p;
+    const double *albedo = maps, *normal = maps + npx * 3, *depth = maps + npx * 6, *alpha = maps + npx * 7;
+    const double* pmaps = g->maps[old].p;
+    const bool feedback = g->q.feedback_iterations > 0 && g->has_state;
+
+    const CameraRec<double> rec = camera_of<double>(cam);
+    CameraRec<double> prev_rec = {};
+    if (g->has_state) prev_rec = camera_of<double>(&g->cam);
+    const bool same_camera = g->has_state && std::memcmp(cam, &g->cam, sizeof(rttnw_camera_desc)) == 0;
+    const TemporalParams prm = temporal_params(rec, g->has_state ? &prev_rec : nullptr, same_camera, g->q.t.max_history, g->q.t.depth_tolerance,
+                                               g->q.t.normal_min, false);
+    rttnw_tile_layout L;
+    fill_layout(w, h, 1, L);
+
+    HIP_TRY_AS(at, hipEventRecord(g->ev0.get(), stream));
+    const dim3 block(32, 8), grid((w + 31) / 32, (h + 7) / 8);
+    if (!packed)
+        hipLaunchKernelGGL((svgf_ingest_kernel<double, false>), grid, block, 0, stream, w, h, L.tiles_x, g->q.demodulate, (const double*)g->raw.p, albedo, alpha,
+                           g->raw.p, g->c.p, g->flags.p);
+    else if (precision == RTTNW_F32)
+        hipLaunchKernelGGL((svgf_ingest_kernel<float, true>), grid, block, 0, stream, w, h, L.tiles_x, g->q.demodulate, (const float*)g->packed.p, albedo, alpha,
+                           g->raw.p, g->c.p, g->flags.p);
+    else
+        hipLaunchKernelGGL((svgf_ingest_kernel<double, true>), grid, block, 0, stream, w, h, L.tiles_x, g->q.demodulate, (const double*)g->packed.p, albedo,
+                           alpha, g->raw.p, g->c.p, g->flags.p);
+    HIP_TRY_AS(at, hipGetLastError());
+
+    const dim3 ablock(SVGF_BLOCK_X, SVGF_BLOCK_Y), agrid((w + SVGF_BLOCK_X - 1) / SVGF_BLOCK_X, (h + SVGF_BLOCK_Y - 1) / SVGF_BLOCK_Y);
+    hipLaunchKernelGGL(svgf_accumulate_kernel, agrid, ablock, 0, stream, w, h, prm, feedback ? 1u : 0u, (const double*)g->c.p, normal, depth, alpha,
+                       (const double*)g->m1[old].p, (const double*)g->m2[old].p, (const double*)g->hist.p, (const double*)g->len[old].p, pmaps + npx * 3,
+                       pmaps + npx * 6, pmaps + npx * 7, g->m1[nxt].p, g->m2[nxt].p, g->acc.p, g->len[nxt].p, g->xy.p);
+    HIP_TRY_AS(at, hipGetLastError());
+
+    if (int rc = variance_passes_device(at.c_str(), w, h, nullptr, g->vprm, nullptr, normal, depth, alpha, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                        g->m1[nxt].p, nullptr, g->m2[nxt].p, g->len[nxt].p, nullptr, g->var.p, stream)) return rc;
+
+    const double* filter_albedo = g->q.demodulate ? g->ones.p : albedo;
+    double* const fc[2] = {g->fc[0].p, g->fc[1].p};
+    double* const fv[2] = {g->fv[0].p, g->fv[1].p};
+    int fo = 0;
+    if (int rc = atrous_passes_tap_device(w, h, g->acc.p, g->var.p, filter_albedo, normal, depth, alpha, g->q.d.iterations, g->dprm, fc, fv, g->scratch_rgba.p,
+                                          g->q.feedback_iterations, g->q.feedback_iterations ? g->hist.p : nullptr, stream, fo)) return rc;
+
+    hipLaunchKernelGGL(svgf_emit_kernel, dim3((uint32_t(npx) + 255u) / 256u), dim3(256), 0, stream, uint32_t(npx), (const double*)fc[fo], (const double*)g->acc.p,
+                       albedo, (const uint8_t*)g->flags.p, g->out_lin.p, g->out_acc.p, g->rgba.p);
+    HIP_TRY_AS(at, hipGetLastError());
+    HIP_TRY_AS(at, hipEventRecord(g->ev1.get(), stream));
+    HIP_TRY_AS(at, hipStreamSynchronize(stream));
+
+    // the state is the frame's from here on
+    g->cur = nxt;
+    g->has_state = true;
+    g->cam = *cam;
+    if (!out) return RTTNW_OK;
+    const size_t b3 = npx * 3 * sizeof(double), b1 = npx * sizeof(double);
+    const auto copy = [](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+    HIP_TRY_AS(at, copy(out->linear_rgb, g->out_lin.p, b3));
+    HIP_TRY_AS(at, copy(out->rgba8, g->rgba.p, npx * 4));
+    HIP_TRY_AS(at, copy(out->accumulated_rgb, g->out_acc.p, b3));
+    HIP_TRY_AS(at, copy(out->variance_rgb, g->var.p, b3));
+    HIP_TRY_AS(at, copy(out->filtered_variance_rgb, fv[fo], b3));
+    HIP_TRY_AS(at, copy(out->length, g->len[nxt].p, b1));
+    HIP_TRY_AS(at, copy(out->prev_xy, g->xy.p, b1 * 2));
+    HIP_TRY_AS(at, copy(out->moment1_rgb, g->m1[nxt].p, b3));
+    HIP_TRY_AS(at, copy(out->moment2_rgb, g->m2[nxt].p, b3));
+    HIP_TRY_AS(at, copy(out->history_rgb, g->q.feedback_iterations ? g->hist.p : g->m1[nxt].p, b3));
+    HIP_TRY_AS(at, copy(out->raw_rgb, g->raw.p, b3));
+    HIP_TRY_AS(at, copy(out->albedo, albedo, b3));
+    HIP_TRY_AS(at, copy(out->normal, normal, b3));
+    HIP_TRY_AS(at, copy(out->depth, depth, b1));
+    HIP_TRY_AS(at, copy(out->alpha, alpha, b1));
+    if (out->image_ms) {
+        float ms = 0;
+        HIP_TRY_AS(at, hipEventElapsedTime(&ms, g->ev0.get(), g->ev1.get()));
+        *out->image_ms = ms;
+    }
+    return RTTNW_OK;
+}
+
+int svgf_allocate(::rttnw_svgf* g) {
+    const char* const at = "svgf_create: ";
+    const size_t npx = size_t(g->width) * g->height;
+    rttnw_tile_layout L;
+    fill_layout(g->width, g->height, 1, L);
+    HIP_TRY_AS(at, hipGetDevice(&g->device));
+    HIP_TRY_AS(at, g->packed.alloc(size_t(L.pixels_per_rank) * 4 * sizeof(double)));
+    HIP_TRY_AS(at, g->flags.alloc(npx * 3));
+    HIP_TRY_AS(at, g->rgba.alloc(npx * 4));
+    HIP_TRY_AS(at, g->scratch_rgba.alloc(npx * 4));
+    for (DevBuf<double>* b : {&g->raw, &g->c, &g->m1[0], &g->m1[1], &g->m2[0], &g->m2[1], &g->hist, &g->acc, &g->var, &g->ones, &g->fc[0], &g->fc[1], &g->fv[0],
+                              &g->fv[1], &g->out_lin, &g->out_acc})
+        HIP_TRY_AS(at, b->alloc(npx * 3));
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY_AS(at, g->maps[k].alloc(npx * 8));
+        HIP_TRY_AS(at, g->len[k].alloc(npx));
+    }
+    HIP_TRY_AS(at, g->xy.alloc(npx * 2));
+    HIP_TRY_AS(at, create_event(g->ev0));
+    HIP_TRY_AS(at, create_event(g->ev1));
+    hipLaunchKernelGGL(svgf_fill_kernel, dim3(uint32_t((npx * 3 + 255) / 256)), dim3(256), 0, nullptr, npx * 3, 1.0, g->ones.p);
+    HIP_TRY_AS(at, hipGetLastError());
+    if (int rc = variance_admit_lds(at, g->vprm.radius)) return rc;
+    HIP_TRY_AS(at, hipDeviceSynchronize());
+    return RTTNW_OK;
+}
+
+} // namespace
+} // namespace rt
+
+extern "C" {
+
+int rttnw_svgf_create(uint32_t width, uint32_t height, const rttnw_svgf_params* q, rttnw_svgf** out) {
+    const char* const call = "svgf_create";
+    if (!q) return rt::refuse(call, "q is NULL");
+    if (!out) return rt::refuse(call, "out is NULL");
+    *out = nullptr;
+    if (uint64_t(width) * height == 0 || uint64_t(width) * height > (1ull << 28)) return rt::refuse(call, "width * height: empty image (or more than 2^28 pixels)");
+    if (int rc = rt::refuse_params(call, q)) return rc;
+    if (int rc = rt::require_device(call)) return rc;
+    std::unique_ptr<rttnw_svgf> g(new rttnw_svgf());
+    g->width = width;
+    g->height = height;
+    g->q = *q;
+    g->vprm = rt::variance_params(q->v.min_temporal, q->v.radius, q->v.sigma_normal, q->v.sigma_depth);
+    g->dprm = rt::denoise_params(q->d.sigma_luminance, q->d.sigma_normal, q->d.sigma_depth, true);
+    if (int rc = rt::svgf_allocate(g.get())) return rc;
+    *out = g.release();
+    return RTTNW_OK;
+}
+
+void rttnw_svgf_destroy(rttnw_svgf* q) {
+    if (!q) return;
+    rt::DeviceGuard restore;
+    (void)hipSetDevice(q->device);
+    (void)hipDeviceSynchronize();
+    delete q;
+}
+
+int rttnw_svgf_reset(rttnw_svgf* q) {
+    if (!q) return rt::refuse("svgf_reset", "q is NULL");
+    q->has_state = false;
+    return RTTNW_OK;
+}
+
+int rttnw_svgf_push(rttnw_svgf* q, const rttnw_camera_desc* cam, const double* linear_rgb, const double* albedo, const double* normal, const double* depth,
+                    const double* alpha, const rttnw_svgf_out* out) {
+    const char* const call = "svgf_push";
+    // (the handle last: a handle exists only on a machine with a device, and the other refusals need none)
+    if (!cam) return rt::refuse(call, "cam is NULL");
+    if (!linear_rgb) return rt::refuse(call, "linear_rgb is NULL");
+    if (!albedo || !normal || !depth || !alpha) return rt::refuse(call, "NULL argument (albedo, normal, depth or alpha)");
+    if (!q) return rt::refuse(call, "q is NULL");
+    using rt::set_last_error; // (HIP_TRY_AS names it)
+    const std::string at = std::string(call) + ": ";
+    rt::DeviceGuard restore;
+    HIP_TRY_AS(at, hipSetDevice(q->device));
+    const size_t npx = size_t(q->width) * q->height, b3 = npx * 3 * sizeof(double), b1 = npx * sizeof(double);
+    double* maps = q->maps[q->cur ^ 1].p;
+    HIP_TRY_AS(at, hipMemcpy(q->raw.p, linear_rgb, b3, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps, albedo, b3, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps + npx * 3, normal, b3, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps + npx * 6, depth, b1, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps + npx * 7, alpha, b1, hipMemcpyHostToDevice));
+    return rt::svgf_run(call, q, cam, false, RTTNW_F64, out);
+}
+
+int rttnw_svgf_frame(rttnw_svgf* q, rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_svgf_out* out, rttnw_stats* stats) {
+    const char* const call = "svgf_frame";
+    if (!cam) return rt::refuse(call, "cam is NULL");
+    if (!p) return rt::refuse(call, "p is NULL");
+    if (int rc = rt::refuse_host_output_misuse(call, p->reserved0, p)) return rc; // tile_world != 1 among them
+    if (!q) return rt::refuse(call, "q is NULL");
+    if (!s) return rt::refuse(call, "s is NULL");
+    if (p->width != q->width || p->height != q->height) return rt::refuse(call, "p->width and p->height must equal the handle's");
+    if (int rc = rt::validate(s, cam, p)) return rc;
+    if (s->device->device != q->device) return rt::refuse(call, "s: the scene was committed on another device than the handle's");
+    rttnw_params pf = *p;
+    pf.spp = q->q.feature_spp ? q->q.feature_spp : (p->spp < 16u ? p->spp : 16u);
+    rt::DeviceGuard restore;
+    if (int rc = rt::render_tiles_any(s, s->device, cam, p, q->packed.p, nullptr, stats)) return rc;
+    if (int rc = RT_BY_PRECISION(p->precision, render_features_device_t, s, cam, &pf, q->maps[q->cur ^ 1].p, nullptr)) return rc;
+    if (stats) {
+        const uint64_t feature_rays = uint64_t(p->width) * p->height * pf.spp;
+        stats->samples += feature_rays;
+        stats->rays += feature_rays;
+    }
+    return rt::svgf_run(call, q, cam, true, p->precision, out);
+}
+
+} // extern "C"

@@ -78,6 +78,34 @@ __global__ __launch_bounds__(int(VARIANCE_BLOCK_X* VARIANCE_BLOCK_Y)) void varia
 
 } // namespace
 
+// The estimate kernel's dynamic LDS, admitted once: the tile of radius 4 is more than the 64 KiB a kernel has without asking.  Before a caller starts
+// its clock; rttnw_svgf_create calls it for the handle's radius.
+int variance_admit_lds(const char* at, uint32_t radius) {
+    HIP_TRY_AS(at, hipFuncSetAttribute(reinterpret_cast<const void*>(variance_estimate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       int(variance_lds_bytes(radius))));
+    return RTTNW_OK;
+}
+
+// The two kernels on buffers that are already on the device, enqueued on `stream` — nothing else: no allocation, no copy, no wait.  With
+// prm == nullptr stage A is not run: d_out, d_m2 and d_len hold a stage A's outputs already (svgf.hip's accumulate kernel wrote them) and only the
+// estimate is enqueued; d_lin, the prev_* buffers, d_rgba and d_xy are then not used.  The LDS of vprm.radius was admitted by the caller.
+int variance_passes_device(const char* at, uint32_t width, uint32_t height, const TemporalParams* prm, const VarianceParams& vprm, const double* d_lin,
+                           const double* d_normal, const double* d_depth, const double* d_alpha, const double* d_plin, const double* d_pm2,
+                           const double* d_plen, const double* d_pnormal, const double* d_pdepth, const double* d_palpha, double* d_out, uint8_t* d_rgba,
+                           double* d_m2, double* d_len, double* d_xy, double* d_var, hipStream_t stream) {
+    const dim3 block(VARIANCE_BLOCK_X, VARIANCE_BLOCK_Y);
+    const dim3 grid((width + VARIANCE_BLOCK_X - 1) / VARIANCE_BLOCK_X, (height + VARIANCE_BLOCK_Y - 1) / VARIANCE_BLOCK_Y);
+    if (prm) {
+        hipLaunchKernelGGL(variance_accumulate_kernel, grid, block, 0, stream, width, height, *prm, d_lin, d_normal, d_depth, d_alpha, d_plin, d_pm2, d_plen,
+                           d_pnormal, d_pdepth, d_palpha, d_out, d_rgba, d_m2, d_len, d_xy);
+        HIP_TRY_AS(at, hipGetLastError());
+    }
+    hipLaunchKernelGGL(variance_estimate_kernel, grid, block, variance_lds_bytes(vprm.radius), stream, width, height, vprm, d_out, d_m2, d_len, d_normal,
+                       d_depth, d_alpha, d_var);
+    HIP_TRY_AS(at, hipGetLastError());
+    return RTTNW_OK;
+}
+
 int variance_device(uint32_t width, uint32_t height, const TemporalParams& prm, const VarianceParams& vprm, const double* linear_rgb, const double* normal,
                     const double* depth, const double* alpha, const double* prev_linear_rgb, const double* prev_moment2_rgb, const double* prev_length,
                     const double* prev_normal, const double* prev_depth, const double* prev_alpha, double* out_linear_rgb, uint8_t* out_rgba8,
@@ -106,23 +134,15 @@ int variance_device(uint32_t width, uint32_t height, const TemporalParams& prm, 
     HIP_TRY_AS(at, d_xy.alloc(npx * 2));
     HIP_TRY_AS(at, d_var.alloc(npx * 3));
     HIP_TRY_AS(at, d_rgba.alloc(npx * 4));
-    // the tile of radius 4 is more than the 64 KiB a kernel has without asking: admit it before the clock starts
-    const size_t lds_bytes = variance_lds_bytes(vprm.radius);
-    HIP_TRY_AS(at, hipFuncSetAttribute(reinterpret_cast<const void*>(variance_estimate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+    if (int rc = variance_admit_lds(at, vprm.radius)) return rc; // before the clock starts
     Event ev0, ev1;
     HIP_TRY_AS(at, create_event(ev0));
     HIP_TRY_AS(at, create_event(ev1));
 
     const hipStream_t stream = nullptr;
-    const dim3 block(VARIANCE_BLOCK_X, VARIANCE_BLOCK_Y);
-    const dim3 grid((width + VARIANCE_BLOCK_X - 1) / VARIANCE_BLOCK_X, (height + VARIANCE_BLOCK_Y - 1) / VARIANCE_BLOCK_Y);
     HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
-    hipLaunchKernelGGL(variance_accumulate_kernel, grid, block, 0, stream, width, height, prm, d_lin.p, d_normal.p, d_depth.p, d_alpha.p, d_plin.p, d_pm2.p,
-                       d_plen.p, d_pnormal.p, d_pdepth.p, d_palpha.p, d_out.p, d_rgba.p, d_m2.p, d_len.p, d_xy.p);
-    HIP_TRY_AS(at, hipGetLastError());
-    hipLaunchKernelGGL(variance_estimate_kernel, grid, block, lds_bytes, stream, width, height, vprm, d_out.p, d_m2.p, d_len.p, d_normal.p, d_depth.p,
-                       d_alpha.p, d_var.p);
-    HIP_TRY_AS(at, hipGetLastError());
+    if (int rc = variance_passes_device(at, width, height, &prm, vprm, d_lin.p, d_normal.p, d_depth.p, d_alpha.p, d_plin.p, d_pm2.p, d_plen.p, d_pnormal.p,
+                                        d_pdepth.p, d_palpha.p, d_out.p, d_rgba.p, d_m2.p, d_len.p, d_xy.p, d_var.p, stream)) return rc;
     HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
     HIP_TRY_AS(at, hipDeviceSynchronize());
     if (kernel_ms) {

@@ -507,6 +507,121 @@ def render_sequence(scene, cams, params, temporal=True, denoise=False, iteration
     return frames
 
 
+SVGF_ARRAYS = {"linear_rgb": 3, "rgba8": 4, "accumulated_rgb": 3, "variance_rgb": 3, "filtered_variance_rgb": 3, "length": 0, "prev_xy": 2,
+               "moment1_rgb": 3, "moment2_rgb": 3, "history_rgb": 3, "raw_rgb": 3, "albedo": 3, "normal": 3, "depth": 0, "alpha": 0}
+
+
+class SvgfSequence:
+    """An `rttnw_svgf` handle: a sequence's history on the device, and one call per frame — `frame` renders it, `push` takes a frame the caller
+    rendered — that runs accumulate, estimate, filter and feed back without the host between them (include/rttnw_hip.h states the contract).
+    `feedback` j: the colour history is the filter's result after j passes (0: the unfiltered accumulation, `render_sequence`'s); `demodulate`:
+    everything the history holds is colour / albedo.  The other parameters are `temporal_variance`'s and `denoise`'s, a 0 their default.  Each
+    call returns a dict of the outputs named in `want` (default: all of `SVGF_ARRAYS`), "image_ms" and "cam"; `frame` adds "stats".  A context
+    manager: the handle is destroyed on exit."""
+
+    def __init__(self, width, height, feedback=0, demodulate=False, feature_spp=0, iterations=5, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0,
+                 max_history=0, depth_tolerance=0.0, normal_min=0.0, min_temporal=0, radius=0, variance_sigma_normal=0.0, variance_sigma_depth=0.0):
+        who = "SvgfSequence"
+        if int(width) < 1 or int(height) < 1:
+            raise ValueError("%s: width and height must be at least 1, got %r x %r" % (who, width, height))
+        if not 0 <= int(iterations) <= 8:
+            raise ValueError("%s: iterations must be 0 .. 8, got %r" % (who, iterations))
+        if not 0 <= int(feedback) <= int(iterations):
+            raise ValueError("%s: feedback must be 0 .. iterations (%d), got %r" % (who, iterations, feedback))
+        self.width, self.height = int(width), int(height)
+        self.params = abi.Svgf(feedback_iterations=int(feedback), demodulate=1 if demodulate else 0, feature_spp=int(feature_spp), reserved0=0,
+                               t=abi.Temporal(max_history=int(max_history), reserved0=0, depth_tolerance=depth_tolerance, normal_min=normal_min),
+                               v=abi.Variance(min_temporal=int(min_temporal), radius=int(radius), sigma_normal=variance_sigma_normal,
+                                              sigma_depth=variance_sigma_depth, reserved0=0, reserved1=0),
+                               d=_denoise_params(int(iterations), sigma_luminance, sigma_normal, sigma_depth))
+        self._b = library.product()
+        self.handle = C.c_void_p()
+        check(self._b.svgf_create(self.width, self.height, C.byref(self.params), C.byref(self.handle)), self._b, "rttnw_svgf_create")
+
+    def close(self):
+        if self.handle:
+            self._b.svgf_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """Drop the history: the next call is a first frame."""
+        check(self._b.svgf_reset(self.handle), self._b, "rttnw_svgf_reset")
+
+    def _outputs(self, want):
+        """(dict of zeroed arrays, the rttnw_svgf_out over them, the image_ms cell); `want` None: everything, () : nothing (no struct at all)."""
+        names = tuple(SVGF_ARRAYS) if want is None else tuple(want)
+        for name in names:
+            if name not in SVGF_ARRAYS:
+                raise ValueError("SvgfSequence: no output named %r (there are %s)" % (name, ", ".join(SVGF_ARRAYS)))
+        h, w = self.height, self.width
+        arrays = {name: np.zeros((h, w, SVGF_ARRAYS[name]) if SVGF_ARRAYS[name] else (h, w), dtype=np.uint8 if name == "rgba8" else np.float64)
+                  for name in names}
+        ms = C.c_double(0.0)
+        out = abi.SvgfOut(image_ms=C.addressof(ms), **{name: a.ctypes.data for name, a in arrays.items()})
+        return arrays, out, ms
+
+    def push(self, linear, features, cam, want=None, no_outputs=False):
+        """`rttnw_svgf_push`: a frame the caller rendered (`linear` HxWx3, `features` as `render_features` returns them).  `no_outputs`: the
+        call is made with a NULL `out` and only advances the state."""
+        lin = np.ascontiguousarray(linear, dtype=np.float64)
+        if lin.shape != (self.height, self.width, 3):
+            raise ValueError("SvgfSequence.push: the frame is %dx%dx3, got %s" % (self.height, self.width, lin.shape))
+        f = _feature_arrays(features, self.height, self.width)
+        arrays, out, ms = self._outputs(() if no_outputs else want)
+        rc = self._b.svgf_push(self.handle, C.byref(cam), lin.ctypes.data, f["albedo"].ctypes.data, f["normal"].ctypes.data, f["depth"].ctypes.data,
+                               f["alpha"].ctypes.data, None if no_outputs else C.byref(out))
+        check(rc, self._b, "rttnw_svgf_push")
+        arrays["image_ms"], arrays["cam"] = ms.value, cam
+        return arrays
+
+    def frame(self, scene, cam, params, want=None, no_outputs=False):
+        """`rttnw_svgf_frame`: the frame rendered by the call itself, `rttnw_render`'s trace of `params` and the feature pass beside it."""
+        arrays, out, ms = self._outputs(() if no_outputs else want)
+        st = Stats()
+        rc = self._b.svgf_frame(self.handle, scene.handle, C.byref(cam), C.byref(params), None if no_outputs else C.byref(out), C.byref(st))
+        check(rc, self._b, "rttnw_svgf_frame")
+        arrays["image_ms"], arrays["cam"], arrays["stats"] = ms.value, cam, st
+        return arrays
+
+
+def render_sequence_device(scene, cams, params, feedback=0, demodulate=False, iterations=5, max_history=0, depth_tolerance=0.0, normal_min=0.0,
+                           on_frame=None, want=("linear_rgb", "rgba8", "raw_rgb", "length", "accumulated_rgb", "moment2_rgb", "variance_rgb", "prev_xy",
+                                                "albedo", "normal", "depth", "alpha")):
+    """`render_sequence(..., variance=True, denoise=True)` on the device: one `SvgfSequence`, one `frame` call per camera, frame k at
+    `sample_begin = params.sample_begin + k * params.spp`.  With `feedback` 0 and without `demodulate` the images are that function's, bit for
+    bit.  Returns the same list of dicts — "linear", "rgba8", "raw", "length", "accumulated" ("linear", "rgba8" absent, "moment2", "variance",
+    "length", "prev_xy"), "features", "cam", "stats" — and "image_ms", the device time behind the trace and the feature pass.  An entry of a
+    frame is None where `want` leaves its output out."""
+    frames = []
+    with SvgfSequence(params.width, params.height, feedback=feedback, demodulate=demodulate, iterations=iterations, max_history=max_history,
+                      depth_tolerance=depth_tolerance, normal_min=normal_min) as seq:
+        for k, cam in enumerate(cams):
+            p = copy.copy(params)
+            p.sample_begin = params.sample_begin + k * params.spp
+            got = seq.frame(scene, cam, p, want=want)
+            features = {name: got.get(name) for name in ("albedo", "normal", "depth", "alpha")}
+            accumulated = {"linear": got.get("accumulated_rgb"), "moment2": got.get("moment2_rgb"), "variance": got.get("variance_rgb"),
+                           "length": got.get("length"), "prev_xy": got.get("prev_xy"), "features": features, "cam": cam}
+            frame = {"linear": got.get("linear_rgb"), "rgba8": got.get("rgba8"), "raw": got.get("raw_rgb"), "length": got.get("length"),
+                     "accumulated": accumulated, "features": features, "cam": cam, "stats": got["stats"], "image_ms": got["image_ms"]}
+            frames.append(frame)
+            if on_frame is not None:
+                on_frame(k, frame)
+    return frames
+
+
 def lattice_mask(width, height, level):
     """The lattice of a preview as a mask (HxW u8): 1 where x % 2^level == 0 and y % 2^level == 0, row 0 at the top."""
     if not 0 <= int(level) <= 6:
