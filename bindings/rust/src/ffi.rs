@@ -158,6 +158,18 @@ pub struct rttnw_variance_params {
     pub reserved1: u32,
 }
 
+/// What `rttnw_temporal_clamp` takes beside the two blocks of `rttnw_temporal_variance`, and `rttnw_svgf_set_clamp` alone (include/rttnw_hip.h states
+/// the contract); a 0 is the library default (a window of radius 3, one standard deviation, `rttnw_denoise`'s sigmas); a `gamma` of +inf never clips.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rttnw_clamp_params {
+    pub radius: u32,
+    pub reserved0: u32,
+    pub gamma: f64,
+    pub sigma_normal: f64,
+    pub sigma_depth: f64,
+}
+
 /// Opaque handle of the SVGF loop (`rttnw_svgf_create`): a sequence's history on the device.
 #[repr(C)]
 pub struct rttnw_svgf {
@@ -323,6 +335,9 @@ extern "C" {
     pub fn rttnw_denoise_nlm(width: u32, height: u32, half_a: *const f64, half_b: *const f64, var_a: *const f64, var_b: *const f64, d: *const rttnw_nlm_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_half_a: *mut f64, out_half_b: *mut f64, out_error_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_denoise_select(width: u32, height: u32, half_a: *const f64, half_b: *const f64, var_a: *const f64, var_b: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, dn: *const rttnw_denoise_params, nl: *const rttnw_nlm_params, sel: *const rttnw_select_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_blend: *mut f64, out_feature_rgb: *mut f64, out_nlm_rgb: *mut f64, out_error_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_temporal_accumulate(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, linear_rgb: *const f64, variance_rgb: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, prev_linear_rgb: *const f64, prev_variance_rgb: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, out_length: *mut f64, out_prev_xy: *mut f64, kernel_ms: *mut f64) -> c_int;
+    pub fn rttnw_temporal_clamp(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, linear_rgb: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, prev_linear_rgb: *const f64, prev_moment2_rgb: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, v: *const rttnw_variance_params, k: *const rttnw_clamp_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_moment2_rgb: *mut f64, out_length: *mut f64, out_prev_xy: *mut f64, out_variance_rgb: *mut f64, out_mean_rgb: *mut f64, out_sd_rgb: *mut f64, out_clipped: *mut u8, kernel_ms: *mut f64) -> c_int;
+    pub fn rttnw_svgf_set_clamp(q: *mut rttnw_svgf, k: *const rttnw_clamp_params) -> c_int;
+    pub fn rttnw_svgf_clipped(q: *mut rttnw_svgf, out_clipped: *mut u8) -> c_int;
     pub fn rttnw_svgf_create(width: u32, height: u32, q: *const rttnw_svgf_params, out: *mut *mut rttnw_svgf) -> c_int;
     pub fn rttnw_svgf_destroy(q: *mut rttnw_svgf);
     pub fn rttnw_svgf_reset(q: *mut rttnw_svgf) -> c_int;

@@ -44,8 +44,8 @@ extern "C" {
                              *  rttnw_render_adaptive_resume with rttnw_adaptive_state_doubles, rttnw_render_adaptive_region,
                              *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select,
                              *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised, rttnw_denoise_nlm,
-                             *  rttnw_denoise_select, rttnw_temporal_accumulate, rttnw_temporal_variance and the rttnw_svgf_create family came later,
-                             *  without a version bump: a caller detects each by its symbol) */
+                             *  rttnw_denoise_select, rttnw_temporal_accumulate, rttnw_temporal_variance, the rttnw_svgf_create family, rttnw_temporal_clamp,
+                             *  rttnw_svgf_set_clamp and rttnw_svgf_clipped came later, without a version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -681,6 +681,70 @@ int rttnw_svgf_push(rttnw_svgf* q, const rttnw_camera_desc* cam, const double* l
                     const double* depth, const double* alpha, const rttnw_svgf_out* out);
 int rttnw_svgf_frame(rttnw_svgf* q, rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_svgf_out* out,
                      rttnw_stats* stats);
+
+/* Clipping the reprojected history to the frame: rttnw_temporal_variance with neighbourhood variance clipping (Karis 2014; Salvi 2016) in front of
+ * its blend.  The three blocks above leave colour clamping of the history out of their scope; clipping now lives here.  A history reprojected by
+ * the first hit ghosts on glass, on mirrors and on anything that moves, depth and normal accept it there, and a ghost that lasts has a small
+ * temporal variance: nothing above compares the history's colour with the frame it is blended into.  This call does: it takes the mean and the
+ * standard deviation of THIS frame's colour over a small window and clips the reprojected history into mean +- gamma * sd before the blend.
+ * Calling convention as rttnw_temporal_variance: every argument of that entry point in the same order, k after v, three optional outputs before
+ * kernel_ms; host arrays in and out (row-major, top row first), blocking, on the current device, no scene handle; no CPU fallback:
+ * RTTNW_ERR_HIP without a device.  Everything is double.
+ *
+ * Stage S, the frame's statistics.  pos(x) = x < 0 ? 0 : x.  For a pixel with alpha != 0: the window of rttnw_temporal_variance's spatial
+ *   estimate — dy = -radius .. radius (outer), dx = -radius .. radius (inner), the centre among the taps; taps outside the image, or whose
+ *   alpha == 0, are dropped; a tap weighs w = w_n * w_z in that stage's expressions — with radius and sigmas from k, over the planes m1' = cur (this
+ *   frame's colour) and m2' = cur * cur (rounded once).  Sw = sum w;  Sw > 0: mu = (sum w * m1') / Sw and q = (sum w * m2') / Sw;  otherwise
+ *   mu = cur and q = cur * cur.  sd = sqrt(pos(q - mu * mu)).  A pixel with alpha == 0 has mu = cur, sd = 0.  lo = mu - gamma * sd;
+ *   hi = mu + gamma * sd: one product and one sum each, not fused.  out_mean_rgb = mu and out_sd_rgb = sd, for every pixel.
+ * Stage A', accumulate.  rttnw_temporal_variance's stage A in its expressions and its order up to the history's means h1 = (sum wt * m1') / W and
+ *   h2 = (sum wt * m2') / W.  Then per channel h1c = h1 < lo ? lo : (h1 > hi ? hi : h1).  Every comparison with a NaN is false, so a NaN history,
+ *   NaN bounds, or the inf * 0 bounds of gamma = +inf with sd = 0 clip nothing.  Bit ch of out_clipped is set exactly where one of the two
+ *   branches was taken.  On a clipped channel h2c = (h2 - h1 * h1) + h1c * h1c: the history keeps its spread about the moved mean; on an unclipped
+ *   channel h2c = h2 — a branch, not arithmetic.  The blend is stage A's with h1c and h2c in place of h1 and h2: out = (1 - a) * h1c + a * cur,
+ *   out_m2 = (1 - a) * h2c + a * s.  out_length, out_prev_xy and every pass-through case (no history, alpha == 0, no place in the previous frame,
+ *   W > 0 false) are stage A's, with out_clipped = 0.
+ * Stage B, estimate.  rttnw_temporal_variance's, unchanged, on stage A''s outputs; its window takes radius and sigmas from v.
+ * Consequences.  Where no channel of a pixel is clipped, every shared output equals rttnw_temporal_variance's bits there (out_variance_rgb on the
+ *   spatial branch: where no pixel of its window was clipped).  With gamma = +inf every shared output equals rttnw_temporal_variance's bits and
+ *   out_clipped is all 0.
+ * Arithmetic.  + - * /, sqrt, floor, abs and comparisons only; every sum starts from 0.0 and adds in the order stated; no product is fused into a
+ *   sum; non-finite values are not special-cased.  So the device code, a host build of the same header (rttnw_amd/csrc/clamp.hpp) and a
+ *   restatement in numpy give the same bits.
+ * Outputs, each optional: rttnw_temporal_variance's six; out_mean_rgb w*h*3; out_sd_rgb w*h*3; out_clipped w*h bytes; kernel_ms: device time of
+ *   both kernels (the fused statistics-and-accumulate kernel, the estimate).
+ * Refusals, before the device is touched, each message naming temporal_clamp and the argument, RTTNW_ERR_INVALID: everything
+ *   rttnw_temporal_variance refuses, in its order; then a NULL k, k->radius > 4, k->reserved0 != 0, a negative or NaN gamma, a negative or NaN
+ *   sigma.
+ * The handle.  rttnw_svgf_set_clamp switches clipping on for an rttnw_svgf handle (NULL: off, the default); it takes effect from the next frame
+ *   call, keeps the history, refuses what rttnw_temporal_clamp refuses for k (the handle is checked last), and allocates the one byte map it needs:
+ *   frame calls still allocate nothing (the kernel's tile fits the LDS a kernel has without asking).  With a clamp set two steps of the handle's
+ *   contract change, everything else stays:
+ *   1. TV = rttnw_temporal_clamp(...) over the same arguments, k beside them.
+ *   2. With feedback and a state, A = rttnw_temporal_clamp(cam, cam', c, F, prev_linear_rgb = H, prev_moment2_rgb = M2, prev_length = L, the state's
+ *      normal, depth and alpha, t, v, k).out_linear_rgb.  The bounds depend only on c, F and k, so H is clipped to the same interval as M1.
+ *   rttnw_svgf_clipped copies out the last frame call's map, w*h bytes: bits 0 - 2 are TV's out_clipped, bits 4 - 6 the H call's (0 without
+ *   feedback); before any frame call, or after a call without a clamp, the map is all 0.  With `demodulate` the statistics are those of c, so a
+ *   texture does not widen the interval.  With gamma = +inf every field of rttnw_svgf_out equals the unclamped handle's bits.
+ * Out of scope: clipping in another colour space (YCoCg); cutting the history length where a pixel was clipped; a "fast history" as the source of
+ *   the bounds; a node-wide form; the native rttnw program. */
+struct rttnw_clamp_params {
+    uint32_t radius;     /* the window is (2 radius + 1)^2; 0 = default 3; 1 .. 4 */
+    uint32_t reserved0;  /* must be 0 */
+    double gamma;        /* half-width of the admitted interval in standard deviations; 0 = default 1.0; +inf = never clip;
+                            negative or NaN refused */
+    double sigma_normal, sigma_depth; /* as rttnw_variance_params: 0 = rttnw_denoise's defaults */
+};
+typedef struct rttnw_clamp_params rttnw_clamp_params;
+int rttnw_temporal_clamp(uint32_t width, uint32_t height, const rttnw_camera_desc* cam, const rttnw_camera_desc* prev_cam,
+                         const double* linear_rgb, const double* normal, const double* depth, const double* alpha,
+                         const double* prev_linear_rgb, const double* prev_moment2_rgb, const double* prev_length,
+                         const double* prev_normal, const double* prev_depth, const double* prev_alpha,
+                         const rttnw_temporal_params* t, const rttnw_variance_params* v, const rttnw_clamp_params* k,
+                         double* out_linear_rgb, uint8_t* out_rgba8, double* out_moment2_rgb, double* out_length, double* out_prev_xy,
+                         double* out_variance_rgb, double* out_mean_rgb, double* out_sd_rgb, uint8_t* out_clipped, double* kernel_ms);
+int rttnw_svgf_set_clamp(rttnw_svgf* q, const rttnw_clamp_params* k);   /* NULL: off, the default */
+int rttnw_svgf_clipped(rttnw_svgf* q, uint8_t* out_clipped);            /* w*h: the last frame call's map */
 
 /* `render()` on the GPUs of ONE NODE, in one call from one host thread ("library owns its HIP
  * streams / RCCL comms"): the framebuffer's 8x8 tiles are interleaved over `ngpu` ranks, rank r traces its tiles on

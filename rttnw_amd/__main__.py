@@ -59,6 +59,9 @@ guided by normal and depth elsewhere); with --denoise that variance is rttnw_den
 the frames of --orbit K --temporal-variance --denoise, bit for bit, without the copies between the stages.  --feedback J feeds the filter's
 result after J passes (0 .. --denoise-iterations; SVGF: 1) back into the colour history; --demodulate accumulates, estimates and filters
 colour / albedo, so textures neither blur in the reprojection nor read as variance.  --feedback and --demodulate need --svgf.
+--clamp GAMMA (with --temporal-variance or --svgf) clips the reprojected history to each frame before the blend (rttnw_temporal_clamp): the mean
+and the standard deviation of the frame's colour over a 7x7 window guided by normal and depth admit the history within GAMMA deviations (0: the
+default, 1.0) and move it to the nearer bound outside — ghosts of reflections and refractions go, at the price of some noise coming back.
 """
 import argparse
 import sys
@@ -130,6 +133,10 @@ def refusal(args, refine, devices, window):
         return "--svgf needs --orbit: it runs the accumulate, estimate, filter loop over the frames of a sequence"
     if (args.feedback or args.demodulate) and not args.svgf:
         return "--feedback and --demodulate need --svgf: only the loop on the device has them"
+    if args.clamp is not None and not (args.temporal_variance or args.svgf):
+        return "--clamp needs --temporal-variance or --svgf: it clips the history those accumulate"
+    if args.clamp is not None and not args.clamp >= 0.0:
+        return "--clamp must be at least 0 standard deviations (0: the default, 1.0)"
     if args.temporal_variance and not on["--orbit"]:
         return "--temporal-variance needs --orbit: it estimates the variance from the accumulated frames of a sequence"
     if args.temporal and not on["--orbit"]:
@@ -234,6 +241,8 @@ def main(argv=None):
     ap.add_argument("--feedback", type=int, default=0, metavar="J", help="svgf: feed the filter's result after J passes back into the colour history "
                     "(0 .. --denoise-iterations; default 0: the unfiltered accumulation)")
     ap.add_argument("--demodulate", action="store_true", help="svgf: accumulate, estimate and filter colour / albedo")
+    ap.add_argument("--clamp", type=float, default=None, metavar="GAMMA", help="temporal-variance, svgf: clip the reprojected history into the frame's "
+                    "neighbourhood mean +- GAMMA standard deviations before the blend (rttnw_temporal_clamp; 0: the default, 1.0)")
     ap.add_argument("--guided", action="store_true", help="adaptive sampling: stop pixels on the noise of the denoised image "
                     "(rttnw_render_adaptive_denoised); writes the denoised image")
     ap.add_argument("--preview", type=int, default=None, metavar="L", help="adaptive sampling: trace 1 pixel in 4^L (x %% 2^L == 0 and y %% 2^L == 0, "
@@ -310,13 +319,14 @@ def main(argv=None):
 
         if args.svgf:
             frames = render.render_sequence_device(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, feedback=args.feedback,
-                                                   demodulate=args.demodulate, iterations=args.denoise_iterations, on_frame=write)
+                                                   demodulate=args.demodulate, iterations=args.denoise_iterations, on_frame=write, clamp=args.clamp)
             args.temporal = args.temporal_variance = True
         else:
             frames = render.render_sequence(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, temporal=args.temporal, denoise=args.denoise,
-                                            iterations=args.denoise_iterations, on_frame=write, variance=args.temporal_variance)
-        print("%.3fs (%d frames of %d spp, %g degrees apart: trace kernels %.1f ms; written to %s)"
-              % (time.time() - t0, args.orbit, p.spp, args.orbit_step, trace_ms[0], os.path.join(where, "frame_000.png ...")))
+                                            iterations=args.denoise_iterations, on_frame=write, variance=args.temporal_variance, clamp=args.clamp)
+        clamped = "" if args.clamp is None else ", the history clipped at gamma %g" % (args.clamp or 1.0)
+        print("%.3fs (%d frames of %d spp, %g degrees apart%s: trace kernels %.1f ms; written to %s)"
+              % (time.time() - t0, args.orbit, p.spp, args.orbit_step, clamped, trace_ms[0], os.path.join(where, "frame_000.png ...")))
         if args.temporal:
             length = frames[-1]["length"]
             print("temporal: the last frame's history counts %.2f frames on average, %.1f %% of its pixels were reset"

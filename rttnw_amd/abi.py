@@ -84,6 +84,12 @@ class Variance(C.Structure):
                 ("reserved0", C.c_uint32), ("reserved1", C.c_uint32)]
 
 
+class Clamp(C.Structure):
+    """`rttnw_clamp_params` — what `rttnw_temporal_clamp` takes beside the two blocks of `rttnw_temporal_variance`, and `rttnw_svgf_set_clamp` alone
+    (a 0: the library default; a `gamma` of +inf never clips)."""
+    _fields_ = [("radius", C.c_uint32), ("reserved0", C.c_uint32), ("gamma", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
+
+
 class Svgf(C.Structure):
     """`rttnw_svgf_params` — the settings of an `rttnw_svgf` handle: the loop's own, then the three stages' blocks (a 0: that stage's default)."""
     _fields_ = [("feedback_iterations", C.c_uint32), ("demodulate", C.c_uint32), ("feature_spp", C.c_uint32), ("reserved0", C.c_uint32),
@@ -198,6 +204,10 @@ PRODUCT_FUNCS = [
     ("svgf_reset", C.c_int, [C.c_void_p]),
     ("svgf_push", C.c_int, [C.c_void_p, C.POINTER(CameraDesc)] + [C.c_void_p] * 5 + [C.POINTER(SvgfOut)]),
     ("svgf_frame", C.c_int, [C.c_void_p, scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(SvgfOut), C.POINTER(Stats)]),
+    ("temporal_clamp", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(CameraDesc), C.POINTER(CameraDesc)] + [C.c_void_p] * 10 +
+                                [C.POINTER(Temporal), C.POINTER(Variance), C.POINTER(Clamp)] + [C.c_void_p] * 9 + [C.POINTER(C.c_double)]),
+    ("svgf_set_clamp", C.c_int, [C.c_void_p, C.POINTER(Clamp)]),
+    ("svgf_clipped", C.c_int, [C.c_void_p, C.c_void_p]),
     ("render_preview", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Preview), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("budget_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint64,

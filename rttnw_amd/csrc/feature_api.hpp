@@ -10,6 +10,7 @@
 #include "select.hpp"
 #include "temporal.hpp"
 #include "variance.hpp"
+#include "clamp.hpp"
 
 namespace rt {
 
@@ -75,6 +76,26 @@ int variance_passes_device(const char* at, uint32_t width, uint32_t height, cons
                            const double* d_normal, const double* d_depth, const double* d_alpha, const double* d_plin, const double* d_pm2,
                            const double* d_plen, const double* d_pnormal, const double* d_pdepth, const double* d_palpha, double* d_out, uint8_t* d_rgba,
                            double* d_m2, double* d_len, double* d_xy, double* d_var, hipStream_t stream);
+
+// rttnw_temporal_clamp's device half (clamp.hip): host arrays in, host arrays out (each optional), blocking, on the current device: the fused
+// statistics-and-accumulate kernel of clamp.hpp, then variance.hip's estimate as it is.  Arguments were checked by the caller.
+int clamp_device(uint32_t width, uint32_t height, const TemporalParams& prm, const VarianceParams& vprm, const ClampParams& kprm, const double* linear_rgb,
+                 const double* normal, const double* depth, const double* alpha, const double* prev_linear_rgb, const double* prev_moment2_rgb,
+                 const double* prev_length, const double* prev_normal, const double* prev_depth, const double* prev_alpha, double* out_linear_rgb,
+                 uint8_t* out_rgba8, double* out_moment2_rgb, double* out_length, double* out_prev_xy, double* out_variance_rgb, double* out_mean_rgb,
+                 double* out_sd_rgb, uint8_t* out_clipped, double* kernel_ms);
+// ... and its kernel alone, enqueued on `stream` over buffers that are already on the device: nothing allocated, nothing copied, no wait; its tile
+// needs no admission.  With `feedback` the fed-back colour history d_phist rides on the same taps, is clipped into the same interval and blended into
+// d_acc (rttnw_svgf_push's step 2); d_clipped (w*h bytes) takes M1's channels in bits 0 - 2 and H's in bits 4 - 6.  d_phist, d_rgba, d_acc, d_mean
+// and d_sd may be nullptr.
+int clamp_accumulate_device(const char* at, uint32_t width, uint32_t height, const TemporalParams& prm, const ClampParams& kprm, bool feedback,
+                            const double* d_lin, const double* d_normal, const double* d_depth, const double* d_alpha, const double* d_pm1, const double* d_pm2,
+                            const double* d_phist, const double* d_plen, const double* d_pnormal, const double* d_pdepth, const double* d_palpha, double* d_m1,
+                            uint8_t* d_rgba, double* d_m2, double* d_acc, double* d_len, double* d_xy, double* d_mean, double* d_sd, uint8_t* d_clipped,
+                            hipStream_t stream);
+// What rttnw_temporal_clamp and rttnw_svgf_set_clamp refuse for a rttnw_clamp_params (feature_api.cpp): 0, or RTTNW_ERR_INVALID behind a message
+// "<call>: ..." that names the field
+int clamp_refuse_params(const char* call, const rttnw_clamp_params* k);
 
 // rttnw_denoise's passes with a tap of the pass loop (denoise.hip): atrous_passes_device without flags, and d_tap (w*h*3) receives the linear image
 // the same call would return with `tap_after` iterations, 1 <= tap_after <= iterations.  rttnw_svgf_push's feedback.

@@ -1,4 +1,4 @@
-// svgf.hip — rttnw_svgf_create / _destroy / _reset / _push / _frame (include/rttnw_hip.h): the SVGF loop over a history that stays on the device,
+// svgf.hip — rttnw_svgf_create / _destroy / _reset / _set_clamp / _clipped / _push / _frame (include/rttnw_hip.h): the SVGF loop over a history that stays on the device,
 // around the arithmetic of svgf.hpp, double throughout.  The handle owns every buffer from rttnw_svgf_create on; a frame call enqueues, on one
 // stream and without allocating,
 //   svgf_ingest_kernel      one thread per pixel, blocks of 32 x 8: the frame's colour — the trace's packed tiles (reals of the render's precision,
@@ -7,6 +7,7 @@
 //   svgf_accumulate_kernel  one thread per pixel, blocks of 64 x 4 like variance_accumulate_kernel: the reprojection and the four taps once,
 //                           M1, M2 and — with feedback — the colour over H on them; plain global loads, no LDS
 //   variance_estimate_kernel (variance.hip) and the à-trous passes (denoise.hip) as they are, the feedback a tap of the pass loop
+//   (with rttnw_svgf_set_clamp: clamp.hip's clamp_accumulate_kernel in svgf_accumulate_kernel's place, M1 and H clipped to the frame's interval)
 //   svgf_emit_kernel        one thread per pixel: the result and the accumulation multiplied back, and the RGBA8
 // then waits once and copies out what the caller asked for.  No atomics.
 #include "feature_api.hpp"
@@ -25,6 +26,10 @@ struct rttnw_svgf {
     rt::DevBuf<uint8_t> packed, flags, rgba, scratch_rgba;
     rt::DevBuf<double> raw, c, maps[2], m1[2], m2[2], len[2], hist, acc, xy, var, ones, fc[2], fv[2], out_lin, out_acc;
     rt::Event ev0, ev1;
+    // rttnw_svgf_set_clamp: off by default.  `clipped` is allocated by the first set call; clipped_live: the last frame call ran with a clamp and wrote it
+    bool clamp = false, clipped_live = false;
+    rt::ClampParams kprm = {};
+    rt::DevBuf<uint8_t> clipped;
 };
 
 namespace rt {
@@ -154,11 +159,18 @@ int svgf_run(const char* call, ::rttnw_svgf* g, const rttnw_camera_desc* cam, bo
                            alpha, g->raw.p, g->c.p, g->flags.p);
     HIP_TRY_AS(at, hipGetLastError());
 
-    const dim3 ablock(SVGF_BLOCK_X, SVGF_BLOCK_Y), agrid((w + SVGF_BLOCK_X - 1) / SVGF_BLOCK_X, (h + SVGF_BLOCK_Y - 1) / SVGF_BLOCK_Y);
-    hipLaunchKernelGGL(svgf_accumulate_kernel, agrid, ablock, 0, stream, w, h, prm, feedback ? 1u : 0u, (const double*)g->c.p, normal, depth, alpha,
-                       (const double*)g->m1[old].p, (const double*)g->m2[old].p, (const double*)g->hist.p, (const double*)g->len[old].p, pmaps + npx * 3,
-                       pmaps + npx * 6, pmaps + npx * 7, g->m1[nxt].p, g->m2[nxt].p, g->acc.p, g->len[nxt].p, g->xy.p);
-    HIP_TRY_AS(at, hipGetLastError());
+    if (g->clamp) { // steps 1 and 2 through rttnw_temporal_clamp's kernel (clamp.hip): M1 and H clipped into the frame's interval on the same taps
+        if (int rc = clamp_accumulate_device(at.c_str(), w, h, prm, g->kprm, feedback, g->c.p, normal, depth, alpha, g->m1[old].p, g->m2[old].p, g->hist.p,
+                                             g->len[old].p, pmaps + npx * 3, pmaps + npx * 6, pmaps + npx * 7, g->m1[nxt].p, nullptr, g->m2[nxt].p, g->acc.p,
+                                             g->len[nxt].p, g->xy.p, nullptr, nullptr, g->clipped.p, stream)) return rc;
+    } else {
+        const dim3 ablock(SVGF_BLOCK_X, SVGF_BLOCK_Y), agrid((w + SVGF_BLOCK_X - 1) / SVGF_BLOCK_X, (h + SVGF_BLOCK_Y - 1) / SVGF_BLOCK_Y);
+        hipLaunchKernelGGL(svgf_accumulate_kernel, agrid, ablock, 0, stream, w, h, prm, feedback ? 1u : 0u, (const double*)g->c.p, normal, depth, alpha,
+                           (const double*)g->m1[old].p, (const double*)g->m2[old].p, (const double*)g->hist.p, (const double*)g->len[old].p, pmaps + npx * 3,
+                           pmaps + npx * 6, pmaps + npx * 7, g->m1[nxt].p, g->m2[nxt].p, g->acc.p, g->len[nxt].p, g->xy.p);
+        HIP_TRY_AS(at, hipGetLastError());
+    }
+    g->clipped_live = g->clamp;
 
     if (int rc = variance_passes_device(at.c_str(), w, h, nullptr, g->vprm, nullptr, normal, depth, alpha, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                         g->m1[nxt].p, nullptr, g->m2[nxt].p, g->len[nxt].p, nullptr, g->var.p, stream)) return rc;
@@ -268,6 +280,44 @@ void rttnw_svgf_destroy(rttnw_svgf* q) {
 int rttnw_svgf_reset(rttnw_svgf* q) {
     if (!q) return rt::refuse("svgf_reset", "q is NULL");
     q->has_state = false;
+    return RTTNW_OK;
+}
+
+int rttnw_svgf_set_clamp(rttnw_svgf* q, const rttnw_clamp_params* k) {
+    const char* const call = "svgf_set_clamp";
+    if (k)
+        if (int rc = rt::clamp_refuse_params(call, k)) return rc;
+    if (!q) return rt::refuse(call, "q is NULL");
+    if (!k) {
+        q->clamp = false;
+        return RTTNW_OK;
+    }
+    if (!q->clipped.p) { // the one byte map, once: frame calls still allocate nothing
+        using rt::set_last_error;
+        const std::string at = std::string(call) + ": ";
+        rt::DeviceGuard restore;
+        HIP_TRY_AS(at, hipSetDevice(q->device));
+        HIP_TRY_AS(at, q->clipped.alloc(size_t(q->width) * q->height));
+    }
+    q->kprm = rt::clamp_params(k->radius, k->gamma, k->sigma_normal, k->sigma_depth);
+    q->clamp = true;
+    return RTTNW_OK;
+}
+
+int rttnw_svgf_clipped(rttnw_svgf* q, uint8_t* out_clipped) {
+    const char* const call = "svgf_clipped";
+    if (!out_clipped) return rt::refuse(call, "out_clipped is NULL");
+    if (!q) return rt::refuse(call, "q is NULL");
+    const size_t npx = size_t(q->width) * q->height;
+    if (!q->clipped_live) { // before any frame call, or after one without a clamp
+        std::memset(out_clipped, 0, npx);
+        return RTTNW_OK;
+    }
+    using rt::set_last_error;
+    const std::string at = std::string(call) + ": ";
+    rt::DeviceGuard restore;
+    HIP_TRY_AS(at, hipSetDevice(q->device));
+    HIP_TRY_AS(at, hipMemcpy(out_clipped, q->clipped.p, npx, hipMemcpyDeviceToHost));
     return RTTNW_OK;
 }
 

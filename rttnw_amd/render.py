@@ -5,6 +5,7 @@ all tracing happens in the hand-written HIP kernels behind `rttnw_render_tiles_d
 """
 import copy
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -449,6 +450,72 @@ def temporal_variance(linear, features, cam, history=None, min_temporal=0, radiu
     return out
 
 
+CLAMP_OUTPUTS = VARIANCE_OUTPUTS + ("mean", "sd", "clipped")
+
+
+def _clamp_params(who, gamma, clamp_radius, clamp_sigma_normal, clamp_sigma_depth):
+    """`rttnw_clamp_params` behind its ranges."""
+    if not gamma >= 0.0:
+        raise ValueError("%s: gamma must be at least 0 (0: the default, 1.0; inf: never clip), got %r" % (who, gamma))
+    if not 0 <= int(clamp_radius) <= 4:
+        raise ValueError("%s: clamp_radius must be 0 .. 4 (0: the default, 3), got %r" % (who, clamp_radius))
+    if not clamp_sigma_normal >= 0.0 or not clamp_sigma_depth >= 0.0:
+        raise ValueError("%s: clamp_sigma_normal and clamp_sigma_depth must be at least 0 (0: the defaults, 64 and 0.1), got %r, %r"
+                         % (who, clamp_sigma_normal, clamp_sigma_depth))
+    return abi.Clamp(radius=int(clamp_radius), reserved0=0, gamma=float(gamma), sigma_normal=clamp_sigma_normal, sigma_depth=clamp_sigma_depth)
+
+
+def temporal_clamp(linear, features, cam, history=None, gamma=0.0, clamp_radius=0, clamp_sigma_normal=0.0, clamp_sigma_depth=0.0, min_temporal=0,
+                   radius=0, sigma_normal=0.0, sigma_depth=0.0, max_history=0, depth_tolerance=0.0, normal_min=0.0, want_ms=False, want_statistics=True):
+    """`rttnw_temporal_clamp`: `temporal_variance` with the reprojected history clipped to the frame in front of the blend — the mean and the
+    standard deviation of THIS frame's colour over a (2 clamp_radius + 1)^2 window, weighted by normal and depth as the variance estimate's
+    window is (`clamp_sigma_normal`, `clamp_sigma_depth`), admit the history inside mean +- `gamma` deviations and move it to the nearer bound
+    outside.  A parameter of 0 is the library default (gamma 1, radius 3, the filter's sigmas); a gamma of inf never clips.  The other keywords
+    are `temporal_variance`'s.  Returns that function's dict with "mean" and "sd" HxWx3 (the window's statistics) and "clipped" HxW u8 (bit ch: the
+    channel was clipped), usable as the next call's history.  Without `want_statistics` "mean" and "sd" are not asked for (None): the kernel then
+    takes the statistics only where a history is blended, as the `SvgfSequence` handle runs it."""
+    who = "temporal_clamp"
+    lin = _temporal_frame(who, linear, max_history, depth_tolerance, normal_min)
+    h, w = lin.shape[:2]
+    if int(min_temporal) == 1 or not 0 <= int(min_temporal) <= 65535:
+        raise ValueError("%s: min_temporal must be 0 (the default, 4) or 2 .. 65535, got %r" % (who, min_temporal))
+    if not 0 <= int(radius) <= 4:
+        raise ValueError("%s: radius must be 0 .. 4 (0: the default, 3), got %r" % (who, radius))
+    if not sigma_normal >= 0.0 or not sigma_depth >= 0.0:
+        raise ValueError("%s: sigma_normal and sigma_depth must be at least 0 (0: the defaults, 64 and 0.1), got %r, %r" % (who, sigma_normal, sigma_depth))
+    k = _clamp_params(who, gamma, clamp_radius, clamp_sigma_normal, clamp_sigma_depth)
+    prev = [None] * 6
+    prev_cam = None
+    if history is not None:
+        missing = [key for key in ("linear", "moment2", "length", "features", "cam") if history.get(key) is None]
+        if missing:
+            raise ValueError("%s: the history is a previous call's result (it lacks %s)" % (who, ", ".join(missing)))
+        pf = history["features"]
+        prev = [np.ascontiguousarray(a, dtype=np.float64) for a in (history["linear"], history["moment2"], history["length"], pf["normal"], pf["depth"],
+                                                                    pf["alpha"])]
+        prev_cam = history["cam"]
+    f = {key: np.ascontiguousarray(features[key], dtype=np.float64) for key in ("normal", "depth", "alpha")}
+    for arr, shape in ((f["normal"], (h, w, 3)), (f["depth"], (h, w)), (f["alpha"], (h, w)), (prev[0], (h, w, 3)), (prev[1], (h, w, 3)), (prev[2], (h, w)),
+                       (prev[3], (h, w, 3)), (prev[4], (h, w)), (prev[5], (h, w))):
+        if arr is not None and arr.shape != shape:
+            raise ValueError("%s: every array is of one %dx%d frame, got %s where %s was expected" % (who, w, h, arr.shape, shape))
+    b = library.product()
+    out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "moment2": np.zeros((h, w, 3)), "length": np.zeros((h, w)),
+           "prev_xy": np.zeros((h, w, 2)), "variance": np.zeros((h, w, 3)), "mean": np.zeros((h, w, 3)) if want_statistics else None,
+           "sd": np.zeros((h, w, 3)) if want_statistics else None, "clipped": np.zeros((h, w), dtype=np.uint8)}
+    t = abi.Temporal(max_history=int(max_history), reserved0=0, depth_tolerance=depth_tolerance, normal_min=normal_min)
+    v = abi.Variance(min_temporal=int(min_temporal), radius=int(radius), sigma_normal=sigma_normal, sigma_depth=sigma_depth, reserved0=0, reserved1=0)
+    ms = C.c_double(0.0)
+    rc = b.temporal_clamp(w, h, C.byref(cam), None if prev_cam is None else C.byref(prev_cam), lin.ctypes.data, f["normal"].ctypes.data,
+                          f["depth"].ctypes.data, f["alpha"].ctypes.data, *[_ptr(a) for a in prev], C.byref(t), C.byref(v), C.byref(k),
+                          *[_ptr(out[name]) for name in CLAMP_OUTPUTS], C.byref(ms))
+    check(rc, b, "rttnw_temporal_clamp")
+    out["features"], out["cam"] = features, cam
+    if want_ms:
+        out["ms"] = ms.value
+    return out
+
+
 def orbit_cameras(cam, frames, step_degrees):
     """The cameras of an orbit of `frames` frames that ENDS at `cam`: frame k's lookfrom is `cam`'s, turned about the axis through lookat along
     view_up by (k - (frames - 1)) * step_degrees degrees (Rodrigues' formula); everything else is `cam`'s."""
@@ -473,7 +540,7 @@ _spatial_denoise = denoise   # (render_sequence has a parameter of that name)
 
 
 def render_sequence(scene, cams, params, temporal=True, denoise=False, iterations=5, max_history=0, depth_tolerance=0.0, normal_min=0.0,
-                    on_frame=None, variance=False):
+                    on_frame=None, variance=False, clamp=None):
     """One frame per camera of `cams`: frame k is `render_host` with `sample_begin = params.sample_begin + k * params.spp` (so the frames are
     independent estimates), its `render_features` of min(spp, 16) samples, and — with `temporal` — `temporal_accumulate` over the previous
     frame's result.  With `denoise` the image shown is `rttnw_denoise` of the accumulated one; the history stays unfiltered.  Returns a list of
@@ -481,9 +548,15 @@ def render_sequence(scene, cams, params, temporal=True, denoise=False, iteration
     `temporal_accumulate` result, None without `temporal`), "features", "cam", "stats" (the render's Stats).  `on_frame(k, frame)` is called
     as each frame is done.  With `variance` (which needs `temporal`) the frame goes through `temporal_variance` instead — accumulate, estimate,
     filter, the three stages of SVGF — and `rttnw_denoise` receives its "variance" for the colour stop; "accumulated" then carries "moment2"
-    and "variance"."""
+    and "variance".  `clamp` (a number, which needs `variance`): the frames go through `temporal_clamp` with that gamma instead — the history is
+    clipped to each frame's neighbourhood statistics before the blend — and "accumulated" carries "mean", "sd" and "clipped" as well; None, the
+    default, leaves the frames as they are."""
     if variance and not temporal:
         raise ValueError("render_sequence: variance needs temporal: the variance is estimated from the accumulated history")
+    if clamp is not None and not variance:
+        raise ValueError("render_sequence: clamp needs variance: the clip stands in front of temporal_variance's blend")
+    if clamp is not None and not float(clamp) >= 0.0:
+        raise ValueError("render_sequence: clamp is the gamma of temporal_clamp, at least 0 (0: the default, 1.0), got %r" % (clamp,))
     frames, history = [], None
     for k, cam in enumerate(cams):
         p = copy.copy(params)
@@ -495,6 +568,8 @@ def render_sequence(scene, cams, params, temporal=True, denoise=False, iteration
         lin = raw
         if temporal:
             accumulate = temporal_variance if variance else temporal_accumulate
+            if clamp is not None:
+                accumulate = functools.partial(temporal_clamp, gamma=float(clamp))
             history = accumulate(raw, features, cam, history=history, max_history=max_history, depth_tolerance=depth_tolerance, normal_min=normal_min)
             lin, rgba = history["linear"], history["rgba8"]
         if denoise:
@@ -559,6 +634,23 @@ class SvgfSequence:
         """Drop the history: the next call is a first frame."""
         check(self._b.svgf_reset(self.handle), self._b, "rttnw_svgf_reset")
 
+    def set_clamp(self, gamma=0.0, radius=0, sigma_normal=0.0, sigma_depth=0.0):
+        """`rttnw_svgf_set_clamp`: from the next call on the reprojected history — the moments' and, with feedback, the colour's — is clipped to the
+        frame's neighbourhood statistics as `temporal_clamp` clips it (a 0: its default; a gamma of inf never clips).  The history is kept."""
+        k = _clamp_params("SvgfSequence.set_clamp", gamma, radius, sigma_normal, sigma_depth)
+        check(self._b.svgf_set_clamp(self.handle, C.byref(k)), self._b, "rttnw_svgf_set_clamp")
+
+    def clear_clamp(self):
+        """Clipping off again, from the next call on: the default."""
+        check(self._b.svgf_set_clamp(self.handle, None), self._b, "rttnw_svgf_set_clamp")
+
+    def clipped(self):
+        """`rttnw_svgf_clipped`: HxW u8 of the last frame call — bits 0 - 2 the clipped channels of the first moment, bits 4 - 6 those of the
+        fed-back colour history; all 0 before any call and after a call without a clamp."""
+        out = np.zeros((self.height, self.width), dtype=np.uint8)
+        check(self._b.svgf_clipped(self.handle, out.ctypes.data), self._b, "rttnw_svgf_clipped")
+        return out
+
     def _outputs(self, want):
         """(dict of zeroed arrays, the rttnw_svgf_out over them, the image_ms cell); `want` None: everything, () : nothing (no struct at all)."""
         names = tuple(SVGF_ARRAYS) if want is None else tuple(want)
@@ -598,15 +690,20 @@ class SvgfSequence:
 
 def render_sequence_device(scene, cams, params, feedback=0, demodulate=False, iterations=5, max_history=0, depth_tolerance=0.0, normal_min=0.0,
                            on_frame=None, want=("linear_rgb", "rgba8", "raw_rgb", "length", "accumulated_rgb", "moment2_rgb", "variance_rgb", "prev_xy",
-                                                "albedo", "normal", "depth", "alpha")):
+                                                "albedo", "normal", "depth", "alpha"), clamp=None):
     """`render_sequence(..., variance=True, denoise=True)` on the device: one `SvgfSequence`, one `frame` call per camera, frame k at
     `sample_begin = params.sample_begin + k * params.spp`.  With `feedback` 0 and without `demodulate` the images are that function's, bit for
     bit.  Returns the same list of dicts — "linear", "rgba8", "raw", "length", "accumulated" ("linear", "rgba8" absent, "moment2", "variance",
     "length", "prev_xy"), "features", "cam", "stats" — and "image_ms", the device time behind the trace and the feature pass.  An entry of a
-    frame is None where `want` leaves its output out."""
+    frame is None where `want` leaves its output out.  `clamp` (a number): the handle clips its history with that gamma (`SvgfSequence.set_clamp`)
+    and each frame carries "clipped", the call's map; None, the default, leaves the frames as they are."""
+    if clamp is not None and not float(clamp) >= 0.0:
+        raise ValueError("render_sequence_device: clamp is the gamma of temporal_clamp, at least 0 (0: the default, 1.0), got %r" % (clamp,))
     frames = []
     with SvgfSequence(params.width, params.height, feedback=feedback, demodulate=demodulate, iterations=iterations, max_history=max_history,
                       depth_tolerance=depth_tolerance, normal_min=normal_min) as seq:
+        if clamp is not None:
+            seq.set_clamp(gamma=float(clamp))
         for k, cam in enumerate(cams):
             p = copy.copy(params)
             p.sample_begin = params.sample_begin + k * params.spp
@@ -616,6 +713,8 @@ def render_sequence_device(scene, cams, params, feedback=0, demodulate=False, it
                            "length": got.get("length"), "prev_xy": got.get("prev_xy"), "features": features, "cam": cam}
             frame = {"linear": got.get("linear_rgb"), "rgba8": got.get("rgba8"), "raw": got.get("raw_rgb"), "length": got.get("length"),
                      "accumulated": accumulated, "features": features, "cam": cam, "stats": got["stats"], "image_ms": got["image_ms"]}
+            if clamp is not None:
+                frame["clipped"] = seq.clipped()
             frames.append(frame)
             if on_frame is not None:
                 on_frame(k, frame)
