@@ -170,6 +170,16 @@ pub struct rttnw_clamp_params {
     pub sigma_depth: f64,
 }
 
+/// What `rttnw_temporal_probe` takes beside `rttnw_temporal_params`, and `rttnw_svgf_set_sampling` alone (include/rttnw_hip.h states the contract);
+/// a 0 is the library default (a boost of 8, a fill of 8.0).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rttnw_sampling_params {
+    pub boost: u32,
+    pub reserved0: u32,
+    pub fill: f64,
+}
+
 /// Opaque handle of the SVGF loop (`rttnw_svgf_create`): a sequence's history on the device.
 #[repr(C)]
 pub struct rttnw_svgf {
@@ -338,6 +348,9 @@ extern "C" {
     pub fn rttnw_temporal_clamp(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, linear_rgb: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, prev_linear_rgb: *const f64, prev_moment2_rgb: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, v: *const rttnw_variance_params, k: *const rttnw_clamp_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_moment2_rgb: *mut f64, out_length: *mut f64, out_prev_xy: *mut f64, out_variance_rgb: *mut f64, out_mean_rgb: *mut f64, out_sd_rgb: *mut f64, out_clipped: *mut u8, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_svgf_set_clamp(q: *mut rttnw_svgf, k: *const rttnw_clamp_params) -> c_int;
     pub fn rttnw_svgf_clipped(q: *mut rttnw_svgf, out_clipped: *mut u8) -> c_int;
+    pub fn rttnw_temporal_probe(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, normal: *const f64, depth: *const f64, alpha: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, a: *const rttnw_sampling_params, out_length: *mut f64, out_prev_xy: *mut f64, out_multiplier: *mut u8, kernel_ms: *mut f64) -> c_int;
+    pub fn rttnw_svgf_set_sampling(q: *mut rttnw_svgf, a: *const rttnw_sampling_params) -> c_int;
+    pub fn rttnw_svgf_samples(q: *mut rttnw_svgf, out_spp: *mut u32, out_length: *mut f64) -> c_int;
     pub fn rttnw_svgf_create(width: u32, height: u32, q: *const rttnw_svgf_params, out: *mut *mut rttnw_svgf) -> c_int;
     pub fn rttnw_svgf_destroy(q: *mut rttnw_svgf);
     pub fn rttnw_svgf_reset(q: *mut rttnw_svgf) -> c_int;

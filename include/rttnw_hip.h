@@ -45,7 +45,8 @@ extern "C" {
                              *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select,
                              *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised, rttnw_denoise_nlm,
                              *  rttnw_denoise_select, rttnw_temporal_accumulate, rttnw_temporal_variance, the rttnw_svgf_create family, rttnw_temporal_clamp,
-                             *  rttnw_svgf_set_clamp and rttnw_svgf_clipped came later, without a version bump: a caller detects each by its symbol) */
+                             *  rttnw_svgf_set_clamp, rttnw_svgf_clipped, rttnw_temporal_probe, rttnw_svgf_set_sampling and rttnw_svgf_samples came
+                             *  later, without a version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -745,6 +746,77 @@ int rttnw_temporal_clamp(uint32_t width, uint32_t height, const rttnw_camera_des
                          double* out_variance_rgb, double* out_mean_rgb, double* out_sd_rgb, uint8_t* out_clipped, double* kernel_ms);
 int rttnw_svgf_set_clamp(rttnw_svgf* q, const rttnw_clamp_params* k);   /* NULL: off, the default */
 int rttnw_svgf_clipped(rttnw_svgf* q, uint8_t* out_clipped);            /* w*h: the last frame call's map */
+
+/* Adaptive sampling inside the SVGF sequence: pixels whose history is thin get more samples in this frame.  The handle's block above leaves
+ * adaptive sampling inside the sequence out of its scope; it now lives here.  Along an orbit a large share of the pixels finds no history (a
+ * disocclusion, the frame's edge) and enters the filter with the frame's few samples beside neighbours that hold dozens of frames.  Which pixels
+ * those are is known BEFORE the trace: reprojection needs this frame's first-hit features and the state's, not its colour.
+ *
+ * rttnw_temporal_probe: where each pixel's history is, and how long, without colour.  Calling convention as rttnw_temporal_accumulate: host arrays
+ * in and out (row-major, top row first), blocking, on the current device, no scene handle; no CPU fallback: RTTNW_ERR_HIP without a device.
+ * Everything is double.
+ * Pixel rule.  rttnw_temporal_accumulate's geometry and acceptance, unchanged: steps 1 and 2 of that contract (the surface point, its place
+ *   (fx, fy) in the previous frame and its distance zq there), then the four taps in the order 00, 10, 01, 11 through that contract's tests,
+ *   with the same wt, sw = sw + wt and sl = sl + wt * prev_length[tp].  Where sw > 0, Lp = sl / sw.  Lp = 0.0 on every pass-through case: no
+ *   history, alpha == 0, no place in the previous frame, or sw > 0 false.  out_length = Lp.  out_prev_xy is rttnw_temporal_accumulate's.
+ * Multiplier.  k = floor(fill / (Lp + 1.0)).  m is the largest of 1, 2, 4, 8 that is <= min(k, boost); m = 1 when k < 1 (a NaN compares false:
+ *   m = 1), and m = 1 where this frame's alpha == 0.  out_multiplier = m, one byte a pixel.
+ * Consequence.  With the same inputs rttnw_temporal_accumulate's out_length equals Lp == 0 ? 1 : min(Lp + 1, max_history), bit for bit (min as
+ *   that contract takes it: grown < max_history ? grown : max_history), and the two out_prev_xy are equal bitwise, NaNs included.
+ * Arithmetic.  + - * /, sqrt, floor and comparisons only; no product is fused into a sum; every sum starts from 0.0 and adds in the order
+ *   stated; non-finite values are not special-cased.  So the device code, a host build of the same header (rttnw_amd/csrc/probe.hpp) and a
+ *   restatement in numpy give the same bits.
+ * Outputs, each optional: out_length w*h; out_prev_xy w*h*2; out_multiplier w*h bytes; kernel_ms: device time of the one kernel.
+ * Refusals, before the device is touched, each message naming temporal_probe and the argument, RTTNW_ERR_INVALID: everything
+ *   rttnw_temporal_accumulate refuses for the arguments the two calls share, in its order (a NULL cam; a NULL normal, depth or alpha; a NULL t; an
+ *   empty image or more than 2^28 pixels; the four prev_* arrays not all or none; a history without prev_cam; t's fields); then a NULL a, a->boost
+ *   not in {0, 1, 2, 4, 8}, a->reserved0 != 0, and a->fill that is NaN, infinite or in (0, 1).
+ *
+ * The handle.  rttnw_svgf_set_sampling switches sampling on for an rttnw_svgf handle (NULL: off, the default); it takes effect from the next frame
+ *   call, keeps the history, refuses what rttnw_temporal_probe refuses for a (the handle is checked last), and allocates what it needs there and
+ *   then (two maps, the mask and selection bytes, the list of 2x2 blocks and the list passes' sums: 44 bytes a pixel).  rttnw_svgf_push is
+ *   unaffected: the caller rendered that frame.  rttnw_svgf_out and rttnw_svgf_params are unchanged.  With sampling set, rttnw_svgf_frame changes in
+ *   one place, the colour C it renders:
+ *   1. The feature pass runs first; it does not depend on the trace, so F keeps its bits.
+ *   2. m = rttnw_temporal_probe(cam, cam', F, the state's L, normal, depth and alpha, t, a).out_multiplier.  With an empty state
+ *      m = min(boost, largest power of two <= floor(fill)) on every hit pixel, 1 on every miss.
+ *   3. For every pixel, C(p) is the pixel of rttnw_render(s, cam, p with spp = m(p) * p->spp, the same sample_begin), bit for bit; equivalently
+ *      of rttnw_render_region under the mask {m == level} with spp = level * p->spp.
+ *   4. Steps 0 to 5 of the handle's contract run on that C, unchanged, also with a clamp set.
+ *   So a frame call with sampling equals rttnw_svgf_push of that composed C and of F, in every output.  With boost = 1, or sampling never set,
+ *   every output and the handle's state are the bits of a handle without it.
+ * How it is traced.  Everything stays on the device.  The plain pass traces EVERY pixel at p->spp as without sampling; then, per level 2, 4, 8 up
+ *   to boost, the pixels of that level are listed as rttnw_render_region lists a mask, traced at level * p->spp, and written over the plain
+ *   pass's.  The plain pass's samples of a boosted pixel are discarded.  Each level's list reads its length back with an 8-byte copy, so the call
+ *   waits up to three more times than without sampling; a level nobody holds traces nothing.
+ * Accounting.  stats->samples counts what was traced, the discarded samples included: width * height * p->spp of the plain pass, plus
+ *   m(p) * p->spp of every pixel with m(p) > 1, plus the feature pass's rays as without sampling.  stats->rays is what it is without sampling (the
+ *   feature pass's rays: the handle takes no counters).  stats->kernel_ms is the plain pass's plus the time from the probe to the last level's
+ *   write, the waits for the lists' lengths included.
+ *   rttnw_svgf_samples copies out the last rttnw_svgf_frame call's map, each array optional: out_spp w*h, m(p) * p->spp; out_length w*h, Lp.
+ *   Before any frame call out_spp is all 0 and out_length all 0; after a frame call without sampling out_spp is that call's p->spp everywhere and
+ *   out_length all 0.  rttnw_svgf_push leaves the map as it is.
+ * Sample indices.  A frame call with sampling may consume sample indices [sample_begin, sample_begin + boost * spp): a caller who wants
+ *   independent frames advances p->sample_begin by boost * p->spp a frame.  rttnw_svgf_frame refuses, before the device is touched and on the terms
+ *   of its other checks (RTTNW_ERR_INVALID, naming svgf_frame), a p->spp whose product with the handle's boost is no spp rttnw_render accepts
+ *   (more than 2^32 - 1).
+ * Deliberately unchanged: the blend still weighs a frame as one frame, whatever its sample count.  With the defaults (boost 8, fill 8.0) a
+ *   disoccluded pixel gets 8, 4, 2, 2, 1, ... times spp over its first frames (Lp = 0, 1, 2, 3, 4): the schedule decays instead of stepping.
+ * Out of scope: a sample-weighted history length; dilating the multiplier map; a different rule for the first frame; the variance, not only the
+ *   length, as the driver; a node-wide form; the native rttnw program. */
+struct rttnw_sampling_params {
+    uint32_t boost;      /* largest multiplier of p->spp a pixel may get: 1, 2, 4 or 8; 0 = default 8 */
+    uint32_t reserved0;  /* must be 0 */
+    double fill;         /* a pixel is boosted while (reprojected length + 1) * m <= fill; 0 = default 8.0; >= 1, finite */
+};
+typedef struct rttnw_sampling_params rttnw_sampling_params;
+int rttnw_temporal_probe(uint32_t width, uint32_t height, const rttnw_camera_desc* cam, const rttnw_camera_desc* prev_cam,
+                         const double* normal, const double* depth, const double* alpha,
+                         const double* prev_length, const double* prev_normal, const double* prev_depth, const double* prev_alpha,
+                         const rttnw_temporal_params* t, const rttnw_sampling_params* a,
+                         double* out_length, double* out_prev_xy, uint8_t* out_multiplier, double* kernel_ms);
+int rttnw_svgf_set_sampling(rttnw_svgf* q, const rttnw_sampling_params* a);  /* NULL: off, the default */
+int rttnw_svgf_samples(rttnw_svgf* q, uint32_t* out_spp, double* out_length); /* w*h each, optional: the last rttnw_svgf_frame call's map */
 
 /* `render()` on the GPUs of ONE NODE, in one call from one host thread ("library owns its HIP
  * streams / RCCL comms"): the framebuffer's 8x8 tiles are interleaved over `ngpu` ranks, rank r traces its tiles on

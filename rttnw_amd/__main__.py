@@ -62,6 +62,9 @@ colour / albedo, so textures neither blur in the reprojection nor read as varian
 --clamp GAMMA (with --temporal-variance or --svgf) clips the reprojected history to each frame before the blend (rttnw_temporal_clamp): the mean
 and the standard deviation of the frame's colour over a 7x7 window guided by normal and depth admit the history within GAMMA deviations (0: the
 default, 1.0) and move it to the nearer bound outside — ghosts of reflections and refractions go, at the price of some noise coming back.
+--boost B (with --svgf; 1, 2, 4 or 8) gives pixels whose reprojected history is thin — disocclusions, the frame's edge, the first frame — up to B
+times --spp samples in that frame (rttnw_svgf_set_sampling): the largest of 1, 2, 4, 8 that is at most B and at most FILL / (history length + 1),
+--fill FILL (default 8).  --spp-map spp_%03d.png writes each frame's samples per pixel as a grey image (spp * 255 / (B * --spp)).
 """
 import argparse
 import sys
@@ -137,6 +140,18 @@ def refusal(args, refine, devices, window):
         return "--clamp needs --temporal-variance or --svgf: it clips the history those accumulate"
     if args.clamp is not None and not args.clamp >= 0.0:
         return "--clamp must be at least 0 standard deviations (0: the default, 1.0)"
+    if (args.boost is not None or args.fill is not None) and not args.svgf:
+        return "--boost and --fill need --svgf: only the loop on the device chooses samples per pixel"
+    if args.fill is not None and args.boost is None:
+        return "--fill needs --boost: without it every pixel gets --spp samples"
+    if args.boost is not None and args.boost not in (1, 2, 4, 8):
+        return "--boost must be 1, 2, 4 or 8"
+    if args.fill is not None and not 1.0 <= args.fill < float("inf"):
+        return "--fill must be finite and at least 1"
+    if args.svgf and args.spp_map is not None and args.boost is None:
+        return "--spp-map with --svgf needs --boost: without it every pixel gets --spp samples"
+    if args.svgf and args.spp_map is not None and "%" not in args.spp_map:
+        return "--spp-map with --svgf names one file per frame: it needs a %d (as in spp_%03d.png)"
     if args.temporal_variance and not on["--orbit"]:
         return "--temporal-variance needs --orbit: it estimates the variance from the accumulated frames of a sequence"
     if args.temporal and not on["--orbit"]:
@@ -215,7 +230,7 @@ def main(argv=None):
     ap.add_argument("--noise", type=float, default=None, help="adaptive sampling: relative noise bound (standard error / mean); --spp is the cap")
     ap.add_argument("--abs-noise", type=float, default=0.0, help="adaptive sampling: absolute noise bound added to the relative one")
     ap.add_argument("--pass-spp", type=int, default=64, help="adaptive sampling: samples per pixel per pass (the cap must be a multiple)")
-    ap.add_argument("--spp-map", default=None, help="adaptive sampling: also write a grey-scale PNG of samples / cap")
+    ap.add_argument("--spp-map", default=None, help="adaptive sampling: also write a grey-scale PNG of samples / cap; svgf with --boost: one per frame, the name holding a %%d for the frame's number, as in spp_%%03d.png")
     ap.add_argument("--denoise", action="store_true", help="filter the image with the feature-guided denoiser (rttnw_denoise)")
     ap.add_argument("--denoise-iterations", type=int, default=5, help="a-trous passes of the denoiser (0..8)")
     ap.add_argument("--denoise-nlm", action="store_true", help="render two halves of spp / 2 samples and filter them with non-local means "
@@ -243,6 +258,10 @@ def main(argv=None):
     ap.add_argument("--demodulate", action="store_true", help="svgf: accumulate, estimate and filter colour / albedo")
     ap.add_argument("--clamp", type=float, default=None, metavar="GAMMA", help="temporal-variance, svgf: clip the reprojected history into the frame's "
                     "neighbourhood mean +- GAMMA standard deviations before the blend (rttnw_temporal_clamp; 0: the default, 1.0)")
+    ap.add_argument("--boost", type=int, default=None, metavar="B", help="svgf: up to B (1, 2, 4 or 8) times --spp samples for pixels whose reprojected "
+                    "history is thin (rttnw_svgf_set_sampling)")
+    ap.add_argument("--fill", type=float, default=None, metavar="FILL", help="svgf, with --boost: a pixel is boosted while (history length + 1) * "
+                    "multiplier <= FILL (default 8)")
     ap.add_argument("--guided", action="store_true", help="adaptive sampling: stop pixels on the noise of the denoised image "
                     "(rttnw_render_adaptive_denoised); writes the denoised image")
     ap.add_argument("--preview", type=int, default=None, metavar="L", help="adaptive sampling: trace 1 pixel in 4^L (x %% 2^L == 0 and y %% 2^L == 0, "
@@ -316,10 +335,15 @@ def main(argv=None):
         def write(k, frame):
             trace_ms[0] += frame["stats"].kernel_ms
             Image.fromarray(np.ascontiguousarray(frame["rgba8"]), "RGBA").save(os.path.join(where, "frame_%03d.png" % k))
+            if args.svgf and args.spp_map is not None:
+                grey = (frame["spp"].astype(np.uint64) * 255 // (args.boost * p.spp)).astype(np.uint8)
+                Image.fromarray(grey, "L").save(args.spp_map % k)
 
         if args.svgf:
             frames = render.render_sequence_device(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, feedback=args.feedback,
-                                                   demodulate=args.demodulate, iterations=args.denoise_iterations, on_frame=write, clamp=args.clamp)
+                                                   demodulate=args.demodulate, iterations=args.denoise_iterations, on_frame=write, clamp=args.clamp,
+                                                   sampling=None if args.boost is None else (args.boost, args.fill or 0.0),
+                                                   want_spp=args.boost is not None)
             args.temporal = args.temporal_variance = True
         else:
             frames = render.render_sequence(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, temporal=args.temporal, denoise=args.denoise,
@@ -331,6 +355,11 @@ def main(argv=None):
             length = frames[-1]["length"]
             print("temporal: the last frame's history counts %.2f frames on average, %.1f %% of its pixels were reset"
                   % (length.mean(), 100.0 * (length == 1.0).mean() if args.orbit > 1 else 0.0))
+        if args.svgf and args.boost is not None:
+            total = sum(int(f["spp"].sum()) for f in frames)
+            print("sampling: boost %d, fill %g: %.2f samples a pixel and frame on average (%d traced in all, the feature pass's rays and the plain pass's discarded samples included)"
+                  % (args.boost, args.fill or 8.0, total / (len(frames) * float(w * h)),
+                     sum(int(f["stats"].samples) for f in frames)))
         if args.svgf:
             print("svgf: feedback %d, %s; %.3f ms a frame on the device behind the trace and the feature pass"
                   % (args.feedback, "colour / albedo" if args.demodulate else "colour", sum(f["image_ms"] for f in frames) / len(frames)))

@@ -90,6 +90,12 @@ class Clamp(C.Structure):
     _fields_ = [("radius", C.c_uint32), ("reserved0", C.c_uint32), ("gamma", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
 
 
+class Sampling(C.Structure):
+    """`rttnw_sampling_params` — what `rttnw_temporal_probe` takes beside `rttnw_temporal_params`, and `rttnw_svgf_set_sampling` alone: the largest
+    multiple of the frame's spp a pixel may get and the fill the boost aims at (a 0: the library default, 8 and 8.0)."""
+    _fields_ = [("boost", C.c_uint32), ("reserved0", C.c_uint32), ("fill", C.c_double)]
+
+
 class Svgf(C.Structure):
     """`rttnw_svgf_params` — the settings of an `rttnw_svgf` handle: the loop's own, then the three stages' blocks (a 0: that stage's default)."""
     _fields_ = [("feedback_iterations", C.c_uint32), ("demodulate", C.c_uint32), ("feature_spp", C.c_uint32), ("reserved0", C.c_uint32),
@@ -208,6 +214,10 @@ PRODUCT_FUNCS = [
                                 [C.POINTER(Temporal), C.POINTER(Variance), C.POINTER(Clamp)] + [C.c_void_p] * 9 + [C.POINTER(C.c_double)]),
     ("svgf_set_clamp", C.c_int, [C.c_void_p, C.POINTER(Clamp)]),
     ("svgf_clipped", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("temporal_probe", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(CameraDesc), C.POINTER(CameraDesc)] + [C.c_void_p] * 7 +
+                                [C.POINTER(Temporal), C.POINTER(Sampling)] + [C.c_void_p] * 3 + [C.POINTER(C.c_double)]),
+    ("svgf_set_sampling", C.c_int, [C.c_void_p, C.POINTER(Sampling)]),
+    ("svgf_samples", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("render_preview", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Preview), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("budget_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint64,

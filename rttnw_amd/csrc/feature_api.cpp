@@ -2,7 +2,7 @@
 // rttnw_temporal_variance and rttnw_reconstruct (include/rttnw_hip.h): argument checks, then the feature pass of the requested arithmetic build (feature_kernels.hpp), the
 // device half of the denoiser and of the reconstruction (denoise.hip), the non-local-means filter's (nlm.hip), the per-pixel choice between the two
 // (select.hip), the temporal accumulation (temporal.hip), that accumulation with its variance estimate (variance.hip) or with the history clipped to
-// the frame in front of it (rttnw_temporal_clamp, clamp.hip).  Host code only.
+// the frame in front of it (rttnw_temporal_clamp, clamp.hip), or the colour-free probe of that accumulation (rttnw_temporal_probe, probe.hip).  Host code only.
 #include "feature_api.hpp"
 
 namespace rt {
@@ -14,6 +14,15 @@ int clamp_refuse_params(const char* call, const rttnw_clamp_params* k) {
     if (k->reserved0 != 0) return refuse("k->reserved0 must be 0");
     if (!(k->gamma >= 0.0)) return refuse("k->gamma must be >= 0 (and not NaN; +inf never clips)");
     if (!(k->sigma_normal >= 0.0) || !(k->sigma_depth >= 0.0)) return refuse("the sigmas (k->sigma_normal, k->sigma_depth) must be >= 0 (and not NaN)");
+    return 0;
+}
+
+int sampling_refuse_params(const char* call, const rttnw_sampling_params* a) {
+    const auto refuse = [call](const char* what) { set_last_error(std::string(call) + ": " + what); return int(RTTNW_ERR_INVALID); };
+    if (!a) return refuse("a is NULL");
+    if (a->boost != 0 && a->boost != 1 && a->boost != 2 && a->boost != 4 && a->boost != 8) return refuse("a->boost must be 0 (the default, 8), 1, 2, 4 or 8");
+    if (a->reserved0 != 0) return refuse("a->reserved0 must be 0");
+    if (!temporal_finite(a->fill) || !(a->fill == 0.0 || a->fill >= 1.0)) return refuse("a->fill must be 0 (the default, 8.0) or finite and >= 1 (and not NaN)");
     return 0;
 }
 
@@ -208,6 +217,34 @@ int rttnw_temporal_clamp(uint32_t width, uint32_t height, const rttnw_camera_des
                             rt::clamp_params(k->radius, k->gamma, k->sigma_normal, k->sigma_depth), linear_rgb, normal, depth, alpha, prev_linear_rgb,
                             prev_moment2_rgb, prev_length, prev_normal, prev_depth, prev_alpha, out_linear_rgb, out_rgba8, out_moment2_rgb, out_length,
                             out_prev_xy, out_variance_rgb, out_mean_rgb, out_sd_rgb, out_clipped, kernel_ms);
+}
+
+int rttnw_temporal_probe(uint32_t width, uint32_t height, const rttnw_camera_desc* cam, const rttnw_camera_desc* prev_cam, const double* normal,
+                         const double* depth, const double* alpha, const double* prev_length, const double* prev_normal, const double* prev_depth,
+                         const double* prev_alpha, const rttnw_temporal_params* t, const rttnw_sampling_params* a, double* out_length, double* out_prev_xy,
+                         uint8_t* out_multiplier, double* kernel_ms) {
+    // what rttnw_temporal_accumulate refuses for the arguments the two share, in its order, then the sampling block's own
+    const auto refuse = [](const char* what) { rt::set_last_error(std::string("temporal_probe: ") + what); return int(RTTNW_ERR_INVALID); };
+    if (!cam) return refuse("cam is NULL");
+    if (!normal || !depth || !alpha) return refuse("NULL argument (normal, depth or alpha)");
+    if (!t) return refuse("t is NULL");
+    if (uint64_t(width) * height == 0 || uint64_t(width) * height > (1ull << 28)) return refuse("width * height: empty image (or more than 2^28 pixels)");
+    const int given = (prev_length != nullptr) + (prev_normal != nullptr) + (prev_depth != nullptr) + (prev_alpha != nullptr);
+    const bool has_history = given == 4;
+    if (given != 0 && given != 4) return refuse("the prev_* arrays go together: prev_length, prev_normal, prev_depth and prev_alpha all, or none");
+    if (has_history && !prev_cam) return refuse("prev_cam is NULL beside a history");
+    if (t->max_history > rt::TEMPORAL_HISTORY_LIMIT) return refuse("t->max_history is more than 65535");
+    if (t->reserved0 != 0) return refuse("t->reserved0 must be 0");
+    if (!(t->depth_tolerance >= 0.0)) return refuse("t->depth_tolerance must be >= 0 (and not NaN)");
+    if (!(t->normal_min >= -1.0 && t->normal_min <= 1.0)) return refuse("t->normal_min must lie in [-1, 1] (and not be NaN)");
+    if (int rc = rt::sampling_refuse_params("temporal_probe", a)) return rc;
+    const rt::CameraRec<double> rec = rt::camera_of<double>(cam);
+    rt::CameraRec<double> prev_rec = {};
+    if (has_history) prev_rec = rt::camera_of<double>(prev_cam);
+    const bool same_camera = has_history && std::memcmp(cam, prev_cam, sizeof(rttnw_camera_desc)) == 0;
+    const rt::TemporalParams prm = rt::temporal_params(rec, has_history ? &prev_rec : nullptr, same_camera, t->max_history, t->depth_tolerance, t->normal_min, false);
+    return rt::probe_device(width, height, prm, rt::sampling_params(a->boost, a->fill), normal, depth, alpha, prev_length, prev_normal, prev_depth, prev_alpha,
+                            out_length, out_prev_xy, out_multiplier, kernel_ms);
 }
 
 int rttnw_reconstruct(uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const uint8_t* valid, const double* albedo,

@@ -1,7 +1,8 @@
 // feature_api.hpp — what feature_api.cpp (the extern "C" half of rttnw_render_features and rttnw_denoise) calls: the feature pass's launch
 // code per arithmetic build (feature_kernels.hpp, instantiated in features_f32.hip / features_f64.hip / features_f64_strict.hip) and the
 // device halves of the denoiser and of rttnw_reconstruct (denoise.hip), of rttnw_denoise_nlm (nlm.hip), of rttnw_denoise_select (select.hip), of
-// rttnw_temporal_accumulate (temporal.hip) and of rttnw_temporal_variance (variance.hip).
+// rttnw_temporal_accumulate (temporal.hip), of rttnw_temporal_variance (variance.hip), of rttnw_temporal_clamp (clamp.hip) and of
+// rttnw_temporal_probe (probe.hip).
 // Kept out of render_common.hpp: the render kernels' translation units do not read it.
 #pragma once
 #include "render_common.hpp"
@@ -11,6 +12,7 @@
 #include "temporal.hpp"
 #include "variance.hpp"
 #include "clamp.hpp"
+#include "probe.hpp"
 
 namespace rt {
 
@@ -96,6 +98,25 @@ int clamp_accumulate_device(const char* at, uint32_t width, uint32_t height, con
 // What rttnw_temporal_clamp and rttnw_svgf_set_clamp refuse for a rttnw_clamp_params (feature_api.cpp): 0, or RTTNW_ERR_INVALID behind a message
 // "<call>: ..." that names the field
 int clamp_refuse_params(const char* call, const rttnw_clamp_params* k);
+
+// rttnw_temporal_probe's device half (probe.hip): host arrays in, host arrays out (each optional), blocking, on the current device: one kernel
+// (probe.hpp).  The prev_* arrays are read only with prm.has_history.  Arguments were checked by the caller.
+int probe_device(uint32_t width, uint32_t height, const TemporalParams& prm, const SamplingParams& smp, const double* normal, const double* depth,
+                 const double* alpha, const double* prev_length, const double* prev_normal, const double* prev_depth, const double* prev_alpha,
+                 double* out_length, double* out_prev_xy, uint8_t* out_multiplier, double* kernel_ms);
+// ... and what rttnw_svgf_frame enqueues of it on `stream` over buffers that are already on the device: nothing allocated, nothing copied, no wait.
+// probe_enqueue_device: the kernel (d_xy may be nullptr); probe_level_mask_device: the byte mask {multiplier == level} over n_pixels pixels, as
+// region_select_launch reads one; probe_scatter_device: the selected pixels of a list pass's running sums (n_quads listed blocks, 16 reals of the
+// render's precision each) to their places in the packed tiles of a whole frame (tile_world 1).
+int probe_enqueue_device(const char* at, uint32_t width, uint32_t height, const TemporalParams& prm, const SamplingParams& smp, const double* d_normal,
+                         const double* d_depth, const double* d_alpha, const double* d_plen, const double* d_pnormal, const double* d_pdepth,
+                         const double* d_palpha, double* d_len, double* d_xy, uint8_t* d_multiplier, hipStream_t stream);
+int probe_level_mask_device(const char* at, uint32_t n_pixels, const uint8_t* d_multiplier, uint32_t level, uint8_t* d_mask, hipStream_t stream);
+int probe_scatter_device(const char* at, uint32_t precision, const void* d_sums, const uint32_t* d_quads, uint32_t n_quads, void* d_packed,
+                         hipStream_t stream);
+// What rttnw_temporal_probe and rttnw_svgf_set_sampling refuse for a rttnw_sampling_params (feature_api.cpp): 0, or RTTNW_ERR_INVALID behind a
+// message "<call>: ..." that names the field
+int sampling_refuse_params(const char* call, const rttnw_sampling_params* a);
 
 // rttnw_denoise's passes with a tap of the pass loop (denoise.hip): atrous_passes_device without flags, and d_tap (w*h*3) receives the linear image
 // the same call would return with `tap_after` iterations, 1 <= tap_after <= iterations.  rttnw_svgf_push's feedback.

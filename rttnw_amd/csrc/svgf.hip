@@ -1,4 +1,4 @@
-// svgf.hip — rttnw_svgf_create / _destroy / _reset / _set_clamp / _clipped / _push / _frame (include/rttnw_hip.h): the SVGF loop over a history that stays on the device,
+// svgf.hip — rttnw_svgf_create / _destroy / _reset / _set_clamp / _clipped / _set_sampling / _samples / _push / _frame (include/rttnw_hip.h): the SVGF loop over a history that stays on the device,
 // around the arithmetic of svgf.hpp, double throughout.  The handle owns every buffer from rttnw_svgf_create on; a frame call enqueues, on one
 // stream and without allocating,
 //   svgf_ingest_kernel      one thread per pixel, blocks of 32 x 8: the frame's colour — the trace's packed tiles (reals of the render's precision,
@@ -9,9 +9,12 @@
 //   variance_estimate_kernel (variance.hip) and the à-trous passes (denoise.hip) as they are, the feedback a tap of the pass loop
 //   (with rttnw_svgf_set_clamp: clamp.hip's clamp_accumulate_kernel in svgf_accumulate_kernel's place, M1 and H clipped to the frame's interval)
 //   svgf_emit_kernel        one thread per pixel: the result and the accumulation multiplied back, and the RGBA8
+//   (with rttnw_svgf_set_sampling, in front of all that: probe.hip's probe_kernel over the frame's features and the state's, and per level of the
+//   boost a list of 2x2 blocks — pixel_lists.hip — traced by render_tiles_t and written over the plain trace's pixels; one 8-byte copy per level)
 // then waits once and copies out what the caller asked for.  No atomics.
 #include "feature_api.hpp"
 #include "render_multi.hpp"
+#include "pixel_lists.hpp"
 #include "svgf.hpp"
 
 struct rttnw_svgf {
@@ -30,6 +33,16 @@ struct rttnw_svgf {
     bool clamp = false, clipped_live = false;
     rt::ClampParams kprm = {};
     rt::DevBuf<uint8_t> clipped;
+    // rttnw_svgf_set_sampling: off by default.  The buffers are allocated by the first set call: the probe's length and multiplier maps, the level
+    // mask and selection bytes, the list of 2x2 blocks with its scan, and the list passes' running sums (as large as the packed frame: every block
+    // listed).  samples_live: the last frame call ran with sampling and wrote the maps; last_spp: the last frame call's p->spp (0 before any).
+    bool sampling = false, samples_live = false;
+    uint32_t last_spp = 0;
+    rt::SamplingParams sprm = {};
+    rt::DevBuf<double> s_len;
+    rt::DevBuf<uint8_t> s_mult, s_mask, s_select, s_sums;
+    rt::DevBuf<uint32_t> s_quads, s_scan;
+    rt::Event ev2, ev3;
 };
 
 namespace rt {
@@ -124,6 +137,55 @@ int refuse_params(const char* call, const rttnw_svgf_params* q) {
     return 0;
 }
 
+// The reprojection of a frame seen through `cam` into the handle's state (none: a first frame)
+TemporalParams svgf_temporal_params(const ::rttnw_svgf* g, const rttnw_camera_desc* cam) {
+    const CameraRec<double> rec = camera_of<double>(cam);
+    CameraRec<double> prev_rec = {};
+    if (g->has_state) prev_rec = camera_of<double>(&g->cam);
+    const bool same_camera = g->has_state && std::memcmp(cam, &g->cam, sizeof(rttnw_camera_desc)) == 0;
+    return temporal_params(rec, g->has_state ? &prev_rec : nullptr, same_camera, g->q.t.max_history, g->q.t.depth_tolerance, g->q.t.normal_min, false);
+}
+
+// rttnw_svgf_set_sampling's steps 2 and 3 behind the plain trace of the frame (g->packed holds every pixel at p->spp) and the feature pass
+// (maps[cur ^ 1]): the probe over the frame's features and the state's, then per level 2, 4, 8 up to the boost the mask {m == level}, its selection
+// bytes, the list of 2x2 blocks over them — one 8-byte copy gives the host its length —, render_tiles_t over that list at level * p->spp and the
+// selected pixels' records written over the plain trace's in g->packed.  A level nobody holds traces nothing.  `traced`: the samples of the list
+// passes.  Everything on the null stream, between g->ev2 and g->ev3.
+int svgf_boost_levels(const char* call, ::rttnw_svgf* g, ::rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, uint64_t& traced) {
+    const std::string at = std::string(call) + ": ";
+    const uint32_t w = g->width, h = g->height;
+    const size_t npx = size_t(w) * h;
+    const hipStream_t stream = nullptr;
+    const double* maps = g->maps[g->cur ^ 1].p;
+    const double* pmaps = g->maps[g->cur].p;
+    rttnw_tile_layout L;
+    fill_layout(w, h, 1, L);
+    const uint32_t n_blocks = L.n_tiles * 16u;
+    traced = 0;
+    HIP_TRY_AS(at, hipSetDevice(g->device));
+    HIP_TRY_AS(at, hipEventRecord(g->ev2.get(), stream));
+    if (int rc = probe_enqueue_device(at.c_str(), w, h, svgf_temporal_params(g, cam), g->sprm, maps + npx * 3, maps + npx * 6, maps + npx * 7, g->len[g->cur].p,
+                                      pmaps + npx * 3, pmaps + npx * 6, pmaps + npx * 7, g->s_len.p, nullptr, g->s_mult.p, stream)) return rc;
+    for (uint32_t level = 2; level <= g->sprm.boost; level *= 2) {
+        if (int rc = probe_level_mask_device(at.c_str(), uint32_t(npx), g->s_mult.p, level, g->s_mask.p, stream)) return rc;
+        if (int rc = region_select_launch(w, h, 0, 1, g->s_mask.p, g->s_select.p, 0, 0, w, h, stream)) return rc;
+        if (int rc = enqueue_quad_list(g->s_select.p, n_blocks, g->s_scan.p, g->s_quads.p, stream)) return rc;
+        uint32_t count[2] = {0, 0}; // listed blocks, selected pixels
+        HIP_TRY_AS(at, hipMemcpy(count, quad_list_totals(g->s_scan.p, n_blocks), sizeof(count), hipMemcpyDeviceToHost));
+        if (count[0] == 0) continue;
+        ListPass list;
+        list.quads = g->s_quads.p;
+        list.n_quads = count[0];
+        rttnw_params pl = *p;
+        pl.spp = level * p->spp;
+        if (int rc = render_tiles_any(s, s->device, cam, &pl, g->s_sums.p, stream, nullptr, false, false, &list)) return rc;
+        if (int rc = probe_scatter_device(at.c_str(), p->precision, g->s_sums.p, g->s_quads.p, list.n_quads, g->packed.p, stream)) return rc;
+        traced += uint64_t(count[1]) * pl.spp;
+    }
+    HIP_TRY_AS(at, hipEventRecord(g->ev3.get(), stream));
+    return RTTNW_OK;
+}
+
 // Steps 0 - 5 of the contract behind a frame whose features are in maps[cur ^ 1]: ingest (`packed`: the trace's tiles of `precision`, or the
 // uploaded doubles), accumulate, estimate, filter with the tap, emit — enqueued between the handle's events —, the one wait, the outputs.
 int svgf_run(const char* call, ::rttnw_svgf* g, const rttnw_camera_desc* cam, bool packed, uint32_t precision, const rttnw_svgf_out* out) {
@@ -137,12 +199,7 @@ int svgf_run(const char* call, ::rttnw_svgf* g, const rttnw_camera_desc* cam, bo
     const double* pmaps = g->maps[old].p;
     const bool feedback = g->q.feedback_iterations > 0 && g->has_state;
 
-    const CameraRec<double> rec = camera_of<double>(cam);
-    CameraRec<double> prev_rec = {};
-    if (g->has_state) prev_rec = camera_of<double>(&g->cam);
-    const bool same_camera = g->has_state && std::memcmp(cam, &g->cam, sizeof(rttnw_camera_desc)) == 0;
-    const TemporalParams prm = temporal_params(rec, g->has_state ? &prev_rec : nullptr, same_camera, g->q.t.max_history, g->q.t.depth_tolerance,
-                                               g->q.t.normal_min, false);
+    const TemporalParams prm = svgf_temporal_params(g, cam);
     rttnw_tile_layout L;
     fill_layout(w, h, 1, L);
 
@@ -321,6 +378,61 @@ int rttnw_svgf_clipped(rttnw_svgf* q, uint8_t* out_clipped) {
     return RTTNW_OK;
 }
 
+int rttnw_svgf_set_sampling(rttnw_svgf* q, const rttnw_sampling_params* a) {
+    const char* const call = "svgf_set_sampling";
+    if (a)
+        if (int rc = rt::sampling_refuse_params(call, a)) return rc;
+    if (!q) return rt::refuse(call, "q is NULL");
+    if (!a) {
+        q->sampling = false;
+        return RTTNW_OK;
+    }
+    if (!q->s_mult.p) { // the maps, the list and the list passes' sums, once: frame calls still allocate none of the handle's buffers
+        using rt::set_last_error;
+        const std::string at = std::string(call) + ": ";
+        const size_t npx = size_t(q->width) * q->height;
+        rttnw_tile_layout L;
+        rt::fill_layout(q->width, q->height, 1, L);
+        const uint32_t n_blocks = L.n_tiles * 16u;
+        rt::DeviceGuard restore;
+        HIP_TRY_AS(at, hipSetDevice(q->device));
+        HIP_TRY_AS(at, q->s_len.alloc(npx));
+        HIP_TRY_AS(at, q->s_mask.alloc(npx));
+        HIP_TRY_AS(at, q->s_select.alloc(L.pixels_per_rank));
+        HIP_TRY_AS(at, q->s_quads.alloc(n_blocks));
+        HIP_TRY_AS(at, q->s_scan.alloc(rt::quad_scan_words(n_blocks)));
+        HIP_TRY_AS(at, q->s_sums.alloc(size_t(L.pixels_per_rank) * 4 * sizeof(double)));
+        HIP_TRY_AS(at, rt::create_event(q->ev2));
+        HIP_TRY_AS(at, rt::create_event(q->ev3));
+        HIP_TRY_AS(at, q->s_mult.alloc(npx)); // (last: its presence says that all of them are there)
+    }
+    q->sprm = rt::sampling_params(a->boost, a->fill);
+    q->sampling = true;
+    return RTTNW_OK;
+}
+
+int rttnw_svgf_samples(rttnw_svgf* q, uint32_t* out_spp, double* out_length) {
+    const char* const call = "svgf_samples";
+    if (!q) return rt::refuse(call, "q is NULL");
+    const size_t npx = size_t(q->width) * q->height;
+    if (!q->samples_live) { // before any frame call (last_spp is 0), or after one without sampling: every pixel got p->spp, no length was probed
+        if (out_spp) std::fill(out_spp, out_spp + npx, q->last_spp);
+        if (out_length) std::fill(out_length, out_length + npx, 0.0);
+        return RTTNW_OK;
+    }
+    using rt::set_last_error;
+    const std::string at = std::string(call) + ": ";
+    rt::DeviceGuard restore;
+    HIP_TRY_AS(at, hipSetDevice(q->device));
+    if (out_spp) {
+        std::vector<uint8_t> m(npx);
+        HIP_TRY_AS(at, hipMemcpy(m.data(), q->s_mult.p, npx, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < npx; ++i) out_spp[i] = uint32_t(m[i]) * q->last_spp;
+    }
+    if (out_length) HIP_TRY_AS(at, hipMemcpy(out_length, q->s_len.p, npx * sizeof(double), hipMemcpyDeviceToHost));
+    return RTTNW_OK;
+}
+
 int rttnw_svgf_push(rttnw_svgf* q, const rttnw_camera_desc* cam, const double* linear_rgb, const double* albedo, const double* normal, const double* depth,
                     const double* alpha, const rttnw_svgf_out* out) {
     const char* const call = "svgf_push";
@@ -351,19 +463,37 @@ int rttnw_svgf_frame(rttnw_svgf* q, rttnw_scene* s, const rttnw_camera_desc* cam
     if (!q) return rt::refuse(call, "q is NULL");
     if (!s) return rt::refuse(call, "s is NULL");
     if (p->width != q->width || p->height != q->height) return rt::refuse(call, "p->width and p->height must equal the handle's");
+    // with sampling a pixel may get boost * p->spp samples: that product must be a spp rttnw_render takes
+    const bool boosted = q->sampling; // (a boost of 1 still probes: rttnw_svgf_samples returns the lengths)
+    if (boosted && uint64_t(q->sprm.boost) * p->spp > 0xFFFFFFFFull) return rt::refuse(call, "p->spp times the handle's boost (rttnw_svgf_set_sampling) is more than a render's spp can be");
     if (int rc = rt::validate(s, cam, p)) return rc;
     if (s->device->device != q->device) return rt::refuse(call, "s: the scene was committed on another device than the handle's");
     rttnw_params pf = *p;
     pf.spp = q->q.feature_spp ? q->q.feature_spp : (p->spp < 16u ? p->spp : 16u);
     rt::DeviceGuard restore;
-    if (int rc = rt::render_tiles_any(s, s->device, cam, p, q->packed.p, nullptr, stats)) return rc;
-    if (int rc = RT_BY_PRECISION(p->precision, render_features_device_t, s, cam, &pf, q->maps[q->cur ^ 1].p, nullptr)) return rc;
+    uint64_t boost_samples = 0;
+    if (!boosted) {
+        if (int rc = rt::render_tiles_any(s, s->device, cam, p, q->packed.p, nullptr, stats)) return rc;
+        if (int rc = RT_BY_PRECISION(p->precision, render_features_device_t, s, cam, &pf, q->maps[q->cur ^ 1].p, nullptr)) return rc;
+    } else {
+        // the feature pass first — it does not depend on the trace —, then the plain trace of every pixel, then the boosted levels over it
+        if (int rc = RT_BY_PRECISION(p->precision, render_features_device_t, s, cam, &pf, q->maps[q->cur ^ 1].p, nullptr)) return rc;
+        if (int rc = rt::render_tiles_any(s, s->device, cam, p, q->packed.p, nullptr, stats)) return rc;
+        if (int rc = rt::svgf_boost_levels(call, q, s, cam, p, boost_samples)) return rc;
+    }
+    q->samples_live = boosted;
+    q->last_spp = p->spp;
     if (stats) {
         const uint64_t feature_rays = uint64_t(p->width) * p->height * pf.spp;
-        stats->samples += feature_rays;
+        stats->samples += feature_rays + boost_samples;
         stats->rays += feature_rays;
     }
-    return rt::svgf_run(call, q, cam, true, p->precision, out);
+    const int rc = rt::svgf_run(call, q, cam, true, p->precision, out);
+    if (rc == RTTNW_OK && boosted && stats) { // (svgf_run waited for the stream: both events are reached)
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, q->ev2.get(), q->ev3.get()) == hipSuccess) stats->kernel_ms += ms;
+    }
+    return rc;
 }
 
 } // extern "C"

@@ -516,6 +516,57 @@ def temporal_clamp(linear, features, cam, history=None, gamma=0.0, clamp_radius=
     return out
 
 
+PROBE_OUTPUTS = ("length", "prev_xy", "multiplier")
+
+
+def _sampling_params(who, boost, fill):
+    """`rttnw_sampling_params` behind its ranges."""
+    if int(boost) not in (0, 1, 2, 4, 8):
+        raise ValueError("%s: boost must be 1, 2, 4 or 8 (0: the default, 8), got %r" % (who, boost))
+    if not (fill == 0.0 or 1.0 <= fill < float("inf")):
+        raise ValueError("%s: fill must be finite and at least 1 (0: the default, 8.0), got %r" % (who, fill))
+    return abi.Sampling(boost=int(boost), reserved0=0, fill=float(fill))
+
+
+def temporal_probe(features, cam, history=None, boost=0, fill=0.0, max_history=0, depth_tolerance=0.0, normal_min=0.0, want_ms=False):
+    """`rttnw_temporal_probe`: where each pixel's history is and how long, from the frame's `features` and camera and the previous call's result
+    alone — no colour —, and how many times the frame's samples the pixel should get: the largest of 1, 2, 4, 8 that is at most `boost` and at
+    most floor(`fill` / (length + 1)); 1 on a miss.  `history`: a dict with "length", "features" and "cam" (what `temporal_accumulate` and its
+    kin return), or None: no history, every hit pixel gets the first frame's multiplier.  A parameter of 0 is the library default (boost 8,
+    fill 8.0, `temporal_accumulate`'s three).  Returns a dict: "length" HxW (the reprojected history length, 0 where there is none), "prev_xy"
+    HxWx2 (`temporal_accumulate`'s), "multiplier" HxW u8 — and "ms", the kernel's time, with `want_ms`."""
+    who = "temporal_probe"
+    f = {k: np.ascontiguousarray(features[k], dtype=np.float64) for k in ("normal", "depth", "alpha")}
+    if f["depth"].ndim != 2:
+        raise ValueError("%s: the depth map is HxW, got %s" % (who, f["depth"].shape))
+    h, w = f["depth"].shape
+    _temporal_frame(who, np.zeros((1, 1, 3)), max_history, depth_tolerance, normal_min)
+    a = _sampling_params(who, boost, fill)
+    prev = [None] * 4
+    prev_cam = None
+    if history is not None:
+        missing = [k for k in ("length", "features", "cam") if history.get(k) is None]
+        if missing:
+            raise ValueError("%s: the history is a previous call's result (it lacks %s)" % (who, ", ".join(missing)))
+        pf = history["features"]
+        prev = [np.ascontiguousarray(x, dtype=np.float64) for x in (history["length"], pf["normal"], pf["depth"], pf["alpha"])]
+        prev_cam = history["cam"]
+    for arr, shape in ((f["normal"], (h, w, 3)), (f["alpha"], (h, w)), (prev[0], (h, w)), (prev[1], (h, w, 3)), (prev[2], (h, w)), (prev[3], (h, w))):
+        if arr is not None and arr.shape != shape:
+            raise ValueError("%s: every array is of one %dx%d frame, got %s where %s was expected" % (who, w, h, arr.shape, shape))
+    b = library.product()
+    out = {"length": np.zeros((h, w)), "prev_xy": np.zeros((h, w, 2)), "multiplier": np.zeros((h, w), dtype=np.uint8)}
+    t = abi.Temporal(max_history=int(max_history), reserved0=0, depth_tolerance=depth_tolerance, normal_min=normal_min)
+    ms = C.c_double(0.0)
+    rc = b.temporal_probe(w, h, C.byref(cam), None if prev_cam is None else C.byref(prev_cam), f["normal"].ctypes.data, f["depth"].ctypes.data,
+                          f["alpha"].ctypes.data, *[_ptr(x) for x in prev], C.byref(t), C.byref(a), *[_ptr(out[name]) for name in PROBE_OUTPUTS],
+                          C.byref(ms))
+    check(rc, b, "rttnw_temporal_probe")
+    if want_ms:
+        out["ms"] = ms.value
+    return out
+
+
 def orbit_cameras(cam, frames, step_degrees):
     """The cameras of an orbit of `frames` frames that ENDS at `cam`: frame k's lookfrom is `cam`'s, turned about the axis through lookat along
     view_up by (k - (frames - 1)) * step_degrees degrees (Rodrigues' formula); everything else is `cam`'s."""
@@ -651,6 +702,25 @@ class SvgfSequence:
         check(self._b.svgf_clipped(self.handle, out.ctypes.data), self._b, "rttnw_svgf_clipped")
         return out
 
+    def set_sampling(self, boost=0, fill=0.0):
+        """`rttnw_svgf_set_sampling`: from the next `frame` call on, pixels whose reprojected history is thin are traced with up to `boost` times
+        the frame's samples, as `temporal_probe` rules (a 0: its default, 8 and 8.0).  The history is kept.  Such a call may consume sample
+        indices up to sample_begin + boost * spp: advance `sample_begin` by that much a frame.  Returns the boost in force."""
+        a = _sampling_params("SvgfSequence.set_sampling", boost, fill)
+        check(self._b.svgf_set_sampling(self.handle, C.byref(a)), self._b, "rttnw_svgf_set_sampling")
+        return a.boost or 8
+
+    def clear_sampling(self):
+        """Sampling off again, from the next call on: the default."""
+        check(self._b.svgf_set_sampling(self.handle, None), self._b, "rttnw_svgf_set_sampling")
+
+    def samples(self):
+        """`rttnw_svgf_samples`: (HxW u32, the samples each pixel of the last `frame` call was given; HxW f64, the reprojected history length the
+        choice was made on).  Before any `frame` call both are 0; after one without sampling the first is that call's spp, the second 0."""
+        spp, length = np.zeros((self.height, self.width), dtype=np.uint32), np.zeros((self.height, self.width))
+        check(self._b.svgf_samples(self.handle, spp.ctypes.data, length.ctypes.data), self._b, "rttnw_svgf_samples")
+        return spp, length
+
     def _outputs(self, want):
         """(dict of zeroed arrays, the rttnw_svgf_out over them, the image_ms cell); `want` None: everything, () : nothing (no struct at all)."""
         names = tuple(SVGF_ARRAYS) if want is None else tuple(want)
@@ -690,23 +760,34 @@ class SvgfSequence:
 
 def render_sequence_device(scene, cams, params, feedback=0, demodulate=False, iterations=5, max_history=0, depth_tolerance=0.0, normal_min=0.0,
                            on_frame=None, want=("linear_rgb", "rgba8", "raw_rgb", "length", "accumulated_rgb", "moment2_rgb", "variance_rgb", "prev_xy",
-                                                "albedo", "normal", "depth", "alpha"), clamp=None):
+                                                "albedo", "normal", "depth", "alpha"), clamp=None, sampling=None, want_spp=False):
     """`render_sequence(..., variance=True, denoise=True)` on the device: one `SvgfSequence`, one `frame` call per camera, frame k at
     `sample_begin = params.sample_begin + k * params.spp`.  With `feedback` 0 and without `demodulate` the images are that function's, bit for
     bit.  Returns the same list of dicts — "linear", "rgba8", "raw", "length", "accumulated" ("linear", "rgba8" absent, "moment2", "variance",
     "length", "prev_xy"), "features", "cam", "stats" — and "image_ms", the device time behind the trace and the feature pass.  An entry of a
     frame is None where `want` leaves its output out.  `clamp` (a number): the handle clips its history with that gamma (`SvgfSequence.set_clamp`)
-    and each frame carries "clipped", the call's map; None, the default, leaves the frames as they are."""
+    and each frame carries "clipped", the call's map; None, the default, leaves the frames as they are.  `sampling` (a boost, or a pair
+    (boost, fill); a 0: the default, 8 and 8.0): the handle gives pixels with a thin history up to boost times the frame's samples
+    (`SvgfSequence.set_sampling`), and frame k starts at `sample_begin + k * boost * spp`; with `want_spp` each frame carries "spp" (HxW u32, the
+    samples each pixel got) and "probe_length" (the reprojected history length behind the choice)."""
     if clamp is not None and not float(clamp) >= 0.0:
         raise ValueError("render_sequence_device: clamp is the gamma of temporal_clamp, at least 0 (0: the default, 1.0), got %r" % (clamp,))
+    if sampling is not None:
+        sampling = tuple(sampling) if isinstance(sampling, (tuple, list)) else (sampling, 0.0)
+        if len(sampling) != 2:
+            raise ValueError("render_sequence_device: sampling is a boost or a pair (boost, fill), got %r" % (sampling,))
+        _sampling_params("render_sequence_device", *sampling)
+    stride = 1
     frames = []
     with SvgfSequence(params.width, params.height, feedback=feedback, demodulate=demodulate, iterations=iterations, max_history=max_history,
                       depth_tolerance=depth_tolerance, normal_min=normal_min) as seq:
         if clamp is not None:
             seq.set_clamp(gamma=float(clamp))
+        if sampling is not None:
+            stride = seq.set_sampling(boost=sampling[0], fill=sampling[1])
         for k, cam in enumerate(cams):
             p = copy.copy(params)
-            p.sample_begin = params.sample_begin + k * params.spp
+            p.sample_begin = params.sample_begin + k * stride * params.spp
             got = seq.frame(scene, cam, p, want=want)
             features = {name: got.get(name) for name in ("albedo", "normal", "depth", "alpha")}
             accumulated = {"linear": got.get("accumulated_rgb"), "moment2": got.get("moment2_rgb"), "variance": got.get("variance_rgb"),
@@ -715,6 +796,8 @@ def render_sequence_device(scene, cams, params, feedback=0, demodulate=False, it
                      "accumulated": accumulated, "features": features, "cam": cam, "stats": got["stats"], "image_ms": got["image_ms"]}
             if clamp is not None:
                 frame["clipped"] = seq.clipped()
+            if want_spp:
+                frame["spp"], frame["probe_length"] = seq.samples()
             frames.append(frame)
             if on_frame is not None:
                 on_frame(k, frame)
