@@ -122,6 +122,21 @@ pub struct rttnw_nlm_params {
     pub reserved1: u32,
 }
 
+/// The parameters of `rttnw_denoise_regress` (include/rttnw_hip.h states the contract); a radius, `k` or `ridge` of 0 is the library default;
+/// `features` holds the bits 1 (albedo), 2 (normal), 4 (depth) and has no default: 0 means no regressor.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rttnw_regress_params {
+    pub search_radius: u32,
+    pub patch_radius: u32,
+    pub k: f64,
+    pub ridge: f64,
+    pub features: u32,
+    pub demodulate: u32,
+    pub reserved0: u32,
+    pub reserved1: u32,
+}
+
 /// The parameters of `rttnw_denoise_select` (include/rttnw_hip.h states the contract); a radius of 0 is the library default, and
 /// `use_default_margin != 0` takes the default margin (0.01) and ignores `margin`: a margin of 0 is a margin of 0.
 #[repr(C)]
@@ -344,6 +359,7 @@ extern "C" {
     pub fn rttnw_denoise(width: u32, height: u32, linear_rgb: *const f64, variance_rgb: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, d: *const rttnw_denoise_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_denoise_nlm(width: u32, height: u32, half_a: *const f64, half_b: *const f64, var_a: *const f64, var_b: *const f64, d: *const rttnw_nlm_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_half_a: *mut f64, out_half_b: *mut f64, out_error_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_denoise_select(width: u32, height: u32, half_a: *const f64, half_b: *const f64, var_a: *const f64, var_b: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, dn: *const rttnw_denoise_params, nl: *const rttnw_nlm_params, sel: *const rttnw_select_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_blend: *mut f64, out_feature_rgb: *mut f64, out_nlm_rgb: *mut f64, out_error_rgb: *mut f64, kernel_ms: *mut f64) -> c_int;
+    pub fn rttnw_denoise_regress(width: u32, height: u32, half_a: *const f64, half_b: *const f64, var_a: *const f64, var_b: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, g: *const rttnw_regress_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_half_a: *mut f64, out_half_b: *mut f64, out_error_rgb: *mut f64, out_fit: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_temporal_accumulate(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, linear_rgb: *const f64, variance_rgb: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, prev_linear_rgb: *const f64, prev_variance_rgb: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_variance_rgb: *mut f64, out_length: *mut f64, out_prev_xy: *mut f64, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_temporal_clamp(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, linear_rgb: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, prev_linear_rgb: *const f64, prev_moment2_rgb: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, v: *const rttnw_variance_params, k: *const rttnw_clamp_params, out_linear_rgb: *mut f64, out_rgba8: *mut u8, out_moment2_rgb: *mut f64, out_length: *mut f64, out_prev_xy: *mut f64, out_variance_rgb: *mut f64, out_mean_rgb: *mut f64, out_sd_rgb: *mut f64, out_clipped: *mut u8, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_svgf_set_clamp(q: *mut rttnw_svgf, k: *const rttnw_clamp_params) -> c_int;

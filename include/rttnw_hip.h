@@ -45,8 +45,8 @@ extern "C" {
                              *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select,
                              *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised, rttnw_denoise_nlm,
                              *  rttnw_denoise_select, rttnw_temporal_accumulate, rttnw_temporal_variance, the rttnw_svgf_create family, rttnw_temporal_clamp,
-                             *  rttnw_svgf_set_clamp, rttnw_svgf_clipped, rttnw_temporal_probe, rttnw_svgf_set_sampling and rttnw_svgf_samples came
-                             *  later, without a version bump: a caller detects each by its symbol) */
+                             *  rttnw_svgf_set_clamp, rttnw_svgf_clipped, rttnw_temporal_probe, rttnw_svgf_set_sampling, rttnw_svgf_samples and
+                             *  rttnw_denoise_regress came later, without a version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -477,6 +477,73 @@ int rttnw_denoise_select(uint32_t width, uint32_t height, const double* half_a, 
                          const rttnw_denoise_params* dn, const rttnw_nlm_params* nl, const rttnw_select_params* sel,
                          double* out_linear_rgb, uint8_t* out_rgba8, double* out_blend, double* out_feature_rgb, double* out_nlm_rgb,
                          double* out_error_rgb, double* kernel_ms);
+
+/* A third spatial filter, which joins the two above: weighted first-order regression of colour on the first-hit features (Moon, Carr and Yoon
+ * 2014, "Adaptive rendering based on weighted local regression"; Bitterli et al. 2016, "Nonlinearly weighted first-order regression for
+ * denoising Monte Carlo renderings").  The weights are rttnw_denoise_nlm's, cross-filtered, so no weight depends on the noise it averages; but
+ * where non-local means fits a CONSTANT to the candidates of a pixel, this fits a local linear model of colour in the features (albedo,
+ * normal, depth of rttnw_render_features) and keeps only the intercept.  A constant fit blurs whatever the features explain — a texture, a
+ * shading gradient across a curved surface, a depth ramp; the first-order fit does not.  With demodulation the colour is divided by the albedo
+ * before the weights are measured, as rttnw_denoise does.  The calling convention is rttnw_denoise_nlm's: host arrays in and out (row-major,
+ * top row first), blocking, on the current device, no scene handle; no CPU fallback: RTTNW_ERR_HIP without a device.  Everything is double;
+ * every output is optional.  half_a, half_b, var_a, var_b as for rttnw_denoise_nlm; albedo, normal w*h*3, depth, alpha w*h.
+ *
+ * Arithmetic rules.  Every product is rounded on its own (none is fused into a sum), every sum starts from 0.0 and adds its terms in the order
+ *   stated, and only + - * /, sqrt and comparisons are used.  So the device code, a host build of the same header
+ *   (rttnw_amd/csrc/regress.hpp) and a restatement in numpy give the same bits.
+ * 1. Demodulation (demodulate != 0; needs albedo and alpha).  For a pixel with alpha != 0 and a channel with albedo > 1e-3 (rttnw_denoise's
+ *    rule and constant) a and b are divided by the albedo, and given variances by albedo * albedo (the product rounded once).  The pair variance,
+ *    when no variances are given, is formed from the demodulated halves.  Steps 2 to 5 run on these arrays.  At the end a' and b' are
+ *    multiplied by the centre's albedo in the same channels, before step 6.
+ * 2. Weights.  w_B(p, o) and w_A(p, o) are exactly rttnw_denoise_nlm's, with its coordinates, clamping and pair variance unchanged; the offsets
+ *    run row-major (oy outer, ox inner) and the centre weight is 1.
+ * 3. Regressors.  The pixel's feature mask m is `features`, or 0 when the centre's alpha == 0.  With m == 0 no feature array is read for that
+ *    pixel and no candidate is dropped.  With m != 0 a candidate whose clamped pixel has alpha == 0 is dropped: it enters no sum.  x(q) holds
+ *    the selected components in the order albedo r g b, normal x y z, depth; each is feature(q) - feature(p) as stored, except the depth
+ *    component, which is (z_q - z_p) / z_p with z = depth / alpha.  d is the number of components: 0, 1, 3, 4, 6 or 7.
+ * 4. Sums, over the kept candidates in offset order, y the other half's colour at the candidate (the half being fitted), c = 0 .. 2:
+ *      s = s + w;  t_c = t_c + w * y_c                      (rttnw_denoise_nlm's two sums)
+ *      wx_i = w * x_i, formed once per candidate and component;  b_i = b_i + wx_i;  A_ij = A_ij + wx_i * x_j for j <= i;  C_ic = C_ic + wx_i * y_c
+ *    After the loop: A_ii = A_ii + ridge * s.
+ * 5. Solve: the features first, the constant eliminated last.  Cholesky row by row: for j = 0 .. d-1 and i = 0 .. j: acc = A_ji, then
+ *    acc = acc - L_jk * L_ik for k = 0 .. i-1 in order; when i < j: L_ji = acc / L_ii; when i == j: the pivot test acc > 0 must hold, and
+ *    L_jj = sqrt(acc).  Forward substitution, k in order: u_j = (b_j - sum_k L_jk u_k) / L_jj, and G_jc likewise from C_jc.
+ *    uu = sum_j u_j * u_j, uG_c = sum_j u_j * G_jc, den = s - uu.  The fitted value at p is (t_c - uG_c) / den.
+ *    Fallback.  The pixel falls back when a pivot test is false (this includes a NaN) or when den >= 0.5 is false.  In exact arithmetic
+ *    den >= 1 (the centre has weight 1 and x = 0; the rest is Cauchy-Schwarz), so a smaller den means the solve lost its accuracy.  The
+ *    fallback is the zero-order value t_c / s, over the same kept candidates.  With d == 0 the formulas reduce to t_c / s exactly:
+ *    uu = uG = 0.0.
+ * 6. Outputs.  a' uses w_B and regresses half a; b' uses w_A and regresses half b.  out_half_a and out_half_b w*h*3 hold a' and b';
+ *    out_linear_rgb w*h*3 = (a' + b') * 0.5, out_rgba8 w*h*4 of it after main.rs:219-225, alpha 255, and out_error_rgb w*h*3 =
+ *    (a' - b')^2 * 0.25, as rttnw_denoise_nlm forms them; out_fit w*h holds 0.0, 1.0 or 2.0: how many of the two directions used the
+ *    first-order value; kernel_ms: device time of the call's kernels.
+ * 7. Properties.  (1) With features == 0 and demodulate == 0 every output of rttnw_denoise_nlm is reproduced bit for bit, and the four feature
+ *    arrays may be NULL.  (2) Swapping (half_a, var_a) with (half_b, var_b) swaps out_half_a with out_half_b and leaves the other outputs
+ *    bit-identical.  (3) A pixel's outputs depend on the inputs within r + f + 1 pixels of it only.  (4) Non-finite inputs are not
+ *    special-cased beyond the two tests of step 5.
+ * Parameters.  search_radius, patch_radius and k as rttnw_nlm_params (0 = 7, 3, 0.7).  ridge 0 = the library default, 1e-1 (DESIGN.md
+ *   section 10b has the sweep it was taken from).  features has no default: 0 is meaningful.
+ * Refusals, before the device is touched, in this order, each message naming denoise_regress and the argument: RTTNW_ERR_INVALID for
+ *   everything rttnw_denoise_nlm refuses — a NULL half_a or half_b — and a NULL g; exactly one of var_a / var_b; width * height == 0;
+ *   search_radius > 16; patch_radius > 4; a negative or NaN k; features > 7; a negative or NaN ridge; a non-zero reserved field;
+ *   features != 0 with a NULL array among those it selects — alpha whenever features != 0, albedo with bit 1, normal with bit 2, depth with
+ *   bit 4; demodulate != 0 with a NULL albedo or alpha.
+ * Out of scope: offering this filter to rttnw_denoise_select as a third candidate, prefiltering the features, a second-order or
+ *   per-channel-bandwidth fit, steering the adaptive rounds by out_error_rgb or out_fit, the SVGF handle, a node-wide form, the native rttnw
+ *   program. */
+struct rttnw_regress_params {
+    uint32_t search_radius, patch_radius; /* r, f: as rttnw_nlm_params; 0 = 7, 3; r <= 16, f <= 4 */
+    double k;                             /* as rttnw_nlm_params; 0 = 0.7 */
+    double ridge;                         /* lambda; 0 = the library default; negative or NaN refused */
+    uint32_t features;                    /* bits: 1 albedo (3 regressors), 2 normal (3), 4 depth (1); 0 .. 7, no default: 0 is meaningful */
+    uint32_t demodulate;                  /* != 0: filter colour / albedo */
+    uint32_t reserved0, reserved1;        /* must be 0 */
+};                                        /* 40 bytes, offsets 0 4 8 16 24 28 32 36 */
+typedef struct rttnw_regress_params rttnw_regress_params;
+int rttnw_denoise_regress(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b,
+                          const double* albedo, const double* normal, const double* depth, const double* alpha, const rttnw_regress_params* g,
+                          double* out_linear_rgb, uint8_t* out_rgba8, double* out_half_a, double* out_half_b, double* out_error_rgb,
+                          double* out_fit, double* kernel_ms);
 
 /* Temporal accumulation: this frame blended with the previous call's result, fetched from where each pixel's surface point was in the previous
  * frame.  The scene is static and the camera moves (a turntable, a fly-through), so the point behind a pixel was, almost always, seen by the

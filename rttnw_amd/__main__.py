@@ -45,13 +45,20 @@ each half with rttnw_denoise and with non-local means, and takes per pixel the f
 must win by (-2 .. 2; without the flag the library default, 0.01); FILE receives the blend weight as a grey PNG (white: non-local means).
 --denoise-iterations and the --nlm- flags set the two filters.  --spp must be even.  It does not combine with --noise, --denoise,
 --denoise-nlm, --features, --devices, --window or --passes.
+--denoise-regress [--ridge X] [--regress-features anz] [--no-demodulate] [--fit-map FILE] renders the same two halves and the first-hit features of
+min(spp, 16) samples and fits, per pixel, a linear model of colour in the features under non-local means' weights, keeping its intercept
+(rttnw_denoise_regress): what the features explain — a texture, a shading gradient, a depth ramp — is not blurred.  --regress-features takes the
+letters of the regressors (a albedo, n normal, z depth; default anz; "none" for no regressor), X is the ridge (0: the library default),
+--no-demodulate filters colour in place of colour / albedo, FILE receives the fit count as a grey PNG (white: both directions used the first-order
+fit).  The --nlm- flags set the weights.  --spp must be even.  It does not combine with --noise, --denoise, --denoise-nlm, --denoise-select,
+--features, --devices, --window or --passes.
 --orbit K [--orbit-step DEG] [--temporal] [--denoise] renders K frames of --spp samples each from a camera that turns about the axis through
 lookat along view_up, DEG degrees a frame (default 1.0), and ENDS at the scene's own camera: frame k's lookfrom is the scene's, turned by
 (k - (K - 1)) * DEG degrees.  Frame k takes its samples at sample_begin = k * spp, so the frames are independent estimates.  With --temporal
 every frame is blended with the previous result, fetched from where each pixel's surface point was in the previous frame
 (rttnw_temporal_accumulate, guided by first-hit features of min(spp, 16) samples); with --denoise the frame written is rttnw_denoise of it,
 and the history stays unfiltered.  The frames are written as frame_000.png, frame_001.png, ... beside --out.  --orbit does not combine with
---noise, --window, --devices, --denoise-nlm, --denoise-select, --features or --passes; --temporal needs --orbit.
+--noise, --window, --devices, --denoise-nlm, --denoise-select, --denoise-regress, --features or --passes; --temporal needs --orbit.
 --temporal-variance (it implies --temporal and needs --orbit) carries the colour's second moment along the same history and estimates the
 variance of every pixel's accumulated mean (rttnw_temporal_variance: from the two moments where the history counts 4 frames, from a 7x7 window
 guided by normal and depth elsewhere); with --denoise that variance is rttnw_denoise's colour stop: accumulate, estimate, filter.
@@ -94,6 +101,17 @@ def parse_window(text):
     return (x0, y0, x1, y1) if x0 < x1 and y0 < y1 else None
 
 
+def regress_mask(text):
+    """'anz' -> 7: the feature mask of rttnw_denoise_regress from the letters a (albedo, 1), n (normal, 2), z (depth, 4) in any order; 'none' -> 0;
+    None for another letter, a repeated one or an empty string."""
+    if text == "none":
+        return 0
+    bits = {"a": 1, "n": 2, "z": 4}
+    if not text or any(ch not in bits for ch in text) or len(set(text)) != len(text):
+        return None
+    return sum(bits[ch] for ch in text)
+
+
 def parse_devices(text):
     """'0,1,2' -> [0, 1, 2]: 1 to 64 non-negative integers (repeats allowed), or None."""
     parts = text.split(",")
@@ -121,7 +139,7 @@ def refusal(args, refine, devices, window):
           "--refine": args.refine is not None, "--devices": args.devices is not None, "--resume": args.resume is not None,
           "--save-state": args.save_state is not None, "--window": args.window is not None, "--passes": args.passes > 1,
           "--features": args.features is not None, "--denoise": args.denoise, "--denoise-nlm": args.denoise_nlm,
-          "--denoise-select": args.denoise_select, "--orbit": args.orbit is not None}
+          "--denoise-select": args.denoise_select, "--denoise-regress": args.denoise_regress, "--orbit": args.orbit is not None}
     iterations = (0 <= args.denoise_iterations <= 8, "--denoise-iterations must be 0 .. 8")
     state_needs, state_clashes = "only the adaptive render has a state", ("--window", "--passes")
     # in the order they are checked: (flag, why it needs --noise or None, the flags it does not combine with, the reason given for that,
@@ -132,6 +150,10 @@ def refusal(args, refine, devices, window):
                       (args.nlm_k >= 0.0, "--nlm-k must be at least 0 (0: the default, 0.7)")]
     if args.blend_map is not None and not args.denoise_select:
         return "--blend-map needs --denoise-select: only that call has a blend weight"
+    if (args.ridge is not None or args.regress_features is not None or args.no_demodulate or args.fit_map is not None) and not args.denoise_regress:
+        return "--ridge, --regress-features, --no-demodulate and --fit-map need --denoise-regress: only that call has them"
+    if args.regress_features is not None and regress_mask(args.regress_features) is None:
+        return "--regress-features wants letters of a (albedo), n (normal), z (depth), or none; got %r" % args.regress_features
     if args.svgf and not on["--orbit"]:
         return "--svgf needs --orbit: it runs the accumulate, estimate, filter loop over the frames of a sequence"
     if (args.feedback or args.demodulate) and not args.svgf:
@@ -157,7 +179,7 @@ def refusal(args, refine, devices, window):
     if args.temporal and not on["--orbit"]:
         return "--temporal needs --orbit: it accumulates the frames of a sequence"
     rules = [
-        ("--orbit", None, ("--noise", "--window", "--devices", "--denoise-nlm", "--denoise-select", "--features", "--passes"),
+        ("--orbit", None, ("--noise", "--window", "--devices", "--denoise-nlm", "--denoise-select", "--denoise-regress", "--features", "--passes"),
          ": it renders a sequence of plain frames of the whole image, on one GPU", [],
          [(not on["--orbit"] or 1 <= args.orbit <= 1000, "--orbit must be 1 .. 1000 frames"),
           (args.orbit_step == args.orbit_step and abs(args.orbit_step) <= 360.0, "--orbit-step must be -360 .. 360 degrees"), iterations,
@@ -167,6 +189,10 @@ def refusal(args, refine, devices, window):
          [(args.spp == 0 or (args.spp >= 2 and args.spp % 2 == 0), EVEN_SPP % ("--denoise-select", args.spp)),
           (args.select_margin is None or -2.0 <= args.select_margin <= 2.0, "--select-margin must be -2 .. 2 (without it: the default, 0.01)"),
           iterations] + nlm_parameters),
+        ("--denoise-regress", None, ("--noise", "--denoise", "--denoise-nlm", "--denoise-select", "--features", "--devices", "--window", "--passes"),
+         ": it fits two plain half renders of the whole frame to their first-hit features, on one GPU", [],
+         [(args.spp == 0 or (args.spp >= 2 and args.spp % 2 == 0), EVEN_SPP % ("--denoise-regress", args.spp)),
+          (args.ridge is None or args.ridge >= 0.0, "--ridge must be at least 0 (0: the library default)")] + nlm_parameters),
         ("--denoise-nlm", None, ("--noise", "--denoise", "--features", "--devices", "--window", "--passes"),
          ": it filters two plain half renders of the whole frame, on one GPU", [], nlm_parameters),
         ("--guided-budget", "it is the adaptive render under a budget of samples, ranked by the filtered image's noise",
@@ -244,6 +270,14 @@ def main(argv=None):
                     "default 0.01)")
     ap.add_argument("--blend-map", default=None, metavar="FILE", help="selection: also write the blend weight as a grey-scale PNG (white: "
                     "non-local means)")
+    ap.add_argument("--denoise-regress", action="store_true", help="render two halves and the first-hit features and fit colour to the features "
+                    "under non-local means' weights (rttnw_denoise_regress)")
+    ap.add_argument("--ridge", type=float, default=None, metavar="X", help="regression: the ridge (0 or absent: the library default)")
+    ap.add_argument("--regress-features", default=None, metavar="anz", help="regression: the regressors, letters of a (albedo), n (normal), "
+                    "z (depth), or none (default anz)")
+    ap.add_argument("--no-demodulate", action="store_true", help="regression: filter colour, not colour / albedo")
+    ap.add_argument("--fit-map", default=None, metavar="FILE", help="regression: also write the fit count as a grey-scale PNG (white: both "
+                    "directions used the first-order fit)")
     ap.add_argument("--orbit", type=int, default=None, metavar="K", help="render K frames from a camera that turns about lookat and ends at the "
                     "scene's own; writes frame_000.png, ... beside --out")
     ap.add_argument("--orbit-step", type=float, default=1.0, metavar="DEG", help="orbit: degrees per frame (default 1.0)")
@@ -314,9 +348,10 @@ def main(argv=None):
     cam.aspect_ratio = setup.width / setup.height
     p = make_params(w, h, args.spp or setup.spp, background=tuple(setup.background), seed=args.seed,
                     precision={"f32": abi.F32, "f64": abi.F64, "f64strict": abi.F64_STRICT}[args.precision])
-    if args.denoise_select and (p.spp < 2 or p.spp % 2):   # (the scene's own spp: a given --spp was refused above)
-        print(EVEN_SPP % ("--denoise-select", p.spp), file=sys.stderr)
-        return 1
+    for flag, on in (("--denoise-select", args.denoise_select), ("--denoise-regress", args.denoise_regress)):
+        if on and (p.spp < 2 or p.spp % 2):   # (the scene's own spp: a given --spp was refused above)
+            print(EVEN_SPP % (flag, p.spp), file=sys.stderr)
+            return 1
     if window is not None:
         x0, y0, x1, y1 = window
         if x1 > w or y1 > h:
@@ -370,7 +405,7 @@ def main(argv=None):
         return 0
     features = None
     own_filter = args.guided or args.preview is not None or args.guided_budget is not None   # the call's own image is the filtered one
-    if (args.denoise and not own_filter) or args.features or args.denoise_select:
+    if (args.denoise and not own_filter) or args.features or args.denoise_select or args.denoise_regress:
         if args.denoise and args.passes > 1:
             print("--denoise does not combine with --passes", file=sys.stderr)
             return 1
@@ -507,6 +542,21 @@ def main(argv=None):
         print("selection: %.1f %% of the pixels took non-local means, %.1f %% the feature-guided filter, %.1f %% a blend of the two"
               % (100.0 * (out["blend"] == 1.0).mean(), 100.0 * (out["blend"] == 0.0).mean(),
                  100.0 * ((out["blend"] > 0.0) & (out["blend"] < 1.0)).mean()))
+        return 0
+    if args.denoise_regress:
+        (lin_a, _, st_a), (lin_b, _, st_b) = render.render_halves(sc, cam, p)
+        mask = 7 if args.regress_features is None else regress_mask(args.regress_features)
+        out = render.denoise_regress(lin_a, lin_b, None, None, features, mask=mask, demodulate=not args.no_demodulate, ridge=args.ridge or 0.0,
+                                     search_radius=args.nlm_search_radius, patch_radius=args.nlm_patch_radius, k=args.nlm_k, want_ms=True)
+        Image.fromarray(out["rgba8"], "RGBA").save(args.out)
+        if args.fit_map:
+            Image.fromarray((out["fit"] * 127.5).astype(np.uint8), "L").save(args.fit_map)
+        ms = st_a.kernel_ms + st_b.kernel_ms
+        print("%.3fs (two halves of %d spp: trace kernels %.1f ms, %.1f Msamples/s; features %.1f ms; first-order regression %.2f ms)"
+              % (time.time() - t0, p.spp // 2, ms, (st_a.samples + st_b.samples) / max(ms, 1e-9) / 1e3, features["stats"].kernel_ms, out["ms"]))
+        print("regression: features %s, %s; %.1f %% of the pixels used the first-order fit in both directions, %.1f %% in neither"
+              % ("".join(ch for ch, bit in (("a", 1), ("n", 2), ("z", 4)) if mask & bit) or "none", "colour" if args.no_demodulate else "colour / albedo",
+                 100.0 * (out["fit"] == 2.0).mean(), 100.0 * (out["fit"] == 0.0).mean()))
         return 0
     lin, rgba, st = render.render_host(sc, cam, p)
     Image.fromarray(finish(lin, rgba, None), "RGBA").save(args.out)

@@ -66,6 +66,13 @@ class Nlm(C.Structure):
                 ("reserved1", C.c_uint32)]
 
 
+class Regress(C.Structure):
+    """`rttnw_regress_params` — the parameters of `rttnw_denoise_regress` (a radius, `k` or `ridge` of 0: the library default; `features`: bits 1
+    albedo, 2 normal, 4 depth, where 0 means no regressor)."""
+    _fields_ = [("search_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("k", C.c_double), ("ridge", C.c_double), ("features", C.c_uint32),
+                ("demodulate", C.c_uint32), ("reserved0", C.c_uint32), ("reserved1", C.c_uint32)]
+
+
 class Select(C.Structure):
     """`rttnw_select_params` — the parameters of `rttnw_denoise_select` (a radius of 0: the library default; `use_default_margin` != 0: the
     default margin, `margin` ignored)."""
@@ -201,6 +208,7 @@ PRODUCT_FUNCS = [
     ("denoise_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.POINTER(Denoise), C.POINTER(Nlm), C.POINTER(Select), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    ("denoise_regress", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 8 + [C.POINTER(Regress)] + [C.c_void_p] * 6 + [C.POINTER(C.c_double)]),
     ("temporal_accumulate", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(CameraDesc), C.POINTER(CameraDesc)] + [C.c_void_p] * 11 +
                                      [C.POINTER(Temporal)] + [C.c_void_p] * 5 + [C.POINTER(C.c_double)]),
     ("temporal_variance", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(CameraDesc), C.POINTER(CameraDesc)] + [C.c_void_p] * 10 +

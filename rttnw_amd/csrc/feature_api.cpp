@@ -2,8 +2,10 @@
 // rttnw_temporal_variance and rttnw_reconstruct (include/rttnw_hip.h): argument checks, then the feature pass of the requested arithmetic build (feature_kernels.hpp), the
 // device half of the denoiser and of the reconstruction (denoise.hip), the non-local-means filter's (nlm.hip), the per-pixel choice between the two
 // (select.hip), the temporal accumulation (temporal.hip), that accumulation with its variance estimate (variance.hip) or with the history clipped to
-// the frame in front of it (rttnw_temporal_clamp, clamp.hip), or the colour-free probe of that accumulation (rttnw_temporal_probe, probe.hip).  Host code only.
+// the frame in front of it (rttnw_temporal_clamp, clamp.hip), or the colour-free probe of that accumulation (rttnw_temporal_probe, probe.hip); and of
+// rttnw_denoise_regress, whose device half (regress.hip) is declared in regress.hpp: no other unit reads it.  Host code only.
 #include "feature_api.hpp"
+#include "regress.hpp"
 
 namespace rt {
 
@@ -103,6 +105,32 @@ int rttnw_denoise_select(uint32_t width, uint32_t height, const double* half_a, 
                              rt::nlm_params(nl->search_radius, nl->patch_radius, nl->k),
                              rt::select_params(sel->error_radius, sel->blend_radius, sel->margin, sel->use_default_margin != 0), out_linear_rgb, out_rgba8,
                              out_blend, out_feature_rgb, out_nlm_rgb, out_error_rgb, kernel_ms);
+}
+
+int rttnw_denoise_regress(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b,
+                          const double* albedo, const double* normal, const double* depth, const double* alpha, const rttnw_regress_params* g,
+                          double* out_linear_rgb, uint8_t* out_rgba8, double* out_half_a, double* out_half_b, double* out_error_rgb, double* out_fit,
+                          double* kernel_ms) {
+    // what rttnw_denoise_nlm refuses for the arguments the two share, in its order, then the regression's own, in the struct's order
+    const auto refuse = [](const char* what) { rt::set_last_error(std::string("denoise_regress: ") + what); return int(RTTNW_ERR_INVALID); };
+    if (!half_a || !half_b) return refuse("NULL argument (half_a or half_b)");
+    if (!g) return refuse("g is NULL");
+    if ((var_a == nullptr) != (var_b == nullptr)) return refuse("var_a and var_b go together: both or neither");
+    if (uint64_t(width) * height == 0 || uint64_t(width) * height > (1ull << 28)) return refuse("width * height: empty image (or more than 2^28 pixels)");
+    if (g->search_radius > rt::NLM_MAX_SEARCH_RADIUS) return refuse("g->search_radius is more than 16");
+    if (g->patch_radius > rt::NLM_MAX_PATCH_RADIUS) return refuse("g->patch_radius is more than 4");
+    if (!(g->k >= 0.0)) return refuse("g->k must be >= 0 (and not NaN)");
+    if (g->features > rt::REGRESS_ALL) return refuse("g->features is more than 7 (bits: 1 albedo, 2 normal, 4 depth)");
+    if (!(g->ridge >= 0.0)) return refuse("g->ridge must be >= 0 (and not NaN)");
+    if (g->reserved0 != 0 || g->reserved1 != 0) return refuse("g->reserved0 and g->reserved1 must be 0");
+    if (g->features != 0 && !alpha) return refuse("alpha is NULL: g->features != 0 needs it");
+    if ((g->features & rt::REGRESS_ALBEDO) && !albedo) return refuse("albedo is NULL: bit 1 of g->features selects it");
+    if ((g->features & rt::REGRESS_NORMAL) && !normal) return refuse("normal is NULL: bit 2 of g->features selects it");
+    if ((g->features & rt::REGRESS_DEPTH) && !depth) return refuse("depth is NULL: bit 4 of g->features selects it");
+    if (g->demodulate != 0 && (!albedo || !alpha)) return refuse("g->demodulate != 0 needs albedo and alpha");
+    return rt::regress_device(width, height, half_a, half_b, var_a, var_b, albedo, normal, depth, alpha,
+                              rt::regress_params(g->search_radius, g->patch_radius, g->k, g->ridge, g->features, g->demodulate), out_linear_rgb,
+                              out_rgba8, out_half_a, out_half_b, out_error_rgb, out_fit, kernel_ms);
 }
 
 int rttnw_temporal_accumulate(uint32_t width, uint32_t height, const rttnw_camera_desc* cam, const rttnw_camera_desc* prev_cam, const double* linear_rgb,

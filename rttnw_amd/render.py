@@ -295,6 +295,46 @@ def denoise_nlm(half_a, half_b, var_a=None, var_b=None, search_radius=0, patch_r
     return out
 
 
+REGRESS_OUTPUTS = ("linear", "rgba8", "half_a", "half_b", "error", "fit")
+
+
+def denoise_regress(half_a, half_b, var_a=None, var_b=None, features=None, *, mask=7, demodulate=True, ridge=0.0, search_radius=0, patch_radius=0,
+                    k=0.0, want_ms=False):
+    """`rttnw_denoise_regress`: first-order regression of colour on the first-hit features, weighted by `denoise_nlm`'s cross-filtered weights,
+    over the two half-buffers `render_halves` returns.  `features` is what `render_features` returns (it may be None with `mask` 0 and
+    `demodulate` False: the call is then `denoise_nlm`, bit for bit); `mask` selects the regressors (bits: 1 albedo, 2 normal, 4 depth),
+    `demodulate` filters colour / albedo, `ridge` 0 is the library default; the other parameters are `denoise_nlm`'s.  Returns `denoise_nlm`'s dict
+    plus "fit" HxW (0, 1 or 2: how many of the two directions used the first-order value) — and "ms", the device time, with `want_ms`."""
+    b = library.product()
+    a_, b_ = np.ascontiguousarray(half_a, dtype=np.float64), np.ascontiguousarray(half_b, dtype=np.float64)
+    h, w = a_.shape[:2]
+    if (var_a is None) != (var_b is None):
+        raise ValueError("denoise_regress: var_a and var_b go together: both or neither")
+    va = None if var_a is None else np.ascontiguousarray(var_a, dtype=np.float64)
+    vb = None if var_b is None else np.ascontiguousarray(var_b, dtype=np.float64)
+    for arr in (a_, b_, va, vb):
+        if arr is not None and arr.shape != (h, w, 3):
+            raise ValueError("denoise_regress: every half and variance is HxWx3 of one frame, got %s beside %s" % (arr.shape, (h, w, 3)))
+    if not 0 <= int(mask) <= 7:
+        raise ValueError("denoise_regress: mask must be 0 .. 7 (bits: 1 albedo, 2 normal, 4 depth), got %r" % (mask,))
+    if not ridge >= 0.0:
+        raise ValueError("denoise_regress: ridge must be at least 0 (0: the library default), got %r" % (ridge,))
+    if features is None and (mask or demodulate):
+        raise ValueError("denoise_regress: a mask other than 0 and demodulate need features (what render_features returns)")
+    f = {name: None for name in ("albedo", "normal", "depth", "alpha")} if features is None else _feature_arrays(features, h, w)
+    out = {"linear": np.zeros((h, w, 3)), "rgba8": np.zeros((h, w, 4), dtype=np.uint8), "half_a": np.zeros((h, w, 3)),
+           "half_b": np.zeros((h, w, 3)), "error": np.zeros((h, w, 3)), "fit": np.zeros((h, w))}
+    g = abi.Regress(search_radius=search_radius, patch_radius=patch_radius, k=k, ridge=ridge, features=int(mask), demodulate=1 if demodulate else 0,
+                    reserved0=0, reserved1=0)
+    ms = C.c_double(0.0)
+    rc = b.denoise_regress(w, h, a_.ctypes.data, b_.ctypes.data, _ptr(va), _ptr(vb), _ptr(f["albedo"]), _ptr(f["normal"]), _ptr(f["depth"]),
+                           _ptr(f["alpha"]), C.byref(g), *[out[name].ctypes.data for name in REGRESS_OUTPUTS], C.byref(ms))
+    check(rc, b, "rttnw_denoise_regress")
+    if want_ms:
+        out["ms"] = ms.value
+    return out
+
+
 SELECT_OUTPUTS = ("linear", "rgba8", "blend", "feature", "nlm", "error")
 
 
