@@ -9,6 +9,7 @@
 // The passes read 25 taps per pixel straight from global memory: the image and its features are a few megabytes, L2-resident, and from the
 // third pass on (stride >= 4) the taps of neighbouring pixels no longer share lines a tile in LDS would save.
 #include "feature_api.hpp"
+#include "filter_call.hpp"
 #include "reconstruct.hpp"
 
 namespace rt {
@@ -148,51 +149,40 @@ int atrous_passes_tap_device(uint32_t width, uint32_t height, const double* d_in
 int atrous_device(const char* call, uint32_t width, uint32_t height, const double* linear_rgb, const double* variance_rgb, const uint8_t* valid,
                   const double* albedo, const double* normal, const double* depth, const double* alpha, uint32_t iterations, const DenoiseParams& prm,
                   double* out_linear_rgb, uint8_t* out_rgba8, double* out_variance_rgb, uint8_t* out_valid, double* kernel_ms) {
-    if (int rc = require_device(call)) return rc;
-    const std::string at = std::string(call) + ": ";
-    const size_t npx = size_t(width) * height;
+    FilterCall fc;
+    if (int rc = fc.open(call, width, height)) return rc;
     const bool has_var = variance_rgb != nullptr, has_flags = valid != nullptr;
     DevBuf<double> d_in, d_var, d_albedo, d_normal, d_depth, d_alpha, d_c[2], d_v[2];
     DevBuf<uint8_t> d_valid, d_h[2], d_rgba, d_out_valid;
-    HIP_TRY_AS(at, upload(d_in, linear_rgb, npx * 3));
-    if (has_var) HIP_TRY_AS(at, upload(d_var, variance_rgb, npx * 3));
-    HIP_TRY_AS(at, upload(d_albedo, albedo, npx * 3));
-    HIP_TRY_AS(at, upload(d_normal, normal, npx * 3));
-    HIP_TRY_AS(at, upload(d_depth, depth, npx));
-    HIP_TRY_AS(at, upload(d_alpha, alpha, npx));
-    if (has_flags) HIP_TRY_AS(at, upload(d_valid, valid, npx));
+    fc.upload(d_in, linear_rgb, 3);
+    if (has_var) fc.upload(d_var, variance_rgb, 3);
+    fc.upload(d_albedo, albedo, 3);
+    fc.upload(d_normal, normal, 3);
+    fc.upload(d_depth, depth, 1);
+    fc.upload(d_alpha, alpha, 1);
+    if (has_flags) fc.upload(d_valid, valid, 1);
     for (int k = 0; k < 2; ++k) {
-        HIP_TRY_AS(at, d_c[k].alloc(npx * 3));
-        if (has_var) HIP_TRY_AS(at, d_v[k].alloc(npx * 3));
-        if (has_flags) HIP_TRY_AS(at, d_h[k].alloc(npx));
+        fc.alloc(d_c[k], 3);
+        if (has_var) fc.alloc(d_v[k], 3);
+        if (has_flags) fc.alloc(d_h[k], 1);
     }
-    HIP_TRY_AS(at, d_rgba.alloc(npx * 4));
-    if (has_flags) HIP_TRY_AS(at, d_out_valid.alloc(npx));
-    Event ev0, ev1;
-    HIP_TRY_AS(at, create_event(ev0));
-    HIP_TRY_AS(at, create_event(ev1));
+    fc.alloc(d_rgba, 4);
+    if (has_flags) fc.alloc(d_out_valid, 1);
 
     // the passes step, between the two events
-    const hipStream_t stream = nullptr;
     double* const c[2] = {d_c[0].p, d_c[1].p};
     double* const v[2] = {d_v[0].p, d_v[1].p};
     uint8_t* const h[2] = {d_h[0].p, d_h[1].p};
     int out = 0;
-    HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
+    if (int rc = fc.start()) return rc;
     if (int rc = atrous_passes_device(width, height, d_in.p, has_var ? d_var.p : nullptr, d_valid.p, d_albedo.p, d_normal.p, d_depth.p, d_alpha.p, iterations,
-                                      prm, c, v, h, d_rgba.p, d_out_valid.p, stream, out)) return rc;
-    HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
-    HIP_TRY_AS(at, hipDeviceSynchronize());
-    if (kernel_ms) {
-        float ms = 0;
-        HIP_TRY_AS(at, hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-        *kernel_ms = ms;
-    }
-    if (out_linear_rgb) HIP_TRY_AS(at, hipMemcpy(out_linear_rgb, c[out], npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_rgba8) HIP_TRY_AS(at, hipMemcpy(out_rgba8, d_rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_variance_rgb && has_var) HIP_TRY_AS(at, hipMemcpy(out_variance_rgb, v[out], npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_valid && has_flags) HIP_TRY_AS(at, hipMemcpy(out_valid, d_out_valid.p, npx, hipMemcpyDeviceToHost));
-    return RTTNW_OK;
+                                      prm, c, v, h, d_rgba.p, d_out_valid.p, fc.stream, out)) return rc;
+    if (int rc = fc.finish(kernel_ms)) return rc;
+    fc.copy_out(out_linear_rgb, c[out], 3);
+    fc.copy_out(out_rgba8, d_rgba, 4);
+    if (has_var) fc.copy_out(out_variance_rgb, v[out], 3);
+    if (has_flags) fc.copy_out(out_valid, d_out_valid, 1);
+    return fc.rc;
 }
 
 } // namespace rt

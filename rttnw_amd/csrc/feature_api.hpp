@@ -1,8 +1,10 @@
-// feature_api.hpp — what feature_api.cpp (the extern "C" half of rttnw_render_features and rttnw_denoise) calls: the feature pass's launch
-// code per arithmetic build (feature_kernels.hpp, instantiated in features_f32.hip / features_f64.hip / features_f64_strict.hip) and the
-// device halves of the denoiser and of rttnw_reconstruct (denoise.hip), of rttnw_denoise_nlm (nlm.hip), of rttnw_denoise_select (select.hip), of
-// rttnw_temporal_accumulate (temporal.hip), of rttnw_temporal_variance (variance.hip), of rttnw_temporal_clamp (clamp.hip) and of
-// rttnw_temporal_probe (probe.hip).
+// feature_api.hpp — what feature_api.cpp (the extern "C" half of rttnw_render_features and of the nine image-filter entry points), svgf.hip (the
+// rttnw_svgf handle) and render_adaptive_api.cpp (the filtering adaptive renders) share: the feature pass's launch code per arithmetic build
+// (feature_kernels.hpp, instantiated in features_f32.hip / features_f64.hip / features_f64_strict.hip); the device halves of rttnw_denoise and
+// rttnw_reconstruct (denoise.hip), rttnw_denoise_nlm (nlm.hip), rttnw_denoise_select (select.hip), rttnw_temporal_accumulate (temporal.hip),
+// rttnw_temporal_variance (variance.hip), rttnw_temporal_clamp (clamp.hip) and rttnw_temporal_probe (probe.hip), each as a blocking call on host
+// arrays (on filter_call.hpp's scaffold) and as its kernels alone on device buffers; and what the entry points refuse for a parameter block
+// (feature_api.cpp).  rttnw_denoise_regress's device half is declared in regress.hpp.
 // Kept out of render_common.hpp: the render kernels' translation units do not read it.
 #pragma once
 #include "render_common.hpp"
@@ -15,6 +17,20 @@
 #include "probe.hpp"
 
 namespace rt {
+
+// ---- Refusals (feature_api.cpp).  One function per parameter block, for every entry point that takes the block, on its own or inside a struct of
+// its own: 0, or RTTNW_ERR_INVALID behind the message "<call>: ..." that names the field.  `field`: how the caller's signature names the block,
+// "t->", "q->t.", "dn->", "g->denoise."; a limit or a text lives here once.
+int refuse(const char* call, const std::string& what); // RTTNW_ERR_INVALID behind "<call>: <what>"
+int image_size_refused(const char* call, uint32_t width, uint32_t height); // an empty image, or more pixels than the filters' 32-bit indices take
+int temporal_refuse_params(const char* call, const char* field, const rttnw_temporal_params& t);
+int variance_refuse_params(const char* call, const char* field, const rttnw_variance_params& v);
+int denoise_refuse_params(const char* call, const char* field, const rttnw_denoise_params& d);
+int nlm_refuse_params(const char* call, const char* field, const rttnw_nlm_params& d);
+int clamp_refuse_params(const char* call, const rttnw_clamp_params* k);       // a NULL k among them: rttnw_temporal_clamp, rttnw_svgf_set_clamp
+int sampling_refuse_params(const char* call, const rttnw_sampling_params* a); // a NULL a among them: rttnw_temporal_probe, rttnw_svgf_set_sampling
+// The reprojection of a frame seen through `cam` into a history seen through `prev_cam` (nullptr: no history), under a checked t
+TemporalParams history_temporal_params(const rttnw_camera_desc* cam, const rttnw_camera_desc* prev_cam, const rttnw_temporal_params& t, bool has_variance);
 
 // rttnw_render_features' device half: host outputs (each optional), blocking — and the same pass with its maps left on the device
 // (feature_kernels.hpp).  Arguments were checked by the caller.
@@ -95,9 +111,6 @@ int clamp_accumulate_device(const char* at, uint32_t width, uint32_t height, con
                             const double* d_phist, const double* d_plen, const double* d_pnormal, const double* d_pdepth, const double* d_palpha, double* d_m1,
                             uint8_t* d_rgba, double* d_m2, double* d_acc, double* d_len, double* d_xy, double* d_mean, double* d_sd, uint8_t* d_clipped,
                             hipStream_t stream);
-// What rttnw_temporal_clamp and rttnw_svgf_set_clamp refuse for a rttnw_clamp_params (feature_api.cpp): 0, or RTTNW_ERR_INVALID behind a message
-// "<call>: ..." that names the field
-int clamp_refuse_params(const char* call, const rttnw_clamp_params* k);
 
 // rttnw_temporal_probe's device half (probe.hip): host arrays in, host arrays out (each optional), blocking, on the current device: one kernel
 // (probe.hpp).  The prev_* arrays are read only with prm.has_history.  Arguments were checked by the caller.
@@ -114,9 +127,6 @@ int probe_enqueue_device(const char* at, uint32_t width, uint32_t height, const 
 int probe_level_mask_device(const char* at, uint32_t n_pixels, const uint8_t* d_multiplier, uint32_t level, uint8_t* d_mask, hipStream_t stream);
 int probe_scatter_device(const char* at, uint32_t precision, const void* d_sums, const uint32_t* d_quads, uint32_t n_quads, void* d_packed,
                          hipStream_t stream);
-// What rttnw_temporal_probe and rttnw_svgf_set_sampling refuse for a rttnw_sampling_params (feature_api.cpp): 0, or RTTNW_ERR_INVALID behind a
-// message "<call>: ..." that names the field
-int sampling_refuse_params(const char* call, const rttnw_sampling_params* a);
 
 // rttnw_denoise's passes with a tap of the pass loop (denoise.hip): atrous_passes_device without flags, and d_tap (w*h*3) receives the linear image
 // the same call would return with `tap_after` iterations, 1 <= tap_after <= iterations.  rttnw_svgf_push's feedback.

@@ -10,6 +10,7 @@
 // per offset.  T = 32 where its LDS fits a CU (148 KiB at the default radii: one block of 16 waves per CU; 1.4 deltas per pixel and offset),
 // T = 16 otherwise (155 KiB at r 16, f 4; 1.9 and more deltas per pixel and offset).  DESIGN.md §10b has the measured times.
 #include "feature_api.hpp"
+#include "filter_call.hpp"
 #include "nlm.hpp"
 
 namespace rt {
@@ -135,49 +136,37 @@ int nlm_passes_device(const char* at, uint32_t width, uint32_t height, const dou
 // caller asked for.
 int nlm_device(uint32_t width, uint32_t height, const double* half_a, const double* half_b, const double* var_a, const double* var_b, const NlmParams& prm,
                double* out_linear_rgb, uint8_t* out_rgba8, double* out_half_a, double* out_half_b, double* out_error_rgb, double* kernel_ms) {
-    if (int rc = require_device("denoise_nlm")) return rc;
-    const char* const at = "denoise_nlm: ";
-    const size_t npx = size_t(width) * height;
+    FilterCall fc;
+    if (int rc = fc.open("denoise_nlm", width, height)) return rc;
     const bool has_var = var_a != nullptr;
     DevBuf<double> d_a, d_b, d_va, d_vb, d_fa, d_fb, d_out, d_err;
     DevBuf<uint8_t> d_rgba;
-    HIP_TRY_AS(at, upload(d_a, half_a, npx * 3));
-    HIP_TRY_AS(at, upload(d_b, half_b, npx * 3));
+    fc.upload(d_a, half_a, 3);
+    fc.upload(d_b, half_b, 3);
     if (has_var) {
-        HIP_TRY_AS(at, upload(d_va, var_a, npx * 3));
-        HIP_TRY_AS(at, upload(d_vb, var_b, npx * 3));
+        fc.upload(d_va, var_a, 3);
+        fc.upload(d_vb, var_b, 3);
     } else {
-        HIP_TRY_AS(at, d_va.alloc(npx * 3)); // the pair variance: one array for both guides
+        fc.alloc(d_va, 3); // the pair variance: one array for both guides
     }
-    HIP_TRY_AS(at, d_fa.alloc(npx * 3));
-    HIP_TRY_AS(at, d_fb.alloc(npx * 3));
-    HIP_TRY_AS(at, d_out.alloc(npx * 3));
-    HIP_TRY_AS(at, d_err.alloc(npx * 3));
-    HIP_TRY_AS(at, d_rgba.alloc(npx * 4));
+    fc.alloc(d_fa, 3);
+    fc.alloc(d_fb, 3);
+    fc.alloc(d_out, 3);
+    fc.alloc(d_err, 3);
+    fc.alloc(d_rgba, 4);
     NlmPlan plan;
-    if (int rc = nlm_plan_device(at, prm, plan)) return rc;
-    Event ev0, ev1;
-    HIP_TRY_AS(at, create_event(ev0));
-    HIP_TRY_AS(at, create_event(ev1));
+    if (int rc = nlm_plan_device(fc.at.c_str(), prm, plan)) return rc; // before the clock starts
 
-    const hipStream_t stream = nullptr;
-    HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
-    if (int rc = nlm_passes_device(at, width, height, d_a.p, d_b.p, has_var ? d_va.p : nullptr, has_var ? d_vb.p : nullptr, has_var ? nullptr : d_va.p, prm,
-                                   plan, d_fa.p, d_fb.p, d_out.p, d_rgba.p, d_err.p, stream)) return rc;
-    HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
-    HIP_TRY_AS(at, hipDeviceSynchronize());
-    if (kernel_ms) {
-        float ms = 0;
-        HIP_TRY_AS(at, hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-        *kernel_ms = ms;
-    }
-    const size_t bytes = npx * 3 * sizeof(double);
-    if (out_linear_rgb) HIP_TRY_AS(at, hipMemcpy(out_linear_rgb, d_out.p, bytes, hipMemcpyDeviceToHost));
-    if (out_rgba8) HIP_TRY_AS(at, hipMemcpy(out_rgba8, d_rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_half_a) HIP_TRY_AS(at, hipMemcpy(out_half_a, d_fa.p, bytes, hipMemcpyDeviceToHost));
-    if (out_half_b) HIP_TRY_AS(at, hipMemcpy(out_half_b, d_fb.p, bytes, hipMemcpyDeviceToHost));
-    if (out_error_rgb) HIP_TRY_AS(at, hipMemcpy(out_error_rgb, d_err.p, bytes, hipMemcpyDeviceToHost));
-    return RTTNW_OK;
+    if (int rc = fc.start()) return rc;
+    if (int rc = nlm_passes_device(fc.at.c_str(), width, height, d_a.p, d_b.p, has_var ? d_va.p : nullptr, has_var ? d_vb.p : nullptr, has_var ? nullptr : d_va.p,
+                                   prm, plan, d_fa.p, d_fb.p, d_out.p, d_rgba.p, d_err.p, fc.stream)) return rc;
+    if (int rc = fc.finish(kernel_ms)) return rc;
+    fc.copy_out(out_linear_rgb, d_out, 3);
+    fc.copy_out(out_rgba8, d_rgba, 4);
+    fc.copy_out(out_half_a, d_fa, 3);
+    fc.copy_out(out_half_b, d_fb, 3);
+    fc.copy_out(out_error_rgb, d_err, 3);
+    return fc.rc;
 }
 
 } // namespace rt

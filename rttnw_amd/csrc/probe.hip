@@ -6,6 +6,7 @@
 //   probe_scatter_kernel    one thread per slot of a list pass's running sums (rttnw_render_region's layout: 4 reals per slot, slot = 4 * list
 //                           position + pixel in block): a selected pixel's record moves to its place in a frame's packed tiles.  A copy, no arithmetic.
 #include "feature_api.hpp"
+#include "filter_call.hpp"
 
 namespace rt {
 namespace {
@@ -80,41 +81,30 @@ int probe_scatter_device(const char* at, uint32_t precision, const void* d_sums,
 int probe_device(uint32_t width, uint32_t height, const TemporalParams& prm, const SamplingParams& smp, const double* normal, const double* depth,
                  const double* alpha, const double* prev_length, const double* prev_normal, const double* prev_depth, const double* prev_alpha,
                  double* out_length, double* out_prev_xy, uint8_t* out_multiplier, double* kernel_ms) {
-    if (int rc = require_device("temporal_probe")) return rc;
-    const char* const at = "temporal_probe: ";
-    const size_t npx = size_t(width) * height;
+    FilterCall fc;
+    if (int rc = fc.open("temporal_probe", width, height)) return rc;
     DevBuf<double> d_normal, d_depth, d_alpha, d_plen, d_pnormal, d_pdepth, d_palpha, d_len, d_xy;
     DevBuf<uint8_t> d_mult;
-    HIP_TRY_AS(at, upload(d_normal, normal, npx * 3));
-    HIP_TRY_AS(at, upload(d_depth, depth, npx));
-    HIP_TRY_AS(at, upload(d_alpha, alpha, npx));
+    fc.upload(d_normal, normal, 3);
+    fc.upload(d_depth, depth, 1);
+    fc.upload(d_alpha, alpha, 1);
     if (prm.has_history) {
-        HIP_TRY_AS(at, upload(d_plen, prev_length, npx));
-        HIP_TRY_AS(at, upload(d_pnormal, prev_normal, npx * 3));
-        HIP_TRY_AS(at, upload(d_pdepth, prev_depth, npx));
-        HIP_TRY_AS(at, upload(d_palpha, prev_alpha, npx));
+        fc.upload(d_plen, prev_length, 1);
+        fc.upload(d_pnormal, prev_normal, 3);
+        fc.upload(d_pdepth, prev_depth, 1);
+        fc.upload(d_palpha, prev_alpha, 1);
     }
-    HIP_TRY_AS(at, d_len.alloc(npx));
-    HIP_TRY_AS(at, d_xy.alloc(npx * 2));
-    HIP_TRY_AS(at, d_mult.alloc(npx));
-    Event ev0, ev1;
-    HIP_TRY_AS(at, create_event(ev0));
-    HIP_TRY_AS(at, create_event(ev1));
-    const hipStream_t stream = nullptr;
-    HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
-    if (int rc = probe_enqueue_device(at, width, height, prm, smp, d_normal.p, d_depth.p, d_alpha.p, d_plen.p, d_pnormal.p, d_pdepth.p, d_palpha.p, d_len.p,
-                                      d_xy.p, d_mult.p, stream)) return rc;
-    HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
-    HIP_TRY_AS(at, hipDeviceSynchronize());
-    if (kernel_ms) {
-        float ms = 0;
-        HIP_TRY_AS(at, hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-        *kernel_ms = ms;
-    }
-    if (out_length) HIP_TRY_AS(at, hipMemcpy(out_length, d_len.p, npx * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_prev_xy) HIP_TRY_AS(at, hipMemcpy(out_prev_xy, d_xy.p, npx * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_multiplier) HIP_TRY_AS(at, hipMemcpy(out_multiplier, d_mult.p, npx, hipMemcpyDeviceToHost));
-    return RTTNW_OK;
+    fc.alloc(d_len, 1);
+    fc.alloc(d_xy, 2);
+    fc.alloc(d_mult, 1);
+    if (int rc = fc.start()) return rc;
+    if (int rc = probe_enqueue_device(fc.at.c_str(), width, height, prm, smp, d_normal.p, d_depth.p, d_alpha.p, d_plen.p, d_pnormal.p, d_pdepth.p, d_palpha.p,
+                                      d_len.p, d_xy.p, d_mult.p, fc.stream)) return rc;
+    if (int rc = fc.finish(kernel_ms)) return rc;
+    fc.copy_out(out_length, d_len, 1);
+    fc.copy_out(out_prev_xy, d_xy, 2);
+    fc.copy_out(out_multiplier, d_mult, 1);
+    return fc.rc;
 }
 
 } // namespace rt

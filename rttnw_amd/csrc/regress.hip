@@ -11,6 +11,7 @@
 // The 60 running doubles of d = 7 are 120 VGPRs before the loop's own: they do not fit the 128 registers of a 1024-thread block, so masks
 // with d >= 6 run the 16-pixel tile (256 threads) at every radius (regress.hpp regress_tile_large); KERNELS.md has the registers per mask.
 #include "feature_api.hpp"
+#include "filter_call.hpp"
 #include "regress.hpp"
 
 namespace rt {
@@ -164,44 +165,44 @@ int regress_device(uint32_t width, uint32_t height, const double* half_a, const 
                    const double* albedo, const double* normal, const double* depth, const double* alpha, const RegressParams& prm,
                    double* out_linear_rgb, uint8_t* out_rgba8, double* out_half_a, double* out_half_b, double* out_error_rgb, double* out_fit,
                    double* kernel_ms) {
-    if (int rc = require_device("denoise_regress")) return rc;
-    const char* const at = "denoise_regress: ";
-    const size_t npx = size_t(width) * height;
+    FilterCall fc;
+    if (int rc = fc.open("denoise_regress", width, height)) return rc;
+    const size_t npx = fc.npx;
     const uint32_t mask = prm.features;
     const bool has_var = var_a != nullptr, demodulate = prm.demodulate != 0;
     DevBuf<double> d_a, d_b, d_va, d_vb, d_albedo, d_normal, d_depth, d_alpha, d_wa, d_wb, d_wva, d_wvb, d_pair, d_fa, d_fb, d_out, d_err, d_fit;
     DevBuf<uint8_t> d_rgba, d_fit_a, d_fit_b;
     DevBuf<RegressRecord> d_rec;
-    HIP_TRY_AS(at, upload(d_a, half_a, npx * 3));
-    HIP_TRY_AS(at, upload(d_b, half_b, npx * 3));
+    fc.upload(d_a, half_a, 3);
+    fc.upload(d_b, half_b, 3);
     if (has_var) {
-        HIP_TRY_AS(at, upload(d_va, var_a, npx * 3));
-        HIP_TRY_AS(at, upload(d_vb, var_b, npx * 3));
+        fc.upload(d_va, var_a, 3);
+        fc.upload(d_vb, var_b, 3);
     } else {
-        HIP_TRY_AS(at, d_pair.alloc(npx * 3)); // the pair variance: one array for both guides
+        fc.alloc(d_pair, 3); // the pair variance: one array for both guides
     }
     // the feature arrays the call reads: each one its mask bit asks for, the albedo for the demodulation, alpha for either
-    if ((mask & REGRESS_ALBEDO) || demodulate) HIP_TRY_AS(at, upload(d_albedo, albedo, npx * 3));
-    if (mask & REGRESS_NORMAL) HIP_TRY_AS(at, upload(d_normal, normal, npx * 3));
-    if (mask & REGRESS_DEPTH) HIP_TRY_AS(at, upload(d_depth, depth, npx));
-    if (mask != 0u || demodulate) HIP_TRY_AS(at, upload(d_alpha, alpha, npx));
+    if ((mask & REGRESS_ALBEDO) || demodulate) fc.upload(d_albedo, albedo, 3);
+    if (mask & REGRESS_NORMAL) fc.upload(d_normal, normal, 3);
+    if (mask & REGRESS_DEPTH) fc.upload(d_depth, depth, 1);
+    if (mask != 0u || demodulate) fc.upload(d_alpha, alpha, 1);
     if (demodulate) {
-        HIP_TRY_AS(at, d_wa.alloc(npx * 3));
-        HIP_TRY_AS(at, d_wb.alloc(npx * 3));
+        fc.alloc(d_wa, 3);
+        fc.alloc(d_wb, 3);
         if (has_var) {
-            HIP_TRY_AS(at, d_wva.alloc(npx * 3));
-            HIP_TRY_AS(at, d_wvb.alloc(npx * 3));
+            fc.alloc(d_wva, 3);
+            fc.alloc(d_wvb, 3);
         }
     }
-    if (mask != 0u) HIP_TRY_AS(at, d_rec.alloc(npx));
-    HIP_TRY_AS(at, d_fa.alloc(npx * 3));
-    HIP_TRY_AS(at, d_fb.alloc(npx * 3));
-    HIP_TRY_AS(at, d_out.alloc(npx * 3));
-    HIP_TRY_AS(at, d_err.alloc(npx * 3));
-    HIP_TRY_AS(at, d_fit.alloc(npx));
-    HIP_TRY_AS(at, d_rgba.alloc(npx * 4));
-    HIP_TRY_AS(at, d_fit_a.alloc(npx));
-    HIP_TRY_AS(at, d_fit_b.alloc(npx));
+    if (mask != 0u) fc.alloc(d_rec, 1);
+    fc.alloc(d_fa, 3);
+    fc.alloc(d_fb, 3);
+    fc.alloc(d_out, 3);
+    fc.alloc(d_err, 3);
+    fc.alloc(d_fit, 1);
+    fc.alloc(d_rgba, 4);
+    fc.alloc(d_fit_a, 1);
+    fc.alloc(d_fit_b, 1);
 
     // the filter kernel of the call's mask and radii, its dynamic LDS admitted before the clock starts
     const bool large = regress_tile_large(mask, prm.nlm.r, prm.nlm.f);
@@ -212,15 +213,12 @@ int regress_device(uint32_t width, uint32_t height, const double* half_a, const 
     const RegressFilter filter = large ? LARGE[mask] : SMALL[mask];
     const uint32_t tile = large ? NLM_TILE_LARGE : NLM_TILE_SMALL;
     const size_t lds_bytes = nlm_lds_bytes(tile, prm.nlm.r, prm.nlm.f);
-    HIP_TRY_AS(at, hipFuncSetAttribute(reinterpret_cast<const void*>(filter), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-    Event ev0, ev1;
-    HIP_TRY_AS(at, create_event(ev0));
-    HIP_TRY_AS(at, create_event(ev1));
+    HIP_TRY_AS(fc.at, hipFuncSetAttribute(reinterpret_cast<const void*>(filter), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
 
-    const hipStream_t stream = nullptr;
+    const hipStream_t stream = fc.stream;
     const dim3 flat_block(256), pixel_grid(uint32_t((npx + 255) / 256)), value_grid(uint32_t((npx * 3 + 255) / 256));
     const dim3 tiles((width + tile - 1) / tile, (height + tile - 1) / tile, 2);
-    HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
+    if (int rc = fc.start()) return rc;
     if (demodulate || mask != 0u)
         hipLaunchKernelGGL(regress_prepare_kernel, pixel_grid, flat_block, 0, stream, uint32_t(npx), mask, demodulate, d_a.p, d_b.p, d_va.p, d_vb.p,
                            d_albedo.p, d_normal.p, d_depth.p, d_alpha.p, d_wa.p, d_wb.p, d_wva.p, d_wvb.p, d_rec.p);
@@ -233,22 +231,15 @@ int regress_device(uint32_t width, uint32_t height, const double* half_a, const 
     hipLaunchKernelGGL(filter, tiles, dim3(tile * tile), lds_bytes, stream, view, prm, d_rec.p, d_albedo.p, d_alpha.p, d_fa.p, d_fb.p, d_fit_a.p, d_fit_b.p);
     hipLaunchKernelGGL(regress_finish_kernel, value_grid, flat_block, 0, stream, uint32_t(npx), d_fa.p, d_fb.p, d_fit_a.p, d_fit_b.p, d_out.p, d_rgba.p,
                        d_err.p, d_fit.p);
-    HIP_TRY_AS(at, hipGetLastError());
-    HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
-    HIP_TRY_AS(at, hipDeviceSynchronize());
-    if (kernel_ms) {
-        float ms = 0;
-        HIP_TRY_AS(at, hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-        *kernel_ms = ms;
-    }
-    const size_t bytes = npx * 3 * sizeof(double);
-    if (out_linear_rgb) HIP_TRY_AS(at, hipMemcpy(out_linear_rgb, d_out.p, bytes, hipMemcpyDeviceToHost));
-    if (out_rgba8) HIP_TRY_AS(at, hipMemcpy(out_rgba8, d_rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_half_a) HIP_TRY_AS(at, hipMemcpy(out_half_a, d_fa.p, bytes, hipMemcpyDeviceToHost));
-    if (out_half_b) HIP_TRY_AS(at, hipMemcpy(out_half_b, d_fb.p, bytes, hipMemcpyDeviceToHost));
-    if (out_error_rgb) HIP_TRY_AS(at, hipMemcpy(out_error_rgb, d_err.p, bytes, hipMemcpyDeviceToHost));
-    if (out_fit) HIP_TRY_AS(at, hipMemcpy(out_fit, d_fit.p, npx * sizeof(double), hipMemcpyDeviceToHost));
-    return RTTNW_OK;
+    HIP_TRY_AS(fc.at, hipGetLastError());
+    if (int rc = fc.finish(kernel_ms)) return rc;
+    fc.copy_out(out_linear_rgb, d_out, 3);
+    fc.copy_out(out_rgba8, d_rgba, 4);
+    fc.copy_out(out_half_a, d_fa, 3);
+    fc.copy_out(out_half_b, d_fb, 3);
+    fc.copy_out(out_error_rgb, d_err, 3);
+    fc.copy_out(out_fit, d_fit, 1);
+    return fc.rc;
 }
 
 } // namespace rt

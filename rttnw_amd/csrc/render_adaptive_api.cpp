@@ -35,17 +35,6 @@ static int refuse_unknown_devices(const char* caller, uint32_t ngpu, const int32
         if (device_ids[r] < 0 || device_ids[r] >= n_dev) { set_last_error(std::string(caller) + ": no such device in device_ids"); return RTTNW_ERR_INVALID; }
     return 0;
 }
-// The denoiser's parameters inside rttnw_guided (`field` "g->") and rttnw_preview ("v->")
-static int refuse_denoise_misuse(const char* caller, const char* field, const rttnw_denoise_params& dn) {
-    const std::string at = std::string(caller) + ": " + field + "denoise";
-    if (dn.iterations > DENOISE_MAX_ITERATIONS) { set_last_error(at + ".iterations: more than 8 iterations"); return RTTNW_ERR_INVALID; }
-    if (dn.reserved0 != 0) { set_last_error(at + ".reserved0 must be 0"); return RTTNW_ERR_INVALID; }
-    if (!(dn.sigma_luminance >= 0.0) || !(dn.sigma_normal >= 0.0) || !(dn.sigma_depth >= 0.0)) {
-        set_last_error(at + ": the sigmas (sigma_luminance, sigma_normal, sigma_depth) must be >= 0 (and not NaN)");
-        return RTTNW_ERR_INVALID;
-    }
-    return 0;
-}
 
 // Where a call's level loop starts, and up to which level each rank must look even when a list comes back empty (a fresh render: level 0 only)
 struct LevelPlan {
@@ -655,7 +644,7 @@ extern "C" int rttnw_render_adaptive_denoised(rttnw_scene* s, const rttnw_camera
     if (int rc = refuse_adaptive_misuse("render_adaptive_denoised", p, a)) return rc;
     if (int rc = refuse_host_output_misuse("render_adaptive_denoised", a->reserved0, p)) return rc;
     if (g->reserved0 != 0) { set_last_error("render_adaptive_denoised: g->reserved0 must be 0"); return RTTNW_ERR_INVALID; }
-    if (int rc = refuse_denoise_misuse("render_adaptive_denoised", "g->", g->denoise)) return rc;
+    if (int rc = denoise_refuse_params("render_adaptive_denoised", "g->denoise.", g->denoise)) return rc;
     if (int rc = validate(s, cam, p)) return rc;
     return adaptive_denoised_render(s, cam, *p, *a, *g, out_linear_rgb, out_rgba8, out_spp, out_stderr_rgb, out_raw_linear_rgb, out_raw_stderr_rgb, state_out,
                                     stats);
@@ -729,7 +718,7 @@ extern "C" int rttnw_render_preview(rttnw_scene* s, const rttnw_camera_desc* cam
     if (int rc = refuse_adaptive_misuse("render_preview", p, a)) return rc;
     if (int rc = refuse_host_output_misuse("render_preview", a->reserved0, p)) return rc;
     if (v->level > 6) { set_last_error("render_preview: v->level must be 0 .. 6"); return RTTNW_ERR_INVALID; }
-    if (int rc = refuse_denoise_misuse("render_preview", "v->", v->denoise)) return rc;
+    if (int rc = denoise_refuse_params("render_preview", "v->denoise.", v->denoise)) return rc;
     if (int rc = validate(s, cam, p)) return rc;
     return preview_render(s, cam, *p, *a, *v, out_linear_rgb, out_rgba8, out_valid, out_spp, out_raw_linear_rgb, out_raw_stderr_rgb, state_out, stats);
 }
@@ -949,7 +938,7 @@ extern "C" int rttnw_render_adaptive_budget_denoised(rttnw_scene* s, const rttnw
         return RTTNW_ERR_INVALID;
     }
     if (g->reserved0 != 0) { set_last_error(std::string(call) + ": g->reserved0 must be 0"); return RTTNW_ERR_INVALID; }
-    if (int rc = refuse_denoise_misuse(call, "g->", g->denoise)) return rc;
+    if (int rc = denoise_refuse_params(call, "g->denoise.", g->denoise)) return rc;
     uint32_t first_level = 0; // (not used: every round finds the levels of its own pixels)
     std::string err;
     if (state_in)

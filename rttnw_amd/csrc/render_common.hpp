@@ -38,7 +38,7 @@ namespace rt {
     do {                                                                                   \
         hipError_t e_ = (expr);                                                            \
         if (e_ != hipSuccess) {                                                            \
-            set_last_error(text + hipGetErrorString(e_));                                  \
+            ::rt::set_last_error(text + hipGetErrorString(e_));                                  \
             return RTTNW_ERR_HIP;                                                          \
         }                                                                                  \
     } while (0)

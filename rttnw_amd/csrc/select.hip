@@ -9,6 +9,7 @@
 // window sum around that position but m of the nearest pixel inside (the contract clamps the coordinate of m, then the window's): that pixel
 // lies inside the block's own m region, so the second stage reads m through clamped indices.  Four barriers per tile.
 #include "feature_api.hpp"
+#include "filter_call.hpp"
 
 namespace rt {
 namespace {
@@ -94,53 +95,51 @@ int select_device(uint32_t width, uint32_t height, const double* half_a, const d
                   const double* albedo, const double* normal, const double* depth, const double* alpha, uint32_t iterations, const DenoiseParams& dn,
                   const NlmParams& nl, const SelectParams& sel, double* out_linear_rgb, uint8_t* out_rgba8, double* out_blend, double* out_feature_rgb,
                   double* out_nlm_rgb, double* out_error_rgb, double* kernel_ms) {
-    if (int rc = require_device("denoise_select")) return rc;
-    const char* const at = "denoise_select: ";
-    const size_t npx = size_t(width) * height;
+    FilterCall fc;
+    if (int rc = fc.open("denoise_select", width, height)) return rc;
+    const size_t npx = fc.npx;
     const bool has_var = var_a != nullptr;
     DevBuf<double> d_a, d_b, d_va, d_vb, d_albedo, d_normal, d_depth, d_alpha, d_ca[2], d_cb[2], d_v[2], d_na, d_nb, d_d, d_out, d_blend, d_feature, d_nlm, d_err;
     DevBuf<uint8_t> d_rgba;
-    HIP_TRY_AS(at, upload(d_a, half_a, npx * 3));
-    HIP_TRY_AS(at, upload(d_b, half_b, npx * 3));
+    fc.upload(d_a, half_a, 3);
+    fc.upload(d_b, half_b, 3);
     if (has_var) {
-        HIP_TRY_AS(at, upload(d_va, var_a, npx * 3));
-        HIP_TRY_AS(at, upload(d_vb, var_b, npx * 3));
+        fc.upload(d_va, var_a, 3);
+        fc.upload(d_vb, var_b, 3);
     } else {
-        HIP_TRY_AS(at, d_va.alloc(npx * 3)); // the pair variance of the non-local-means step: one array for both guides
+        fc.alloc(d_va, 3); // the pair variance of the non-local-means step: one array for both guides
     }
-    HIP_TRY_AS(at, upload(d_albedo, albedo, npx * 3));
-    HIP_TRY_AS(at, upload(d_normal, normal, npx * 3));
-    HIP_TRY_AS(at, upload(d_depth, depth, npx));
-    HIP_TRY_AS(at, upload(d_alpha, alpha, npx));
+    fc.upload(d_albedo, albedo, 3);
+    fc.upload(d_normal, normal, 3);
+    fc.upload(d_depth, depth, 1);
+    fc.upload(d_alpha, alpha, 1);
     for (int k = 0; k < 2; ++k) {
-        HIP_TRY_AS(at, d_ca[k].alloc(npx * 3));
-        HIP_TRY_AS(at, d_cb[k].alloc(npx * 3));
-        if (has_var) HIP_TRY_AS(at, d_v[k].alloc(npx * 3)); // the filtered variances are not an output: the two runs share their buffers
+        fc.alloc(d_ca[k], 3);
+        fc.alloc(d_cb[k], 3);
+        if (has_var) fc.alloc(d_v[k], 3); // the filtered variances are not an output: the two runs share their buffers
     }
-    HIP_TRY_AS(at, d_na.alloc(npx * 3));
-    HIP_TRY_AS(at, d_nb.alloc(npx * 3));
-    HIP_TRY_AS(at, d_d.alloc(npx));
-    HIP_TRY_AS(at, d_out.alloc(npx * 3));
-    HIP_TRY_AS(at, d_blend.alloc(npx));
-    HIP_TRY_AS(at, d_feature.alloc(npx * 3));
-    HIP_TRY_AS(at, d_nlm.alloc(npx * 3));
-    HIP_TRY_AS(at, d_err.alloc(npx * 3));
-    HIP_TRY_AS(at, d_rgba.alloc(npx * 4)); // the à-trous runs' RGBA8, then the call's
+    fc.alloc(d_na, 3);
+    fc.alloc(d_nb, 3);
+    fc.alloc(d_d, 1);
+    fc.alloc(d_out, 3);
+    fc.alloc(d_blend, 1);
+    fc.alloc(d_feature, 3);
+    fc.alloc(d_nlm, 3);
+    fc.alloc(d_err, 3);
+    fc.alloc(d_rgba, 4); // the à-trous runs' RGBA8, then the call's
+    const char* const at = fc.at.c_str();
     NlmPlan plan;
     if (int rc = nlm_plan_device(at, nl, plan)) return rc;
     const size_t lds_bytes = select_lds_bytes(sel.s, sel.t);
     HIP_TRY_AS(at, hipFuncSetAttribute(reinterpret_cast<const void*>(select_blend_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-    Event ev0, ev1;
-    HIP_TRY_AS(at, create_event(ev0));
-    HIP_TRY_AS(at, create_event(ev1));
 
-    const hipStream_t stream = nullptr;
+    const hipStream_t stream = fc.stream;
     double* const ca[2] = {d_ca[0].p, d_ca[1].p};
     double* const cb[2] = {d_cb[0].p, d_cb[1].p};
     double* const v[2] = {d_v[0].p, d_v[1].p};
     uint8_t* const no_h[2] = {nullptr, nullptr};
     int out_a = 0, out_b = 0;
-    HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
+    if (int rc = fc.start()) return rc;
     if (int rc = atrous_passes_device(width, height, d_a.p, has_var ? d_va.p : nullptr, nullptr, d_albedo.p, d_normal.p, d_depth.p, d_alpha.p, iterations, dn,
                                       ca, v, no_h, d_rgba.p, nullptr, stream, out_a)) return rc;
     if (int rc = atrous_passes_device(width, height, d_b.p, has_var ? d_vb.p : nullptr, nullptr, d_albedo.p, d_normal.p, d_depth.p, d_alpha.p, iterations, dn,
@@ -154,21 +153,14 @@ int select_device(uint32_t width, uint32_t height, const double* half_a, const d
     hipLaunchKernelGGL(select_blend_kernel, tiles, dim3(SELECT_BLOCK), lds_bytes, stream, width, height, sel, d_d.p, fa, fb, d_na.p, d_nb.p, d_out.p,
                        d_rgba.p, d_blend.p, d_feature.p, d_nlm.p, d_err.p);
     HIP_TRY_AS(at, hipGetLastError());
-    HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
-    HIP_TRY_AS(at, hipDeviceSynchronize());
-    if (kernel_ms) {
-        float ms = 0;
-        HIP_TRY_AS(at, hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-        *kernel_ms = ms;
-    }
-    const size_t bytes = npx * 3 * sizeof(double);
-    if (out_linear_rgb) HIP_TRY_AS(at, hipMemcpy(out_linear_rgb, d_out.p, bytes, hipMemcpyDeviceToHost));
-    if (out_rgba8) HIP_TRY_AS(at, hipMemcpy(out_rgba8, d_rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_blend) HIP_TRY_AS(at, hipMemcpy(out_blend, d_blend.p, npx * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_feature_rgb) HIP_TRY_AS(at, hipMemcpy(out_feature_rgb, d_feature.p, bytes, hipMemcpyDeviceToHost));
-    if (out_nlm_rgb) HIP_TRY_AS(at, hipMemcpy(out_nlm_rgb, d_nlm.p, bytes, hipMemcpyDeviceToHost));
-    if (out_error_rgb) HIP_TRY_AS(at, hipMemcpy(out_error_rgb, d_err.p, bytes, hipMemcpyDeviceToHost));
-    return RTTNW_OK;
+    if (int rc = fc.finish(kernel_ms)) return rc;
+    fc.copy_out(out_linear_rgb, d_out, 3);
+    fc.copy_out(out_rgba8, d_rgba, 4);
+    fc.copy_out(out_blend, d_blend, 1);
+    fc.copy_out(out_feature_rgb, d_feature, 3);
+    fc.copy_out(out_nlm_rgb, d_nlm, 3);
+    fc.copy_out(out_error_rgb, d_err, 3);
+    return fc.rc;
 }
 
 } // namespace rt

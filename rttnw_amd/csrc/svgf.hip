@@ -108,30 +108,12 @@ __global__ void svgf_fill_kernel(size_t n, double value, double* __restrict__ ou
     if (i < n) out[i] = value;
 }
 
-int refuse(const char* call, const char* what) {
-    set_last_error(std::string(call) + ": " + what);
-    return RTTNW_ERR_INVALID;
-}
-
 // What rttnw_temporal_variance, rttnw_temporal_accumulate and rttnw_denoise refuse for their parameter blocks, then the loop's own
 int refuse_params(const char* call, const rttnw_svgf_params* q) {
-    const rttnw_temporal_params& t = q->t;
-    const rttnw_variance_params& v = q->v;
-    const rttnw_denoise_params& d = q->d;
-    if (t.max_history > TEMPORAL_HISTORY_LIMIT) return refuse(call, "q->t.max_history is more than 65535");
-    if (t.reserved0 != 0) return refuse(call, "q->t.reserved0 must be 0");
-    if (!(t.depth_tolerance >= 0.0)) return refuse(call, "q->t.depth_tolerance must be >= 0 (and not NaN)");
-    if (!(t.normal_min >= -1.0 && t.normal_min <= 1.0)) return refuse(call, "q->t.normal_min must lie in [-1, 1] (and not be NaN)");
-    if (v.min_temporal == 1 || v.min_temporal > TEMPORAL_HISTORY_LIMIT) return refuse(call, "q->v.min_temporal must be 0 (the default, 4) or 2 .. 65535");
-    if (v.radius > VARIANCE_MAX_RADIUS) return refuse(call, "q->v.radius is more than 4");
-    if (v.reserved0 != 0 || v.reserved1 != 0) return refuse(call, "q->v.reserved0 and q->v.reserved1 must be 0");
-    if (!(v.sigma_normal >= 0.0) || !(v.sigma_depth >= 0.0)) return refuse(call, "the sigmas (q->v.sigma_normal, q->v.sigma_depth) must be >= 0 (and not NaN)");
-    if (d.iterations > DENOISE_MAX_ITERATIONS) return refuse(call, "q->d.iterations: more than 8 iterations");
-    if (d.reserved0 != 0) return refuse(call, "q->d.reserved0 must be 0");
-    if (!(d.sigma_luminance >= 0.0) || !(d.sigma_normal >= 0.0) || !(d.sigma_depth >= 0.0)) {
-        return refuse(call, "the sigmas (q->d.sigma_luminance, sigma_normal, sigma_depth) must be >= 0 (and not NaN)");
-    }
-    if (q->feedback_iterations > d.iterations) return refuse(call, "q->feedback_iterations is more than q->d.iterations");
+    if (int rc = temporal_refuse_params(call, "q->t.", q->t)) return rc;
+    if (int rc = variance_refuse_params(call, "q->v.", q->v)) return rc;
+    if (int rc = denoise_refuse_params(call, "q->d.", q->d)) return rc;
+    if (q->feedback_iterations > q->d.iterations) return refuse(call, "q->feedback_iterations is more than q->d.iterations");
     if (q->demodulate > 1) return refuse(call, "q->demodulate must be 0 or 1");
     if (q->reserved0 != 0) return refuse(call, "q->reserved0 must be 0");
     return 0;
@@ -139,12 +121,21 @@ int refuse_params(const char* call, const rttnw_svgf_params* q) {
 
 // The reprojection of a frame seen through `cam` into the handle's state (none: a first frame)
 TemporalParams svgf_temporal_params(const ::rttnw_svgf* g, const rttnw_camera_desc* cam) {
-    const CameraRec<double> rec = camera_of<double>(cam);
-    CameraRec<double> prev_rec = {};
-    if (g->has_state) prev_rec = camera_of<double>(&g->cam);
-    const bool same_camera = g->has_state && std::memcmp(cam, &g->cam, sizeof(rttnw_camera_desc)) == 0;
-    return temporal_params(rec, g->has_state ? &prev_rec : nullptr, same_camera, g->q.t.max_history, g->q.t.depth_tolerance, g->q.t.normal_min, false);
+    return history_temporal_params(cam, g->has_state ? &g->cam : nullptr, g->q.t, false);
 }
+
+// A call on an existing handle: the handle's device made current until the caller returns, and the prefix of a HIP failure's message
+struct OnHandleDevice {
+    DeviceGuard restore;
+    std::string at;
+    int rc = RTTNW_OK; // RTTNW_ERR_HIP, the message set, where the device could not be made current
+    OnHandleDevice(const char* call, const ::rttnw_svgf* g) : at(std::string(call) + ": ") {
+        const hipError_t e = hipSetDevice(g->device);
+        if (e == hipSuccess) return;
+        set_last_error(at + "hipSetDevice(q->device): " + hipGetErrorString(e));
+        rc = RTTNW_ERR_HIP;
+    }
+};
 
 // rttnw_svgf_set_sampling's steps 2 and 3 behind the plain trace of the frame (g->packed holds every pixel at p->spp) and the feature pass
 // (maps[cur ^ 1]): the probe over the frame's features and the state's, then per level 2, 4, 8 up to the boost the mask {m == level}, its selection
@@ -312,7 +303,7 @@ int rttnw_svgf_create(uint32_t width, uint32_t height, const rttnw_svgf_params* 
     if (!q) return rt::refuse(call, "q is NULL");
     if (!out) return rt::refuse(call, "out is NULL");
     *out = nullptr;
-    if (uint64_t(width) * height == 0 || uint64_t(width) * height > (1ull << 28)) return rt::refuse(call, "width * height: empty image (or more than 2^28 pixels)");
+    if (int rc = rt::image_size_refused(call, width, height)) return rc;
     if (int rc = rt::refuse_params(call, q)) return rc;
     if (int rc = rt::require_device(call)) return rc;
     std::unique_ptr<rttnw_svgf> g(new rttnw_svgf());
@@ -350,11 +341,9 @@ int rttnw_svgf_set_clamp(rttnw_svgf* q, const rttnw_clamp_params* k) {
         return RTTNW_OK;
     }
     if (!q->clipped.p) { // the one byte map, once: frame calls still allocate nothing
-        using rt::set_last_error;
-        const std::string at = std::string(call) + ": ";
-        rt::DeviceGuard restore;
-        HIP_TRY_AS(at, hipSetDevice(q->device));
-        HIP_TRY_AS(at, q->clipped.alloc(size_t(q->width) * q->height));
+        const rt::OnHandleDevice on(call, q);
+        if (on.rc) return on.rc;
+        HIP_TRY_AS(on.at, q->clipped.alloc(size_t(q->width) * q->height));
     }
     q->kprm = rt::clamp_params(k->radius, k->gamma, k->sigma_normal, k->sigma_depth);
     q->clamp = true;
@@ -370,11 +359,9 @@ int rttnw_svgf_clipped(rttnw_svgf* q, uint8_t* out_clipped) {
         std::memset(out_clipped, 0, npx);
         return RTTNW_OK;
     }
-    using rt::set_last_error;
-    const std::string at = std::string(call) + ": ";
-    rt::DeviceGuard restore;
-    HIP_TRY_AS(at, hipSetDevice(q->device));
-    HIP_TRY_AS(at, hipMemcpy(out_clipped, q->clipped.p, npx, hipMemcpyDeviceToHost));
+    const rt::OnHandleDevice on(call, q);
+    if (on.rc) return on.rc;
+    HIP_TRY_AS(on.at, hipMemcpy(out_clipped, q->clipped.p, npx, hipMemcpyDeviceToHost));
     return RTTNW_OK;
 }
 
@@ -388,14 +375,13 @@ int rttnw_svgf_set_sampling(rttnw_svgf* q, const rttnw_sampling_params* a) {
         return RTTNW_OK;
     }
     if (!q->s_mult.p) { // the maps, the list and the list passes' sums, once: frame calls still allocate none of the handle's buffers
-        using rt::set_last_error;
-        const std::string at = std::string(call) + ": ";
         const size_t npx = size_t(q->width) * q->height;
         rttnw_tile_layout L;
         rt::fill_layout(q->width, q->height, 1, L);
         const uint32_t n_blocks = L.n_tiles * 16u;
-        rt::DeviceGuard restore;
-        HIP_TRY_AS(at, hipSetDevice(q->device));
+        const rt::OnHandleDevice on(call, q);
+        if (on.rc) return on.rc;
+        const std::string& at = on.at;
         HIP_TRY_AS(at, q->s_len.alloc(npx));
         HIP_TRY_AS(at, q->s_mask.alloc(npx));
         HIP_TRY_AS(at, q->s_select.alloc(L.pixels_per_rank));
@@ -420,10 +406,9 @@ int rttnw_svgf_samples(rttnw_svgf* q, uint32_t* out_spp, double* out_length) {
         if (out_length) std::fill(out_length, out_length + npx, 0.0);
         return RTTNW_OK;
     }
-    using rt::set_last_error;
-    const std::string at = std::string(call) + ": ";
-    rt::DeviceGuard restore;
-    HIP_TRY_AS(at, hipSetDevice(q->device));
+    const rt::OnHandleDevice on(call, q);
+    if (on.rc) return on.rc;
+    const std::string& at = on.at;
     if (out_spp) {
         std::vector<uint8_t> m(npx);
         HIP_TRY_AS(at, hipMemcpy(m.data(), q->s_mult.p, npx, hipMemcpyDeviceToHost));
@@ -441,10 +426,9 @@ int rttnw_svgf_push(rttnw_svgf* q, const rttnw_camera_desc* cam, const double* l
     if (!linear_rgb) return rt::refuse(call, "linear_rgb is NULL");
     if (!albedo || !normal || !depth || !alpha) return rt::refuse(call, "NULL argument (albedo, normal, depth or alpha)");
     if (!q) return rt::refuse(call, "q is NULL");
-    using rt::set_last_error; // (HIP_TRY_AS names it)
-    const std::string at = std::string(call) + ": ";
-    rt::DeviceGuard restore;
-    HIP_TRY_AS(at, hipSetDevice(q->device));
+    const rt::OnHandleDevice on(call, q);
+    if (on.rc) return on.rc;
+    const std::string& at = on.at;
     const size_t npx = size_t(q->width) * q->height, b3 = npx * 3 * sizeof(double), b1 = npx * sizeof(double);
     double* maps = q->maps[q->cur ^ 1].p;
     HIP_TRY_AS(at, hipMemcpy(q->raw.p, linear_rgb, b3, hipMemcpyHostToDevice));

@@ -4,6 +4,7 @@
 // The four taps of the previous frame are plain global loads: neighbouring pixels land on neighbouring history pixels, so the caches serve the
 // gather, and a tile staged in LDS would have to cover wherever the block's pixels map to.  No LDS, no atomics, no barrier.
 #include "feature_api.hpp"
+#include "filter_call.hpp"
 
 namespace rt {
 namespace {
@@ -36,54 +37,43 @@ int temporal_device(uint32_t width, uint32_t height, const TemporalParams& prm, 
                     const double* depth, const double* alpha, const double* prev_linear_rgb, const double* prev_variance_rgb, const double* prev_length,
                     const double* prev_normal, const double* prev_depth, const double* prev_alpha, double* out_linear_rgb, uint8_t* out_rgba8,
                     double* out_variance_rgb, double* out_length, double* out_prev_xy, double* kernel_ms) {
-    if (int rc = require_device("temporal_accumulate")) return rc;
-    const char* const at = "temporal_accumulate: ";
-    const size_t npx = size_t(width) * height;
+    FilterCall fc;
+    if (int rc = fc.open("temporal_accumulate", width, height)) return rc;
     const bool has_var = prm.has_variance != 0, has_history = prm.has_history != 0;
     DevBuf<double> d_lin, d_var, d_normal, d_depth, d_alpha, d_plin, d_pvar, d_plen, d_pnormal, d_pdepth, d_palpha, d_out, d_ovar, d_len, d_xy;
     DevBuf<uint8_t> d_rgba;
-    HIP_TRY_AS(at, upload(d_lin, linear_rgb, npx * 3));
-    if (has_var) HIP_TRY_AS(at, upload(d_var, variance_rgb, npx * 3));
-    HIP_TRY_AS(at, upload(d_normal, normal, npx * 3));
-    HIP_TRY_AS(at, upload(d_depth, depth, npx));
-    HIP_TRY_AS(at, upload(d_alpha, alpha, npx));
+    fc.upload(d_lin, linear_rgb, 3);
+    if (has_var) fc.upload(d_var, variance_rgb, 3);
+    fc.upload(d_normal, normal, 3);
+    fc.upload(d_depth, depth, 1);
+    fc.upload(d_alpha, alpha, 1);
     if (has_history) {
-        HIP_TRY_AS(at, upload(d_plin, prev_linear_rgb, npx * 3));
-        if (has_var) HIP_TRY_AS(at, upload(d_pvar, prev_variance_rgb, npx * 3));
-        HIP_TRY_AS(at, upload(d_plen, prev_length, npx));
-        HIP_TRY_AS(at, upload(d_pnormal, prev_normal, npx * 3));
-        HIP_TRY_AS(at, upload(d_pdepth, prev_depth, npx));
-        HIP_TRY_AS(at, upload(d_palpha, prev_alpha, npx));
+        fc.upload(d_plin, prev_linear_rgb, 3);
+        if (has_var) fc.upload(d_pvar, prev_variance_rgb, 3);
+        fc.upload(d_plen, prev_length, 1);
+        fc.upload(d_pnormal, prev_normal, 3);
+        fc.upload(d_pdepth, prev_depth, 1);
+        fc.upload(d_palpha, prev_alpha, 1);
     }
-    HIP_TRY_AS(at, d_out.alloc(npx * 3));
-    if (has_var) HIP_TRY_AS(at, d_ovar.alloc(npx * 3));
-    HIP_TRY_AS(at, d_len.alloc(npx));
-    HIP_TRY_AS(at, d_xy.alloc(npx * 2));
-    HIP_TRY_AS(at, d_rgba.alloc(npx * 4));
-    Event ev0, ev1;
-    HIP_TRY_AS(at, create_event(ev0));
-    HIP_TRY_AS(at, create_event(ev1));
+    fc.alloc(d_out, 3);
+    if (has_var) fc.alloc(d_ovar, 3);
+    fc.alloc(d_len, 1);
+    fc.alloc(d_xy, 2);
+    fc.alloc(d_rgba, 4);
 
-    const hipStream_t stream = nullptr;
     const dim3 block(TEMPORAL_BLOCK_X, TEMPORAL_BLOCK_Y);
     const dim3 grid((width + TEMPORAL_BLOCK_X - 1) / TEMPORAL_BLOCK_X, (height + TEMPORAL_BLOCK_Y - 1) / TEMPORAL_BLOCK_Y);
-    HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
-    hipLaunchKernelGGL(temporal_accumulate_kernel, grid, block, 0, stream, width, height, prm, d_lin.p, d_var.p, d_normal.p, d_depth.p, d_alpha.p, d_plin.p,
+    if (int rc = fc.start()) return rc;
+    hipLaunchKernelGGL(temporal_accumulate_kernel, grid, block, 0, fc.stream, width, height, prm, d_lin.p, d_var.p, d_normal.p, d_depth.p, d_alpha.p, d_plin.p,
                        d_pvar.p, d_plen.p, d_pnormal.p, d_pdepth.p, d_palpha.p, d_out.p, d_rgba.p, d_ovar.p, d_len.p, d_xy.p);
-    HIP_TRY_AS(at, hipGetLastError());
-    HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
-    HIP_TRY_AS(at, hipDeviceSynchronize());
-    if (kernel_ms) {
-        float ms = 0;
-        HIP_TRY_AS(at, hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-        *kernel_ms = ms;
-    }
-    if (out_linear_rgb) HIP_TRY_AS(at, hipMemcpy(out_linear_rgb, d_out.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_rgba8) HIP_TRY_AS(at, hipMemcpy(out_rgba8, d_rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_variance_rgb && has_var) HIP_TRY_AS(at, hipMemcpy(out_variance_rgb, d_ovar.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_length) HIP_TRY_AS(at, hipMemcpy(out_length, d_len.p, npx * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_prev_xy) HIP_TRY_AS(at, hipMemcpy(out_prev_xy, d_xy.p, npx * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    return RTTNW_OK;
+    HIP_TRY_AS(fc.at, hipGetLastError());
+    if (int rc = fc.finish(kernel_ms)) return rc;
+    fc.copy_out(out_linear_rgb, d_out, 3);
+    fc.copy_out(out_rgba8, d_rgba, 4);
+    if (has_var) fc.copy_out(out_variance_rgb, d_ovar, 3);
+    fc.copy_out(out_length, d_len, 1);
+    fc.copy_out(out_prev_xy, d_xy, 2);
+    return fc.rc;
 }
 
 } // namespace rt

@@ -11,6 +11,7 @@
 //                               most of the frame.
 // No atomics.
 #include "feature_api.hpp"
+#include "filter_call.hpp"
 
 namespace rt {
 namespace {
@@ -110,54 +111,18 @@ int variance_device(uint32_t width, uint32_t height, const TemporalParams& prm, 
                     const double* depth, const double* alpha, const double* prev_linear_rgb, const double* prev_moment2_rgb, const double* prev_length,
                     const double* prev_normal, const double* prev_depth, const double* prev_alpha, double* out_linear_rgb, uint8_t* out_rgba8,
                     double* out_moment2_rgb, double* out_length, double* out_prev_xy, double* out_variance_rgb, double* kernel_ms) {
-    if (int rc = require_device("temporal_variance")) return rc;
-    const char* const at = "temporal_variance: ";
-    const size_t npx = size_t(width) * height;
-    const bool has_history = prm.has_history != 0;
-    DevBuf<double> d_lin, d_normal, d_depth, d_alpha, d_plin, d_pm2, d_plen, d_pnormal, d_pdepth, d_palpha, d_out, d_m2, d_len, d_xy, d_var;
-    DevBuf<uint8_t> d_rgba;
-    HIP_TRY_AS(at, upload(d_lin, linear_rgb, npx * 3));
-    HIP_TRY_AS(at, upload(d_normal, normal, npx * 3));
-    HIP_TRY_AS(at, upload(d_depth, depth, npx));
-    HIP_TRY_AS(at, upload(d_alpha, alpha, npx));
-    if (has_history) {
-        HIP_TRY_AS(at, upload(d_plin, prev_linear_rgb, npx * 3));
-        HIP_TRY_AS(at, upload(d_pm2, prev_moment2_rgb, npx * 3));
-        HIP_TRY_AS(at, upload(d_plen, prev_length, npx));
-        HIP_TRY_AS(at, upload(d_pnormal, prev_normal, npx * 3));
-        HIP_TRY_AS(at, upload(d_pdepth, prev_depth, npx));
-        HIP_TRY_AS(at, upload(d_palpha, prev_alpha, npx));
-    }
-    HIP_TRY_AS(at, d_out.alloc(npx * 3));
-    HIP_TRY_AS(at, d_m2.alloc(npx * 3));
-    HIP_TRY_AS(at, d_len.alloc(npx));
-    HIP_TRY_AS(at, d_xy.alloc(npx * 2));
-    HIP_TRY_AS(at, d_var.alloc(npx * 3));
-    HIP_TRY_AS(at, d_rgba.alloc(npx * 4));
-    if (int rc = variance_admit_lds(at, vprm.radius)) return rc; // before the clock starts
-    Event ev0, ev1;
-    HIP_TRY_AS(at, create_event(ev0));
-    HIP_TRY_AS(at, create_event(ev1));
+    FilterCall fc;
+    if (int rc = fc.open("temporal_variance", width, height)) return rc;
+    MomentBuffers d;
+    d.stage(fc, prm.has_history != 0, linear_rgb, normal, depth, alpha, prev_linear_rgb, prev_moment2_rgb, prev_length, prev_normal, prev_depth, prev_alpha);
+    if (int rc = variance_admit_lds(fc.at.c_str(), vprm.radius)) return rc; // before the clock starts
 
-    const hipStream_t stream = nullptr;
-    HIP_TRY_AS(at, hipEventRecord(ev0.get(), stream));
-    if (int rc = variance_passes_device(at, width, height, &prm, vprm, d_lin.p, d_normal.p, d_depth.p, d_alpha.p, d_plin.p, d_pm2.p, d_plen.p, d_pnormal.p,
-                                        d_pdepth.p, d_palpha.p, d_out.p, d_rgba.p, d_m2.p, d_len.p, d_xy.p, d_var.p, stream)) return rc;
-    HIP_TRY_AS(at, hipEventRecord(ev1.get(), stream));
-    HIP_TRY_AS(at, hipDeviceSynchronize());
-    if (kernel_ms) {
-        float ms = 0;
-        HIP_TRY_AS(at, hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-        *kernel_ms = ms;
-    }
-    const size_t bytes = npx * 3 * sizeof(double);
-    if (out_linear_rgb) HIP_TRY_AS(at, hipMemcpy(out_linear_rgb, d_out.p, bytes, hipMemcpyDeviceToHost));
-    if (out_rgba8) HIP_TRY_AS(at, hipMemcpy(out_rgba8, d_rgba.p, npx * 4, hipMemcpyDeviceToHost));
-    if (out_moment2_rgb) HIP_TRY_AS(at, hipMemcpy(out_moment2_rgb, d_m2.p, bytes, hipMemcpyDeviceToHost));
-    if (out_length) HIP_TRY_AS(at, hipMemcpy(out_length, d_len.p, npx * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_prev_xy) HIP_TRY_AS(at, hipMemcpy(out_prev_xy, d_xy.p, npx * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_variance_rgb) HIP_TRY_AS(at, hipMemcpy(out_variance_rgb, d_var.p, bytes, hipMemcpyDeviceToHost));
-    return RTTNW_OK;
+    if (int rc = fc.start()) return rc;
+    if (int rc = variance_passes_device(fc.at.c_str(), width, height, &prm, vprm, d.lin.p, d.normal.p, d.depth.p, d.alpha.p, d.plin.p, d.pm2.p, d.plen.p,
+                                        d.pnormal.p, d.pdepth.p, d.palpha.p, d.out.p, d.rgba.p, d.m2.p, d.len.p, d.xy.p, d.var.p, fc.stream)) return rc;
+    if (int rc = fc.finish(kernel_ms)) return rc;
+    d.copy_out(fc, out_linear_rgb, out_rgba8, out_moment2_rgb, out_length, out_prev_xy, out_variance_rgb);
+    return fc.rc;
 }
 
 } // namespace rt
