@@ -853,16 +853,23 @@ def lattice_mask(width, height, level):
     return m
 
 
-def reconstruct(linear, valid, features, stderr=None, iterations=5, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0, want_ms=False):
+def reconstruct(linear, valid, features, stderr=None, iterations=5, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0, want_ms=False,
+                variance=None):
     """`rttnw_reconstruct`: `denoise` over an image of which only the pixels with a nonzero byte in `valid` (HxW) hold a value — the taps that
-    hold nothing are dropped, the pixels that hold nothing are filled from those that do.  `linear` and `stderr` are never read where `valid` is 0.
+    hold nothing are dropped, the pixels that hold nothing are filled from those that do.  `stderr` (HxWx3) is squared into the variance of the
+    pixel means; `variance` (HxWx3, in place of `stderr`) is that variance as it stands, so that an infinite, NaN or zero one arrives exactly.
+    `linear`, `stderr` and `variance` are never read where `valid` is 0.
     Returns (linear HxWx3 f64, rgba8 HxWx4 u8 with alpha 0 where nothing could be filled, variance HxWx3 f64 or None, valid HxW u8) — and the
     device time in ms after them with `want_ms`."""
     b = library.product()
     lin = np.ascontiguousarray(linear, dtype=np.float64)
     h, w = lin.shape[:2]
     ok = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+    if stderr is not None and variance is not None:
+        raise ValueError("reconstruct: stderr or variance, not both")
     var = None if stderr is None else np.ascontiguousarray(np.square(np.asarray(stderr, dtype=np.float64)))
+    if variance is not None:
+        var = np.ascontiguousarray(variance, dtype=np.float64)
     assert lin.shape == (h, w, 3) and ok.shape == (h, w)
     f = _feature_arrays(features, h, w)
     assert var is None or var.shape == (h, w, 3)

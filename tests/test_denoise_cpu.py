@@ -4,6 +4,7 @@ the contract promises."""
 import numpy as np
 import pytest
 
+import denoise_cases
 import denoise_ref
 
 
@@ -42,71 +43,58 @@ def test_explicit_sigmas_reach_the_weights(host):
 
 
 def test_zero_iterations_is_the_identity(host):
-    rng = np.random.default_rng(1)
-    colour, var, f = denoise_ref.random_inputs(rng, 37, 29)
-    out, rgba, out_var = host(colour, var, f, 0)
-    assert _same_bits(out, colour) and _same_bits(out_var, var)
-    assert np.array_equal(rgba, denoise_ref.quantise(colour))
+    denoise_cases.check_zero_iterations_is_the_identity(host)
 
 
 def test_a_constant_image_stays_constant(host):
-    h, w = 48, 40
-    f = {"albedo": np.full((h, w, 3), 0.73), "normal": np.tile([0.0, 0.6, 0.8], (h, w, 1)), "depth": np.full((h, w), 12.5),
-         "alpha": np.ones((h, w))}
-    colour = np.tile([0.31, 1.7, 0.052], (h, w, 1))
-    var = np.full((h, w, 3), 1e-3)
-    for v in (None, var):
-        out, _, _ = host(colour, v, f, 5)
-        # 25 taps of normalised weights: the sum of w c over the sum of w, each within a few ulp of c
-        assert np.all(np.abs(out - colour) <= 32 * np.spacing(colour)), np.abs(out - colour).max()
+    denoise_cases.check_a_constant_image_stays_constant(host)
 
 
 def test_alpha_zero_pixels_pass_through_and_reach_no_neighbour(host):
-    rng = np.random.default_rng(2)
-    colour, var, f = denoise_ref.random_inputs(rng, 37, 29)
-    sky = f["alpha"] == 0.0
-    assert sky.sum() > 50
-    out, _, out_var = host(colour, var, f, 4)
-    assert _same_bits(out[sky], colour[sky]) and _same_bits(out_var[sky], var[sky])
-    other = colour.copy()
-    other[sky] = rng.exponential(50.0, size=(int(sky.sum()), 3))
-    f2 = dict(f, albedo=f["albedo"].copy(), normal=f["normal"].copy(), depth=f["depth"].copy())
-    f2["albedo"][sky], f2["normal"][sky], f2["depth"][sky] = 0.9, [0.0, 0.0, 1.0], 5.0
-    out2, _, _ = host(other, var, f2, 4)
-    assert _same_bits(out2[~sky], out[~sky])
-    assert _same_bits(out2[sky], other[sky])
+    denoise_cases.check_alpha_zero_pixels_pass_through_and_reach_no_neighbour(host)
 
 
 def test_no_colour_crosses_an_edge_between_orthogonal_normals(host):
-    rng = np.random.default_rng(3)
-    h, w = 40, 48
-    left = np.zeros((h, w), dtype=bool)
-    left[:, : w // 2] = True
-    normal = np.where(left[..., None], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]) * np.ones((h, w, 1))
-    f = {"albedo": np.full((h, w, 3), 0.5), "normal": normal, "depth": np.full((h, w), 10.0), "alpha": np.ones((h, w))}
-    colour = rng.exponential(1.0, size=(h, w, 3))
-    out, _, _ = host(colour, None, f, 5)
-    other = colour.copy()
-    other[~left] += 100.0
-    out2, _, _ = host(other, None, f, 5)
-    assert _same_bits(out2[left], out[left])                       # w_n = 0 exactly across the edge
-    assert np.all(out2[~left] > 90.0) and np.all(out[left] < 20.0)
-    assert out[left].std() < 0.5 * colour[left].std()              # ... while each side was smoothed
+    denoise_cases.check_no_colour_crosses_an_edge_between_orthogonal_normals(host)
 
 
 def test_a_variance_that_is_not_finite_is_treated_as_absent(host):
-    rng = np.random.default_rng(4)
-    colour, _, f = denoise_ref.random_inputs(rng, 37, 29, with_variance=False)
-    plain, _, _ = host(colour, None, f, 3)
-    for bad in (np.inf, np.nan):
-        out, _, out_var = host(colour, np.full(colour.shape, bad), f, 3)
-        assert _same_bits(out, plain)
-        assert not np.isfinite(out_var).any()
-    # one pixel without a variance among pixels that have one: it is filtered with w_l = 1, and keeps its own variance
-    var = np.full(colour.shape, 0.04)
-    var[10, 10] = np.inf
-    f1 = dict(f, alpha=np.ones_like(f["alpha"]))
-    out, _, out_var = host(colour, var, f1, 1)
-    want, _, want_var = denoise_ref.denoise(colour, var, f1, 1)
-    assert _same_bits(out, want) and _same_bits(out_var, want_var)
-    assert np.isinf(out_var[10, 10]).all() and np.isfinite(out_var[10, 11]).all()
+    denoise_cases.check_a_variance_that_is_not_finite_is_treated_as_absent(host)
+
+
+# ---- the frames of tests/denoise_cases.py: what the device is held to in tests/test_gpu_denoise.py, anchored here without one
+
+@pytest.mark.parametrize("size,with_variance", denoise_cases.FRAMES, ids=denoise_cases.FRAME_IDS)
+def test_hostile_frames_hold_every_kind_of_value(size, with_variance):
+    """From the inputs alone: every frame of 297 pixels or more has hit pixels with a zero normal, a negative and a zero depth, fractional alpha, an
+    albedo channel in (0, 1e-3] and one below the threshold beside one above it, pixels with alpha 0, and each of an infinite, a NaN and a zero
+    variance."""
+    counts = denoise_cases.assert_not_vacuous(size, with_variance)
+    assert len(counts) == (10 if with_variance else 7)
+    colour, var, f = denoise_cases.frame(size, with_variance)
+    assert colour.shape == (size[1], size[0], 3) and f["depth"].shape == (size[1], size[0])
+
+
+@pytest.mark.parametrize("size,with_variance", denoise_cases.FRAMES, ids=denoise_cases.FRAME_IDS)
+def test_host_build_equals_the_numpy_restatement_on_hostile_frames(host, size, with_variance):
+    """Every size, iteration count (up to the 8 the entry point allows: strides beyond the frame) and sigma set; every pixel of every output."""
+    colour, var, f = denoise_cases.frame(size, with_variance)
+    for iterations in denoise_cases.ITERATIONS:
+        for k, sigmas in enumerate(denoise_cases.SIGMAS):
+            got = host(colour, var, f, iterations, **sigmas)
+            denoise_cases.assert_same_results(got, denoise_cases.denoise_reference(size, with_variance, iterations, k), (iterations, k))
+            assert (got[2] is None) == (not with_variance)
+
+
+def test_passes_6_to_8_change_the_image_and_the_farthest_tap_weighs(host):
+    for with_variance in (True, False):
+        five, eight = (denoise_cases.denoise_reference((129, 7), with_variance, it, 0)[0] for it in (5, 8))
+        assert not denoise_cases.same(five, eight)
+    denoise_cases.check_far_tap(host)
+    denoise_cases.check_far_tap(host, transposed=True)
+
+
+@pytest.mark.parametrize("with_variance", [True, False])
+def test_a_pixel_depends_on_the_stated_margin_of_pixels_around_it(host, with_variance):
+    denoise_cases.check_locality(host, with_variance)
+    denoise_cases.check_locality(denoise_ref.denoise, with_variance)

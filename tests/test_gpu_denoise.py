@@ -3,6 +3,7 @@ renders, and the filter lowers the error against the CPU oracle's converged wind
 import numpy as np
 import pytest
 
+import denoise_cases
 import denoise_ref
 from golden_cases import WINDOWS, load_windows
 from rttnw_amd import abi, library, render
@@ -95,3 +96,50 @@ def test_final_scene_windows_are_recorded(scenes, adaptive):
     for key, noisy, den in rows:
         print("%s %s: MSE noisy %.4g, denoised %.4g, ratio %.2f" % (key, "variance" if adaptive else "no variance", noisy, den, noisy / den))
         assert np.isfinite(noisy) and np.isfinite(den)
+
+
+# ---- the frames of tests/denoise_cases.py: sizes no render here has, values no render has, all eight passes
+
+def _device(colour, variance, f, iterations, **sigmas):
+    """rttnw_denoise as a `run` of tests/denoise_cases.py: the variance as it stands, so an infinite, a NaN and a zero one arrive exactly."""
+    return render.denoise(colour, f, iterations=iterations, variance=variance, **sigmas)
+
+
+@pytest.mark.parametrize("size,with_variance", denoise_cases.FRAMES, ids=denoise_cases.FRAME_IDS)
+def test_device_equals_restatement_and_host_harness_on_hostile_frames(gpu, host, size, with_variance):
+    """Every size, iteration count and sigma set of tests/denoise_cases.py; every pixel of the linear image, its RGBA8 and its variance, against
+    the numpy restatement and against the host build."""
+    denoise_cases.assert_not_vacuous(size, with_variance)
+    colour, var, f = denoise_cases.frame(size, with_variance)
+    for iterations in denoise_cases.ITERATIONS:
+        for k, sigmas in enumerate(denoise_cases.SIGMAS):
+            got = _device(colour, var, f, iterations, **sigmas)
+            denoise_cases.assert_same_results(got, denoise_cases.denoise_reference(size, with_variance, iterations, k), (iterations, k))
+            denoise_cases.assert_same_results(got, host(colour, var, f, iterations, **sigmas), (iterations, k, "host"))
+            assert (got[2] is None) == (not with_variance)
+
+
+@pytest.mark.parametrize("check", denoise_cases.PROPERTIES, ids=[c.__name__[6:] for c in denoise_cases.PROPERTIES])
+def test_the_contract_properties_hold_on_the_device(gpu, check):
+    check(_device)
+
+
+def test_passes_6_to_8_change_the_image_and_the_farthest_tap_weighs(gpu):
+    """129x7: eight iterations are not five — the passes whose stride exceeds most of the frame still run —, and the one tap of pass 8 that lies
+    inside the image (column 0 to column 128, row 0 to row 128 of 7x129) is neither dropped nor wrapped: bit for bit the restatement, in which
+    it weighs."""
+    for with_variance in (True, False):
+        colour, var, f = denoise_cases.frame((129, 7), with_variance)
+        five, eight = (_device(colour, var, f, it)[0] for it in (5, 8))
+        assert not denoise_cases.same(five, eight)
+        assert denoise_cases.same(eight, denoise_cases.denoise_reference((129, 7), with_variance, 8, 0)[0])
+    denoise_cases.check_far_tap(_device)
+    denoise_cases.check_far_tap(_device, transposed=True)
+
+
+@pytest.mark.parametrize("with_variance", [True, False], ids=["variance", "no-variance"])
+def test_a_pixel_depends_on_the_stated_margin_of_pixels_around_it(gpu, with_variance):
+    """A 53x33 crop of the 70x41 frame, its origin (5, 3) off the 32x8 blocks, 2 iterations: 6 pixels in from the crop's edge every pixel is the
+    whole frame's, bit for bit; 5 pixels in it is not (tests/denoise_cases.py says why 6; tests/test_denoise_cpu.py holds the host build and the
+    restatement to both halves)."""
+    denoise_cases.check_locality(_device, with_variance)

@@ -3,6 +3,7 @@ renders of which only a lattice holds a value — the rest poisoned with NaN —
 import numpy as np
 import pytest
 
+import denoise_cases
 import reconstruct_ref
 from rttnw_amd import abi, library, render
 from rttnw_amd import scene as S
@@ -98,3 +99,32 @@ def test_every_pixel_valid_is_rttnw_denoise(frames, name, size, with_variance):
             assert np.array_equal(_bits(out_var), _bits(want_var)), iterations
         else:
             assert out_var is None and want_var is None
+
+
+# ---- the frames and masks of tests/denoise_cases.py: sizes, values and validity patterns no render here has, all eight passes
+
+@pytest.mark.parametrize("size,with_variance", denoise_cases.FRAMES, ids=denoise_cases.FRAME_IDS)
+def test_device_equals_restatement_and_host_harness_on_hostile_frames(gpu, host, size, with_variance):
+    """Every size, mask, iteration count and sigma set of tests/denoise_cases.py; every pixel of the linear image, its RGBA8, its variance and
+    out_valid, against the numpy restatement and against the host build.  The variance travels as it stands (`variance=`)."""
+    f = denoise_cases.frame(size, with_variance)[2]
+    for name, (c, v, valid) in denoise_cases.masked_frames(size, with_variance).items():
+        for iterations in denoise_cases.ITERATIONS:
+            for k, sigmas in enumerate(denoise_cases.SIGMAS):
+                got = render.reconstruct(c, valid, f, iterations=iterations, variance=v, **sigmas)
+                want = denoise_cases.reconstruct_reference(size, with_variance, name, iterations, k)
+                denoise_cases.assert_same_results(got, want, (name, iterations, k))
+                denoise_cases.assert_same_results(got, host(c, v, valid, f, iterations, **sigmas), (name, iterations, k, "host"))
+                assert np.isfinite(got[0]).all() and (got[2] is None) == (not with_variance)
+    if size == (45, 37) and with_variance:
+        assert min(denoise_cases.fill_counts(size, True, "random0.02", 5)) > 0          # filled, never filled, filled without a variance
+
+
+def test_stderr_and_variance_are_one_input(gpu):
+    colour, var, f = denoise_cases.frame((33, 9), False)
+    stderr = np.full(colour.shape, 0.25)
+    valid = denoise_cases.masked_frames((33, 9), False)["random0.3"][2]
+    denoise_cases.assert_same_results(render.reconstruct(colour, valid, f, stderr, iterations=2),
+                                      render.reconstruct(colour, valid, f, iterations=2, variance=np.square(stderr)))
+    with pytest.raises(ValueError):
+        render.reconstruct(colour, valid, f, stderr, variance=np.square(stderr))

@@ -4,6 +4,7 @@ pattern, with the invalid pixels poisoned — and the properties the contract pr
 import numpy as np
 import pytest
 
+import denoise_cases
 import denoise_ref
 import reconstruct_ref
 
@@ -146,3 +147,29 @@ def test_nothing_is_filled_across_an_edge_between_orthogonal_normals(host):
     out, _, _, ok = host(colour, None, valid, f, 5)
     assert np.array_equal(ok != 0, left)                        # w_n = 0 exactly across the edge: the right wall holds nothing
     assert (out[~left] == 0.0).all() and np.all(np.abs(out[left] - 1.0) < 1e-12)
+
+
+# ---- the frames and masks of tests/denoise_cases.py: what the device is held to in tests/test_gpu_reconstruct.py, anchored here without one
+
+@pytest.mark.parametrize("size,with_variance", denoise_cases.FRAMES, ids=denoise_cases.FRAME_IDS)
+def test_host_build_equals_the_numpy_restatement_on_hostile_frames(host, size, with_variance):
+    """Every size, mask, iteration count and sigma set; every pixel of every output, the invalid pixels poisoned with NaN."""
+    f = denoise_cases.frame(size, with_variance)[2]
+    masks = denoise_cases.masked_frames(size, with_variance)
+    assert list(masks) == denoise_cases.MASK_IDS
+    for name, (c, v, valid) in masks.items():
+        assert np.isnan(c[~valid]).all() and (v is None or np.isnan(v[~valid]).all())
+        for iterations in denoise_cases.ITERATIONS:
+            for k, sigmas in enumerate(denoise_cases.SIGMAS):
+                got = host(c, v, valid, f, iterations, **sigmas)
+                want = denoise_cases.reconstruct_reference(size, with_variance, name, iterations, k)
+                denoise_cases.assert_same_results(got, want, (name, iterations, k))
+                assert np.isfinite(got[0]).all(), (name, iterations, k)             # a NaN of an invalid pixel reaches nothing
+
+
+def test_the_sparse_mask_reaches_every_branch_of_the_fill():
+    """45x37 with 2 pixels in 100 valid, 5 passes, on the restatement's output: pixels filled from their taps, pixels never filled (a zero normal,
+    or nothing in reach), and filled pixels none of whose taps had a finite variance (theirs is +inf).  Measured: 1294, 58 and 18."""
+    filled, never, no_variance = denoise_cases.fill_counts((45, 37), True, "random0.02", 5)
+    print("filled %d, never filled %d, filled with no finite-variance tap %d" % (filled, never, no_variance))
+    assert filled > 0 and never > 0 and no_variance > 0
