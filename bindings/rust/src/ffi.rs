@@ -367,6 +367,9 @@ extern "C" {
     pub fn rttnw_temporal_probe(width: u32, height: u32, cam: *const rttnw_camera_desc, prev_cam: *const rttnw_camera_desc, normal: *const f64, depth: *const f64, alpha: *const f64, prev_length: *const f64, prev_normal: *const f64, prev_depth: *const f64, prev_alpha: *const f64, t: *const rttnw_temporal_params, a: *const rttnw_sampling_params, out_length: *mut f64, out_prev_xy: *mut f64, out_multiplier: *mut u8, kernel_ms: *mut f64) -> c_int;
     pub fn rttnw_svgf_set_sampling(q: *mut rttnw_svgf, a: *const rttnw_sampling_params) -> c_int;
     pub fn rttnw_svgf_samples(q: *mut rttnw_svgf, out_spp: *mut u32, out_length: *mut f64) -> c_int;
+    pub fn rttnw_svgf_set_regress(q: *mut rttnw_svgf, g: *const rttnw_regress_params, variance_source: u32) -> c_int;
+    pub fn rttnw_svgf_push_halves(q: *mut rttnw_svgf, cam: *const rttnw_camera_desc, half_a: *const f64, half_b: *const f64, albedo: *const f64, normal: *const f64, depth: *const f64, alpha: *const f64, out: *const rttnw_svgf_out) -> c_int;
+    pub fn rttnw_svgf_halves(q: *mut rttnw_svgf, out_acc_a: *mut f64, out_acc_b: *mut f64, out_filtered_a: *mut f64, out_filtered_b: *mut f64, out_fit: *mut f64) -> c_int;
     pub fn rttnw_svgf_create(width: u32, height: u32, q: *const rttnw_svgf_params, out: *mut *mut rttnw_svgf) -> c_int;
     pub fn rttnw_svgf_destroy(q: *mut rttnw_svgf);
     pub fn rttnw_svgf_reset(q: *mut rttnw_svgf) -> c_int;

@@ -45,8 +45,8 @@ extern "C" {
                              *  rttnw_render_adaptive_denoised, rttnw_reconstruct, rttnw_render_preview, rttnw_budget_select,
                              *  rttnw_render_adaptive_budget, rttnw_render_adaptive_budget_denoised, rttnw_denoise_nlm,
                              *  rttnw_denoise_select, rttnw_temporal_accumulate, rttnw_temporal_variance, the rttnw_svgf_create family, rttnw_temporal_clamp,
-                             *  rttnw_svgf_set_clamp, rttnw_svgf_clipped, rttnw_temporal_probe, rttnw_svgf_set_sampling, rttnw_svgf_samples and
-                             *  rttnw_denoise_regress came later, without a version bump: a caller detects each by its symbol) */
+                             *  rttnw_svgf_set_clamp, rttnw_svgf_clipped, rttnw_temporal_probe, rttnw_svgf_set_sampling, rttnw_svgf_samples,
+                             *  rttnw_denoise_regress, rttnw_svgf_set_regress, rttnw_svgf_push_halves and rttnw_svgf_halves came later, without a version bump: a caller detects each by its symbol) */
 
 typedef struct rttnw_scene rttnw_scene; /* opaque */
 typedef int32_t rttnw_id;
@@ -529,7 +529,8 @@ int rttnw_denoise_select(uint32_t width, uint32_t height, const double* half_a, 
  *   features != 0 with a NULL array among those it selects — alpha whenever features != 0, albedo with bit 1, normal with bit 2, depth with
  *   bit 4; demodulate != 0 with a NULL albedo or alpha.
  * Out of scope: offering this filter to rttnw_denoise_select as a third candidate, prefiltering the features, a second-order or
- *   per-channel-bandwidth fit, steering the adaptive rounds by out_error_rgb or out_fit, the SVGF handle, a node-wide form, the native rttnw
+ *   per-channel-bandwidth fit, steering the adaptive rounds by out_error_rgb or out_fit, the SVGF handle (which now lives below, at
+ *   rttnw_svgf_set_regress), a node-wide form, the native rttnw
  *   program. */
 struct rttnw_regress_params {
     uint32_t search_radius, patch_radius; /* r, f: as rttnw_nlm_params; 0 = 7, 3; r <= 16, f <= 4 */
@@ -710,7 +711,8 @@ int rttnw_temporal_variance(uint32_t width, uint32_t height, const rttnw_camera_
  *   demodulate > 1; reserved0 != 0; for rttnw_svgf_frame a size that differs from the handle's or tile_world != 1.
  * One call at a time per handle; handles are independent of each other.
  * Out of scope: a node-wide form; adaptive sampling inside the sequence; colour clamping of the history; the non-local-means and select filters
- *   as the spatial stage; the native rttnw program; moving geometry. */
+ *   as the spatial stage (non-local means and the regression filter now live below, at rttnw_svgf_set_regress; select stays out); the native rttnw
+ *   program; moving geometry. */
 typedef struct rttnw_svgf rttnw_svgf; /* opaque */
 struct rttnw_svgf_params {
     uint32_t feedback_iterations; /* 0: the history is the unfiltered accumulation; j >= 1: the colour history is the filter's result after j
@@ -884,6 +886,55 @@ int rttnw_temporal_probe(uint32_t width, uint32_t height, const rttnw_camera_des
                          double* out_length, double* out_prev_xy, uint8_t* out_multiplier, double* kernel_ms);
 int rttnw_svgf_set_sampling(rttnw_svgf* q, const rttnw_sampling_params* a);  /* NULL: off, the default */
 int rttnw_svgf_samples(rttnw_svgf* q, uint32_t* out_spp, double* out_length); /* w*h each, optional: the last rttnw_svgf_frame call's map */
+
+/* The regression filter as the SVGF spatial stage: the handle carries two half-buffer histories along its reprojection and hands them, with its
+ * temporal variance estimate, to rttnw_denoise_regress.  The handle's block above leaves the non-local-means filter as the spatial stage out of its
+ * scope, and rttnw_denoise_regress's leaves out the SVGF handle; both now live here.  rttnw_denoise leans on the first hit alone and blurs what it
+ * does not describe — a noise texture, what mirrors and glass show; rttnw_denoise_nlm and rttnw_denoise_regress measure their weights on the colour,
+ * but on a single frame they measure them on two halves of a few samples each.  Here the weights are measured on ACCUMULATED halves.  With
+ * g->features == 0 the same switch gives non-local means as the spatial stage.  No new struct: rttnw_svgf_params and rttnw_svgf_out are unchanged.
+ *
+ * rttnw_svgf_set_regress switches the stage on for an rttnw_svgf handle (g NULL: off, the default); variance_source chooses the variances the
+ *   filter's weights read: 0 the handle's temporal estimate, 1 the filter's own pair variance.  Setting or clearing the stage resets the history,
+ *   as rttnw_svgf_reset does (a history without the halves is none); a NULL g on a handle without the stage is a no-op and keeps the history.
+ *   Every buffer the stage needs is allocated there and then and the filter kernel's dynamic LDS is admitted — a second packed trace buffer, the
+ *   two ingested halves, Ha and Hb as ping-pong pairs, and the filter's workspace (records, the two filtered halves, fit bytes, error, fit): frame
+ *   calls still allocate nothing.  The stage is exclusive with feedback_iterations != 0, a clamp and sampling.
+ * The contract is a composition of the existing entry points, bit for bit.  With the stage set the state gains Ha and Hb, the accumulated halves;
+ *   the rest of the state is unchanged.  A call has the halves a and b, features F and camera cam; cam' is the state's camera.
+ *   C = (a + b) * 0.5: this is raw_rgb.
+ * 0. The handle's step 0 applied to C, a and b separately, giving c, ca, cb; the "was divided" channels are C's (the rule reads F only).
+ * 1. The handle's step 1 on c, unchanged: TV = rttnw_temporal_variance(...) gives M1, M2, L, prev_xy and var.  Consequence: these five, and
+ *    moment1_rgb, moment2_rgb, length, prev_xy and variance_rgb, equal bit for bit those of a plain handle (feedback 0, the same t, v and demodulate)
+ *    pushed with C.
+ * 2. With a state, Aa = rttnw_temporal_accumulate(cam, cam', ca, no variances, F, prev_linear_rgb = Ha, prev_length = L, the state's normal, depth
+ *    and alpha, t).out_linear_rgb, and Ab likewise from cb over Hb; on the device the four taps are computed once and carry four quantities.  Without
+ *    a state Aa = ca and Ab = cb.  The new Ha and Hb are Aa and Ab: there is no feedback.
+ * 3. R = rttnw_denoise_regress(Aa, Ab, var_a, var_b, F.albedo, F.normal, F.depth, F.alpha, g).  variance_source 0: var_a = var_b = var + var, one
+ *    sum — each half is a mean over half the samples of M1, so its variance is twice M1's.  variance_source 1: both NULL, the filter's own pair
+ *    variance.  g->demodulate must be 0: the handle's demodulate does that job.  F.albedo is passed as a regressor, not as a divisor, also when the
+ *    handle demodulates.  With g->features == 0 this step is rttnw_denoise_nlm(Aa, Ab, var_a, var_b) bit for bit (property 1 of that contract).
+ * 5. Emit.  linear_rgb = R.out_linear_rgb multiplied back on the channels step 0 divided, rgba8 made from it; accumulated_rgb = (Aa + Ab) * 0.5
+ *    treated likewise; filtered_variance_rgb = R.out_error_rgb; history_rgb = M1; everything else as without the stage.
+ * rttnw_svgf_push_halves is rttnw_svgf_push for a handle with the stage: half_a and half_b (w*h*3 each) stand where linear_rgb stood.
+ * rttnw_svgf_frame on such a handle renders Ca = rttnw_render(spp = p->spp / 2, sample_begin) and Cb = rttnw_render(spp = p->spp / 2,
+ *   sample_begin + p->spp / 2), the feature pass as without the stage, and is then rttnw_svgf_push_halves of those, bit for bit in every
+ *   precision.  p->spp must be even and at least 2.  stats sums the two traces.
+ * rttnw_svgf_halves copies out, each array optional, Aa, Ab, R.out_half_a and R.out_half_b (w*h*3 each) and R.out_fit (w*h) of the last frame call,
+ *   in the filter's units; before any frame call with the stage — and after the stage was set anew or cleared — every array is all 0.
+ * Refusals, before the device is touched, each message naming the call, RTTNW_ERR_INVALID.  rttnw_svgf_set_regress, in this order: everything
+ *   rttnw_denoise_regress refuses for g, in its order; g->demodulate != 0; variance_source > 1; a NULL q (the handle is checked last); a handle with
+ *   feedback_iterations != 0, a clamp set or sampling set.  rttnw_svgf_set_clamp and rttnw_svgf_set_sampling with a non-NULL block refuse a handle
+ *   with the stage; rttnw_svgf_push refuses one; rttnw_svgf_push_halves refuses a handle without it, after rttnw_svgf_push's own checks;
+ *   rttnw_svgf_frame on a handle with the stage refuses an odd p->spp and p->spp < 2.
+ * Out of scope: rttnw_denoise_select as a stage; feeding the filtered halves back into Ha and Hb; a clamp or sampling together with this stage; a
+ *   sample-weighted blend; a node-wide form; the native rttnw program. */
+int rttnw_svgf_set_regress(rttnw_svgf* q, const rttnw_regress_params* g, uint32_t variance_source); /* g NULL: off, the default */
+int rttnw_svgf_push_halves(rttnw_svgf* q, const rttnw_camera_desc* cam, const double* half_a, const double* half_b,
+                           const double* albedo, const double* normal, const double* depth, const double* alpha,
+                           const rttnw_svgf_out* out);
+int rttnw_svgf_halves(rttnw_svgf* q, double* out_acc_a, double* out_acc_b, double* out_filtered_a, double* out_filtered_b,
+                      double* out_fit); /* w*h*3 x4, w*h; each optional; the last frame call's, in the filter's units */
 
 /* `render()` on the GPUs of ONE NODE, in one call from one host thread ("library owns its HIP
  * streams / RCCL comms"): the framebuffer's 8x8 tiles are interleaved over `ngpu` ranks, rank r traces its tiles on

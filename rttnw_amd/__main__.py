@@ -72,6 +72,11 @@ default, 1.0) and move it to the nearer bound outside — ghosts of reflections 
 --boost B (with --svgf; 1, 2, 4 or 8) gives pixels whose reprojected history is thin — disocclusions, the frame's edge, the first frame — up to B
 times --spp samples in that frame (rttnw_svgf_set_sampling): the largest of 1, 2, 4, 8 that is at most B and at most FILL / (history length + 1),
 --fill FILL (default 8).  --spp-map spp_%03d.png writes each frame's samples per pixel as a grey image (spp * 255 / (B * --spp)).
+--spatial nlm|regress (with --svgf; an even --spp) replaces the loop's à-trous filter by rttnw_denoise_nlm or rttnw_denoise_regress over two half
+histories the handle accumulates along the same reprojection (rttnw_svgf_set_regress): the weights are measured on accumulated halves, not on
+two halves of one frame.  --regress-variance temporal|pair chooses the variances those weights read: the loop's temporal estimate (the default)
+or the filter's own pair variance.  --fit-map fit_%03d.png writes each frame's fit count as a grey image.  The stage does not combine with
+--feedback, --clamp or --boost.
 """
 import argparse
 import sys
@@ -150,8 +155,19 @@ def refusal(args, refine, devices, window):
                       (args.nlm_k >= 0.0, "--nlm-k must be at least 0 (0: the default, 0.7)")]
     if args.blend_map is not None and not args.denoise_select:
         return "--blend-map needs --denoise-select: only that call has a blend weight"
-    if (args.ridge is not None or args.regress_features is not None or args.no_demodulate or args.fit_map is not None) and not args.denoise_regress:
+    staged = args.svgf and args.spatial in ("nlm", "regress")   # the regression filter as the loop's spatial stage: --fit-map goes with it too
+    if (args.ridge is not None or args.regress_features is not None or args.no_demodulate or (args.fit_map is not None and not staged)) and not args.denoise_regress:
         return "--ridge, --regress-features, --no-demodulate and --fit-map need --denoise-regress: only that call has them"
+    if (args.spatial is not None or args.regress_variance is not None) and not args.svgf:
+        return "--spatial and --regress-variance need --svgf: only the loop on the device has a choice of spatial stage"
+    if args.regress_variance is not None and not staged:
+        return "--regress-variance needs --spatial nlm or --spatial regress: the à-trous stage takes the temporal estimate as it is"
+    if staged and (args.feedback or args.clamp is not None or args.boost is not None):
+        return "--spatial %s does not combine with --feedback, --clamp or --boost: the stage is exclusive with them" % args.spatial
+    if staged and args.spp and (args.spp < 2 or args.spp % 2):
+        return EVEN_SPP % ("--spatial " + args.spatial, args.spp)
+    if staged and args.fit_map is not None and "%" not in args.fit_map:
+        return "--fit-map with --svgf names one file per frame: it needs a %d (as in fit_%03d.png)"
     if args.regress_features is not None and regress_mask(args.regress_features) is None:
         return "--regress-features wants letters of a (albedo), n (normal), z (depth), or none; got %r" % args.regress_features
     if args.svgf and not on["--orbit"]:
@@ -290,6 +306,10 @@ def main(argv=None):
     ap.add_argument("--feedback", type=int, default=0, metavar="J", help="svgf: feed the filter's result after J passes back into the colour history "
                     "(0 .. --denoise-iterations; default 0: the unfiltered accumulation)")
     ap.add_argument("--demodulate", action="store_true", help="svgf: accumulate, estimate and filter colour / albedo")
+    ap.add_argument("--spatial", choices=("atrous", "nlm", "regress"), default=None, help="svgf: the spatial stage — the à-trous filter (the default), "
+                    "or non-local means / the first-order regression over two accumulated halves (rttnw_svgf_set_regress; an even --spp)")
+    ap.add_argument("--regress-variance", choices=("temporal", "pair"), default=None, help="svgf, with --spatial nlm or regress: the variances the "
+                    "filter's weights read — the loop's temporal estimate (the default) or the filter's own pair variance")
     ap.add_argument("--clamp", type=float, default=None, metavar="GAMMA", help="temporal-variance, svgf: clip the reprojected history into the frame's "
                     "neighbourhood mean +- GAMMA standard deviations before the blend (rttnw_temporal_clamp; 0: the default, 1.0)")
     ap.add_argument("--boost", type=int, default=None, metavar="B", help="svgf: up to B (1, 2, 4 or 8) times --spp samples for pixels whose reprojected "
@@ -348,7 +368,8 @@ def main(argv=None):
     cam.aspect_ratio = setup.width / setup.height
     p = make_params(w, h, args.spp or setup.spp, background=tuple(setup.background), seed=args.seed,
                     precision={"f32": abi.F32, "f64": abi.F64, "f64strict": abi.F64_STRICT}[args.precision])
-    for flag, on in (("--denoise-select", args.denoise_select), ("--denoise-regress", args.denoise_regress)):
+    staged = args.svgf and args.spatial in ("nlm", "regress")
+    for flag, on in (("--denoise-select", args.denoise_select), ("--denoise-regress", args.denoise_regress), ("--spatial %s" % args.spatial, staged)):
         if on and (p.spp < 2 or p.spp % 2):   # (the scene's own spp: a given --spp was refused above)
             print(EVEN_SPP % (flag, p.spp), file=sys.stderr)
             return 1
@@ -373,12 +394,15 @@ def main(argv=None):
             if args.svgf and args.spp_map is not None:
                 grey = (frame["spp"].astype(np.uint64) * 255 // (args.boost * p.spp)).astype(np.uint8)
                 Image.fromarray(grey, "L").save(args.spp_map % k)
+            if staged and args.fit_map is not None:
+                Image.fromarray((frame["halves"]["fit"] * 127.5).astype(np.uint8), "L").save(args.fit_map % k)
 
         if args.svgf:
             frames = render.render_sequence_device(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, feedback=args.feedback,
                                                    demodulate=args.demodulate, iterations=args.denoise_iterations, on_frame=write, clamp=args.clamp,
                                                    sampling=None if args.boost is None else (args.boost, args.fill or 0.0),
-                                                   want_spp=args.boost is not None)
+                                                   want_spp=args.boost is not None, spatial=args.spatial or "atrous",
+                                                   regress_variance=args.regress_variance or "temporal", want_halves=staged and args.fit_map is not None)
             args.temporal = args.temporal_variance = True
         else:
             frames = render.render_sequence(sc, render.orbit_cameras(cam, args.orbit, args.orbit_step), p, temporal=args.temporal, denoise=args.denoise,
@@ -398,6 +422,9 @@ def main(argv=None):
         if args.svgf:
             print("svgf: feedback %d, %s; %.3f ms a frame on the device behind the trace and the feature pass"
                   % (args.feedback, "colour / albedo" if args.demodulate else "colour", sum(f["image_ms"] for f in frames) / len(frames)))
+        if staged:
+            print("spatial stage: %s over two accumulated halves, its weights on the %s variance"
+                  % ("first-order regression" if args.spatial == "regress" else "non-local means", args.regress_variance or "temporal"))
         if args.temporal_variance:
             var = frames[-1]["accumulated"]["variance"]
             print("temporal-variance: the last frame's mean standard error is %.4g; %.1f %% of its pixels took the spatial estimate"

@@ -226,6 +226,9 @@ PRODUCT_FUNCS = [
                                 [C.POINTER(Temporal), C.POINTER(Sampling)] + [C.c_void_p] * 3 + [C.POINTER(C.c_double)]),
     ("svgf_set_sampling", C.c_int, [C.c_void_p, C.POINTER(Sampling)]),
     ("svgf_samples", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("svgf_set_regress", C.c_int, [C.c_void_p, C.POINTER(Regress), C.c_uint32]),
+    ("svgf_push_halves", C.c_int, [C.c_void_p, C.POINTER(CameraDesc)] + [C.c_void_p] * 6 + [C.POINTER(SvgfOut)]),
+    ("svgf_halves", C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
     ("render_preview", C.c_int, [scene_p, C.POINTER(CameraDesc), C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(Preview), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     ("budget_select", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint64,

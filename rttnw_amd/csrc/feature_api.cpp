@@ -59,6 +59,17 @@ int nlm_refuse_params(const char* call, const char* field, const rttnw_nlm_param
     return 0;
 }
 
+int regress_refuse_params(const char* call, const rttnw_regress_params* g) {
+    if (!g) return refuse(call, "g is NULL");
+    if (g->search_radius > NLM_MAX_SEARCH_RADIUS) return refuse(call, "g->search_radius is more than 16");
+    if (g->patch_radius > NLM_MAX_PATCH_RADIUS) return refuse(call, "g->patch_radius is more than 4");
+    if (!(g->k >= 0.0)) return refuse(call, "g->k must be >= 0 (and not NaN)");
+    if (g->features > REGRESS_ALL) return refuse(call, "g->features is more than 7 (bits: 1 albedo, 2 normal, 4 depth)");
+    if (!(g->ridge >= 0.0)) return refuse(call, "g->ridge must be >= 0 (and not NaN)");
+    if (g->reserved0 != 0 || g->reserved1 != 0) return refuse(call, "g->reserved0 and g->reserved1 must be 0");
+    return 0;
+}
+
 int clamp_refuse_params(const char* call, const rttnw_clamp_params* k) {
     if (!k) return refuse(call,"k is NULL");
     if (k->radius > VARIANCE_MAX_RADIUS) return refuse(call,"k->radius is more than 4");
@@ -157,12 +168,7 @@ int rttnw_denoise_regress(uint32_t width, uint32_t height, const double* half_a,
     if (!g) return rt::refuse(call, "g is NULL");
     if ((var_a == nullptr) != (var_b == nullptr)) return rt::refuse(call, "var_a and var_b go together: both or neither");
     if (int rc = rt::image_size_refused(call, width, height)) return rc;
-    if (g->search_radius > rt::NLM_MAX_SEARCH_RADIUS) return rt::refuse(call, "g->search_radius is more than 16");
-    if (g->patch_radius > rt::NLM_MAX_PATCH_RADIUS) return rt::refuse(call, "g->patch_radius is more than 4");
-    if (!(g->k >= 0.0)) return rt::refuse(call, "g->k must be >= 0 (and not NaN)");
-    if (g->features > rt::REGRESS_ALL) return rt::refuse(call, "g->features is more than 7 (bits: 1 albedo, 2 normal, 4 depth)");
-    if (!(g->ridge >= 0.0)) return rt::refuse(call, "g->ridge must be >= 0 (and not NaN)");
-    if (g->reserved0 != 0 || g->reserved1 != 0) return rt::refuse(call, "g->reserved0 and g->reserved1 must be 0");
+    if (int rc = rt::regress_refuse_params(call, g)) return rc;
     if (g->features != 0 && !alpha) return rt::refuse(call, "alpha is NULL: g->features != 0 needs it");
     if ((g->features & rt::REGRESS_ALBEDO) && !albedo) return rt::refuse(call, "albedo is NULL: bit 1 of g->features selects it");
     if ((g->features & rt::REGRESS_NORMAL) && !normal) return rt::refuse(call, "normal is NULL: bit 2 of g->features selects it");

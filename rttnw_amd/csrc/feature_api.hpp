@@ -27,6 +27,7 @@ int temporal_refuse_params(const char* call, const char* field, const rttnw_temp
 int variance_refuse_params(const char* call, const char* field, const rttnw_variance_params& v);
 int denoise_refuse_params(const char* call, const char* field, const rttnw_denoise_params& d);
 int nlm_refuse_params(const char* call, const char* field, const rttnw_nlm_params& d);
+int regress_refuse_params(const char* call, const rttnw_regress_params* g);   // a NULL g among them: rttnw_denoise_regress, rttnw_svgf_set_regress
 int clamp_refuse_params(const char* call, const rttnw_clamp_params* k);       // a NULL k among them: rttnw_temporal_clamp, rttnw_svgf_set_clamp
 int sampling_refuse_params(const char* call, const rttnw_sampling_params* a); // a NULL a among them: rttnw_temporal_probe, rttnw_svgf_set_sampling
 // The reprojection of a frame seen through `cam` into a history seen through `prev_cam` (nullptr: no history), under a checked t

@@ -10,6 +10,9 @@
 //   regress_finish_kernel    the mean of the two fitted halves, its RGBA8, the error estimate and the fit count
 // The 60 running doubles of d = 7 are 120 VGPRs before the loop's own: they do not fit the 128 registers of a 1024-thread block, so masks
 // with d >= 6 run the 16-pixel tile (256 threads) at every radius (regress.hpp regress_tile_large); KERNELS.md has the registers per mask.
+// The host half is split as nlm.hip's: regress_plan_device (the filter instantiation, its tile, its LDS admitted), regress_passes_device (the
+// kernels enqueued over device pointers: nothing allocated, copied or waited for — the rttnw_svgf handle's spatial stage calls it, svgf.hip) and
+// regress_device, the blocking call on host arrays around the two.
 #include "feature_api.hpp"
 #include "filter_call.hpp"
 #include "regress.hpp"
@@ -151,13 +154,54 @@ __global__ void regress_finish_kernel(uint32_t n, const double* __restrict__ fa,
     }
 }
 
-using RegressFilter = void (*)(NlmView, RegressParams, const RegressRecord*, const double*, const double*, double*, double*, uint8_t*, uint8_t*);
+using RegressFilter = decltype(RegressPlan::filter);
 // (a mask that never takes the large tile has no large instantiation: its slot holds mask 0's, which is never launched for it)
 template <uint32_t M> constexpr RegressFilter regress_filter(bool large) {
     return large ? regress_filter_kernel<int(NLM_TILE_LARGE), regress_mask_fits_large_tile(M) ? M : 0u> : regress_filter_kernel<int(NLM_TILE_SMALL), M>;
 }
 
 } // namespace
+
+// The filter kernel of the call's mask and radii, its tile, and its dynamic LDS admitted: before the caller starts its clock
+int regress_plan_device(const char* at, const RegressParams& prm, RegressPlan& plan) {
+    const uint32_t mask = prm.features;
+    const bool large = regress_tile_large(mask, prm.nlm.r, prm.nlm.f);
+    static const RegressFilter LARGE[8] = {regress_filter<0>(true), regress_filter<1>(true), regress_filter<2>(true), regress_filter<3>(true),
+                                               regress_filter<4>(true), regress_filter<5>(true), regress_filter<6>(true), regress_filter<7>(true)};
+    static const RegressFilter SMALL[8] = {regress_filter<0>(false), regress_filter<1>(false), regress_filter<2>(false), regress_filter<3>(false),
+                                               regress_filter<4>(false), regress_filter<5>(false), regress_filter<6>(false), regress_filter<7>(false)};
+    plan.filter = large ? LARGE[mask] : SMALL[mask];
+    plan.tile = large ? NLM_TILE_LARGE : NLM_TILE_SMALL;
+    plan.lds_bytes = nlm_lds_bytes(plan.tile, prm.nlm.r, prm.nlm.f);
+    HIP_TRY_AS(at, hipFuncSetAttribute(reinterpret_cast<const void*>(plan.filter), hipFuncAttributeMaxDynamicSharedMemorySize, int(plan.lds_bytes)));
+    return RTTNW_OK;
+}
+
+// The kernels alone, enqueued on `stream` over buffers that are already on the device: nothing allocated, nothing copied, no wait
+int regress_passes_device(const char* at, uint32_t width, uint32_t height, const double* d_a, const double* d_b, const double* d_var_a, const double* d_var_b,
+                          const double* d_albedo, const double* d_normal, const double* d_depth, const double* d_alpha, const RegressParams& prm,
+                          const RegressPlan& plan, const RegressWork& k, hipStream_t stream) {
+    const size_t npx = size_t(width) * height;
+    const uint32_t mask = prm.features;
+    const bool has_var = d_var_a != nullptr, demodulate = prm.demodulate != 0;
+    const dim3 flat_block(256), pixel_grid(uint32_t((npx + 255) / 256)), value_grid(uint32_t((npx * 3 + 255) / 256));
+    const dim3 tiles((width + plan.tile - 1) / plan.tile, (height + plan.tile - 1) / plan.tile, 2);
+    if (demodulate || mask != 0u)
+        hipLaunchKernelGGL(regress_prepare_kernel, pixel_grid, flat_block, 0, stream, uint32_t(npx), mask, demodulate, d_a, d_b, d_var_a, d_var_b, d_albedo,
+                           d_normal, d_depth, d_alpha, k.wa, k.wb, k.wva, k.wvb, k.rec);
+    const double* w_a = demodulate ? k.wa : d_a;
+    const double* w_b = demodulate ? k.wb : d_b;
+    const double* w_va = !has_var ? k.pair : demodulate ? k.wva : d_var_a;
+    const double* w_vb = !has_var ? k.pair : demodulate ? k.wvb : d_var_b;
+    if (!has_var) hipLaunchKernelGGL(regress_variance_kernel, value_grid, flat_block, 0, stream, width, height, w_a, w_b, k.pair);
+    const NlmView view{width, height, w_a, w_b, w_va, w_vb};
+    hipLaunchKernelGGL(plan.filter, tiles, dim3(plan.tile * plan.tile), plan.lds_bytes, stream, view, prm, (const RegressRecord*)k.rec, d_albedo, d_alpha, k.fa,
+                       k.fb, k.fit_a, k.fit_b);
+    hipLaunchKernelGGL(regress_finish_kernel, value_grid, flat_block, 0, stream, uint32_t(npx), (const double*)k.fa, (const double*)k.fb,
+                       (const uint8_t*)k.fit_a, (const uint8_t*)k.fit_b, k.out, k.rgba, k.err, k.fit);
+    HIP_TRY_AS(at, hipGetLastError());
+    return RTTNW_OK;
+}
 
 // rttnw_denoise_regress's device half: the caller's arrays and the workspace on the device, the kernels between two events, the outputs the
 // caller asked for.
@@ -167,7 +211,6 @@ int regress_device(uint32_t width, uint32_t height, const double* half_a, const 
                    double* kernel_ms) {
     FilterCall fc;
     if (int rc = fc.open("denoise_regress", width, height)) return rc;
-    const size_t npx = fc.npx;
     const uint32_t mask = prm.features;
     const bool has_var = var_a != nullptr, demodulate = prm.demodulate != 0;
     DevBuf<double> d_a, d_b, d_va, d_vb, d_albedo, d_normal, d_depth, d_alpha, d_wa, d_wb, d_wva, d_wvb, d_pair, d_fa, d_fb, d_out, d_err, d_fit;
@@ -203,35 +246,14 @@ int regress_device(uint32_t width, uint32_t height, const double* half_a, const 
     fc.alloc(d_rgba, 4);
     fc.alloc(d_fit_a, 1);
     fc.alloc(d_fit_b, 1);
+    if (fc.rc) return fc.rc;
 
-    // the filter kernel of the call's mask and radii, its dynamic LDS admitted before the clock starts
-    const bool large = regress_tile_large(mask, prm.nlm.r, prm.nlm.f);
-    static const RegressFilter LARGE[8] = {regress_filter<0>(true), regress_filter<1>(true), regress_filter<2>(true), regress_filter<3>(true),
-                                               regress_filter<4>(true), regress_filter<5>(true), regress_filter<6>(true), regress_filter<7>(true)};
-    static const RegressFilter SMALL[8] = {regress_filter<0>(false), regress_filter<1>(false), regress_filter<2>(false), regress_filter<3>(false),
-                                               regress_filter<4>(false), regress_filter<5>(false), regress_filter<6>(false), regress_filter<7>(false)};
-    const RegressFilter filter = large ? LARGE[mask] : SMALL[mask];
-    const uint32_t tile = large ? NLM_TILE_LARGE : NLM_TILE_SMALL;
-    const size_t lds_bytes = nlm_lds_bytes(tile, prm.nlm.r, prm.nlm.f);
-    HIP_TRY_AS(fc.at, hipFuncSetAttribute(reinterpret_cast<const void*>(filter), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-
-    const hipStream_t stream = fc.stream;
-    const dim3 flat_block(256), pixel_grid(uint32_t((npx + 255) / 256)), value_grid(uint32_t((npx * 3 + 255) / 256));
-    const dim3 tiles((width + tile - 1) / tile, (height + tile - 1) / tile, 2);
+    RegressPlan plan;
+    if (int rc = regress_plan_device(fc.at.c_str(), prm, plan)) return rc; // before the clock starts
+    const RegressWork work{d_wa.p, d_wb.p, d_wva.p, d_wvb.p, d_pair.p, d_rec.p, d_fa.p, d_fb.p, d_fit_a.p, d_fit_b.p, d_out.p, d_rgba.p, d_err.p, d_fit.p};
     if (int rc = fc.start()) return rc;
-    if (demodulate || mask != 0u)
-        hipLaunchKernelGGL(regress_prepare_kernel, pixel_grid, flat_block, 0, stream, uint32_t(npx), mask, demodulate, d_a.p, d_b.p, d_va.p, d_vb.p,
-                           d_albedo.p, d_normal.p, d_depth.p, d_alpha.p, d_wa.p, d_wb.p, d_wva.p, d_wvb.p, d_rec.p);
-    const double* w_a = demodulate ? d_wa.p : d_a.p;
-    const double* w_b = demodulate ? d_wb.p : d_b.p;
-    const double* w_va = !has_var ? d_pair.p : demodulate ? d_wva.p : d_va.p;
-    const double* w_vb = !has_var ? d_pair.p : demodulate ? d_wvb.p : d_vb.p;
-    if (!has_var) hipLaunchKernelGGL(regress_variance_kernel, value_grid, flat_block, 0, stream, width, height, w_a, w_b, d_pair.p);
-    const NlmView view{width, height, w_a, w_b, w_va, w_vb};
-    hipLaunchKernelGGL(filter, tiles, dim3(tile * tile), lds_bytes, stream, view, prm, d_rec.p, d_albedo.p, d_alpha.p, d_fa.p, d_fb.p, d_fit_a.p, d_fit_b.p);
-    hipLaunchKernelGGL(regress_finish_kernel, value_grid, flat_block, 0, stream, uint32_t(npx), d_fa.p, d_fb.p, d_fit_a.p, d_fit_b.p, d_out.p, d_rgba.p,
-                       d_err.p, d_fit.p);
-    HIP_TRY_AS(fc.at, hipGetLastError());
+    if (int rc = regress_passes_device(fc.at.c_str(), width, height, d_a.p, d_b.p, d_va.p, d_vb.p, d_albedo.p, d_normal.p, d_depth.p, d_alpha.p, prm, plan, work,
+                                       fc.stream)) return rc;
     if (int rc = fc.finish(kernel_ms)) return rc;
     fc.copy_out(out_linear_rgb, d_out, 3);
     fc.copy_out(out_rgba8, d_rgba, 4);

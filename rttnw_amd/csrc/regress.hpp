@@ -156,4 +156,31 @@ int regress_device(uint32_t width, uint32_t height, const double* half_a, const 
                    double* out_linear_rgb, uint8_t* out_rgba8, double* out_half_a, double* out_half_b, double* out_error_rgb, double* out_fit,
                    double* kernel_ms);
 
+// ... and its kernels alone, in the shape of nlm_plan_device / nlm_passes_device: regress_plan_device picks the filter kernel of the call's mask
+// and radii and its tile, and admits its dynamic LDS — before the caller starts its clock —, regress_passes_device enqueues the kernels on
+// `stream` over buffers that are already on the device: nothing allocated, nothing copied, no wait.  d_var_a / d_var_b: the guides' variances,
+// or both nullptr: the pair variance is then formed into the workspace's `pair`.  The feature arrays are read as the mask and `demodulate` ask
+// (the others may be nullptr).  `at`: the prefix of an error's message.  rttnw_svgf_push_halves' spatial stage (svgf.hip).
+struct RegressPlan {
+    void (*filter)(NlmView, RegressParams, const RegressRecord*, const double*, const double*, double*, double*, uint8_t*, uint8_t*);
+    uint32_t tile;
+    size_t lds_bytes;
+};
+struct RegressWork {             // device buffers, per pixel:
+    double *wa, *wb, *wva, *wvb; // 3 each: the demodulated halves and given variances (read and written only with demodulate)
+    double* pair;                // 3: the pair variance (only without given variances)
+    RegressRecord* rec;          // 1 record (only with a mask)
+    double *fa, *fb;             // 3 each: the two fitted halves
+    uint8_t *fit_a, *fit_b;      // 1 byte each: "the first-order value was used"
+    double* out;                 // 3: their mean
+    uint8_t* rgba;               // 4 bytes: its RGBA8
+    double *err, *fit;           // 3, 1: the error estimate and the fit count
+};
+int regress_plan_device(const char* at, const RegressParams& prm, RegressPlan& plan);
+#ifdef __HIPCC__
+int regress_passes_device(const char* at, uint32_t width, uint32_t height, const double* d_a, const double* d_b, const double* d_var_a, const double* d_var_b,
+                          const double* d_albedo, const double* d_normal, const double* d_depth, const double* d_alpha, const RegressParams& prm,
+                          const RegressPlan& plan, const RegressWork& work, hipStream_t stream);
+#endif
+
 } // namespace rt

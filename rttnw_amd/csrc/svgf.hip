@@ -11,6 +11,10 @@
 //   svgf_emit_kernel        one thread per pixel: the result and the accumulation multiplied back, and the RGBA8
 //   (with rttnw_svgf_set_sampling, in front of all that: probe.hip's probe_kernel over the frame's features and the state's, and per level of the
 //   boost a list of 2x2 blocks — pixel_lists.hip — traced by render_tiles_t and written over the plain trace's pixels; one 8-byte copy per level)
+//   (with rttnw_svgf_set_regress, and rttnw_svgf_push_halves / rttnw_svgf_halves beside it: svgf_ingest_halves_kernel over two halves — two traces
+//   of p->spp / 2, or two uploaded images —, svgf_accumulate_halves_kernel with the half histories Ha and Hb on the taps in H's place, the estimate
+//   as it is, regress.hip's kernels — regress_passes_device — in the à-trous passes' place over the two accumulated halves, and
+//   svgf_emit_halves_kernel, which shows the mean of those halves as the accumulation)
 // then waits once and copies out what the caller asked for.  No atomics.
 #include "feature_api.hpp"
 #include "render_multi.hpp"
@@ -43,6 +47,17 @@ struct rttnw_svgf {
     rt::DevBuf<uint8_t> s_mult, s_mask, s_select, s_sums;
     rt::DevBuf<uint32_t> s_quads, s_scan;
     rt::Event ev2, ev3;
+    // rttnw_svgf_set_regress: off by default.  The buffers are allocated by the set calls, each when a setting first needs it: the second half's
+    // packed trace, the ingested halves ca / cb (rttnw_svgf_push_halves uploads into them), the accumulated halves ha / hb as ping-pong pairs beside
+    // m1 / m2 (ha[cur], hb[cur] are the state), the doubled variance, and rttnw_denoise_regress's workspace.  halves_live: the last frame call ran
+    // with the stage and wrote what rttnw_svgf_halves copies out.
+    bool regress = false, halves_live = false;
+    uint32_t variance_source = 0;
+    rt::RegressParams gprm = {};
+    rt::RegressPlan gplan = {};
+    rt::DevBuf<uint8_t> packed_b, g_rgba, g_fit_a, g_fit_b;
+    rt::DevBuf<double> ca, cb, ha[2], hb[2], var2, g_pair, g_fa, g_fb, g_out, g_err, g_fit;
+    rt::DevBuf<rt::RegressRecord> g_rec;
 };
 
 namespace rt {
@@ -101,6 +116,82 @@ __global__ void svgf_emit_kernel(uint32_t n, const double* __restrict__ filtered
         out_rgba8[size_t(i) * 4 + ch] = denoise_quantise(lin);
     }
     out_rgba8[size_t(i) * 4 + 3] = 255;
+}
+
+// rttnw_svgf_set_regress's ingest: the two halves — two packed tile buffers of the trace, or the two row-major images rttnw_svgf_push_halves
+// uploaded into out_ca / out_cb (each thread reads its pixel's values before it writes them: the arrays are not `__restrict__`) — to their mean
+// C (out_raw), and C and both halves divided under the one rule: c, ca, cb.  The flags are C's, which are the halves' too: the rule reads the
+// albedo and alpha only.
+template <typename T, bool PACKED>
+__global__ void svgf_ingest_halves_kernel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t demodulate, const T* half_a, const T* half_b,
+                                          const double* __restrict__ albedo, const double* __restrict__ alpha, double* __restrict__ out_raw,
+                                          double* __restrict__ out_c, double* out_ca, double* out_cb, uint8_t* __restrict__ out_flags) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const size_t p = size_t(y) * width + x;
+    const size_t s = PACKED ? (tile_permuted(x >> 3, y >> 3, tiles_x) * 64ull + ((y & 7u) << 3) + (x & 7u)) * 4ull : p * 3;
+    const double a = alpha[p];
+    double va[3], vb[3];
+    for (int ch = 0; ch < 3; ++ch) {
+        va[ch] = double(half_a[s + ch]);
+        vb[ch] = double(half_b[s + ch]);
+    }
+    for (int ch = 0; ch < 3; ++ch) {
+        const double mean = svgf_halves_mean(va[ch], vb[ch]), alb = albedo[p * 3 + ch];
+        uint8_t divided, same;
+        out_raw[p * 3 + ch] = mean;
+        out_c[p * 3 + ch] = svgf_ingest_value(demodulate != 0u, mean, alb, a, divided);
+        out_ca[p * 3 + ch] = svgf_ingest_value(demodulate != 0u, va[ch], alb, a, same);
+        out_cb[p * 3 + ch] = svgf_ingest_value(demodulate != 0u, vb[ch], alb, a, same);
+        out_flags[p * 3 + ch] = divided;
+    }
+}
+
+// svgf_accumulate_kernel with the two half histories on the taps: five RGB planes gathered per tap (M1, M2, Ha, Hb and the state's normal), plain
+// global loads, no LDS
+__global__ __launch_bounds__(int(SVGF_BLOCK_X* SVGF_BLOCK_Y)) void svgf_accumulate_halves_kernel(
+    uint32_t width, uint32_t height, TemporalParams prm, const double* __restrict__ linear, const double* __restrict__ half_a,
+    const double* __restrict__ half_b, const double* __restrict__ normal, const double* __restrict__ depth, const double* __restrict__ alpha,
+    const double* __restrict__ prev_moment1, const double* __restrict__ prev_moment2, const double* __restrict__ prev_half_a,
+    const double* __restrict__ prev_half_b, const double* __restrict__ prev_length, const double* __restrict__ prev_normal,
+    const double* __restrict__ prev_depth, const double* __restrict__ prev_alpha, double* __restrict__ out_moment1, double* __restrict__ out_moment2,
+    double* __restrict__ out_half_a, double* __restrict__ out_half_b, double* __restrict__ out_length, double* __restrict__ out_prev_xy) {
+    const uint32_t x = blockIdx.x * SVGF_BLOCK_X + threadIdx.x, y = blockIdx.y * SVGF_BLOCK_Y + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const SvgfAccumulatedHalves px = svgf_accumulate_halves_pixel(width, height, x, y, prm, linear, half_a, half_b, normal, depth, alpha, prev_moment1,
+                                                                  prev_moment2, prev_half_a, prev_half_b, prev_length, prev_normal, prev_depth, prev_alpha);
+    const size_t p = size_t(y) * width + x;
+    for (int ch = 0; ch < 3; ++ch) {
+        out_moment1[p * 3 + ch] = px.m1[ch];
+        out_moment2[p * 3 + ch] = px.m2[ch];
+        out_half_a[p * 3 + ch] = px.a[ch];
+        out_half_b[p * 3 + ch] = px.b[ch];
+    }
+    out_length[p] = px.length;
+    out_prev_xy[p * 2] = px.xy[0];
+    out_prev_xy[p * 2 + 1] = px.xy[1];
+}
+
+// svgf_emit_kernel behind the regression stage: the accumulation shown is the mean of the two accumulated halves
+__global__ void svgf_emit_halves_kernel(uint32_t n, const double* __restrict__ filtered, const double* __restrict__ acc_a, const double* __restrict__ acc_b,
+                                        const double* __restrict__ albedo, const uint8_t* __restrict__ flags, double* __restrict__ out_linear,
+                                        double* __restrict__ out_accumulated, uint8_t* __restrict__ out_rgba8) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; // one thread per pixel
+    if (i >= n) return;
+    const size_t o = size_t(i) * 3;
+    for (int ch = 0; ch < 3; ++ch) {
+        const double lin = svgf_emit_value(filtered[o + ch], albedo[o + ch], flags[o + ch]);
+        out_linear[o + ch] = lin;
+        out_accumulated[o + ch] = svgf_emit_value(svgf_halves_mean(acc_a[o + ch], acc_b[o + ch]), albedo[o + ch], flags[o + ch]);
+        out_rgba8[size_t(i) * 4 + ch] = denoise_quantise(lin);
+    }
+    out_rgba8[size_t(i) * 4 + 3] = 255;
+}
+
+// var + var, one sum: the variance of a half, which is a mean over half the samples of M1 (rttnw_svgf_set_regress, variance_source 0)
+__global__ void svgf_half_variance_kernel(size_t n, const double* __restrict__ var, double* __restrict__ out) {
+    const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = svgf_half_variance(var[i]);
 }
 
 __global__ void svgf_fill_kernel(size_t n, double value, double* __restrict__ out) {
@@ -196,7 +287,17 @@ int svgf_run(const char* call, ::rttnw_svgf* g, const rttnw_camera_desc* cam, bo
 
     HIP_TRY_AS(at, hipEventRecord(g->ev0.get(), stream));
     const dim3 block(32, 8), grid((w + 31) / 32, (h + 7) / 8);
-    if (!packed)
+    if (g->regress) { // the two halves: rttnw_svgf_push_halves uploaded them into ca / cb, rttnw_svgf_frame traced them into packed / packed_b
+        if (!packed)
+            hipLaunchKernelGGL((svgf_ingest_halves_kernel<double, false>), grid, block, 0, stream, w, h, L.tiles_x, g->q.demodulate, (const double*)g->ca.p,
+                               (const double*)g->cb.p, albedo, alpha, g->raw.p, g->c.p, g->ca.p, g->cb.p, g->flags.p);
+        else if (precision == RTTNW_F32)
+            hipLaunchKernelGGL((svgf_ingest_halves_kernel<float, true>), grid, block, 0, stream, w, h, L.tiles_x, g->q.demodulate, (const float*)g->packed.p,
+                               (const float*)g->packed_b.p, albedo, alpha, g->raw.p, g->c.p, g->ca.p, g->cb.p, g->flags.p);
+        else
+            hipLaunchKernelGGL((svgf_ingest_halves_kernel<double, true>), grid, block, 0, stream, w, h, L.tiles_x, g->q.demodulate, (const double*)g->packed.p,
+                               (const double*)g->packed_b.p, albedo, alpha, g->raw.p, g->c.p, g->ca.p, g->cb.p, g->flags.p);
+    } else if (!packed)
         hipLaunchKernelGGL((svgf_ingest_kernel<double, false>), grid, block, 0, stream, w, h, L.tiles_x, g->q.demodulate, (const double*)g->raw.p, albedo, alpha,
                            g->raw.p, g->c.p, g->flags.p);
     else if (precision == RTTNW_F32)
@@ -207,18 +308,25 @@ int svgf_run(const char* call, ::rttnw_svgf* g, const rttnw_camera_desc* cam, bo
                            alpha, g->raw.p, g->c.p, g->flags.p);
     HIP_TRY_AS(at, hipGetLastError());
 
-    if (g->clamp) { // steps 1 and 2 through rttnw_temporal_clamp's kernel (clamp.hip): M1 and H clipped into the frame's interval on the same taps
+    const dim3 ablock(SVGF_BLOCK_X, SVGF_BLOCK_Y), agrid((w + SVGF_BLOCK_X - 1) / SVGF_BLOCK_X, (h + SVGF_BLOCK_Y - 1) / SVGF_BLOCK_Y);
+    if (g->regress) { // steps 1 and 2 with Ha and Hb on the taps (the stage is exclusive with the clamp and with feedback)
+        hipLaunchKernelGGL(svgf_accumulate_halves_kernel, agrid, ablock, 0, stream, w, h, prm, (const double*)g->c.p, (const double*)g->ca.p,
+                           (const double*)g->cb.p, normal, depth, alpha, (const double*)g->m1[old].p, (const double*)g->m2[old].p, (const double*)g->ha[old].p,
+                           (const double*)g->hb[old].p, (const double*)g->len[old].p, pmaps + npx * 3, pmaps + npx * 6, pmaps + npx * 7, g->m1[nxt].p,
+                           g->m2[nxt].p, g->ha[nxt].p, g->hb[nxt].p, g->len[nxt].p, g->xy.p);
+        HIP_TRY_AS(at, hipGetLastError());
+    } else if (g->clamp) { // steps 1 and 2 through rttnw_temporal_clamp's kernel (clamp.hip): M1 and H clipped into the frame's interval on the same taps
         if (int rc = clamp_accumulate_device(at.c_str(), w, h, prm, g->kprm, feedback, g->c.p, normal, depth, alpha, g->m1[old].p, g->m2[old].p, g->hist.p,
                                              g->len[old].p, pmaps + npx * 3, pmaps + npx * 6, pmaps + npx * 7, g->m1[nxt].p, nullptr, g->m2[nxt].p, g->acc.p,
                                              g->len[nxt].p, g->xy.p, nullptr, nullptr, g->clipped.p, stream)) return rc;
     } else {
-        const dim3 ablock(SVGF_BLOCK_X, SVGF_BLOCK_Y), agrid((w + SVGF_BLOCK_X - 1) / SVGF_BLOCK_X, (h + SVGF_BLOCK_Y - 1) / SVGF_BLOCK_Y);
         hipLaunchKernelGGL(svgf_accumulate_kernel, agrid, ablock, 0, stream, w, h, prm, feedback ? 1u : 0u, (const double*)g->c.p, normal, depth, alpha,
                            (const double*)g->m1[old].p, (const double*)g->m2[old].p, (const double*)g->hist.p, (const double*)g->len[old].p, pmaps + npx * 3,
                            pmaps + npx * 6, pmaps + npx * 7, g->m1[nxt].p, g->m2[nxt].p, g->acc.p, g->len[nxt].p, g->xy.p);
         HIP_TRY_AS(at, hipGetLastError());
     }
     g->clipped_live = g->clamp;
+    g->halves_live = g->regress;
 
     if (int rc = variance_passes_device(at.c_str(), w, h, nullptr, g->vprm, nullptr, normal, depth, alpha, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                         g->m1[nxt].p, nullptr, g->m2[nxt].p, g->len[nxt].p, nullptr, g->var.p, stream)) return rc;
@@ -227,11 +335,29 @@ int svgf_run(const char* call, ::rttnw_svgf* g, const rttnw_camera_desc* cam, bo
     double* const fc[2] = {g->fc[0].p, g->fc[1].p};
     double* const fv[2] = {g->fv[0].p, g->fv[1].p};
     int fo = 0;
-    if (int rc = atrous_passes_tap_device(w, h, g->acc.p, g->var.p, filter_albedo, normal, depth, alpha, g->q.d.iterations, g->dprm, fc, fv, g->scratch_rgba.p,
-                                          g->q.feedback_iterations, g->q.feedback_iterations ? g->hist.p : nullptr, stream, fo)) return rc;
+    const double* filtered_variance = nullptr;
+    if (g->regress) { // step 3 is rttnw_denoise_regress over the accumulated halves, F.albedo a regressor; step 5 shows the mean of the halves
+        const size_t n3 = npx * 3;
+        double* half_var = nullptr; // variance_source 1: the filter's own pair variance
+        if (g->variance_source == 0u) {
+            half_var = g->var2.p;
+            hipLaunchKernelGGL(svgf_half_variance_kernel, dim3(uint32_t((n3 + 255) / 256)), dim3(256), 0, stream, n3, (const double*)g->var.p, half_var);
+        }
+        const RegressWork work{nullptr, nullptr, nullptr, nullptr, g->g_pair.p, g->g_rec.p, g->g_fa.p, g->g_fb.p, g->g_fit_a.p, g->g_fit_b.p, g->g_out.p,
+                               g->g_rgba.p, g->g_err.p, g->g_fit.p};
+        if (int rc = regress_passes_device(at.c_str(), w, h, g->ha[nxt].p, g->hb[nxt].p, half_var, half_var, albedo, normal, depth, alpha, g->gprm, g->gplan,
+                                           work, stream)) return rc;
+        hipLaunchKernelGGL(svgf_emit_halves_kernel, dim3((uint32_t(npx) + 255u) / 256u), dim3(256), 0, stream, uint32_t(npx), (const double*)g->g_out.p,
+                           (const double*)g->ha[nxt].p, (const double*)g->hb[nxt].p, albedo, (const uint8_t*)g->flags.p, g->out_lin.p, g->out_acc.p, g->rgba.p);
+        filtered_variance = g->g_err.p;
+    } else {
+        if (int rc = atrous_passes_tap_device(w, h, g->acc.p, g->var.p, filter_albedo, normal, depth, alpha, g->q.d.iterations, g->dprm, fc, fv, g->scratch_rgba.p,
+                                              g->q.feedback_iterations, g->q.feedback_iterations ? g->hist.p : nullptr, stream, fo)) return rc;
 
-    hipLaunchKernelGGL(svgf_emit_kernel, dim3((uint32_t(npx) + 255u) / 256u), dim3(256), 0, stream, uint32_t(npx), (const double*)fc[fo], (const double*)g->acc.p,
-                       albedo, (const uint8_t*)g->flags.p, g->out_lin.p, g->out_acc.p, g->rgba.p);
+        hipLaunchKernelGGL(svgf_emit_kernel, dim3((uint32_t(npx) + 255u) / 256u), dim3(256), 0, stream, uint32_t(npx), (const double*)fc[fo], (const double*)g->acc.p,
+                           albedo, (const uint8_t*)g->flags.p, g->out_lin.p, g->out_acc.p, g->rgba.p);
+        filtered_variance = fv[fo];
+    }
     HIP_TRY_AS(at, hipGetLastError());
     HIP_TRY_AS(at, hipEventRecord(g->ev1.get(), stream));
     HIP_TRY_AS(at, hipStreamSynchronize(stream));
@@ -247,7 +373,7 @@ int svgf_run(const char* call, ::rttnw_svgf* g, const rttnw_camera_desc* cam, bo
     HIP_TRY_AS(at, copy(out->rgba8, g->rgba.p, npx * 4));
     HIP_TRY_AS(at, copy(out->accumulated_rgb, g->out_acc.p, b3));
     HIP_TRY_AS(at, copy(out->variance_rgb, g->var.p, b3));
-    HIP_TRY_AS(at, copy(out->filtered_variance_rgb, fv[fo], b3));
+    HIP_TRY_AS(at, copy(out->filtered_variance_rgb, filtered_variance, b3));
     HIP_TRY_AS(at, copy(out->length, g->len[nxt].p, b1));
     HIP_TRY_AS(at, copy(out->prev_xy, g->xy.p, b1 * 2));
     HIP_TRY_AS(at, copy(out->moment1_rgb, g->m1[nxt].p, b3));
@@ -340,6 +466,7 @@ int rttnw_svgf_set_clamp(rttnw_svgf* q, const rttnw_clamp_params* k) {
         q->clamp = false;
         return RTTNW_OK;
     }
+    if (q->regress) return rt::refuse(call, "q: the handle has a regression stage (rttnw_svgf_set_regress), which is exclusive with a clamp");
     if (!q->clipped.p) { // the one byte map, once: frame calls still allocate nothing
         const rt::OnHandleDevice on(call, q);
         if (on.rc) return on.rc;
@@ -374,6 +501,7 @@ int rttnw_svgf_set_sampling(rttnw_svgf* q, const rttnw_sampling_params* a) {
         q->sampling = false;
         return RTTNW_OK;
     }
+    if (q->regress) return rt::refuse(call, "q: the handle has a regression stage (rttnw_svgf_set_regress), which is exclusive with sampling");
     if (!q->s_mult.p) { // the maps, the list and the list passes' sums, once: frame calls still allocate none of the handle's buffers
         const size_t npx = size_t(q->width) * q->height;
         rttnw_tile_layout L;
@@ -426,6 +554,7 @@ int rttnw_svgf_push(rttnw_svgf* q, const rttnw_camera_desc* cam, const double* l
     if (!linear_rgb) return rt::refuse(call, "linear_rgb is NULL");
     if (!albedo || !normal || !depth || !alpha) return rt::refuse(call, "NULL argument (albedo, normal, depth or alpha)");
     if (!q) return rt::refuse(call, "q is NULL");
+    if (q->regress) return rt::refuse(call, "q: the handle has a regression stage (rttnw_svgf_set_regress): it takes rttnw_svgf_push_halves");
     const rt::OnHandleDevice on(call, q);
     if (on.rc) return on.rc;
     const std::string& at = on.at;
@@ -439,6 +568,97 @@ int rttnw_svgf_push(rttnw_svgf* q, const rttnw_camera_desc* cam, const double* l
     return rt::svgf_run(call, q, cam, false, RTTNW_F64, out);
 }
 
+int rttnw_svgf_set_regress(rttnw_svgf* q, const rttnw_regress_params* g, uint32_t variance_source) {
+    const char* const call = "svgf_set_regress";
+    if (g) {
+        if (int rc = rt::regress_refuse_params(call, g)) return rc;
+        if (g->demodulate != 0) return rt::refuse(call, "g->demodulate must be 0: the handle's own demodulate does that job");
+        if (variance_source > 1) return rt::refuse(call, "variance_source must be 0 (the temporal estimate) or 1 (the filter's pair variance)");
+    }
+    if (!q) return rt::refuse(call, "q is NULL");
+    if (!g) {
+        if (!q->regress) return RTTNW_OK; // nothing to clear: the history stays
+        q->regress = q->halves_live = false;
+        q->has_state = false;
+        return RTTNW_OK;
+    }
+    if (q->q.feedback_iterations != 0 || q->clamp || q->sampling)
+        return rt::refuse(call, "q: the regression stage is exclusive with feedback_iterations != 0, a clamp (rttnw_svgf_set_clamp) and sampling (rttnw_svgf_set_sampling)");
+    const rt::RegressParams prm = rt::regress_params(g->search_radius, g->patch_radius, g->k, g->ridge, g->features, 0);
+    const rt::OnHandleDevice on(call, q);
+    if (on.rc) return on.rc;
+    const std::string& at = on.at;
+    const size_t npx = size_t(q->width) * q->height;
+    rttnw_tile_layout L;
+    rt::fill_layout(q->width, q->height, 1, L);
+    // every buffer the stage needs under these settings, each once: frame calls still allocate nothing
+    if (!q->packed_b.p) HIP_TRY_AS(at, q->packed_b.alloc(size_t(L.pixels_per_rank) * 4 * sizeof(double)));
+    for (rt::DevBuf<double>* b : {&q->ca, &q->cb, &q->ha[0], &q->ha[1], &q->hb[0], &q->hb[1], &q->g_fa, &q->g_fb, &q->g_out, &q->g_err})
+        if (!b->p) HIP_TRY_AS(at, b->alloc(npx * 3));
+    rt::DevBuf<double>& half_var = variance_source == 0u ? q->var2 : q->g_pair;
+    if (!half_var.p) HIP_TRY_AS(at, half_var.alloc(npx * 3));
+    if (!q->g_fit.p) HIP_TRY_AS(at, q->g_fit.alloc(npx));
+    if (!q->g_rgba.p) HIP_TRY_AS(at, q->g_rgba.alloc(npx * 4));
+    if (!q->g_fit_a.p) HIP_TRY_AS(at, q->g_fit_a.alloc(npx));
+    if (!q->g_fit_b.p) HIP_TRY_AS(at, q->g_fit_b.alloc(npx));
+    if (prm.features != 0u && !q->g_rec.p) HIP_TRY_AS(at, q->g_rec.alloc(npx));
+    rt::RegressPlan plan;
+    if (int rc = rt::regress_plan_device(at.c_str(), prm, plan)) return rc; // the filter kernel's dynamic LDS, admitted here
+    q->gprm = prm;
+    q->gplan = plan;
+    q->variance_source = variance_source;
+    q->regress = true;
+    q->halves_live = false;
+    q->has_state = false; // as rttnw_svgf_reset: a history without Ha and Hb is none
+    return RTTNW_OK;
+}
+
+int rttnw_svgf_push_halves(rttnw_svgf* q, const rttnw_camera_desc* cam, const double* half_a, const double* half_b, const double* albedo,
+                           const double* normal, const double* depth, const double* alpha, const rttnw_svgf_out* out) {
+    const char* const call = "svgf_push_halves";
+    // rttnw_svgf_push's checks, half_a and half_b where linear_rgb stood
+    if (!cam) return rt::refuse(call, "cam is NULL");
+    if (!half_a || !half_b) return rt::refuse(call, "NULL argument (half_a or half_b)");
+    if (!albedo || !normal || !depth || !alpha) return rt::refuse(call, "NULL argument (albedo, normal, depth or alpha)");
+    if (!q) return rt::refuse(call, "q is NULL");
+    if (!q->regress) return rt::refuse(call, "q: the handle has no regression stage (rttnw_svgf_set_regress): it takes rttnw_svgf_push");
+    const rt::OnHandleDevice on(call, q);
+    if (on.rc) return on.rc;
+    const std::string& at = on.at;
+    const size_t npx = size_t(q->width) * q->height, b3 = npx * 3 * sizeof(double), b1 = npx * sizeof(double);
+    double* maps = q->maps[q->cur ^ 1].p;
+    HIP_TRY_AS(at, hipMemcpy(q->ca.p, half_a, b3, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(q->cb.p, half_b, b3, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps, albedo, b3, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps + npx * 3, normal, b3, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps + npx * 6, depth, b1, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps + npx * 7, alpha, b1, hipMemcpyHostToDevice));
+    return rt::svgf_run(call, q, cam, false, RTTNW_F64, out);
+}
+
+int rttnw_svgf_halves(rttnw_svgf* q, double* out_acc_a, double* out_acc_b, double* out_filtered_a, double* out_filtered_b, double* out_fit) {
+    const char* const call = "svgf_halves";
+    if (!q) return rt::refuse(call, "q is NULL");
+    const size_t npx = size_t(q->width) * q->height;
+    if (!q->halves_live) { // before any frame call with the stage, or after the stage was set anew or cleared
+        for (double* o : {out_acc_a, out_acc_b, out_filtered_a, out_filtered_b})
+            if (o) std::fill(o, o + npx * 3, 0.0);
+        if (out_fit) std::fill(out_fit, out_fit + npx, 0.0);
+        return RTTNW_OK;
+    }
+    const rt::OnHandleDevice on(call, q);
+    if (on.rc) return on.rc;
+    const std::string& at = on.at;
+    const size_t b3 = npx * 3 * sizeof(double);
+    const auto copy = [](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+    HIP_TRY_AS(at, copy(out_acc_a, q->ha[q->cur].p, b3)); // (the last frame call's Aa and Ab are the state's Ha and Hb)
+    HIP_TRY_AS(at, copy(out_acc_b, q->hb[q->cur].p, b3));
+    HIP_TRY_AS(at, copy(out_filtered_a, q->g_fa.p, b3));
+    HIP_TRY_AS(at, copy(out_filtered_b, q->g_fb.p, b3));
+    HIP_TRY_AS(at, copy(out_fit, q->g_fit.p, npx * sizeof(double)));
+    return RTTNW_OK;
+}
+
 int rttnw_svgf_frame(rttnw_svgf* q, rttnw_scene* s, const rttnw_camera_desc* cam, const rttnw_params* p, const rttnw_svgf_out* out, rttnw_stats* stats) {
     const char* const call = "svgf_frame";
     if (!cam) return rt::refuse(call, "cam is NULL");
@@ -450,13 +670,31 @@ int rttnw_svgf_frame(rttnw_svgf* q, rttnw_scene* s, const rttnw_camera_desc* cam
     // with sampling a pixel may get boost * p->spp samples: that product must be a spp rttnw_render takes
     const bool boosted = q->sampling; // (a boost of 1 still probes: rttnw_svgf_samples returns the lengths)
     if (boosted && uint64_t(q->sprm.boost) * p->spp > 0xFFFFFFFFull) return rt::refuse(call, "p->spp times the handle's boost (rttnw_svgf_set_sampling) is more than a render's spp can be");
+    // with a regression stage the frame is traced as two halves of p->spp / 2 samples
+    if (q->regress && (p->spp < 2u || p->spp % 2u != 0u)) return rt::refuse(call, "p->spp must be even and at least 2 on a handle with a regression stage (rttnw_svgf_set_regress): two halves of p->spp / 2");
     if (int rc = rt::validate(s, cam, p)) return rc;
     if (s->device->device != q->device) return rt::refuse(call, "s: the scene was committed on another device than the handle's");
     rttnw_params pf = *p;
     pf.spp = q->q.feature_spp ? q->q.feature_spp : (p->spp < 16u ? p->spp : 16u);
     rt::DeviceGuard restore;
     uint64_t boost_samples = 0;
-    if (!boosted) {
+    if (q->regress) { // the two halves, disjoint sample ranges, then the feature pass as without the stage; `stats` sums the two traces
+        rttnw_params pa = *p, pb = *p;
+        pa.spp = pb.spp = p->spp / 2u;
+        pb.sample_begin = p->sample_begin + p->spp / 2u;
+        rttnw_stats sb = {};
+        if (int rc = rt::render_tiles_any(s, s->device, cam, &pa, q->packed.p, nullptr, stats)) return rc;
+        if (int rc = rt::render_tiles_any(s, s->device, cam, &pb, q->packed_b.p, nullptr, stats ? &sb : nullptr)) return rc;
+        if (stats) {
+            stats->samples += sb.samples;
+            stats->rays += sb.rays;
+            stats->nodes_visited += sb.nodes_visited;
+            stats->prims_tested += sb.prims_tested;
+            stats->texel_fetches += sb.texel_fetches;
+            stats->kernel_ms += sb.kernel_ms;
+        }
+        if (int rc = RT_BY_PRECISION(p->precision, render_features_device_t, s, cam, &pf, q->maps[q->cur ^ 1].p, nullptr)) return rc;
+    } else if (!boosted) {
         if (int rc = rt::render_tiles_any(s, s->device, cam, p, q->packed.p, nullptr, stats)) return rc;
         if (int rc = RT_BY_PRECISION(p->precision, render_features_device_t, s, cam, &pf, q->maps[q->cur ^ 1].p, nullptr)) return rc;
     } else {

@@ -675,6 +675,9 @@ def render_sequence(scene, cams, params, temporal=True, denoise=False, iteration
 
 SVGF_ARRAYS = {"linear_rgb": 3, "rgba8": 4, "accumulated_rgb": 3, "variance_rgb": 3, "filtered_variance_rgb": 3, "length": 0, "prev_xy": 2,
                "moment1_rgb": 3, "moment2_rgb": 3, "history_rgb": 3, "raw_rgb": 3, "albedo": 3, "normal": 3, "depth": 0, "alpha": 0}
+HALVES_ARRAYS = ("acc_a", "acc_b", "filtered_a", "filtered_b", "fit")    # rttnw_svgf_halves' outputs, in its order
+REGRESS_VARIANCE = ("temporal", "pair")                                  # rttnw_svgf_set_regress' variance_source 0, 1
+SPATIAL_STAGES = ("atrous", "nlm", "regress")
 
 
 class SvgfSequence:
@@ -761,6 +764,50 @@ class SvgfSequence:
         check(self._b.svgf_samples(self.handle, spp.ctypes.data, length.ctypes.data), self._b, "rttnw_svgf_samples")
         return spp, length
 
+    def set_regress(self, mask=7, variance="temporal", ridge=0.0, search_radius=0, patch_radius=0, k=0.0):
+        """`rttnw_svgf_set_regress`: from the next call on the spatial stage is `denoise_regress` over two half histories the handle accumulates
+        beside the moments — with `mask` 0, `denoise_nlm`.  `variance`: "temporal" hands the filter the handle's temporal estimate (doubled: a half
+        holds half the samples), "pair" leaves it its own pair variance.  The other parameters are `denoise_regress`'s, a 0 their default.  The
+        history is dropped.  The stage is exclusive with feedback, a clamp and sampling; frames go in through `push_halves` or `frame` (an even spp)."""
+        who = "SvgfSequence.set_regress"
+        if variance not in REGRESS_VARIANCE:
+            raise ValueError("%s: variance is one of %s, got %r" % (who, ", ".join(REGRESS_VARIANCE), variance))
+        if not 0 <= int(mask) <= 7:
+            raise ValueError("%s: mask must be 0 .. 7 (bits: 1 albedo, 2 normal, 4 depth), got %r" % (who, mask))
+        if not ridge >= 0.0:
+            raise ValueError("%s: ridge must be at least 0 (0: the library default), got %r" % (who, ridge))
+        g = abi.Regress(search_radius=search_radius, patch_radius=patch_radius, k=k, ridge=ridge, features=int(mask), demodulate=0, reserved0=0, reserved1=0)
+        check(self._b.svgf_set_regress(self.handle, C.byref(g), REGRESS_VARIANCE.index(variance)), self._b, "rttnw_svgf_set_regress")
+
+    def clear_regress(self):
+        """The à-trous filter as the spatial stage again: the default.  The history is dropped if the stage was set."""
+        check(self._b.svgf_set_regress(self.handle, None, 0), self._b, "rttnw_svgf_set_regress")
+
+    def halves(self, want=HALVES_ARRAYS):
+        """`rttnw_svgf_halves`: a dict of the last frame call's "acc_a", "acc_b" (the accumulated halves), "filtered_a", "filtered_b" (the two fitted
+        halves), HxWx3 each, and "fit" (HxW: how many of the two directions used the first-order value), in the filter's units; `want` names those
+        to copy out.  All 0 before any call with the stage."""
+        for name in want:
+            if name not in HALVES_ARRAYS:
+                raise ValueError("SvgfSequence.halves: no output named %r (there are %s)" % (name, ", ".join(HALVES_ARRAYS)))
+        out = {name: np.zeros((self.height, self.width) if name == "fit" else (self.height, self.width, 3)) for name in want}
+        check(self._b.svgf_halves(self.handle, *[_ptr(out.get(name)) for name in HALVES_ARRAYS]), self._b, "rttnw_svgf_halves")
+        return out
+
+    def push_halves(self, half_a, half_b, features, cam, want=None, no_outputs=False):
+        """`rttnw_svgf_push_halves`: `push` on a handle with `set_regress` — the frame as the two halves `render_halves` returns."""
+        a_, b_ = np.ascontiguousarray(half_a, dtype=np.float64), np.ascontiguousarray(half_b, dtype=np.float64)
+        for arr in (a_, b_):
+            if arr.shape != (self.height, self.width, 3):
+                raise ValueError("SvgfSequence.push_halves: a half is %dx%dx3, got %s" % (self.height, self.width, arr.shape))
+        f = _feature_arrays(features, self.height, self.width)
+        arrays, out, ms = self._outputs(() if no_outputs else want)
+        rc = self._b.svgf_push_halves(self.handle, C.byref(cam), a_.ctypes.data, b_.ctypes.data, f["albedo"].ctypes.data, f["normal"].ctypes.data,
+                                      f["depth"].ctypes.data, f["alpha"].ctypes.data, None if no_outputs else C.byref(out))
+        check(rc, self._b, "rttnw_svgf_push_halves")
+        arrays["image_ms"], arrays["cam"] = ms.value, cam
+        return arrays
+
     def _outputs(self, want):
         """(dict of zeroed arrays, the rttnw_svgf_out over them, the image_ms cell); `want` None: everything, () : nothing (no struct at all)."""
         names = tuple(SVGF_ARRAYS) if want is None else tuple(want)
@@ -800,7 +847,8 @@ class SvgfSequence:
 
 def render_sequence_device(scene, cams, params, feedback=0, demodulate=False, iterations=5, max_history=0, depth_tolerance=0.0, normal_min=0.0,
                            on_frame=None, want=("linear_rgb", "rgba8", "raw_rgb", "length", "accumulated_rgb", "moment2_rgb", "variance_rgb", "prev_xy",
-                                                "albedo", "normal", "depth", "alpha"), clamp=None, sampling=None, want_spp=False):
+                                                "albedo", "normal", "depth", "alpha"), clamp=None, sampling=None, want_spp=False, spatial="atrous",
+                           regress_variance="temporal", want_halves=False):
     """`render_sequence(..., variance=True, denoise=True)` on the device: one `SvgfSequence`, one `frame` call per camera, frame k at
     `sample_begin = params.sample_begin + k * params.spp`.  With `feedback` 0 and without `demodulate` the images are that function's, bit for
     bit.  Returns the same list of dicts — "linear", "rgba8", "raw", "length", "accumulated" ("linear", "rgba8" absent, "moment2", "variance",
@@ -809,7 +857,19 @@ def render_sequence_device(scene, cams, params, feedback=0, demodulate=False, it
     and each frame carries "clipped", the call's map; None, the default, leaves the frames as they are.  `sampling` (a boost, or a pair
     (boost, fill); a 0: the default, 8 and 8.0): the handle gives pixels with a thin history up to boost times the frame's samples
     (`SvgfSequence.set_sampling`), and frame k starts at `sample_begin + k * boost * spp`; with `want_spp` each frame carries "spp" (HxW u32, the
-    samples each pixel got) and "probe_length" (the reprojected history length behind the choice)."""
+    samples each pixel got) and "probe_length" (the reprojected history length behind the choice).  `spatial`: "atrous" (the default) filters with
+    `rttnw_denoise`; "regress" and "nlm" make `denoise_regress` (every feature) or `denoise_nlm` the spatial stage over two accumulated halves
+    (`SvgfSequence.set_regress`; an even spp; no feedback, clamp or sampling beside it), `regress_variance` ("temporal" or "pair") choosing the
+    variances its weights read; with `want_halves` each frame carries "halves", what `SvgfSequence.halves` returns."""
+    if spatial not in SPATIAL_STAGES:
+        raise ValueError("render_sequence_device: spatial is one of %s, got %r" % (", ".join(SPATIAL_STAGES), spatial))
+    if regress_variance not in REGRESS_VARIANCE:
+        raise ValueError("render_sequence_device: regress_variance is one of %s, got %r" % (", ".join(REGRESS_VARIANCE), regress_variance))
+    if spatial != "atrous":
+        if feedback or clamp is not None or sampling is not None:
+            raise ValueError("render_sequence_device: spatial=%r does not combine with feedback, clamp or sampling" % (spatial,))
+        if params.spp < 2 or params.spp % 2:
+            raise ValueError("render_sequence_device: spatial=%r traces two halves: spp must be even and at least 2, got %d" % (spatial, params.spp))
     if clamp is not None and not float(clamp) >= 0.0:
         raise ValueError("render_sequence_device: clamp is the gamma of temporal_clamp, at least 0 (0: the default, 1.0), got %r" % (clamp,))
     if sampling is not None:
@@ -825,6 +885,8 @@ def render_sequence_device(scene, cams, params, feedback=0, demodulate=False, it
             seq.set_clamp(gamma=float(clamp))
         if sampling is not None:
             stride = seq.set_sampling(boost=sampling[0], fill=sampling[1])
+        if spatial != "atrous":
+            seq.set_regress(mask=7 if spatial == "regress" else 0, variance=regress_variance)
         for k, cam in enumerate(cams):
             p = copy.copy(params)
             p.sample_begin = params.sample_begin + k * stride * params.spp
@@ -838,6 +900,8 @@ def render_sequence_device(scene, cams, params, feedback=0, demodulate=False, it
                 frame["clipped"] = seq.clipped()
             if want_spp:
                 frame["spp"], frame["probe_length"] = seq.samples()
+            if want_halves:
+                frame["halves"] = seq.halves()
             frames.append(frame)
             if on_frame is not None:
                 on_frame(k, frame)
