@@ -1,9 +1,9 @@
 // clamp.hpp — the arithmetic of rttnw_temporal_clamp (include/rttnw_hip.h has the contract, DESIGN.md §10b the why), shared by the device kernel
 // (clamp.hip) and the host test harness (tests/clamp_host): neighbourhood variance clipping (Karis 2014; Salvi 2016) of the reprojected history in
 // front of the blend of variance.hpp's stage A.  Stage S takes the mean and the standard deviation of THIS frame's colour over the window of
-// variance_spatial — the same taps, drop rules, weights and order —, stage A' is variance_accumulate_pixel up to the history's two means, clips
-// the first into mean +- gamma * sd and blends.  One gather carries M1, M2 and — for the rttnw_svgf handle, with feedback — the colour history H:
-// the reprojection and the four taps are computed once, and H is clipped into the same interval as M1.
+// variance_spatial — the same taps, drop rules and order, the weights denoise.hpp's denoise_edge_stops —, stage A' takes temporal.hpp's taps and
+// the history's two means on them as variance.hpp's stage A does, clips the first into mean +- gamma * sd and blends.  One gather carries M1, M2
+// and — for the rttnw_svgf handle, with feedback — the colour history H: the taps are taken once, and H is clipped into the same interval as M1.
 //
 // Everything is double.  + - * /, sqrt, floor and comparisons only, every product through unfused_mul() (adaptive.hpp), the order of every sum
 // fixed here, so the device code, a g++ host build and a numpy restatement produce the same bits (tests/test_clamp_cpu.py, tests/test_gpu_clamp.py):
@@ -68,14 +68,8 @@ RT_HD void clamp_statistics(const ClampView& v, const ClampParams& prm, int w, i
             const int q = clamp_at(v, xx, yy);
             if (v.alpha[q] == 0.0) continue;
             const int q3 = q * v.pixel_step;
-            double wn = unfused_mul(n0[0], v.normal[q3]) + unfused_mul(n0[1], v.normal[q3 + v.channel_step]) +
-                        unfused_mul(n0[2], v.normal[q3 + 2 * v.channel_step]);
-            wn = wn > 0.0 ? wn : 0.0;
-            for (uint32_t k = 0; k < prm.normal_squarings; ++k) wn = unfused_mul(wn, wn);
-            const double z = v.depth[q], az = z < 0.0 ? -z : z;
-            const double qz = (z0 - z) / (unfused_mul(unfused_mul(prm.sigma_depth, az0 + az), 0.5) + DENOISE_TINY);
-            const double rz = 1.0 / (1.0 + unfused_mul(qz, qz));
-            const double wt = unfused_mul(wn, unfused_mul(rz, rz));
+            const EdgeStops e = denoise_edge_stops(n0, z0, az0, v.normal + q3, v.channel_step, v.depth[q], prm.normal_squarings, prm.sigma_depth);
+            const double wt = unfused_mul(e.wn, e.wz);
             sw = sw + wt;
             for (int ch = 0; ch < 3; ++ch) {
                 const double cq = v.colour[q3 + ch * v.channel_step];
@@ -91,50 +85,21 @@ RT_HD void clamp_statistics(const ClampView& v, const ClampParams& prm, int w, i
     }
 }
 
-// Stage A', first half: variance_accumulate_pixel's reprojection and four taps — its expressions in its order —, with the sums left open: the
-// window's bounds come between them and the blend.  `blend` is false in every pass-through case (no history, alpha == 0, no place in the previous
-// frame, W > 0 false).  sh is summed only with `feedback` (prev_history is then read).  The `prev_*` arrays are not read without a history.
-struct ClampGathered {
-    double sw, sl, s1[3], s2[3], sh[3], xy[2];
-    bool blend;
+// Stage A', first half: temporal.hpp's taps and the three sums over them, left open: the window's bounds come between them and the blend.  sh is
+// summed only with `feedback` (prev_history is then read) and is 0.0 otherwise; all three are 0.0 where `blend` is false.
+struct ClampGathered : TemporalTaps {
+    double s1[3], s2[3], sh[3];
 };
 RT_HD ClampGathered clamp_gather_pixel(uint32_t w, uint32_t h, uint32_t x, uint32_t y, const TemporalParams& q, bool feedback, const double* normal,
                                        const double* depth, const double* alpha, const double* prev_moment1, const double* prev_moment2,
                                        const double* prev_history, const double* prev_length, const double* prev_normal, const double* prev_depth,
                                        const double* prev_alpha) {
-    const size_t p = size_t(y) * w + x, o = p * 3;
-    const double nan = NAN;
     ClampGathered g;
-    g.sw = g.sl = 0.0;
-    for (int ch = 0; ch < 3; ++ch) g.s1[ch] = g.s2[ch] = g.sh[ch] = 0.0;
-    g.xy[0] = g.xy[1] = nan;
-    g.blend = false;
-    const double al = alpha[p];
-    if (!q.has_history || al == 0.0) return g;
-    double fx, fy, zq;
-    if (!temporal_where(w, h, x, y, q, depth[p] / al, fx, fy, zq)) return g;
-    g.xy[0] = fx;
-    g.xy[1] = fy;
-    const double x0 = floor(fx), y0 = floor(fy);
-    const double ax = fx - x0, ay = fy - y0;
-    const int ix = int(x0), iy = int(y0); // -1 .. w - 1, -1 .. h - 1
-    const double nn = temporal_dot(normal + o, normal + o);
-    for (int j = 0; j < 2; ++j)
-        for (int i = 0; i < 2; ++i) { // 00, 10, 01, 11
-            const int tx = ix + i, ty = iy + j;
-            if (tx < 0 || tx >= int(w) || ty < 0 || ty >= int(h)) continue;
-            const size_t tp = size_t(ty) * w + size_t(tx);
-            if (!temporal_accepts(q, tp, normal + o, nn, zq, prev_length, prev_normal, prev_depth, prev_alpha)) continue;
-            const double wt = unfused_mul(i ? ax : 1.0 - ax, j ? ay : 1.0 - ay);
-            g.sw = g.sw + wt;
-            g.sl = g.sl + unfused_mul(wt, prev_length[tp]);
-            for (int ch = 0; ch < 3; ++ch) {
-                g.s1[ch] = g.s1[ch] + unfused_mul(wt, prev_moment1[tp * 3 + ch]);
-                g.s2[ch] = g.s2[ch] + unfused_mul(wt, prev_moment2[tp * 3 + ch]);
-                if (feedback) g.sh[ch] = g.sh[ch] + unfused_mul(wt, prev_history[tp * 3 + ch]);
-            }
-        }
-    g.blend = g.sw > 0.0;
+    static_cast<TemporalTaps&>(g) = temporal_taps(w, h, x, y, q, normal, depth, alpha, prev_length, prev_normal, prev_depth, prev_alpha);
+    temporal_tap_sum(g, prev_moment1, g.s1);
+    temporal_tap_sum(g, prev_moment2, g.s2);
+    for (int ch = 0; ch < 3; ++ch) g.sh[ch] = 0.0;
+    if (feedback) temporal_tap_sum(g, prev_history, g.sh);
     return g;
 }
 
@@ -170,9 +135,7 @@ RT_HD ClampAccumulated clamp_finish_pixel(const ClampGathered& g, const Temporal
     out.length = 1.0;
     out.clipped = 0;
     if (!g.blend) return out;
-    const double grown = g.sl / g.sw + 1.0;
-    const double n = grown < q.max_history ? grown : q.max_history;
-    const double wa = 1.0 / n, wb = 1.0 - wa;
+    const TemporalBlend b = temporal_blend(g, q);
     for (int ch = 0; ch < 3; ++ch) {
         const double half = unfused_mul(prm.gamma, sd[ch]);
         const double lo = mu[ch] - half, hi = mu[ch] + half;
@@ -184,17 +147,17 @@ RT_HD ClampAccumulated clamp_finish_pixel(const ClampGathered& g, const Temporal
             h2c = (h2 - unfused_mul(h1, h1)) + unfused_mul(h1c, h1c);
             out.clipped = uint8_t(out.clipped | (1u << ch));
         }
-        out.m1[ch] = unfused_mul(wb, h1c) + unfused_mul(wa, cur[ch]);
-        out.m2[ch] = unfused_mul(wb, h2c) + unfused_mul(wa, sq[ch]);
+        out.m1[ch] = unfused_mul(b.wb, h1c) + unfused_mul(b.wa, cur[ch]);
+        out.m2[ch] = unfused_mul(b.wb, h2c) + unfused_mul(b.wa, sq[ch]);
         if (feedback) {
             const double hc = clamp_clip(g.sh[ch] / g.sw, lo, hi, moved);
             if (moved) out.clipped = uint8_t(out.clipped | (16u << ch));
-            out.a[ch] = unfused_mul(wb, hc) + unfused_mul(wa, cur[ch]);
+            out.a[ch] = unfused_mul(b.wb, hc) + unfused_mul(b.wa, cur[ch]);
         } else {
             out.a[ch] = out.m1[ch];
         }
     }
-    out.length = n;
+    out.length = b.n;
     return out;
 }
 

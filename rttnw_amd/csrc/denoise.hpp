@@ -122,6 +122,24 @@ template <bool FLAGS> RT_HD double atrous_centre_variance(const DenoiseView& in,
     return sum / sum_w; // (the centre itself is always among the taps: the caller has checked it)
 }
 
+// The feature stops of one tap, stated once for the à-trous pass below and the windows of variance.hpp and clamp.hpp: w_n and w_z of the formulas
+// below, apart — the pass multiplies its kernel weight in between.  n0, z0, az0 = |z0|: the centre's; n0 and n are three values `step` doubles apart.
+struct EdgeStops {
+    double wn, wz;
+};
+RT_HD EdgeStops denoise_edge_stops(const double* n0, double z0, double az0, const double* n, int step, double z, uint32_t normal_squarings,
+                                   double sigma_depth) {
+    EdgeStops e;
+    e.wn = unfused_mul(n0[0], n[0]) + unfused_mul(n0[1], n[step]) + unfused_mul(n0[2], n[2 * step]);
+    e.wn = e.wn > 0.0 ? e.wn : 0.0;
+    for (uint32_t k = 0; k < normal_squarings; ++k) e.wn = unfused_mul(e.wn, e.wn);
+    const double az = z < 0.0 ? -z : z;
+    const double qz = (z0 - z) / (unfused_mul(unfused_mul(sigma_depth, az0 + az), 0.5) + DENOISE_TINY);
+    const double rz = 1.0 / (1.0 + unfused_mul(qz, qz));
+    e.wz = unfused_mul(rz, rz);
+    return e;
+}
+
 // One pixel of one pass at stride `stride` (2^i in pass i): out_colour[3], out_variance[3] (written only when the view has a variance); returns H'.
 //   tap weight  w = h_x h_y * w_n * w_z * w_l,  h = (1, 4, 6, 4, 1) / 16;  taps outside the image, with alpha == 0 or without H are dropped
 //   w_n = max(0, n.n')^(2^k)                                             (k squarings)
@@ -164,20 +182,13 @@ RT_HD uint8_t atrous_filter_pixel(const DenoiseView& in, const uint8_t* holds, c
             if (in.alpha[q] == 0.0 || (FLAGS && !holds[q])) continue;
             const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
             const double h = double((ax == 0 ? 6 : ax == 1 ? 4 : 1) * (ay == 0 ? 6 : ay == 1 ? 4 : 1)) / 256.0; // exact
-            const double* n = in.normal + q * 3;
-            double wn = unfused_mul(n0[0], n[0]) + unfused_mul(n0[1], n[1]) + unfused_mul(n0[2], n[2]);
-            wn = wn > 0.0 ? wn : 0.0;
-            for (uint32_t k = 0; k < prm.normal_squarings; ++k) wn = unfused_mul(wn, wn);
-            const double z = in.depth[q], az = z < 0.0 ? -z : z;
-            const double qz = (z0 - z) / (unfused_mul(unfused_mul(prm.sigma_depth, az0 + az), 0.5) + DENOISE_TINY);
-            const double rz = 1.0 / (1.0 + unfused_mul(qz, qz));
-            const double wz = unfused_mul(rz, rz);
+            const EdgeStops e = denoise_edge_stops(n0, z0, az0, in.normal + q * 3, 1, in.depth[q], prm.normal_squarings, prm.sigma_depth);
             double wl = 1.0;
             if (var0) {
                 const double ql = (lum0 - denoise_luminance(in.colour + q * 3)) / lum_scale;
                 wl = 1.0 / (1.0 + unfused_mul(ql, ql));
             }
-            const double w = unfused_mul(unfused_mul(unfused_mul(h, wn), wz), wl);
+            const double w = unfused_mul(unfused_mul(unfused_mul(h, e.wn), e.wz), wl);
             sum_w = sum_w + w;
             for (int ch = 0; ch < 3; ++ch) sum_c[ch] = sum_c[ch] + unfused_mul(w, in.colour[q * 3 + ch]);
             if ((var0 || fill_var) && denoise_finite3(in.variance + q * 3)) {

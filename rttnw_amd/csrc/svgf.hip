@@ -228,6 +228,20 @@ struct OnHandleDevice {
     }
 };
 
+// An optional output of a call: nothing where the caller passed no array
+hipError_t copy_out(void* dst, const void* src, size_t bytes) { return dst ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
+
+// The four feature planes of a pushed frame, host to maps[cur ^ 1] in rttnw_render_features' layout: albedo, normal, depth, alpha
+int svgf_upload_features(const std::string& at, ::rttnw_svgf* g, const double* albedo, const double* normal, const double* depth, const double* alpha) {
+    const size_t npx = size_t(g->width) * g->height, b3 = npx * 3 * sizeof(double), b1 = npx * sizeof(double);
+    double* maps = g->maps[g->cur ^ 1].p;
+    HIP_TRY_AS(at, hipMemcpy(maps, albedo, b3, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps + npx * 3, normal, b3, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps + npx * 6, depth, b1, hipMemcpyHostToDevice));
+    HIP_TRY_AS(at, hipMemcpy(maps + npx * 7, alpha, b1, hipMemcpyHostToDevice));
+    return RTTNW_OK;
+}
+
 // rttnw_svgf_set_sampling's steps 2 and 3 behind the plain trace of the frame (g->packed holds every pixel at p->spp) and the feature pass
 // (maps[cur ^ 1]): the probe over the frame's features and the state's, then per level 2, 4, 8 up to the boost the mask {m == level}, its selection
 // bytes, the list of 2x2 blocks over them — one 8-byte copy gives the host its length —, render_tiles_t over that list at level * p->spp and the
@@ -368,22 +382,21 @@ int svgf_run(const char* call, ::rttnw_svgf* g, const rttnw_camera_desc* cam, bo
     g->cam = *cam;
     if (!out) return RTTNW_OK;
     const size_t b3 = npx * 3 * sizeof(double), b1 = npx * sizeof(double);
-    const auto copy = [](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
-    HIP_TRY_AS(at, copy(out->linear_rgb, g->out_lin.p, b3));
-    HIP_TRY_AS(at, copy(out->rgba8, g->rgba.p, npx * 4));
-    HIP_TRY_AS(at, copy(out->accumulated_rgb, g->out_acc.p, b3));
-    HIP_TRY_AS(at, copy(out->variance_rgb, g->var.p, b3));
-    HIP_TRY_AS(at, copy(out->filtered_variance_rgb, filtered_variance, b3));
-    HIP_TRY_AS(at, copy(out->length, g->len[nxt].p, b1));
-    HIP_TRY_AS(at, copy(out->prev_xy, g->xy.p, b1 * 2));
-    HIP_TRY_AS(at, copy(out->moment1_rgb, g->m1[nxt].p, b3));
-    HIP_TRY_AS(at, copy(out->moment2_rgb, g->m2[nxt].p, b3));
-    HIP_TRY_AS(at, copy(out->history_rgb, g->q.feedback_iterations ? g->hist.p : g->m1[nxt].p, b3));
-    HIP_TRY_AS(at, copy(out->raw_rgb, g->raw.p, b3));
-    HIP_TRY_AS(at, copy(out->albedo, albedo, b3));
-    HIP_TRY_AS(at, copy(out->normal, normal, b3));
-    HIP_TRY_AS(at, copy(out->depth, depth, b1));
-    HIP_TRY_AS(at, copy(out->alpha, alpha, b1));
+    HIP_TRY_AS(at, copy_out(out->linear_rgb, g->out_lin.p, b3));
+    HIP_TRY_AS(at, copy_out(out->rgba8, g->rgba.p, npx * 4));
+    HIP_TRY_AS(at, copy_out(out->accumulated_rgb, g->out_acc.p, b3));
+    HIP_TRY_AS(at, copy_out(out->variance_rgb, g->var.p, b3));
+    HIP_TRY_AS(at, copy_out(out->filtered_variance_rgb, filtered_variance, b3));
+    HIP_TRY_AS(at, copy_out(out->length, g->len[nxt].p, b1));
+    HIP_TRY_AS(at, copy_out(out->prev_xy, g->xy.p, b1 * 2));
+    HIP_TRY_AS(at, copy_out(out->moment1_rgb, g->m1[nxt].p, b3));
+    HIP_TRY_AS(at, copy_out(out->moment2_rgb, g->m2[nxt].p, b3));
+    HIP_TRY_AS(at, copy_out(out->history_rgb, g->q.feedback_iterations ? g->hist.p : g->m1[nxt].p, b3));
+    HIP_TRY_AS(at, copy_out(out->raw_rgb, g->raw.p, b3));
+    HIP_TRY_AS(at, copy_out(out->albedo, albedo, b3));
+    HIP_TRY_AS(at, copy_out(out->normal, normal, b3));
+    HIP_TRY_AS(at, copy_out(out->depth, depth, b1));
+    HIP_TRY_AS(at, copy_out(out->alpha, alpha, b1));
     if (out->image_ms) {
         float ms = 0;
         HIP_TRY_AS(at, hipEventElapsedTime(&ms, g->ev0.get(), g->ev1.get()));
@@ -558,13 +571,9 @@ int rttnw_svgf_push(rttnw_svgf* q, const rttnw_camera_desc* cam, const double* l
     const rt::OnHandleDevice on(call, q);
     if (on.rc) return on.rc;
     const std::string& at = on.at;
-    const size_t npx = size_t(q->width) * q->height, b3 = npx * 3 * sizeof(double), b1 = npx * sizeof(double);
-    double* maps = q->maps[q->cur ^ 1].p;
+    const size_t b3 = size_t(q->width) * q->height * 3 * sizeof(double);
     HIP_TRY_AS(at, hipMemcpy(q->raw.p, linear_rgb, b3, hipMemcpyHostToDevice));
-    HIP_TRY_AS(at, hipMemcpy(maps, albedo, b3, hipMemcpyHostToDevice));
-    HIP_TRY_AS(at, hipMemcpy(maps + npx * 3, normal, b3, hipMemcpyHostToDevice));
-    HIP_TRY_AS(at, hipMemcpy(maps + npx * 6, depth, b1, hipMemcpyHostToDevice));
-    HIP_TRY_AS(at, hipMemcpy(maps + npx * 7, alpha, b1, hipMemcpyHostToDevice));
+    if (int rc = rt::svgf_upload_features(at, q, albedo, normal, depth, alpha)) return rc;
     return rt::svgf_run(call, q, cam, false, RTTNW_F64, out);
 }
 
@@ -625,14 +634,10 @@ int rttnw_svgf_push_halves(rttnw_svgf* q, const rttnw_camera_desc* cam, const do
     const rt::OnHandleDevice on(call, q);
     if (on.rc) return on.rc;
     const std::string& at = on.at;
-    const size_t npx = size_t(q->width) * q->height, b3 = npx * 3 * sizeof(double), b1 = npx * sizeof(double);
-    double* maps = q->maps[q->cur ^ 1].p;
+    const size_t b3 = size_t(q->width) * q->height * 3 * sizeof(double);
     HIP_TRY_AS(at, hipMemcpy(q->ca.p, half_a, b3, hipMemcpyHostToDevice));
     HIP_TRY_AS(at, hipMemcpy(q->cb.p, half_b, b3, hipMemcpyHostToDevice));
-    HIP_TRY_AS(at, hipMemcpy(maps, albedo, b3, hipMemcpyHostToDevice));
-    HIP_TRY_AS(at, hipMemcpy(maps + npx * 3, normal, b3, hipMemcpyHostToDevice));
-    HIP_TRY_AS(at, hipMemcpy(maps + npx * 6, depth, b1, hipMemcpyHostToDevice));
-    HIP_TRY_AS(at, hipMemcpy(maps + npx * 7, alpha, b1, hipMemcpyHostToDevice));
+    if (int rc = rt::svgf_upload_features(at, q, albedo, normal, depth, alpha)) return rc;
     return rt::svgf_run(call, q, cam, false, RTTNW_F64, out);
 }
 
@@ -650,12 +655,11 @@ int rttnw_svgf_halves(rttnw_svgf* q, double* out_acc_a, double* out_acc_b, doubl
     if (on.rc) return on.rc;
     const std::string& at = on.at;
     const size_t b3 = npx * 3 * sizeof(double);
-    const auto copy = [](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
-    HIP_TRY_AS(at, copy(out_acc_a, q->ha[q->cur].p, b3)); // (the last frame call's Aa and Ab are the state's Ha and Hb)
-    HIP_TRY_AS(at, copy(out_acc_b, q->hb[q->cur].p, b3));
-    HIP_TRY_AS(at, copy(out_filtered_a, q->g_fa.p, b3));
-    HIP_TRY_AS(at, copy(out_filtered_b, q->g_fb.p, b3));
-    HIP_TRY_AS(at, copy(out_fit, q->g_fit.p, npx * sizeof(double)));
+    HIP_TRY_AS(at, rt::copy_out(out_acc_a, q->ha[q->cur].p, b3)); // (the last frame call's Aa and Ab are the state's Ha and Hb)
+    HIP_TRY_AS(at, rt::copy_out(out_acc_b, q->hb[q->cur].p, b3));
+    HIP_TRY_AS(at, rt::copy_out(out_filtered_a, q->g_fa.p, b3));
+    HIP_TRY_AS(at, rt::copy_out(out_filtered_b, q->g_fb.p, b3));
+    HIP_TRY_AS(at, rt::copy_out(out_fit, q->g_fit.p, npx * sizeof(double)));
     return RTTNW_OK;
 }
 

@@ -4,7 +4,7 @@
 // denoise.hpp's passes, both as they are.
 //   ingest      the frame's colour as doubles and, with `demodulate`, divided by the first-hit albedo under rttnw_denoise's rule, with one "was
 //               divided" byte per channel
-//   accumulate  variance_accumulate_pixel — the reprojection and the four taps computed once — with a third quantity on the same accepted taps:
+//   accumulate  variance.hpp's stage A on temporal.hpp's taps — the reprojection and the four taps computed once — with a third quantity on them:
 //               the fed-back colour history H beside the moments M1 and M2.  Each quantity is, bit for bit, what its own entry point computes:
 //               M1, M2, length and xy rttnw_temporal_variance's stage A, the colour rttnw_temporal_accumulate's over prev_linear = H
 //   emit        the filtered image and the accumulation multiplied back on the channels ingest divided, and the RGBA8
@@ -34,58 +34,29 @@ struct SvgfAccumulated {
     double m1[3], m2[3], a[3], length, xy[2]; // a: the filter's input — the blend over H with `feedback`, m1 without
 };
 
-// Accumulate, one pixel: variance_accumulate_pixel's expressions in its order, and with `feedback` (a fed-back history exists: prev_history is
-// read) temporal_pixel's colour over prev_history on the same taps.  The `prev_*` arrays are not read without a history.
+// Accumulate, one pixel: temporal.hpp's taps once, variance.hpp's stage A on them over prev_moment1 and prev_moment2, and with `feedback` (a
+// fed-back history exists: prev_history is read) temporal_pixel's colour over prev_history on the same taps.  The `prev_*` arrays are not read
+// without a history.
 RT_HD SvgfAccumulated svgf_accumulate_pixel(uint32_t w, uint32_t h, uint32_t x, uint32_t y, const TemporalParams& q, bool feedback, const double* linear,
                                             const double* normal, const double* depth, const double* alpha, const double* prev_moment1,
                                             const double* prev_moment2, const double* prev_history, const double* prev_length, const double* prev_normal,
                                             const double* prev_depth, const double* prev_alpha) {
-    const size_t p = size_t(y) * w + x, o = p * 3;
-    const double nan = NAN;
+    const size_t o = (size_t(y) * w + x) * 3;
+    const TemporalTaps t = temporal_taps(w, h, x, y, q, normal, depth, alpha, prev_length, prev_normal, prev_depth, prev_alpha);
+    const VarianceAccumulated m = variance_accumulate_taps(t, q, linear + o, prev_moment1, prev_moment2);
     SvgfAccumulated out;
-    double sq[3];
-    for (int ch = 0; ch < 3; ++ch) { // this frame alone: no history, a miss, a reset
-        out.m1[ch] = out.a[ch] = linear[o + ch];
-        out.m2[ch] = sq[ch] = unfused_mul(linear[o + ch], linear[o + ch]);
-    }
-    out.length = 1.0;
-    out.xy[0] = out.xy[1] = nan;
-    const double al = alpha[p];
-    if (!q.has_history || al == 0.0) return out;
-    double fx, fy, zq;
-    if (!temporal_where(w, h, x, y, q, depth[p] / al, fx, fy, zq)) return out;
-    out.xy[0] = fx;
-    out.xy[1] = fy;
-    const double x0 = floor(fx), y0 = floor(fy);
-    const double ax = fx - x0, ay = fy - y0;
-    const int ix = int(x0), iy = int(y0); // -1 .. w - 1, -1 .. h - 1
-    const double nn = temporal_dot(normal + o, normal + o);
-    double sw = 0.0, sl = 0.0, s1[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0}, sh[3] = {0.0, 0.0, 0.0};
-    for (int j = 0; j < 2; ++j)
-        for (int i = 0; i < 2; ++i) { // 00, 10, 01, 11
-            const int tx = ix + i, ty = iy + j;
-            if (tx < 0 || tx >= int(w) || ty < 0 || ty >= int(h)) continue;
-            const size_t tp = size_t(ty) * w + size_t(tx);
-            if (!temporal_accepts(q, tp, normal + o, nn, zq, prev_length, prev_normal, prev_depth, prev_alpha)) continue;
-            const double wt = unfused_mul(i ? ax : 1.0 - ax, j ? ay : 1.0 - ay);
-            sw = sw + wt;
-            sl = sl + unfused_mul(wt, prev_length[tp]);
-            for (int ch = 0; ch < 3; ++ch) {
-                s1[ch] = s1[ch] + unfused_mul(wt, prev_moment1[tp * 3 + ch]);
-                s2[ch] = s2[ch] + unfused_mul(wt, prev_moment2[tp * 3 + ch]);
-                if (feedback) sh[ch] = sh[ch] + unfused_mul(wt, prev_history[tp * 3 + ch]);
-            }
-        }
-    if (!(sw > 0.0)) return out; // reset
-    const double grown = sl / sw + 1.0;
-    const double n = grown < q.max_history ? grown : q.max_history;
-    const double wa = 1.0 / n, wb = 1.0 - wa;
     for (int ch = 0; ch < 3; ++ch) {
-        out.m1[ch] = unfused_mul(wb, s1[ch] / sw) + unfused_mul(wa, linear[o + ch]);
-        out.m2[ch] = unfused_mul(wb, s2[ch] / sw) + unfused_mul(wa, sq[ch]);
-        out.a[ch] = feedback ? unfused_mul(wb, sh[ch] / sw) + unfused_mul(wa, linear[o + ch]) : out.m1[ch];
+        out.m1[ch] = out.a[ch] = m.c[ch];
+        out.m2[ch] = m.m2[ch];
     }
-    out.length = n;
+    out.length = m.length;
+    out.xy[0] = m.xy[0];
+    out.xy[1] = m.xy[1];
+    if (!feedback || !t.blend) return out;
+    double sh[3];
+    temporal_tap_sum(t, prev_history, sh);
+    const TemporalBlend b = temporal_blend(t, q);
+    for (int ch = 0; ch < 3; ++ch) out.a[ch] = unfused_mul(b.wb, sh[ch] / t.sw) + unfused_mul(b.wa, linear[o + ch]);
     return out;
 }
 
@@ -93,65 +64,36 @@ struct SvgfAccumulatedHalves {
     double m1[3], m2[3], a[3], b[3], length, xy[2]; // a, b: the two accumulated halves Aa and Ab, the regression stage's inputs
 };
 
-// Accumulate with rttnw_svgf_set_regress, one pixel: svgf_accumulate_pixel's expressions in its order, and the two half histories Ha and Hb on the
-// accepted taps where H rides there — each blended with its own half of the frame, temporal_pixel's colour over prev_half_a / prev_half_b.  M1, M2,
-// length and xy are svgf_accumulate_pixel's of `linear` bit for bit.  Every pass-through case leaves a half as the frame's.  The `prev_*` arrays
-// are not read without a history.
+// Accumulate with rttnw_svgf_set_regress, one pixel: svgf_accumulate_pixel's M1, M2, length and xy of `linear`, and the two half histories Ha and Hb
+// on the same taps where H rides there — each blended with its own half of the frame, temporal_pixel's colour over prev_half_a / prev_half_b.  Every
+// pass-through case leaves a half as the frame's.  The `prev_*` arrays are not read without a history.
 RT_HD SvgfAccumulatedHalves svgf_accumulate_halves_pixel(uint32_t w, uint32_t h, uint32_t x, uint32_t y, const TemporalParams& q, const double* linear,
                                                         const double* half_a, const double* half_b, const double* normal, const double* depth,
                                                         const double* alpha, const double* prev_moment1, const double* prev_moment2,
                                                         const double* prev_half_a, const double* prev_half_b, const double* prev_length,
                                                         const double* prev_normal, const double* prev_depth, const double* prev_alpha) {
-    const size_t p = size_t(y) * w + x, o = p * 3;
-    const double nan = NAN;
+    const size_t o = (size_t(y) * w + x) * 3;
+    const TemporalTaps t = temporal_taps(w, h, x, y, q, normal, depth, alpha, prev_length, prev_normal, prev_depth, prev_alpha);
+    const VarianceAccumulated m = variance_accumulate_taps(t, q, linear + o, prev_moment1, prev_moment2);
     SvgfAccumulatedHalves out;
-    double sq[3];
-    for (int ch = 0; ch < 3; ++ch) { // this frame alone: no history, a miss, a reset
-        out.m1[ch] = linear[o + ch];
-        out.m2[ch] = sq[ch] = unfused_mul(linear[o + ch], linear[o + ch]);
+    for (int ch = 0; ch < 3; ++ch) {
+        out.m1[ch] = m.c[ch];
+        out.m2[ch] = m.m2[ch];
         out.a[ch] = half_a[o + ch];
         out.b[ch] = half_b[o + ch];
     }
-    out.length = 1.0;
-    out.xy[0] = out.xy[1] = nan;
-    const double al = alpha[p];
-    if (!q.has_history || al == 0.0) return out;
-    double fx, fy, zq;
-    if (!temporal_where(w, h, x, y, q, depth[p] / al, fx, fy, zq)) return out;
-    out.xy[0] = fx;
-    out.xy[1] = fy;
-    const double x0 = floor(fx), y0 = floor(fy);
-    const double ax = fx - x0, ay = fy - y0;
-    const int ix = int(x0), iy = int(y0); // -1 .. w - 1, -1 .. h - 1
-    const double nn = temporal_dot(normal + o, normal + o);
-    double sw = 0.0, sl = 0.0, s1[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0}, sa[3] = {0.0, 0.0, 0.0}, sb[3] = {0.0, 0.0, 0.0};
-    for (int j = 0; j < 2; ++j)
-        for (int i = 0; i < 2; ++i) { // 00, 10, 01, 11
-            const int tx = ix + i, ty = iy + j;
-            if (tx < 0 || tx >= int(w) || ty < 0 || ty >= int(h)) continue;
-            const size_t tp = size_t(ty) * w + size_t(tx);
-            if (!temporal_accepts(q, tp, normal + o, nn, zq, prev_length, prev_normal, prev_depth, prev_alpha)) continue;
-            const double wt = unfused_mul(i ? ax : 1.0 - ax, j ? ay : 1.0 - ay);
-            sw = sw + wt;
-            sl = sl + unfused_mul(wt, prev_length[tp]);
-            for (int ch = 0; ch < 3; ++ch) {
-                s1[ch] = s1[ch] + unfused_mul(wt, prev_moment1[tp * 3 + ch]);
-                s2[ch] = s2[ch] + unfused_mul(wt, prev_moment2[tp * 3 + ch]);
-                sa[ch] = sa[ch] + unfused_mul(wt, prev_half_a[tp * 3 + ch]);
-                sb[ch] = sb[ch] + unfused_mul(wt, prev_half_b[tp * 3 + ch]);
-            }
-        }
-    if (!(sw > 0.0)) return out; // reset
-    const double grown = sl / sw + 1.0;
-    const double n = grown < q.max_history ? grown : q.max_history;
-    const double wa = 1.0 / n, wb = 1.0 - wa;
+    out.length = m.length;
+    out.xy[0] = m.xy[0];
+    out.xy[1] = m.xy[1];
+    if (!t.blend) return out;
+    double sa[3], sb[3];
+    temporal_tap_sum(t, prev_half_a, sa);
+    temporal_tap_sum(t, prev_half_b, sb);
+    const TemporalBlend b = temporal_blend(t, q);
     for (int ch = 0; ch < 3; ++ch) {
-        out.m1[ch] = unfused_mul(wb, s1[ch] / sw) + unfused_mul(wa, linear[o + ch]);
-        out.m2[ch] = unfused_mul(wb, s2[ch] / sw) + unfused_mul(wa, sq[ch]);
-        out.a[ch] = unfused_mul(wb, sa[ch] / sw) + unfused_mul(wa, half_a[o + ch]);
-        out.b[ch] = unfused_mul(wb, sb[ch] / sw) + unfused_mul(wa, half_b[o + ch]);
+        out.a[ch] = unfused_mul(b.wb, sa[ch] / t.sw) + unfused_mul(b.wa, half_a[o + ch]);
+        out.b[ch] = unfused_mul(b.wb, sb[ch] / t.sw) + unfused_mul(b.wa, half_b[o + ch]);
     }
-    out.length = n;
     return out;
 }
 

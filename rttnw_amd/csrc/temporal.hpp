@@ -12,7 +12,12 @@
 //   q = P - o_p;  lambda = dot(e, n) / dot(q, n), n = H_p x V_p, e = llc_p - o_p;  r = lambda q - e
 //   fx = (dot(r, H_p) / dot(H_p, H_p)) * w - 0.5;  fy = (h - (dot(r, V_p) / dot(V_p, V_p)) * h) - 0.5;  zq = sqrt(dot(q, q))
 //   taps (floor(fx) + i, floor(fy) + j), i then j, weights (i ? ax : 1 - ax) * (j ? ay : 1 - ay); sums from 0.0 over the accepted taps in that order
-//   N = min(L + 1, max_history);  a = 1 / N;  out = (1 - a) * hist + a * cur;  out_var = ((1 - a)(1 - a)) * vh + (a a) * var
+//   temporal_taps:     tap k = 00, 10, 01, 11 kept where it is inside the image and temporal_accepts it;  W = sum wt;  SL = sum wt * length';
+//                      blend = W > 0 — each sum a chain of its own over the kept taps, a tap not kept skipped
+//   temporal_tap_sum:  S[ch] = sum wt * q'[ch] of one RGB quantity q of the previous frame, likewise;  its mean is S / W
+//   temporal_blend:    L = SL / W;  N = min(L + 1, max_history);  a = 1 / N;  (1 - a)
+//   out = (1 - a) * hist + a * cur;  out_var = ((1 - a)(1 - a)) * vh + (a a) * var
+// The three functions are the one statement of the reprojected gather: variance.hpp, clamp.hpp, probe.hpp and svgf.hpp hang their quantities on them.
 #pragma once
 #include "denoise.hpp"
 
@@ -112,6 +117,82 @@ RT_HD bool temporal_accepts(const TemporalParams& q, size_t p, const double* nor
     return true;
 }
 
+// The reprojection and the four bilinear taps of one pixel, once for every stage that reads a history (temporal_pixel here; variance.hpp, clamp.hpp,
+// probe.hpp and svgf.hpp): which taps are kept, their weights and places, and the two sums every stage needs.  Fixed slots in the order 00, 10, 01,
+// 11 with a flag each: a tap outside the image or refused by temporal_accepts is SKIPPED, never weighted 0 — histories carry NaN and inf.  No tap
+// is kept (blend == false, sw == sl == 0.0) without a history, where alpha == 0, where the pixel has no place in the previous frame (xy stays NaN)
+// and where the kept weights do not sum above 0 (a reset).  The `prev_*` arrays are not read without a history.
+struct TemporalTaps {
+    double xy[2];  // (fx, fy); NaN, NaN where the pixel has no place in the previous frame
+    double sw, sl; // sum wt and sum wt * prev_length over the kept taps, from 0.0, in tap order
+    double wt[4];
+    size_t at[4];  // pixel index of tap k in the previous frame
+    bool ok[4];    // tap k is kept
+    bool blend;    // sw > 0
+};
+RT_HD TemporalTaps temporal_taps(uint32_t w, uint32_t h, uint32_t x, uint32_t y, const TemporalParams& q, const double* normal, const double* depth,
+                                 const double* alpha, const double* prev_length, const double* prev_normal, const double* prev_depth,
+                                 const double* prev_alpha) {
+    const size_t p = size_t(y) * w + x, o = p * 3;
+    TemporalTaps t;
+    t.xy[0] = t.xy[1] = NAN;
+    t.sw = t.sl = 0.0;
+    t.blend = false;
+    for (int k = 0; k < 4; ++k) {
+        t.ok[k] = false;
+        t.wt[k] = 0.0;
+        t.at[k] = 0;
+    }
+    const double a = alpha[p];
+    if (!q.has_history || a == 0.0) return t;
+    double fx, fy, zq;
+    if (!temporal_where(w, h, x, y, q, depth[p] / a, fx, fy, zq)) return t;
+    t.xy[0] = fx;
+    t.xy[1] = fy;
+    const double x0 = floor(fx), y0 = floor(fy);
+    const double ax = fx - x0, ay = fy - y0;
+    const int ix = int(x0), iy = int(y0); // -1 .. w - 1, -1 .. h - 1
+    const double nn = temporal_dot(normal + o, normal + o);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { // 00, 10, 01, 11; unrolled, so that every slot is a register on the device
+        const int i = k & 1, j = k >> 1;
+        const int tx = ix + i, ty = iy + j;
+        if (tx < 0 || tx >= int(w) || ty < 0 || ty >= int(h)) continue;
+        const size_t tp = size_t(ty) * w + size_t(tx);
+        if (!temporal_accepts(q, tp, normal + o, nn, zq, prev_length, prev_normal, prev_depth, prev_alpha)) continue;
+        const double wt = unfused_mul(i ? ax : 1.0 - ax, j ? ay : 1.0 - ay);
+        t.ok[k] = true;
+        t.wt[k] = wt;
+        t.at[k] = tp;
+        t.sw = t.sw + wt;
+        t.sl = t.sl + unfused_mul(wt, prev_length[tp]);
+    }
+    t.blend = t.sw > 0.0;
+    return t;
+}
+
+// One RGB quantity of the previous frame over the kept taps: a chain of its own per channel, from 0.0, in tap order
+RT_HD void temporal_tap_sum(const TemporalTaps& t, const double* prev_rgb, double* s) {
+    s[0] = s[1] = s[2] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (t.ok[k])
+            for (int ch = 0; ch < 3; ++ch) s[ch] = s[ch] + unfused_mul(t.wt[k], prev_rgb[t.at[k] * 3 + ch]);
+}
+
+// The running mean's weights where t.blend: the history's length grown by this frame, capped; wa for this frame, wb for the history
+struct TemporalBlend {
+    double n, wa, wb;
+};
+RT_HD TemporalBlend temporal_blend(const TemporalTaps& t, const TemporalParams& q) {
+    const double grown = t.sl / t.sw + 1.0;
+    TemporalBlend b;
+    b.n = grown < q.max_history ? grown : q.max_history;
+    b.wa = 1.0 / b.n;
+    b.wb = 1.0 - b.wa;
+    return b;
+}
+
 struct TemporalPixel {
     double c[3], v[3], length, xy[2]; // v is meaningful with variances only
 };
@@ -120,49 +201,26 @@ struct TemporalPixel {
 RT_HD TemporalPixel temporal_pixel(uint32_t w, uint32_t h, uint32_t x, uint32_t y, const TemporalParams& q, const double* linear, const double* variance,
                                    const double* normal, const double* depth, const double* alpha, const double* prev_linear, const double* prev_variance,
                                    const double* prev_length, const double* prev_normal, const double* prev_depth, const double* prev_alpha) {
-    const size_t p = size_t(y) * w + x, o = p * 3;
-    const double nan = NAN;
+    const size_t o = (size_t(y) * w + x) * 3;
     TemporalPixel out;
     for (int ch = 0; ch < 3; ++ch) { // this frame alone: no history, a miss, a reset
         out.c[ch] = linear[o + ch];
         out.v[ch] = q.has_variance ? variance[o + ch] : 0.0;
     }
     out.length = 1.0;
-    out.xy[0] = out.xy[1] = nan;
-    const double a = alpha[p];
-    if (!q.has_history || a == 0.0) return out;
-    double fx, fy, zq;
-    if (!temporal_where(w, h, x, y, q, depth[p] / a, fx, fy, zq)) return out;
-    out.xy[0] = fx;
-    out.xy[1] = fy;
-    const double x0 = floor(fx), y0 = floor(fy);
-    const double ax = fx - x0, ay = fy - y0;
-    const int ix = int(x0), iy = int(y0); // -1 .. w - 1, -1 .. h - 1
-    const double nn = temporal_dot(normal + o, normal + o);
-    double sw = 0.0, sl = 0.0, sc[3] = {0.0, 0.0, 0.0}, sv[3] = {0.0, 0.0, 0.0};
-    for (int j = 0; j < 2; ++j)
-        for (int i = 0; i < 2; ++i) { // 00, 10, 01, 11
-            const int tx = ix + i, ty = iy + j;
-            if (tx < 0 || tx >= int(w) || ty < 0 || ty >= int(h)) continue;
-            const size_t tp = size_t(ty) * w + size_t(tx);
-            if (!temporal_accepts(q, tp, normal + o, nn, zq, prev_length, prev_normal, prev_depth, prev_alpha)) continue;
-            const double wt = unfused_mul(i ? ax : 1.0 - ax, j ? ay : 1.0 - ay);
-            sw = sw + wt;
-            sl = sl + unfused_mul(wt, prev_length[tp]);
-            for (int ch = 0; ch < 3; ++ch) {
-                sc[ch] = sc[ch] + unfused_mul(wt, prev_linear[tp * 3 + ch]);
-                if (q.has_variance) sv[ch] = sv[ch] + unfused_mul(wt, prev_variance[tp * 3 + ch]);
-            }
-        }
-    if (!(sw > 0.0)) return out; // reset
-    const double grown = sl / sw + 1.0;
-    const double n = grown < q.max_history ? grown : q.max_history;
-    const double wa = 1.0 / n, wb = 1.0 - wa;
+    const TemporalTaps t = temporal_taps(w, h, x, y, q, normal, depth, alpha, prev_length, prev_normal, prev_depth, prev_alpha);
+    out.xy[0] = t.xy[0];
+    out.xy[1] = t.xy[1];
+    if (!t.blend) return out;
+    double sc[3], sv[3];
+    temporal_tap_sum(t, prev_linear, sc);
+    if (q.has_variance) temporal_tap_sum(t, prev_variance, sv);
+    const TemporalBlend b = temporal_blend(t, q);
     for (int ch = 0; ch < 3; ++ch) {
-        out.c[ch] = unfused_mul(wb, sc[ch] / sw) + unfused_mul(wa, linear[o + ch]);
-        if (q.has_variance) out.v[ch] = unfused_mul(unfused_mul(wb, wb), sv[ch] / sw) + unfused_mul(unfused_mul(wa, wa), variance[o + ch]);
+        out.c[ch] = unfused_mul(b.wb, sc[ch] / t.sw) + unfused_mul(b.wa, linear[o + ch]);
+        if (q.has_variance) out.v[ch] = unfused_mul(unfused_mul(b.wb, b.wb), sv[ch] / t.sw) + unfused_mul(unfused_mul(b.wa, b.wa), variance[o + ch]);
     }
-    out.length = n;
+    out.length = b.n;
     return out;
 }
 

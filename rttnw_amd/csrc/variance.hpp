@@ -1,7 +1,7 @@
 // variance.hpp — the arithmetic of rttnw_temporal_variance (include/rttnw_hip.h has the contract, DESIGN.md §10b the why), shared by the device
 // kernels (variance.hip) and the host test harness (tests/variance_host): the variance estimation of SVGF (Schied et al. 2017, §4.2) behind the
-// accumulation of temporal.hpp.  Stage A is rttnw_temporal_accumulate without variances — the same reprojection, taps and blend, through
-// temporal_where and temporal_accepts — with the second moment riding on the accepted taps.  Stage B reads stage A's outputs: where a pixel's
+// accumulation of temporal.hpp.  Stage A is rttnw_temporal_accumulate without variances — its reprojection, taps and blend, through temporal_taps,
+// temporal_tap_sum and temporal_blend — with the second moment riding on the accepted taps.  Stage B reads stage A's outputs: where a pixel's
 // history is long enough the variance of its mean comes from the two moments, elsewhere from a window guided by normal and depth.
 //
 // Everything is double.  + - * /, sqrt, floor and comparisons only, every product through unfused_mul() (adaptive.hpp), the order of every sum
@@ -9,7 +9,7 @@
 // tests/test_gpu_variance.py):
 //   A: h2 = (sum wt m2') / W;  s = cur * cur;  out_m2 = (1 - a) * h2 + a * s;  out_m2 = s wherever the colour passes through
 //   B: pos(x) = x < 0 ? 0 : x;  alpha == 0: 0;  N >= min_temporal: pos(m2 - m1 m1) / (N - 1);  otherwise over the window, dy outer, dx inner,
-//      w = w_n w_z (denoise.hpp, atrous_filter_pixel), Sw = sum w, M1 = (sum w m1') / Sw, M2 = (sum w m2') / Sw:  pos(M2 - M1 M1) / N;
+//      w = w_n w_z (denoise.hpp, denoise_edge_stops), Sw = sum w, M1 = (sum w m1') / Sw, M2 = (sum w m2') / Sw:  pos(M2 - M1 M1) / N;
 //      Sw > 0 false: pos(m2 - m1 m1) / N
 #pragma once
 #include "temporal.hpp"
@@ -39,57 +39,40 @@ struct VarianceAccumulated {
     double c[3], m2[3], length, xy[2];
 };
 
-// Stage A, one pixel: temporal_pixel without variances — the same expressions in the same order, so c, length and xy are its bits — and the second
-// moment beside the colour.  The `prev_*` arrays are not read without a history.
+// Stage A on taps that are already taken (svgf.hpp takes them once for more quantities): `cur` is this pixel's colour; every pass-through case
+// leaves the colour and its square.
+RT_HD VarianceAccumulated variance_accumulate_taps(const TemporalTaps& t, const TemporalParams& q, const double* cur, const double* prev_linear,
+                                                   const double* prev_moment2) {
+    VarianceAccumulated out;
+    double sq[3];
+    for (int ch = 0; ch < 3; ++ch) { // this frame alone: no history, a miss, a reset
+        out.c[ch] = cur[ch];
+        out.m2[ch] = sq[ch] = unfused_mul(cur[ch], cur[ch]);
+    }
+    out.length = 1.0;
+    out.xy[0] = t.xy[0];
+    out.xy[1] = t.xy[1];
+    if (!t.blend) return out;
+    double sc[3], s2[3];
+    temporal_tap_sum(t, prev_linear, sc);
+    temporal_tap_sum(t, prev_moment2, s2);
+    const TemporalBlend b = temporal_blend(t, q);
+    for (int ch = 0; ch < 3; ++ch) {
+        out.c[ch] = unfused_mul(b.wb, sc[ch] / t.sw) + unfused_mul(b.wa, cur[ch]);
+        out.m2[ch] = unfused_mul(b.wb, s2[ch] / t.sw) + unfused_mul(b.wa, sq[ch]);
+    }
+    out.length = b.n;
+    return out;
+}
+
+// Stage A, one pixel: temporal.hpp's taps — so c, length and xy are temporal_pixel's bits without variances — and the second moment beside the
+// colour.  The `prev_*` arrays are not read without a history.
 RT_HD VarianceAccumulated variance_accumulate_pixel(uint32_t w, uint32_t h, uint32_t x, uint32_t y, const TemporalParams& q, const double* linear,
                                                     const double* normal, const double* depth, const double* alpha, const double* prev_linear,
                                                     const double* prev_moment2, const double* prev_length, const double* prev_normal,
                                                     const double* prev_depth, const double* prev_alpha) {
-    const size_t p = size_t(y) * w + x, o = p * 3;
-    const double nan = NAN;
-    VarianceAccumulated out;
-    double sq[3];
-    for (int ch = 0; ch < 3; ++ch) { // this frame alone: no history, a miss, a reset
-        out.c[ch] = linear[o + ch];
-        out.m2[ch] = sq[ch] = unfused_mul(linear[o + ch], linear[o + ch]);
-    }
-    out.length = 1.0;
-    out.xy[0] = out.xy[1] = nan;
-    const double a = alpha[p];
-    if (!q.has_history || a == 0.0) return out;
-    double fx, fy, zq;
-    if (!temporal_where(w, h, x, y, q, depth[p] / a, fx, fy, zq)) return out;
-    out.xy[0] = fx;
-    out.xy[1] = fy;
-    const double x0 = floor(fx), y0 = floor(fy);
-    const double ax = fx - x0, ay = fy - y0;
-    const int ix = int(x0), iy = int(y0); // -1 .. w - 1, -1 .. h - 1
-    const double nn = temporal_dot(normal + o, normal + o);
-    double sw = 0.0, sl = 0.0, sc[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0};
-    for (int j = 0; j < 2; ++j)
-        for (int i = 0; i < 2; ++i) { // 00, 10, 01, 11
-            const int tx = ix + i, ty = iy + j;
-            if (tx < 0 || tx >= int(w) || ty < 0 || ty >= int(h)) continue;
-            const size_t tp = size_t(ty) * w + size_t(tx);
-            if (!temporal_accepts(q, tp, normal + o, nn, zq, prev_length, prev_normal, prev_depth, prev_alpha)) continue;
-            const double wt = unfused_mul(i ? ax : 1.0 - ax, j ? ay : 1.0 - ay);
-            sw = sw + wt;
-            sl = sl + unfused_mul(wt, prev_length[tp]);
-            for (int ch = 0; ch < 3; ++ch) {
-                sc[ch] = sc[ch] + unfused_mul(wt, prev_linear[tp * 3 + ch]);
-                s2[ch] = s2[ch] + unfused_mul(wt, prev_moment2[tp * 3 + ch]);
-            }
-        }
-    if (!(sw > 0.0)) return out; // reset
-    const double grown = sl / sw + 1.0;
-    const double n = grown < q.max_history ? grown : q.max_history;
-    const double wa = 1.0 / n, wb = 1.0 - wa;
-    for (int ch = 0; ch < 3; ++ch) {
-        out.c[ch] = unfused_mul(wb, sc[ch] / sw) + unfused_mul(wa, linear[o + ch]);
-        out.m2[ch] = unfused_mul(wb, s2[ch] / sw) + unfused_mul(wa, sq[ch]);
-    }
-    out.length = n;
-    return out;
+    const TemporalTaps t = temporal_taps(w, h, x, y, q, normal, depth, alpha, prev_length, prev_normal, prev_depth, prev_alpha);
+    return variance_accumulate_taps(t, q, linear + (size_t(y) * w + x) * 3, prev_linear, prev_moment2);
 }
 
 // What stage B reads, as a window onto the image: element (0, 0) of the view is image pixel (x0, y0), rows are `stride` pixels apart; channel ch
@@ -122,14 +105,8 @@ RT_HD void variance_spatial(const VarianceView& v, const VarianceParams& prm, in
             const int q = variance_at(v, xx, yy);
             if (v.alpha[q] == 0.0) continue;
             const int q3 = q * v.pixel_step;
-            double wn = unfused_mul(n0[0], v.normal[q3]) + unfused_mul(n0[1], v.normal[q3 + v.channel_step]) +
-                        unfused_mul(n0[2], v.normal[q3 + 2 * v.channel_step]);
-            wn = wn > 0.0 ? wn : 0.0;
-            for (uint32_t k = 0; k < prm.normal_squarings; ++k) wn = unfused_mul(wn, wn);
-            const double z = v.depth[q], az = z < 0.0 ? -z : z;
-            const double qz = (z0 - z) / (unfused_mul(unfused_mul(prm.sigma_depth, az0 + az), 0.5) + DENOISE_TINY);
-            const double rz = 1.0 / (1.0 + unfused_mul(qz, qz));
-            const double wt = unfused_mul(wn, unfused_mul(rz, rz));
+            const EdgeStops e = denoise_edge_stops(n0, z0, az0, v.normal + q3, v.channel_step, v.depth[q], prm.normal_squarings, prm.sigma_depth);
+            const double wt = unfused_mul(e.wn, e.wz);
             sw = sw + wt;
             for (int ch = 0; ch < 3; ++ch) {
                 s1[ch] = s1[ch] + unfused_mul(wt, v.m1[q3 + ch * v.channel_step]);
